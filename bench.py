@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """bench.py -- decoder hot-path throughput on MI355X (BASELINE.json metric: samples/sec, 6-cam T=8 900q
-r50 704x256; plus the sampling kernel's HBM roofline fraction and a CPU native-PyTorch baseline).
+r50 704x256; with --full also the sampling kernel's HBM roofline fraction, the other GEMM modes and a CPU native-PyTorch
+baseline).  A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR writes the last
+timed step's outputs.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -87,7 +89,7 @@ def live_kernel_stats(config, gemm, timeout=120):
     try:
         cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', tmp, '-o', 'b', '--',
                sys.executable, os.path.join(ROOT, 'bench.py'), '--config', config, '--gemm', gemm, '--steps', '20', '--warmup', '3',
-               '--no-cpu-baseline', '--no-alt', '--no-detector', '--no-live-pmc'] + CHILD_ARGS
+               '--full', '--no-cpu-baseline', '--no-alt', '--no-detector', '--no-live-pmc'] + CHILD_ARGS
         r = subprocess.run(cmd, cwd='/tmp', env=env, capture_output=True, text=True, timeout=timeout)
         csvs = [os.path.join(d, f) for d, _, fs in os.walk(tmp) for f in fs if f.endswith('kernel_stats.csv')]
         if r.returncode != 0 or not csvs:
@@ -128,7 +130,7 @@ def live_pmc(config, timeout=90):
             out = os.path.join(tmp, counter)
             cmd = ['rocprofv3', '--pmc', counter, '--kernel-trace', '--output-format', 'csv', '-d', out, '-o', 'b', '--',
                    sys.executable, os.path.join(ROOT, 'bench.py'), '--config', config, '--steps', '3', '--warmup', '2',
-                   '--no-cpu-baseline', '--no-alt', '--no-detector', '--no-live-pmc'] + CHILD_ARGS
+                   '--full', '--no-cpu-baseline', '--no-alt', '--no-detector', '--no-live-pmc'] + CHILD_ARGS
             r = subprocess.run(cmd, cwd='/tmp', env=env, capture_output=True, text=True, timeout=timeout)
             csvs = [os.path.join(d, f) for d, _, fs in os.walk(out) for f in fs if f.endswith('counter_collection.csv')]
             if r.returncode != 0 or not csvs:
@@ -333,6 +335,15 @@ def detector_standin(args, T, L, Q, B, ih, iw, sizes, device, transformer):
                     'publishes 15.8 FPS for this pipeline on an RTX 3090 (README.md:28)' % (iw, ih, B)}
 
 
+def dump_outputs(out_dir, arrays):
+    """{name: tensor} -> out_dir/<name>.npy in float32: what a caller of the timed path receives, so that two builds can be compared
+    output for output on the same seeded inputs.  The largest config's outputs are under 1 MB, so nothing is sampled."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -358,7 +369,15 @@ def main():
     ap.add_argument('--gemm', default=DEFAULT_GEMM, choices=sorted(runtime.GEMM_MODES),
                     help='the two big mixing GEMMs: f16x3 = fp32-class scaled fp16 hi + lo split, 3 products (default); f32 = exact f32-input MFMA; '
                          'bf16x6 = hi + mid + lo bf16 images, 6 products; f16x4 = 4 fp16 products; bf16x3s / bf16x3 = 3 bf16 products (2^-16 class)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also everything beside the headline figure: host issue time, per-kernel HIP-event timings and '
+                         'rooflines (with live rocprofv3 re-runs), the other GEMM modes, the eager step, the detector stand-in and the CPU baseline '
+                         '(the --no-* options and --detector select among these)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (rank 0) as DIR/cls_scores.npy and DIR/bbox_preds.npy (float32)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     for flag, val in (('--feat-dtype', args.feat_dtype), ('--query-order', args.query_order)):
         if val is not None:
@@ -420,158 +439,145 @@ def main():
         step()
     # The timed region runs un-instrumented: with the same input tensors every step the module replays ONE captured hipGraph per
     # step (feature relayout + 6 layers; runtime.StepGraphs), and HIP events cannot be read back from a graph.  The kernel
-    # timings for the roofline fields come from extra EAGER steps right after it (same inputs, same cache state).
-    fused_cfg = ops_sample_mix_supported(L, T, P_cfg) and not (L == 5 and fdtype == torch.float32 and os.environ.get('SBEV_NO_FUSE_L5F32'))     # the runtime's own rule (csrc/decoder.hip)
+    # timings for the roofline fields (--full) come from extra EAGER steps right after it (same inputs, same cache state).
     shard.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    checksum = 0.0
     for _ in range(args.steps):
         cls, box = step()
     torch.cuda.synchronize()
     shard.barrier()
     elapsed = time.perf_counter() - t0
     runtime.check_pair_faults()       # a timed step with a lost pair hand-off would be an invalid (and ~1 s slow) step: raise, never report it
-    # host time to enqueue ONE step while the queue has room (the upload ring is 8 deep: issuing more than that many steps ahead
-    # simply waits for the GPU, which is what the round-2 figure measured)
-    t1 = time.perf_counter()
-    for _ in range(6):
-        step()
-    host_issue = (time.perf_counter() - t1) / 6
-    torch.cuda.synchronize()
+    checksum = float(cls.double().abs().sum().item() + box.double().abs().sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'cls_scores': cls, 'bbox_preds': box})
+    if args.full:
+        # host time to enqueue ONE step while the queue has room (the upload ring is 8 deep: issuing more than that many steps ahead
+        # simply waits for the GPU, which is what the round-2 figure measured)
+        t1 = time.perf_counter()
+        for _ in range(6):
+            step()
+        host_issue = (time.perf_counter() - t1) / 6
+        torch.cuda.synchronize()
     rt = model.decoder._runtime
     graph_info = {'replays': rt.step_graphs.replays, 'captures': rt.step_graphs.captures} if rt is not None else None
     launches_per_layer = rt.launches_per_layer(B, Q) if rt is not None else None
-    # HIP events around the gather launches, on their stream, in every 5th of the following eager steps: the two records
-    # around a launch leave ~5.6 us of idle stream each.  The decoder step runs the gather FUSED with the adaptive-mixing
-    # kernel where the fused launch covers the shape (kind 3); otherwise the stand-alone sampler (kind 0) is what it launches.
-    runtime.profile_stride(PROFILE_EVERY)
-    runtime.profile_sampler(8 if fused_cfg else 1)
-    for _ in range(min(30, max(10, args.steps))):
-        step()
-    torch.cuda.synchronize()
-    fused_ms = sorted(runtime.read_kernel_ms(3)) if fused_cfg else []
-    kernel_ms = [] if fused_cfg else sorted(runtime.read_sampler_ms())
-    # a few extra steps outside the timed region: the two mixing GEMMs bracketed, and -- when the timed steps ran the fused
-    # launch -- the same decoder step with the sampler as its own launch (fusion off), so that the stand-alone sampling
-    # kernel of BASELINE.json's metric is timed in the decoder's cache state on the same inputs
-    runtime.profile_stride(1)
-    if fused_cfg:                                # (own phase: event records around the neighbouring GEMM launches would inflate it)
-        runtime.fuse_sample_mix(False)
-        for _ in range(3):                       # the unfused step touches a workspace region the fused one never did: warm it
-            step()
+    if args.full:
+        fused_cfg = ops_sample_mix_supported(L, T, P_cfg) and not (L == 5 and fdtype == torch.float32 and os.environ.get('SBEV_NO_FUSE_L5F32'))     # the runtime's own rule (csrc/decoder.hip)
+        # HIP events around the gather launches, on their stream, in every 5th of the following eager steps: the two records
+        # around a launch leave ~5.6 us of idle stream each.  The decoder step runs the gather FUSED with the adaptive-mixing
+        # kernel where the fused launch covers the shape (kind 3); otherwise the stand-alone sampler (kind 0) is what it launches.
         runtime.profile_stride(PROFILE_EVERY)
-        runtime.profile_sampler(1)
-        for _ in range(min(20, 2 * args.steps)):
+        runtime.profile_sampler(8 if fused_cfg else 1)
+        for _ in range(min(30, max(10, args.steps))):
             step()
         torch.cuda.synchronize()
-        kernel_ms = sorted(runtime.read_sampler_ms())
-        runtime.fuse_sample_mix(True)
+        fused_ms = sorted(runtime.read_kernel_ms(3)) if fused_cfg else []
+        kernel_ms = [] if fused_cfg else sorted(runtime.read_sampler_ms())
+        # a few extra steps outside the timed region: the two mixing GEMMs bracketed, and -- when the timed steps ran the fused
+        # launch -- the same decoder step with the sampler as its own launch (fusion off), so that the stand-alone sampling
+        # kernel of BASELINE.json's metric is timed in the decoder's cache state on the same inputs
         runtime.profile_stride(1)
-    runtime.profile_sampler(6)
-    for _ in range(min(10, args.steps)):
-        step()
-    torch.cuda.synchronize()
-    gemm_ms = [sorted(runtime.read_kernel_ms(k)) for k in (1, 2)]
-    runtime.profile_sampler(False)
-    checksum = float(cls.double().abs().sum().item() + box.double().abs().sum().item())
+        if fused_cfg:                                # (own phase: event records around the neighbouring GEMM launches would inflate it)
+            runtime.fuse_sample_mix(False)
+            for _ in range(3):                       # the unfused step touches a workspace region the fused one never did: warm it
+                step()
+            runtime.profile_stride(PROFILE_EVERY)
+            runtime.profile_sampler(1)
+            for _ in range(min(20, 2 * args.steps)):
+                step()
+            torch.cuda.synchronize()
+            kernel_ms = sorted(runtime.read_sampler_ms())
+            runtime.fuse_sample_mix(True)
+            runtime.profile_stride(1)
+        runtime.profile_sampler(6)
+        for _ in range(min(10, args.steps)):
+            step()
+        torch.cuda.synchronize()
+        gemm_ms = [sorted(runtime.read_kernel_ms(k)) for k in (1, 2)]
+        runtime.profile_sampler(False)
 
-    # secondary measurements (rank 0, N = 1 only): the same steps in the other modes of the two big mixing GEMMs -- first of all the
-    # exact f32-input MFMA kernels -- reported next to, never instead of, `value` (which is the mode of --gemm, by default the library's)
-    alt = None
-    if world == 1 and args.gemm == DEFAULT_GEMM and not args.no_alt:
-        alt = {}
-        for mode in [m for m in ('f32', 'f16x3', 'bf16x6', 'bf16x3s', 'bf16x3') if m != args.gemm]:
-            what = GEMM_WHAT[mode]
-            model.decoder.gemm_mode = mode
+        # secondary measurements (rank 0, N = 1 only): the same steps in the other modes of the two big mixing GEMMs -- first of all the
+        # exact f32-input MFMA kernels -- reported next to, never instead of, `value` (which is the mode of --gemm, by default the library's)
+        alt = None
+        if world == 1 and args.gemm == DEFAULT_GEMM and not args.no_alt:
+            alt = {}
+            for mode in [m for m in ('f32', 'f16x3', 'bf16x6', 'bf16x3s', 'bf16x3') if m != args.gemm]:
+                what = GEMM_WHAT[mode]
+                model.decoder.gemm_mode = mode
+                try:
+                    for _ in range(3):
+                        step()
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    for _ in range(args.steps):
+                        cls3, box3 = step()
+                    torch.cuda.synchronize()
+                    dt3 = time.perf_counter() - t1
+                    runtime.profile_sampler(6)
+                    for _ in range(min(5, args.steps)):
+                        step()
+                    torch.cuda.synchronize()
+                    g_ms = [runtime.read_kernel_ms(k) for k in (1, 2)]
+                    runtime.profile_sampler(False)
+                    alt[mode] = {'gemm': what, 'value': round(args.steps * B / dt3, 3), 'unit': 'samples/s', 'ms_per_step': round(1e3 * dt3 / args.steps, 4),
+                                 'generator_us': round(1e3 * sum(g_ms[0]) / len(g_ms[0]), 2) if g_ms[0] else None,      # (None: this mode's kernel is not bracketed)
+                                 'out_proj_us': round(1e3 * sum(g_ms[1]) / len(g_ms[1]), 2) if g_ms[1] else None,
+                                 'max_abs_dev_vs_default_layer0': round(float(max((cls3[0] - cls[0]).abs().max(), (box3[0] - box[0]).abs().max())), 8)}
+                except Exception as e:      # noqa: BLE001  (a secondary figure must never take the metric line down)
+                    alt[mode] = {'error': repr(e)[:300]}
+                finally:
+                    model.decoder.gemm_mode = args.gemm
+
+        # ... and the same step EAGER (no graph replay) on the exact kernels: the figure that stays comparable with rounds 1-2 and with an
+        # eager reference loop
+        eager_f32 = None
+        if world == 1 and args.gemm == DEFAULT_GEMM and not args.no_alt:
+            sg, model.decoder.static_graph, model.decoder.gemm_mode = model.decoder.static_graph, False, 'f32'
             try:
                 for _ in range(3):
                     step()
                 torch.cuda.synchronize()
                 t1 = time.perf_counter()
                 for _ in range(args.steps):
-                    cls3, box3 = step()
-                torch.cuda.synchronize()
-                dt3 = time.perf_counter() - t1
-                runtime.profile_sampler(6)
-                for _ in range(min(5, args.steps)):
                     step()
                 torch.cuda.synchronize()
-                g_ms = [runtime.read_kernel_ms(k) for k in (1, 2)]
-                runtime.profile_sampler(False)
-                alt[mode] = {'gemm': what, 'value': round(args.steps * B / dt3, 3), 'unit': 'samples/s', 'ms_per_step': round(1e3 * dt3 / args.steps, 4),
-                             'generator_us': round(1e3 * sum(g_ms[0]) / len(g_ms[0]), 2) if g_ms[0] else None,      # (None: this mode's kernel is not bracketed)
-                             'out_proj_us': round(1e3 * sum(g_ms[1]) / len(g_ms[1]), 2) if g_ms[1] else None,
-                             'max_abs_dev_vs_default_layer0': round(float(max((cls3[0] - cls[0]).abs().max(), (box3[0] - box[0]).abs().max())), 8)}
-            except Exception as e:      # noqa: BLE001  (a secondary figure must never take the metric line down)
-                alt[mode] = {'error': repr(e)[:300]}
+                dt = time.perf_counter() - t1
+                eager_f32 = {'value': round(args.steps * B / dt, 3), 'unit': 'samples/s', 'ms_per_step': round(1e3 * dt / args.steps, 4),
+                             'what': 'the same steps enqueued eagerly (no hipGraph replay), exact f32-input MFMA kernels for the two mixing GEMMs'}
+            except Exception as e:      # noqa: BLE001
+                eager_f32 = {'error': repr(e)[:300]}
             finally:
-                model.decoder.gemm_mode = args.gemm
+                model.decoder.static_graph, model.decoder.gemm_mode = sg, args.gemm
 
-    # ... and the same step EAGER (no graph replay) on the exact kernels: the figure that stays comparable with rounds 1-2 and with an
-    # eager reference loop
-    eager_f32 = None
-    if world == 1 and args.gemm == DEFAULT_GEMM and not args.no_alt:
-        sg, model.decoder.static_graph, model.decoder.gemm_mode = model.decoder.static_graph, False, 'f32'
-        try:
-            for _ in range(3):
-                step()
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(args.steps):
-                step()
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t1
-            eager_f32 = {'value': round(args.steps * B / dt, 3), 'unit': 'samples/s', 'ms_per_step': round(1e3 * dt / args.steps, 4),
-                         'what': 'the same steps enqueued eagerly (no hipGraph replay), exact f32-input MFMA kernels for the two mixing GEMMs'}
-        except Exception as e:      # noqa: BLE001
-            eager_f32 = {'error': repr(e)[:300]}
-        finally:
-            model.decoder.static_graph, model.decoder.gemm_mode = sg, args.gemm
-
-    detector = None
-    if world == 1 and (args.detector or (args.config == 'c2' and not args.no_detector and not args.online)):
-        try:
-            detector = detector_standin(args, T, L, Q, B, ih, iw, sizes, device, model)
-        except Exception as e:      # noqa: BLE001  (a labelled secondary figure must never take the metric line down)
-            detector = {'error': repr(e)[:300]}
+        detector = None
+        if world == 1 and (args.detector or (args.config == 'c2' and not args.no_detector and not args.online)):
+            try:
+                detector = detector_standin(args, T, L, Q, B, ih, iw, sizes, device, model)
+            except Exception as e:      # noqa: BLE001  (a labelled secondary figure must never take the metric line down)
+                detector = {'error': repr(e)[:300]}
 
     # the one collective: metric all-reduce (MAX of elapsed, SUM of samples / checksum) over RCCL
     elapsed_max, samples, checksum_sum, elapsed_min = shard.reduce_metrics(elapsed, args.steps * B, checksum, per_rank=True)
 
     if rank == 0:
-        avg_ms = sum(kernel_ms) / max(len(kernel_ms), 1)
-        smp = model.decoder.decoder_layer.sampling
-        G_, P_, Cg_ = smp.num_groups, smp.num_points, 256 // smp.num_groups
-        npts = B * T * G_ * Q * P_                                 # B' * Q * P sampled points per launch
-        sf = 4 if fdtype == torch.float32 else 2
-        bytes_per_pt = L * 4 * Cg_ * sf + 12 + 4 * L + Cg_ * 4     # SURVEY.md section 8d byte model
-        alg_bytes = npts * bytes_per_pt
-        alg_gbps = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        # physical HBM-side rate: PMC bytes per launch (fabric-side L2 requests = HBM + Infinity-Cache traffic) of the last
-        # committed profile of THIS config over the live HIP-event time -- a fraction of the 8 TB/s peak by construction.
-        # The section-8d algorithmic rate prices every tap as a miss and therefore exceeds the pin rate whenever taps hit in
-        # L2: it is reported beside it with the implied hit fraction, never as `frac`.
-        # (the committed profiles are of the config's own storage type: with --feat-dtype only counters measured now apply)
         own_dtype = args.feat_dtype is None or {'fp32': torch.float32, 'fp16': torch.float16, 'bf16': torch.bfloat16}[args.feat_dtype] == cfg_fields(cfg)[4]
-        pmc, pmc_file = pmc_profile(args.config) if own_dtype else (None, None)
-        live = live_pmc(args.config) if (world == 1 and not args.no_live_pmc) else None
-        live_src = 'measured in this run: bench.py re-ran 5 steps of this config under rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes; x2 gfx950 correction), bytes per launch'
-        if live and 'msmv_fwd_kernel' in live:
-            pmc = dict(pmc or {}, **live['msmv_fwd_kernel'])          # keeps the committed profile's L2 hit ratio beside the live bytes
-            pmc_file = None
-        traffic = pmc['hbm_bytes_per_launch'] if pmc else None
-        hbm_gbps = traffic / (avg_ms * 1e-3) / 1e9 if (traffic and avg_ms > 0) else None
         out = {
             'metric': 'decoder samples/sec (6-cam T=%d %dq %s, 6 layers, features resident in HBM)' % (T, Q, pyr),
             'value': round(samples / elapsed_max, 3), 'unit': 'samples/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': round(1e3 * elapsed_max / args.steps, 4),
-            'host_issue_ms_per_step': round(1e3 * host_issue, 4),
-            # the two comparison figures up front (short fields: they survive a truncated record): the graph-replayed step on the exact
-            # f32-input MFMA kernels, and that step enqueued eagerly
-            'exact_f32': ({'value': alt['f32']['value'], 'ms_per_step': alt['f32']['ms_per_step']} if (alt and 'value' in alt.get('f32', {})) else None),
-            'eager_f32': ({'value': eager_f32['value'], 'ms_per_step': eager_f32['ms_per_step']} if (eager_f32 and 'value' in eager_f32) else None),
+        }
+        if args.full:
+            out.update({
+                'host_issue_ms_per_step': round(1e3 * host_issue, 4),
+                # the two comparison figures up front (short fields: they survive a truncated record): the graph-replayed step on the exact
+                # f32-input MFMA kernels, and that step enqueued eagerly
+                'exact_f32': ({'value': alt['f32']['value'], 'ms_per_step': alt['f32']['ms_per_step']} if (alt and 'value' in alt.get('f32', {})) else None),
+                'eager_f32': ({'value': eager_f32['value'], 'ms_per_step': eager_f32['ms_per_step']} if (eager_f32 and 'value' in eager_f32) else None),
+            })
+        out.update({
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': ('f32' if fdtype == torch.float32 else ('bf16' if fdtype == torch.bfloat16 else 'fp16') + '-storage/f32-math') + ('' if args.gemm == 'f32' else ' (the two mixing GEMMs: %s = %s)' % (args.gemm, GEMM_WHAT[args.gemm])),
             'data': 'synthetic',
@@ -585,113 +591,135 @@ def main():
                        'checksum': checksum_sum},
             # per-rank spread (weak scaling: every rank runs the same per-GPU batch): slowest / fastest rank's own rate
             'per_rank_samples_per_s': {'min': round(args.steps * B / elapsed_max, 3), 'max': round(args.steps * B / elapsed_min, 3)},
-            'roofline': {'kernel': 'msmv_fwd_kernel (adaptive sampling gather)', 'bound': 'hbm',
-                         'achieved': round(hbm_gbps, 1) if hbm_gbps else None, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-                         'frac': round(hbm_gbps / HBM_PEAK_GBPS, 4) if hbm_gbps else None,
-                         'frac_of_measured_copy_peak': round(hbm_gbps / HBM_COPY_GBPS, 4) if hbm_gbps else None,
-                         'traffic': traffic,
-                         'traffic_source': (live_src if pmc_file is None else 'profiles/%s: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE, bytes per launch, same config'
-                                            % pmc_file) if pmc else 'no PMC profile for this config',
-                         'achieved_is': 'PMC bytes per launch / live HIP-event time per launch (physical, <= peak); achieved_algorithmic is the '
-                                        'SURVEY 8d byte model (every tap priced as a miss) over the same time',
-                         'achieved_algorithmic': round(alg_gbps, 1),
-                         'algorithmic_over_peak': round(alg_gbps / HBM_PEAK_GBPS, 4),
-                         'algorithmic_bytes_per_launch': alg_bytes,
-                         'cache_served_fraction': round(1.0 - traffic / alg_bytes, 4) if traffic else None,
-                         'l2_hit_ratio_pmc': pmc.get('l2_hit_ratio') if pmc else None,
-                         'launches': len(kernel_ms), 'avg_us': round(avg_ms * 1e3, 2),
-                         'event_sampling': ('HIP events around the stand-alone sampler launches of every %dth of %d extra decoder steps run with the fusion off right after '
-                                            'the timed region (inside it the gather runs fused with the mixing kernel: roofline_fused)' % (PROFILE_EVERY, min(20, 2 * args.steps)))
-                                           if fused_ms else 'HIP events around the sampler launches of every %dth of the eager steps run right after the timed region (which replays a captured graph)' % PROFILE_EVERY},
-        }
-        # the tracer's view of the same kernels (no event records, no launch gaps): this command re-run now under rocprofv3 --kernel-trace --stats
-        kt = live_kernel_stats(args.config, args.gemm) if (world == 1 and not args.no_live_pmc) else None
-        if kt and 'msmv_fwd_kernel' in kt:
-            out['roofline']['avg_us_rocprof'] = kt['msmv_fwd_kernel']
-            if traffic:
-                out['roofline']['frac_rocprof'] = round(traffic / (kt['msmv_fwd_kernel'] * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4)
-        if fused_ms:
-            # the launch the timed steps really run: gather + adaptive mixing in one kernel.  Algorithmic bytes = the sampler's
-            # gather reads (no [B,Q,G,T*P,C] write any more) + the item's dynamic parameters + its mixed output
-            f_avg = sum(fused_ms) / len(fused_ms)
-            items = B * Q * G_
-            f_alg = npts * (L * 4 * Cg_ * sf + 12 + 4 * L) + items * ((Cg_ * Cg_ + 128 * T * P_) * 4 + 128 * Cg_ * 4)
-            fp, fp_file = pmc_profile(args.config, 'adaptive_mixing_kernel') if own_dtype else (None, None)
-            if live and 'adaptive_mixing_kernel' in live:
-                fp, fp_file = live['adaptive_mixing_kernel'], None
-            f_traffic = fp['hbm_bytes_per_launch'] if fp else None
-            out['roofline_fused'] = {'kernel': 'adaptive_mixing_kernel<RT, true, L, FT> (gather + adaptive mixing, one launch)', 'bound': 'hbm',
-                                     'achieved': round(f_traffic / (f_avg * 1e-3) / 1e9, 1) if f_traffic else None, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
-                                     'frac': round(f_traffic / (f_avg * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if f_traffic else None,
-                                     'traffic': f_traffic, 'traffic_source': (live_src if fp_file is None else 'profiles/%s' % fp_file) if fp else 'no PMC profile for this config',
-                                     'achieved_algorithmic': round(f_alg / (f_avg * 1e-3) / 1e9, 1), 'algorithmic_bytes_per_launch': f_alg,
-                                     'launches': len(fused_ms), 'avg_us': round(f_avg * 1e3, 2),
-                                     'event_sampling': 'HIP events around the fused launches of every %dth of the eager steps run right after the timed region (which replays a captured graph)' % PROFILE_EVERY}
-            if kt and 'adaptive_mixing_kernel' in kt:
-                out['roofline_fused']['avg_us_rocprof'] = kt['adaptive_mixing_kernel']
-            # the kernel the timed steps spend the most time in (the stand-alone sampler above is BASELINE.json's metric kernel; inside
-            # the step its gather runs fused): first-class, same numbers as roofline_fused
-            rf = out['roofline_fused']
-            out['roofline']['dominant_kernel'] = {'kernel': 'adaptive_mixing_kernel (gather + adaptive mixing, one launch)', 'bound': 'hbm',
-                                                  'avg_us': rf['avg_us'], 'achieved': rf['achieved'], 'frac': rf['frac'], 'traffic': rf['traffic'],
-                                                  'share_of_step': round(6 * rf['avg_us'] * 1e-3 / (1e3 * elapsed_max / args.steps), 3)}
-        # the kernels that dominate the step by TIME are the two mixing GEMMs (MFMA-bound, exact fp32): same live HIP-event
-        # measurement, priced against the f32-input MFMA peak; PMC MFMA-pipe utilisation from profiles/ when present
-        if args.gemm != 'f32' and all(gemm_ms):
-            # the split-operand kernels: arithmetic done = nprod image products on the 16-bit matrix core; `fp32_equiv` prices the GEMM itself
-            D_, Pin_, Pout_ = 256, T * P_, 128
-            npr = GEMM_PRODUCTS[args.gemm]
-            fl_g = 2.0 * B * Q * D_ * (G_ * (Cg_ * Cg_ + Pin_ * Pout_))
-            fl_o = 2.0 * B * Q * D_ * (G_ * Pout_ * Cg_)
-            g_us, o_us = (sum(ms) / len(ms) * 1e3 for ms in gemm_ms)
-            out['roofline_mfma'] = [
-                {'kernel': name, 'bound': 'mfma', 'achieved': round(npr * fl / (us * 1e-6) / 1e12, 1), 'peak': MFMA_16BIT_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                 'frac': round(npr * fl / (us * 1e-6) / 1e12 / MFMA_16BIT_PEAK_TFLOPS, 4), 'image_products': npr,
-                 'fp32_equiv_tflops': round(fl / (us * 1e-6) / 1e12, 1), 'launches': len(ms), 'avg_us': round(us, 2), 'algorithmic_flop_per_launch': fl}
-                for name, fl, us, ms in (('%s (mixing parameter generator, %s)' % ('gemm_f16s_gen_ws_kernel' if GEMM_PRODUCTS[args.gemm] in (3, 4) and args.gemm != 'bf16x3' else 'gemm_bf16s_gen3_kernel', args.gemm), fl_g, g_us, gemm_ms[0]),
-                                         ('gemm_bf16s_out%s_kernel (mixing out-projection, split-K, %s)' % (('8' if B * Q >= OUT8_MIN_ROWS else '4') if args.gemm.startswith('f16') else '3', args.gemm), fl_o, o_us, gemm_ms[1]))]
-            # the fp32-class emulation may be the default once generator + out-projection <= 2 x 60 us at config 2
-            out['gemm_gate'] = {'generator_us': round(g_us, 2), 'out_proj_us': round(o_us, 2), 'sum_us': round(g_us + o_us, 2),
-                                'measured': 'HIP events around the two launches of 10 eager steps right after the timed region (an upper bound: the records '
-                                            'include the launch gap)', 'config': args.config}
-            gk = (kt or {}).get('gemm_f16s_gen_ws_kernel', (kt or {}).get('gemm_bf16s_gen3_kernel'))
-            if gk:
-                ok = kt.get('gemm_bf16s_out8_kernel', kt.get('gemm_bf16s_out4_kernel', kt.get('gemm_bf16s_out3_kernel')))
-                out['gemm_gate'].update({'generator_us_rocprof': gk, 'out_proj_us_rocprof': ok,
-                                         'sum_us_rocprof': round(gk + ok, 2) if ok else None,
-                                         'rocprof': 'rocprofv3 --kernel-trace --stats of 23 steps of this command re-run now on this box: AverageNs of the two kernels'})
-        if args.gemm == 'f32' and all(gemm_ms):
-            D_, Pin_, Pout_ = 256, T * P_, 128
-            flops = 2.0 * B * Q * D_ * (G_ * (Cg_ * Cg_ + Pin_ * Pout_))          # generator; the out-projection has G*Pout*Cg*D = the same at Pin = 32
-            flops2 = 2.0 * B * Q * D_ * (G_ * Pout_ * Cg_)
-            util = mfma_util()
-            out['roofline_mfma'] = [
-                {'kernel': name, 'bound': 'mfma', 'achieved': round(fl / (sum(ms) / len(ms) * 1e-3) / 1e12, 1), 'peak': MFMA_F32_PEAK_TFLOPS,
-                 'unit': 'TFLOP/s', 'frac': round(fl / (sum(ms) / len(ms) * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
-                 'launches': len(ms), 'avg_us': round(sum(ms) / len(ms) * 1e3, 2), 'algorithmic_flop_per_launch': fl,
-                 'mfma_pipe_util_pmc': util.get(key)}
-                for name, key, fl, ms in (('gemm_nt_f32_strip_kernel (mixing parameter generator)', 'gemm_nt_f32_strip_kernel<false>', flops, gemm_ms[0]),
-                                          ('gemm_nt_f32_regtile_kernel (mixing out-projection, split-K)', 'gemm_nt_f32_regtile_kernel', flops2, gemm_ms[1]))]
-        if alt is not None:
-            out['alt_gemm'] = alt
-        if eager_f32 is not None:
-            out['eager_f32_detail'] = eager_f32
-        if detector is not None:
-            out['detector_standin'] = detector
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(cfg, model.state_dict())
-            out['gpu_over_cpu'] = round(out['value'] / out['cpu_baseline']['value'], 1)
-            if args.config == 'c2':
-                # the CPU baseline at c1 too (BASELINE.json configs[0], the reference's own CPU-runnable case), with
-                # the HIP path at the same shape beside it
-                try:
-                    c1_gpu, c1_model = gpu_quick('c1', device)
-                    c1 = cpu_baseline(CONFIGS['c1'], c1_model.state_dict(), max_seconds=10.0, thread_sweep=(4, 8, 16, 32))
-                    c1['gpu_value'] = c1_gpu
-                    c1['gpu_over_cpu'] = round(c1_gpu / c1['value'], 1)
-                    out['cpu_baseline']['c1'] = c1
-                except Exception as e:      # noqa: BLE001
-                    out['cpu_baseline']['c1'] = {'error': repr(e)[:300]}
+        })
+        if args.full:
+            avg_ms = sum(kernel_ms) / max(len(kernel_ms), 1)
+            smp = model.decoder.decoder_layer.sampling
+            G_, P_, Cg_ = smp.num_groups, smp.num_points, 256 // smp.num_groups
+            npts = B * T * G_ * Q * P_                                 # B' * Q * P sampled points per launch
+            sf = 4 if fdtype == torch.float32 else 2
+            bytes_per_pt = L * 4 * Cg_ * sf + 12 + 4 * L + Cg_ * 4     # SURVEY.md section 8d byte model
+            alg_bytes = npts * bytes_per_pt
+            alg_gbps = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            # physical HBM-side rate: PMC bytes per launch (fabric-side L2 requests = HBM + Infinity-Cache traffic) of the last
+            # committed profile of THIS config over the live HIP-event time -- a fraction of the 8 TB/s peak by construction.
+            # The section-8d algorithmic rate prices every tap as a miss and therefore exceeds the pin rate whenever taps hit in
+            # L2: it is reported beside it with the implied hit fraction, never as `frac`.
+            # (the committed profiles are of the config's own storage type: with --feat-dtype only counters measured now apply)
+            pmc, pmc_file = pmc_profile(args.config) if own_dtype else (None, None)
+            live = live_pmc(args.config) if (world == 1 and not args.no_live_pmc) else None
+            live_src = 'measured in this run: bench.py re-ran 5 steps of this config under rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes; x2 gfx950 correction), bytes per launch'
+            if live and 'msmv_fwd_kernel' in live:
+                pmc = dict(pmc or {}, **live['msmv_fwd_kernel'])          # keeps the committed profile's L2 hit ratio beside the live bytes
+                pmc_file = None
+            traffic = pmc['hbm_bytes_per_launch'] if pmc else None
+            hbm_gbps = traffic / (avg_ms * 1e-3) / 1e9 if (traffic and avg_ms > 0) else None
+            out['roofline'] = {'kernel': 'msmv_fwd_kernel (adaptive sampling gather)', 'bound': 'hbm',
+                               'achieved': round(hbm_gbps, 1) if hbm_gbps else None, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+                               'frac': round(hbm_gbps / HBM_PEAK_GBPS, 4) if hbm_gbps else None,
+                               'frac_of_measured_copy_peak': round(hbm_gbps / HBM_COPY_GBPS, 4) if hbm_gbps else None,
+                               'traffic': traffic,
+                               'traffic_source': (live_src if pmc_file is None else 'profiles/%s: rocprofv3 --pmc FETCH_SIZE (x2, gfx950) + WRITE_SIZE, bytes per launch, same config'
+                                                  % pmc_file) if pmc else 'no PMC profile for this config',
+                               'achieved_is': 'PMC bytes per launch / live HIP-event time per launch (physical, <= peak); achieved_algorithmic is the '
+                                              'SURVEY 8d byte model (every tap priced as a miss) over the same time',
+                               'achieved_algorithmic': round(alg_gbps, 1),
+                               'algorithmic_over_peak': round(alg_gbps / HBM_PEAK_GBPS, 4),
+                               'algorithmic_bytes_per_launch': alg_bytes,
+                               'cache_served_fraction': round(1.0 - traffic / alg_bytes, 4) if traffic else None,
+                               'l2_hit_ratio_pmc': pmc.get('l2_hit_ratio') if pmc else None,
+                               'launches': len(kernel_ms), 'avg_us': round(avg_ms * 1e3, 2),
+                               'event_sampling': ('HIP events around the stand-alone sampler launches of every %dth of %d extra decoder steps run with the fusion off right after '
+                                                  'the timed region (inside it the gather runs fused with the mixing kernel: roofline_fused)' % (PROFILE_EVERY, min(20, 2 * args.steps)))
+                                                 if fused_ms else 'HIP events around the sampler launches of every %dth of the eager steps run right after the timed region (which replays a captured graph)' % PROFILE_EVERY}
+            # the tracer's view of the same kernels (no event records, no launch gaps): this command re-run now under rocprofv3 --kernel-trace --stats
+            kt = live_kernel_stats(args.config, args.gemm) if (world == 1 and not args.no_live_pmc) else None
+            if kt and 'msmv_fwd_kernel' in kt:
+                out['roofline']['avg_us_rocprof'] = kt['msmv_fwd_kernel']
+                if traffic:
+                    out['roofline']['frac_rocprof'] = round(traffic / (kt['msmv_fwd_kernel'] * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4)
+            if fused_ms:
+                # the launch the timed steps really run: gather + adaptive mixing in one kernel.  Algorithmic bytes = the sampler's
+                # gather reads (no [B,Q,G,T*P,C] write any more) + the item's dynamic parameters + its mixed output
+                f_avg = sum(fused_ms) / len(fused_ms)
+                items = B * Q * G_
+                f_alg = npts * (L * 4 * Cg_ * sf + 12 + 4 * L) + items * ((Cg_ * Cg_ + 128 * T * P_) * 4 + 128 * Cg_ * 4)
+                fp, fp_file = pmc_profile(args.config, 'adaptive_mixing_kernel') if own_dtype else (None, None)
+                if live and 'adaptive_mixing_kernel' in live:
+                    fp, fp_file = live['adaptive_mixing_kernel'], None
+                f_traffic = fp['hbm_bytes_per_launch'] if fp else None
+                out['roofline_fused'] = {'kernel': 'adaptive_mixing_kernel<RT, true, L, FT> (gather + adaptive mixing, one launch)', 'bound': 'hbm',
+                                         'achieved': round(f_traffic / (f_avg * 1e-3) / 1e9, 1) if f_traffic else None, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
+                                         'frac': round(f_traffic / (f_avg * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if f_traffic else None,
+                                         'traffic': f_traffic, 'traffic_source': (live_src if fp_file is None else 'profiles/%s' % fp_file) if fp else 'no PMC profile for this config',
+                                         'achieved_algorithmic': round(f_alg / (f_avg * 1e-3) / 1e9, 1), 'algorithmic_bytes_per_launch': f_alg,
+                                         'launches': len(fused_ms), 'avg_us': round(f_avg * 1e3, 2),
+                                         'event_sampling': 'HIP events around the fused launches of every %dth of the eager steps run right after the timed region (which replays a captured graph)' % PROFILE_EVERY}
+                if kt and 'adaptive_mixing_kernel' in kt:
+                    out['roofline_fused']['avg_us_rocprof'] = kt['adaptive_mixing_kernel']
+                # the kernel the timed steps spend the most time in (the stand-alone sampler above is BASELINE.json's metric kernel; inside
+                # the step its gather runs fused): first-class, same numbers as roofline_fused
+                rf = out['roofline_fused']
+                out['roofline']['dominant_kernel'] = {'kernel': 'adaptive_mixing_kernel (gather + adaptive mixing, one launch)', 'bound': 'hbm',
+                                                      'avg_us': rf['avg_us'], 'achieved': rf['achieved'], 'frac': rf['frac'], 'traffic': rf['traffic'],
+                                                      'share_of_step': round(6 * rf['avg_us'] * 1e-3 / (1e3 * elapsed_max / args.steps), 3)}
+            # the kernels that dominate the step by TIME are the two mixing GEMMs (MFMA-bound, exact fp32): same live HIP-event
+            # measurement, priced against the f32-input MFMA peak; PMC MFMA-pipe utilisation from profiles/ when present
+            if args.gemm != 'f32' and all(gemm_ms):
+                # the split-operand kernels: arithmetic done = nprod image products on the 16-bit matrix core; `fp32_equiv` prices the GEMM itself
+                D_, Pin_, Pout_ = 256, T * P_, 128
+                npr = GEMM_PRODUCTS[args.gemm]
+                fl_g = 2.0 * B * Q * D_ * (G_ * (Cg_ * Cg_ + Pin_ * Pout_))
+                fl_o = 2.0 * B * Q * D_ * (G_ * Pout_ * Cg_)
+                g_us, o_us = (sum(ms) / len(ms) * 1e3 for ms in gemm_ms)
+                out['roofline_mfma'] = [
+                    {'kernel': name, 'bound': 'mfma', 'achieved': round(npr * fl / (us * 1e-6) / 1e12, 1), 'peak': MFMA_16BIT_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                     'frac': round(npr * fl / (us * 1e-6) / 1e12 / MFMA_16BIT_PEAK_TFLOPS, 4), 'image_products': npr,
+                     'fp32_equiv_tflops': round(fl / (us * 1e-6) / 1e12, 1), 'launches': len(ms), 'avg_us': round(us, 2), 'algorithmic_flop_per_launch': fl}
+                    for name, fl, us, ms in (('%s (mixing parameter generator, %s)' % ('gemm_f16s_gen_ws_kernel' if GEMM_PRODUCTS[args.gemm] in (3, 4) and args.gemm != 'bf16x3' else 'gemm_bf16s_gen3_kernel', args.gemm), fl_g, g_us, gemm_ms[0]),
+                                             ('gemm_bf16s_out%s_kernel (mixing out-projection, split-K, %s)' % (('8' if B * Q >= OUT8_MIN_ROWS else '4') if args.gemm.startswith('f16') else '3', args.gemm), fl_o, o_us, gemm_ms[1]))]
+                # the fp32-class emulation may be the default once generator + out-projection <= 2 x 60 us at config 2
+                out['gemm_gate'] = {'generator_us': round(g_us, 2), 'out_proj_us': round(o_us, 2), 'sum_us': round(g_us + o_us, 2),
+                                    'measured': 'HIP events around the two launches of 10 eager steps right after the timed region (an upper bound: the records '
+                                                'include the launch gap)', 'config': args.config}
+                gk = (kt or {}).get('gemm_f16s_gen_ws_kernel', (kt or {}).get('gemm_bf16s_gen3_kernel'))
+                if gk:
+                    ok = kt.get('gemm_bf16s_out8_kernel', kt.get('gemm_bf16s_out4_kernel', kt.get('gemm_bf16s_out3_kernel')))
+                    out['gemm_gate'].update({'generator_us_rocprof': gk, 'out_proj_us_rocprof': ok,
+                                             'sum_us_rocprof': round(gk + ok, 2) if ok else None,
+                                             'rocprof': 'rocprofv3 --kernel-trace --stats of 23 steps of this command re-run now on this box: AverageNs of the two kernels'})
+            if args.gemm == 'f32' and all(gemm_ms):
+                D_, Pin_, Pout_ = 256, T * P_, 128
+                flops = 2.0 * B * Q * D_ * (G_ * (Cg_ * Cg_ + Pin_ * Pout_))          # generator; the out-projection has G*Pout*Cg*D = the same at Pin = 32
+                flops2 = 2.0 * B * Q * D_ * (G_ * Pout_ * Cg_)
+                util = mfma_util()
+                out['roofline_mfma'] = [
+                    {'kernel': name, 'bound': 'mfma', 'achieved': round(fl / (sum(ms) / len(ms) * 1e-3) / 1e12, 1), 'peak': MFMA_F32_PEAK_TFLOPS,
+                     'unit': 'TFLOP/s', 'frac': round(fl / (sum(ms) / len(ms) * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
+                     'launches': len(ms), 'avg_us': round(sum(ms) / len(ms) * 1e3, 2), 'algorithmic_flop_per_launch': fl,
+                     'mfma_pipe_util_pmc': util.get(key)}
+                    for name, key, fl, ms in (('gemm_nt_f32_strip_kernel (mixing parameter generator)', 'gemm_nt_f32_strip_kernel<false>', flops, gemm_ms[0]),
+                                              ('gemm_nt_f32_regtile_kernel (mixing out-projection, split-K)', 'gemm_nt_f32_regtile_kernel', flops2, gemm_ms[1]))]
+            if alt is not None:
+                out['alt_gemm'] = alt
+            if eager_f32 is not None:
+                out['eager_f32_detail'] = eager_f32
+            if detector is not None:
+                out['detector_standin'] = detector
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(cfg, model.state_dict())
+                out['gpu_over_cpu'] = round(out['value'] / out['cpu_baseline']['value'], 1)
+                if args.config == 'c2':
+                    # the CPU baseline at c1 too (BASELINE.json configs[0], the reference's own CPU-runnable case), with
+                    # the HIP path at the same shape beside it
+                    try:
+                        c1_gpu, c1_model = gpu_quick('c1', device)
+                        c1 = cpu_baseline(CONFIGS['c1'], c1_model.state_dict(), max_seconds=10.0, thread_sweep=(4, 8, 16, 32))
+                        c1['gpu_value'] = c1_gpu
+                        c1['gpu_over_cpu'] = round(c1_gpu / c1['value'], 1)
+                        out['cpu_baseline']['c1'] = c1
+                    except Exception as e:      # noqa: BLE001
+                        out['cpu_baseline']['c1'] = {'error': repr(e)[:300]}
         print(json.dumps(out))
     shard.shutdown()
 

@@ -29,7 +29,7 @@ def _last_json(stdout):
 
 
 def test_single_process_line_has_the_contract_fields():
-    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '2', '--no-cpu-baseline', '--no-alt'], cwd=ROOT,
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '2', '--full', '--no-cpu-baseline', '--no-alt'], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -43,6 +43,26 @@ def test_single_process_line_has_the_contract_fields():
     if shutil.which('rocprofv3'):
         assert d['roofline']['traffic_source'].startswith('measured in this run'), d['roofline']['traffic_source']
         assert 1.5e8 < d['roofline']['traffic'] < 3.5e8 and d['roofline']['frac'] <= 1.0
+
+
+def test_plain_line_times_only_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full the line carries the headline fields and none of the secondary figures; --dump-outputs writes the outputs of
+    the last timed step, the same tensors the line's checksum is taken over."""
+    import numpy as np
+    r = subprocess.run([sys.executable, 'bench.py', '--steps', '3', '--warmup', '2', '--dump-outputs', str(tmp_path)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'config'):
+        assert k in d, k
+    assert d['steps'] == 3 and d['warmup'] == 2 and d['value'] > 0
+    assert abs(d['value'] - 1e3 / d['ms_per_step']) < 0.01 * d['value']
+    assert not {'roofline', 'host_issue_ms_per_step', 'alt_gemm', 'detector_standin', 'cpu_baseline'} & set(d), sorted(d)
+    outs = [np.load(tmp_path / (name + '.npy')) for name in ('cls_scores', 'bbox_preds')]
+    for a in outs:
+        assert a.dtype == np.float32 and a.shape == (6, 1, 900, 10) and np.isfinite(a).all()
+    s = sum(float(np.abs(a.astype(np.float64)).sum()) for a in outs)
+    assert abs(s - d['config']['checksum']) <= 1e-9 * s
 
 
 def test_two_ranks_as_the_driver_launches_them():

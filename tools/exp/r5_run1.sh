@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 O=$R/gpurun_out/r5_1
 mkdir -p $O
-Q="--no-cpu-baseline --no-alt --no-detector --no-live-pmc"
+Q="--full --no-cpu-baseline --no-alt --no-detector --no-live-pmc"
 export PYTHONUNBUFFERED=1
 
 echo "== 1 pytest -m gpu"

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r6_c6
 mkdir -p $O
-Q="--no-cpu-baseline --no-alt --no-detector --no-live-pmc"
+Q="--full --no-cpu-baseline --no-alt --no-detector --no-live-pmc"
 cd /tmp && export TMPDIR=/tmp
 CMD="python $R/bench.py --config c6 $Q --steps 3 --warmup 2"
 i=0

@@ -5,7 +5,7 @@ TAG=${1:-c2}; shift
 OUT=$R/gpurun_out/r6_kt_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-alt --no-detector --no-live-pmc"
+Q="--full --no-cpu-baseline --no-alt --no-detector --no-live-pmc"
 for mode in lazy dense; do
   if [ $mode = dense ]; then export SBEV_NO_SPARSE_RELAYOUT=1; else unset SBEV_NO_SPARSE_RELAYOUT; fi
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$mode -o b -- python $R/bench.py $Q --steps 20 "$@" > $OUT/$mode.log 2>&1

@@ -5,7 +5,7 @@ TAG=${1:-c2}; shift
 OUT=$R/gpurun_out/r6_seq_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-alt --no-detector --no-live-pmc"
+Q="--full --no-cpu-baseline --no-alt --no-detector --no-live-pmc"
 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -o b -- python $R/bench.py $Q --steps 12 --warmup 4 "$@" > $OUT/run.log 2>&1
 f=$(find $OUT/t -name "*kernel_trace.csv" | head -1)
 python - "$f" > $OUT/seq.txt <<'PY'

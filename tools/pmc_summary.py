@@ -71,7 +71,7 @@ def main():
             res[s].update({'TCC_HIT_sum': round(h), 'TCC_MISS_sum': round(m), 'l2_hit_ratio': round(h / (h + m), 4)})
     json.dump({'config': config,
                'note': 'rocprofv3 --pmc FETCH_SIZE, --pmc WRITE_SIZE and --pmc TCC_HIT_sum TCC_MISS_sum in separate passes of `python bench.py --config %s '
-                       '--steps 4 --warmup 2 --no-cpu-baseline --no-alt --no-detector` (tools/profile_pmc.sh); KiB units; FETCH_SIZE x2 (gfx950 wide-read '
+                       '--full --steps 4 --warmup 2 --no-cpu-baseline --no-alt --no-detector` (tools/profile_pmc.sh); KiB units; FETCH_SIZE x2 (gfx950 wide-read '
                        'under-count, validated on transpose_tiles_kernel whose true read bytes are known); FETCH/WRITE are fabric-side L2 requests, i.e. '
                        'HBM + Infinity-Cache traffic' % config, 'kernels': res}, open(out, 'w'), indent=1)
     for name in sorted(set(dropped)):

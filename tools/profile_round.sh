@@ -9,9 +9,9 @@ ROUND=${1:-r6}
 OUT=$R/gpurun_out/prof_$ROUND
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $OUT/bench_line.json 2> $OUT/bench.err
+python $R/bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err
 tail -1 $OUT/bench_line.json | cut -c1-400
-Q="--no-cpu-baseline --no-alt --no-detector --no-live-pmc"
+Q="--full --no-cpu-baseline --no-alt --no-detector --no-live-pmc"
 # kernel stats of the same workload: the default mode of the two mixing GEMMs (f16x3), the exact f32-MFMA kernels, bf16x6
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o bench -- python $R/bench.py $Q --steps 20 > $OUT/kt.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_f32 -o bench -- python $R/bench.py $Q --steps 20 --gemm f32 > $OUT/kt_f32.log 2>&1
@@ -40,7 +40,7 @@ python $R/bench.py --nhwc $Q --steps 50 2>/dev/null | tail -1 > $OUT/bench_nhwc.
 python $R/bench.py --online $Q --steps 50 2>/dev/null | tail -1 > $OUT/bench_online.json; cut -c1-200 $OUT/bench_online.json
 SBEV_NO_SAMPLE_MIX=1 python $R/bench.py $Q --steps 50 2>/dev/null | tail -1 > $OUT/bench_unfused.json; cut -c1-200 $OUT/bench_unfused.json
 # fp16 feature storage (the reference's eval mode before its out_fp32 cast): NCHW lists through the 2-byte relayout; c2 with live PMC
-python $R/bench.py --feat-dtype fp16 --no-cpu-baseline --no-alt --no-detector --steps 50 2>/dev/null | tail -1 > $OUT/bench_fp16.json; cut -c1-200 $OUT/bench_fp16.json
+python $R/bench.py --feat-dtype fp16 --full --no-cpu-baseline --no-alt --no-detector --steps 50 2>/dev/null | tail -1 > $OUT/bench_fp16.json; cut -c1-200 $OUT/bench_fp16.json
 python $R/bench.py --feat-dtype fp16 --nhwc $Q --steps 50 2>/dev/null | tail -1 > $OUT/bench_fp16_nhwc.json; cut -c1-200 $OUT/bench_fp16_nhwc.json
 for c in c3 c4; do python $R/bench.py --config $c --feat-dtype fp16 $Q --steps 30 2>/dev/null | tail -1 > $OUT/bench_${c}_fp16.json; cut -c1-200 $OUT/bench_${c}_fp16.json; done
 for i in 1 2 3; do python $R/tools/bench_train.py --graph 2>&1 | tail -1 >> $OUT/train.log; done; tail -3 $OUT/train.log
