@@ -298,9 +298,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f16s_kernel(const TnArgs a) {
 }  // namespace
 
 extern "C" int sbev_gemm_tn_f16s_ok(int64_t M, int64_t N, int64_t K) {
-    // enough tiles to fill the chip without a split of K (else: sbev_gemm_f32 and its split-K plan)
+    // enough tiles to fill the chip without a split of K (else: sbev_gemm_f32 and its split-K plan); and contiguous operands
+    // (lda = M, ldb = N) within the 32-bit buffer offsets sbev_gemm_tn_f16s requires (K * lda, K * ldb < 2^29): a caller that
+    // asks this predicate must not be sent into a refusal -- the mixing backward's grad_W_pg has K * M = B*Q * 4 (64^2 + 128 Pin),
+    // over 2^29 from B*Q = 6899 at Pin 120
     return M >= 4 && N >= 4 && M % 4 == 0 && N % 4 == 0 && K >= TK && K < (1LL << 26) && ((M + TM - 1) / TM) * ((N + TN - 1) / TN) >= 256 &&
-           ((M + TM - 1) / TM) * ((N + TN - 1) / TN) <= 0x7fffffffLL;
+           ((M + TM - 1) / TM) * ((N + TN - 1) / TN) <= 0x7fffffffLL && K * M < (1LL << 29) && K * N < (1LL << 29);
 }
 
 extern "C" int sbev_gemm_tn_f16s(const float* A, int64_t lda, const float* a_scale, const float* B, int64_t ldb, const float* b_scale,

@@ -192,6 +192,12 @@ def test_round3_training_entry_points_validate_without_gpu(lib):
     # grad_W on the fp16 kernel: shape coverage (>= 256 tiles of 128 x 128, K >= 32, multiples of 4), 32-bit buffer offsets
     assert lib.sbev_gemm_tn_f16s_ok(256, 32768, 900) == 1 and lib.sbev_gemm_tn_f16s_ok(32768, 256, 900) == 1
     assert lib.sbev_gemm_tn_f16s_ok(256, 256, 900) == 0 and lib.sbev_gemm_tn_f16s_ok(256, 32768, 16) == 0 and lib.sbev_gemm_tn_f16s_ok(258, 32768, 900) == 0
+    # contiguous operands past the 32-bit buffer offsets (K * M or K * N >= 2^29) are refused here, so that callers fall back to the
+    # exact kernels instead of meeting the launch's refusal: grad_W_pg at Pin 120 (NP = 77824) from B*Q = 6899, grad_W_op (N = 32768) from 16384
+    assert lib.sbev_gemm_tn_f16s_ok(77824, 256, 6898) == 1 and lib.sbev_gemm_tn_f16s_ok(77824, 256, 6899) == 0
+    assert lib.sbev_gemm_tn_f16s_ok(77824, 256, 7200) == 0 and lib.sbev_gemm_tn_f16s_ok(256, 77824, 7200) == 0
+    assert lib.sbev_gemm_tn_f16s_ok(256, 32768, 16383) == 1 and lib.sbev_gemm_tn_f16s_ok(256, 32768, 16384) == 0
+    assert lib.sbev_gemm_tn_f16s_ok(32768, 256, 16384) == 0 and lib.sbev_gemm_tn_f16s_ok(256, 32768, 7200) == 1
     assert lib.sbev_gemm_tn_f16s(one, 256, one, one, 32768, one, one, 32768, 256, 256, 900, 0, None) == -1               # too few tiles
     assert lib.sbev_gemm_tn_f16s(one, 256, None, one, 32768, one, one, 32768, 256, 32768, 900, 0, None) == -1            # null scale
     assert lib.sbev_gemm_tn_f16s(one, 128, one, one, 32768, one, one, 32768, 256, 32768, 900, 0, None) == -1             # lda < M

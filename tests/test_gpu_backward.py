@@ -291,12 +291,14 @@ def test_adaptive_mixing_fp16_gemms_full_size_without_a_tap_match_the_exact_path
 
 
 @torch.enable_grad()
-@pytest.mark.parametrize('T,L,pyr', [(2, 4, 'tiny'), (4, 5, 'tiny5')])
-def test_sampling_function_vs_oracle_autograd(T, L, pyr):
+@pytest.mark.parametrize('T,L,pyr,P', [pytest.param(2, 4, 'tiny', 4, id='2-4-tiny'), pytest.param(4, 5, 'tiny5', 4, id='4-5-tiny5'),
+                                       pytest.param(15, 5, 'tiny5', 4, id='15-5-tiny5-P4'), pytest.param(15, 5, 'tiny5', 8, id='15-5-tiny5-P8')])
+def test_sampling_function_vs_oracle_autograd(T, L, pyr, P):
     """sample points -> projection / view select -> gather, differentiated: grads wrt the box (centre, dims, yaw), the packed
-    offsets | level logits and the feature maps vs the oracle's torch ops under autograd (fp32 on the CPU)."""
+    offsets | level logits and the feature maps vs the oracle's torch ops under autograd (fp32 on the CPU).  T = 15 with P = 4 and
+    P = 8 are the two trainval configs: G * P = 32 points on the front kernel's wave, T * P = 120 rows of the OUT_MIX gradient."""
     from oracle import sparsebev_oracle as O
-    B, Q, G, P = 2, 36, 4, 4
+    B, Q, G = 2, 36, 4
     ih, iw, sizes = S.PYRAMIDS[pyr]
     g = torch.Generator().manual_seed(T * 10 + L)
     bbox, _ = S.make_queries(B, Q, seed=7)
@@ -323,6 +325,8 @@ def test_sampling_function_vs_oracle_autograd(T, L, pyr):
     fr = O.regroup_features(fc, channel_last=False)
     ref, _ = O.sampling_4d(pts, fr, sw, l2i, ih, iw, O.msmv_sampling_gridsample)
     ref.backward(gy)
+    print('sampling T=%d P=%d L=%d: out %.2e  grad_bbox %.2e  grad_offsets|logits %.2e  grad_feats %s' % (
+        T, P, L, rel(out, ref), rel(bd.grad, bc.grad), rel(sd.grad, sc.grad), ' '.join('%.2e' % rel(d.grad, c.grad) for d, c in zip(dev_feats, fc))))
     assert rel(out, ref) < 1e-4
     assert rel(bd.grad, bc.grad) < 2e-4 and bd.grad[..., 8:].abs().max() == 0
     assert rel(sd.grad, sc.grad) < 2e-4
@@ -352,9 +356,9 @@ def test_refine_bbox_function_vs_torch():
     assert ((bd.grad[..., :3].cpu().double() - bc.grad[..., :3]).abs()[inner]).max() < 1e-4 * bc.grad.abs().max()
 
 
-def build(T, L, seed, num_layers):
-    params = S.make_params(seed, embed_dims=256, num_frames=T, num_points=4, num_levels=L)
-    m = SparseBEVTransformer(256, num_frames=T, num_points=4, num_layers=num_layers, num_levels=L, num_classes=10,
+def build(T, L, seed, num_layers, num_points=4):
+    params = S.make_params(seed, embed_dims=256, num_frames=T, num_points=num_points, num_levels=L)
+    m = SparseBEVTransformer(256, num_frames=T, num_points=num_points, num_layers=num_layers, num_levels=L, num_classes=10,
                              code_size=10, pc_range=S.PC_RANGE)
     m.load_state_dict({PREFIX + k: v for k, v in params.items()}, strict=True)
     return m.to(DEV)
