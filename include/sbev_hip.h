@@ -792,6 +792,18 @@ int sbev_debug_chain_pair_drop(int enable);
  * + mixing, + 1 for the activation split of the split-bf16 GEMM modes. */
 int sbev_decoder_launches_per_layer(const sbev_decoder_config* cfg, const sbev_decoder_weights* weights);
 
+/* The process-wide switches a decoder step is planned from, as the library holds them now -- whichever way each was set (its setter,
+ * its environment variable at load, the library itself after a pair fault).  sbev_decoder_forward / _lazy / _capture read exactly this
+ * set, once per call; a step captured under one reading must only be replayed under an equal one, so a caller that caches captured
+ * steps puts ALL returned values into its key.  Fills out[0 .. min(n, capacity)) and returns n, the number of values (11 today; later
+ * versions only append).  Needs no device.  Order:
+ *    0 sbev_decoder_row_chain            1 sbev_decoder_chain_pair          2 sbev_decoder_fuse_sample_mix
+ *    3 fused gather + mixing for 5 fp32 levels (no setter: SBEV_NO_FUSE_L5F32 in the environment clears it)
+ *    4 sbev_decoder_query_order (0 / 1 / 2)   5 sbev_decoder_lazy_scan_launch    6 sbev_decoder_out_fold
+ *    7 sbev_linear_gen_weight_stationary      8 sbev_linear_out8_min_rows (rows)  9 sbev_msmv_buffer_taps
+ *   10 sbev_get_box_convention */
+int sbev_decoder_switches(int32_t* out, int capacity);
+
 /* fp16 GEMM modes: log2 of the power of two the out-projection's input (relu(LayerNorm) over out_points * embed_dims / G elements:
  * |x| <= sqrt(n - 1)) is multiplied by before its fp16 split inside sbev_decoder_forward: 9 for n = 8192. */
 int sbev_decoder_mixed_up_log2(const sbev_decoder_config* cfg);

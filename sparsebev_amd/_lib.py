@@ -65,6 +65,7 @@ SIGNATURES = {
                                                 ctypes.c_int64, ctypes.c_int, _vp]),
     'sbev_decoder_workspace_bytes': (ctypes.c_int64, [_vp]),
     'sbev_decoder_launches_per_layer': (ctypes.c_int, [_vp, _vp]),
+    'sbev_decoder_switches': (ctypes.c_int, [_c_i32p, ctypes.c_int]),
     'sbev_decoder_forward': (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, ctypes.c_int64, _vp]),
     'sbev_decoder_forward_lazy': (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -9,6 +9,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include "sbev_common.hpp"
 
 #include <mutex>
@@ -167,9 +168,9 @@ struct ProfCallScope {      // see sbev_profile_stride below
 
 // the fused gather + mixing kernel covers this config: shape (sbev_sample_mix_supported), the 5-level fp32 switch, and every level's
 // per-(sample, frame) NHWC slab below 2 GiB (the fused kernel's taps are 31-bit buffer offsets: sbev_sample_mix_slabs_ok)
-static bool sample_mix_fusable(const sbev_decoder_config& c) {
+static bool sample_mix_fusable(const sbev_decoder_config& c, bool fuse_l5_f32) {
     if (sbev_sample_mix_supported(c.L, c.D / c.G, c.P, c.T, c.G, c.G) == 0) return false;
-    if (c.L == 5 && c.feat_dtype == SBEV_F32 && g_fuse_l5_f32.load(std::memory_order_relaxed) == 0) return false;
+    if (c.L == 5 && c.feat_dtype == SBEV_F32 && !fuse_l5_f32) return false;
     int32_t hw[2 * SBEV_MAX_LEVELS];
     int64_t sv[SBEV_MAX_LEVELS];
     for (int l = 0; l < c.L; ++l) {
@@ -180,24 +181,105 @@ static bool sample_mix_fusable(const sbev_decoder_config& c) {
     return sbev_sample_mix_slabs_ok(hw, c.L, c.feat_dtype, c.N, c.D / c.G, sv, c.D) != 0;
 }
 
-// Kernel launches sbev_decoder_forward enqueues per layer for this config / weight set under the current switches (what
-// bench.py reports; the decision code is the forward's own)
-extern "C" int sbev_decoder_launches_per_layer(const sbev_decoder_config* cfg, const sbev_decoder_weights* w) {
-    if (validate(cfg) != SBEV_OK || !w) return -1;
-    const sbev_decoder_config& c = *cfg;
-    const int64_t BQ = (int64_t)c.B * c.Q;
-    const bool fork = c.overlap != 0;
-    const bool chain = g_row_chain.load(std::memory_order_relaxed) != 0 && w->chain_pack != nullptr && !fork && sbev::row_chain_supported(c) &&
-                       sbev::row_chain_pays(BQ);
-    const bool fused = g_fuse_sample_mix.load(std::memory_order_relaxed) != 0 &&
-                       sample_mix_fusable(c);
-    const int split = (c.gemm_mode == SBEV_GEMM_BF16X6 || c.gemm_mode == SBEV_GEMM_BF16X3S) ? 1      // x1 -> bf16 image fragments
-                      : (c.gemm_mode == SBEV_GEMM_F16X3 || c.gemm_mode == SBEV_GEMM_F16X4) ? (chain ? 0 : 1)      // x1 -> fp16 image fragments (the attention chain writes them)
-                      : (c.gemm_mode == SBEV_GEMM_BF16X3 && sbev_linear_bf16x3_strip_ok(BQ, c.G * ((c.D / c.G) * (c.D / c.G) + c.T * c.P * c.out_points), c.D)) ? 1 : 0;
+// The one reader of the process-wide switches: a step is planned from ONE reading, so a switch toggled while a step is being enqueued
+// takes effect at the next step, never between two layers.  The same struct answers sbev_decoder_switches (the callers' graph key).
+static sbev::Switches read_switches() {
+    sbev::Switches s;
+    s.row_chain = g_row_chain.load(std::memory_order_relaxed);
+    s.chain_pair = sbev::chain_pair_enabled() ? 1 : 0;
+    s.fuse_sample_mix = g_fuse_sample_mix.load(std::memory_order_relaxed);
+    s.fuse_l5_f32 = g_fuse_l5_f32.load(std::memory_order_relaxed);
+    s.query_order = g_query_order.load(std::memory_order_relaxed);
+    s.lazy_scan_launch = g_lazy_scan_launch.load(std::memory_order_relaxed);
+    s.out_fold = sbev::out_fold_enabled() ? 1 : 0;
+    s.gen_weight_stationary = sbev::gen_weight_stationary_enabled() ? 1 : 0;
+    s.out8_min_rows = sbev::out8_min_rows_setting();
+    s.msmv_buffer_taps = sbev::msmv_buffer_taps_enabled() ? 1 : 0;      // (read again by each sampler launch: both variants are bit-identical)
+    s.box_convention = sbev::box_convention();                        // (read by the box kernels' launchers)
+    return s;
+}
+
+extern "C" int sbev_decoder_switches(int32_t* out, int capacity) {
+    constexpr int n = (int)(sizeof(sbev::Switches) / sizeof(int32_t));
+    static_assert(sizeof(sbev::Switches) == n * sizeof(int32_t), "sbev::Switches: int32_t fields only");
+    const sbev::Switches s = read_switches();
+    if (out && capacity > 0) std::memcpy(out, &s, sizeof(int32_t) * (capacity < n ? capacity : n));
+    return n;
+}
+
+// What one decoder step enqueues for a (config, weight set, reading of the switches): every path decision of sbev_decoder_forward is
+// taken HERE, decoder_forward_impl follows the plan and sbev_decoder_launches_per_layer reports it.  Touches no device.
+struct StepPlan {
+    int nimg;                // split-bf16 / fp16 kernels (gemm_bf16s.hip): their mode code 2 = bf16x3s, 3 = bf16x6, 4 = f16x3, 5 = f16x4; else 0
+    int64_t BQ;
+    int pgN, mixN, soN;
+    int splits;              // split-K plan of the exact / 3 x bf16 out-projection
+    bool fork, fork_pg;      // classification branch on the aux stream; + parameter-generator GEMM beside the sampling chain
+    bool chain;              // row chains (row_chain.hip): 6 launches per layer instead of 17
+    bool fused;              // gather + mixing in one launch
+    int order_mode;          // sbev_query_order in effect: 0 none, 1 sorted every layer, 2 once per step (from the input boxes)
+    bool pg_strip;           // 3 x bf16 mode: x1 split once per layer and streamed past W-stationary strips
+    bool pack_launch;        // a launch of its own turns x1 into the generator's operand (image fragments / bf16 triples)
+    bool gen_ws;             // the split-image generator is the weight-stationary kernel
+    bool scan_in_gen;        // on-demand relayout: the scans of layers 1.. ride in that kernel's prologue
+    bool fold_wanted;        // the out-projection may fold its slabs inside its launch (the launcher decides: shape, device, fault word)
+    bool grouped;            // op-by-op tail: independent small ops share launches
+    int out8_min_rows;
+    int launches_per_layer;
+};
+
+static StepPlan plan_step(const sbev_decoder_config& c, const sbev_decoder_weights& w, bool lazy, bool aux_ok, const sbev::Switches& sw) {
+    StepPlan p{};
+    p.nimg = c.gemm_mode == SBEV_GEMM_BF16X6 ? 3 : c.gemm_mode == SBEV_GEMM_BF16X3S ? 2 : c.gemm_mode == SBEV_GEMM_F16X3 ? 4
+             : c.gemm_mode == SBEV_GEMM_F16X4 ? 5 : 0;
+    const int D = c.D, Cg = c.D / c.G, Pin = c.T * c.P;
+    p.BQ = (int64_t)c.B * c.Q;
+    p.pgN = c.G * (Cg * Cg + Pin * c.out_points);
+    p.mixN = c.G * c.out_points * Cg;
+    p.soN = c.G * c.P * (3 + c.L);
+    p.splits = out_proj_splits(p.BQ, D, p.mixN);
+    p.fork = c.overlap != 0 && aux_ok;
+    p.fork_pg = c.overlap == 1 && aux_ok;
+    // everything between the out-projection GEMM and the self attention, and between the self attention and the sampler, is row-local
+    // and runs with the rows in LDS -- when the caller supplied packed weights (sbev_decoder_weights.chain_pack)
+    p.chain = sw.row_chain != 0 && w.chain_pack != nullptr && !p.fork && sbev::row_chain_supported(c) && sbev::row_chain_pays(p.BQ);
+    // ONE launch when the fused kernel covers the shape (the sampled features then never touch HBM), else the sampler followed by the
+    // mixing kernel (same arithmetic, bit-identical results)
+    // (round 2 kept two launches for 5 fp32 levels: 168 registers + spills, 272 vs 277 samples/s at config 4; the lean chunk code
+    // of round 3 fits without spills -- g_fuse_l5_f32; 4 fp32 levels +1.6 % at config 2, 5 bf16 levels +4.3 % at config 5)
+    p.fused = sw.fuse_sample_mix != 0 && sample_mix_fusable(c, sw.fuse_l5_f32 != 0);
+    // launch order of a layer's gather items: sorted from the layer's input boxes (one workgroup per sample); mode 2: from the step's
+    // INPUT boxes only -- the refinements move a box by a fraction of its camera column
+    p.order_mode = p.chain && p.fused && c.Q <= sbev_query_order_max() ? sw.query_order : 0;
+    p.pg_strip = c.gemm_mode == SBEV_GEMM_BF16X3 && sbev_linear_bf16x3_strip_ok(p.BQ, p.pgN, D) != 0;
+    // (fp16 GEMM modes: the attention chain also leaves x1 as the generator's fragment operand -- no pack launch)
+    p.pack_launch = p.nimg ? !(p.nimg >= 4 && p.chain) : p.pg_strip;
+    p.gen_ws = p.nimg != 0 && sw.gen_weight_stationary != 0 && sbev::gen_ws_shape_ok(p.BQ, D, p.pgN, p.nimg);
+    // on-demand relayout, layers 1..5: the scan (find + move what this layer's points marked) rides in the generator GEMM's prologue
+    // where that kernel is the weight-stationary one (fp16 modes) -- the only launch between the marks and the gather that does not touch
+    // the features; sbev_decoder_lazy_scan_launch(1) / SBEV_LAZY_SCAN_LAUNCH=1 keeps it a launch of its own (A/B; bit-identical)
+    // (up to 1024 rows: measured at config 2 555 vs 541 samples/s; at 3200 / 3600 rows a layer adds tens of thousands of units and the
+    // launch of its own, with one workgroup per 16 tiles, spreads them better: 1303-1321 vs 1312-1349 and 521 vs 523 -- neutral, kept apart)
+    p.scan_in_gen = lazy && p.chain && p.nimg >= 4 && sw.lazy_scan_launch == 0 && p.BQ <= 1024 && p.gen_ws;
+    // fp16 modes: the S slabs are folded inside the out-projection launch where all its workgroups are resident at once (<= ~1000
+    // rows on 256 CUs) and the fault word is there to report a row tile that never completed; the tail then reads ONE row block
+    p.fold_wanted = p.chain && p.nimg >= 4 && sw.chain_pair != 0 && sw.out_fold != 0;
+    // only while sbev_linear_f32 would pick the same small-tile kernel for each of them (keeps the results identical
+    // to the op-by-op path); large batches have enough tiles per linear anyway
+    p.grouped = !p.fork && (D == 256 || D == 512) && ((p.BQ + 127) / 128) * ((D + 127) / 128) < 256;
+    p.out8_min_rows = sw.out8_min_rows;
     // chains: attention, attention chain, generator, gather + mixing, out-projection, tail (+ next front)
     // op by op: 17 with the fused gather + mixing (DESIGN_HISTORY.md section 4)
-    const bool ordered = chain && fused && g_query_order.load(std::memory_order_relaxed) == 1 && c.Q <= sbev_query_order_max();      // (mode 2: one sort per STEP)
-    return (chain ? 6 : 17) + (fused ? 0 : 1) + split + (ordered ? 1 : 0);
+    // (+ the sort of every layer in order mode 1; mode 2 sorts once per STEP)
+    p.launches_per_layer = (p.chain ? 6 : 17) + (p.fused ? 0 : 1) + (p.pack_launch ? 1 : 0) + (p.order_mode == 1 ? 1 : 0);
+    return p;
+}
+
+// Kernel launches sbev_decoder_forward enqueues per layer for this config / weight set under the current switches (what
+// bench.py reports): the forward's own plan, with the aux stream taken as available -- this call creates no stream and touches no device
+extern "C" int sbev_decoder_launches_per_layer(const sbev_decoder_config* cfg, const sbev_decoder_weights* w) {
+    if (validate(cfg) != SBEV_OK || !w) return -1;
+    return plan_step(*cfg, *w, false, true, read_switches()).launches_per_layer;
 }
 
 // fp16 modes: the out-projection's input -- relu(LayerNorm without affine over n = out_points * C / G elements), so |x| <= sqrt(n - 1)
@@ -234,23 +316,20 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
         return SBEV_EFAULT;
     }
     const sbev::ProfCallScope prof_scope;     // with sbev_profile_stride(n): only every n-th call's launches are bracketed
+    Aux& ax = aux();
+    const StepPlan p = plan_step(c, *w, lazy != nullptr, ax.ok, read_switches());
+    const int nimg = p.nimg, pgN = p.pgN, mixN = p.mixN, soN = p.soN, splits = p.splits;
+    const int64_t BQ = p.BQ;
+    const bool fork = p.fork, fork_pg = p.fork_pg, chain = p.chain, fused = p.fused;
     SBEV_REQUIRE((((uintptr_t)workspace) & 255) == 0, "sbev_decoder_forward: workspace must be 256-byte aligned");
     SBEV_REQUIRE(cfg->gemm_mode != SBEV_GEMM_BF16X3 || (w->pg_w2 && w->op_w2), "sbev_decoder_forward: gemm_mode bf16x3 needs pg_w2 / op_w2");
-    // split-bf16 / fp16 kernels (gemm_bf16s.hip): their mode code 2 = bf16x3s, 3 = bf16x6, 4 = f16x3, 5 = f16x4
-    const int nimg = cfg->gemm_mode == SBEV_GEMM_BF16X6 ? 3 : cfg->gemm_mode == SBEV_GEMM_BF16X3S ? 2 : cfg->gemm_mode == SBEV_GEMM_F16X3 ? 4
-                     : cfg->gemm_mode == SBEV_GEMM_F16X4 ? 5 : 0;
     SBEV_REQUIRE(nimg == 0 || (w->pg_ws && w->op_wp), "sbev_decoder_forward: gemm_mode %d needs pg_ws / op_wp", cfg->gemm_mode);
     SBEV_REQUIRE(nimg < 4 || (w->pg_wdown && w->op_nscale && w->pg_xscale), "sbev_decoder_forward: gemm_mode %d needs pg_wdown / op_nscale / pg_xscale", cfg->gemm_mode);
     const int mixed_up = sbev_decoder_mixed_up_log2(cfg);
     const Buffers b = carve(c, workspace);
     SBEV_REQUIRE((int64_t)b.bytes <= workspace_bytes, "sbev_decoder_forward: workspace too small (%lld < %zu)", (long long)workspace_bytes, b.bytes);
 
-    const int64_t BQ = (int64_t)c.B * c.Q;
     const int D = c.D, Cg = c.D / c.G, Pin = c.T * c.P;
-    const int pgN = c.G * (Cg * Cg + Pin * c.out_points);
-    const int mixN = c.G * c.out_points * Cg;
-    const int soN = c.G * c.P * (3 + c.L);
-    const int splits = out_proj_splits(BQ, D, mixN);
     const float eps = 1e-5f;
 
     // on-demand relayout (sbev_decoder_forward_lazy): feats_nhwc are DESTINATIONS; every layer's point selection marks the units its
@@ -281,18 +360,14 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
     }
 
     hipStream_t s_main = reinterpret_cast<hipStream_t>(stream);
-    Aux& ax = aux();
-    const bool fork = c.overlap != 0 && ax.ok;        // classification branch on the aux stream
-    const bool fork_pg = c.overlap == 1 && ax.ok;     // + parameter-generator GEMM beside the sampling chain
     sbev_stream_t s_aux = fork ? reinterpret_cast<sbev_stream_t>(ax.stream) : stream;
     int evi = 0;
     auto next_ev = [&]() { return ax.ev[(evi++) & 7]; };
     hipEvent_t ev_cls = nullptr;
 
     // parameter generator in the 3 x bf16 mode: x1 is split once per layer and streamed past W-stationary strips
-    const bool pg_strip = c.gemm_mode == SBEV_GEMM_BF16X3 && sbev_linear_bf16x3_strip_ok(BQ, pgN, D) != 0;
     auto generator_bf16x3 = [&](sbev_stream_t st) -> int {
-        if (!pg_strip) return sbev_linear_bf16x3(b.x1, w->pg_w2, w->pg_b, nullptr, b.params, BQ, pgN, D, D, pgN, 0, st);
+        if (!p.pg_strip) return sbev_linear_bf16x3(b.x1, w->pg_w2, w->pg_b, nullptr, b.params, BQ, pgN, D, D, pgN, 0, st);
         uint16_t* x2 = reinterpret_cast<uint16_t*>(b.x1s);
         int e = sbev_split_bf16x3_weights(b.x1, x2, BQ, D, st);
         if (e != SBEV_OK) return e;
@@ -302,36 +377,25 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
     SBEV_REQUIRE(nimg == 0 || (sbev_linear_bf16s_gen_ok(BQ, pgN, D) && sbev_linear_bf16s_out_ok(BQ, D, mixN)),
                  "sbev_decoder_forward: gemm_mode %d does not cover this shape (rows %lld, generator %d x %d, out-projection %d x %d)",
                  cfg->gemm_mode, (long long)BQ, pgN, D, D, mixN);
-    // on-demand relayout, layers 1..5: the scan (find + move what this layer's points marked) rides in the generator GEMM's prologue
-    // where that kernel is the weight-stationary one (fp16 modes) -- the only launch between the marks and the gather that does not touch
-    // the features; sbev_decoder_lazy_scan_launch(1) / SBEV_LAZY_SCAN_LAUNCH=1 keeps it a launch of its own (A/B; bit-identical)
-    const bool scan_own_launch = g_lazy_scan_launch.load(std::memory_order_relaxed) != 0;
-    // (up to 1024 rows: measured at config 2 555 vs 541 samples/s; at 3200 / 3600 rows a layer adds tens of thousands of units and the
-    // launch of its own, with one workgroup per 16 tiles, spreads them better: 1303-1321 vs 1312-1349 and 521 vs 523 -- neutral, kept apart)
-    const bool scan_in_gen = lazy && nimg >= 4 && !scan_own_launch && BQ <= 1024 && sbev::linear_f16s_gen_takes_scan(BQ, pgN, D, pgN, nimg - 1);
-    auto generator_bf16s = [&](sbev_stream_t st, bool packed = false, int scan_layer = -1) -> int {      // x1 -> image fragments (once per layer) -> Y = X W^T + b
+    // x1 -> image fragments (a launch of its own unless the attention chain wrote them) -> Y = X W^T + b; scan_layer > 0: that layer's
+    // on-demand relayout scan inside the generator
+    auto generator_bf16s = [&](sbev_stream_t st, int scan_layer = -1) -> int {
         uint16_t* xs = reinterpret_cast<uint16_t*>(b.x1s);
-        if (nimg >= 4 && scan_layer > 0) {                    // (fragments there already -- chain or pack launch --, this layer's scan inside)
-            const sbev::LazyScan lz{&lplan, lazy->table, lazy->index, lazy->src, const_cast<void* const*>(feats_nhwc), c.feat_dtype == SBEV_F32 ? 4 : 2,
-                                    b.touch_need, b.touch_done, scan_layer + 1 == c.num_layers};
-            if (!packed) {
-                int e = sbev_pack_f16s_frags(b.x1, D, xs, const_cast<float*>(w->pg_xscale), (int)BQ, D, 2, st);
-                if (e != SBEV_OK) return e;
-            }
-            return sbev::linear_f16s_gen_scan(xs, w->pg_xscale, w->pg_ws, w->pg_wdown, w->pg_b, b.params, BQ, pgN, D, pgN, 0, nimg - 1, lz,
-                                              reinterpret_cast<hipStream_t>(st));
-        }
-        if (nimg >= 4 && packed)                               // (the attention chain already wrote the fragments)
-            return sbev_linear_f16s_gen(xs, w->pg_xscale, w->pg_ws, w->pg_wdown, w->pg_b, b.params, BQ, pgN, D, pgN, 0, nimg - 1, st);
-        if (nimg >= 4) {                                       // fp16 hi + lo: x1 scaled by one power of two (its maximum -> [2^14, 2^15))
+        if (p.pack_launch) {
+            // fp16 hi + lo: x1 scaled by one power of two (its maximum -> [2^14, 2^15))
             // (the power of two comes with the weights: norm1's output is bounded by sqrt(D - 1) max|gamma| + max|beta| -- no pass for a maximum)
-            int e = sbev_pack_f16s_frags(b.x1, D, xs, const_cast<float*>(w->pg_xscale), (int)BQ, D, 2, st);
+            int e = nimg >= 4 ? sbev_pack_f16s_frags(b.x1, D, xs, const_cast<float*>(w->pg_xscale), (int)BQ, D, 2, st)
+                              : sbev_pack_bf16s_frags(b.x1, D, xs, (int)BQ, D, nimg, st);
             if (e != SBEV_OK) return e;
-            return sbev_linear_f16s_gen(xs, w->pg_xscale, w->pg_ws, w->pg_wdown, w->pg_b, b.params, BQ, pgN, D, pgN, 0, nimg - 1, st);
         }
-        int e = sbev_pack_bf16s_frags(b.x1, D, xs, (int)BQ, D, nimg, st);
-        if (e != SBEV_OK) return e;
-        return sbev_linear_bf16s_gen(xs, w->pg_ws, w->pg_b, b.params, BQ, pgN, D, pgN, 0, nimg, st);
+        auto gen = [&](const sbev::LazyScan* lz) {
+            return sbev::linear_gen_split(xs, w->pg_xscale, w->pg_ws, w->pg_wdown, w->pg_b, b.params, BQ, pgN, D, pgN, 0, nimg, p.gen_ws, lz,
+                                          reinterpret_cast<hipStream_t>(st));
+        };
+        if (scan_layer <= 0) return gen(nullptr);
+        const sbev::LazyScan lz{&lplan, lazy->table, lazy->index, lazy->src, const_cast<void* const*>(feats_nhwc), c.feat_dtype == SBEV_F32 ? 4 : 2,
+                                b.touch_need, b.touch_done, scan_layer + 1 == c.num_layers};
+        return gen(&lz);
     };
 
     // the mixing launches: in the fp16 GEMM modes their epilogue leaves `mixed` as (fp16 hi, fp16 lo) pairs of mixed 2^mixed_up -- the
@@ -349,41 +413,31 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
         return sbev_adaptive_mixing_f32(b.sampled, b.params, b.mixed, BQ, c.G, Pin, Cg, c.out_points, eps, st);
     };
 
-    // read ONCE per call (a toggle 0 -> 2 between two layers' loads walked an unsorted b.order)
-    const int query_order_mode = g_query_order.load(std::memory_order_relaxed);
     const float* bbox = query_bbox;
     const float* feat = query_feat;
     bool pe0_done = false;             // the previous layer's tail already ran this layer's first position-encoder stage
-    // Row chains (row_chain.hip): 6 launches per layer instead of 17 -- everything between the out-projection GEMM and the self
-    // attention, and between the self attention and the sampler, is row-local and runs with the rows in LDS.
-    const bool chain = g_row_chain.load(std::memory_order_relaxed) != 0 && w->chain_pack != nullptr && !fork && sbev::row_chain_supported(c) &&
-                       sbev::row_chain_pays(BQ);
+    // Row chains (row_chain.hip): 6 launches per layer instead of 17
     if (chain) TRY(sbev::launch_chain_front(c, *w, query_bbox, query_feat, b.x, b.qkvt, eps, s_main));
     for (int layer = 0; layer < c.num_layers; ++layer) {
         float* cls_l = cls_out + (int64_t)layer * BQ * c.num_classes;
         float* box_l = bbox_out + (int64_t)layer * BQ * c.code_size;
         if (chain) {
-            const bool fused = g_fuse_sample_mix.load(std::memory_order_relaxed) != 0 &&
-                               sample_mix_fusable(c);
-            // launch order of this layer's gather items: sorted from the layer's input boxes (one workgroup per sample)
-            const bool ordered = fused && query_order_mode != 0 && c.Q <= sbev_query_order_max();
-            // (mode 2: sorted from the step's INPUT boxes only -- the refinements move a box by a fraction of its camera column)
-            if (ordered && (layer == 0 || query_order_mode == 1)) TRY(sbev_query_order(bbox, c.code_size, c.pc_range, c.B, c.Q, b.order, stream));
+            if (p.order_mode != 0 && (layer == 0 || p.order_mode == 1)) TRY(sbev_query_order(bbox, c.code_size, c.pc_range, c.B, c.Q, b.order, stream));
             TRY(sbev_sasa_f32(b.qkvt, c.attn_in_rows, bbox, c.pc_range, attn_mask, b.att, c.B, c.Q, c.H, D / c.H, stream));
             // (fp16 GEMM modes: the chain also leaves x1 as the generator's fragment operand -- no pack launch)
             TRY(sbev::launch_chain_attn(c, *w, b.att, b.x, b.x1, bbox, time_diff, lidar2img, b.loc, b.wbp, eps, s_main,
                                         nimg >= 4 ? reinterpret_cast<uint16_t*>(b.x1s) : nullptr, nimg >= 4 ? w->pg_xscale : nullptr, b.pair_sync,
                                         lazy ? &lplan : nullptr, lazy ? b.touch_need : nullptr));
-            const bool ride = scan_in_gen && layer > 0;
+            const bool ride = p.scan_in_gen && layer > 0;
             if (!ride) TRY(lazy_move(layer));      // (layer 0's move behind the generator instead of in front of it: measured equal, 537-539 both ways)
             if (nimg)
-                TRY(generator_bf16s(stream, true, ride ? layer : -1));
+                TRY(generator_bf16s(stream, ride ? layer : -1));
             else if (c.gemm_mode == SBEV_GEMM_BF16X3)
                 TRY(generator_bf16x3(stream));
             else
                 TRY(sbev_linear_f32(b.x1, w->pg_w, w->pg_b, nullptr, b.params, BQ, pgN, D, D, D, pgN, 0, stream));
             if (fused) {
-                TRY(mix_fused(stream, ordered ? b.order : nullptr));
+                TRY(mix_fused(stream, p.order_mode != 0 ? b.order : nullptr));
             } else {
                 if (c.n_slots > 0)
                     TRY(sbev_msmv_fwd_ring(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
@@ -394,17 +448,18 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
                 TRY(mix_plain(stream));
             }
             int used = 0;
-            // fp16 modes: the S slabs are folded inside the out-projection launch where all its workgroups are resident at once (<= ~1000
-            // rows on 256 CUs) and the fault word is there to report a row tile that never completed; the tail then reads ONE row block
-            const bool fold = nimg >= 4 && sbev::chain_pair_enabled() && sbev::out_fold_ok(BQ, mixN) && sbev::chain_fault_word_ready();
+            bool folded = false;      // the out-projection folded its slabs inside its launch: the tail reads ONE row block, b.folded
+            // (the fold needs the fault word to report a row tile that never completed)
+            const bool fold = p.fold_wanted && sbev::out_fold_shape_ok(BQ, mixN) && sbev::chain_fault_word_ready();
             if (nimg)
-                TRY(sbev::launch_splitk_slabs_bf16s(b.mixed, w->op_wp, BQ, mixN, mixN, nimg, b.slabs, &used, s_main, mixed_up, w->op_nscale, nimg >= 4, nullptr,
-                                                    fold ? b.pair_sync + sbev::chain_fold_sync_offset(BQ) : nullptr, fold ? b.folded : nullptr));
+                TRY(sbev::launch_splitk_slabs_bf16s(b.mixed, w->op_wp, BQ, mixN, mixN, nimg, b.slabs, &used, s_main, p.out8_min_rows, mixed_up, w->op_nscale,
+                                                    nimg >= 4, nullptr, fold ? b.pair_sync + sbev::chain_fold_sync_offset(BQ) : nullptr,
+                                                    fold ? b.folded : nullptr, &folded));
             else if (c.gemm_mode == SBEV_GEMM_BF16X3)
                 TRY(sbev::launch_splitk_slabs_bf16x3(b.mixed, w->op_w2, BQ, D, mixN, mixN, splits, b.slabs, &used, s_main));
             else
                 TRY(sbev::launch_splitk_slabs(b.mixed, w->op_w, BQ, D, mixN, mixN, mixN, splits, b.slabs, &used, s_main));
-            TRY(sbev::launch_chain_tail(c, *w, (fold && used == 1) ? b.folded : b.slabs, used, b.x1, bbox, c.T > 1 ? vel_div : nullptr, b.x3, cls_l, box_l,
+            TRY(sbev::launch_chain_tail(c, *w, folded ? b.folded : b.slabs, used, b.x1, bbox, c.T > 1 ? vel_div : nullptr, b.x3, cls_l, box_l,
                                         layer + 1 < c.num_layers, b.x, b.qkvt, eps, s_main, b.pair_x, b.pair_sync));
             bbox = box_l;
             continue;
@@ -446,12 +501,7 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
                                             c.B, c.Q, c.T, c.N, c.G, c.P, c.L, c.image_h, c.image_w, c.eps_homo, b.loc, b.wbp,
                                             lazy ? &lplan : nullptr, lazy ? b.touch_need : nullptr, c.hw, s_main));
         TRY(lazy_move(layer));
-        // gather + adaptive mixing: ONE launch when the fused kernel covers the shape (the sampled features then never
-        // touch HBM), else the sampler followed by the mixing kernel (same arithmetic, bit-identical results)
-        // (round 2 kept two launches for 5 fp32 levels: 168 registers + spills, 272 vs 277 samples/s at config 4; the lean chunk code
-        // of round 3 fits without spills -- g_fuse_l5_f32; 4 fp32 levels +1.6 % at config 2, 5 bf16 levels +4.3 % at config 5)
-        const bool fused = g_fuse_sample_mix.load(std::memory_order_relaxed) != 0 &&
-                           sample_mix_fusable(c);
+        // gather + adaptive mixing: one launch (fused) or the sampler followed by the mixing kernel
         if (!fused) {
             if (c.n_slots > 0)
                 TRY(sbev_msmv_fwd_ring(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
@@ -490,9 +540,7 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
         auto prob = [&](const float* X, const float* W, const float* bias, float* Y, int N, int relu) {
             return sbev_linear_problem{X, W, bias, nullptr, Y, BQ, N, D, D, D, N, relu};
         };
-        // only while sbev_linear_f32 would pick the same small-tile kernel for each of them (keeps the results identical
-        // to the op-by-op path); large batches have enough tiles per linear anyway
-        const bool grouped = !fork && (D == 256 || D == 512) && ((BQ + 127) / 128) * ((D + 127) / 128) < 256;
+        const bool grouped = p.grouped;
         const sbev::LnPrologue norm3{w->norm3_g, w->norm3_b, eps, 0, nullptr, b.x3};
         if (grouped) {
             // 5 launches for norm3 + the 9 ops of the two branches + refine (+ the next layer's first position-encoder stage):

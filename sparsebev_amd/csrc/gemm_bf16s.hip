@@ -1666,8 +1666,7 @@ Out4Plan out8_plan(long long M, int K) {
     }
     return p;
 }
-bool out8_takes(long long M, int K) {
-    const int mr = g_out8_min_rows.load(std::memory_order_relaxed);
+bool out8_takes(long long M, int K, int mr) {      // mr: the caller's reading of g_out8_min_rows
     if (mr <= 0 || M < mr) return false;
     const Out4Plan p = out8_plan(M, K);
     return p.base >= 2 && p.ntm <= 256;
@@ -1740,12 +1739,15 @@ extern "C" int sbev_linear_bf16s_gen_ok(int64_t M, int N, int K) {
            ntm_of(M) <= 256;
 }
 
-static bool gen_ws_takes(int64_t M, int N, int K, int64_t ldy, int nimg) {
-    return g_gen_ws.load(std::memory_order_relaxed) != 0 && K == 16 * WS_KS && nimg != 3 && M * ldy * 4 < 0x7fffffffLL;
-}
+namespace sbev {
+bool gen_weight_stationary_enabled() { return g_gen_ws.load(std::memory_order_relaxed) != 0; }
+// weight-stationary kernel (round 4): K = 256, two images, Y addressable by a 31-bit byte offset
+bool gen_ws_shape_ok(int64_t M, int K, int64_t ldy, int nimg) { return K == 16 * WS_KS && nimg != 3 && M * ldy * 4 < 0x7fffffffLL; }
+}  // namespace sbev
 
 static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias, float* Y, int64_t M, int N, int K, int64_t ldy, int relu,
-                      int nimg, const float* xscale, const float* colscale, sbev_stream_t stream, const sbev::LazyScan* lz = nullptr) {
+                      int nimg, const float* xscale, const float* colscale, bool weight_stationary, sbev_stream_t stream,
+                      const sbev::LazyScan* lz = nullptr) {
     SBEV_REQUIRE(M >= 0 && sbev_linear_bf16s_gen_ok(M > 0 ? M : 1, N, K), "sbev_linear_bf16s_gen: needs N %% 256 == 0, K %% 32 == 0, K <= 4096 (M=%lld N=%d K=%d)", (long long)M, N, K);
     if (M == 0) return SBEV_OK;
     SBEV_REQUIRE(Xs && Ws && Y && ldy >= N && ldy % 4 == 0, "sbev_linear_bf16s_gen: bad pointers / leading dimension");
@@ -1758,9 +1760,9 @@ static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias,
     }();
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipEvent_t e0, e1;
-    // weight-stationary kernel (round 4): K = 256, two images, Y addressable by a 31-bit byte offset
-    SBEV_REQUIRE(!lz || gen_ws_takes(M, N, K, ldy, nimg), "generator: the on-demand relayout's scan rides in the weight-stationary kernel only");
-    if (gen_ws_takes(M, N, K, ldy, nimg)) {
+    const bool ws = weight_stationary && sbev::gen_ws_shape_ok(M, K, ldy, nimg);
+    SBEV_REQUIRE(!lz || ws, "generator: the on-demand relayout's scan rides in the weight-stationary kernel only");
+    if (ws) {
         // row splits: tasks = column tiles x splits walked by <= one workgroup per CU; a task costs its fragments + ~4 fragments' worth
         // of weight load (256 KB that nothing overlaps).  c2 (29 fragments, 128 column tiles): 2 splits = 256 tasks of 15 / 14 fragments
         const int nct = N / G_COLS;
@@ -1859,7 +1861,7 @@ static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias,
 extern "C" int sbev_linear_bf16s_gen(const uint16_t* Xs, const uint16_t* Ws, const float* bias, float* Y, int64_t M, int N, int K,
                                      int64_t ldy, int relu, int nimg, sbev_stream_t stream) {
     SBEV_REQUIRE(nimg == 2 || nimg == 3, "sbev_linear_bf16s_gen: nimg=%d (2 = bf16x3, 3 = bf16x6)", nimg);
-    return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nimg, nullptr, nullptr, stream);
+    return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nimg, nullptr, nullptr, sbev::gen_weight_stationary_enabled(), stream);
 }
 
 // fp16 hi + lo images (sbev_pack_f16s_frags): xscale = X's {up, down} (per tensor), wdown = the [N] down-scales of W's rows;
@@ -1868,16 +1870,16 @@ extern "C" int sbev_linear_f16s_gen(const uint16_t* Xs, const float* xscale, con
                                     int64_t M, int N, int K, int64_t ldy, int relu, int nprod, sbev_stream_t stream) {
     SBEV_REQUIRE(nprod == 3 || nprod == 4, "sbev_linear_f16s_gen: nprod=%d (3 or 4 image products)", nprod);
     SBEV_REQUIRE(M == 0 || (xscale && wdown), "sbev_linear_f16s_gen: null scale pointer");
-    return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nprod + 1, xscale, wdown, stream);
+    return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nprod + 1, xscale, wdown, sbev::gen_weight_stationary_enabled(), stream);
 }
 
 namespace sbev {
-bool linear_f16s_gen_takes_scan(int64_t M, int N, int K, int64_t ldy, int nprod) { return gen_ws_takes(M, N, K, ldy, nprod + 1); }
-int linear_f16s_gen_scan(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y, int64_t M,
-                         int N, int K, int64_t ldy, int relu, int nprod, const LazyScan& lz, hipStream_t stream) {
-    SBEV_REQUIRE(nprod == 3 || nprod == 4, "sbev_linear_f16s_gen: nprod=%d (3 or 4 image products)", nprod);
-    SBEV_REQUIRE(M == 0 || (xscale && wdown), "sbev_linear_f16s_gen: null scale pointer");
-    return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nprod + 1, xscale, wdown, reinterpret_cast<sbev_stream_t>(stream), &lz);
+int linear_gen_split(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y, int64_t M,
+                     int N, int K, int64_t ldy, int relu, int nimg, bool weight_stationary, const LazyScan* lz, hipStream_t stream) {
+    SBEV_REQUIRE(nimg >= 2 && nimg <= 5, "sbev_linear_bf16s_gen: nimg=%d (2 = bf16x3, 3 = bf16x6, 4 / 5 = fp16 with 3 / 4 image products)", nimg);
+    SBEV_REQUIRE(nimg < 4 || M == 0 || (xscale && wdown), "sbev_linear_f16s_gen: null scale pointer");
+    return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nimg, nimg >= 4 ? xscale : nullptr, nimg >= 4 ? wdown : nullptr, weight_stationary,
+                      reinterpret_cast<sbev_stream_t>(stream), lz);
 }
 }  // namespace sbev
 
@@ -1901,8 +1903,9 @@ namespace sbev {
 std::atomic<int> g_out_fold{getenv("SBEV_OUT_FOLD") ? 1 : 0};
 std::atomic<int> g_out_fold_drop{0};
 int out_fold_drop(int enable) { return g_out_fold_drop.exchange(enable ? 1 : 0, std::memory_order_relaxed); }
-bool out_fold_ok(long long M, int K) {
-    if (g_out_fold.load(std::memory_order_relaxed) == 0 || M < 1 || M > 4096) return false;
+bool out_fold_enabled() { return g_out_fold.load(std::memory_order_relaxed) != 0; }
+bool out_fold_shape_ok(long long M, int K) {
+    if (M < 1 || M > 4096) return false;
     const Out4Plan pl = out4_plan(M, K);
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
@@ -1913,6 +1916,7 @@ bool out_fold_install(void* host_word_dev) {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_fold_fault_host), &host_word_dev, sizeof(host_word_dev)) == hipSuccess;
 }
 int out8_min_rows(int rows) { return g_out8_min_rows.exchange(out8_clamp(rows), std::memory_order_relaxed); }
+int out8_min_rows_setting() { return g_out8_min_rows.load(std::memory_order_relaxed); }
 int out_fold_switch(int enable) { return g_out_fold.exchange(enable ? 1 : 0, std::memory_order_relaxed); }
 long long out_fold_timeouts() {
     unsigned v = 0;
@@ -1921,16 +1925,18 @@ long long out_fold_timeouts() {
 }
 
 int launch_splitk_slabs_bf16s(const float* X, const uint16_t* Wp, int64_t M, int K, int64_t ldx, int nimg, float* slabs, int* used,
-                              hipStream_t s, int x_up_log2, const float* nscale, bool x_pairs, const float* xdev, unsigned* fold_sync,
-                              float* folded) {
+                              hipStream_t s, int out8_min_rows, int x_up_log2, const float* nscale, bool x_pairs, const float* xdev,
+                              unsigned* fold_sync, float* folded, bool* did_fold) {
+    if (did_fold) *did_fold = false;
     SBEV_REQUIRE(nimg < 4 || nscale, "sbev_linear_splitk_f16s: null scale pointer");
     SBEV_REQUIRE(!xdev || (nimg >= 4 && !x_pairs), "sbev_linear_splitk_f16s: a device-side X scale needs an fp16 mode and fp32 X");
     if (x_pairs) {                              // fp16 modes with the pre-split operand: 128-row tiles
         SBEV_REQUIRE(nimg >= 4, "sbev_linear_splitk_f16s: pre-split X needs an fp16 mode");
-        const bool big = out8_takes(M, K);                               // batch shapes: 256-row tiles (a third less operand delivery)
+        const bool big = out8_takes(M, K, out8_min_rows);                            // batch shapes: 256-row tiles (a third less operand delivery)
         const Out4Plan pl = big ? out8_plan(M, K) : out4_plan(M, K);
-        const bool fold = !big && fold_sync && folded && out_fold_ok(M, K);      // (the caller asked AND the shape / device allow it: else S slabs as before)
+        const bool fold = !big && fold_sync && folded && out_fold_shape_ok(M, K);      // (the caller asked AND the shape / device allow it: else S slabs as before)
         *used = fold ? 1 : pl.S;                                        // folded: the consumer reads `folded` as ONE slab
+        if (did_fold) *did_fold = fold;
         Out4Args a4{reinterpret_cast<const unsigned*>(X), Wp, slabs, (int)M, K, (long long)ldx, pl.ntm, pl.base, pl.rem, pl.S, nscale,
                     fold ? fold_sync : nullptr, fold ? folded : nullptr, g_out_fold_drop.load(std::memory_order_relaxed)};
         const long long wgs4 = (long long)pl.ntm * pl.S;
@@ -1990,7 +1996,7 @@ extern "C" int sbev_linear_splitk_bf16s(const float* X, const uint16_t* Wp, cons
     SBEV_REQUIRE(X && Wp && Y && workspace && ldx % 4 == 0 && ldx >= K, "sbev_linear_splitk_bf16s: bad pointers");
     SBEV_REQUIRE((((uintptr_t)X | (uintptr_t)Wp | (uintptr_t)workspace) & 15) == 0, "sbev_linear_splitk_bf16s: 16-byte alignment");
     int used = 0;
-    const int st = sbev::launch_splitk_slabs_bf16s(X, Wp, M, K, ldx, nimg, workspace, &used, reinterpret_cast<hipStream_t>(stream), 0, nullptr, false);
+    const int st = sbev::launch_splitk_slabs_bf16s(X, Wp, M, K, ldx, nimg, workspace, &used, reinterpret_cast<hipStream_t>(stream), sbev::out8_min_rows_setting(), 0, nullptr, false);
     if (st != SBEV_OK) return st;
     return sbev_splitk_reduce_f32(workspace, used, bias, residual, ln_w, ln_b, ln_eps, Y, M, N, relu, stream);
 }
@@ -2008,7 +2014,7 @@ extern "C" int sbev_linear_splitk_f16s(const float* X, int x_is_pairs, int x_up_
     SBEV_REQUIRE(X && Wp && Y && workspace && nscale && ldx % 4 == 0 && ldx >= K, "sbev_linear_splitk_f16s: bad pointers");
     SBEV_REQUIRE((((uintptr_t)X | (uintptr_t)Wp | (uintptr_t)workspace | (uintptr_t)nscale) & 15) == 0, "sbev_linear_splitk_f16s: 16-byte alignment");
     int used = 0;
-    const int st = sbev::launch_splitk_slabs_bf16s(X, Wp, M, K, ldx, nprod + 1, workspace, &used, reinterpret_cast<hipStream_t>(stream), x_up_log2, nscale,
+    const int st = sbev::launch_splitk_slabs_bf16s(X, Wp, M, K, ldx, nprod + 1, workspace, &used, reinterpret_cast<hipStream_t>(stream), sbev::out8_min_rows_setting(), x_up_log2, nscale,
                                                    x_is_pairs != 0);
     if (st != SBEV_OK) return st;
     return sbev_splitk_reduce_f32(workspace, used, bias, residual, ln_w, ln_b, ln_eps, Y, M, N, relu, stream);
@@ -2026,7 +2032,7 @@ extern "C" int sbev_linear_splitk_f16s_xdev(const float* X, const float* x_scale
     SBEV_REQUIRE(X && x_scale && Wp && Y && workspace && wdown && ldx % 4 == 0 && ldx >= K, "sbev_linear_splitk_f16s_xdev: bad pointers");
     SBEV_REQUIRE((((uintptr_t)X | (uintptr_t)Wp | (uintptr_t)workspace | (uintptr_t)wdown) & 15) == 0, "sbev_linear_splitk_f16s_xdev: 16-byte alignment");
     int used = 0;
-    const int st = sbev::launch_splitk_slabs_bf16s(X, Wp, M, K, ldx, nprod + 1, workspace, &used, reinterpret_cast<hipStream_t>(stream), 0, wdown, false, x_scale);
+    const int st = sbev::launch_splitk_slabs_bf16s(X, Wp, M, K, ldx, nprod + 1, workspace, &used, reinterpret_cast<hipStream_t>(stream), sbev::out8_min_rows_setting(), 0, wdown, false, x_scale);
     if (st != SBEV_OK) return st;
     return sbev_splitk_reduce_f32(workspace, used, bias, residual, ln_w, ln_b, ln_eps, Y, M, N, relu, stream);
 }

@@ -238,6 +238,9 @@ static int msmv_fwd_impl(const void* const* feats, const int32_t* hw, int L, int
 extern "C" int sbev_msmv_buffer_taps(int enable) {
     return g_buffer_taps.exchange(enable ? 1 : 0, std::memory_order_relaxed);
 }
+namespace sbev {
+bool msmv_buffer_taps_enabled() { return g_buffer_taps.load(std::memory_order_relaxed) != 0; }
+}  // namespace sbev
 
 extern "C" int sbev_msmv_fwd(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
                              int64_t Bp, int N, int C, int Q, int P,

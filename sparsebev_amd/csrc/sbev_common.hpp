@@ -45,19 +45,33 @@ int launch_splitk_slabs(const float* X, const float* W, int64_t M, int N, int K,
 int launch_splitk_slabs_bf16x3(const float* X, const uint16_t* W2, int64_t M, int N, int K, int64_t ldx, int splits,
                                float* workspace, int* used, hipStream_t s);
 
+// Every process-wide switch that influences what a decoder step enqueues, read ONCE per step (decoder.hip: read_switches) and handed
+// down from there.  sbev_decoder_switches() copies this struct out field by field IN THIS ORDER (include/sbev_hip.h lists it), so a
+// switch added here is part of every caller's graph key: int32_t fields only.
+struct Switches {
+    int32_t row_chain, chain_pair, fuse_sample_mix, fuse_l5_f32, query_order, lazy_scan_launch, out_fold, gen_weight_stationary,
+        out8_min_rows, msmv_buffer_taps, box_convention;
+};
+bool msmv_buffer_taps_enabled();      // msmv_sampling.hip (read by the sampler launchers themselves: public entry points of their own)
+
 // gemm_bf16s.hip: the GEMM half of sbev_linear_splitk_bf16s (*used partial slabs [used, M, 256], not reduced)
-// fold_sync + folded (pre-split fp16 operand only): the S chunk-workgroups of a row tile fold their slabs INSIDE the launch into
-// `folded` [M, 256] and *used = 1 -- taken only where out_fold_ok(M, K) (every workgroup of the launch resident at once); fold_sync: one
-// zeroed word per row tile (<= 64).  A row tile that never completes within the poll bound raises the decoder's fault word.
+// out8_min_rows: the caller's reading of sbev_linear_out8_min_rows (pre-split operand only: rows from which the 256-row tiles run).
+// fold_sync + folded (pre-split fp16 operand only; null unless the caller WANTS the fold): the S chunk-workgroups of a row tile fold their
+// slabs INSIDE the launch into `folded` [M, 256], *used = 1 and *did_fold = true -- taken only where out_fold_shape_ok(M, K) (every
+// workgroup of the launch resident at once) and the 128-row kernel runs; fold_sync: one zeroed word per row tile (<= 64).  A row tile
+// that never completes within the poll bound raises the decoder's fault word.
 int launch_splitk_slabs_bf16s(const float* X, const uint16_t* Wp, int64_t M, int K, int64_t ldx, int nimg, float* slabs, int* used,
-                              hipStream_t s, int x_up_log2 = 0, const float* nscale = nullptr, bool x_pairs = false, const float* xdev = nullptr,
-                              unsigned* fold_sync = nullptr, float* folded = nullptr);
-bool out_fold_ok(long long M, int K);
+                              hipStream_t s, int out8_min_rows, int x_up_log2 = 0, const float* nscale = nullptr, bool x_pairs = false,
+                              const float* xdev = nullptr, unsigned* fold_sync = nullptr, float* folded = nullptr, bool* did_fold = nullptr);
+bool out_fold_shape_ok(long long M, int K);
+bool out_fold_enabled();              // sbev_decoder_out_fold's current setting
 bool out_fold_install(void* host_word_dev);
 long long out_fold_timeouts();
 int out_fold_switch(int enable);
 int out8_min_rows(int rows);
+int out8_min_rows_setting();          // sbev_linear_out8_min_rows' current setting
 int out_fold_drop(int enable);
+bool gen_weight_stationary_enabled(); // sbev_linear_gen_weight_stationary's current setting
 
 // layout.hip: on-demand relayout of the units the sample points mark (sample_point.hpp::TouchMap); need / done: one 4-byte word per tile
 struct LazyPlan {
@@ -79,9 +93,12 @@ struct LazyScan {
     uint32_t *need, *done;
     bool last;
 };
-bool linear_f16s_gen_takes_scan(int64_t M, int N, int K, int64_t ldy, int nprod);
-int linear_f16s_gen_scan(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y, int64_t M,
-                         int N, int K, int64_t ldy, int relu, int nprod, const LazyScan& lz, hipStream_t stream);
+// the split-image generator GEMM behind sbev_linear_bf16s_gen (nimg 2 / 3; xscale = wdown = null) and sbev_linear_f16s_gen (nimg 4 / 5);
+// weight_stationary: the caller's reading of sbev_linear_gen_weight_stationary -- the weight-stationary kernel runs where it is set AND
+// gen_ws_shape_ok; lz (non-null: this layer's scan in the kernel's prologue) needs both
+bool gen_ws_shape_ok(int64_t M, int K, int64_t ldy, int nimg);
+int linear_gen_split(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y, int64_t M,
+                     int N, int K, int64_t ldy, int relu, int nimg, bool weight_stationary, const LazyScan* lz, hipStream_t stream);
 int launch_lazy_relayout(const LazyPlan& p, const void* const* table, const int32_t* index, const void* const* src, void* const* out,
                          int esize, uint32_t* need, uint32_t* done, bool first, bool last, hipStream_t s);
 

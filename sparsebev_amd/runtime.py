@@ -285,8 +285,7 @@ class DecoderRuntime:
         """pyramid: transformer.FeaturePyramid; ctx: transformer.DecoderContext.  Returns (cls, bbox) stacked over
         layers -- raw, or with ``finish`` nan_to_num'ed by one more launch of this library (sbev_finish_outputs: what
         SparseBEVTransformer.forward applies, models/sparsebev_transformer.py:35-36)."""
-        if _STATE['chain_pair']:
-            check_pair_faults()             # an earlier step lost a pair hand-off: raise before anything is enqueued on top of it
+        check_pair_faults()                 # an earlier step lost a pair hand-off: raise before anything is enqueued on top of it
         args, _keep, cls, box = self._prepare(query_bbox, query_feat, pyramid, ctx, attn_mask)
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         lib = _lib.load()
@@ -312,8 +311,7 @@ class DecoderRuntime:
         (sbev_decoder_forward_lazy): channels-last buffers (``buffers``, or new uninitialised ones) receive only the units the sample
         points read.  Bit-identical to ``forward`` on ``FeaturePyramid(mlvl_feats)``.  Returns (cls, box, pyramid-of-buffers)."""
         from . import transformer as TR
-        if _STATE['chain_pair']:
-            check_pair_faults()
+        check_pair_faults()
         pyramid = buffers if buffers is not None else TR.FeaturePyramid.empty_like_nchw(mlvl_feats)
         args, _keep, cls, box = self._prepare(query_bbox, query_feat, pyramid, ctx, attn_mask)
         lib = _lib.load()
@@ -452,15 +450,13 @@ class StepGraphs:
         if not hasattr(mlvl_feats, 'levels') and not all(torch.is_tensor(f) and f.is_cuda for f in mlvl_feats):
             return None
         from . import transformer as TR
-        if _STATE['chain_pair']:
-            check_pair_faults()             # (before a capture or replay is built on an invalid step; one host-memory read)
+        check_pair_faults()                 # (before a capture or replay is built on an invalid step; one host-memory read)
         sig = rt._ensure_bound()
         fkey, ident, staged = self._feat_key(mlvl_feats)
         key = (tuple(query_bbox.shape), tuple(query_feat.shape), fkey, None if attn_mask is None else tuple(attn_mask.shape), sig,
-               torch.cuda.current_device(), _STATE['row_chain'], _STATE['chain_pair'], _STATE['fuse'], _STATE['order'], _lib.load().sbev_get_box_convention(),
-               rt.decoder.num_layers, tuple(rt.decoder.pc_range),
+               torch.cuda.current_device(), _switch_key(), rt.decoder.num_layers, tuple(rt.decoder.pc_range),
                torch.cuda.current_stream(query_bbox.device).cuda_stream,      # per stream: a graph's workspace belongs to the stream it replays on
-               bool(finish), _STATE['relayout_multi'], _STATE['lazy'], _STATE['out_fold'])
+               bool(finish))
         e = self.entries.get(key, False)
         if e is False or (isinstance(e, _FirstSighting) and not e.same(ident)):
             # first sighting (or an address whose tensor died and was recycled): eager this time, capture if it comes again
@@ -671,13 +667,31 @@ class DecoderGraph:
             pass
 
 
-# process-wide switches mirrored here so that a captured step is only replayed under the settings it was recorded with
+# The process-wide switches live in the LIBRARY (sbev_decoder_switches reports them, however each was set); Python owns only these:
 import os as _os
-_STATE = {'row_chain': True, 'chain_pair': not _os.environ.get('SBEV_NO_CHAIN_PAIR'), 'fuse': True, 'profile': 0,
-          'out_fold': bool(_os.environ.get('SBEV_OUT_FOLD')),          # A/B (off: measured slower): the out-projection folds its split-K slabs inside its launch
-          'lazy': not _os.environ.get('SBEV_NO_SPARSE_RELAYOUT'),      # staged NCHW pyramids: on-demand relayout of the units the sample points read
-          'relayout_multi': not _os.environ.get('SBEV_NO_RELAYOUT_MULTI'),      # staged fp32 NCHW pyramids: all levels in one launch (A/B switch)
-          'order': (lambda v: 2 if v == 2 else int(v != 0))(int(_os.environ.get('SBEV_QUERY_ORDER', '0') or 0))}
+
+
+class _State(dict):
+    def __missing__(self, key):
+        if key != 'order':
+            raise KeyError(key)
+        return _switch_key()[4]        # until query_order() is called: the library's own start value (SBEV_QUERY_ORDER)
+
+
+# ('order' is kept for reports only -- query_order() writes it, nothing here decides by it)
+_STATE = _State(profile=0,
+                lazy=not _os.environ.get('SBEV_NO_SPARSE_RELAYOUT'),      # staged NCHW pyramids: on-demand relayout of the units the sample points read
+                relayout_multi=not _os.environ.get('SBEV_NO_RELAYOUT_MULTI'))      # staged fp32 NCHW pyramids: all levels in one launch (A/B switch)
+
+
+def _switch_key():
+    """Everything process-wide that changes what a step enqueues: the library's switches as it holds them NOW (sbev_decoder_switches:
+    the struct sbev_decoder_forward plans a step from, in include/sbev_hip.h's order) + the two Python-side ones.  A captured step is
+    only replayed under the key it was recorded with."""
+    buf = (ctypes.c_int32 * 32)()
+    n = _lib.load().sbev_decoder_switches(buf, 32)
+    assert 0 < n <= 32
+    return tuple(buf[:n]) + (bool(_STATE['lazy']), bool(_STATE['relayout_multi']))
 
 
 def out_fold(enable):
@@ -685,9 +699,7 @@ def out_fold(enable):
     modes, row chains, <= ~1000 rows; follows ``chain_pair``) so that the tail chain reads one row block instead of 32 slabs.  Bit-identical
     results either way.  OFF by default -- at config 2 it costs the out-projection 12.6 us and saves the tail 4 (DESIGN.md section 4.4);
     ``SBEV_OUT_FOLD=1`` starts with it on.  Returns the previous setting."""
-    prev = bool(_lib.load().sbev_decoder_out_fold(int(bool(enable))))
-    _STATE['out_fold'] = bool(enable)
-    return prev
+    return bool(_lib.load().sbev_decoder_out_fold(int(bool(enable))))
 
 
 def lazy_relayout(enable):
@@ -712,7 +724,6 @@ def fuse_sample_mix(enable):
     """Gather + adaptive mixing as one launch inside sbev_decoder_forward where the fused kernel covers the shape (default on;
     results are bit-identical either way).  ``SBEV_NO_SAMPLE_MIX=1`` in the environment switches it off for A/B runs."""
     _lib.check(_lib.load().sbev_decoder_fuse_sample_mix(int(bool(enable))), 'sbev_decoder_fuse_sample_mix')
-    _STATE['fuse'] = bool(enable)
 
 
 def row_chain(enable):
@@ -720,7 +731,6 @@ def row_chain(enable):
     launches with the rows in LDS instead of one launch per op (default on where the kernels cover the layer's shape; results
     agree to fp32 round-off, not bit for bit).  ``SBEV_NO_ROW_CHAIN=1`` in the environment switches it off for A/B runs."""
     _lib.check(_lib.load().sbev_decoder_row_chain(int(bool(enable))), 'sbev_decoder_row_chain')
-    _STATE['row_chain'] = bool(enable)
 
 
 def chain_pair(enable):
@@ -728,17 +738,14 @@ def chain_pair(enable):
     where both members of every pair fit the device in one round: <= ~2000 rows on 256 CUs; results agree with the
     single-workgroup tail to fp32 round-off).  ``SBEV_NO_CHAIN_PAIR=1`` in the environment starts with it off.  Returns the
     previous setting."""
-    prev = _lib.load().sbev_decoder_chain_pair(int(bool(enable)))
-    _STATE['chain_pair'] = bool(enable)
-    return bool(prev)
+    return bool(_lib.load().sbev_decoder_chain_pair(int(bool(enable))))
 
 
 def _on_pair_fault():
-    """SBEV_EFAULT came back (``_lib.check``): mirror what the library did (pair mode off -- captured pair-mode steps are keyed on
+    """SBEV_EFAULT came back (``_lib.check``): pair mode off (the library did that already; captured pair-mode steps are keyed on
     the switch and are not hit again) and acknowledge, so that the caller's repeated step runs on the single-workgroup tail."""
     lib = _lib.load()
     lib.sbev_decoder_chain_pair(0)
-    _STATE['chain_pair'] = False
     lib.sbev_decoder_chain_pair_faults_ack()
     import warnings
     warnings.warn('sparsebev_amd: a pair-mode tail hand-off timed out (GPU shared / preempted?); pair mode is off for the rest of the process')

@@ -99,6 +99,29 @@ def test_new_tensors_weight_updates_and_switches_never_hit_a_stale_graph():
         assert torch.equal(o1[0], w[0]) and torch.equal(o2[0], w[0])
     finally:
         runtime.row_chain(True)
+    # ... whichever way a switch is set: the key is the LIBRARY's own reading (sbev_decoder_switches), so the raw C setters -- which the
+    # Python runtime never sees -- open a new entry too, and restoring the switch finds the first graph again
+    from sparsebev_amd import _lib
+    lib = _lib.load()
+    sg = g.decoder._runtime.step_graphs
+    for setter, other in ((lib.sbev_decoder_lazy_scan_launch, 1), (lib.sbev_linear_gen_weight_stationary, 0),
+                          (lib.sbev_linear_out8_min_rows, 0), (lib.sbev_msmv_buffer_taps, 0)):
+        w = e(bbox, feat, list(feats), None, metas)
+        captures, replays = sg.captures, sg.replays
+        o = g(bbox, feat, list(feats), None, metas)                  # the graph recorded under the settings we started with
+        assert sg.captures == captures and sg.replays == replays + 1 and torch.equal(o[0], w[0]) and torch.equal(o[1], w[1])
+        prev = setter(other)
+        try:
+            assert prev != other
+            outs = [g(bbox, feat, list(feats), None, metas) for _ in range(3)]       # eager, capture + replay, replay
+            w2 = e(bbox, feat, list(feats), None, metas)
+            assert sg.captures == captures + 1 and sg.replays == replays + 3, (setter, sg.captures, sg.replays)
+            for o in outs:
+                assert torch.equal(o[0], w2[0]) and torch.equal(o[1], w2[1])
+        finally:
+            setter(prev)
+        o = g(bbox, feat, list(feats), None, metas)
+        assert sg.captures == captures + 1 and sg.replays == replays + 4 and torch.equal(o[0], w[0]) and torch.equal(o[1], w[1])
     # a different layer count on the same module (tests do this) is another step
     g.decoder.num_layers = e.decoder.num_layers = 1
     assert g(bbox, feat, list(feats), None, metas)[0].shape[0] == 1

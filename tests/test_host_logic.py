@@ -135,3 +135,198 @@ def test_version_switch_reaches_the_library():
         VERSION.name = 'v1.0.0'
     assert lib.sbev_get_box_convention() == 0
     assert lib.sbev_set_box_convention(7) != 0 and b'convention' in lib.sbev_last_error()
+
+
+# ---- what a decoder step enqueues is decided in one place (csrc/decoder.hip: plan_step) ------------------------------------------
+
+_PLAN_PYRAMIDS = {4: [(64, 176), (32, 88), (16, 44), (8, 22)], 5: [(128, 352), (64, 176), (32, 88), (16, 44), (8, 22)]}
+
+
+def _plan_config(gemm_mode, overlap, L, feat_dtype, B):
+    from sparsebev_amd import runtime as R
+    c = R.DecoderConfig()
+    c.B, c.Q, c.T, c.N, c.G, c.P, c.L = B, 900, 8, 6, 4, 4, L
+    c.D, c.H, c.ffn, c.num_classes, c.code_size, c.num_layers = 256, 8, 512, 10, 10, 6
+    c.out_points, c.attn_in_rows, c.feat_dtype = 128, 3 * 256 + 8, feat_dtype
+    for l, (h, w) in enumerate(_PLAN_PYRAMIDS[L]):
+        c.hw[l][0], c.hw[l][1] = h, w
+    c.image_h, c.image_w, c.eps_homo, c.gemm_mode, c.overlap = 256.0, 704.0, 1e-5, gemm_mode, overlap
+    return c
+
+
+# one line per (gemm_mode 0..5, row_chain 1 / 0, fuse_sample_mix 1 / 0, query_order 0 / 1 / 2) in itertools.product order; within a line
+# (overlap 0 / 1 / 2) x (L=4 fp32, L=5 fp32, L=5 bf16) x (900, 3600, 7200 rows) x (chain_pack null, non-null), same order
+_LAUNCHES_PER_LAYER = [
+    '17 6 17 6 17 17 17 6 17 6 17 17 17 6 17 6 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17',
+    '17 7 17 7 17 17 17 7 17 7 17 17 17 7 17 7 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17',
+    '17 6 17 6 17 17 17 6 17 6 17 17 17 6 17 6 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17',
+    '17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17',
+    '17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17 17',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 8 18 8 18 18 18 8 18 8 18 18 18 8 18 8 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 8 19 8 19 19 19 8 19 8 19 19 19 8 19 8 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 8 19 8 19 19 19 8 19 8 19 19 19 8 19 8 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 8 19 8 19 19 19 8 19 8 19 19 19 8 19 8 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 8 18 8 18 18 18 8 18 8 18 18 18 8 18 8 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 8 19 8 19 19 19 8 19 8 19 19 19 8 19 8 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 8 19 8 19 19 19 8 19 8 19 19 19 8 19 8 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 8 19 8 19 19 19 8 19 8 19 19 19 8 19 8 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 8 18 8 18 18 18 8 18 8 18 18 18 8 18 8 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 8 19 8 19 19 19 8 19 8 19 19 19 8 19 8 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 8 19 8 19 19 19 8 19 8 19 19 19 8 19 8 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 8 19 8 19 19 19 8 19 8 19 19 19 8 19 8 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '18 6 18 6 18 18 18 6 18 6 18 18 18 6 18 6 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 6 18 6 18 18 18 6 18 6 18 18 18 6 18 6 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 7 19 7 19 19 19 7 19 7 19 19 19 7 19 7 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 7 19 7 19 19 19 7 19 7 19 19 19 7 19 7 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 7 19 7 19 19 19 7 19 7 19 19 19 7 19 7 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '18 6 18 6 18 18 18 6 18 6 18 18 18 6 18 6 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 7 18 7 18 18 18 7 18 7 18 18 18 7 18 7 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 6 18 6 18 18 18 6 18 6 18 18 18 6 18 6 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 7 19 7 19 19 19 7 19 7 19 19 19 7 19 7 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 7 19 7 19 19 19 7 19 7 19 19 19 7 19 7 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 7 19 7 19 19 19 7 19 7 19 19 19 7 19 7 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18 18',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+    '19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19 19',
+]
+
+
+def test_launches_per_layer_table_is_the_recorded_one():
+    """sbev_decoder_launches_per_layer is the forward's own plan (csrc/decoder.hip: plan_step); its values for 3888 (mode, switches, shape,
+    weights) cases + one invalid config equal the table recorded from the commit BEFORE the plan existed, when the entry point was a hand
+    copy of the forward's conditions.  The table was printed by this very loop (the two `for` statements below with `row.append(got)` in
+    place of the comparison, one `' '.join` per row) run against a build of that commit.  No device needed."""
+    import ctypes
+    import itertools
+    from sparsebev_amd import _lib, runtime as R
+    lib = _lib.load()
+    before = R._switch_key()
+    keep = ctypes.create_string_buffer(64)           # any non-null address: the entry point never reads through chain_pack
+    table = [[int(v) for v in line.split()] for line in _LAUNCHES_PER_LAYER]
+    assert len(table) == 72 and all(len(r) == 54 for r in table)
+    n = 0
+    try:
+        for row, (mode, chain, fuse, order) in zip(table, itertools.product(range(6), (1, 0), (1, 0), (0, 1, 2))):
+            lib.sbev_decoder_row_chain(chain)
+            lib.sbev_decoder_fuse_sample_mix(fuse)
+            lib.sbev_decoder_query_order(order)
+            for want, (overlap, (L, dt), B, pack) in zip(row, itertools.product((0, 1, 2), ((4, 0), (5, 0), (5, 1)), (1, 4, 8), (False, True))):
+                w = R.DecoderWeights()
+                if pack:
+                    w.chain_pack = ctypes.cast(keep, ctypes.c_void_p)
+                got = lib.sbev_decoder_launches_per_layer(ctypes.byref(_plan_config(mode, overlap, L, dt, B)), ctypes.byref(w))
+                assert got == want, (mode, chain, fuse, order, overlap, L, dt, B, pack, got, want)
+                n += 1
+    finally:
+        lib.sbev_decoder_row_chain(before[0])
+        lib.sbev_decoder_fuse_sample_mix(before[2])
+        lib.sbev_decoder_query_order(before[4])
+    assert n == 3888 and R._switch_key() == before
+    bad = _plan_config(0, 0, 4, 0, 1)
+    bad.gemm_mode = 6
+    assert lib.sbev_decoder_launches_per_layer(ctypes.byref(bad), ctypes.byref(R.DecoderWeights())) == -1
+    assert lib.sbev_decoder_launches_per_layer(ctypes.byref(_plan_config(4, 0, 4, 0, 1)), None) == -1
+
+
+def test_every_switch_is_in_the_step_graph_key():
+    """runtime._switch_key() -- the switch part of StepGraphs' key -- is the library's own reading (sbev_decoder_switches) + the two
+    Python-side switches: toggling ANY switch changes it, restoring the switch restores it, and the raw C setter and the Python wrapper
+    (where there is one) give the same key.  Includes the four the key used to miss: out8_min_rows, lazy_scan_launch,
+    gen_weight_stationary, msmv_buffer_taps."""
+    import ctypes
+    from sparsebev_amd import _lib, runtime as R
+    from sparsebev_amd.utils import VERSION
+    lib = _lib.load()
+    buf = (ctypes.c_int32 * 4)()
+    assert lib.sbev_decoder_switches(buf, 4) == 11 and tuple(buf) == R._switch_key()[:4]       # (a short buffer is filled, never overrun)
+    assert lib.sbev_decoder_switches(None, 0) == 11
+    base = R._switch_key()
+    assert len(base) == 13 and base[10] == lib.sbev_get_box_convention()
+
+    def set_version(code):
+        VERSION.name = {0: 'v1.0.0', 1: 'v0.17.1'}[code]
+
+    # (position in the key, raw C setter, Python wrapper or None, another value)
+    cases = [(0, lib.sbev_decoder_row_chain, R.row_chain, 1 - base[0]),
+             (1, lib.sbev_decoder_chain_pair, R.chain_pair, 1 - base[1]),
+             (2, lib.sbev_decoder_fuse_sample_mix, R.fuse_sample_mix, 1 - base[2]),
+             (4, lib.sbev_decoder_query_order, R.query_order, 1 if base[4] != 1 else 2),
+             (4, lib.sbev_decoder_query_order, R.query_order, 2 if base[4] != 2 else 0),
+             (5, lib.sbev_decoder_lazy_scan_launch, None, 1 - base[5]),
+             (6, lib.sbev_decoder_out_fold, R.out_fold, 1 - base[6]),
+             (7, lib.sbev_linear_gen_weight_stationary, None, 1 - base[7]),
+             (8, lib.sbev_linear_out8_min_rows, None, 0 if base[8] else 1024),
+             (8, lib.sbev_linear_out8_min_rows, None, base[8] + 1024),
+             (9, lib.sbev_msmv_buffer_taps, None, 1 - base[9]),
+             (10, lib.sbev_set_box_convention, set_version, 1 - base[10])]
+    seen = {base}
+    for pos, c_set, py_set, other in cases:
+        keys = []
+        for setter in (c_set, py_set):
+            if setter is None:
+                continue
+            try:
+                setter(other)
+                keys.append(R._switch_key())
+            finally:
+                setter(base[pos])
+            assert R._switch_key() == base, (pos, other)
+        changed = base[:pos] + (other,) + base[pos + 1:]
+        assert all(k == changed for k in keys), (pos, other, keys)       # that switch moved, no other did, both ways of setting agree
+        seen.add(changed)
+    assert len(seen) == len(cases) + 1
+    # the two switches Python owns
+    prev = R.lazy_relayout(not base[11])
+    try:
+        assert prev == base[11] and R._switch_key() == base[:11] + (not base[11], base[12])
+    finally:
+        R.lazy_relayout(prev)
+    R._STATE['relayout_multi'] = not base[12]
+    try:
+        assert R._switch_key() == base[:12] + (not base[12],)
+    finally:
+        R._STATE['relayout_multi'] = base[12]
+    assert R._switch_key() == base
+    # the one report-only entry that stays in _STATE follows query_order() and starts from the library's value
+    assert R._STATE['order'] == base[4]
