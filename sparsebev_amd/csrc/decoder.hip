@@ -208,7 +208,7 @@ extern "C" int sbev_decoder_switches(int32_t* out, int capacity) {
 }
 
 // What one decoder step enqueues for a (config, weight set, reading of the switches): every path decision of sbev_decoder_forward is
-// taken HERE, decoder_forward_impl follows the plan and sbev_decoder_launches_per_layer reports it.  Touches no device.
+// taken HERE, Step (below) follows the plan and sbev_decoder_launches_per_layer reports it.  Touches no device.
 struct StepPlan {
     int nimg;                // split-bf16 / fp16 kernels (gemm_bf16s.hip): their mode code 2 = bf16x3s, 3 = bf16x6, 4 = f16x3, 5 = f16x4; else 0
     int64_t BQ;
@@ -298,6 +298,260 @@ extern "C" int64_t sbev_decoder_workspace_bytes(const sbev_decoder_config* cfg) 
     return (int64_t)carve(*cfg, nullptr).bytes;
 }
 
+namespace {
+
+// One decoder step being enqueued: follows its StepPlan, one member function per stage.  Built once per call, on the stack.
+struct Step {
+    const sbev_decoder_config& c;
+    const sbev_decoder_weights& w;
+    const StepPlan& p;
+    const Buffers& b;
+    const void* const* feats_nhwc;
+    const float *query_bbox, *query_feat, *time_diff, *lidar2img, *vel_div;
+    const uint8_t* attn_mask;
+    float *cls_out, *bbox_out;
+    // on-demand relayout (sbev_decoder_forward_lazy): feats_nhwc are DESTINATIONS; every layer's point selection marks the units its
+    // points read and one launch behind it moves the marked units that this step has not moved yet (csrc/layout.hip)
+    const sbev_lazy_feats* lazy;
+    sbev_stream_t stream;            // the caller's stream ...
+    Aux& ax;                         // ... and the aux stream + event ring, used only when p.fork
+    hipStream_t s_main = reinterpret_cast<hipStream_t>(stream);
+    sbev_stream_t s_aux = p.fork ? reinterpret_cast<sbev_stream_t>(ax.stream) : stream;
+    int evi = 0;                     // next event of ax.ev
+    sbev::LazyPlan lplan{};
+    // feature pyramid descriptors: zero-copy NHWC, group g = channel slice [g*Cg, (g+1)*Cg)
+    int32_t hw[2 * SBEV_MAX_LEVELS];
+    int64_t sbo[SBEV_MAX_LEVELS], sv[SBEV_MAX_LEVELS];
+    const int mixed_up = sbev_decoder_mixed_up_log2(&c), D = c.D, Cg = c.D / c.G, Pin = c.T * c.P;
+    const float eps = 1e-5f;
+    const float* bbox = query_bbox;  // both paths: the layer's input boxes (the previous layer's refined ones)
+    const float* feat = query_feat;  // op by op: the layer's input features (query_feat, then x3)
+    bool pe0_done = false;           // op by op: the previous layer's grouped tail already ran this layer's first position-encoder stage
+    hipEvent_t ev_cls = nullptr;     // forked: end of the previous layer's classification branch on the aux stream
+
+    float* cls_of(int layer) const { return cls_out + (int64_t)layer * p.BQ * c.num_classes; }
+    float* box_of(int layer) const { return bbox_out + (int64_t)layer * p.BQ * c.code_size; }
+    int feat_esize() const { return c.feat_dtype == SBEV_F32 ? 4 : 2; }
+
+    int fork_to_aux() {      // the aux stream continues from here (callers: only when p.fork)
+        hipEvent_t e = ax.ev[(evi++) & 7];
+        TRY(hip_ok(hipEventRecord(e, s_main), "hipEventRecord"));
+        return hip_ok(hipStreamWaitEvent(ax.stream, e, 0), "hipStreamWaitEvent");
+    }
+    int record_on_aux(hipEvent_t* ev) {
+        *ev = ax.ev[(evi++) & 7];
+        return hip_ok(hipEventRecord(*ev, ax.stream), "hipEventRecord");
+    }
+    int join(hipEvent_t ev) { return ev ? hip_ok(hipStreamWaitEvent(s_main, ev, 0), "hipStreamWaitEvent") : SBEV_OK; }      // null: nothing was forked
+    int lazy_move(int layer) {
+        if (!lazy) return SBEV_OK;
+        return sbev::launch_lazy_relayout(lplan, lazy->table, lazy->index, lazy->src, const_cast<void* const*>(feats_nhwc), feat_esize(),
+                                          b.touch_need, b.touch_done, layer == 0, layer + 1 == c.num_layers, s_main);
+    }
+
+    // parameter generator in the 3 x bf16 mode: x1 is split once per layer and streamed past W-stationary strips
+    int generator_bf16x3(sbev_stream_t st) {
+        if (!p.pg_strip) return sbev_linear_bf16x3(b.x1, w.pg_w2, w.pg_b, nullptr, b.params, p.BQ, p.pgN, D, D, p.pgN, 0, st);
+        uint16_t* x2 = reinterpret_cast<uint16_t*>(b.x1s);
+        TRY(sbev_split_bf16x3_weights(b.x1, x2, p.BQ, D, st));
+        return sbev_linear_bf16x3_strip(x2, w.pg_w2, w.pg_b, b.params, p.BQ, p.pgN, D, p.pgN, 0, st);
+    }
+    // split-image modes: x1 -> image fragments (a launch of its own unless the attention chain wrote them) -> Y = X W^T + b;
+    // scan_layer > 0: that layer's on-demand relayout scan inside the generator
+    int generator_bf16s(sbev_stream_t st, int scan_layer) {
+        uint16_t* xs = reinterpret_cast<uint16_t*>(b.x1s);
+        if (p.pack_launch) {
+            // fp16 hi + lo: x1 scaled by one power of two (its maximum -> [2^14, 2^15))
+            // (the power of two comes with the weights: norm1's output is bounded by sqrt(D - 1) max|gamma| + max|beta| -- no pass for a maximum)
+            TRY(p.nimg >= 4 ? sbev_pack_f16s_frags(b.x1, D, xs, const_cast<float*>(w.pg_xscale), (int)p.BQ, D, 2, st)
+                            : sbev_pack_bf16s_frags(b.x1, D, xs, (int)p.BQ, D, p.nimg, st));
+        }
+        sbev::LazyScan lz{};
+        if (scan_layer > 0)
+            lz = sbev::LazyScan{&lplan, lazy->table, lazy->index, lazy->src, const_cast<void* const*>(feats_nhwc), feat_esize(),
+                                b.touch_need, b.touch_done, scan_layer + 1 == c.num_layers};
+        return sbev::linear_gen_split(xs, w.pg_xscale, w.pg_ws, w.pg_wdown, w.pg_b, b.params, p.BQ, p.pgN, D, p.pgN, 0, p.nimg, p.gen_ws,
+                                      scan_layer > 0 ? &lz : nullptr, reinterpret_cast<hipStream_t>(st));
+    }
+    int generator(sbev_stream_t st, int scan_layer) {
+        if (p.nimg) return generator_bf16s(st, scan_layer);
+        if (c.gemm_mode == SBEV_GEMM_BF16X3) return generator_bf16x3(st);
+        return sbev_linear_f32(b.x1, w.pg_w, w.pg_b, nullptr, b.params, p.BQ, p.pgN, D, D, D, p.pgN, 0, st);
+    }
+
+    int gather(sbev_stream_t st) {      // the stand-alone sampler
+        if (c.n_slots > 0)
+            return sbev_msmv_fwd_ring(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
+                                      c.G, sbo, Cg, sv, D, b.loc, b.wbp, b.sampled, SBEV_OUT_MIX, c.T, c.G, c.frame_slots, c.n_slots, st);
+        return sbev_msmv_fwd(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
+                             c.G, sbo, Cg, sv, D, b.loc, b.wbp, b.sampled, SBEV_OUT_MIX, c.T, c.G, st);
+    }
+    // gather + adaptive mixing: one launch (fused) or the sampler followed by the mixing kernel.  `params_ready` (forked generator, else
+    // null): the join sits where the generator's output is first needed -- behind the stand-alone sampler, which reads none of it.
+    // The mixing launches: in the fp16 GEMM modes their epilogue leaves `mixed` as (fp16 hi, fp16 lo) pairs of mixed 2^mixed_up -- the
+    // out-projection's operand, split once per element where the VALU is idle instead of inside the GEMM
+    int gather_and_mix(sbev_stream_t st, const int32_t* order, hipEvent_t params_ready = nullptr) {
+        if (!p.fused) TRY(gather(st));
+        TRY(join(params_ready));
+        if (!p.fused && p.nimg >= 4) return sbev_adaptive_mixing_pairs_f16(b.sampled, b.params, b.mixed, p.BQ, c.G, Pin, Cg, c.out_points, eps, mixed_up, st);
+        if (!p.fused) return sbev_adaptive_mixing_f32(b.sampled, b.params, b.mixed, p.BQ, c.G, Pin, Cg, c.out_points, eps, st);
+        if (p.nimg >= 4)
+            return sbev_sample_mix_pairs_f16_ordered(feats_nhwc, hw, c.L, c.feat_dtype, c.B, c.N, c.Q, c.T, c.G, c.P, Cg, sbo, Cg, sv, D, b.loc, b.wbp,
+                                                     c.n_slots > 0 ? c.frame_slots : nullptr, c.n_slots, b.params, b.mixed, c.out_points, eps, mixed_up, order, st);
+        return sbev_sample_mix_f32_ordered(feats_nhwc, hw, c.L, c.feat_dtype, c.B, c.N, c.Q, c.T, c.G, c.P, Cg, sbo, Cg, sv, D, b.loc, b.wbp,
+                                           c.n_slots > 0 ? c.frame_slots : nullptr, c.n_slots, b.params, b.mixed, c.out_points, eps, order, st);
+    }
+
+    // out-projection, row chains: the split-K slabs are left for the tail chain (`used` of them), or folded inside the launch into ONE row block, b.folded
+    int out_projection_slabs(int* used, bool* folded) {
+        // (the fold needs the fault word to report a row tile that never completed)
+        const bool fold = p.fold_wanted && sbev::out_fold_shape_ok(p.BQ, p.mixN) && sbev::chain_fault_word_ready();
+        if (p.nimg)
+            return sbev::launch_splitk_slabs_bf16s(b.mixed, w.op_wp, p.BQ, p.mixN, p.mixN, p.nimg, b.slabs, used, s_main, p.out8_min_rows, mixed_up,
+                                                   w.op_nscale, p.nimg >= 4, nullptr, fold ? b.pair_sync + sbev::chain_fold_sync_offset(p.BQ) : nullptr,
+                                                   fold ? b.folded : nullptr, folded);
+        if (c.gemm_mode == SBEV_GEMM_BF16X3)
+            return sbev::launch_splitk_slabs_bf16x3(b.mixed, w.op_w2, p.BQ, D, p.mixN, p.mixN, p.splits, b.slabs, used, s_main);
+        return sbev::launch_splitk_slabs(b.mixed, w.op_w, p.BQ, D, p.mixN, p.mixN, p.mixN, p.splits, b.slabs, used, s_main);
+    }
+    // out-projection, op by op: + bias + x1, norm2 -> x2                         (:171)
+    int out_projection(sbev_stream_t st) {
+        if (p.nimg >= 4)
+            return sbev_linear_splitk_f16s(b.mixed, 1, mixed_up, w.op_wp, w.op_nscale, w.op_b, b.x1, w.norm2_g, w.norm2_b, eps, b.x2, p.BQ, D, p.mixN,
+                                           p.mixN, 0, p.nimg - 1, b.slabs, st);
+        if (p.nimg)
+            return sbev_linear_splitk_bf16s(b.mixed, w.op_wp, w.op_b, b.x1, w.norm2_g, w.norm2_b, eps, b.x2, p.BQ, D, p.mixN, p.mixN,
+                                            0, p.nimg, b.slabs, st);
+        if (c.gemm_mode == SBEV_GEMM_BF16X3)
+            return sbev_linear_splitk_bf16x3(b.mixed, w.op_w2, w.op_b, b.x1, w.norm2_g, w.norm2_b, eps, b.x2, p.BQ, D, p.mixN, p.mixN,
+                                             0, p.splits, b.slabs, st);
+        return sbev_linear_splitk_f32(b.mixed, w.op_w, w.op_b, b.x1, w.norm2_g, w.norm2_b, eps, b.x2, p.BQ, D, p.mixN, p.mixN, p.mixN,
+                                      0, p.splits, b.slabs, st);
+    }
+
+    // a layer as row chains (row_chain.hip): 6 launches instead of 17
+    int layer_chain(int layer) {
+        if (p.order_mode != 0 && (layer == 0 || p.order_mode == 1)) TRY(sbev_query_order(bbox, c.code_size, c.pc_range, c.B, c.Q, b.order, stream));
+        TRY(sbev_sasa_f32(b.qkvt, c.attn_in_rows, bbox, c.pc_range, attn_mask, b.att, c.B, c.Q, c.H, D / c.H, stream));
+        // (fp16 GEMM modes: the chain also leaves x1 as the generator's fragment operand -- no pack launch)
+        TRY(sbev::launch_chain_attn(c, w, b.att, b.x, b.x1, bbox, time_diff, lidar2img, b.loc, b.wbp, eps, s_main,
+                                    p.nimg >= 4 ? reinterpret_cast<uint16_t*>(b.x1s) : nullptr, p.nimg >= 4 ? w.pg_xscale : nullptr, b.pair_sync,
+                                    lazy ? &lplan : nullptr, lazy ? b.touch_need : nullptr));
+        const bool ride = p.scan_in_gen && layer > 0;
+        if (!ride) TRY(lazy_move(layer));      // (layer 0's move behind the generator instead of in front of it: measured equal, 537-539 both ways)
+        TRY(generator(stream, ride ? layer : -1));
+        TRY(gather_and_mix(stream, p.order_mode != 0 ? b.order : nullptr));
+        int used = 0;
+        bool folded = false;      // the out-projection folded its slabs inside its launch: the tail reads ONE row block, b.folded
+        TRY(out_projection_slabs(&used, &folded));
+        TRY(sbev::launch_chain_tail(c, w, folded ? b.folded : b.slabs, used, b.x1, bbox, c.T > 1 ? vel_div : nullptr, b.x3, cls_of(layer), box_of(layer),
+                                    layer + 1 < c.num_layers, b.x, b.qkvt, eps, s_main, b.pair_x, b.pair_sync));
+        bbox = box_of(layer);
+        return SBEV_OK;
+    }
+
+    // a layer op by op: 17 launches with the fused gather + mixing (DESIGN_HISTORY.md section 4)
+    int layer_ops(int layer) {
+        // position encoder -> x = feat + pos                                   (sparsebev_transformer.py:166-167)
+        if (!pe0_done) TRY(sbev_linear3_ln_relu_f32(bbox, layer == 0 ? 10 : c.code_size, w.pe0_w, w.pe0_b, w.pe1_g, w.pe1_b, eps, b.t0, p.BQ, D, stream));
+        pe0_done = false;
+        TRY(sbev_linear_f32(b.t0, w.pe3_w, w.pe3_b, nullptr, b.t1, p.BQ, D, D, D, D, D, 0, stream));
+        // Three of the layer's LayerNorms run as the PROLOGUE of the small-tile Linear that consumes them
+        // (sbev_ln_linear_f32: one launch instead of two, the normalised rows are stored for the other readers):
+        // here the position encoder's last norm (+ ReLU, + query_feat) -> x, with the attention in-projection
+        TRY(sbev_ln_linear_f32(b.t1, w.pe4_g, w.pe4_b, eps, 1, feat, b.x, w.attn_in_w, w.attn_in_b, nullptr, b.qkvt,
+                               p.BQ, c.attn_in_rows, D, D, c.attn_in_rows, 0, stream));
+        // scale-adaptive self attention                                         (:169)
+        TRY(sbev_sasa_f32(b.qkvt, c.attn_in_rows, bbox, c.pc_range, attn_mask, b.att, c.B, c.Q, c.H, D / c.H, stream));
+        TRY(sbev_linear_f32(b.att, w.attn_out_w, w.attn_out_b, b.x, b.t1, p.BQ, D, D, D, D, D, 0, stream));
+        // norm1 -> x1, with the Linear of the sampling offsets / level logits      (:169-170)
+        TRY(sbev_ln_linear_f32(b.t1, w.norm1_g, w.norm1_b, eps, 0, nullptr, b.x1, w.samp_w, w.samp_b, nullptr, b.so,
+                               p.BQ, p.soN, D, D, p.soN, 0, stream));
+        // fork: parameter generator (needs only x1) on the aux stream, beside the sampling chain
+        hipEvent_t ev_pg = nullptr;
+        if (p.fork_pg) TRY(fork_to_aux());
+        TRY(generator(p.fork_pg ? s_aux : stream, -1));
+        if (p.fork_pg) TRY(record_on_aux(&ev_pg));
+        // adaptive spatio-temporal sampling                                     (:170)
+        TRY(sbev::launch_sample_and_project(bbox, b.so, p.soN, b.so + c.G * c.P * 3, p.soN, time_diff, lidar2img, c.pc_range,
+                                            c.B, c.Q, c.T, c.N, c.G, c.P, c.L, c.image_h, c.image_w, c.eps_homo, b.loc, b.wbp,
+                                            lazy ? &lplan : nullptr, lazy ? b.touch_need : nullptr, c.hw, s_main));
+        TRY(lazy_move(layer));
+        // gather + adaptive mixing (join: the generator's output is needed now), out-projection + norm2  (:171)
+        TRY(gather_and_mix(stream, nullptr, ev_pg));
+        TRY(out_projection(stream));
+        // (the previous layer's classification branch still reads x3 on the aux stream: join before x3 is rewritten)
+        TRY(join(ev_cls));
+        // FFN + norm3                                                           (:172)
+        TRY(sbev_linear_f32(b.x2, w.ffn0_w, w.ffn0_b, nullptr, b.h, p.BQ, c.ffn, D, D, D, c.ffn, 1, stream));
+        TRY(sbev_linear_f32(b.h, w.ffn1_w, w.ffn1_b, b.x2, b.t1, p.BQ, D, c.ffn, c.ffn, c.ffn, D, 0, stream));
+        // norm3 -> x3 is the prologue of the branches' first Linear
+        // classification branch (output only) and regression branch + box refinement (:174-183): two independent chains of small linears
+        TRY(p.grouped ? branches_grouped(layer) : branches_forked(layer));
+        // next layer: query_bbox = bbox_pred.detach() (:93), query_feat = this layer's output
+        bbox = box_of(layer);
+        // x3 is read by the next layer only as `feat` in its third launch and rewritten only by its norm3: no copy
+        feat = b.x3;
+        return SBEV_OK;
+    }
+
+    sbev_linear_problem problem(const float* X, const float* W, const float* bias, float* Y, int N, int relu) const {
+        return sbev_linear_problem{X, W, bias, nullptr, Y, p.BQ, N, D, D, D, N, relu};
+    }
+    // 5 launches for norm3 + the 9 ops of the two branches + refine (+ the next layer's first position-encoder stage):
+    // ops that do not depend on each other share a launch (gemm.hip: group / pair kernels, same arithmetic as alone)
+    int branches_grouped(int layer) {
+        const bool ln_fused = sbev::ln_linear_fusable(p.BQ, D, D);      // norm3 -> x3 as the prologue of the first group launch, else a launch of its own
+        if (!ln_fused) TRY(sbev_layer_norm_f32(b.t1, w.norm3_g, w.norm3_b, eps, nullptr, b.x3, p.BQ, D, 0, stream));
+        const float* x = ln_fused ? b.t1 : b.x3;
+        const sbev_linear_problem g1[2] = {problem(x, w.cls0_w, w.cls0_b, b.c0, D, 0), problem(x, w.reg0_w, w.reg0_b, b.r0, D, 1)};
+        const sbev::LnPrologue norm3{w.norm3_g, w.norm3_b, eps, 0, nullptr, b.x3};
+        TRY(ln_fused ? sbev::launch_linear_group(g1, 2, &norm3, s_main) : sbev_linear_group_f32(g1, 2, stream));
+        TRY(sbev::launch_ln_and_linear(b.c0, w.cls1_g, w.cls1_b, eps, 1, b.c1, p.BQ, D, b.r0, w.reg2_w, w.reg2_b, b.r1, D, D, 1, s_main));
+        const sbev_linear_problem g2[2] = {problem(b.c1, w.cls3_w, w.cls3_b, b.c0, D, 0), problem(b.r1, w.reg4_w, w.reg4_b, b.reg, c.code_size, 0)};
+        TRY(sbev_linear_group_f32(g2, 2, stream));
+        TRY(sbev::launch_ln_and_refine(b.c0, w.cls4_g, w.cls4_b, eps, 1, b.c1, p.BQ, D,
+                                       bbox, b.reg, c.T > 1 ? vel_div : nullptr, box_of(layer), c.Q, c.code_size, s_main));
+        if (layer + 1 == c.num_layers)
+            return sbev_linear_f32(b.c1, w.cls6_w, w.cls6_b, nullptr, cls_of(layer), p.BQ, c.num_classes, D, D, D, c.num_classes, 0, stream);
+        // the next layer's Linear(3->D)+LayerNorm+ReLU only needs this layer's boxes
+        TRY(sbev::launch_linear_and_lin3(b.c1, w.cls6_w, w.cls6_b, cls_of(layer), p.BQ, c.num_classes, D, 0,
+                                         box_of(layer), c.code_size, w.pe0_w, w.pe0_b, w.pe1_g, w.pe1_b, eps, b.t0, D, s_main));
+        pe0_done = true;
+        return SBEV_OK;
+    }
+    // one launch per op; with p.fork the classification branch goes to the aux stream (s_aux == stream unless forked)
+    int branches_forked(int layer) {
+        // norm3 + the classification branch's first Linear on the main stream (x3 is read by both branches) ...
+        TRY(sbev_ln_linear_f32(b.t1, w.norm3_g, w.norm3_b, eps, 0, nullptr, b.x3, w.cls0_w, w.cls0_b, nullptr, b.c0,
+                               p.BQ, D, D, D, D, 0, stream));
+        if (p.fork) TRY(fork_to_aux());      // ... then the rest of it aside
+        TRY(sbev_layer_norm_f32(b.c0, w.cls1_g, w.cls1_b, eps, nullptr, b.c1, p.BQ, D, 1, s_aux));
+        TRY(sbev_linear_f32(b.c1, w.cls3_w, w.cls3_b, nullptr, b.c0, p.BQ, D, D, D, D, D, 0, s_aux));
+        TRY(sbev_layer_norm_f32(b.c0, w.cls4_g, w.cls4_b, eps, nullptr, b.c1, p.BQ, D, 1, s_aux));
+        TRY(sbev_linear_f32(b.c1, w.cls6_w, w.cls6_b, nullptr, cls_of(layer), p.BQ, c.num_classes, D, D, D, c.num_classes, 0, s_aux));
+        if (p.fork) TRY(record_on_aux(&ev_cls));
+        TRY(sbev_linear_f32(b.x3, w.reg0_w, w.reg0_b, nullptr, b.r0, p.BQ, D, D, D, D, D, 1, stream));
+        TRY(sbev_linear_f32(b.r0, w.reg2_w, w.reg2_b, nullptr, b.r1, p.BQ, D, D, D, D, D, 1, stream));
+        TRY(sbev_linear_f32(b.r1, w.reg4_w, w.reg4_b, nullptr, b.reg, p.BQ, c.code_size, D, D, D, c.code_size, 0, stream));
+        return sbev_refine_bbox(bbox, b.reg, c.T > 1 ? vel_div : nullptr, box_of(layer), c.B, c.Q, c.code_size, stream);
+    }
+
+    int run() {
+        for (int l = 0; l < c.L; ++l) {
+            hw[2 * l] = c.hw[l][0];
+            hw[2 * l + 1] = c.hw[l][1];
+            sv[l] = (int64_t)c.hw[l][0] * c.hw[l][1] * D;
+            sbo[l] = sv[l] * c.N;
+        }
+        if (p.chain) TRY(sbev::launch_chain_front(c, w, query_bbox, query_feat, b.x, b.qkvt, eps, s_main));
+        for (int layer = 0; layer < c.num_layers; ++layer) TRY(p.chain ? layer_chain(layer) : layer_ops(layer));
+        return join(ev_cls);      // final join
+    }
+};
+
+}  // namespace
+
 static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decoder_weights* w,
                                 const void* const* feats_nhwc, const float* query_bbox, const float* query_feat,
                                 const float* time_diff, const float* lidar2img, const float* vel_div,
@@ -318,284 +572,26 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
     const sbev::ProfCallScope prof_scope;     // with sbev_profile_stride(n): only every n-th call's launches are bracketed
     Aux& ax = aux();
     const StepPlan p = plan_step(c, *w, lazy != nullptr, ax.ok, read_switches());
-    const int nimg = p.nimg, pgN = p.pgN, mixN = p.mixN, soN = p.soN, splits = p.splits;
-    const int64_t BQ = p.BQ;
-    const bool fork = p.fork, fork_pg = p.fork_pg, chain = p.chain, fused = p.fused;
     SBEV_REQUIRE((((uintptr_t)workspace) & 255) == 0, "sbev_decoder_forward: workspace must be 256-byte aligned");
     SBEV_REQUIRE(cfg->gemm_mode != SBEV_GEMM_BF16X3 || (w->pg_w2 && w->op_w2), "sbev_decoder_forward: gemm_mode bf16x3 needs pg_w2 / op_w2");
-    SBEV_REQUIRE(nimg == 0 || (w->pg_ws && w->op_wp), "sbev_decoder_forward: gemm_mode %d needs pg_ws / op_wp", cfg->gemm_mode);
-    SBEV_REQUIRE(nimg < 4 || (w->pg_wdown && w->op_nscale && w->pg_xscale), "sbev_decoder_forward: gemm_mode %d needs pg_wdown / op_nscale / pg_xscale", cfg->gemm_mode);
-    const int mixed_up = sbev_decoder_mixed_up_log2(cfg);
+    SBEV_REQUIRE(p.nimg == 0 || (w->pg_ws && w->op_wp), "sbev_decoder_forward: gemm_mode %d needs pg_ws / op_wp", cfg->gemm_mode);
+    SBEV_REQUIRE(p.nimg < 4 || (w->pg_wdown && w->op_nscale && w->pg_xscale), "sbev_decoder_forward: gemm_mode %d needs pg_wdown / op_nscale / pg_xscale", cfg->gemm_mode);
     const Buffers b = carve(c, workspace);
     SBEV_REQUIRE((int64_t)b.bytes <= workspace_bytes, "sbev_decoder_forward: workspace too small (%lld < %zu)", (long long)workspace_bytes, b.bytes);
 
-    const int D = c.D, Cg = c.D / c.G, Pin = c.T * c.P;
-    const float eps = 1e-5f;
-
-    // on-demand relayout (sbev_decoder_forward_lazy): feats_nhwc are DESTINATIONS; every layer's point selection marks the units its
-    // points read and one launch behind it moves the marked units that this step has not moved yet (csrc/layout.hip)
-    sbev::LazyPlan lplan{};
+    Step step{c, *w, p, b, feats_nhwc, query_bbox, query_feat, time_diff, lidar2img, vel_div, attn_mask, cls_out, bbox_out, lazy, stream, ax};
     if (lazy) {
-        SBEV_REQUIRE(lazy_plan_of(c, &lplan) && b.touch_need, "sbev_decoder_forward_lazy: config not covered (dense pyramid, 4 groups of 64 channels)");
+        SBEV_REQUIRE(lazy_plan_of(c, &step.lplan) && b.touch_need, "sbev_decoder_forward_lazy: config not covered (dense pyramid, 4 groups of 64 channels)");
         for (int l = 0; l < c.L; ++l)
             SBEV_REQUIRE(feats_nhwc[l] && (((uintptr_t)feats_nhwc[l]) & 15) == 0 &&
                          (lazy->table ? lazy->index[l] >= 0 : (lazy->src[l] && (((uintptr_t)lazy->src[l]) & 15) == 0 && lazy->src[l] != feats_nhwc[l])),
                          "sbev_decoder_forward_lazy: level %d (16-byte aligned NCHW source and NHWC destination)", l);
         SBEV_REQUIRE(!lazy->table || (((uintptr_t)lazy->table) & 7) == 0, "sbev_decoder_forward_lazy: unaligned pointer table");
     }
-    auto lazy_move = [&](int layer) -> int {
-        if (!lazy) return SBEV_OK;
-        return sbev::launch_lazy_relayout(lplan, lazy->table, lazy->index, lazy->src, const_cast<void* const*>(feats_nhwc), c.feat_dtype == SBEV_F32 ? 4 : 2,
-                                          b.touch_need, b.touch_done, layer == 0, layer + 1 == c.num_layers, reinterpret_cast<hipStream_t>(stream));
-    };
-
-    // feature pyramid descriptors: zero-copy NHWC, group g = channel slice [g*Cg, (g+1)*Cg)
-    int32_t hw[2 * SBEV_MAX_LEVELS];
-    int64_t sbo[SBEV_MAX_LEVELS], sv[SBEV_MAX_LEVELS];
-    for (int l = 0; l < c.L; ++l) {
-        hw[2 * l] = c.hw[l][0];
-        hw[2 * l + 1] = c.hw[l][1];
-        sv[l] = (int64_t)c.hw[l][0] * c.hw[l][1] * D;
-        sbo[l] = sv[l] * c.N;
-    }
-
-    hipStream_t s_main = reinterpret_cast<hipStream_t>(stream);
-    sbev_stream_t s_aux = fork ? reinterpret_cast<sbev_stream_t>(ax.stream) : stream;
-    int evi = 0;
-    auto next_ev = [&]() { return ax.ev[(evi++) & 7]; };
-    hipEvent_t ev_cls = nullptr;
-
-    // parameter generator in the 3 x bf16 mode: x1 is split once per layer and streamed past W-stationary strips
-    auto generator_bf16x3 = [&](sbev_stream_t st) -> int {
-        if (!p.pg_strip) return sbev_linear_bf16x3(b.x1, w->pg_w2, w->pg_b, nullptr, b.params, BQ, pgN, D, D, pgN, 0, st);
-        uint16_t* x2 = reinterpret_cast<uint16_t*>(b.x1s);
-        int e = sbev_split_bf16x3_weights(b.x1, x2, BQ, D, st);
-        if (e != SBEV_OK) return e;
-        return sbev_linear_bf16x3_strip(x2, w->pg_w2, w->pg_b, b.params, BQ, pgN, D, pgN, 0, st);
-    };
-
-    SBEV_REQUIRE(nimg == 0 || (sbev_linear_bf16s_gen_ok(BQ, pgN, D) && sbev_linear_bf16s_out_ok(BQ, D, mixN)),
+    SBEV_REQUIRE(p.nimg == 0 || (sbev_linear_bf16s_gen_ok(p.BQ, p.pgN, c.D) && sbev_linear_bf16s_out_ok(p.BQ, c.D, p.mixN)),
                  "sbev_decoder_forward: gemm_mode %d does not cover this shape (rows %lld, generator %d x %d, out-projection %d x %d)",
-                 cfg->gemm_mode, (long long)BQ, pgN, D, D, mixN);
-    // x1 -> image fragments (a launch of its own unless the attention chain wrote them) -> Y = X W^T + b; scan_layer > 0: that layer's
-    // on-demand relayout scan inside the generator
-    auto generator_bf16s = [&](sbev_stream_t st, int scan_layer = -1) -> int {
-        uint16_t* xs = reinterpret_cast<uint16_t*>(b.x1s);
-        if (p.pack_launch) {
-            // fp16 hi + lo: x1 scaled by one power of two (its maximum -> [2^14, 2^15))
-            // (the power of two comes with the weights: norm1's output is bounded by sqrt(D - 1) max|gamma| + max|beta| -- no pass for a maximum)
-            int e = nimg >= 4 ? sbev_pack_f16s_frags(b.x1, D, xs, const_cast<float*>(w->pg_xscale), (int)BQ, D, 2, st)
-                              : sbev_pack_bf16s_frags(b.x1, D, xs, (int)BQ, D, nimg, st);
-            if (e != SBEV_OK) return e;
-        }
-        auto gen = [&](const sbev::LazyScan* lz) {
-            return sbev::linear_gen_split(xs, w->pg_xscale, w->pg_ws, w->pg_wdown, w->pg_b, b.params, BQ, pgN, D, pgN, 0, nimg, p.gen_ws, lz,
-                                          reinterpret_cast<hipStream_t>(st));
-        };
-        if (scan_layer <= 0) return gen(nullptr);
-        const sbev::LazyScan lz{&lplan, lazy->table, lazy->index, lazy->src, const_cast<void* const*>(feats_nhwc), c.feat_dtype == SBEV_F32 ? 4 : 2,
-                                b.touch_need, b.touch_done, scan_layer + 1 == c.num_layers};
-        return gen(&lz);
-    };
-
-    // the mixing launches: in the fp16 GEMM modes their epilogue leaves `mixed` as (fp16 hi, fp16 lo) pairs of mixed 2^mixed_up -- the
-    // out-projection's operand, split once per element where the VALU is idle instead of inside the GEMM
-    auto mix_fused = [&](sbev_stream_t st, const int32_t* order = nullptr) -> int {
-        if (nimg >= 4)
-            return sbev_sample_mix_pairs_f16_ordered(feats_nhwc, hw, c.L, c.feat_dtype, c.B, c.N, c.Q, c.T, c.G, c.P, Cg, sbo, Cg, sv, D, b.loc, b.wbp,
-                                                     c.n_slots > 0 ? c.frame_slots : nullptr, c.n_slots, b.params, b.mixed, c.out_points, eps, mixed_up,
-                                                     order, st);
-        return sbev_sample_mix_f32_ordered(feats_nhwc, hw, c.L, c.feat_dtype, c.B, c.N, c.Q, c.T, c.G, c.P, Cg, sbo, Cg, sv, D, b.loc, b.wbp,
-                                           c.n_slots > 0 ? c.frame_slots : nullptr, c.n_slots, b.params, b.mixed, c.out_points, eps, order, st);
-    };
-    auto mix_plain = [&](sbev_stream_t st) -> int {
-        if (nimg >= 4) return sbev_adaptive_mixing_pairs_f16(b.sampled, b.params, b.mixed, BQ, c.G, Pin, Cg, c.out_points, eps, mixed_up, st);
-        return sbev_adaptive_mixing_f32(b.sampled, b.params, b.mixed, BQ, c.G, Pin, Cg, c.out_points, eps, st);
-    };
-
-    const float* bbox = query_bbox;
-    const float* feat = query_feat;
-    bool pe0_done = false;             // the previous layer's tail already ran this layer's first position-encoder stage
-    // Row chains (row_chain.hip): 6 launches per layer instead of 17
-    if (chain) TRY(sbev::launch_chain_front(c, *w, query_bbox, query_feat, b.x, b.qkvt, eps, s_main));
-    for (int layer = 0; layer < c.num_layers; ++layer) {
-        float* cls_l = cls_out + (int64_t)layer * BQ * c.num_classes;
-        float* box_l = bbox_out + (int64_t)layer * BQ * c.code_size;
-        if (chain) {
-            if (p.order_mode != 0 && (layer == 0 || p.order_mode == 1)) TRY(sbev_query_order(bbox, c.code_size, c.pc_range, c.B, c.Q, b.order, stream));
-            TRY(sbev_sasa_f32(b.qkvt, c.attn_in_rows, bbox, c.pc_range, attn_mask, b.att, c.B, c.Q, c.H, D / c.H, stream));
-            // (fp16 GEMM modes: the chain also leaves x1 as the generator's fragment operand -- no pack launch)
-            TRY(sbev::launch_chain_attn(c, *w, b.att, b.x, b.x1, bbox, time_diff, lidar2img, b.loc, b.wbp, eps, s_main,
-                                        nimg >= 4 ? reinterpret_cast<uint16_t*>(b.x1s) : nullptr, nimg >= 4 ? w->pg_xscale : nullptr, b.pair_sync,
-                                        lazy ? &lplan : nullptr, lazy ? b.touch_need : nullptr));
-            const bool ride = p.scan_in_gen && layer > 0;
-            if (!ride) TRY(lazy_move(layer));      // (layer 0's move behind the generator instead of in front of it: measured equal, 537-539 both ways)
-            if (nimg)
-                TRY(generator_bf16s(stream, ride ? layer : -1));
-            else if (c.gemm_mode == SBEV_GEMM_BF16X3)
-                TRY(generator_bf16x3(stream));
-            else
-                TRY(sbev_linear_f32(b.x1, w->pg_w, w->pg_b, nullptr, b.params, BQ, pgN, D, D, D, pgN, 0, stream));
-            if (fused) {
-                TRY(mix_fused(stream, p.order_mode != 0 ? b.order : nullptr));
-            } else {
-                if (c.n_slots > 0)
-                    TRY(sbev_msmv_fwd_ring(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
-                                           c.G, sbo, Cg, sv, D, b.loc, b.wbp, b.sampled, SBEV_OUT_MIX, c.T, c.G, c.frame_slots, c.n_slots, stream));
-                else
-                    TRY(sbev_msmv_fwd(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
-                                      c.G, sbo, Cg, sv, D, b.loc, b.wbp, b.sampled, SBEV_OUT_MIX, c.T, c.G, stream));
-                TRY(mix_plain(stream));
-            }
-            int used = 0;
-            bool folded = false;      // the out-projection folded its slabs inside its launch: the tail reads ONE row block, b.folded
-            // (the fold needs the fault word to report a row tile that never completed)
-            const bool fold = p.fold_wanted && sbev::out_fold_shape_ok(BQ, mixN) && sbev::chain_fault_word_ready();
-            if (nimg)
-                TRY(sbev::launch_splitk_slabs_bf16s(b.mixed, w->op_wp, BQ, mixN, mixN, nimg, b.slabs, &used, s_main, p.out8_min_rows, mixed_up, w->op_nscale,
-                                                    nimg >= 4, nullptr, fold ? b.pair_sync + sbev::chain_fold_sync_offset(BQ) : nullptr,
-                                                    fold ? b.folded : nullptr, &folded));
-            else if (c.gemm_mode == SBEV_GEMM_BF16X3)
-                TRY(sbev::launch_splitk_slabs_bf16x3(b.mixed, w->op_w2, BQ, D, mixN, mixN, splits, b.slabs, &used, s_main));
-            else
-                TRY(sbev::launch_splitk_slabs(b.mixed, w->op_w, BQ, D, mixN, mixN, mixN, splits, b.slabs, &used, s_main));
-            TRY(sbev::launch_chain_tail(c, *w, folded ? b.folded : b.slabs, used, b.x1, bbox, c.T > 1 ? vel_div : nullptr, b.x3, cls_l, box_l,
-                                        layer + 1 < c.num_layers, b.x, b.qkvt, eps, s_main, b.pair_x, b.pair_sync));
-            bbox = box_l;
-            continue;
-        }
-        // position encoder -> x = feat + pos                                   (sparsebev_transformer.py:166-167)
-        if (!pe0_done) TRY(sbev_linear3_ln_relu_f32(bbox, layer == 0 ? 10 : c.code_size, w->pe0_w, w->pe0_b, w->pe1_g, w->pe1_b, eps, b.t0, BQ, D, stream));
-        pe0_done = false;
-        TRY(sbev_linear_f32(b.t0, w->pe3_w, w->pe3_b, nullptr, b.t1, BQ, D, D, D, D, D, 0, stream));
-        // Three of the layer's LayerNorms run as the PROLOGUE of the small-tile Linear that consumes them
-        // (sbev_ln_linear_f32: one launch instead of two, the normalised rows are stored for the other readers):
-        // here the position encoder's last norm (+ ReLU, + query_feat) -> x, with the attention in-projection
-        TRY(sbev_ln_linear_f32(b.t1, w->pe4_g, w->pe4_b, eps, 1, feat, b.x, w->attn_in_w, w->attn_in_b, nullptr, b.qkvt,
-                               BQ, c.attn_in_rows, D, D, c.attn_in_rows, 0, stream));
-        // scale-adaptive self attention                                         (:169)
-        TRY(sbev_sasa_f32(b.qkvt, c.attn_in_rows, bbox, c.pc_range, attn_mask, b.att, c.B, c.Q, c.H, D / c.H, stream));
-        TRY(sbev_linear_f32(b.att, w->attn_out_w, w->attn_out_b, b.x, b.t1, BQ, D, D, D, D, D, 0, stream));
-        // norm1 -> x1, with the Linear of the sampling offsets / level logits      (:169-170)
-        TRY(sbev_ln_linear_f32(b.t1, w->norm1_g, w->norm1_b, eps, 0, nullptr, b.x1, w->samp_w, w->samp_b, nullptr, b.so,
-                               BQ, soN, D, D, soN, 0, stream));
-        // fork: parameter generator (needs only x1) on the aux stream, beside the sampling chain
-        hipEvent_t ev_pg = nullptr;
-        if (fork_pg) {
-            hipEvent_t e = next_ev();
-            TRY(hip_ok(hipEventRecord(e, s_main), "hipEventRecord"));
-            TRY(hip_ok(hipStreamWaitEvent(ax.stream, e, 0), "hipStreamWaitEvent"));
-        }
-        if (nimg)
-            TRY(generator_bf16s(fork_pg ? s_aux : stream));
-        else if (c.gemm_mode == SBEV_GEMM_BF16X3)
-            TRY(generator_bf16x3(fork_pg ? s_aux : stream));
-        else
-            TRY(sbev_linear_f32(b.x1, w->pg_w, w->pg_b, nullptr, b.params, BQ, pgN, D, D, D, pgN, 0, fork_pg ? s_aux : stream));
-        if (fork_pg) {
-            ev_pg = next_ev();
-            TRY(hip_ok(hipEventRecord(ev_pg, ax.stream), "hipEventRecord"));
-        }
-        // adaptive spatio-temporal sampling                                     (:170)
-        TRY(sbev::launch_sample_and_project(bbox, b.so, soN, b.so + c.G * c.P * 3, soN, time_diff, lidar2img, c.pc_range,
-                                            c.B, c.Q, c.T, c.N, c.G, c.P, c.L, c.image_h, c.image_w, c.eps_homo, b.loc, b.wbp,
-                                            lazy ? &lplan : nullptr, lazy ? b.touch_need : nullptr, c.hw, s_main));
-        TRY(lazy_move(layer));
-        // gather + adaptive mixing: one launch (fused) or the sampler followed by the mixing kernel
-        if (!fused) {
-            if (c.n_slots > 0)
-                TRY(sbev_msmv_fwd_ring(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
-                                       c.G, sbo, Cg, sv, D, b.loc, b.wbp, b.sampled, SBEV_OUT_MIX, c.T, c.G, c.frame_slots, c.n_slots, stream));
-            else
-                TRY(sbev_msmv_fwd(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
-                                  c.G, sbo, Cg, sv, D, b.loc, b.wbp, b.sampled, SBEV_OUT_MIX, c.T, c.G, stream));
-        }
-        // adaptive mixing + norm2 (join: the generator's output is needed now)  (:171)
-        if (fork_pg) TRY(hip_ok(hipStreamWaitEvent(s_main, ev_pg, 0), "hipStreamWaitEvent"));
-        if (fused)
-            TRY(mix_fused(stream));
-        else
-            TRY(mix_plain(stream));
-        if (nimg >= 4)
-            TRY(sbev_linear_splitk_f16s(b.mixed, 1, mixed_up, w->op_wp, w->op_nscale, w->op_b, b.x1, w->norm2_g, w->norm2_b, eps, b.x2, BQ, D, mixN, mixN,
-                                        0, nimg - 1, b.slabs, stream));
-        else if (nimg)
-            TRY(sbev_linear_splitk_bf16s(b.mixed, w->op_wp, w->op_b, b.x1, w->norm2_g, w->norm2_b, eps, b.x2, BQ, D, mixN, mixN,
-                                         0, nimg, b.slabs, stream));
-        else if (c.gemm_mode == SBEV_GEMM_BF16X3)
-            TRY(sbev_linear_splitk_bf16x3(b.mixed, w->op_w2, w->op_b, b.x1, w->norm2_g, w->norm2_b, eps, b.x2, BQ, D, mixN, mixN,
-                                          0, splits, b.slabs, stream));
-        else
-            TRY(sbev_linear_splitk_f32(b.mixed, w->op_w, w->op_b, b.x1, w->norm2_g, w->norm2_b, eps, b.x2, BQ, D, mixN, mixN, mixN,
-                                       0, splits, b.slabs, stream));
-        // (the previous layer's classification branch still reads x3 on the aux stream: join before x3 is rewritten)
-        if (fork && ev_cls) TRY(hip_ok(hipStreamWaitEvent(s_main, ev_cls, 0), "hipStreamWaitEvent"));
-        // FFN + norm3                                                           (:172)
-        TRY(sbev_linear_f32(b.x2, w->ffn0_w, w->ffn0_b, nullptr, b.h, BQ, c.ffn, D, D, D, c.ffn, 1, stream));
-        TRY(sbev_linear_f32(b.h, w->ffn1_w, w->ffn1_b, b.x2, b.t1, BQ, D, c.ffn, c.ffn, c.ffn, D, 0, stream));
-        // norm3 -> x3 is the prologue of the branches' first Linear (below)
-        // classification branch (output only) on the aux stream; regression branch + box refinement on the main one (:174-183)
-        // the two branches are independent chains of small linears: each level of them shares one grouped launch
-        // (with `fork` the classification branch goes to the aux stream instead)
-        auto prob = [&](const float* X, const float* W, const float* bias, float* Y, int N, int relu) {
-            return sbev_linear_problem{X, W, bias, nullptr, Y, BQ, N, D, D, D, N, relu};
-        };
-        const bool grouped = p.grouped;
-        const sbev::LnPrologue norm3{w->norm3_g, w->norm3_b, eps, 0, nullptr, b.x3};
-        if (grouped) {
-            // 5 launches for norm3 + the 9 ops of the two branches + refine (+ the next layer's first position-encoder stage):
-            // ops that do not depend on each other share a launch (gemm.hip: group / pair kernels, same arithmetic as alone)
-            const sbev_linear_problem g1[2] = {prob(b.t1, w->cls0_w, w->cls0_b, b.c0, D, 0), prob(b.t1, w->reg0_w, w->reg0_b, b.r0, D, 1)};
-            if (sbev::ln_linear_fusable(BQ, D, D)) {
-                TRY(sbev::launch_linear_group(g1, 2, &norm3, s_main));
-            } else {
-                TRY(sbev_layer_norm_f32(b.t1, w->norm3_g, w->norm3_b, eps, nullptr, b.x3, BQ, D, 0, stream));
-                const sbev_linear_problem g1x[2] = {prob(b.x3, w->cls0_w, w->cls0_b, b.c0, D, 0), prob(b.x3, w->reg0_w, w->reg0_b, b.r0, D, 1)};
-                TRY(sbev_linear_group_f32(g1x, 2, stream));
-            }
-            TRY(sbev::launch_ln_and_linear(b.c0, w->cls1_g, w->cls1_b, eps, 1, b.c1, BQ, D,
-                                           b.r0, w->reg2_w, w->reg2_b, b.r1, D, D, 1, s_main));
-            const sbev_linear_problem g2[2] = {prob(b.c1, w->cls3_w, w->cls3_b, b.c0, D, 0),
-                                               prob(b.r1, w->reg4_w, w->reg4_b, b.reg, c.code_size, 0)};
-            TRY(sbev_linear_group_f32(g2, 2, stream));
-            TRY(sbev::launch_ln_and_refine(b.c0, w->cls4_g, w->cls4_b, eps, 1, b.c1, BQ, D,
-                                           bbox, b.reg, c.T > 1 ? vel_div : nullptr, box_l, c.Q, c.code_size, s_main));
-            if (layer + 1 < c.num_layers) {   // the next layer's Linear(3->D)+LayerNorm+ReLU only needs box_l
-                TRY(sbev::launch_linear_and_lin3(b.c1, w->cls6_w, w->cls6_b, cls_l, BQ, c.num_classes, D, 0,
-                                                 box_l, c.code_size, w->pe0_w, w->pe0_b, w->pe1_g, w->pe1_b, eps, b.t0, D, s_main));
-                pe0_done = true;
-            } else {
-                TRY(sbev_linear_f32(b.c1, w->cls6_w, w->cls6_b, nullptr, cls_l, BQ, c.num_classes, D, D, D, c.num_classes, 0, stream));
-            }
-        } else {   // s_aux == stream unless forked
-            // norm3 + the classification branch's first Linear on the main stream (x3 is read by both branches) ...
-            TRY(sbev_ln_linear_f32(b.t1, w->norm3_g, w->norm3_b, eps, 0, nullptr, b.x3, w->cls0_w, w->cls0_b, nullptr, b.c0,
-                                   BQ, D, D, D, D, 0, stream));
-            if (fork) {   // ... then the rest of it aside
-                hipEvent_t e = next_ev();
-                TRY(hip_ok(hipEventRecord(e, s_main), "hipEventRecord"));
-                TRY(hip_ok(hipStreamWaitEvent(ax.stream, e, 0), "hipStreamWaitEvent"));
-            }
-            TRY(sbev_layer_norm_f32(b.c0, w->cls1_g, w->cls1_b, eps, nullptr, b.c1, BQ, D, 1, s_aux));
-            TRY(sbev_linear_f32(b.c1, w->cls3_w, w->cls3_b, nullptr, b.c0, BQ, D, D, D, D, D, 0, s_aux));
-            TRY(sbev_layer_norm_f32(b.c0, w->cls4_g, w->cls4_b, eps, nullptr, b.c1, BQ, D, 1, s_aux));
-            TRY(sbev_linear_f32(b.c1, w->cls6_w, w->cls6_b, nullptr, cls_l, BQ, c.num_classes, D, D, D, c.num_classes, 0, s_aux));
-            if (fork) {
-                ev_cls = next_ev();
-                TRY(hip_ok(hipEventRecord(ev_cls, ax.stream), "hipEventRecord"));
-            }
-            TRY(sbev_linear_f32(b.x3, w->reg0_w, w->reg0_b, nullptr, b.r0, BQ, D, D, D, D, D, 1, stream));
-            TRY(sbev_linear_f32(b.r0, w->reg2_w, w->reg2_b, nullptr, b.r1, BQ, D, D, D, D, D, 1, stream));
-            TRY(sbev_linear_f32(b.r1, w->reg4_w, w->reg4_b, nullptr, b.reg, BQ, c.code_size, D, D, D, c.code_size, 0, stream));
-        }
-        if (!grouped) TRY(sbev_refine_bbox(bbox, b.reg, c.T > 1 ? vel_div : nullptr, box_l, c.B, c.Q, c.code_size, stream));
-        // next layer: query_bbox = bbox_pred.detach() (:93), query_feat = this layer's output
-        bbox = box_l;
-        // x3 is read by the next layer only as `feat` in its third launch and rewritten only by its norm3: no copy
-        feat = b.x3;
-    }
-    if (fork && ev_cls) TRY(hip_ok(hipStreamWaitEvent(s_main, ev_cls, 0), "hipStreamWaitEvent"));   // final join
-    return SBEV_OK;
+                 cfg->gemm_mode, (long long)p.BQ, p.pgN, c.D, c.D, p.mixN);
+    return step.run();
 }
 
 extern "C" int sbev_decoder_forward(const sbev_decoder_config* cfg, const sbev_decoder_weights* w,

@@ -1,6 +1,9 @@
 """Python face of the C++ decoder runtime (csrc/decoder.hip): one ctypes call enqueues the whole 6-layer
 forward.  Mirrors include/sbev_hip.h's sbev_decoder_config / sbev_decoder_weights field for field."""
 import ctypes
+import math
+import os
+import warnings
 
 import torch
 
@@ -50,7 +53,6 @@ class DecoderRuntime:
     Re-binds automatically when a parameter is replaced or modified in place (``_version`` / ``data_ptr`` change)."""
 
     def __init__(self, decoder, gemm_mode=0, overlap=False):
-        import os
         if os.environ.get('SBEV_NO_SAMPLE_MIX') == '1':
             fuse_sample_mix(False)
         if os.environ.get('SBEV_NO_ROW_CHAIN') == '1':
@@ -112,6 +114,7 @@ class DecoderRuntime:
             attn_in_b = torch.cat([att.in_proj_bias, sa.gen_tau.bias] + ([att.in_proj_bias.new_zeros(pad)] if pad else []), 0).contiguous()
             samp_w = torch.cat([smp.sampling_offset.weight, smp.scale_weights.weight], 0).contiguous()
             samp_b = torch.cat([smp.sampling_offset.bias, smp.scale_weights.bias], 0).contiguous()
+        self._attn_in_rows = attn_in_w.shape[0]
         cb, rb, ffn = layer.cls_branch, layer.reg_branch, layer.ffn.layers
         t = dict(
             pe0_w=pe[0].weight, pe0_b=pe[0].bias, pe1_g=pe[1].weight, pe1_b=pe[1].bias,
@@ -131,7 +134,6 @@ class DecoderRuntime:
         keep = {k: v.detach().contiguous() for k, v in t.items()}
         self.mode_eff = self.gemm_mode      # what the launches run in: an fp16 mode falls back to the exact kernels when norm1 is unfit (below)
         if self.gemm_mode in (GEMM_F16X3, GEMM_F16X4):
-            import math
             # The generator's input is norm1's output; its fp16 scale is fixed per bind from |LayerNorm(x) g + b| <= sqrt(D - 1) max|g| +
             # max|b| (no pass over the activations).  ONE power of two serves the whole tensor, so a channel whose |g| sits far below the
             # largest one lives that many binades under the fp16 range's top: hi stays normal down to 2^-29 of the bound, lo down to 2^-17.
@@ -145,7 +147,6 @@ class DecoderRuntime:
             if not (self.f16_headroom_log2 <= F16_MAX_HEADROOM_LOG2):
                 self.mode_eff = GEMM_F32
                 if not getattr(DecoderRuntime, '_warned_f16_bound', False):
-                    import warnings
                     warnings.warn('sparsebev_amd: norm1 puts typical generator inputs %.1f binades below the a-priori fp16 scale bound '
                                   '(max|gamma| %.3g, median|gamma| %.3g, max|beta| %.3g; limit %d): the two mixing GEMMs run on the exact f32 '
                                   'kernels instead of %s' % (self.f16_headroom_log2, gmax, gmed, bmax, F16_MAX_HEADROOM_LOG2,
@@ -185,11 +186,7 @@ class DecoderRuntime:
         # lane-ordered image of the small Linears' weights for the row-chain kernels (csrc/row_chain.hip), where they cover
         # the layer's shape; re-made with every re-bind
         lib = _lib.load()
-        cfg = DecoderConfig()
-        cfg.B = cfg.Q = 1
-        cfg.T, cfg.N, cfg.G, cfg.P, cfg.L = smp.num_frames, 6, smp.num_groups, smp.num_points, smp.num_levels
-        cfg.D, cfg.H, cfg.ffn = D, H, ffn[0][0].weight.shape[0]
-        cfg.num_classes, cfg.code_size, cfg.attn_in_rows = layer.num_classes, layer.code_size, attn_in_w.shape[0]
+        cfg = self._config(1, 1)            # (the pack depends on the layer's sizes only, not on the rows of a call)
         n_pack = lib.sbev_decoder_chain_pack_floats(ctypes.byref(cfg))
         if n_pack > 0:
             pack = torch.empty(n_pack, device=attn_in_w.device, dtype=torch.float32)
@@ -200,33 +197,30 @@ class DecoderRuntime:
                 w.chain_pack = pack.data_ptr()
             elif not getattr(DecoderRuntime, '_warned_chain', False):
                 # e.g. a device without 160 KB of LDS per workgroup: the op-by-op launches compute the same layer
-                import warnings
                 warnings.warn('sparsebev_amd: row-chain weight image unavailable (%s): running the op-by-op launches'
                               % lib.sbev_last_error().decode('utf-8', 'replace'))
                 DecoderRuntime._warned_chain = True
         self._keep, self._weights = keep, w
-        self._attn_in_rows = attn_in_w.shape[0]
 
-    # -- forward -----------------------------------------------------------------------------------------
-    def _prepare(self, query_bbox, query_feat, pyramid, ctx, attn_mask, own_workspace=False):
-        sig = self._ensure_bound()
+    def _config(self, B, Q, pyramid=None, ctx=None):
+        """The sbev_decoder_config of a [B, Q] call with the bound weights; with ``pyramid`` and ``ctx`` also what a forward reads of
+        them (feature dtype and sizes, the frame ring's slots, image size, pc_range)."""
         dec, layer = self.decoder, self.decoder.decoder_layer
         smp = layer.sampling
-        B, Q, D = query_feat.shape
-        dev = query_feat.device
         cfg = DecoderConfig()
         cfg.B, cfg.Q, cfg.T, cfg.N, cfg.G, cfg.P, cfg.L = B, Q, smp.num_frames, 6, smp.num_groups, smp.num_points, smp.num_levels
-        cfg.D, cfg.H, cfg.ffn = D, layer.self_attn.num_heads, layer.ffn.layers[0][0].weight.shape[0]
+        cfg.D, cfg.H, cfg.ffn = layer.embed_dims, layer.self_attn.num_heads, layer.ffn.layers[0][0].weight.shape[0]
         cfg.num_classes, cfg.code_size, cfg.num_layers = layer.num_classes, layer.code_size, dec.num_layers
         cfg.out_points, cfg.attn_in_rows = layer.mixing.out_points, self._attn_in_rows
+        cfg.gemm_mode, cfg.overlap = self.mode_eff, int(self.overlap)
+        if pyramid is None:
+            return cfg
         cfg.feat_dtype = {torch.bfloat16: 1, torch.float16: 2}.get(pyramid.levels[0].dtype, 0)
-        cfg.gemm_mode = self.mode_eff
         slots = getattr(pyramid, 'frame_slots', None)
         if slots is not None:
             cfg.n_slots = pyramid.n_slots
             for t, sl in enumerate(slots):
                 cfg.frame_slots[t] = int(sl)
-        cfg.overlap = int(self.overlap)
         if len(pyramid.levels) != cfg.L or pyramid.T != cfg.T or pyramid.B != B:
             raise RuntimeError('feature pyramid (L=%d, T=%d, B=%d) does not match the decoder config (L=%d, T=%d, B=%d)'
                                % (len(pyramid.levels), pyramid.T, pyramid.B, cfg.L, cfg.T, B))
@@ -235,6 +229,21 @@ class DecoderRuntime:
         cfg.image_h, cfg.image_w, cfg.eps_homo = float(ctx.image_h), float(ctx.image_w), 1e-5
         for i, v in enumerate(dec.pc_range):
             cfg.pc_range[i] = float(v)
+        return cfg
+
+    def _finished(self, cls, box, stream):
+        """(cls, box) nan_to_num'ed into new tensors by one more launch (sbev_finish_outputs)"""
+        cls_o, box_o = torch.empty_like(cls), torch.empty_like(box)
+        _lib.check(_lib.load().sbev_finish_outputs(_ptr(cls), _ptr(box), _ptr(cls_o), _ptr(box_o), cls.numel(), box.numel(), stream), 'sbev_finish_outputs')
+        return cls_o, box_o
+
+    # -- forward -----------------------------------------------------------------------------------------
+    def _prepare(self, query_bbox, query_feat, pyramid, ctx, attn_mask, own_workspace=False):
+        sig = self._ensure_bound()
+        B, Q, D = query_feat.shape
+        dev = query_feat.device
+        cfg = self._config(B, Q, pyramid, ctx)
+        cfg.D = D                           # the queries' own width: the library refuses one that does not fit the layer
         lib = _lib.load()
         need = lib.sbev_decoder_workspace_bytes(ctypes.byref(cfg))
         if need < 0:
@@ -271,14 +280,7 @@ class DecoderRuntime:
     def launches_per_layer(self, B, Q):
         """What sbev_decoder_forward would enqueue per layer for a [B, Q] call with the bound weights (asks the library)."""
         self._ensure_bound()
-        dec, layer = self.decoder, self.decoder.decoder_layer
-        smp = layer.sampling
-        cfg = DecoderConfig()
-        cfg.B, cfg.Q, cfg.T, cfg.N, cfg.G, cfg.P, cfg.L = B, Q, smp.num_frames, 6, smp.num_groups, smp.num_points, smp.num_levels
-        cfg.D, cfg.H, cfg.ffn = layer.embed_dims, layer.self_attn.num_heads, layer.ffn.layers[0][0].weight.shape[0]
-        cfg.num_classes, cfg.code_size, cfg.num_layers = layer.num_classes, layer.code_size, dec.num_layers
-        cfg.out_points, cfg.attn_in_rows = layer.mixing.out_points, self._attn_in_rows
-        cfg.gemm_mode, cfg.overlap = self.mode_eff, int(self.overlap)
+        cfg = self._config(B, Q)
         return int(_lib.load().sbev_decoder_launches_per_layer(ctypes.byref(cfg), ctypes.byref(self._weights)))
 
     def forward(self, query_bbox, query_feat, pyramid, ctx, attn_mask=None, finish=False):
@@ -291,11 +293,7 @@ class DecoderRuntime:
         lib = _lib.load()
         st = lib.sbev_decoder_forward(*args, stream)
         _lib.check(st, 'sbev_decoder_forward')
-        if finish:
-            cls_o, box_o = torch.empty_like(cls), torch.empty_like(box)
-            _lib.check(lib.sbev_finish_outputs(_ptr(cls), _ptr(box), _ptr(cls_o), _ptr(box_o), cls.numel(), box.numel(), stream), 'sbev_finish_outputs')
-            return cls_o, box_o
-        return cls, box
+        return self._finished(cls, box, stream) if finish else (cls, box)
 
     def lazy_ok(self, mlvl_feats):
         """whether a feature LIST qualifies for the on-demand relayout of the eager step: the switch is on, every level is a contiguous,
@@ -326,9 +324,7 @@ class DecoderRuntime:
         st = lib.sbev_decoder_forward_lazy(args[0], args[1], args[2], ctypes.byref(lz), *args[3:], stream)
         _lib.check(st, 'sbev_decoder_forward_lazy')
         if finish:
-            cls_o, box_o = torch.empty_like(cls), torch.empty_like(box)
-            _lib.check(lib.sbev_finish_outputs(_ptr(cls), _ptr(box), _ptr(cls_o), _ptr(box_o), cls.numel(), box.numel(), stream), 'sbev_finish_outputs')
-            return cls_o, box_o, pyramid
+            cls, box = self._finished(cls, box, stream)
         return cls, box, pyramid
 
     def capture(self, query_bbox, query_feat, pyramid, ctx, attn_mask=None):

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import load_golden, runtime_op_by_op, free_running_bound, report_free_running
+from conftest import load_golden, op_by_op_runtime, runtime_op_by_op, free_running_bound, report_free_running
 from sparsebev_amd import synthetic as S
 from sparsebev_amd.transformer import SparseBEVTransformer, FeaturePyramid, DecoderContext
 
@@ -327,6 +327,37 @@ def test_captured_graph_replays_bit_identically_and_follows_in_place_updates():
     graph.destroy()
     with pytest.raises(RuntimeError):
         graph.replay()
+
+
+@pytest.mark.parametrize('overlap', [1, 2])
+def test_forked_step_equals_the_single_stream_step_eager_and_replayed(overlap):
+    """``overlap`` 1 (generator GEMM + classification branch on the aux stream) and 2 (classification branch only): the forked
+    step enqueues the op-by-op launches across two streams with event forks / joins, so it must reproduce the single-stream
+    op-by-op step (overlap 0 with the row chains off; its grouped tail launches compute the same arithmetic as the ops alone)
+    bit for bit -- eager, and replayed from a captured graph with two parallel branches.  (Measured before the enqueue was split
+    into per-stage functions: max |difference| 0.0 for both outputs at overlap 1 and 2, so equality is what is asserted.)"""
+    from sparsebev_amd.runtime import DecoderRuntime
+    B, Q, T, L = 1, 64, 4, 4
+    ih, iw, sizes = S.PYRAMIDS['tiny']
+    model = build(T, L, 41)
+    metas = S.make_img_metas(B, T, ih, iw)
+    feats = [f.to(DEV) for f in S.make_features(B, T, sizes, seed=42)]
+    pyr, ctx = FeaturePyramid(feats), DecoderContext(metas, B, torch.device(DEV))
+    bbox, feat = [t.to(DEV) for t in S.make_queries(B, Q, seed=43)]
+    with op_by_op_runtime():
+        single = DecoderRuntime(model.decoder, overlap=0)
+        ref = [t.clone() for t in single.forward(bbox, feat, pyr, ctx)]
+        forked = DecoderRuntime(model.decoder, overlap=overlap)
+        eager = [t.clone() for t in forked.forward(bbox, feat, pyr, ctx)]
+        graph = DecoderRuntime(model.decoder, overlap=overlap).capture(bbox.clone(), feat.clone(), pyr, ctx)
+    assert graph.num_nodes >= 6 * 17
+    torch.cuda.synchronize()
+    print('overlap %d vs 0: max|cls| %.3e max|bbox| %.3e' % (overlap, (eager[0] - ref[0]).abs().max().item(), (eager[1] - ref[1]).abs().max().item()))
+    assert torch.equal(eager[0], ref[0]) and torch.equal(eager[1], ref[1])
+    for _ in range(2):
+        cls, box = graph.replay()
+        assert torch.equal(cls, eager[0]) and torch.equal(box, eager[1])
+    graph.destroy()
 
 
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
