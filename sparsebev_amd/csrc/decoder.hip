@@ -150,6 +150,22 @@ inline int hip_ok(hipError_t e, const char* what) {
     return SBEV_ELAUNCH;
 }
 
+// The config's feature pyramid as the samplers' description: zero-copy NHWC levels [B*T*N, H, W, D] (or the ring's [B*n_slots*N, ...]),
+// group g = channel slice [g*Cg, (g+1)*Cg); sample points loc / weights of all B*T*G sample batches
+struct ConfigPyramid {
+    int64_t sbo[SBEV_MAX_LEVELS], sv[SBEV_MAX_LEVELS];
+    sbev::PyramidDesc d;
+    ConfigPyramid(const sbev_decoder_config& c, const void* const* feats, const float* loc, const float* weights)
+        : d{feats, &c.hw[0][0], c.L, c.feat_dtype, c.N, c.D / c.G, c.Q, c.P, c.G, sbo, c.D / c.G, sv, c.D, loc, weights,
+            c.n_slots > 0 ? c.frame_slots : nullptr, c.n_slots} {
+        for (int l = 0; l < c.L; ++l) {
+            sv[l] = (int64_t)c.hw[l][0] * c.hw[l][1] * c.D;
+            sbo[l] = sv[l] * c.N;
+        }
+    }
+    ConfigPyramid(const ConfigPyramid&) = delete;      // (d points into this object)
+};
+
 #define TRY(expr)                 \
     do {                          \
         int st__ = (expr);        \
@@ -171,14 +187,8 @@ struct ProfCallScope {      // see sbev_profile_stride below
 static bool sample_mix_fusable(const sbev_decoder_config& c, bool fuse_l5_f32) {
     if (sbev_sample_mix_supported(c.L, c.D / c.G, c.P, c.T, c.G, c.G) == 0) return false;
     if (c.L == 5 && c.feat_dtype == SBEV_F32 && !fuse_l5_f32) return false;
-    int32_t hw[2 * SBEV_MAX_LEVELS];
-    int64_t sv[SBEV_MAX_LEVELS];
-    for (int l = 0; l < c.L; ++l) {
-        hw[2 * l] = c.hw[l][0];
-        hw[2 * l + 1] = c.hw[l][1];
-        sv[l] = (int64_t)c.hw[l][0] * c.hw[l][1] * c.D;
-    }
-    return sbev_sample_mix_slabs_ok(hw, c.L, c.feat_dtype, c.N, c.D / c.G, sv, c.D) != 0;
+    const ConfigPyramid py(c, nullptr, nullptr, nullptr);
+    return sbev_sample_mix_slabs_ok(py.d.hw, py.d.L, py.d.feat_dtype, py.d.N, py.d.C, py.d.stride_v, py.d.stride_px) != 0;
 }
 
 // The one reader of the process-wide switches: a step is planned from ONE reading, so a switch toggled while a step is being enqueued
@@ -319,9 +329,7 @@ struct Step {
     sbev_stream_t s_aux = p.fork ? reinterpret_cast<sbev_stream_t>(ax.stream) : stream;
     int evi = 0;                     // next event of ax.ev
     sbev::LazyPlan lplan{};
-    // feature pyramid descriptors: zero-copy NHWC, group g = channel slice [g*Cg, (g+1)*Cg)
-    int32_t hw[2 * SBEV_MAX_LEVELS];
-    int64_t sbo[SBEV_MAX_LEVELS], sv[SBEV_MAX_LEVELS];
+    const ConfigPyramid pyramid{c, feats_nhwc, b.loc, b.wbp};      // what every gather of the step samples
     const int mixed_up = sbev_decoder_mixed_up_log2(&c), D = c.D, Cg = c.D / c.G, Pin = c.T * c.P;
     const float eps = 1e-5f;
     const float* bbox = query_bbox;  // both paths: the layer's input boxes (the previous layer's refined ones)
@@ -380,11 +388,7 @@ struct Step {
     }
 
     int gather(sbev_stream_t st) {      // the stand-alone sampler
-        if (c.n_slots > 0)
-            return sbev_msmv_fwd_ring(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
-                                      c.G, sbo, Cg, sv, D, b.loc, b.wbp, b.sampled, SBEV_OUT_MIX, c.T, c.G, c.frame_slots, c.n_slots, st);
-        return sbev_msmv_fwd(feats_nhwc, hw, c.L, c.feat_dtype, (int64_t)c.B * c.T * c.G, c.N, Cg, c.Q, c.P,
-                             c.G, sbo, Cg, sv, D, b.loc, b.wbp, b.sampled, SBEV_OUT_MIX, c.T, c.G, st);
+        return sbev::msmv_fwd(pyramid.d, (int64_t)c.B * c.T * c.G, b.sampled, SBEV_OUT_MIX, c.T, c.G, st);
     }
     // gather + adaptive mixing: one launch (fused) or the sampler followed by the mixing kernel.  `params_ready` (forked generator, else
     // null): the join sits where the generator's output is first needed -- behind the stand-alone sampler, which reads none of it.
@@ -395,11 +399,7 @@ struct Step {
         TRY(join(params_ready));
         if (!p.fused && p.nimg >= 4) return sbev_adaptive_mixing_pairs_f16(b.sampled, b.params, b.mixed, p.BQ, c.G, Pin, Cg, c.out_points, eps, mixed_up, st);
         if (!p.fused) return sbev_adaptive_mixing_f32(b.sampled, b.params, b.mixed, p.BQ, c.G, Pin, Cg, c.out_points, eps, st);
-        if (p.nimg >= 4)
-            return sbev_sample_mix_pairs_f16_ordered(feats_nhwc, hw, c.L, c.feat_dtype, c.B, c.N, c.Q, c.T, c.G, c.P, Cg, sbo, Cg, sv, D, b.loc, b.wbp,
-                                                     c.n_slots > 0 ? c.frame_slots : nullptr, c.n_slots, b.params, b.mixed, c.out_points, eps, mixed_up, order, st);
-        return sbev_sample_mix_f32_ordered(feats_nhwc, hw, c.L, c.feat_dtype, c.B, c.N, c.Q, c.T, c.G, c.P, Cg, sbo, Cg, sv, D, b.loc, b.wbp,
-                                           c.n_slots > 0 ? c.frame_slots : nullptr, c.n_slots, b.params, b.mixed, c.out_points, eps, order, st);
+        return sbev::sample_mix(pyramid.d, c.B, c.T, c.G, b.params, b.mixed, c.out_points, eps, p.nimg >= 4 ? ldexpf(1.f, mixed_up) : 0.f, order, st);
     }
 
     // out-projection, row chains: the split-K slabs are left for the tail chain (`used` of them), or folded inside the launch into ONE row block, b.folded
@@ -538,12 +538,6 @@ struct Step {
     }
 
     int run() {
-        for (int l = 0; l < c.L; ++l) {
-            hw[2 * l] = c.hw[l][0];
-            hw[2 * l + 1] = c.hw[l][1];
-            sv[l] = (int64_t)c.hw[l][0] * c.hw[l][1] * D;
-            sbo[l] = sv[l] * c.N;
-        }
         if (p.chain) TRY(sbev::launch_chain_front(c, w, query_bbox, query_feat, b.x, b.qkvt, eps, s_main));
         for (int layer = 0; layer < c.num_layers; ++layer) TRY(p.chain ? layer_chain(layer) : layer_ops(layer));
         return join(ev_cls);      // final join

@@ -614,88 +614,76 @@ extern "C" int sbev_sample_mix_supported(int L, int C, int P, int T, int gdiv, i
 // 64-bit path for larger ones).  hw = {H0, W0, H1, W1, ...}, strides in elements.
 extern "C" int sbev_sample_mix_slabs_ok(const int32_t* hw, int L, int feat_dtype, int N, int Cg, const int64_t* stride_v, int64_t stride_px) {
     if (!hw || !stride_v || L < 1 || L > SBEV_MAX_LEVELS) return 0;
+    sbev::PyramidDesc d{};
+    d.hw = hw; d.L = L; d.feat_dtype = feat_dtype; d.N = N; d.C = Cg; d.stride_v = stride_v; d.stride_px = stride_px;
     for (int l = 0; l < L; ++l)
-        if (!msmv_slab_fits_buffer(N, hw[2 * l], hw[2 * l + 1], stride_v[l], stride_px, Cg, feat_dtype == SBEV_F32 ? 4 : 2)) return 0;
+        if (!msmv_slab_fits_buffer(d, l)) return 0;
     return 1;
 }
 
-static int sample_mix_impl(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
-                           int64_t B, int N, int Q, int T, int G, int P, int Cg,
-                           const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
-                           const float* loc, const float* weights, const int32_t* frame_slots, int n_slots,
-                           const float* params, float* y, int Pout, float eps, float out_up, const int32_t* order, sbev_stream_t stream) {
-    SBEV_REQUIRE(feats && hw && stride_bo && stride_v, "sbev_sample_mix_f32: null descriptor array");
-    SBEV_REQUIRE(sbev_sample_mix_supported(L, Cg, P, T, G, G), "sbev_sample_mix_f32: needs L in {4,5}, C = 64, P in {4,8}, T*P in 4..64 or 116..120 (got L=%d C=%d P=%d T=%d)", L, Cg, P, T);
+// the implementation behind the four sbev_sample_mix_* entry points (d.C channels per group, d.gdiv == G), also called by the decoder step
+int sbev::sample_mix(const sbev::PyramidDesc& d, int64_t B, int T, int G, const float* params, float* y, int Pout, float eps, float out_up,
+                     const int32_t* order, sbev_stream_t stream) {
+    const char* who = "sbev_sample_mix_f32";
+    SBEV_REQUIRE(d.feats && d.hw && d.stride_bo && d.stride_v, "sbev_sample_mix_f32: null descriptor array");
+    SBEV_REQUIRE(sbev_sample_mix_supported(d.L, d.C, d.P, T, d.gdiv, G), "sbev_sample_mix_f32: needs L in {4,5}, C = 64, P in {4,8}, T*P in 4..64 or 116..120 (got L=%d C=%d P=%d T=%d)", d.L, d.C, d.P, T);
     SBEV_REQUIRE(Pout == POUT, "sbev_sample_mix_f32: built for 128 out points");
-    SBEV_REQUIRE(B >= 0 && Q >= 0 && N >= 1 && G >= 1, "sbev_sample_mix_f32: bad sizes");
-    SBEV_REQUIRE(feat_dtype == SBEV_F32 || feat_dtype == SBEV_BF16 || feat_dtype == SBEV_F16, "sbev_sample_mix_f32: feat_dtype %d", feat_dtype);
-    SBEV_REQUIRE(stride_px % 4 == 0 && stride_g % 4 == 0, "sbev_sample_mix_f32: pixel/group strides must be multiples of 4 elements");
-    if (B == 0 || Q == 0) return SBEV_OK;
-    SBEV_REQUIRE(loc && weights && params && y, "sbev_sample_mix_f32: null pointer");
-    SBEV_REQUIRE(B * Q * G <= 0x7fffffffLL && B * (int64_t)T * G * Q <= 0x7fffffffLL, "sbev_sample_mix_f32: too many items");
+    SBEV_REQUIRE(B >= 0 && d.Q >= 0 && d.N >= 1 && G >= 1, "sbev_sample_mix_f32: bad sizes");
+    SBEV_REQUIRE(d.feat_dtype == SBEV_F32 || d.feat_dtype == SBEV_BF16 || d.feat_dtype == SBEV_F16, "sbev_sample_mix_f32: feat_dtype %d", d.feat_dtype);
+    SBEV_REQUIRE(d.stride_px % 4 == 0 && d.stride_g % 4 == 0, "sbev_sample_mix_f32: pixel/group strides must be multiples of 4 elements");
+    if (B == 0 || d.Q == 0) return SBEV_OK;        // (before the levels are looked at, unlike sbev_msmv_fwd)
+    SBEV_REQUIRE(d.loc && d.weights && params && y, "sbev_sample_mix_f32: null pointer");
+    SBEV_REQUIRE(B * d.Q * G <= 0x7fffffffLL && B * (int64_t)T * G * d.Q <= 0x7fffffffLL, "sbev_sample_mix_f32: too many items");
     SampleMixArgs a{};
-    a.params = params; a.y = y; a.n_items = B * Q * G; a.Pin = T * P; a.eps = eps; a.out_up = out_up;
+    a.params = params; a.y = y; a.n_items = B * d.Q * G; a.Pin = T * d.P; a.eps = eps; a.out_up = out_up;
     a.order = order;
     a.order_per = (int)((a.n_items + 7) / 8);
     SBEV_REQUIRE(!order || (((uintptr_t)order) & 3) == 0, "sbev_sample_mix_f32: order must be 4-byte aligned");
+    if (int st = sbev::check_levels(d, true, who)) return st;
+    for (int l = 0; l < d.L; ++l)
+        SBEV_REQUIRE(d.stride_v[l] >= 0 && d.stride_px >= 0 && msmv_slab_fits_buffer(d, l),
+                     "sbev_sample_mix_f32: level %d: one (sample-batch) slab must stay below 2 GiB: the taps are 31-bit buffer offsets -- "
+                     "sbev_sample_mix_slabs_ok; use sbev_msmv_fwd + sbev_adaptive_mixing_f32 otherwise", l);
     MsmvArgs& m = a.s;
-    for (int l = 0; l < L; ++l) {
-        SBEV_REQUIRE(feats[l] != nullptr && hw[2 * l] >= 1 && hw[2 * l + 1] >= 1, "sbev_sample_mix_f32: level %d", l);
-        SBEV_REQUIRE(stride_bo[l] % 4 == 0 && stride_v[l] % 4 == 0 && stride_v[l] >= 0 && stride_px >= 0 &&
-                         msmv_slab_fits_buffer(N, hw[2 * l], hw[2 * l + 1], stride_v[l], stride_px, Cg, feat_dtype == SBEV_F32 ? 4 : 2),
-                     "sbev_sample_mix_f32: level %d strides (multiples of 4; one (sample-batch) slab must stay below 2 GiB: the taps are 31-bit "
-                     "buffer offsets -- sbev_sample_mix_slabs_ok; use sbev_msmv_fwd + sbev_adaptive_mixing_f32 otherwise)", l);
-        m.feat[l] = feats[l];
-        m.H[l] = hw[2 * l]; m.W[l] = hw[2 * l + 1];
-        m.stride_bo[l] = stride_bo[l]; m.stride_v[l] = stride_v[l];
-    }
-    m.stride_g = stride_g; m.stride_px = stride_px;
-    m.loc = loc; m.w = weights; m.out = nullptr;
-    m.n_waves = B * T * G * Q;
-    m.N = N; m.C = Cg; m.Q = Q; m.P = P; m.gdiv = G; m.T = T; m.G = G;
-    if (frame_slots) {
-        SBEV_REQUIRE(T <= SBEV_MAX_FRAMES && n_slots >= T, "sbev_sample_mix_f32: ring needs T <= %d, n_slots >= T", SBEV_MAX_FRAMES);
-        m.ring_T = T; m.n_slots = n_slots;
-        for (int t = 0; t < T; ++t) {
-            SBEV_REQUIRE(frame_slots[t] >= 0 && frame_slots[t] < n_slots, "sbev_sample_mix_f32: frame_slots[%d] out of range", t);
-            m.slots[t] = frame_slots[t];
-        }
-    }
+    sbev::fill_pyramid(m, d);
+    m.n_waves = B * T * G * d.Q;
+    m.T = T; m.G = G;
+    if (int st = msmv_fill_ring(m, d, B * T * G, T, G, who)) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (feat_dtype == SBEV_F32) return L == 4 ? launch_sample_mix_rt<4, float>(a, s) : launch_sample_mix_rt<5, float>(a, s);
-    if (feat_dtype == SBEV_F16) return L == 4 ? launch_sample_mix_rt<4, _Float16>(a, s) : launch_sample_mix_rt<5, _Float16>(a, s);
-    return L == 4 ? launch_sample_mix_rt<4, unsigned short>(a, s) : launch_sample_mix_rt<5, unsigned short>(a, s);
+    if (d.feat_dtype == SBEV_F32) return d.L == 4 ? launch_sample_mix_rt<4, float>(a, s) : launch_sample_mix_rt<5, float>(a, s);
+    if (d.feat_dtype == SBEV_F16) return d.L == 4 ? launch_sample_mix_rt<4, _Float16>(a, s) : launch_sample_mix_rt<5, _Float16>(a, s);
+    return d.L == 4 ? launch_sample_mix_rt<4, unsigned short>(a, s) : launch_sample_mix_rt<5, unsigned short>(a, s);
 }
 
+// The four entry points.  _ordered: the same launch with its workgroups in the order of sbev_query_order (order [B*Q]: a permutation of
+// the rows b*Q + q, each sample's rows contiguous): results are bit-identical, only WHERE and WHEN an item runs changes (see
+// SampleMixArgs::order); null = launch order.  _pairs_f16: y as (fp16 hi, fp16 lo) pairs of y 2^up_log2 (see sbev_adaptive_mixing_pairs_f16)
 extern "C" int sbev_sample_mix_f32(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
                                    int64_t B, int N, int Q, int T, int G, int P, int Cg,
                                    const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
                                    const float* loc, const float* weights, const int32_t* frame_slots, int n_slots,
                                    const float* params, float* y, int Pout, float eps, sbev_stream_t stream) {
-    return sample_mix_impl(feats, hw, L, feat_dtype, B, N, Q, T, G, P, Cg, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots,
-                           params, y, Pout, eps, 0.f, nullptr, stream);
+    return sbev::sample_mix({feats, hw, L, feat_dtype, N, Cg, Q, P, G, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots},
+                            B, T, G, params, y, Pout, eps, 0.f, nullptr, stream);
 }
 
-// the same launch with its workgroups in the order of sbev_query_order (order [B*Q]: a permutation of the rows b*Q + q, each sample's
-// rows contiguous): results are bit-identical, only WHERE and WHEN an item runs changes (see SampleMixArgs::order); null = launch order
 extern "C" int sbev_sample_mix_f32_ordered(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
                                            int64_t B, int N, int Q, int T, int G, int P, int Cg,
                                            const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
                                            const float* loc, const float* weights, const int32_t* frame_slots, int n_slots,
                                            const float* params, float* y, int Pout, float eps, const int32_t* order, sbev_stream_t stream) {
-    return sample_mix_impl(feats, hw, L, feat_dtype, B, N, Q, T, G, P, Cg, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots,
-                           params, y, Pout, eps, 0.f, order, stream);
+    return sbev::sample_mix({feats, hw, L, feat_dtype, N, Cg, Q, P, G, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots},
+                            B, T, G, params, y, Pout, eps, 0.f, order, stream);
 }
 
-// the same, y as (fp16 hi, fp16 lo) pairs of y 2^up_log2 (see sbev_adaptive_mixing_pairs_f16)
 extern "C" int sbev_sample_mix_pairs_f16(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
                                          int64_t B, int N, int Q, int T, int G, int P, int Cg,
                                          const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
                                          const float* loc, const float* weights, const int32_t* frame_slots, int n_slots,
                                          const float* params, void* y, int Pout, float eps, int up_log2, sbev_stream_t stream) {
     SBEV_REQUIRE(up_log2 >= -100 && up_log2 <= 100, "sbev_sample_mix_pairs_f16: up_log2=%d", up_log2);
-    return sample_mix_impl(feats, hw, L, feat_dtype, B, N, Q, T, G, P, Cg, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots,
-                           params, static_cast<float*>(y), Pout, eps, ldexpf(1.f, up_log2), nullptr, stream);
+    return sbev::sample_mix({feats, hw, L, feat_dtype, N, Cg, Q, P, G, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots},
+                            B, T, G, params, static_cast<float*>(y), Pout, eps, ldexpf(1.f, up_log2), nullptr, stream);
 }
 
 extern "C" int sbev_sample_mix_pairs_f16_ordered(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
@@ -705,6 +693,6 @@ extern "C" int sbev_sample_mix_pairs_f16_ordered(const void* const* feats, const
                                                  const float* params, void* y, int Pout, float eps, int up_log2, const int32_t* order,
                                                  sbev_stream_t stream) {
     SBEV_REQUIRE(up_log2 >= -100 && up_log2 <= 100, "sbev_sample_mix_pairs_f16: up_log2=%d", up_log2);
-    return sample_mix_impl(feats, hw, L, feat_dtype, B, N, Q, T, G, P, Cg, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots,
-                           params, static_cast<float*>(y), Pout, eps, ldexpf(1.f, up_log2), order, stream);
+    return sbev::sample_mix({feats, hw, L, feat_dtype, N, Cg, Q, P, G, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots},
+                            B, T, G, params, static_cast<float*>(y), Pout, eps, ldexpf(1.f, up_log2), order, stream);
 }

@@ -89,11 +89,24 @@ constexpr unsigned MSMV_OUTSIDE = 0x80000000u;
 constexpr unsigned MSMV_BUF_RECORDS = 0x7fffffffu;
 constexpr int MSMV_RSRC_DW3 = 0x00020000;           // gfx9 raw buffer, 32-bit data format (composable_kernel's constant for gfx9)
 
-// host: the largest in-slab byte offset a tap of this level can carry (last pixel of the last view + the lanes' channel offset + one
+// host: the largest in-slab byte offset a tap of level l can carry (last pixel of the last view + the lanes' channel offset + one
 // 16-byte load) stays below the buffer's 2^31 - 1 records
-inline bool msmv_slab_fits_buffer(long long N, long long H, long long W, long long stride_v, long long stride_px, long long C, long long esize) {
-    const long long last = (N - 1) * stride_v + (H * W - 1) * stride_px + (C > 64 ? C : 64) + 4;
-    return last * esize < (long long)MSMV_BUF_RECORDS;
+inline bool msmv_slab_fits_buffer(const sbev::PyramidDesc& d, int l) {
+    const long long last = d.slab_span(l) + (d.C > 64 ? d.C : 64) + 4;
+    return last * (d.feat_dtype == SBEV_F32 ? 4 : 2) < (long long)MSMV_BUF_RECORDS;
+}
+// host: the ring's slot table -> a.slots (no ring: nothing).  B' = B*T*G sample batches, `who`: the entry point, for its messages
+inline int msmv_fill_ring(MsmvArgs& a, const sbev::PyramidDesc& d, int64_t Bp, int T, int G, const char* who) {
+    if (!d.frame_slots) return SBEV_OK;
+    SBEV_REQUIRE(T >= 1 && T <= SBEV_MAX_FRAMES && d.n_slots >= T && d.gdiv == G && Bp % ((int64_t)T * G) == 0,
+                 "%s: need 1 <= T <= %d, n_slots >= T, gdiv == G, B' = B*T*G", who, SBEV_MAX_FRAMES);
+    a.ring_T = T;
+    a.n_slots = d.n_slots;
+    for (int t = 0; t < T; ++t) {
+        SBEV_REQUIRE(d.frame_slots[t] >= 0 && d.frame_slots[t] < d.n_slots, "%s: frame_slots[%d] = %d out of range", who, t, d.frame_slots[t]);
+        a.slots[t] = d.frame_slots[t];
+    }
+    return SBEV_OK;
 }
 
 template <int L, typename FT, bool BUF>

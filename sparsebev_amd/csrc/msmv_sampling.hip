@@ -174,65 +174,40 @@ int launch_t(const MsmvArgs& a, int L, int out_layout, bool slabs_fit_buffer, hi
 
 }  // namespace
 
-static int msmv_fwd_impl(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
-                         int64_t Bp, int N, int C, int Q, int P,
-                         int gdiv, const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v,
-                         int64_t stride_px, const float* loc, const float* weights, float* out,
-                         int out_layout, int T, int G, const int32_t* frame_slots, int n_slots, sbev_stream_t stream) {
-    SBEV_REQUIRE(feats && hw && stride_bo && stride_v, "sbev_msmv_fwd: null descriptor array");
-    SBEV_REQUIRE(L >= 1 && L <= SBEV_MAX_LEVELS, "sbev_msmv_fwd: L=%d not in 1..%d", L, SBEV_MAX_LEVELS);
-    SBEV_REQUIRE(P >= 1 && P <= SBEV_MAX_POINTS, "sbev_msmv_fwd: num_point exceed limits (P=%d > %d)", P, SBEV_MAX_POINTS);
-    SBEV_REQUIRE(C >= 4 && C % 4 == 0, "sbev_msmv_fwd: C=%d must be a positive multiple of 4", C);
-    SBEV_REQUIRE(N >= 1 && Q >= 0 && Bp >= 0 && gdiv >= 1, "sbev_msmv_fwd: bad sizes");
-    SBEV_REQUIRE(feat_dtype == SBEV_F32 || feat_dtype == SBEV_BF16 || feat_dtype == SBEV_F16, "sbev_msmv_fwd: feat_dtype %d", feat_dtype);
+// the implementation behind sbev_msmv_fwd and sbev_msmv_fwd_ring (d.frame_slots), also called by the decoder step
+int sbev::msmv_fwd(const sbev::PyramidDesc& d, int64_t Bp, float* out, int out_layout, int T, int G, sbev_stream_t stream) {
+    const char* who = "sbev_msmv_fwd";
+    if (int st = sbev::check_pyramid(d, who)) return st;
+    SBEV_REQUIRE(d.C >= 4 && d.C % 4 == 0, "sbev_msmv_fwd: C=%d must be a positive multiple of 4", d.C);
+    SBEV_REQUIRE(d.N >= 1 && d.Q >= 0 && Bp >= 0 && d.gdiv >= 1, "sbev_msmv_fwd: bad sizes");
+    SBEV_REQUIRE(d.feat_dtype == SBEV_F32 || d.feat_dtype == SBEV_BF16 || d.feat_dtype == SBEV_F16, "sbev_msmv_fwd: feat_dtype %d", d.feat_dtype);
     SBEV_REQUIRE(out_layout == SBEV_OUT_REF || out_layout == SBEV_OUT_MIX, "sbev_msmv_fwd: out_layout %d", out_layout);
-    SBEV_REQUIRE(stride_px % 4 == 0 && stride_g % 4 == 0, "sbev_msmv_fwd: pixel/group strides must be multiples of 4 elements");
+    SBEV_REQUIRE(d.stride_px % 4 == 0 && d.stride_g % 4 == 0, "sbev_msmv_fwd: pixel/group strides must be multiples of 4 elements");
     if (out_layout == SBEV_OUT_MIX)
         SBEV_REQUIRE(T >= 1 && G >= 1 && Bp % ((int64_t)T * G) == 0, "sbev_msmv_fwd: B'=%lld is not B*T*G (T=%d, G=%d)", (long long)Bp, T, G);
-    const bool empty = Bp == 0 || Q == 0;          // an empty call still validates its level descriptors
-    SBEV_REQUIRE(empty || (loc && weights && out), "sbev_msmv_fwd: null loc/weights/out");
-    MsmvArgs a{};
+    const bool empty = Bp == 0 || d.Q == 0;        // an empty call still validates its level descriptors
+    SBEV_REQUIRE(empty || (d.loc && d.weights && out), "sbev_msmv_fwd: null loc/weights/out");
+    if (int st = sbev::check_levels(d, !empty, who)) return st;
     bool fit = true;        // every (sample-batch, group) slab + a lane's channel offset addressable by a 31-bit BYTE offset
-    const int64_t esize = feat_dtype == SBEV_F32 ? 4 : 2;
-    for (int l = 0; l < L; ++l) {
-        SBEV_REQUIRE(empty || feats[l] != nullptr, "sbev_msmv_fwd: feats[%d] is null", l);
-        SBEV_REQUIRE(hw[2 * l] >= 1 && hw[2 * l + 1] >= 1, "sbev_msmv_fwd: level %d has empty map", l);
-        SBEV_REQUIRE(stride_bo[l] % 4 == 0 && stride_v[l] % 4 == 0, "sbev_msmv_fwd: level %d strides must be multiples of 4 elements", l);
+    for (int l = 0; l < d.L; ++l) {
         // the kernel keeps a tap's offset INSIDE one sample-batch slab (view * stride_v + pixel * stride_px) in 32 bits with
         // bit 31 as its "outside the map" flag; the slab base itself is 64-bit.  Refuse maps one slab of which does not fit.
-        SBEV_REQUIRE(stride_v[l] >= 0 && stride_px >= 0 &&
-                         (int64_t)(N - 1) * stride_v[l] + ((int64_t)hw[2 * l] * hw[2 * l + 1] - 1) * stride_px + C <= 0x7fffffffLL,
+        SBEV_REQUIRE(d.stride_v[l] >= 0 && d.stride_px >= 0 && d.slab_span(l) + d.C <= 0x7fffffffLL,
                      "sbev_msmv_fwd: level %d: one (sample-batch) slab spans %lld elements, the in-slab tap offset is 32-bit (limit 2^31 - 1)",
-                     l, (long long)((int64_t)(N - 1) * stride_v[l] + ((int64_t)hw[2 * l] * hw[2 * l + 1] - 1) * stride_px + C));
-        fit = fit && msmv_slab_fits_buffer(N, hw[2 * l], hw[2 * l + 1], stride_v[l], stride_px, C, esize);
-        a.feat[l] = feats[l];
-        a.H[l] = hw[2 * l];
-        a.W[l] = hw[2 * l + 1];
-        a.stride_bo[l] = stride_bo[l];
-        a.stride_v[l] = stride_v[l];
+                     l, (long long)(d.slab_span(l) + d.C));
+        fit = fit && msmv_slab_fits_buffer(d, l);
     }
     if (empty) return SBEV_OK;
-    a.stride_g = stride_g;
-    a.stride_px = stride_px;
-    a.loc = loc;
-    a.w = weights;
+    MsmvArgs a{};
+    sbev::fill_pyramid(a, d);
     a.out = out;
-    a.n_waves = Bp * Q;
-    a.N = N; a.C = C; a.Q = Q; a.P = P; a.gdiv = gdiv; a.T = T; a.G = G;
-    if (frame_slots) {
-        SBEV_REQUIRE(T >= 1 && T <= SBEV_MAX_FRAMES && n_slots >= T && gdiv == G && Bp % ((int64_t)T * G) == 0,
-                     "sbev_msmv_fwd_ring: need 1 <= T <= %d, n_slots >= T, gdiv == G, B' = B*T*G", SBEV_MAX_FRAMES);
-        a.ring_T = T;
-        a.n_slots = n_slots;
-        for (int t = 0; t < T; ++t) {
-            SBEV_REQUIRE(frame_slots[t] >= 0 && frame_slots[t] < n_slots, "sbev_msmv_fwd_ring: frame_slots[%d] = %d out of range", t, frame_slots[t]);
-            a.slots[t] = frame_slots[t];
-        }
-    }
+    a.n_waves = Bp * d.Q;
+    a.T = T; a.G = G;
+    if (int st = msmv_fill_ring(a, d, Bp, T, G, "sbev_msmv_fwd_ring")) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return feat_dtype == SBEV_F32 ? launch_t<float>(a, L, out_layout, fit, s)
-           : feat_dtype == SBEV_F16 ? launch_t<_Float16>(a, L, out_layout, fit, s)
-                                    : launch_t<unsigned short>(a, L, out_layout, fit, s);
+    return d.feat_dtype == SBEV_F32 ? launch_t<float>(a, d.L, out_layout, fit, s)
+           : d.feat_dtype == SBEV_F16 ? launch_t<_Float16>(a, d.L, out_layout, fit, s)
+                                      : launch_t<unsigned short>(a, d.L, out_layout, fit, s);
 }
 
 extern "C" int sbev_msmv_buffer_taps(int enable) {
@@ -247,8 +222,8 @@ extern "C" int sbev_msmv_fwd(const void* const* feats, const int32_t* hw, int L,
                              int gdiv, const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v,
                              int64_t stride_px, const float* loc, const float* weights, float* out,
                              int out_layout, int T, int G, sbev_stream_t stream) {
-    return msmv_fwd_impl(feats, hw, L, feat_dtype, Bp, N, C, Q, P, gdiv, stride_bo, stride_g, stride_v, stride_px, loc, weights,
-                         out, out_layout, T, G, nullptr, 0, stream);
+    return sbev::msmv_fwd({feats, hw, L, feat_dtype, N, C, Q, P, gdiv, stride_bo, stride_g, stride_v, stride_px, loc, weights, nullptr, 0},
+                          Bp, out, out_layout, T, G, stream);
 }
 
 extern "C" int sbev_msmv_fwd_ring(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
@@ -258,6 +233,6 @@ extern "C" int sbev_msmv_fwd_ring(const void* const* feats, const int32_t* hw, i
                                   int out_layout, int T, int G, const int32_t* frame_slots, int n_slots,
                                   sbev_stream_t stream) {
     SBEV_REQUIRE(frame_slots != nullptr, "sbev_msmv_fwd_ring: frame_slots is null");
-    return msmv_fwd_impl(feats, hw, L, feat_dtype, Bp, N, C, Q, P, gdiv, stride_slot, stride_g, stride_v, stride_px, loc, weights,
-                         out, out_layout, T, G, frame_slots, n_slots, stream);
+    return sbev::msmv_fwd({feats, hw, L, feat_dtype, N, C, Q, P, gdiv, stride_slot, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots},
+                          Bp, out, out_layout, T, G, stream);
 }

@@ -242,38 +242,29 @@ int launch_bwd(const BwdArgs& a, hipStream_t s) {
 
 }  // namespace
 
-static int msmv_bwd_impl(const void* const* feats, void* const* grad_feats, const int32_t* hw, int L,
-                         int64_t Bp, int N, int C, int Q, int P,
-                         int gdiv, const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
-                         const float* loc, const float* weights, const float* grad_out, int grad_out_layout, int T, int G,
-                         float* grad_loc, float* grad_weights, sbev_stream_t stream) {
-    SBEV_REQUIRE(feats && hw && stride_bo && stride_v, "sbev_msmv_bwd: null descriptor array");
-    SBEV_REQUIRE(L >= 1 && L <= SBEV_MAX_LEVELS, "sbev_msmv_bwd: L=%d", L);
-    SBEV_REQUIRE(P >= 1 && P <= SBEV_MAX_POINTS, "sbev_msmv_bwd: num_point exceed limits (P=%d)", P);
-    SBEV_REQUIRE(C >= 1 && N >= 1 && Q >= 0 && Bp >= 0 && gdiv >= 1, "sbev_msmv_bwd: bad sizes");
+// the implementation behind sbev_msmv_bwd and sbev_msmv_bwd_ex.  Unlike the forward it takes any C >= 1 and any strides (scalar
+// loads and atomics), and an empty call returns before its levels are looked at
+static int msmv_bwd_impl(const sbev::PyramidDesc& d, void* const* grad_feats, int64_t Bp, const float* grad_out, int grad_out_layout,
+                         int T, int G, float* grad_loc, float* grad_weights, sbev_stream_t stream) {
+    if (int st = sbev::check_pyramid(d, "sbev_msmv_bwd")) return st;
+    SBEV_REQUIRE(d.C >= 1 && d.N >= 1 && d.Q >= 0 && Bp >= 0 && d.gdiv >= 1, "sbev_msmv_bwd: bad sizes");
     SBEV_REQUIRE(grad_out_layout == SBEV_OUT_REF || grad_out_layout == SBEV_OUT_MIX, "sbev_msmv_bwd: grad_out_layout %d", grad_out_layout);
     if (grad_out_layout == SBEV_OUT_MIX)
         SBEV_REQUIRE(T >= 1 && G >= 1 && Bp % ((int64_t)T * G) == 0, "sbev_msmv_bwd: B'=%lld is not B*T*G (T=%d, G=%d)", (long long)Bp, T, G);
-    if (Bp == 0 || Q == 0) return SBEV_OK;
-    SBEV_REQUIRE(loc && weights && grad_out && grad_loc && grad_weights, "sbev_msmv_bwd: null pointer");
+    if (Bp == 0 || d.Q == 0) return SBEV_OK;
+    SBEV_REQUIRE(d.loc && d.weights && grad_out && grad_loc && grad_weights, "sbev_msmv_bwd: null pointer");
     BwdArgs a{};
+    sbev::fill_pyramid(a, d);
     a.want_gfeat = grad_feats != nullptr;
-    for (int l = 0; l < L; ++l) {
-        SBEV_REQUIRE(feats[l] && (!grad_feats || grad_feats[l]), "sbev_msmv_bwd: level %d pointer is null", l);
-        a.feat[l] = static_cast<const float*>(feats[l]);
-        a.gfeat[l] = grad_feats ? static_cast<float*>(grad_feats[l]) : const_cast<float*>(static_cast<const float*>(feats[l]));   // never written when !want_gfeat
-        a.H[l] = hw[2 * l];
-        a.W[l] = hw[2 * l + 1];
-        a.stride_bo[l] = stride_bo[l];
-        a.stride_v[l] = stride_v[l];
+    for (int l = 0; l < d.L; ++l) {
+        SBEV_REQUIRE(d.feats[l] && (!grad_feats || grad_feats[l]), "sbev_msmv_bwd: level %d pointer is null", l);
+        a.gfeat[l] = grad_feats ? static_cast<float*>(grad_feats[l]) : const_cast<float*>(a.feat[l]);   // never written when !want_gfeat
     }
-    a.stride_g = stride_g; a.stride_px = stride_px;
-    a.loc = loc; a.w = weights; a.gout = grad_out; a.gloc = grad_loc; a.gw = grad_weights;
+    a.gout = grad_out; a.gloc = grad_loc; a.gw = grad_weights;
     a.gout_mix = grad_out_layout == SBEV_OUT_MIX; a.T = T; a.G = G;
-    a.n_waves = Bp * Q;
-    a.N = N; a.C = C; a.Q = Q; a.P = P; a.gdiv = gdiv;
+    a.n_waves = Bp * d.Q;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (L) {
+    switch (d.L) {
         case 1: return launch_bwd<1>(a, s);
         case 2: return launch_bwd<2>(a, s);
         case 3: return launch_bwd<3>(a, s);
@@ -288,8 +279,8 @@ extern "C" int sbev_msmv_bwd(const void* const* feats, void* const* grad_feats, 
                              const float* loc, const float* weights, const float* grad_out,
                              float* grad_loc, float* grad_weights, sbev_stream_t stream) {
     SBEV_REQUIRE(grad_feats != nullptr, "sbev_msmv_bwd: null descriptor array");
-    return msmv_bwd_impl(feats, grad_feats, hw, L, Bp, N, C, Q, P, gdiv, stride_bo, stride_g, stride_v, stride_px, loc, weights,
-                         grad_out, SBEV_OUT_REF, 1, 1, grad_loc, grad_weights, stream);
+    return msmv_bwd_impl({feats, hw, L, SBEV_F32, N, C, Q, P, gdiv, stride_bo, stride_g, stride_v, stride_px, loc, weights, nullptr, 0},
+                         grad_feats, Bp, grad_out, SBEV_OUT_REF, 1, 1, grad_loc, grad_weights, stream);
 }
 
 extern "C" int sbev_msmv_bwd_ex(const void* const* feats, void* const* grad_feats, const int32_t* hw, int L,
@@ -297,6 +288,6 @@ extern "C" int sbev_msmv_bwd_ex(const void* const* feats, void* const* grad_feat
                                 int gdiv, const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
                                 const float* loc, const float* weights, const float* grad_out, int grad_out_layout, int T, int G,
                                 float* grad_loc, float* grad_weights, sbev_stream_t stream) {
-    return msmv_bwd_impl(feats, grad_feats, hw, L, Bp, N, C, Q, P, gdiv, stride_bo, stride_g, stride_v, stride_px, loc, weights,
-                         grad_out, grad_out_layout, T, G, grad_loc, grad_weights, stream);
+    return msmv_bwd_impl({feats, hw, L, SBEV_F32, N, C, Q, P, gdiv, stride_bo, stride_g, stride_v, stride_px, loc, weights, nullptr, 0},
+                         grad_feats, Bp, grad_out, grad_out_layout, T, G, grad_loc, grad_weights, stream);
 }

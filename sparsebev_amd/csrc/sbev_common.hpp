@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "../../include/sbev_hip.h"
 
@@ -53,6 +54,59 @@ struct Switches {
         out8_min_rows, msmv_buffer_taps, box_convention;
 };
 bool msmv_buffer_taps_enabled();      // msmv_sampling.hip (read by the sampler launchers themselves: public entry points of their own)
+
+// The feature pyramid + sample points that every sampler entry point is given (include/sbev_hip.h: sbev_msmv_fwd), as ONE value: the
+// extern "C" functions build it from their positional arguments, decoder.hip once per step from its config.  Strides in elements.
+struct PyramidDesc {
+    const void* const* feats;       // [L] level bases
+    const int32_t* hw;              // {H0, W0, H1, W1, ...}
+    int L, feat_dtype, N, C, Q, P, gdiv;
+    const int64_t* stride_bo;       // [L] per (sample-batch / gdiv) -- or per ring slot
+    int64_t stride_g;
+    const int64_t* stride_v;        // [L] per view
+    int64_t stride_px;
+    const float *loc, *weights;
+    const int32_t* frame_slots;     // online frame ring (null: none): logical frame t lives in slot frame_slots[t] of n_slots
+    int n_slots;
+
+    // elements from the base of one (sample-batch) slab of level l to the last pixel of its last view; a limit adds its own tail
+    int64_t slab_span(int l) const { return (int64_t)(N - 1) * stride_v[l] + ((int64_t)hw[2 * l] * hw[2 * l + 1] - 1) * stride_px; }
+};
+// what all three implementations ask first (`who`: the entry point, the prefix of every message)
+inline int check_pyramid(const PyramidDesc& d, const char* who) {
+    SBEV_REQUIRE(d.feats && d.hw && d.stride_bo && d.stride_v, "%s: null descriptor array", who);
+    SBEV_REQUIRE(d.L >= 1 && d.L <= SBEV_MAX_LEVELS, "%s: L=%d not in 1..%d", who, d.L, SBEV_MAX_LEVELS);
+    SBEV_REQUIRE(d.P >= 1 && d.P <= SBEV_MAX_POINTS, "%s: num_point exceed limits (P=%d > %d)", who, d.P, SBEV_MAX_POINTS);
+    return SBEV_OK;
+}
+// the forward's and the fused launch's 16-byte taps: non-empty maps, strides in multiples of 4 elements (the backward asks neither)
+inline int check_levels(const PyramidDesc& d, bool need_feats, const char* who) {
+    for (int l = 0; l < d.L; ++l) {
+        SBEV_REQUIRE(!need_feats || d.feats[l] != nullptr, "%s: feats[%d] is null", who, l);
+        SBEV_REQUIRE(d.hw[2 * l] >= 1 && d.hw[2 * l + 1] >= 1, "%s: level %d has empty map", who, l);
+        SBEV_REQUIRE(d.stride_bo[l] % 4 == 0 && d.stride_v[l] % 4 == 0, "%s: level %d strides must be multiples of 4 elements", who, l);
+    }
+    return SBEV_OK;
+}
+// the description -> a kernel argument block (MsmvArgs, BwdArgs: the same member names)
+template <typename Args>
+inline void fill_pyramid(Args& a, const PyramidDesc& d) {
+    for (int l = 0; l < d.L; ++l) {
+        a.feat[l] = static_cast<std::decay_t<decltype(a.feat[0])>>(d.feats[l]);
+        a.H[l] = d.hw[2 * l];
+        a.W[l] = d.hw[2 * l + 1];
+        a.stride_bo[l] = d.stride_bo[l];
+        a.stride_v[l] = d.stride_v[l];
+    }
+    a.stride_g = d.stride_g; a.stride_px = d.stride_px;
+    a.loc = d.loc; a.w = d.weights;
+    a.N = d.N; a.C = d.C; a.Q = d.Q; a.P = d.P; a.gdiv = d.gdiv;
+}
+// msmv_sampling.hip / mixing.hip: the implementations behind sbev_msmv_fwd[_ring] (B' sample batches) and the four sbev_sample_mix_*
+// (B samples; out_up 0: y is fp32, 2^e: fp16 pairs; order may be null), for callers that hold a description (decoder.hip)
+int msmv_fwd(const PyramidDesc& d, int64_t Bp, float* out, int out_layout, int T, int G, sbev_stream_t stream);
+int sample_mix(const PyramidDesc& d, int64_t B, int T, int G, const float* params, float* y, int Pout, float eps, float out_up,
+               const int32_t* order, sbev_stream_t stream);
 
 // gemm_bf16s.hip: the GEMM half of sbev_linear_splitk_bf16s (*used partial slabs [used, M, 256], not reduced)
 // out8_min_rows: the caller's reading of sbev_linear_out8_min_rows (pre-split operand only: rows from which the 256-row tiles run).

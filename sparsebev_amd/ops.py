@@ -52,16 +52,30 @@ def _no_grad_only(*tensors):
                                   'ops.msmv_sampling (reference layout) and the decoder module in train() mode')
 
 
-def _msmv_launch(feats, hw, feat_dtype, Bp, N, C, Q, P, gdiv, stride_bo, stride_g, stride_v, stride_px,
-                 loc, weights, out, out_layout, T, G):
+def _level_ptrs(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _pyramid(feats, N, G=None):
+    """The C ABI's description of a feature pyramid (include/sbev_hip.h: sbev_msmv_fwd) for channels-last levels [..., H_l, W_l, row]:
+    ``(c_feats, c_hw, L), (gdiv, c_stride_bo, stride_g, c_stride_v, stride_px)`` -- the two runs of positional arguments every sampler
+    entry point takes, strides in elements.  G None: the reference's [B', N, H, W, C] (one group per sample batch); else the grouped
+    [B*T*N or B*n_slots*N, H, W, G*C], group g = channel slice [g*C, (g+1)*C)."""
     L = len(feats)
-    lib = _lib.load()
-    c_feats = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-    c_hw = (ctypes.c_int32 * (2 * L))(*[v for pair in hw for v in pair])
-    c_sbo = (ctypes.c_int64 * L)(*stride_bo)
-    c_sv = (ctypes.c_int64 * L)(*stride_v)
-    st = lib.sbev_msmv_fwd(c_feats, c_hw, L, feat_dtype, Bp, N, C, Q, P, gdiv, c_sbo, stride_g, c_sv, stride_px,
-                           _ptr(loc), _ptr(weights), _ptr(out), out_layout, T, G, _stream())
+    row = feats[0].shape[-1]
+    pixels = [f.shape[-3] * f.shape[-2] for f in feats]
+    c_hw = (ctypes.c_int32 * (2 * L))(*[v for f in feats for v in f.shape[-3:-1]])
+    c_sbo = (ctypes.c_int64 * L)(*[N * n * row for n in pixels])
+    c_sv = (ctypes.c_int64 * L)(*[n * row for n in pixels])
+    gdiv, stride_g = (1, 0) if G is None else (G, row // G)
+    return (_level_ptrs(feats), c_hw, L), (gdiv, c_sbo, stride_g, c_sv, row)
+
+
+def _msmv_launch(feats, Bp, N, C, G, loc, weights, out, out_layout, T, Gout):
+    levels, strides = _pyramid(feats, N, G)
+    Q, P = loc.shape[1:3]
+    st = _lib.load().sbev_msmv_fwd(*levels, _feat_dtype(feats), Bp, N, C, Q, P, *strides,
+                                   _ptr(loc), _ptr(weights), _ptr(out), out_layout, T, Gout, _stream())
     _lib.check(st, 'sbev_msmv_fwd')
 
 
@@ -81,15 +95,11 @@ def _feat_dtype(feats):
 def _msmv_forward(feats, sampling_locations, scale_weights, out_layout, T, G):
     Bp, N, _, _, C = feats[0].shape
     _, Q, P, _ = sampling_locations.shape
-    hw = [(f.shape[2], f.shape[3]) for f in feats]
-    sbo = [N * h * w * C for h, w in hw]
-    sv = [h * w * C for h, w in hw]
     if out_layout == OUT_REF:
         out = torch.empty(Bp, Q, C, P, device=feats[0].device, dtype=torch.float32)
     else:
         out = torch.empty(Bp // (T * G), Q, G, T * P, C, device=feats[0].device, dtype=torch.float32)
-    _msmv_launch(feats, hw, _feat_dtype(feats), Bp, N, C, Q, P, 1, sbo, 0, sv, C,
-                 sampling_locations, scale_weights, out, out_layout, T, G)
+    _msmv_launch(feats, Bp, N, C, None, sampling_locations, scale_weights, out, out_layout, T, G)
     return out
 
 
@@ -108,21 +118,14 @@ class MSMVSampling(torch.autograd.Function):
         if feats[0].dtype != torch.float32:
             raise NotImplementedError('msmv_sampling backward needs fp32 features')
         grad_output = grad_output.contiguous().float()
-        L = len(feats)
         Bp, N, _, _, C = feats[0].shape
         _, Q, P, _ = loc.shape
         gfeats = [torch.zeros_like(f) for f in feats]              # the op accumulates with atomics
         gloc = torch.empty_like(loc)
         gw = torch.empty_like(weights)
-        hw = [(f.shape[2], f.shape[3]) for f in feats]
-        lib = _lib.load()
-        c_feats = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-        c_gfeats = (ctypes.c_void_p * L)(*[f.data_ptr() for f in gfeats])
-        c_hw = (ctypes.c_int32 * (2 * L))(*[v for pair in hw for v in pair])
-        c_sbo = (ctypes.c_int64 * L)(*[N * h * w * C for h, w in hw])
-        c_sv = (ctypes.c_int64 * L)(*[h * w * C for h, w in hw])
-        st = lib.sbev_msmv_bwd(c_feats, c_gfeats, c_hw, L, Bp, N, C, Q, P, 1, c_sbo, 0, c_sv, C,
-                               _ptr(loc), _ptr(weights), _ptr(grad_output), _ptr(gloc), _ptr(gw), _stream())
+        (c_feats, c_hw, L), strides = _pyramid(feats, N)
+        st = _lib.load().sbev_msmv_bwd(c_feats, _level_ptrs(gfeats), c_hw, L, Bp, N, C, Q, P, *strides,
+                                       _ptr(loc), _ptr(weights), _ptr(grad_output), _ptr(gloc), _ptr(gw), _stream())
         _lib.check(st, 'sbev_msmv_bwd')
         return (gloc, gw, *gfeats)
 
@@ -175,15 +178,11 @@ def msmv_sampling_nhwc(feats_nhwc, B, T, G, sampling_locations, scale_weights, o
     for f in feats:
         if not f.is_contiguous() or f.dim() != 4 or f.shape[0] != B * T * N or f.shape[-1] != GC:
             raise RuntimeError('nhwc feature level must be contiguous [B*T*6, H, W, G*C]')
-    hw = [(f.shape[1], f.shape[2]) for f in feats]
-    sbo = [N * h * w * GC for h, w in hw]
-    sv = [h * w * GC for h, w in hw]
     if out_layout == OUT_REF:
         out = torch.empty(Bp, Q, C, P, device=feats[0].device, dtype=torch.float32)
     else:
         out = torch.empty(B, Q, G, T * P, C, device=feats[0].device, dtype=torch.float32)
-    _msmv_launch(feats, hw, _feat_dtype(feats), Bp, N, C, Q, P, G, sbo, C, sv, GC,
-                 sampling_locations.contiguous(), scale_weights.contiguous(), out, out_layout, T, G)
+    _msmv_launch(feats, Bp, N, C, G, sampling_locations.contiguous(), scale_weights.contiguous(), out, out_layout, T, G)
     return out
 
 
@@ -201,19 +200,13 @@ def msmv_sampling_nhwc_backward(feats_nhwc, B, T, G, sampling_locations, scale_w
     Q, P = _check_sampling_args(feats, sampling_locations, scale_weights, Bp, 'msmv_sampling_nhwc_backward')
     GC = feats[0].shape[-1]
     C = GC // G
-    L = len(feats)
-    hw = [(f.shape[1], f.shape[2]) for f in feats]
     gloc = torch.empty_like(sampling_locations)
     gw = torch.empty_like(scale_weights)
-    lib = _lib.load()
-    c_feats = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-    c_gfeats = (ctypes.c_void_p * L)(*[g.data_ptr() for g in grad_feats]) if grad_feats is not None else None
-    c_hw = (ctypes.c_int32 * (2 * L))(*[v for pair in hw for v in pair])
-    c_sbo = (ctypes.c_int64 * L)(*[N * h * w * GC for h, w in hw])
-    c_sv = (ctypes.c_int64 * L)(*[h * w * GC for h, w in hw])
-    st = lib.sbev_msmv_bwd_ex(c_feats, c_gfeats, c_hw, L, Bp, N, C, Q, P, G, c_sbo, C, c_sv, GC,
-                              _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), _ptr(grad_out.contiguous()),
-                              grad_layout, T, G, _ptr(gloc), _ptr(gw), _stream())
+    (c_feats, c_hw, L), strides = _pyramid(feats, N, G)
+    c_gfeats = _level_ptrs(grad_feats) if grad_feats is not None else None
+    st = _lib.load().sbev_msmv_bwd_ex(c_feats, c_gfeats, c_hw, L, Bp, N, C, Q, P, *strides,
+                                      _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), _ptr(grad_out.contiguous()),
+                                      grad_layout, T, G, _ptr(gloc), _ptr(gw), _stream())
     _lib.check(st, 'sbev_msmv_bwd_ex')
     return gloc, gw
 
@@ -231,28 +224,20 @@ def msmv_sampling_ring(levels, B, T, G, frame_slots, n_slots, sampling_locations
     if GC % G != 0 or (GC // G) % 4 != 0:
         raise RuntimeError('ring feature channels %d must split into G=%d groups of a multiple of 4 channels' % (GC, G))
     C = GC // G
-    L = len(feats)
     for f in feats:
         if not f.is_contiguous() or f.dim() != 4 or f.shape[0] != B * n_slots * N or f.shape[-1] != GC:
             raise RuntimeError('ring feature level must be contiguous [B*n_slots*6, H, W, G*C]')
     if len(frame_slots) != T:
         raise RuntimeError('frame_slots must name one slot per frame (T=%d)' % T)
-    hw = [(f.shape[1], f.shape[2]) for f in feats]
-    sslot = [N * h * w * GC for h, w in hw]
-    sv = [h * w * GC for h, w in hw]
     if out_layout == OUT_REF:
         out = torch.empty(Bp, Q, C, P, device=feats[0].device, dtype=torch.float32)
     else:
         out = torch.empty(B, Q, G, T * P, C, device=feats[0].device, dtype=torch.float32)
-    lib = _lib.load()
-    c_feats = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-    c_hw = (ctypes.c_int32 * (2 * L))(*[v for pair in hw for v in pair])
-    c_ss = (ctypes.c_int64 * L)(*sslot)
-    c_sv = (ctypes.c_int64 * L)(*sv)
+    levels, strides = _pyramid(feats, N, G)          # (stride_bo: one ring slot)
     c_slots = (ctypes.c_int32 * T)(*[int(s) for s in frame_slots])
-    st = lib.sbev_msmv_fwd_ring(c_feats, c_hw, L, _feat_dtype(feats), Bp, N, C, Q, P, G, c_ss, C, c_sv, GC,
-                                _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), _ptr(out),
-                                out_layout, T, G, c_slots, n_slots, _stream())
+    st = _lib.load().sbev_msmv_fwd_ring(*levels, _feat_dtype(feats), Bp, N, C, Q, P, *strides,
+                                        _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), _ptr(out),
+                                        out_layout, T, G, c_slots, n_slots, _stream())
     _lib.check(st, 'sbev_msmv_fwd_ring')
     return out
 
@@ -290,21 +275,17 @@ def sample_mix(levels, B, T, G, sampling_locations, scale_weights, params, out_p
     L = len(feats)
     if not sample_mix_supported(L, C, P, T, G):
         raise RuntimeError('sample_mix: shape not covered by the fused kernel (L=%d C=%d P=%d T=%d)' % (L, C, P, T))
-    hw = [(f.shape[1], f.shape[2]) for f in feats]
     params = params.contiguous()
     if params.dtype != torch.float32 or params.numel() != B * Q * G * (C * C + out_points * T * P):
         raise RuntimeError('sample_mix: params must be fp32 [B, Q, G*(C*C + out_points*T*P)]')
     y = torch.empty(B, Q, G * out_points * C, device=params.device, dtype=torch.float32)
-    c_feats = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats])
-    c_hw = (ctypes.c_int32 * (2 * L))(*[v for pair in hw for v in pair])
-    c_sbo = (ctypes.c_int64 * L)(*[N * h * w * GC for h, w in hw])
-    c_sv = (ctypes.c_int64 * L)(*[h * w * GC for h, w in hw])
+    levels, strides = _pyramid(feats, N, G)
     c_slots = (ctypes.c_int32 * T)(*[int(v) for v in frame_slots]) if frame_slots is not None else None
     if order is not None:
         _need_device(order)
         if order.dtype != torch.int32 or order.numel() != B * Q or not order.is_contiguous():
             raise RuntimeError('sample_mix: order must be a contiguous int32 permutation of the B*Q rows')
-    st = _lib.load().sbev_sample_mix_f32_ordered(c_feats, c_hw, L, _feat_dtype(feats), B, N, Q, T, G, P, C, c_sbo, C, c_sv, GC,
+    st = _lib.load().sbev_sample_mix_f32_ordered(*levels, _feat_dtype(feats), B, N, Q, T, G, P, C, *strides[1:],
                                                  _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), c_slots, n_slots,
                                                  _ptr(params), _ptr(y), out_points, 1e-5, _ptr(order) if order is not None else None, _stream())
     _lib.check(st, 'sbev_sample_mix_f32')

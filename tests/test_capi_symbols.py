@@ -66,6 +66,144 @@ def test_argument_validation_without_gpu(lib):
     assert lib.sbev_project_select(None, None, 0, 4, 1, 6, 4, 4, 1.0, 1.0, 1e-5, None, None, None, None, None) == 0
 
 
+def _sampler_entry_points(lib):
+    """The eight entry points that take a feature pyramid + sample points, each as call(**overrides) over ONE shared description
+    (fake pointers: validation returns before any HIP call).  Base: 4 levels of 4 x 4 pixels, grouped channels-last [B*T*N, H, W, G*C]
+    with B, T, G, N, C, Q, P = 1, 2, 4, 6, 64, 3, 4, mixing layout, a 2-slot ring."""
+    M = 6                                                  # array capacity: one more than SBEV_MAX_LEVELS, for the L = 6 row
+    base = dict(L=4, hw=[4, 4] * M, dtype=0, B=1, T=2, G=4, N=6, C=64, Q=3, P=4, gdiv=4, feats=[0x1000] * M, gfeats=[0x1000] * M,
+                sbo=[6 * 16 * 256] * M, sg=64, sv=[16 * 256] * M, spx=256, ptr=0x1000, layout=1, slots=[0, 1], n_slots=2,
+                Pout=128, up=9, order=None)
+
+    def args(o):
+        d = dict(base, **o)
+        d.setdefault('Bp', d['B'] * d['T'] * d['G'])
+        arr = lambda ct, v: None if v is None else (ct * len(v))(*v)
+        d.update(feats=arr(ctypes.c_void_p, d['feats']), gfeats=arr(ctypes.c_void_p, d['gfeats']), hw=arr(ctypes.c_int32, d['hw']),
+                 sbo=arr(ctypes.c_int64, d['sbo']), sv=arr(ctypes.c_int64, d['sv']), slots=arr(ctypes.c_int32, d['slots']),
+                 ptr=ctypes.c_void_p(d['ptr']), order=None if d['order'] is None else ctypes.c_void_p(d['order']))
+        d['pyr'] = (d['gdiv'], d['sbo'], d['sg'], d['sv'], d['spx'], d['ptr'], d['ptr'])      # ... gdiv, strides, loc, weights
+        return d
+
+    def fwd(d, ring):
+        tail = (d['slots'], d['n_slots'], None) if ring else (None,)
+        return (lib.sbev_msmv_fwd_ring if ring else lib.sbev_msmv_fwd)(
+            d['feats'], d['hw'], d['L'], d['dtype'], d['Bp'], d['N'], d['C'], d['Q'], d['P'], *d['pyr'], d['ptr'], d['layout'], d['T'], d['G'], *tail)
+
+    def bwd(d, ex):
+        mid = (d['layout'], d['T'], d['G']) if ex else ()
+        return (lib.sbev_msmv_bwd_ex if ex else lib.sbev_msmv_bwd)(
+            d['feats'], d['gfeats'], d['hw'], d['L'], d['Bp'], d['N'], d['C'], d['Q'], d['P'], *d['pyr'], d['ptr'], *mid, d['ptr'], d['ptr'], None)
+
+    def mix(d, pairs, ordered):
+        fn = getattr(lib, 'sbev_sample_mix_' + ('pairs_f16' if pairs else 'f32') + ('_ordered' if ordered else ''))
+        tail = ((d['up'],) if pairs else ()) + ((d['order'],) if ordered else ()) + (None,)
+        return fn(d['feats'], d['hw'], d['L'], d['dtype'], d['B'], d['N'], d['Q'], d['T'], d['G'], d['P'], d['C'], *d['pyr'][1:],
+                  d['slots'], d['n_slots'], d['ptr'], d['ptr'], d['Pout'], 1e-5, *tail)
+
+    return {'fwd': lambda **o: fwd(args(o), False), 'fwd_ring': lambda **o: fwd(args(o), True),
+            'bwd': lambda **o: bwd(args(o), False), 'bwd_ex': lambda **o: bwd(args(o), True),
+            'mix': lambda **o: mix(args(o), False, False), 'mix_ordered': lambda **o: mix(args(o), False, True),
+            'mix_pairs': lambda **o: mix(args(o), True, False), 'mix_pairs_ordered': lambda **o: mix(args(o), True, True)}
+
+
+def test_sampler_entry_points_refusal_table(lib):
+    """What each of the eight pyramid-taking entry points answers to a table of good and bad descriptions, status and message.  The three
+    implementations behind them do NOT check the same things (the backward accepts any C >= 1 and checks neither strides nor maps; the
+    fused launch needs every slab below the buffer limit; only the forward validates the levels of an empty call): those differences
+    are behaviour and are pinned here.  No row reaches a launch: a refusal returns first, an accepted row is an empty call (B = 0 or
+    Q = 0)."""
+    call = _sampler_entry_points(lib)
+    FWD, BWD = ('fwd', 'fwd_ring'), ('bwd', 'bwd_ex')
+    MIX = ('mix', 'mix_ordered', 'mix_pairs', 'mix_pairs_ordered')
+    OK = (0, b'')
+    hw_at = lambda l, h, w: [4, 4] * l + [h, w] + [4, 4] * (5 - l)          # level l is h x w, the others 4 x 4
+    at = lambda l, v, rest: [rest] * l + [v] + [rest] * (5 - l)
+    big, mid = 8192, 2048            # with N = 1: 8192^2 pixels of 256 elements = 2^34 elements; 2048^2 of them = 2^30 (4 GiB of fp32)
+    unsupported = (-1, b'sbev_sample_mix_f32: needs L in {4,5}')
+    table = [
+        # (overrides, {entry points: (status, substring of sbev_last_error())})
+        (dict(B=0), {FWD + BWD + MIX: OK}),
+        (dict(Q=0), {FWD + BWD + MIX: OK}),
+        (dict(B=0, hw=hw_at(1, 0, 4)), {FWD: (-1, b'sbev_msmv_fwd: level 1 has empty map'), BWD + MIX: OK}),
+        (dict(B=0, feats=at(1, 0, 0x1000)), {FWD + BWD + MIX: OK}),
+        (dict(hw=None), {FWD: (-1, b'sbev_msmv_fwd: null descriptor array'), BWD: (-1, b'sbev_msmv_bwd: null descriptor array'),
+                         MIX: (-1, b'sbev_sample_mix_f32: null descriptor array')}),
+        (dict(B=0, sbo=None), {FWD: (-1, b'sbev_msmv_fwd: null descriptor array'), BWD: (-1, b'sbev_msmv_bwd: null descriptor array'),
+                               MIX: (-1, b'sbev_sample_mix_f32: null descriptor array')}),
+        (dict(B=0, feats=None), {FWD + BWD + MIX: (-1, b'null descriptor array')}),
+        (dict(B=0, sv=None), {FWD + BWD + MIX: (-1, b'null descriptor array')}),
+        (dict(B=0, gfeats=None), {('bwd',): (-1, b'sbev_msmv_bwd: null descriptor array'), ('bwd_ex',): OK}),      # frozen features: _ex only
+        (dict(L=0), {FWD: (-1, b'sbev_msmv_fwd: L=0 not in 1..5'), BWD: (-1, b'sbev_msmv_bwd: L=0'), MIX: unsupported}),
+        (dict(L=6), {FWD: (-1, b'sbev_msmv_fwd: L=6 not in 1..5'), BWD: (-1, b'sbev_msmv_bwd: L=6'), MIX: unsupported}),
+        (dict(B=0, L=3), {FWD + BWD: OK, MIX: unsupported}),
+        (dict(P=33), {FWD: (-1, b'sbev_msmv_fwd: num_point exceed limits (P=33 > 32)'), BWD: (-1, b'sbev_msmv_bwd: num_point exceed limits (P=33'),
+                      MIX: unsupported}),
+        (dict(P=0), {FWD + BWD: (-1, b'num_point exceed limits'), MIX: unsupported}),
+        (dict(B=0, C=6), {FWD: (-1, b'sbev_msmv_fwd: C=6 must be a positive multiple of 4'), BWD: OK, MIX: unsupported}),
+        (dict(C=0), {FWD: (-1, b'sbev_msmv_fwd: C=0 must be'), BWD: (-1, b'sbev_msmv_bwd: bad sizes'), MIX: unsupported}),
+        (dict(N=0), {FWD: (-1, b'sbev_msmv_fwd: bad sizes'), BWD: (-1, b'sbev_msmv_bwd: bad sizes'), MIX: (-1, b'sbev_sample_mix_f32: bad sizes')}),
+        (dict(gdiv=0), {FWD: (-1, b'sbev_msmv_fwd: bad sizes'), BWD: (-1, b'sbev_msmv_bwd: bad sizes')}),
+        (dict(dtype=3), {FWD: (-1, b'sbev_msmv_fwd: feat_dtype 3'), MIX: (-1, b'sbev_sample_mix_f32: feat_dtype 3')}),
+        (dict(hw=hw_at(1, 0, 4)), {FWD: (-1, b'sbev_msmv_fwd: level 1 has empty map'), MIX: (-1, b'sbev_sample_mix_f32: level 1')}),
+        (dict(feats=at(1, 0, 0x1000)), {FWD: (-1, b'sbev_msmv_fwd: feats[1] is null'), BWD: (-1, b'sbev_msmv_bwd: level 1 pointer is null'),
+                                        MIX: (-1, b'sbev_sample_mix_f32: ')}),
+        (dict(gfeats=at(2, 0, 0x1000)), {BWD: (-1, b'sbev_msmv_bwd: level 2 pointer is null')}),
+        (dict(ptr=0), {FWD: (-1, b'sbev_msmv_fwd: null loc/weights/out'), BWD: (-1, b'sbev_msmv_bwd: null pointer'),
+                       MIX: (-1, b'sbev_sample_mix_f32: null pointer')}),
+        # strides: multiples of 4 elements for the forward and the fused launch (16-byte taps); the backward does not ask
+        (dict(B=0, spx=258), {FWD: (-1, b'sbev_msmv_fwd: pixel/group strides must be multiples of 4'), BWD: OK,
+                              MIX: (-1, b'sbev_sample_mix_f32: pixel/group strides must be multiples of 4')}),
+        (dict(B=0, sg=66), {FWD: (-1, b'sbev_msmv_fwd: pixel/group strides'), BWD: OK, MIX: (-1, b'sbev_sample_mix_f32: pixel/group strides')}),
+        (dict(B=0, sv=at(1, 4098, 4096)), {FWD: (-1, b'sbev_msmv_fwd: level 1 strides must be multiples of 4 elements'), BWD + MIX: OK}),
+        (dict(sv=at(1, 4098, 4096)), {FWD: (-1, b'sbev_msmv_fwd: level 1 strides'), MIX: (-1, b'sbev_sample_mix_f32: level 1 strides')}),
+        (dict(sbo=at(3, 6 * 4096 + 2, 6 * 4096)), {FWD: (-1, b'sbev_msmv_fwd: level 3 strides'), MIX: (-1, b'sbev_sample_mix_f32: level 3 strides')}),
+        (dict(sv=at(0, -4096, 4096)), {FWD: (-1, b'sbev_msmv_fwd: level 0: one (sample-batch) slab spans'), MIX: (-1, b'one (sample-batch) slab must stay below 2 GiB')}),
+        # one slab beyond the 32-bit in-slab offset: refused by the forward also when the call is empty
+        (dict(N=1, hw=hw_at(0, big, big), sv=at(0, big * big * 256, 4096)),
+         {FWD: (-1, b'the in-slab tap offset is 32-bit (limit 2^31 - 1)'), MIX: (-1, b'one (sample-batch) slab must stay below 2 GiB')}),
+        (dict(B=0, N=1, hw=hw_at(0, big, big), sv=at(0, big * big * 256, 4096)), {FWD: (-1, b'sbev_msmv_fwd: level 0: one (sample-batch) slab spans'), BWD + MIX: OK}),
+        # one slab between the buffer limit (2^31 - 1 BYTES) and 2^31 elements: the forward has its global-load path, the fused launch refuses
+        (dict(B=0, N=1, hw=hw_at(2, mid, mid), sv=at(2, mid * mid * 256, 4096)), {FWD + BWD + MIX: OK}),
+        (dict(N=1, hw=hw_at(2, mid, mid), sv=at(2, mid * mid * 256, 4096)), {MIX: (-1, b'one (sample-batch) slab must stay below 2 GiB')}),
+        (dict(layout=7), {FWD: (-1, b'sbev_msmv_fwd: out_layout 7'), ('bwd_ex',): (-1, b'sbev_msmv_bwd: grad_out_layout 7')}),
+        (dict(Bp=7), {FWD: (-1, b"sbev_msmv_fwd: B'=7 is not B*T*G (T=2, G=4)"), ('bwd_ex',): (-1, b"sbev_msmv_bwd: B'=7 is not B*T*G (T=2, G=4)")}),
+        (dict(Bp=7, Q=0, layout=0), {FWD + BWD: OK}),                        # reference layout: T and G are not read
+        (dict(Bp=8, T=0), {FWD: (-1, b"sbev_msmv_fwd: B'=8 is not B*T*G (T=0, G=4)"), ('bwd_ex',): (-1, b"sbev_msmv_bwd: B'=8 is not B*T*G")}),
+        (dict(Bp=1 << 31), {FWD: (-1, b"sbev_msmv_fwd: B'*Q = 6442450944 too large for one launch")}),
+        (dict(Bp=1 << 32), {BWD: (-1, b"sbev_msmv_bwd: B'*Q too large")}),
+        (dict(B=1 << 29), {MIX: (-1, b'sbev_sample_mix_f32: too many items')}),
+        (dict(Pout=64), {MIX: (-1, b'sbev_sample_mix_f32: built for 128 out points')}),
+        # the ring
+        (dict(B=0, slots=None), {('fwd_ring',): (-1, b'sbev_msmv_fwd_ring: frame_slots is null'), MIX: OK}),
+        (dict(slots=[0, 2]), {('fwd_ring',): (-1, b'sbev_msmv_fwd_ring: frame_slots[1] = 2 out of range'), MIX: (-1, b'sbev_sample_mix_f32: frame_slots[1]')}),
+        (dict(slots=[-1, 1]), {('fwd_ring',): (-1, b'sbev_msmv_fwd_ring: frame_slots[0] = -1 out of range'), MIX: (-1, b'sbev_sample_mix_f32: frame_slots[0]')}),
+        (dict(B=0, slots=[0, 2]), {('fwd_ring',) + MIX: OK}),                # the slot table of an empty call is not read
+        (dict(n_slots=1), {('fwd_ring',): (-1, b'sbev_msmv_fwd_ring: need 1 <= T <= 16, n_slots >= T, gdiv == G'), MIX: (-1, b'T <= 16, n_slots >= T')}),
+        (dict(T=17, slots=list(range(17)), n_slots=17), {('fwd_ring',): (-1, b'sbev_msmv_fwd_ring: need 1 <= T <= 16'), MIX: unsupported}),
+        (dict(gdiv=1), {('fwd_ring',): (-1, b'sbev_msmv_fwd_ring: need 1 <= T <= 16, n_slots >= T, gdiv == G')}),
+        (dict(layout=0, T=2, G=2), {('fwd_ring',): (-1, b'sbev_msmv_fwd_ring: need')}),                                     # gdiv = 4 != G
+        # the fused launch's own arguments
+        (dict(B=0, up=101), {('mix_pairs', 'mix_pairs_ordered'): (-1, b'sbev_sample_mix_pairs_f16: up_log2=101'), ('mix', 'mix_ordered'): OK}),
+        (dict(up=-101), {('mix_pairs', 'mix_pairs_ordered'): (-1, b'sbev_sample_mix_pairs_f16: up_log2=-101')}),
+        (dict(order=0x1002), {('mix_ordered', 'mix_pairs_ordered'): (-1, b'sbev_sample_mix_f32: order must be 4-byte aligned')}),
+        (dict(B=0, order=0x1002), {MIX: OK}),
+    ]
+    for overrides, expected in table:
+        for names, (status, text) in expected.items():
+            for name in names:
+                got = call[name](**overrides)
+                err = lib.sbev_last_error() if got != 0 else b''
+                assert got == status and text in err, (name, overrides, got, err)
+    # the shape / slab predicates the decoder plans with agree with the launch's refusals
+    i32, i64 = lambda v: (ctypes.c_int32 * len(v))(*v), lambda v: (ctypes.c_int64 * len(v))(*v)
+    assert lib.sbev_sample_mix_slabs_ok(i32([4, 4] * 4), 4, 0, 6, 64, i64([4096] * 4), 256) == 1
+    assert lib.sbev_sample_mix_slabs_ok(i32(hw_at(2, mid, mid)), 4, 0, 1, 64, i64(at(2, mid * mid * 256, 4096)), 256) == 0
+    assert lib.sbev_sample_mix_slabs_ok(i32(hw_at(2, mid, mid)), 4, 1, 1, 64, i64(at(2, mid * mid * 256, 4096)), 256) == 1      # bf16: 2^31 - 376 bytes
+    assert lib.sbev_sample_mix_slabs_ok(None, 4, 0, 6, 64, i64([4096] * 4), 256) == 0
+    assert lib.sbev_sample_mix_slabs_ok(i32([4, 4] * 4), 6, 0, 6, 64, i64([4096] * 4), 256) == 0
+
+
 def test_product_has_no_cpu_fallback():
     import torch
     from sparsebev_amd import ops

@@ -38,21 +38,16 @@ def main():
         import ctypes
         from sparsebev_amd import _lib
         lib = _lib.load()
-        Ln = len(feats)
         Bp, N, _, _, C = feats[0].shape
         _, Qn, Pn, _ = loc.shape
         gout = torch.randn(Bp, Qn, C, Pn, device=loc.device)
         gfeats = [torch.zeros_like(f) for f in feats]
         gloc, gw = torch.empty_like(loc), torch.empty_like(wbp)
-        hw = [(f.shape[2], f.shape[3]) for f in feats]
-        c_feats = (ctypes.c_void_p * Ln)(*[f.data_ptr() for f in feats])
-        c_gfeats = (ctypes.c_void_p * Ln)(*[f.data_ptr() for f in gfeats])
-        c_hw = (ctypes.c_int32 * (2 * Ln))(*[v for pair in hw for v in pair])
-        c_sbo = (ctypes.c_int64 * Ln)(*[N * h * w * C for h, w in hw])
-        c_sv = (ctypes.c_int64 * Ln)(*[h * w * C for h, w in hw])
+        (c_feats, c_hw, Ln), strides = ops._pyramid(feats, N)
+        c_gfeats = ops._level_ptrs(gfeats)
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        fn = lambda: lib.sbev_msmv_bwd(c_feats, c_gfeats, c_hw, Ln, Bp, N, C, Qn, Pn, 1, c_sbo, 0, c_sv, C, p(loc), p(wbp), p(gout), p(gloc), p(gw), st)
+        fn = lambda: lib.sbev_msmv_bwd(c_feats, c_gfeats, c_hw, Ln, Bp, N, C, Qn, Pn, *strides, p(loc), p(wbp), p(gout), p(gloc), p(gw), st)
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
