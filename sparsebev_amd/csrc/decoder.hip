@@ -351,11 +351,13 @@ struct Step {
         return hip_ok(hipEventRecord(*ev, ax.stream), "hipEventRecord");
     }
     int join(hipEvent_t ev) { return ev ? hip_ok(hipStreamWaitEvent(s_main, ev, 0), "hipStreamWaitEvent") : SBEV_OK; }      // null: nothing was forked
-    int lazy_move(int layer) {
-        if (!lazy) return SBEV_OK;
-        return sbev::launch_lazy_relayout(lplan, lazy->table, lazy->index, lazy->src, const_cast<void* const*>(feats_nhwc), feat_esize(),
-                                          b.touch_need, b.touch_done, layer == 0, layer + 1 == c.num_layers, s_main);
+    // this layer's on-demand relayout as ONE value, for the stand-alone move or the generator's prologue (plan null: the step has none)
+    sbev::LazyScan lazy_scan(int layer) const {
+        if (!lazy) return {};
+        return {&lplan, lazy->table, lazy->index, lazy->src, const_cast<void* const*>(feats_nhwc), feat_esize(), b.touch_need, b.touch_done,
+                layer + 1 == c.num_layers};
     }
+    int lazy_move(const sbev::LazyScan& scan, bool first) { return scan.plan ? sbev::launch_lazy_relayout(scan, first, s_main) : SBEV_OK; }
 
     // parameter generator in the 3 x bf16 mode: x1 is split once per layer and streamed past W-stationary strips
     int generator_bf16x3(sbev_stream_t st) {
@@ -365,8 +367,8 @@ struct Step {
         return sbev_linear_bf16x3_strip(x2, w.pg_w2, w.pg_b, b.params, p.BQ, p.pgN, D, p.pgN, 0, st);
     }
     // split-image modes: x1 -> image fragments (a launch of its own unless the attention chain wrote them) -> Y = X W^T + b;
-    // scan_layer > 0: that layer's on-demand relayout scan inside the generator
-    int generator_bf16s(sbev_stream_t st, int scan_layer) {
+    // scan non-null: the layer's on-demand relayout scan inside the generator
+    int generator_bf16s(sbev_stream_t st, const sbev::LazyScan* scan) {
         uint16_t* xs = reinterpret_cast<uint16_t*>(b.x1s);
         if (p.pack_launch) {
             // fp16 hi + lo: x1 scaled by one power of two (its maximum -> [2^14, 2^15))
@@ -374,15 +376,11 @@ struct Step {
             TRY(p.nimg >= 4 ? sbev_pack_f16s_frags(b.x1, D, xs, const_cast<float*>(w.pg_xscale), (int)p.BQ, D, 2, st)
                             : sbev_pack_bf16s_frags(b.x1, D, xs, (int)p.BQ, D, p.nimg, st));
         }
-        sbev::LazyScan lz{};
-        if (scan_layer > 0)
-            lz = sbev::LazyScan{&lplan, lazy->table, lazy->index, lazy->src, const_cast<void* const*>(feats_nhwc), feat_esize(),
-                                b.touch_need, b.touch_done, scan_layer + 1 == c.num_layers};
-        return sbev::linear_gen_split(xs, w.pg_xscale, w.pg_ws, w.pg_wdown, w.pg_b, b.params, p.BQ, p.pgN, D, p.pgN, 0, p.nimg, p.gen_ws,
-                                      scan_layer > 0 ? &lz : nullptr, reinterpret_cast<hipStream_t>(st));
+        return sbev::linear_gen_split(xs, w.pg_xscale, w.pg_ws, w.pg_wdown, w.pg_b, b.params, p.BQ, p.pgN, D, p.pgN, 0, p.nimg, p.gen_ws, scan,
+                                      reinterpret_cast<hipStream_t>(st));
     }
-    int generator(sbev_stream_t st, int scan_layer) {
-        if (p.nimg) return generator_bf16s(st, scan_layer);
+    int generator(sbev_stream_t st, const sbev::LazyScan* scan) {
+        if (p.nimg) return generator_bf16s(st, scan);
         if (c.gemm_mode == SBEV_GEMM_BF16X3) return generator_bf16x3(st);
         return sbev_linear_f32(b.x1, w.pg_w, w.pg_b, nullptr, b.params, p.BQ, p.pgN, D, D, D, p.pgN, 0, st);
     }
@@ -403,16 +401,21 @@ struct Step {
     }
 
     // out-projection, row chains: the split-K slabs are left for the tail chain (`used` of them), or folded inside the launch into ONE row block, b.folded
-    int out_projection_slabs(int* used, bool* folded) {
-        // (the fold needs the fault word to report a row tile that never completed)
-        const bool fold = p.fold_wanted && sbev::out_fold_shape_ok(p.BQ, p.mixN) && sbev::chain_fault_word_ready();
-        if (p.nimg)
-            return sbev::launch_splitk_slabs_bf16s(b.mixed, w.op_wp, p.BQ, p.mixN, p.mixN, p.nimg, b.slabs, used, s_main, p.out8_min_rows, mixed_up,
-                                                   w.op_nscale, p.nimg >= 4, nullptr, fold ? b.pair_sync + sbev::chain_fold_sync_offset(p.BQ) : nullptr,
-                                                   fold ? b.folded : nullptr, folded);
+    int out_projection_slabs(sbev::OutProjResult* r) {
+        *r = {0, false};
+        if (p.nimg) {
+            // fp16 modes: `mixed` holds the pairs of mixed 2^mixed_up (gather_and_mix); bf16 modes: fp32, split in the kernel as it is
+            const bool f16 = p.nimg >= 4;
+            // (the fold needs the fault word to report a row tile that never completed)
+            const bool fold = p.fold_wanted && sbev::out_fold_shape_ok(p.BQ, p.mixN) && sbev::chain_fault_word_ready();
+            const sbev::OutProj o{{f16 ? sbev::SplitImageX::F16_PAIRS : sbev::SplitImageX::F32_HOST_EXP, b.mixed, p.mixN, f16 ? mixed_up : 0, nullptr},
+                                  w.op_wp, f16 ? w.op_nscale : nullptr, p.BQ, p.mixN, p.nimg, b.slabs, p.out8_min_rows,
+                                  fold ? b.pair_sync + sbev::chain_fold_sync_offset(p.BQ) : nullptr, fold ? b.folded : nullptr};
+            return sbev::launch_out_proj_slabs(o, r, s_main);
+        }
         if (c.gemm_mode == SBEV_GEMM_BF16X3)
-            return sbev::launch_splitk_slabs_bf16x3(b.mixed, w.op_w2, p.BQ, D, p.mixN, p.mixN, p.splits, b.slabs, used, s_main);
-        return sbev::launch_splitk_slabs(b.mixed, w.op_w, p.BQ, D, p.mixN, p.mixN, p.mixN, p.splits, b.slabs, used, s_main);
+            return sbev::launch_splitk_slabs_bf16x3(b.mixed, w.op_w2, p.BQ, D, p.mixN, p.mixN, p.splits, b.slabs, &r->used, s_main);
+        return sbev::launch_splitk_slabs(b.mixed, w.op_w, p.BQ, D, p.mixN, p.mixN, p.mixN, p.splits, b.slabs, &r->used, s_main);
     }
     // out-projection, op by op: + bias + x1, norm2 -> x2                         (:171)
     int out_projection(sbev_stream_t st) {
@@ -438,13 +441,13 @@ struct Step {
                                     p.nimg >= 4 ? reinterpret_cast<uint16_t*>(b.x1s) : nullptr, p.nimg >= 4 ? w.pg_xscale : nullptr, b.pair_sync,
                                     lazy ? &lplan : nullptr, lazy ? b.touch_need : nullptr));
         const bool ride = p.scan_in_gen && layer > 0;
-        if (!ride) TRY(lazy_move(layer));      // (layer 0's move behind the generator instead of in front of it: measured equal, 537-539 both ways)
-        TRY(generator(stream, ride ? layer : -1));
+        const sbev::LazyScan scan = lazy_scan(layer);
+        if (!ride) TRY(lazy_move(scan, layer == 0));      // (layer 0's move behind the generator instead of in front of it: measured equal, 537-539 both ways)
+        TRY(generator(stream, ride ? &scan : nullptr));
         TRY(gather_and_mix(stream, p.order_mode != 0 ? b.order : nullptr));
-        int used = 0;
-        bool folded = false;      // the out-projection folded its slabs inside its launch: the tail reads ONE row block, b.folded
-        TRY(out_projection_slabs(&used, &folded));
-        TRY(sbev::launch_chain_tail(c, w, folded ? b.folded : b.slabs, used, b.x1, bbox, c.T > 1 ? vel_div : nullptr, b.x3, cls_of(layer), box_of(layer),
+        sbev::OutProjResult op;      // folded: the out-projection folded its slabs inside its launch, the tail reads ONE row block, b.folded
+        TRY(out_projection_slabs(&op));
+        TRY(sbev::launch_chain_tail(c, w, op.folded ? b.folded : b.slabs, op.used, b.x1, bbox, c.T > 1 ? vel_div : nullptr, b.x3, cls_of(layer), box_of(layer),
                                     layer + 1 < c.num_layers, b.x, b.qkvt, eps, s_main, b.pair_x, b.pair_sync));
         bbox = box_of(layer);
         return SBEV_OK;
@@ -470,13 +473,13 @@ struct Step {
         // fork: parameter generator (needs only x1) on the aux stream, beside the sampling chain
         hipEvent_t ev_pg = nullptr;
         if (p.fork_pg) TRY(fork_to_aux());
-        TRY(generator(p.fork_pg ? s_aux : stream, -1));
+        TRY(generator(p.fork_pg ? s_aux : stream, nullptr));
         if (p.fork_pg) TRY(record_on_aux(&ev_pg));
         // adaptive spatio-temporal sampling                                     (:170)
         TRY(sbev::launch_sample_and_project(bbox, b.so, p.soN, b.so + c.G * c.P * 3, p.soN, time_diff, lidar2img, c.pc_range,
                                             c.B, c.Q, c.T, c.N, c.G, c.P, c.L, c.image_h, c.image_w, c.eps_homo, b.loc, b.wbp,
                                             lazy ? &lplan : nullptr, lazy ? b.touch_need : nullptr, c.hw, s_main));
-        TRY(lazy_move(layer));
+        TRY(lazy_move(lazy_scan(layer), layer == 0));
         // gather + adaptive mixing (join: the generator's output is needed now), out-projection + norm2  (:171)
         TRY(gather_and_mix(stream, nullptr, ev_pg));
         TRY(out_projection(stream));

@@ -1609,63 +1609,68 @@ int reserve_lds(Kern k, int bytes, const char* what) {
     return SBEV_OK;
 }
 
-// K chunks of the out-projection: fill the 256 CUs with (64-row tile x chunk) workgroups in whole rounds, at least 8 slabs each
-int out_chunks(long long M, int K) {
-    static const int forced = getenv("SBEV_BF16S_OUT_CHUNKS") ? atoi(getenv("SBEV_BF16S_OUT_CHUNKS")) : 0;      // experiments
-    if (forced > 0 && forced <= K / 32 / 8) return forced;
-    const long long nrt = (M + 63) / 64;
-    const int max_s = K / 32 / 8 < 1 ? 1 : K / 32 / 8;
+// CUs of the current device, asked once per process; `if_unknown` where the query fails
+int device_cus(int if_unknown) {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+        return n;
+    }();
+    return cus >= 1 ? cus : if_unknown;
+}
+
+// reserve the kernel's dynamic LDS and launch it (512 threads) inside the optional HIP-event bracket (profile_kind: profile_begin's);
+// returns the reserve's status -- the launch itself is the caller's check_launch
+template <typename Args>
+int launch_lds(void (*kern)(Args), unsigned grid, int lds_bytes, hipStream_t s, const Args& args, const char* who, int profile_kind) {
+    const int st = reserve_lds(kern, lds_bytes, who);
+    if (st != SBEV_OK) return st;
+    hipEvent_t e0, e1;
+    const bool prof = sbev::profile_begin(s, &e0, &e1, profile_kind);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, s, args);
+    if (prof) sbev::profile_end(s, e0, e1, profile_kind);
+    return SBEV_OK;
+}
+
+// K chunks of an out-projection: the count (<= 64, <= max_s) whose tiles x chunks workgroups fill the 256 CUs best in whole rounds, the
+// smaller count on a tie; one_round: no more workgroups than CUs (more chunks would only add slabs for the consumer to sum)
+int fill_rounds(long long tiles, int max_s, bool one_round) {
     int best = 1;
     double best_eff = 0.0;
-    for (int s = 1; s <= 64 && s <= max_s; ++s) {
-        const long long wgs = nrt * s;
+    for (int s = 1; s <= 64 && s <= max_s && !(one_round && tiles * s > 256); ++s) {
+        const long long wgs = tiles * s;
         const double eff = (double)wgs / (double)(((wgs + 255) / 256) * 256);
         if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
     }
     return best;
 }
 
-// the 128-row kernel's plan: row tiles of <= 4 fragments (balanced), K chunks of >= 8 k-steps that fill the CUs in whole rounds
-struct Out4Plan { int ntm, base, rem, S; };
-Out4Plan out4_plan(long long M, int K) {
-    const int nfrag = (int)((M + 31) / 32);
-    Out4Plan p{};
-    p.ntm = (nfrag + 3) / 4;
-    p.base = nfrag / p.ntm;
-    p.rem = nfrag % p.ntm;
-    const int max_s = K / 16 / 8 < 1 ? 1 : K / 16 / 8;
-    p.S = 1;
-    double best_eff = 0.0;
-    for (int s = 1; s <= 64 && s <= max_s; ++s) {
-        const long long wgs = (long long)p.ntm * s;
-        const double eff = (double)wgs / (double)(((wgs + 255) / 256) * 256);
-        if (eff > best_eff + 1e-9) { best_eff = eff; p.S = s; }
-    }
-    return p;
+// the fp32-X kernel (gemm_bf16s_out3_kernel): 64-row tiles, chunks of >= 8 k-steps of 32
+int out_chunks(long long M, int K) {
+    static const int forced = getenv("SBEV_BF16S_OUT_CHUNKS") ? atoi(getenv("SBEV_BF16S_OUT_CHUNKS")) : 0;      // experiments
+    if (forced > 0 && forced <= K / 32 / 8) return forced;
+    return fill_rounds((M + 63) / 64, K / 32 / 8, false);
 }
 
-// the 256-row kernel's plan: row tiles of <= 8 fragments (balanced, >= 2), K chunks of >= 8 k-steps, ONE round of workgroups (more chunks
-// would only add slabs for the consumer to sum)
+// the pre-split kernels' plan: row tiles of <= max_frags 32-row fragments (balanced: `base`, the first `rem` one more), S chunks of >= 8
+// k-steps of 16.  128-row kernel: 4 fragments, whole rounds.  256-row kernel: 8 fragments (taken from >= 2 per tile), ONE round
 // (measured, samples/s with / without: 3200 rows 1289 / 1189, 3600 rows 506 / 481, 1600 rows 194.6 / 187.2; 900 rows 536.6 / 538.8 -- the
 // kernel itself is 4 us faster there too, but 4 row tiles x 64 chunks leave the tail 64 slabs to sum instead of 32: from 1024 rows)
+struct Out4Plan { int ntm, base, rem, S; };
+Out4Plan out_plan(long long M, int K, int max_frags, bool one_round) {
+    const int nfrag = (int)((M + 31) / 32);
+    Out4Plan p{};
+    p.ntm = (nfrag + max_frags - 1) / max_frags;
+    p.base = nfrag / p.ntm;
+    p.rem = nfrag % p.ntm;
+    p.S = fill_rounds(p.ntm, K / 16 / 8, one_round);
+    return p;
+}
+Out4Plan out4_plan(long long M, int K) { return out_plan(M, K, 4, false); }
+Out4Plan out8_plan(long long M, int K) { return out_plan(M, K, 8, true); }
 constexpr int OUT8_HARD_MIN = 1024;       // (workspaces are sized for the 256-row plan from here on, whatever the switch says later)
 int out8_clamp(int rows) { return rows <= 0 ? 0 : (rows < OUT8_HARD_MIN ? OUT8_HARD_MIN : rows); }
 std::atomic<int> g_out8_min_rows{out8_clamp(getenv("SBEV_OUT8_MIN_ROWS") ? atoi(getenv("SBEV_OUT8_MIN_ROWS")) : OUT8_HARD_MIN)};
-Out4Plan out8_plan(long long M, int K) {
-    const int nfrag = (int)((M + 31) / 32);
-    Out4Plan p{};
-    p.ntm = (nfrag + 7) / 8;
-    p.base = nfrag / p.ntm;
-    p.rem = nfrag % p.ntm;
-    const int max_s = K / 16 / 8 < 1 ? 1 : K / 16 / 8;
-    p.S = 1;
-    double best_eff = 0.0;
-    for (int s = 1; s <= 64 && s <= max_s && (long long)p.ntm * s <= 256; ++s) {
-        const double eff = (double)p.ntm * s / 256.0;
-        if (eff > best_eff + 1e-9) { best_eff = eff; p.S = s; }
-    }
-    return p;
-}
 bool out8_takes(long long M, int K, int mr) {      // mr: the caller's reading of g_out8_min_rows
     if (mr <= 0 || M < mr) return false;
     const Out4Plan p = out8_plan(M, K);
@@ -1745,6 +1750,23 @@ bool gen_weight_stationary_enabled() { return g_gen_ws.load(std::memory_order_re
 bool gen_ws_shape_ok(int64_t M, int K, int64_t ldy, int nimg) { return K == 16 * WS_KS && nimg != 3 && M * ldy * 4 < 0x7fffffffLL; }
 }  // namespace sbev
 
+// the kernel for a mode: nimg 2 / 3 = bf16x3 / bf16x6 (MODE 0 / 1), 4 / 5 = fp16 with 3 / 4 image products (MODE 2 / 3)
+static auto gen_ws_kernel(int nimg, bool relu) -> void (*)(GenWsArgs) {      // (two images only: gen_ws_shape_ok)
+    switch (nimg) {
+        case 2: return relu ? gemm_f16s_gen_ws_kernel<0, true> : gemm_f16s_gen_ws_kernel<0, false>;
+        case 4: return relu ? gemm_f16s_gen_ws_kernel<2, true> : gemm_f16s_gen_ws_kernel<2, false>;
+        default: return relu ? gemm_f16s_gen_ws_kernel<3, true> : gemm_f16s_gen_ws_kernel<3, false>;
+    }
+}
+static auto gen3_kernel(int nimg, int rf) -> void (*)(GenArgs) {             // rf: 4 = 256-row tiles, 2 = 128-row tiles
+    switch (nimg) {
+        case 3: return rf == 4 ? gemm_bf16s_gen3_kernel<1, 4> : gemm_bf16s_gen3_kernel<1, 2>;
+        case 2: return rf == 4 ? gemm_bf16s_gen3_kernel<0, 4> : gemm_bf16s_gen3_kernel<0, 2>;
+        case 4: return rf == 4 ? gemm_bf16s_gen3_kernel<2, 4> : gemm_bf16s_gen3_kernel<2, 2>;
+        default: return rf == 4 ? gemm_bf16s_gen3_kernel<3, 4> : gemm_bf16s_gen3_kernel<3, 2>;
+    }
+}
+
 static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias, float* Y, int64_t M, int N, int K, int64_t ldy, int relu,
                       int nimg, const float* xscale, const float* colscale, bool weight_stationary, sbev_stream_t stream,
                       const sbev::LazyScan* lz = nullptr) {
@@ -1753,13 +1775,8 @@ static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias,
     SBEV_REQUIRE(Xs && Ws && Y && ldy >= N && ldy % 4 == 0, "sbev_linear_bf16s_gen: bad pointers / leading dimension");
     SBEV_REQUIRE((((uintptr_t)Xs | (uintptr_t)Ws | (uintptr_t)Y) & 15) == 0 && (!bias || (((uintptr_t)bias) & 15) == 0), "sbev_linear_bf16s_gen: 16-byte alignment");
     const int nfrag = (int)((M + 31) / 32);
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-        return n;
-    }();
+    const int cus = device_cus(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipEvent_t e0, e1;
     const bool ws = weight_stationary && sbev::gen_ws_shape_ok(M, K, ldy, nimg);
     SBEV_REQUIRE(!lz || ws, "generator: the on-demand relayout's scan rides in the weight-stationary kernel only");
     if (ws) {
@@ -1776,33 +1793,11 @@ static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias,
         GenWsArgs w{Xs, Ws, bias, Y, (int)M, N, (long long)ldy, relu, nrs, nfrag / nrs, nfrag % nrs, nct * nrs, colscale, xscale, 0, 4, {}};
         if (lz) {
             w.lazy_on = 1; w.lazy_esize = lz->esize;
-            LazyArgs& la = w.lazy;
-            la.table = lz->table; la.n_levels = lz->plan->n_levels; la.R = lz->plan->R; la.need = lz->need; la.done = lz->done;
-            la.first = 0; la.last = lz->last ? 1 : 0;
-            for (int l = 0; l < lz->plan->n_levels; ++l) {
-                la.index[l] = lz->table ? lz->index[l] : 0;
-                la.src[l] = lz->table ? nullptr : lz->src[l];
-                la.out[l] = lz->out[l];
-                la.S[l] = lz->plan->S[l]; la.tiles[l] = lz->plan->tiles[l]; la.base[l] = lz->plan->base[l];
-            }
-            la.base[lz->plan->n_levels] = lz->plan->base[lz->plan->n_levels];
+            fill_lazy_args(w.lazy, *lz, false);
         }
         const unsigned grid = (unsigned)(w.ntask < cus ? w.ntask : cus);
-        const int lds = WS_SLOTS * WS_FRAG;
-        int st;
-        const bool prof = sbev::profile_begin(s, &e0, &e1, 1);
-#define SBEV_LAUNCH_WS(MD)                                                                                  \
-        {                                                                                                   \
-            auto kern = relu ? gemm_f16s_gen_ws_kernel<MD, true> : gemm_f16s_gen_ws_kernel<MD, false>;       \
-            st = reserve_lds(kern, lds, "sbev_linear_bf16s_gen");                                           \
-            if (st != SBEV_OK) return st;                                                                   \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, w);                                     \
-        }
-        if (nimg == 2) SBEV_LAUNCH_WS(0)
-        else if (nimg == 4) SBEV_LAUNCH_WS(2)
-        else SBEV_LAUNCH_WS(3)
-#undef SBEV_LAUNCH_WS
-        if (prof) sbev::profile_end(s, e0, e1, 1);
+        const int st = launch_lds(gen_ws_kernel(nimg, relu != 0), grid, WS_SLOTS * WS_FRAG, s, w, "sbev_linear_bf16s_gen", 1);
+        if (st != SBEV_OK) return st;
         return sbev::check_launch("sbev_linear_bf16s_gen");
     }
     // 256-row tiles (wave = 128 x 64) carry 1.5x the MFMA work per operand byte; 128-row tiles only where they fill the chip
@@ -1836,24 +1831,8 @@ static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias,
         const unsigned gridc = (unsigned)(pc * ntm);
         const int bias_bytes = (int)((nc + pc - 1) / pc) * G_COLS * 4 * (nimg >= 4 ? 2 : 1);     // (fp16 modes: + the column scales)
         const int lds = ring_bytes + bias_bytes;
-        int st;
-        const bool prof = sbev::profile_begin(s, &e0, &e1, 1);
-#define SBEV_LAUNCH_GEN(NI, RFV)                                                                            \
-        {                                                                                                   \
-            st = reserve_lds(gemm_bf16s_gen3_kernel<NI, RFV>, lds, "sbev_linear_bf16s_gen");                \
-            if (st != SBEV_OK) return st;                                                                   \
-            hipLaunchKernelGGL((gemm_bf16s_gen3_kernel<NI, RFV>), dim3(gridc), dim3(512), lds, s, ac);      \
-        }
-        if (nimg == 3 && rf == 4) SBEV_LAUNCH_GEN(1, 4)
-        else if (nimg == 3) SBEV_LAUNCH_GEN(1, 2)
-        else if (nimg == 2 && rf == 4) SBEV_LAUNCH_GEN(0, 4)
-        else if (nimg == 2) SBEV_LAUNCH_GEN(0, 2)
-        else if (nimg == 4 && rf == 4) SBEV_LAUNCH_GEN(2, 4)
-        else if (nimg == 4) SBEV_LAUNCH_GEN(2, 2)
-        else if (rf == 4) SBEV_LAUNCH_GEN(3, 4)
-        else SBEV_LAUNCH_GEN(3, 2)
-#undef SBEV_LAUNCH_GEN
-        if (prof) sbev::profile_end(s, e0, e1, 1);
+        const int st = launch_lds(gen3_kernel(nimg, rf), gridc, lds, s, ac, "sbev_linear_bf16s_gen", 1);
+        if (st != SBEV_OK) return st;
     }
     return sbev::check_launch("sbev_linear_bf16s_gen");
 }
@@ -1907,8 +1886,8 @@ bool out_fold_enabled() { return g_out_fold.load(std::memory_order_relaxed) != 0
 bool out_fold_shape_ok(long long M, int K) {
     if (M < 1 || M > 4096) return false;
     const Out4Plan pl = out4_plan(M, K);
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
+    const int cus = device_cus(0);
+    if (cus < 1) return false;
     return pl.S > 1 && (long long)pl.ntm * pl.S <= cus && pl.ntm <= 64 && (long long)pl.S * M * 1024 < 0x7fffffffLL;
 }
 // the fold's fault words (see g_fold_fault_host): `host_word_dev` = device address of the decoder's host-mapped fault word
@@ -1924,81 +1903,82 @@ long long out_fold_timeouts() {
     return (long long)v;
 }
 
-int launch_splitk_slabs_bf16s(const float* X, const uint16_t* Wp, int64_t M, int K, int64_t ldx, int nimg, float* slabs, int* used,
-                              hipStream_t s, int out8_min_rows, int x_up_log2, const float* nscale, bool x_pairs, const float* xdev,
-                              unsigned* fold_sync, float* folded, bool* did_fold) {
-    if (did_fold) *did_fold = false;
-    SBEV_REQUIRE(nimg < 4 || nscale, "sbev_linear_splitk_f16s: null scale pointer");
-    SBEV_REQUIRE(!xdev || (nimg >= 4 && !x_pairs), "sbev_linear_splitk_f16s: a device-side X scale needs an fp16 mode and fp32 X");
-    if (x_pairs) {                              // fp16 modes with the pre-split operand: 128-row tiles
-        SBEV_REQUIRE(nimg >= 4, "sbev_linear_splitk_f16s: pre-split X needs an fp16 mode");
-        const bool big = out8_takes(M, K, out8_min_rows);                            // batch shapes: 256-row tiles (a third less operand delivery)
+static auto pairs_kernel_for(int nimg, bool rows256) -> void (*)(Out4Args) {      // pre-split X: fp16 modes only (nimg 4 / 5)
+    if (rows256) return nimg == 4 ? gemm_bf16s_out8_kernel<2> : gemm_bf16s_out8_kernel<3>;
+    return nimg == 4 ? gemm_bf16s_out4_kernel<2> : gemm_bf16s_out4_kernel<3>;
+}
+static auto out3_kernel(int nimg) -> void (*)(OutArgs) {
+    switch (nimg) {
+        case 3: return gemm_bf16s_out3_kernel<1>;
+        case 2: return gemm_bf16s_out3_kernel<0>;
+        case 4: return gemm_bf16s_out3_kernel<2>;
+        default: return gemm_bf16s_out3_kernel<3>;
+    }
+}
+
+int launch_out_proj_slabs(const OutProj& o, OutProjResult* r, hipStream_t s) {
+    *r = OutProjResult{0, false};
+    const int64_t M = o.M;
+    const int K = o.K;
+    const bool f16 = o.nimg >= 4;
+    SBEV_REQUIRE(!f16 || o.nscale, "sbev_linear_splitk_f16s: null scale pointer");
+    SBEV_REQUIRE(o.X.form != SplitImageX::F32_DEV_SCALE || (f16 && o.X.dev_scale), "sbev_linear_splitk_f16s: a device-side X scale needs an fp16 mode and fp32 X");
+    if (o.X.form == SplitImageX::F16_PAIRS) {   // fp16 modes with the pre-split operand: 128-row tiles
+        SBEV_REQUIRE(f16, "sbev_linear_splitk_f16s: pre-split X needs an fp16 mode");
+        const bool big = out8_takes(M, K, o.out8_min_rows);                          // batch shapes: 256-row tiles (a third less operand delivery)
         const Out4Plan pl = big ? out8_plan(M, K) : out4_plan(M, K);
-        const bool fold = !big && fold_sync && folded && out_fold_shape_ok(M, K);      // (the caller asked AND the shape / device allow it: else S slabs as before)
-        *used = fold ? 1 : pl.S;                                        // folded: the consumer reads `folded` as ONE slab
-        if (did_fold) *did_fold = fold;
-        Out4Args a4{reinterpret_cast<const unsigned*>(X), Wp, slabs, (int)M, K, (long long)ldx, pl.ntm, pl.base, pl.rem, pl.S, nscale,
-                    fold ? fold_sync : nullptr, fold ? folded : nullptr, g_out_fold_drop.load(std::memory_order_relaxed)};
+        r->folded = !big && o.fold_sync && o.folded && out_fold_shape_ok(M, K);       // (the caller asked AND the shape / device allow it: else S slabs as before)
+        r->used = r->folded ? 1 : pl.S;                                               // folded: the consumer reads `folded` as ONE slab
+        const Out4Args a4{reinterpret_cast<const unsigned*>(o.X.x), o.Wp, o.slabs, (int)M, K, (long long)o.X.ldx, pl.ntm, pl.base, pl.rem, pl.S, o.nscale,
+                          r->folded ? o.fold_sync : nullptr, r->folded ? o.folded : nullptr, g_out_fold_drop.load(std::memory_order_relaxed)};
         const long long wgs4 = (long long)pl.ntm * pl.S;
         SBEV_REQUIRE(wgs4 <= 0x7fffffffLL, "sbev_linear_splitk_f16s: too many workgroups");
         constexpr int LDS4 = 144 * 1024;        // 48 KiB of X stages + 8 waves x 12 KiB of W ring (the 128 KiB fold buffer reuses them)
-        hipEvent_t f0, f1;
-        int st4;
-#define SBEV_LAUNCH_OUT4(KERN)                                                                   \
-        {                                                                                        \
-            st4 = reserve_lds(KERN, LDS4, "sbev_linear_splitk_f16s");                            \
-            if (st4 != SBEV_OK) return st4;                                                      \
-            const bool prof = profile_begin(s, &f0, &f1, 2);                                     \
-            hipLaunchKernelGGL(KERN, dim3((unsigned)wgs4), dim3(512), LDS4, s, a4);              \
-            if (prof) profile_end(s, f0, f1, 2);                                                 \
-        }
-        if (big) {
-            if (nimg == 4) SBEV_LAUNCH_OUT4(gemm_bf16s_out8_kernel<2>) else SBEV_LAUNCH_OUT4(gemm_bf16s_out8_kernel<3>)
-        } else {
-            if (nimg == 4) SBEV_LAUNCH_OUT4(gemm_bf16s_out4_kernel<2>) else SBEV_LAUNCH_OUT4(gemm_bf16s_out4_kernel<3>)
-        }
-#undef SBEV_LAUNCH_OUT4
-        return check_launch("sbev_linear_splitk_f16s (gemm, 128-row tiles)");
+        const int st = launch_lds(pairs_kernel_for(o.nimg, big), (unsigned)wgs4, LDS4, s, a4, "sbev_linear_splitk_f16s", 2);
+        return st != SBEV_OK ? st : check_launch("sbev_linear_splitk_f16s (gemm, 128-row tiles)");
     }
     const int S = out_chunks(M, K);
-    *used = S;
-    OutArgs a{X, Wp, slabs, (int)M, K, (long long)ldx, (int)((M + 63) / 64), S, ldexpf(1.f, x_up_log2), nscale, xdev};
+    r->used = S;
+    const OutArgs a{o.X.x, o.Wp, o.slabs, (int)M, K, (long long)o.X.ldx, (int)((M + 63) / 64), S, ldexpf(1.f, o.X.up_log2), o.nscale,
+                    o.X.form == SplitImageX::F32_DEV_SCALE ? o.X.dev_scale : nullptr};
     const long long wgs = (long long)a.nrt * S;
     SBEV_REQUIRE(wgs <= 0x7fffffffLL, "sbev_linear_splitk_bf16s: too many workgroups");
-    hipEvent_t e0, e1;
-    int st;
     constexpr int LDS3 = 2 * 3 * 3 * O_IMG;     // 2 halves x 3 stages x 3 images x 4 KiB = 72 KiB (>= the 64 KiB fold buffer)
     constexpr int LDS2 = 65536;                 // two images: 48 KiB of stages, 64 KiB fold buffer
-#define SBEV_LAUNCH_OUT(KERN, LDSB)                                                              \
-    {                                                                                            \
-        st = reserve_lds(KERN, LDSB, "sbev_linear_splitk_bf16s");                                \
-        if (st != SBEV_OK) return st;                                                            \
-        const bool prof = profile_begin(s, &e0, &e1, 2);                                         \
-        hipLaunchKernelGGL(KERN, dim3((unsigned)wgs), dim3(512), LDSB, s, a);                    \
-        if (prof) profile_end(s, e0, e1, 2);                                                     \
-    }
-    if (nimg == 3) SBEV_LAUNCH_OUT(gemm_bf16s_out3_kernel<1>, LDS3)
-    else if (nimg == 2) SBEV_LAUNCH_OUT(gemm_bf16s_out3_kernel<0>, LDS2)
-    else if (nimg == 4) SBEV_LAUNCH_OUT(gemm_bf16s_out3_kernel<2>, LDS2)
-    else SBEV_LAUNCH_OUT(gemm_bf16s_out3_kernel<3>, LDS2)
-#undef SBEV_LAUNCH_OUT
-    return check_launch("sbev_linear_splitk_bf16s (gemm)");
+    const int st = launch_lds(out3_kernel(o.nimg), (unsigned)wgs, o.nimg == 3 ? LDS3 : LDS2, s, a, "sbev_linear_splitk_bf16s", 2);
+    return st != SBEV_OK ? st : check_launch("sbev_linear_splitk_bf16s (gemm)");
 }
 }  // namespace sbev
+
+// The three split-K out-projection entry points: checks in one order (mode, host exponent, shape, empty call, pointers, alignment), then
+// the slabs, then the reducer with the row epilogue.  `who` prefixes every message.  mode: nimg (bf16) or nprod (fp16: nimg = nprod + 1,
+// nscale required); a device-side scale is required where the form says so
+namespace {
+struct RowEpilogue { const float *bias, *residual, *ln_w, *ln_b; float ln_eps; float* Y; int relu; };
+int splitk_entry(const char* who, bool f16, int mode, const sbev::SplitImageX& X, const uint16_t* Wp, const float* nscale, const RowEpilogue& e,
+                 int64_t M, int N, int K, float* workspace, sbev_stream_t stream) {
+    if (f16) SBEV_REQUIRE(mode == 3 || mode == 4, "%s: nprod=%d (3 or 4 image products)", who, mode);
+    else SBEV_REQUIRE(mode == 2 || mode == 3, "%s: nimg=%d (2 = bf16x3, 3 = bf16x6)", who, mode);
+    SBEV_REQUIRE(X.up_log2 >= -100 && X.up_log2 <= 100, "%s: x_up_log2=%d", who, X.up_log2);
+    SBEV_REQUIRE(M >= 0 && sbev_linear_bf16s_out_ok(M > 0 ? M : 1, N, K), "%s: needs N == 256, K %% 32 == 0, K >= 256 (N=%d K=%d)", who, N, K);
+    if (M == 0) return SBEV_OK;
+    const bool xdev = X.form == sbev::SplitImageX::F32_DEV_SCALE;
+    SBEV_REQUIRE(X.x && Wp && e.Y && workspace && (!f16 || nscale) && (!xdev || X.dev_scale) && X.ldx % 4 == 0 && X.ldx >= K, "%s: bad pointers", who);
+    SBEV_REQUIRE((((uintptr_t)X.x | (uintptr_t)Wp | (uintptr_t)workspace | (uintptr_t)nscale) & 15) == 0, "%s: 16-byte alignment", who);
+    const sbev::OutProj o{X, Wp, nscale, M, K, f16 ? mode + 1 : mode, workspace, sbev::out8_min_rows_setting(), nullptr, nullptr};
+    sbev::OutProjResult r;
+    const int st = sbev::launch_out_proj_slabs(o, &r, reinterpret_cast<hipStream_t>(stream));
+    if (st != SBEV_OK) return st;
+    return sbev_splitk_reduce_f32(workspace, r.used, e.bias, e.residual, e.ln_w, e.ln_b, e.ln_eps, e.Y, M, N, e.relu, stream);
+}
+}  // namespace
 
 extern "C" int sbev_linear_splitk_bf16s(const float* X, const uint16_t* Wp, const float* bias, const float* residual,
                                         const float* ln_w, const float* ln_b, float ln_eps, float* Y,
                                         int64_t M, int N, int K, int64_t ldx, int relu, int nimg, float* workspace,
                                         sbev_stream_t stream) {
-    SBEV_REQUIRE(nimg == 2 || nimg == 3, "sbev_linear_splitk_bf16s: nimg=%d (2 = bf16x3, 3 = bf16x6)", nimg);
-    SBEV_REQUIRE(M >= 0 && sbev_linear_bf16s_out_ok(M > 0 ? M : 1, N, K), "sbev_linear_splitk_bf16s: needs N == 256, K %% 32 == 0, K >= 256 (N=%d K=%d)", N, K);
-    if (M == 0) return SBEV_OK;
-    SBEV_REQUIRE(X && Wp && Y && workspace && ldx % 4 == 0 && ldx >= K, "sbev_linear_splitk_bf16s: bad pointers");
-    SBEV_REQUIRE((((uintptr_t)X | (uintptr_t)Wp | (uintptr_t)workspace) & 15) == 0, "sbev_linear_splitk_bf16s: 16-byte alignment");
-    int used = 0;
-    const int st = sbev::launch_splitk_slabs_bf16s(X, Wp, M, K, ldx, nimg, workspace, &used, reinterpret_cast<hipStream_t>(stream), sbev::out8_min_rows_setting(), 0, nullptr, false);
-    if (st != SBEV_OK) return st;
-    return sbev_splitk_reduce_f32(workspace, used, bias, residual, ln_w, ln_b, ln_eps, Y, M, N, relu, stream);
+    return splitk_entry("sbev_linear_splitk_bf16s", false, nimg, {sbev::SplitImageX::F32_HOST_EXP, X, ldx, 0, nullptr}, Wp, nullptr,
+                        {bias, residual, ln_w, ln_b, ln_eps, Y, relu}, M, N, K, workspace, stream);
 }
 
 // fp16 hi + lo: X (fp32) is multiplied by 2^x_up_log2 and split in the kernel -- the CALLER guarantees |X| 2^x_up_log2 < 65504 (an
@@ -2007,17 +1987,9 @@ extern "C" int sbev_linear_splitk_bf16s(const float* X, const uint16_t* Wp, cons
 extern "C" int sbev_linear_splitk_f16s(const float* X, int x_is_pairs, int x_up_log2, const uint16_t* Wp, const float* nscale, const float* bias, const float* residual,
                                        const float* ln_w, const float* ln_b, float ln_eps, float* Y,
                                        int64_t M, int N, int K, int64_t ldx, int relu, int nprod, float* workspace, sbev_stream_t stream) {
-    SBEV_REQUIRE(nprod == 3 || nprod == 4, "sbev_linear_splitk_f16s: nprod=%d (3 or 4 image products)", nprod);
-    SBEV_REQUIRE(x_up_log2 >= -100 && x_up_log2 <= 100, "sbev_linear_splitk_f16s: x_up_log2=%d", x_up_log2);
-    SBEV_REQUIRE(M >= 0 && sbev_linear_bf16s_out_ok(M > 0 ? M : 1, N, K), "sbev_linear_splitk_f16s: needs N == 256, K %% 32 == 0, K >= 256 (N=%d K=%d)", N, K);
-    if (M == 0) return SBEV_OK;
-    SBEV_REQUIRE(X && Wp && Y && workspace && nscale && ldx % 4 == 0 && ldx >= K, "sbev_linear_splitk_f16s: bad pointers");
-    SBEV_REQUIRE((((uintptr_t)X | (uintptr_t)Wp | (uintptr_t)workspace | (uintptr_t)nscale) & 15) == 0, "sbev_linear_splitk_f16s: 16-byte alignment");
-    int used = 0;
-    const int st = sbev::launch_splitk_slabs_bf16s(X, Wp, M, K, ldx, nprod + 1, workspace, &used, reinterpret_cast<hipStream_t>(stream), sbev::out8_min_rows_setting(), x_up_log2, nscale,
-                                                   x_is_pairs != 0);
-    if (st != SBEV_OK) return st;
-    return sbev_splitk_reduce_f32(workspace, used, bias, residual, ln_w, ln_b, ln_eps, Y, M, N, relu, stream);
+    const sbev::SplitImageX::Form form = x_is_pairs ? sbev::SplitImageX::F16_PAIRS : sbev::SplitImageX::F32_HOST_EXP;
+    return splitk_entry("sbev_linear_splitk_f16s", true, nprod, {form, X, ldx, x_up_log2, nullptr}, Wp, nscale,
+                        {bias, residual, ln_w, ln_b, ln_eps, Y, relu}, M, N, K, workspace, stream);
 }
 
 // The same with X's scale in DEVICE memory (x_scale = {2^e, 2^-e}: sbev_f16s_tensor_scale or the maxima a producer kernel left):
@@ -2026,15 +1998,8 @@ extern "C" int sbev_linear_splitk_f16s(const float* X, int x_is_pairs, int x_up_
 extern "C" int sbev_linear_splitk_f16s_xdev(const float* X, const float* x_scale, const uint16_t* Wp, const float* wdown, const float* bias,
                                             const float* residual, const float* ln_w, const float* ln_b, float ln_eps, float* Y,
                                             int64_t M, int N, int K, int64_t ldx, int relu, int nprod, float* workspace, sbev_stream_t stream) {
-    SBEV_REQUIRE(nprod == 3 || nprod == 4, "sbev_linear_splitk_f16s_xdev: nprod=%d (3 or 4 image products)", nprod);
-    SBEV_REQUIRE(M >= 0 && sbev_linear_bf16s_out_ok(M > 0 ? M : 1, N, K), "sbev_linear_splitk_f16s_xdev: needs N == 256, K %% 32 == 0, K >= 256 (N=%d K=%d)", N, K);
-    if (M == 0) return SBEV_OK;
-    SBEV_REQUIRE(X && x_scale && Wp && Y && workspace && wdown && ldx % 4 == 0 && ldx >= K, "sbev_linear_splitk_f16s_xdev: bad pointers");
-    SBEV_REQUIRE((((uintptr_t)X | (uintptr_t)Wp | (uintptr_t)workspace | (uintptr_t)wdown) & 15) == 0, "sbev_linear_splitk_f16s_xdev: 16-byte alignment");
-    int used = 0;
-    const int st = sbev::launch_splitk_slabs_bf16s(X, Wp, M, K, ldx, nprod + 1, workspace, &used, reinterpret_cast<hipStream_t>(stream), sbev::out8_min_rows_setting(), 0, wdown, false, x_scale);
-    if (st != SBEV_OK) return st;
-    return sbev_splitk_reduce_f32(workspace, used, bias, residual, ln_w, ln_b, ln_eps, Y, M, N, relu, stream);
+    return splitk_entry("sbev_linear_splitk_f16s_xdev", true, nprod, {sbev::SplitImageX::F32_DEV_SCALE, X, ldx, 0, x_scale}, Wp, wdown,
+                        {bias, residual, ln_w, ln_b, ln_eps, Y, relu}, M, N, K, workspace, stream);
 }
 
 // nscale[n] = wdown[n] 2^-x_up_log2 (exact), the per-column factor of the fp16 out-projection's slabs

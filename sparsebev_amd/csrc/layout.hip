@@ -679,23 +679,15 @@ bool lazy_plan(int n_levels, const int32_t* hw, long long n_images, int channels
     return true;
 }
 
-int launch_lazy_relayout(const LazyPlan& p, const void* const* table, const int32_t* index, const void* const* src, void* const* out,
-                         int esize, uint32_t* need, uint32_t* done, bool first, bool last, hipStream_t s) {
+int launch_lazy_relayout(const LazyScan& scan, bool first, hipStream_t s) {
     LazyArgs a{};
-    a.table = table; a.n_levels = p.n_levels; a.R = p.R; a.need = need; a.done = done; a.first = first; a.last = last;
-    for (int l = 0; l < p.n_levels; ++l) {
-        a.index[l] = table ? index[l] : 0;
-        a.src[l] = table ? nullptr : src[l];
-        a.out[l] = out[l];
-        a.S[l] = p.S[l]; a.tiles[l] = p.tiles[l]; a.base[l] = p.base[l];
-    }
-    a.base[p.n_levels] = p.base[p.n_levels];
-    const unsigned total = p.base[p.n_levels];
+    fill_lazy_args(a, scan, first);
+    const unsigned total = scan.plan->base[scan.plan->n_levels];
     if (first) {
-        if (esize == 4) hipLaunchKernelGGL(lazy_tiles_kernel<float>, dim3(total), dim3(256), 0, s, a);
+        if (scan.esize == 4) hipLaunchKernelGGL(lazy_tiles_kernel<float>, dim3(total), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(lazy_tiles_kernel<unsigned short>, dim3(total), dim3(256), 0, s, a);
     } else {
-        if (esize == 4) hipLaunchKernelGGL(lazy_scan_kernel<float>, dim3((total + LAZY_SCAN - 1) / LAZY_SCAN), dim3(256), 0, s, a);
+        if (scan.esize == 4) hipLaunchKernelGGL(lazy_scan_kernel<float>, dim3((total + LAZY_SCAN - 1) / LAZY_SCAN), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(lazy_scan_kernel<unsigned short>, dim3((total + LAZY_SCAN - 1) / LAZY_SCAN), dim3(256), 0, s, a);
     }
     return check_launch("lazy relayout");
@@ -720,6 +712,6 @@ extern "C" int sbev_nchw_to_nhwc_lazy(const void* const* table, const int32_t* i
     for (int l = 0; l < n_levels; ++l)
         SBEV_REQUIRE(out[l] && (((uintptr_t)out[l]) & 15) == 0 && (table ? index[l] >= 0 : (src[l] && (((uintptr_t)src[l]) & 15) == 0)),
                      "sbev_nchw_to_nhwc_lazy: level %d (16-byte aligned source and destination)", l);
-    return sbev::launch_lazy_relayout(p, table, index, src, out, dtype == SBEV_F32 ? 4 : 2, need, done, first != 0, last != 0,
-                                      reinterpret_cast<hipStream_t>(stream));
+    const sbev::LazyScan scan{&p, table, index, src, out, dtype == SBEV_F32 ? 4 : 2, need, done, last != 0};
+    return sbev::launch_lazy_relayout(scan, first != 0, reinterpret_cast<hipStream_t>(stream));
 }

@@ -17,6 +17,18 @@ struct LazyArgs {
     unsigned* done;                        // [total tiles] 4 bytes each: moved in this step
     int first, last;
 };
+// host side: the argument block from the description the callers hold (sbev_common.hpp: LazyScan)
+inline void fill_lazy_args(LazyArgs& a, const sbev::LazyScan& z, bool first) {
+    const sbev::LazyPlan& p = *z.plan;
+    a.table = z.table; a.n_levels = p.n_levels; a.R = p.R; a.need = z.need; a.done = z.done; a.first = first; a.last = z.last;
+    for (int l = 0; l < p.n_levels; ++l) {
+        a.index[l] = z.table ? z.index[l] : 0;
+        a.src[l] = z.table ? nullptr : z.src[l];
+        a.out[l] = z.out[l];
+        a.S[l] = p.S[l]; a.tiles[l] = p.tiles[l]; a.base[l] = p.base[l];
+    }
+    a.base[p.n_levels] = p.base[p.n_levels];
+}
 
 constexpr int LAZY_SCAN = 16;        // tiles per workgroup of the stand-alone scan launch
 __device__ __forceinline__ unsigned lazy_bytes_nonzero(unsigned w) {      // byte k != 0 -> bit k

@@ -108,15 +108,39 @@ int msmv_fwd(const PyramidDesc& d, int64_t Bp, float* out, int out_layout, int T
 int sample_mix(const PyramidDesc& d, int64_t B, int T, int G, const float* params, float* y, int Pout, float eps, float out_up,
                const int32_t* order, sbev_stream_t stream);
 
-// gemm_bf16s.hip: the GEMM half of sbev_linear_splitk_bf16s (*used partial slabs [used, M, 256], not reduced)
-// out8_min_rows: the caller's reading of sbev_linear_out8_min_rows (pre-split operand only: rows from which the 256-row tiles run).
-// fold_sync + folded (pre-split fp16 operand only; null unless the caller WANTS the fold): the S chunk-workgroups of a row tile fold their
-// slabs INSIDE the launch into `folded` [M, 256], *used = 1 and *did_fold = true -- taken only where out_fold_shape_ok(M, K) (every
-// workgroup of the launch resident at once) and the 128-row kernel runs; fold_sync: one zeroed word per row tile (<= 64).  A row tile
-// that never completes within the poll bound raises the decoder's fault word.
-int launch_splitk_slabs_bf16s(const float* X, const uint16_t* Wp, int64_t M, int K, int64_t ldx, int nimg, float* slabs, int* used,
-                              hipStream_t s, int out8_min_rows, int x_up_log2 = 0, const float* nscale = nullptr, bool x_pairs = false,
-                              const float* xdev = nullptr, unsigned* fold_sync = nullptr, float* folded = nullptr, bool* did_fold = nullptr);
+// gemm_bf16s.hip: the GEMM half of sbev_linear_splitk_bf16s / _f16s / _f16s_xdev as ONE description (the entry points build it from
+// their positional arguments, decoder.hip once per layer): `used` partial slabs [used, M, 256], not reduced
+struct SplitImageX {      // the X operand [M, ldx], exactly one form
+    enum Form {
+        F32_HOST_EXP,     // fp32, multiplied by 2^up_log2 and split in the kernel (bf16 modes: up_log2 = 0)
+        F16_PAIRS,        // (fp16 hi, fp16 lo) of x 2^up_log2 in 32-bit slots, split by the producer (fp16 modes only)
+        F32_DEV_SCALE     // fp32, dev_scale = {2^e, 2^-e} in device memory (fp16 modes only)
+    } form;
+    const float* x;
+    int64_t ldx;
+    int up_log2;
+    const float* dev_scale;
+};
+struct OutProj {
+    SplitImageX X;
+    const uint16_t* Wp;
+    const float* nscale;       // null in the bf16 modes; [256] per-column factors of the slabs (F32_DEV_SCALE: W's down-scales)
+    int64_t M;
+    int K, nimg;               // nimg 2 / 3: bf16x3 / bf16x6; 4 / 5: fp16 with 3 / 4 image products
+    float* slabs;
+    int out8_min_rows;         // the caller's reading of sbev_linear_out8_min_rows (F16_PAIRS only: rows from which the 256-row tiles run)
+    // F16_PAIRS only, both null unless the caller WANTS the fold: the S chunk-workgroups of a row tile fold their slabs INSIDE the launch
+    // into `folded` [M, 256] -- taken only where out_fold_shape_ok(M, K) (every workgroup of the launch resident at once) and the 128-row
+    // kernel runs; fold_sync: one zeroed word per row tile (<= 64).  A row tile that never completes within the poll bound raises the
+    // decoder's fault word.
+    unsigned* fold_sync;
+    float* folded;
+};
+struct OutProjResult {
+    int used;                  // slabs to sum
+    bool folded;               // the launch folded them: ONE slab, in OutProj::folded instead of OutProj::slabs
+};
+int launch_out_proj_slabs(const OutProj& o, OutProjResult* r, hipStream_t s);
 bool out_fold_shape_ok(long long M, int K);
 bool out_fold_enabled();              // sbev_decoder_out_fold's current setting
 bool out_fold_install(void* host_word_dev);
@@ -136,7 +160,8 @@ struct LazyPlan {
     unsigned base[SBEV_MAX_LEVELS + 1];      // base[n_levels] = tiles of the pyramid
 };
 bool lazy_plan(int n_levels, const int32_t* hw, long long n_images, int channels, LazyPlan* p);
-// the scan of layers 1..5 riding in the generator GEMM's prologue (gemm_bf16s.hip): what the stand-alone launch would have been given
+// one layer's move as ONE value: the stand-alone launch's argument, and the scan of layers 1..5 riding in the generator GEMM's prologue
+// (gemm_bf16s.hip).  Sources: table[index[l]] (replayable step; src unused) or src[l]
 struct LazyScan {
     const LazyPlan* plan;
     const void* const* table;
@@ -153,8 +178,7 @@ struct LazyScan {
 bool gen_ws_shape_ok(int64_t M, int K, int64_t ldy, int nimg);
 int linear_gen_split(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y, int64_t M,
                      int N, int K, int64_t ldy, int relu, int nimg, bool weight_stationary, const LazyScan* lz, hipStream_t stream);
-int launch_lazy_relayout(const LazyPlan& p, const void* const* table, const int32_t* index, const void* const* src, void* const* out,
-                         int esize, uint32_t* need, uint32_t* done, bool first, bool last, hipStream_t s);
+int launch_lazy_relayout(const LazyScan& scan, bool first, hipStream_t s);      // first: the step's first move (every marked unit is new)
 
 // row_chain.hip: the row-local op chains of a decoder layer as single launches (weights pre-packed: sbev_decoder_chain_pack)
 bool row_chain_supported(const sbev_decoder_config& c);

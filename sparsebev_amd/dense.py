@@ -39,6 +39,11 @@ def _dev(*ts):
             raise RuntimeError('sparsebev_amd.dense needs device tensors (no CPU fallback)')
 
 
+def _rows(x, width=None):
+    """x as contiguous rows [-1, width] (width: its last dimension unless given)"""
+    return x.reshape(-1, x.shape[-1] if width is None else width).contiguous()
+
+
 def _ws(nbytes, device):
     """Reusable split-K workspace (one per device; grown on demand, stream-ordered reuse)."""
     key = str(device)
@@ -66,9 +71,7 @@ def linear(x, w, b, relu=False, residual=None, ln=None, ln_relu=False):
     _dev(x, w)
     K, N = x.shape[-1], w.shape[0]
     lead = x.shape[:-1]
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
+    x2 = _rows(x)
     M = x2.shape[0]
     if K % 4 != 0:                                   # only the 3-wide position-encoder input; see position_encode()
         raise RuntimeError('sbev linear needs K %% 4 == 0 (got K=%d)' % K)
@@ -99,9 +102,7 @@ def split_bf16s_rows(x, nimg=3):
     """fp32 [rows, K] -> int16 [nimg, rows, K]: the row-major bf16 planes hi (, mid), lo with x == sum of the planes exactly
     (nimg = 3) / to 2^-17 relative (nimg = 2).  Operand format of linear_bf16s_gen."""
     _dev(x)
-    x2 = x.reshape(-1, x.shape[-1])
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
+    x2 = _rows(x)
     rows, K = x2.shape
     out = torch.empty(nimg, rows, K, device=x.device, dtype=torch.int16)
     st = _lib.load().sbev_split_bf16s_rows(_p(x2), K, _p(out), rows, K, nimg, _stream())
@@ -134,27 +135,33 @@ def linear_bf16s_gen(x, w_frags, b, nimg=3, relu=False):
     return y.reshape(*x.shape[:-1], N)
 
 
-def linear_splitk_bf16s(x, w_frags, b, nimg=3, residual=None, ln=None, relu=False):
-    """y = LayerNorm?(act(x @ W.T + b) + residual) with W given as pack_bf16s_frags [N/32, K/16, nimg, 64, 8], N == 256
-    (the out-projection's shape); x stays fp32 and is split inside the kernel."""
+def _splitk_out_proj(who, x, w_frags, b, residual, ln, relu, mode, call):
+    """What the split-image out-projections share: rows of x, the slab workspace for the kernels' plan (raises where they do not cover
+    the shape), residual and output, and the argument tail every one of their C calls ends with (bias ... stream; mode = nimg /
+    nprod).  call(lib, x2, N, tail) makes the C call(s) while all of these are alive."""
     _dev(x, w_frags)
-    K = x.shape[-1]
-    N = w_frags.shape[0] * 32
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
+    K, N = x.shape[-1], w_frags.shape[0] * 32
+    x2 = _rows(x)
     M = x2.shape[0]
     lib = _lib.load()
     plan = lib.sbev_linear_bf16s_out_plan(M, N, K)
     if plan <= 0:
-        raise RuntimeError('sbev_linear_splitk_bf16s does not cover M=%d N=%d K=%d' % (M, N, K))
+        raise RuntimeError('%s does not cover M=%d N=%d K=%d' % (who, M, N, K))
     ws = _ws(plan * M * N * 4, x.device)
-    res2 = residual.reshape(-1, N).contiguous() if residual is not None else None
+    res2 = _rows(residual, N) if residual is not None else None
     y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    st = lib.sbev_linear_splitk_bf16s(_p(x2), _p(w_frags), _p(b), _p(res2), _p(ln[0] if ln else None), _p(ln[1] if ln else None),
-                                      1e-5, _p(y), M, N, K, K, int(relu), nimg, _p(ws), _stream())
-    _lib.check(st, 'sbev_linear_splitk_bf16s')
+    lnw, lnb = ln if ln else (None, None)
+    call(lib, x2, N, (_p(b), _p(res2), _p(lnw), _p(lnb), 1e-5, _p(y), M, N, K, K, int(relu), mode, _p(ws), _stream()))
     return y.reshape(*x.shape[:-1], N)
+
+
+def linear_splitk_bf16s(x, w_frags, b, nimg=3, residual=None, ln=None, relu=False):
+    """y = LayerNorm?(act(x @ W.T + b) + residual) with W given as pack_bf16s_frags [N/32, K/16, nimg, 64, 8], N == 256
+    (the out-projection's shape); x stays fp32 and is split inside the kernel."""
+    def call(lib, x2, N, tail):
+        _lib.check(lib.sbev_linear_splitk_bf16s(_p(x2), _p(w_frags), *tail), 'sbev_linear_splitk_bf16s')
+
+    return _splitk_out_proj('sbev_linear_splitk_bf16s', x, w_frags, b, residual, ln, relu, nimg, call)
 
 
 # ---- fp16 hi + lo Linears (csrc/gemm_bf16s.hip, MODE 2 / 3): x 2^e = hi + lo (two fp16 images), 3 or 4 image products --------------
@@ -223,35 +230,21 @@ def linear_splitk_f16s(x, w_frags, w_scales, b, nprod=3, residual=None, ln=None,
     multiplied by 2^x_up_log2 and split inside the kernel (default: from max |x|, one host sync -- the decoder passes its bound);
     x_is_pairs: x is f16s_pairs(x_fp32, x_up_log2) (int32), only de-interleaved inside the kernel;
     x_scale: device {2^e, 2^-e} of x (f16s_tensor_scale) instead of a host-side exponent -- no sync, no bound."""
-    _dev(x, w_frags)
-    K = x.shape[-1]
-    N = w_frags.shape[0] * 32
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
-    M = x2.shape[0]
-    lib = _lib.load()
-    plan = lib.sbev_linear_bf16s_out_plan(M, N, K)
-    if plan <= 0:
-        raise RuntimeError('sbev_linear_splitk_f16s does not cover M=%d N=%d K=%d' % (M, N, K))
-    ws = _ws(plan * M * N * 4, x.device)
-    res2 = residual.reshape(-1, N).contiguous() if residual is not None else None
-    y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    if x_scale is not None:
-        st = lib.sbev_linear_splitk_f16s_xdev(_p(x2), _p(x_scale), _p(w_frags), _p(w_scales[1]), _p(b), _p(res2), _p(ln[0] if ln else None),
-                                              _p(ln[1] if ln else None), 1e-5, _p(y), M, N, K, K, int(relu), nprod, _p(ws), _stream())
-        _lib.check(st, 'sbev_linear_splitk_f16s_xdev')
-        return y.reshape(*x.shape[:-1], N)
-    if x_up_log2 is None:
-        import math
-        mx = float(x2.abs().max())
-        x_up_log2 = 15 - math.frexp(mx)[1] if mx > 0 and math.isfinite(mx) else 0
-    nscale = torch.empty(N, device=x.device, dtype=torch.float32)
-    _lib.check(lib.sbev_f16s_out_scale(_p(w_scales[1]), int(x_up_log2), _p(nscale), N, _stream()), 'sbev_f16s_out_scale')
-    st = lib.sbev_linear_splitk_f16s(_p(x2), int(x_is_pairs), int(x_up_log2), _p(w_frags), _p(nscale), _p(b), _p(res2), _p(ln[0] if ln else None),
-                                     _p(ln[1] if ln else None), 1e-5, _p(y), M, N, K, K, int(relu), nprod, _p(ws), _stream())
-    _lib.check(st, 'sbev_linear_splitk_f16s')
-    return y.reshape(*x.shape[:-1], N)
+    def call(lib, x2, N, tail):
+        if x_scale is not None:
+            st = lib.sbev_linear_splitk_f16s_xdev(_p(x2), _p(x_scale), _p(w_frags), _p(w_scales[1]), *tail)
+            return _lib.check(st, 'sbev_linear_splitk_f16s_xdev')
+        up = x_up_log2
+        if up is None:
+            import math
+            mx = float(x2.abs().max())
+            up = 15 - math.frexp(mx)[1] if mx > 0 and math.isfinite(mx) else 0
+        nscale = torch.empty(N, device=x.device, dtype=torch.float32)
+        _lib.check(lib.sbev_f16s_out_scale(_p(w_scales[1]), int(up), _p(nscale), N, _stream()), 'sbev_f16s_out_scale')
+        st = lib.sbev_linear_splitk_f16s(_p(x2), int(x_is_pairs), int(up), _p(w_frags), _p(nscale), *tail)
+        _lib.check(st, 'sbev_linear_splitk_f16s')
+
+    return _splitk_out_proj('sbev_linear_splitk_f16s', x, w_frags, b, residual, ln, relu, nprod, call)
 
 
 class _LinearProblem(ctypes.Structure):
@@ -270,7 +263,7 @@ def linear_group(problems):
     for i, (x, w, b, relu) in enumerate(problems):
         _dev(x, w)
         K, N = x.shape[-1], w.shape[0]
-        x2 = x.reshape(-1, K).contiguous()
+        x2 = _rows(x)
         w = w.contiguous()
         y = torch.empty(x2.shape[0], N, device=x.device, dtype=torch.float32)
         keep += [x2, w]
@@ -289,9 +282,7 @@ def ln_linear(x, ln_w, ln_b, w, b, eps=1e-5, ln_relu=False, add_after=None, relu
     _dev(x, ln_w, ln_b, w)
     K, N = x.shape[-1], w.shape[0]
     lead = x.shape[:-1]
-    x2 = x.reshape(-1, K)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
+    x2 = _rows(x)
     M = x2.shape[0]
     w = w.contiguous()
     aa = add_after.reshape(-1, K).contiguous() if add_after is not None else None
@@ -308,9 +299,7 @@ def layer_norm(x, w, b, eps=1e-5, relu=False, add_after=None):
     """relu?(LayerNorm(x)) (+ add_after)"""
     _dev(x, w, b)
     N = x.shape[-1]
-    x2 = x.reshape(-1, N)
-    if not x2.is_contiguous():
-        x2 = x2.contiguous()
+    x2 = _rows(x)
     y = torch.empty_like(x2)
     aa = add_after.reshape(-1, N).contiguous() if add_after is not None else None
     st = _lib.load().sbev_layer_norm_f32(_p(x2), _p(w), _p(b), eps, _p(aa), _p(y), x2.shape[0], N, int(relu), _stream())
@@ -325,9 +314,7 @@ def linear_ln_relu(x, w, b, lnw, lnb):
         _dev(x, w)
         N = w.shape[0]
         ldx = x.shape[-1]
-        x2 = x.reshape(-1, ldx)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows(x)
         y = torch.empty(x2.shape[0], N, device=x.device, dtype=torch.float32)
         st = _lib.load().sbev_linear3_ln_relu_f32(_p(x2), ldx, _p(w.contiguous()), _p(b), _p(lnw), _p(lnb), 1e-5, _p(y),
                                                   x2.shape[0], N, _stream())

@@ -204,6 +204,184 @@ def test_sampler_entry_points_refusal_table(lib):
     assert lib.sbev_sample_mix_slabs_ok(i32([4, 4] * 4), 6, 0, 6, 64, i64([4096] * 4), 256) == 0
 
 
+def _split_image_entry_points(lib):
+    """The three split-K out-projection entry points and the two generator entry points, each as call(**overrides) over one good call
+    (fake, aligned pointers; M = 64, N = 256, K = 512): validation returns before any HIP call."""
+    base = dict(X=0x1000, Wp=0x2000, Y=0x3000, ws=0x4000, scale=0x5000, xscale=0x6000, bias=None, M=64, N=256, K=512, ld=None, relu=0,
+                mode=None, pairs=0, up=0)
+    vp = lambda v: None if v is None else ctypes.c_void_p(v)
+
+    def args(o, gen=False):      # mode: nimg / nprod (3 is valid for all five); ld: ldx = K, the generators' ldy = N
+        d = dict(base, **o)
+        d['mode'] = 3 if d['mode'] is None else d['mode']
+        d['ld'] = (d['N'] if gen else d['K']) if d['ld'] is None else d['ld']
+        return d
+
+    def out(d, head):      # ..., bias, residual, ln_w, ln_b, ln_eps, Y, M, N, K, ldx, relu, nimg / nprod, workspace, stream
+        return head + (vp(d['bias']), None, None, None, 1e-5, vp(d['Y']), d['M'], d['N'], d['K'], d['ld'], d['relu'], d['mode'], vp(d['ws']), None)
+
+    def bf16s(**o):
+        d = args(o)
+        return lib.sbev_linear_splitk_bf16s(*out(d, (vp(d['X']), vp(d['Wp']))))
+
+    def f16s(**o):
+        d = args(o)
+        return lib.sbev_linear_splitk_f16s(*out(d, (vp(d['X']), d['pairs'], d['up'], vp(d['Wp']), vp(d['scale']))))
+
+    def xdev(**o):
+        d = args(o)
+        return lib.sbev_linear_splitk_f16s_xdev(*out(d, (vp(d['X']), vp(d['xscale']), vp(d['Wp']), vp(d['scale']))))
+
+    def gen(**o):          # Xs, Ws, bias, Y, M, N, K, ldy, relu, nimg, stream
+        d = args(o, gen=True)
+        return lib.sbev_linear_bf16s_gen(vp(d['X']), vp(d['Wp']), vp(d['bias']), vp(d['Y']), d['M'], d['N'], d['K'], d['ld'], d['relu'], d['mode'], None)
+
+    def f16gen(**o):       # Xs, xscale, Ws, wdown, bias, Y, M, N, K, ldy, relu, nprod, stream
+        d = args(o, gen=True)
+        return lib.sbev_linear_f16s_gen(vp(d['X']), vp(d['xscale']), vp(d['Wp']), vp(d['scale']), vp(d['bias']), vp(d['Y']), d['M'], d['N'], d['K'],
+                                        d['ld'], d['relu'], d['mode'], None)
+
+    return {'bf16s': bf16s, 'f16s': f16s, 'xdev': xdev, 'gen': gen, 'f16gen': f16gen}
+
+
+def test_split_image_gemm_entry_points_refusal_table(lib):
+    """Status and FULL message of sbev_linear_splitk_bf16s / _f16s / _f16s_xdev and sbev_linear_bf16s_gen / sbev_linear_f16s_gen, one
+    provoking call per check in the order the checks run: mode (nimg / nprod), x_up_log2 range where the entry point has one, shape, the
+    empty call (M == 0 returns 0 before any pointer is looked at), pointers, alignment.  A row that breaks several checks at once pins
+    the order.  No row reaches a launch."""
+    call = _split_image_entry_points(lib)
+    nothing = dict(X=None, Wp=None, Y=None, ws=None, scale=None, xscale=None)
+    shape = 'needs N == 256, K % 32 == 0, K >= 256'
+    gshape = 'sbev_linear_bf16s_gen: needs N % 256 == 0, K % 32 == 0, K <= 4096'
+    table = [
+        # ---- sbev_linear_splitk_bf16s
+        ('bf16s', dict(mode=4), -1, 'sbev_linear_splitk_bf16s: nimg=4 (2 = bf16x3, 3 = bf16x6)'),
+        ('bf16s', dict(mode=1, N=128, **nothing), -1, 'sbev_linear_splitk_bf16s: nimg=1 (2 = bf16x3, 3 = bf16x6)'),
+        ('bf16s', dict(N=128), -1, 'sbev_linear_splitk_bf16s: %s (N=128 K=512)' % shape),
+        ('bf16s', dict(K=250, **nothing), -1, 'sbev_linear_splitk_bf16s: %s (N=256 K=250)' % shape),
+        ('bf16s', dict(K=224), -1, 'sbev_linear_splitk_bf16s: %s (N=256 K=224)' % shape),
+        ('bf16s', dict(M=-1), -1, 'sbev_linear_splitk_bf16s: %s (N=256 K=512)' % shape),
+        ('bf16s', dict(M=1 << 22), -1, 'sbev_linear_splitk_bf16s: %s (N=256 K=512)' % shape),
+        ('bf16s', dict(M=0, **nothing), 0, ''),
+        ('bf16s', dict(M=0, mode=2, **nothing), 0, ''),
+        ('bf16s', dict(M=0, N=128, **nothing), -1, 'sbev_linear_splitk_bf16s: %s (N=128 K=512)' % shape),
+        ('bf16s', nothing, -1, 'sbev_linear_splitk_bf16s: bad pointers'),
+        ('bf16s', dict(X=None), -1, 'sbev_linear_splitk_bf16s: bad pointers'),
+        ('bf16s', dict(Wp=None), -1, 'sbev_linear_splitk_bf16s: bad pointers'),
+        ('bf16s', dict(Y=None), -1, 'sbev_linear_splitk_bf16s: bad pointers'),
+        ('bf16s', dict(ws=None, X=0x1004), -1, 'sbev_linear_splitk_bf16s: bad pointers'),
+        ('bf16s', dict(ld=510), -1, 'sbev_linear_splitk_bf16s: bad pointers'),
+        ('bf16s', dict(ld=508), -1, 'sbev_linear_splitk_bf16s: bad pointers'),
+        ('bf16s', dict(X=0x1004), -1, 'sbev_linear_splitk_bf16s: 16-byte alignment'),
+        ('bf16s', dict(Wp=0x2008), -1, 'sbev_linear_splitk_bf16s: 16-byte alignment'),
+        ('bf16s', dict(ws=0x4004), -1, 'sbev_linear_splitk_bf16s: 16-byte alignment'),
+        # ---- sbev_linear_splitk_f16s
+        ('f16s', dict(mode=5), -1, 'sbev_linear_splitk_f16s: nprod=5 (3 or 4 image products)'),
+        ('f16s', dict(mode=2, up=101, N=128, **nothing), -1, 'sbev_linear_splitk_f16s: nprod=2 (3 or 4 image products)'),
+        ('f16s', dict(up=101), -1, 'sbev_linear_splitk_f16s: x_up_log2=101'),
+        ('f16s', dict(up=-101, N=128, M=0, **nothing), -1, 'sbev_linear_splitk_f16s: x_up_log2=-101'),
+        ('f16s', dict(N=128), -1, 'sbev_linear_splitk_f16s: %s (N=128 K=512)' % shape),
+        ('f16s', dict(K=250, pairs=1, **nothing), -1, 'sbev_linear_splitk_f16s: %s (N=256 K=250)' % shape),
+        ('f16s', dict(M=-1), -1, 'sbev_linear_splitk_f16s: %s (N=256 K=512)' % shape),
+        ('f16s', dict(M=0, **nothing), 0, ''),
+        ('f16s', dict(M=0, mode=4, pairs=1, up=100, **nothing), 0, ''),
+        ('f16s', nothing, -1, 'sbev_linear_splitk_f16s: bad pointers'),
+        ('f16s', dict(scale=None), -1, 'sbev_linear_splitk_f16s: bad pointers'),
+        ('f16s', dict(scale=None, pairs=1), -1, 'sbev_linear_splitk_f16s: bad pointers'),
+        ('f16s', dict(ws=None, scale=0x5004), -1, 'sbev_linear_splitk_f16s: bad pointers'),
+        ('f16s', dict(ld=508), -1, 'sbev_linear_splitk_f16s: bad pointers'),
+        ('f16s', dict(X=0x1004), -1, 'sbev_linear_splitk_f16s: 16-byte alignment'),
+        ('f16s', dict(scale=0x5004, pairs=1), -1, 'sbev_linear_splitk_f16s: 16-byte alignment'),
+        ('f16s', dict(ws=0x4008, mode=4), -1, 'sbev_linear_splitk_f16s: 16-byte alignment'),
+        # ---- sbev_linear_splitk_f16s_xdev (no host exponent: no range check; x_scale is required but only 4-byte aligned)
+        ('xdev', dict(mode=5), -1, 'sbev_linear_splitk_f16s_xdev: nprod=5 (3 or 4 image products)'),
+        ('xdev', dict(mode=0, N=128, **nothing), -1, 'sbev_linear_splitk_f16s_xdev: nprod=0 (3 or 4 image products)'),
+        ('xdev', dict(N=128), -1, 'sbev_linear_splitk_f16s_xdev: %s (N=128 K=512)' % shape),
+        ('xdev', dict(K=250, **nothing), -1, 'sbev_linear_splitk_f16s_xdev: %s (N=256 K=250)' % shape),
+        ('xdev', dict(M=0, **nothing), 0, ''),
+        ('xdev', nothing, -1, 'sbev_linear_splitk_f16s_xdev: bad pointers'),
+        ('xdev', dict(xscale=None), -1, 'sbev_linear_splitk_f16s_xdev: bad pointers'),
+        ('xdev', dict(scale=None), -1, 'sbev_linear_splitk_f16s_xdev: bad pointers'),
+        ('xdev', dict(Y=None, Wp=0x2004), -1, 'sbev_linear_splitk_f16s_xdev: bad pointers'),
+        ('xdev', dict(ld=256), -1, 'sbev_linear_splitk_f16s_xdev: bad pointers'),
+        ('xdev', dict(Wp=0x2004), -1, 'sbev_linear_splitk_f16s_xdev: 16-byte alignment'),
+        ('xdev', dict(scale=0x5008), -1, 'sbev_linear_splitk_f16s_xdev: 16-byte alignment'),
+        # ---- sbev_linear_bf16s_gen (K = 512 here: the weight-stationary kernel's K = 256 is not what is tested)
+        ('gen', dict(mode=4), -1, 'sbev_linear_bf16s_gen: nimg=4 (2 = bf16x3, 3 = bf16x6)'),
+        ('gen', dict(mode=5, N=128, **nothing), -1, 'sbev_linear_bf16s_gen: nimg=5 (2 = bf16x3, 3 = bf16x6)'),
+        ('gen', dict(N=128), -1, '%s (M=64 N=128 K=512)' % gshape),
+        ('gen', dict(K=4128, **nothing), -1, '%s (M=64 N=256 K=4128)' % gshape),
+        ('gen', dict(K=48), -1, '%s (M=64 N=256 K=48)' % gshape),
+        ('gen', dict(M=-1), -1, '%s (M=-1 N=256 K=512)' % gshape),
+        ('gen', dict(M=0, **nothing), 0, ''),
+        ('gen', dict(M=0, N=128, **nothing), -1, '%s (M=0 N=128 K=512)' % gshape),
+        ('gen', nothing, -1, 'sbev_linear_bf16s_gen: bad pointers / leading dimension'),
+        ('gen', dict(Y=None, X=0x1004), -1, 'sbev_linear_bf16s_gen: bad pointers / leading dimension'),
+        ('gen', dict(ld=128), -1, 'sbev_linear_bf16s_gen: bad pointers / leading dimension'),
+        ('gen', dict(ld=258), -1, 'sbev_linear_bf16s_gen: bad pointers / leading dimension'),
+        ('gen', dict(X=0x1004), -1, 'sbev_linear_bf16s_gen: 16-byte alignment'),
+        ('gen', dict(bias=0x7004), -1, 'sbev_linear_bf16s_gen: 16-byte alignment'),
+        # ---- sbev_linear_f16s_gen: its own two checks, then the shared generator's under the shared prefix
+        ('f16gen', dict(mode=5), -1, 'sbev_linear_f16s_gen: nprod=5 (3 or 4 image products)'),
+        ('f16gen', dict(mode=2, **nothing), -1, 'sbev_linear_f16s_gen: nprod=2 (3 or 4 image products)'),
+        ('f16gen', dict(xscale=None, N=128), -1, 'sbev_linear_f16s_gen: null scale pointer'),
+        ('f16gen', dict(scale=None), -1, 'sbev_linear_f16s_gen: null scale pointer'),
+        ('f16gen', dict(N=128), -1, '%s (M=64 N=128 K=512)' % gshape),
+        ('f16gen', dict(M=0, **nothing), 0, ''),
+        ('f16gen', dict(X=None), -1, 'sbev_linear_bf16s_gen: bad pointers / leading dimension'),
+        ('f16gen', dict(Wp=0x2008, mode=4), -1, 'sbev_linear_bf16s_gen: 16-byte alignment'),
+    ]
+    for name, overrides, status, text in table:
+        got = call[name](**overrides)
+        err = lib.sbev_last_error().decode() if got != 0 else ''
+        assert (got, err) == (status, text), (name, overrides, got, err)
+
+
+def test_bf16s_out_plan_table(lib):
+    """sbev_linear_bf16s_out_plan(M, 256, K) -- the slabs a caller provides: the largest of the three out-projection kernels' chunk
+    counts -- as a literal table, recorded from the library before the three chunk searches became one; 0 for shapes not covered."""
+    plan = lib.sbev_linear_bf16s_out_plan
+    Ks = (256, 512, 2048, 4096, 32768, 32800)
+    table = {
+        1: [2, 4, 16, 32, 64, 64],
+        31: [2, 4, 16, 32, 64, 64],
+        32: [2, 4, 16, 32, 64, 64],
+        33: [2, 4, 16, 32, 64, 64],
+        64: [2, 4, 16, 32, 64, 64],
+        65: [2, 4, 16, 32, 64, 64],
+        96: [2, 4, 16, 32, 64, 64],
+        128: [2, 4, 16, 32, 64, 64],
+        129: [2, 4, 16, 32, 64, 64],
+        256: [2, 4, 16, 32, 64, 64],
+        257: [2, 4, 16, 32, 64, 64],
+        512: [2, 4, 16, 32, 64, 64],
+        900: [2, 4, 16, 32, 32, 32],
+        1023: [2, 4, 16, 32, 32, 32],
+        1024: [2, 4, 16, 32, 64, 64],
+        1025: [2, 4, 16, 32, 51, 51],
+        1600: [2, 4, 16, 32, 59, 59],
+        2048: [2, 4, 16, 32, 32, 32],
+        2112: [2, 4, 16, 28, 31, 31],
+        3200: [2, 4, 16, 19, 51, 51],
+        3600: [2, 4, 16, 26, 58, 58],
+        4096: [2, 4, 16, 16, 16, 16],
+        4097: [2, 4, 15, 31, 63, 63],
+        8192: [2, 4, 8, 8, 8, 8],
+        16384: [2, 4, 4, 4, 4, 4],
+        65536: [1, 1, 1, 1, 1, 1],
+        100000: [2, 4, 16, 18, 47, 47],
+        4194303: [1, 1, 1, 1, 1, 1],
+    }
+    for M, row in table.items():
+        assert [plan(M, 256, K) for K in Ks] == row, (M, [plan(M, 256, K) for K in Ks])
+    assert {1, 31, 32, 33, 64, 65, 128, 129, 900, 1023, 1024, 1600, 2112, 3200, 3600, 4096, 4097} <= set(table)
+    for M in (1, 900, 4097):
+        assert plan(M, 512, 32768) == 0 and plan(M, 128, 32768) == 0 and plan(M, 256, 250) == 0 and plan(M, 256, 224) == 0
+        assert plan(M, 256, 32776) == 0          # K % 32
+    for K in Ks:
+        assert plan(0, 256, K) == 0 and plan(-1, 256, K) == 0 and plan((0x7fffffff >> 9) + 1, 256, K) == 0
+
+
 def test_product_has_no_cpu_fallback():
     import torch
     from sparsebev_amd import ops
