@@ -24,7 +24,8 @@
 //              gemm_bf16s_out3_kernel -- 64 rows x 256 columns x one chunk, X (fp32) split inside the kernel (bf16 modes; fp16 with a
 //              caller-supplied power of two);  gemm_bf16s_out4_kernel (fp16 modes, the decoder's path) -- <= 128 rows x 256 columns
 //              x one chunk, X handed over as (fp16 hi, fp16 lo) PAIRS by the mixing kernel's epilogue (sbev_*_pairs_f16), W through
-//              a wave-private LDS-DMA ring, the two K halves folded through an [m][n] image of the tile in LDS.
+//              a wave-private LDS-DMA ring, the two K halves folded through an [m][n] image of the tile in LDS;  from 1024 rows
+//              gemm_bf16s_out8_kernel -- <= 256 rows, the same pair pipeline with the two ROW halves as phase groups.
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
@@ -932,14 +933,10 @@ constexpr int O_IMG = 64 * 64;                  // bytes of one image of one hal
 // loads four ahead) and a COMPUTE phase (its 48 MFMAs, then the W fragment loads of the next slab, which land during the following
 // FETCH), a barrier after each, and the second K half takes one extra barrier up front: on every SIMD one wave computes while the
 // other fetches.  The halves never touch each other's LDS ring; they meet only in the final fold.
-// XPRE (fp16 modes): X already holds (fp16 hi, fp16 lo) pairs of x 2^e in its 32-bit slots (the mixing kernel's epilogue made them:
-// sbev_adaptive_mixing_pairs_f16 / sbev_sample_mix_pairs_f16) -- staging a slab is then 8 byte-permutes per thread instead of the
-// ~60 conversion instructions of the split, which the 24 MFMAs of an f16x3 slab no longer hide (trace: COMPUTE 1100 .. 1800 cycles
-// for 792 cycles of matrix work)
-template <int MODE, bool XPRE = false>
+// (X that already holds (fp16 hi, fp16 lo) pairs goes to the pair kernels below: gemm_bf16s_out4_kernel / gemm_bf16s_out8_kernel.)
+template <int MODE>
 __global__ __launch_bounds__(512) void gemm_bf16s_out3_kernel(const OutArgs a) {
     typedef Fmt<MODE> PR;
-    static_assert(!XPRE || PR::F16, "pre-split X is the fp16 pair format");
     constexpr int NIMG = PR::NIMG;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int HSTAGE = NIMG * O_IMG;        // one half's stage
@@ -980,15 +977,7 @@ __global__ __launch_bounds__(512) void gemm_bf16s_out3_kernel(const OutArgs a) {
     const float xup = a.xdev ? a.xdev[0] : a.xup;
     auto stagex = [&](int i, const f32x4 v0, const f32x4 v1) {       // slab i -> ring slot i % 3
         u32x4 im[NIMG];
-        if constexpr (XPRE) {
-            const u32x4 p = __builtin_bit_cast(u32x4, v0), q = __builtin_bit_cast(u32x4, v1);
-            im[0] = (u32x4){__builtin_amdgcn_perm(p.y, p.x, 0x05040100u), __builtin_amdgcn_perm(p.w, p.z, 0x05040100u),
-                            __builtin_amdgcn_perm(q.y, q.x, 0x05040100u), __builtin_amdgcn_perm(q.w, q.z, 0x05040100u)};
-            im[1] = (u32x4){__builtin_amdgcn_perm(p.y, p.x, 0x07060302u), __builtin_amdgcn_perm(p.w, p.z, 0x07060302u),
-                            __builtin_amdgcn_perm(q.y, q.x, 0x07060302u), __builtin_amdgcn_perm(q.w, q.z, 0x07060302u)};
-        } else {
-            split8m<MODE>(v0, v1, xup, im);
-        }
+        split8m<MODE>(v0, v1, xup, im);
         unsigned char* st = hst + (i % NST) * HSTAGE + wofs;
 #pragma unroll
         for (int img = 0; img < NIMG; ++img) *reinterpret_cast<u32x4*>(st + img * O_IMG) = im[img];
@@ -1140,14 +1129,14 @@ __global__ __launch_bounds__(512) void gemm_bf16s_out3_kernel(const OutArgs a) {
     else run(std::integral_constant<int, 1>{});
 }
 
-// ---- out-projection, 128-row tiles (fp16 modes, pre-split X) ---------------------------------------------------------------------
+// ---- out-projection on pre-split X (fp16 modes): the pair kernels ---------------------------------------------------------------------
 // Ablation of the kernel above in f16x3 (c2, 66 us): without its MFMAs 63, without MFMAs and stores 58 -- with three products the
 // kernel is bound by operand DELIVERY: every 64-row tile streams its K chunk of all 256 W rows from L2, 15 row tiles x 33.5 MB =
-// 503 MB (+ 118 MB of X) per launch through ~22 B/clk/CU.  Here a workgroup owns up to 128 rows (4 fragments, balanced like the
-// generator's tiles: 900 rows = 5 x 4 + 3 x 3 fragments) x all 256 columns x one K chunk: half the W bytes per MFMA.  A slab is ONE
-// 16-k step (24 MFMAs per wave with 4 row fragments, as before with 2 fragments x 2 k-steps), so a wave holds 128 accumulator
-// registers + one k-step of fragments (32) + two W sets (32); X arrives as (hi, lo) pairs (the mixing kernel's epilogue), staging is
-// 8 byte-permutes per thread.  Same ping-pong of the two K halves, same fixed-order fold: bit-reproducible.
+// 503 MB (+ 118 MB of X) per launch through ~22 B/clk/CU.  The two kernels below give a workgroup more rows (128 / 256: less W per MFMA)
+// and take X as (fp16 hi, fp16 lo) PAIRS of x 2^e in its 32-bit slots (the mixing kernel's epilogue makes them: sbev_*_pairs_f16), so
+// staging is 8 byte-permutes per thread instead of the ~60 conversion instructions of the split.  They share one operand pipeline (the
+// pieces right below) and differ in three things, which is what their bodies hold: the PHASE GROUPS (K halves / row halves), who owns a
+// W RING (a wave / a column quarter) and the EPILOGUE (K-half fold + optional slab fold / two row passes).
 struct Out4Args {
     const unsigned* Xp;          // [M, ldx] (fp16 hi, fp16 lo) pairs
     const unsigned short* Wp;    // [8][K/16][2][64][8] fp16 fragments
@@ -1163,6 +1152,196 @@ struct Out4Args {
     int debug_drop;              // test hook (sbev_debug_out_fold_drop): chunk 1 of row tile 0 never arrives -- its tile must time out, not hang
 };
 
+// ---- the pair pipeline: a phase group (4 waves, one 64-column quarter each) works on <= 128 rows x one 16-k step at a time -----------
+constexpr int PAIR_NST = 3;                               // depth of the X stage rings and of the W rings
+constexpr int PAIR_IMG = 128 * 32;                        // bytes of one image of one group's X stage: 128 rows x 16 k
+constexpr int PAIR_XSTAGE = 2 * PAIR_IMG;                 // hi | lo
+constexpr int PAIR_WSLOT = 2 * 2 * 1024;                  // one k-step in a W ring: 2 column fragments x 2 images
+constexpr int PAIR_WRING0 = 2 * PAIR_NST * PAIR_XSTAGE;   // the W rings lie behind the two groups' X stage rings
+constexpr int PAIR_FLD = 256 + 4;                         // row stride in floats of the [m][n] image of a finished tile
+
+// 8 (hi, lo) pairs -> 8 hi | 8 lo
+__device__ __forceinline__ void pair_deinterleave(const u32x4 p, const u32x4 q, u32x4& hi, u32x4& lo) {
+    hi = (u32x4){__builtin_amdgcn_perm(p.y, p.x, 0x05040100u), __builtin_amdgcn_perm(p.w, p.z, 0x05040100u),
+                 __builtin_amdgcn_perm(q.y, q.x, 0x05040100u), __builtin_amdgcn_perm(q.w, q.z, 0x05040100u)};
+    lo = (u32x4){__builtin_amdgcn_perm(p.y, p.x, 0x07060302u), __builtin_amdgcn_perm(p.w, p.z, 0x07060302u),
+                 __builtin_amdgcn_perm(q.y, q.x, 0x07060302u), __builtin_amdgcn_perm(q.w, q.z, 0x07060302u)};
+}
+
+// this workgroup's row tile and K chunk (the device side of Out4Plan)
+struct PairTile {
+    int chunk, rt;               // K chunk, row tile
+    int f0, nf;                  // first row fragment of 32 rows, row fragments (1 .. 4 of 128-row tiles, 2 .. 8 of 256-row tiles)
+    __device__ __forceinline__ explicit PairTile(const Out4Args& a) {
+        const unsigned logical = xcd_contiguous(blockIdx.x, gridDim.x);
+        const int c = (int)(logical / (unsigned)a.ntm), r = (int)(logical % (unsigned)a.ntm);
+        chunk = c, rt = r;
+        f0 = r * a.base + (r < a.rem ? r : a.rem);
+        nf = a.base + (r < a.rem ? 1 : 0);
+    }
+    __device__ __forceinline__ int row0() const { return f0 * 32; }
+    // the k-steps of 16 of K chunk ch are [kstep0(a, ch), kstep0(a, ch + 1))
+    __device__ __forceinline__ static int kstep0(const Out4Args& a, int ch) { return (int)((long long)(a.K / 16) * ch / a.S); }
+};
+
+// the k-steps a phase group walks: its i-th one, clamped (past the end the pipeline requests a dummy: the last step again)
+struct KSteps {
+    int first, last;
+    __device__ __forceinline__ int at(int i) const { return first + i < last ? first + i : last; }
+};
+
+// X of phase group 0 / 1, the <= 128 rows from row0: a k-step travels global -> registers (load) -> slot i % 3 of the group's stage
+// ring (stage).  HOOKS: the kernel carries the experiment switches of its operand stream (the 128-row kernel does).
+template <bool HOOKS>
+struct PairXRing {
+    const unsigned* xp;          // staging: thread -> (row of the group's rows, 8-k half of the step)
+    unsigned wofs;               // the thread's 16 bytes of a stage image
+    unsigned char* ring;
+    __device__ __forceinline__ PairXRing(const Out4Args& a, int tid, int row0, unsigned char* lds, int group) {
+        const int th = tid & 255;
+        const int srow = th >> 1, skq = th & 1;
+        int grow = row0 + srow;
+        grow = grow < a.M ? grow : a.M - 1;
+        xp = a.Xp + (long long)grow * a.ldx + skq * 8;
+        wofs = (unsigned)(srow * 32 + skq * 16);
+        ring = lds + group * (PAIR_NST * PAIR_XSTAGE);
+    }
+    __device__ __forceinline__ unsigned char* slot(int i) const { return ring + (i % PAIR_NST) * PAIR_XSTAGE; }
+    __device__ __forceinline__ void load(int sl, u32x4& v0, u32x4& v1) const {       // k-step sl
+#ifdef SBEV_EXP_HOTX
+        if (HOOKS) sl = sl & 7;
+#endif
+        const unsigned* p = xp + (long long)sl * 16;
+#ifdef SBEV_O4_XNT
+        if (HOOKS) {
+            v0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+            v1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + 4));
+            return;
+        }
+#endif
+        // (plain loads: a k-step uses 64 of a line's 128 bytes, the next step the rest -- the line has to survive in L2 until then)
+        v0 = *reinterpret_cast<const u32x4*>(p);
+        v1 = *reinterpret_cast<const u32x4*>(p + 4);
+    }
+    __device__ __forceinline__ void stage(int i, const u32x4 p, const u32x4 q) const {           // -> slot i % 3
+        unsigned char* st = slot(i) + wofs;
+        pair_deinterleave(p, q, *reinterpret_cast<u32x4*>(st), *reinterpret_cast<u32x4*>(st + PAIR_IMG));
+    }
+};
+
+// a lane's place in a 32-row MFMA fragment: row l31 and 8-k half lh of an operand, row l31 and 4-column pieces at 4 lh of an accumulator
+struct FragLane {
+    int l31, lh;
+    unsigned fo;                 // a fragment = 1 KiB of a stage image, read as one b128 per lane
+    __device__ __forceinline__ explicit FragLane(int lane) : l31(lane & 31), lh(lane >> 5), fo((unsigned)l31 * 32u + (unsigned)lh * 16u) {}
+};
+
+template <int NFA>
+__device__ __forceinline__ void read_x_frags(const unsigned char* stage, const FragLane fl, bf16x8 (&xf)[NFA][2]) {
+    const unsigned char* A = stage + fl.fo;
+#pragma unroll
+    for (int img = 0; img < 2; ++img)
+#pragma unroll
+        for (int fa = 0; fa < NFA; ++fa) xf[fa][img] = *reinterpret_cast<const bf16x8*>(A + img * PAIR_IMG + fa * 1024);
+}
+
+// W: the two column fragments of a quarter's k-step (2 x 2 KiB, hi | lo images adjacent) travel global -> LDS by LDS-DMA into a 3-slot
+// ring at LDS byte `base`, requested in a FETCH phase two steps ahead (issue), and are read into registers in the step's own FETCH
+// phase (read): no vector register is in flight for W and the COMPUTE phase is nothing but MFMAs.  (W requests between the MFMAs cost
+// ~200 cycles per phase -- every VMEM issue delays the next MFMA; requested at the start of the FETCH phase straight into
+// registers their L2 latency did not fit the phase: 69 us instead of 62.)  Whose ring it is, and who issues, is the kernel's business.
+template <bool HOOKS>
+struct PairWRing {
+    unsigned base;
+    const unsigned char* wg0;
+    unsigned voff;
+    int KS;
+    __device__ __forceinline__ PairWRing(const Out4Args& a, int wc, int lane, unsigned base_)
+        : base(base_), wg0(reinterpret_cast<const unsigned char*>(a.Wp) + (long long)(2 * wc) * (a.K / 16) * (2 * 1024)),
+          voff((unsigned)lane * 16u), KS(a.K / 16) {}
+    __device__ __forceinline__ void issue(int sl, int i) const {                  // k-step sl -> slot i % 3
+#ifdef SBEV_EXP_HOTW
+        if (HOOKS) sl = sl & 7;
+#endif
+        const unsigned dst = base + (unsigned)((i % PAIR_NST) * PAIR_WSLOT);
+        glds16_images<2>(wg0 + (long long)sl * (2 * 1024), voff, dst);
+        glds16_images<2>(wg0 + ((long long)KS + sl) * (2 * 1024), voff, dst + 2 * 1024);
+    }
+    __device__ __forceinline__ void read(const unsigned char* lds, int i, bf16x8 (&w)[2][2]) const {
+        const unsigned char* src = lds + base + (i % PAIR_NST) * PAIR_WSLOT + voff;
+#pragma unroll
+        for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+            for (int img = 0; img < 2; ++img) w[fb][img] = *reinterpret_cast<const bf16x8*>(src + (fb * 2 + img) * 1024);
+    }
+};
+
+template <int NFA>
+__device__ __forceinline__ void clear_acc(f32x16 (&acc)[NFA][2]) {
+#pragma unroll
+    for (int fa = 0; fa < NFA; ++fa)
+#pragma unroll
+        for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[fa][fb][e] = 0.f;
+}
+
+// a k-step's MFMAs of one wave: PR::N products x NFA row fragments x its 2 column fragments
+template <typename PR, int NFA>
+__device__ __forceinline__ void mfma_step(const bf16x8 (&w)[2][2], const bf16x8 (&xf)[NFA][2], f32x16 (&acc)[NFA][2]) {
+#pragma unroll
+    for (int p = 0; p < PR::N; ++p)
+#pragma unroll
+        for (int fa = 0; fa < NFA; ++fa)
+#pragma unroll
+            for (int fb = 0; fb < 2; ++fb) acc[fa][fb] = SBEV_MFMA(w[fb][PR::ib(p)], xf[fa][PR::ia(p)], acc[fa][fb]);
+}
+
+// a wave's accumulators -> (ADD: added in place to) the [m][n] image of its group's rows in LDS: a lane holds one output ROW m and
+// 4-column pieces.  (Storing to memory from the accumulator layout wrote 32-byte pieces of 32 rows per instruction: 19k of a
+// workgroup's 83k cycles went into the fold + stores -- f16x3 trace.)
+template <bool ADD, int NFA>
+__device__ __forceinline__ void acc_to_image(const f32x16 (&acc)[NFA][2], float* img, int wc, const FragLane fl) {
+    const int l31 = fl.l31, lh = fl.lh;
+#pragma unroll
+    for (int fa = 0; fa < NFA; ++fa)
+#pragma unroll
+        for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4* q = reinterpret_cast<f32x4*>(img + (fa * 32 + l31) * PAIR_FLD + wc * 64 + fb * 32 + 8 * g + 4 * lh);
+                if constexpr (ADD) {
+                    const f32x4 o = *q;
+                    *q = (f32x4){acc[fa][fb][4 * g] + o[0], acc[fa][fb][4 * g + 1] + o[1], acc[fa][fb][4 * g + 2] + o[2], acc[fa][fb][4 * g + 3] + o[3]};
+                } else *q = (f32x4){acc[fa][fb][4 * g], acc[fa][fb][4 * g + 1], acc[fa][fb][4 * g + 2], acc[fa][fb][4 * g + 3]};
+            }
+}
+
+// rows 0 .. nrows - 1 of the image = rows row0 .. of the matrix -> the chunk's slab: all 8 waves read whole rows back and store 1 KiB
+// per instruction.  A lane owns 4 fixed columns of the slab and their nscale (exact: powers of two)
+struct SlabLane {
+    f32x4 sc;
+    float* out;
+    __device__ __forceinline__ SlabLane(const Out4Args& a, int chunk, int lane)
+        : sc(*reinterpret_cast<const f32x4*>(a.nscale + lane * 4)), out(a.P + (long long)chunk * a.M * 256 + lane * 4) {}
+};
+__device__ __forceinline__ void image_rows_to_slab(const Out4Args& a, const SlabLane s, const float* img, int row0, int nrows, int wave, int lane) {
+    const int M = a.M;
+    for (int r = wave; r < nrows; r += 8) {
+        const int row = row0 + r;
+        if (row < M SBEV_EXP_STORE_COND)
+            *reinterpret_cast<f32x4*>(s.out + (long long)row * 256) = *reinterpret_cast<const f32x4*>(img + r * PAIR_FLD + lane * 4) * s.sc;
+    }
+}
+
+template <typename Run>
+__device__ __forceinline__ void dispatch_nfa(int nfa, Run&& run) {          // row fragments of a wave, 1 .. 4, as a constant
+    if (nfa == 4) run(std::integral_constant<int, 4>{});
+    else if (nfa == 3) run(std::integral_constant<int, 3>{});
+    else if (nfa == 2) run(std::integral_constant<int, 2>{});
+    else run(std::integral_constant<int, 1>{});
+}
+
 // a chunk-workgroup whose row tile never became complete within the poll bound (the device was shared: not every workgroup of the launch
 // was resident): counted here and in the host-mapped word the decoder's fault gate reads (csrc/row_chain.hip installs both pointers)
 __device__ unsigned g_fold_timeouts;
@@ -1170,150 +1349,135 @@ __device__ unsigned* g_fold_fault_host;
 constexpr unsigned FOLD_POLL_LIMIT = 1u << 20;
 constexpr int FOLD_CPOL = 17;    // sc0 | sc1: write-through stores, loads served past this XCD's L2 (MI355X guide, inter-workgroup visibility)
 
+// ---- the in-launch slab fold (128-row kernel, Out4Args::fold_sync): the tile's slab, written through; then its S workgroups meet and fold
+// The consumer (the tail row chain) summed the S slabs of its rows itself: 32 slabs x 8 rows = 256 KB per workgroup, read by
+// BOTH members of a pair -- 59 MB through the fabric in the first 10 us of a 48-us launch.  Here every chunk-workgroup sums
+// ceil(rows / S) rows of its tile over all S slabs (slab order 0 .. S - 1 from +0: the consumer's own order, bit for bit)
+// and the consumer reads ONE row block.  img: the finished [m][n] image of the tile's nrows rows.
+__device__ __forceinline__ void fold_slabs_in_launch(const Out4Args& a, const PairTile& t, const float* img, int nrows, int tid, int wave, int lane) {
+    const int M = a.M;
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(a.nscale + lane * 4);
+    const __amdgpu_buffer_rsrc_t slab_rs = __builtin_amdgcn_make_buffer_rsrc(a.P, 0, 0x7fffffff, 0x00020000);
+    const unsigned row_b = 1024u, slab_b = (unsigned)M * 1024u;                   // bytes (S * M * 1 KiB < 2^31: host-checked)
+    for (int r = wave; r < nrows; r += 8) {
+        const int row = t.row0() + r;
+        if (row < M) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(img + r * PAIR_FLD + lane * 4) * sc;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), slab_rs, (int)((unsigned)t.chunk * slab_b + (unsigned)row * row_b + (unsigned)lane * 16u), 0, FOLD_CPOL);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every wave: its slab rows have left
+    __syncthreads();
+    if (a.debug_drop && t.rt == 0 && t.chunk == 1) return;
+    if (tid == 0) {
+        unsigned* const word = a.fold_sync + t.rt;
+        __hip_atomic_fetch_add(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned n = 0;
+        while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)a.S) {
+            __builtin_amdgcn_s_sleep(2);
+            if (++n > FOLD_POLL_LIMIT) {
+                __hip_atomic_fetch_add(&g_fold_timeouts, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                unsigned* const host_word = g_fold_fault_host;
+                if (host_word) __hip_atomic_fetch_add(host_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                break;
+            }
+        }
+    }
+    __syncthreads();
+    const int rp = (nrows + a.S - 1) / a.S;                   // rows of the tile per chunk-workgroup (4 at 128 rows x 32 chunks)
+    for (int j = wave; j < rp; j += 8) {
+        const int r = t.chunk * rp + j, row = t.row0() + r;
+        if (r >= nrows || row >= M) continue;
+        f32x4 s = {0.f, 0.f, 0.f, 0.f};
+        const unsigned base_b = (unsigned)row * row_b + (unsigned)lane * 16u;
+        for (int z0 = 0; z0 < a.S; z0 += 32) {
+            f32x4 q[32];
+#pragma unroll
+            for (int z = 0; z < 32; ++z) {
+                const int zz = z0 + z < a.S ? z0 + z : a.S - 1;
+                q[z] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(slab_rs, (int)((unsigned)zz * slab_b + base_b), 0, FOLD_CPOL));
+            }
+#pragma unroll
+            for (int z = 0; z < 32; ++z) {
+                const float m = z0 + z < a.S ? 1.f : 0.f;
+                s[0] += q[z][0] * m; s[1] += q[z][1] * m; s[2] += q[z][2] * m; s[3] += q[z][3] * m;
+            }
+        }
+        *reinterpret_cast<f32x4*>(a.folded + (long long)row * 256 + lane * 4) = s;
+    }
+}
+
+// ---- out-projection, 128-row tiles -----------------------------------------------------------------------------------------------
+// A workgroup owns up to 128 rows (4 fragments, balanced like the generator's tiles: 900 rows = 5 x 4 + 3 x 3 fragments) x all 256
+// columns x one K chunk: half the W bytes per MFMA of the 64-row kernel.  A slab is ONE 16-k step (24 MFMAs per wave with 4 row
+// fragments, as before with 2 fragments x 2 k-steps), so a wave holds 128 accumulator registers + one k-step of fragments (32) + one W
+// set (16).  The phase groups are the two K HALVES of the chunk, each wave has a W ring of its own, and the halves are folded in fixed
+// order through the [m][n] image: bit-reproducible.
 template <int MODE>
 __global__ __launch_bounds__(512) void gemm_bf16s_out4_kernel(const Out4Args a) {
     typedef Fmt<MODE> PR;
     static_assert(PR::F16 && PR::NIMG == 2, "pre-split fp16 operands");
-    constexpr int NIMG = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr int IMG = 128 * 32;               // bytes of one image of one half's stage: 128 rows x 16 k
-    constexpr int HSTAGE = NIMG * IMG;
-    constexpr int NST = 3;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = wave >> 2, wc = wave & 3;  // K half of the chunk = phase group, 64-column quarter
     SBEV_WGTIME(3, 0)
-    const unsigned logical = xcd_contiguous(blockIdx.x, gridDim.x);
-    const int chunk = (int)(logical / (unsigned)a.ntm), rt = (int)(logical % (unsigned)a.ntm);
-    const int M = a.M;
-    const int f0 = rt * a.base + (rt < a.rem ? rt : a.rem);
-    const int nfa = a.base + (rt < a.rem ? 1 : 0);               // row fragments of this tile: 1 .. 4
-    const int m0 = f0 * 32;
-    const int KS = a.K / 16;
-    const int c0 = (int)((long long)KS * chunk / a.S), c1 = (int)((long long)KS * (chunk + 1) / a.S);
+    const PairTile t(a);
+    const int m0 = t.row0();
+    const int c0 = t.kstep0(a, t.chunk), c1 = t.kstep0(a, t.chunk + 1);
     const int n_all = c1 - c0, n0h = (n_all + 1) / 2;
     const int sb = half == 0 ? c0 : c0 + n0h;            // first k-step of this half
     const int nh = half == 0 ? n0h : n_all - n0h;        // its k-steps (half 0 may have one more)
-
-    const int th = tid & 255;
-    const int srow = th >> 1, skq = th & 1;              // staging: thread -> (row of the tile, 8-k half of the step)
-    int grow = m0 + srow;
-    grow = grow < M ? grow : M - 1;
-    const unsigned* xp = a.Xp + (long long)grow * a.ldx + skq * 8;
-    const unsigned wofs = (unsigned)(srow * 32 + skq * 16);
-    unsigned char* hst = lds + half * (NST * HSTAGE);    // this half's stage ring
-    const int last = nh > 0 ? sb + nh - 1 : c1 - 1;
-    auto loadx = [&](int i, u32x4& v0, u32x4& v1) {      // k-step i of this half (clamped: a dummy past the end)
-        int sl = sb + i;
-        sl = sl < last ? sl : last;
-#ifdef SBEV_EXP_HOTX
-        sl = sl & 7;
-#endif
-        const unsigned* p = xp + (long long)sl * 16;
-#ifdef SBEV_O4_XNT
-        v0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-        v1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + 4));
-#else
-        // (plain loads: a k-step uses 64 of a line's 128 bytes, the next step the rest -- the line has to survive in L2 until then)
-        v0 = *reinterpret_cast<const u32x4*>(p);
-        v1 = *reinterpret_cast<const u32x4*>(p + 4);
-#endif
-    };
-    auto stagex = [&](int i, const u32x4 p, const u32x4 q) {                     // k-step i -> ring slot i % 3: de-interleave hi | lo
-        unsigned char* st = hst + (i % NST) * HSTAGE + wofs;
-        *reinterpret_cast<u32x4*>(st) = (u32x4){__builtin_amdgcn_perm(p.y, p.x, 0x05040100u), __builtin_amdgcn_perm(p.w, p.z, 0x05040100u),
-                                                __builtin_amdgcn_perm(q.y, q.x, 0x05040100u), __builtin_amdgcn_perm(q.w, q.z, 0x05040100u)};
-        *reinterpret_cast<u32x4*>(st + IMG) = (u32x4){__builtin_amdgcn_perm(p.y, p.x, 0x07060302u), __builtin_amdgcn_perm(p.w, p.z, 0x07060302u),
-                                                      __builtin_amdgcn_perm(q.y, q.x, 0x07060302u), __builtin_amdgcn_perm(q.w, q.z, 0x07060302u)};
-    };
-    // W: this wave's two column fragments of a k-step (2 x 2 KiB, hi | lo images adjacent) travel global -> LDS by LDS-DMA into a
-    // wave-private 3-slot ring, requested in the FETCH phase two steps ahead, and are read into registers in the step's own FETCH
-    // phase: no vector register is in flight for W and the COMPUTE phase is nothing but MFMAs.  (W requests between the MFMAs cost
-    // ~200 cycles per phase -- every VMEM issue delays the next MFMA; requested at the start of the FETCH phase straight into
-    // registers their L2 latency did not fit the phase: 69 us instead of 62.)
-    constexpr int WSLOT = 2 * NIMG * 1024;               // one step of one wave: 2 column fragments x 2 images
-    constexpr int WRING0 = 2 * NST * HSTAGE;             // behind the two halves' X stages
-    const unsigned wring = (unsigned)(WRING0 + wave * (NST * WSLOT));
-    const unsigned char* wg0 = reinterpret_cast<const unsigned char*>(a.Wp) + (long long)(2 * wc) * KS * (NIMG * 1024);
-    const unsigned voff = (unsigned)lane * 16u;
-    auto issue_w = [&](int i) {                          // k-step i of this half (clamped) -> ring slot i % 3
-        int sl = sb + i;
-        sl = sl < last ? sl : last;
-#ifdef SBEV_EXP_HOTW
-        sl = sl & 7;
-#endif
-        const unsigned dst = wring + (unsigned)((i % NST) * WSLOT);
-        glds16_images<NIMG>(wg0 + (long long)sl * (NIMG * 1024), voff, dst);
-        glds16_images<NIMG>(wg0 + ((long long)KS + sl) * (NIMG * 1024), voff, dst + NIMG * 1024);
-    };
-    auto readw = [&](int i, bf16x8 (&w)[2][NIMG]) {
-        const unsigned char* src = lds + wring + (i % NST) * WSLOT + voff;
-#pragma unroll
-        for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-            for (int img = 0; img < NIMG; ++img) w[fb][img] = *reinterpret_cast<const bf16x8*>(src + (fb * NIMG + img) * 1024);
-    };
-    const int l31 = lane & 31, lh = lane >> 5;
-    const unsigned fo = (unsigned)l31 * 32u + (unsigned)lh * 16u;       // a fragment = 1 KiB of the image, read as one b128 per lane
+    const PairXRing<true> x(a, tid, m0, lds, half);
+    const KSteps ks{sb, nh > 0 ? sb + nh - 1 : c1 - 1};
+    const PairWRing<true> w(a, wc, lane, (unsigned)(PAIR_WRING0 + wave * (PAIR_NST * PAIR_WSLOT)));      // wave-private
+    const FragLane fl(lane);
 
     auto run = [&](auto nfa_c) {
         constexpr int NFA = decltype(nfa_c)::value;
         f32x16 acc[NFA][2];
-#pragma unroll
-        for (int fa = 0; fa < NFA; ++fa)
-#pragma unroll
-            for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[fa][fb][e] = 0.f;
+        clear_acc(acc);
         u32x4 xa0, xa1, xb0, xb1;                             // X register ring: k-step s + 2 waits in a (s even) / b (s odd)
-        bf16x8 wa[2][NIMG], xf[NFA][NIMG];                    // one W set: the next step's request goes out behind this step's last MFMA
+        bf16x8 wa[2][2], xf[NFA][2];                          // one W set: the next step's request goes out behind this step's last MFMA
                                                               // and lands during the partner's COMPUTE phase (a second set spilled)
         // prologue: k-steps 0 and 1 staged, X of 2 and 3 and W of 0 and 1 requested -- and landed: the counted waits below then
         // start from "nothing outstanding" (per step a wave issues 4 W requests, then 2 X requests)
-        loadx(0, xa0, xa1);
-        loadx(1, xb0, xb1);
-        issue_w(0);
-        issue_w(1);
-        stagex(0, xa0, xa1);
-        loadx(2, xa0, xa1);
-        stagex(1, xb0, xb1);
-        loadx(3, xb0, xb1);
+        x.load(ks.at(0), xa0, xa1);
+        x.load(ks.at(1), xb0, xb1);
+        w.issue(ks.at(0), 0);
+        w.issue(ks.at(1), 1);
+        x.stage(0, xa0, xa1);
+        x.load(ks.at(2), xa0, xa1);
+        x.stage(1, xb0, xb1);
+        x.load(ks.at(3), xb0, xb1);
         wait_vmcnt_imm<0>();
         __syncthreads();
         if (half == 1) phase_barrier();                       // the second K half runs one phase behind
-#define SBEV_O4_STEP(S_, X0, X1)                                                                    \
+#define SBEV_O4_STEP(S_, X0, X1)                                                                            \
         {                                                                                                   \
-            /* FETCH: the step's fragments LDS -> registers */                                              \
-            {                                                                                               \
-                SBEV_TRACE(S_, 0)                                                                           \
-                /* W of this step (requested two steps ago) has landed once at most the 8 younger requests are outstanding: X of */ \
-                /* step + 2 (2), W of step + 1 (4), X of step + 3 (2) -- vector memory operations complete in order             */ \
-                wait_vmcnt_imm<8>();                                                                        \
-                readw((S_), wa);                                                                            \
-                const unsigned char* A = hst + ((S_) % NST) * HSTAGE + fo;                                  \
-                _Pragma("unroll") for (int img = 0; img < NIMG; ++img)                                      \
-                    _Pragma("unroll") for (int fa = 0; fa < NFA; ++fa)                                      \
-                        xf[fa][img] = *reinterpret_cast<const bf16x8*>(A + img * IMG + fa * 1024);          \
-                if ((S_) >= nh) {      /* the unequal last step: this half has none left and multiplies zeros */ \
-                    _Pragma("unroll") for (int fa = 0; fa < NFA; ++fa)                                      \
-                        _Pragma("unroll") for (int img = 0; img < NIMG; ++img)                              \
-                            _Pragma("unroll") for (int e = 0; e < 8; ++e) xf[fa][img][e] = (__bf16)0.f;     \
-                }                                                                                           \
-                SBEV_TRACE(S_, 1)                                                                           \
-                /* the staging of step + 2 and the X request of step + 4 also ride here: this phase otherwise waits ~800 cycles at its */ \
-                /* barrier for the partner's MFMAs, and in the COMPUTE phase every VMEM issue delays the next MFMA                    */ \
-                stagex((S_) + 2, X0, X1);                                                                   \
-                __builtin_amdgcn_sched_barrier(0);     /* (the W requests stay behind the staging: the compiler's wait for X counts only its own loads) */ \
-                issue_w((S_) + 2);                                                                          \
-                loadx((S_) + 4, X0, X1);                                                                    \
+            /* FETCH: the step's fragments LDS -> registers.  W of this step (requested two steps ago) has landed once at most the 8 */ \
+            /* younger requests are outstanding: X of step + 2 (2), W of step + 1 (4), X of step + 3 (2) -- vector memory operations */ \
+            /* complete in order                                                                                                   */ \
+            SBEV_TRACE(S_, 0)                                                                               \
+            wait_vmcnt_imm<8>();                                                                            \
+            w.read(lds, (S_), wa);                                                                          \
+            read_x_frags(x.slot(S_), fl, xf);                                                               \
+            if ((S_) >= nh) {          /* the unequal last step: this half has none left and multiplies zeros */ \
+                _Pragma("unroll") for (int fa = 0; fa < NFA; ++fa)                                          \
+                    _Pragma("unroll") for (int img = 0; img < 2; ++img)                                     \
+                        _Pragma("unroll") for (int e = 0; e < 8; ++e) xf[fa][img][e] = (__bf16)0.f;         \
             }                                                                                               \
+            SBEV_TRACE(S_, 1)                                                                               \
+            /* the staging of step + 2 and the X request of step + 4 also ride here: this phase otherwise waits ~800 cycles at its */ \
+            /* barrier for the partner's MFMAs, and in the COMPUTE phase every VMEM issue delays the next MFMA                    */ \
+            x.stage((S_) + 2, X0, X1);                                                                      \
+            __builtin_amdgcn_sched_barrier(0);     /* (the W requests stay behind the staging: the compiler's wait for X counts only its own loads) */ \
+            w.issue(ks.at((S_) + 2), (S_) + 2);                                                             \
+            x.load(ks.at((S_) + 4), X0, X1);                                                                \
             phase_barrier();                                                                                \
             SBEV_TRACE(S_, 4)                                                                               \
             /* COMPUTE: the step's MFMAs, nothing else */                                                   \
-            _Pragma("unroll") for (int p = 0; p < PR::N; ++p)                                               \
-                _Pragma("unroll") for (int fa = 0; fa < NFA; ++fa)                                          \
-                    _Pragma("unroll") for (int fb = 0; fb < 2; ++fb)                                        \
-                        acc[fa][fb] = SBEV_MFMA(wa[fb][PR::ib(p)], xf[fa][PR::ia(p)], acc[fa][fb]);         \
+            mfma_step<PR>(wa, xf, acc);                                                                     \
             SBEV_TRACE(S_, 5)                                                                               \
             phase_barrier();                                                                                \
             SBEV_TRACE(S_, 6)                                                                               \
@@ -1326,111 +1490,23 @@ __global__ __launch_bounds__(512) void gemm_bf16s_out4_kernel(const Out4Args a) 
         if (sl < n0h) SBEV_O4_STEP(sl, xa0, xa1)
 #undef SBEV_O4_STEP
         if (half == 0) phase_barrier();
-        // fold the two K halves (fixed order: bit-reproducible) and write the chunk's slab -- through an [m][n] image of the whole tile in
-        // LDS: K half 1 writes its accumulators there (a lane holds one output ROW m and 4-column pieces), half 0 adds its own in
-        // place, then all 8 waves read whole rows back and store 1 KiB per instruction.  (Storing from the accumulator layout wrote
-        // 32-byte pieces of 32 rows per instruction: 19k of a workgroup's 83k cycles went into the fold + stores -- f16x3 trace.)
+        // fold the two K halves (fixed order: bit-reproducible) through the [m][n] image of the whole tile: half 1 writes its accumulators
+        // there, half 0 adds its own in place; then the chunk's slab leaves, or the row tile's slabs are folded right here
         wait_vmcnt_imm<0>();                                   // the last (dummy, clamped) W requests still write LDS this image reuses
         __syncthreads();
-        constexpr int FLD = 256 + 4;                           // image row stride in floats
         float* img = reinterpret_cast<float*>(lds);
-        if (half == 1) {
-#pragma unroll
-            for (int fa = 0; fa < NFA; ++fa)
-#pragma unroll
-                for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        *reinterpret_cast<f32x4*>(img + (fa * 32 + l31) * FLD + wc * 64 + fb * 32 + 8 * g + 4 * lh) =
-                            (f32x4){acc[fa][fb][4 * g], acc[fa][fb][4 * g + 1], acc[fa][fb][4 * g + 2], acc[fa][fb][4 * g + 3]};
-        }
+        if (half == 1) acc_to_image<false>(acc, img, wc, fl);
         __syncthreads();
-        if (half == 0) {
-#pragma unroll
-            for (int fa = 0; fa < NFA; ++fa)
-#pragma unroll
-                for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        f32x4* q = reinterpret_cast<f32x4*>(img + (fa * 32 + l31) * FLD + wc * 64 + fb * 32 + 8 * g + 4 * lh);
-                        const f32x4 o = *q;
-                        *q = (f32x4){acc[fa][fb][4 * g] + o[0], acc[fa][fb][4 * g + 1] + o[1], acc[fa][fb][4 * g + 2] + o[2], acc[fa][fb][4 * g + 3] + o[3]};
-                    }
-        }
+        if (half == 0) acc_to_image<true>(acc, img, wc, fl);
         __syncthreads();
-        if (a.fold_sync == nullptr) {
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(a.nscale + lane * 4);          // a lane owns 4 fixed columns: exact powers of two
-            float* out = a.P + (long long)chunk * M * 256 + lane * 4;
-            for (int r = wave; r < NFA * 32; r += 8) {
-                const int row = m0 + r;
-                if (row < M SBEV_EXP_STORE_COND)
-                    *reinterpret_cast<f32x4*>(out + (long long)row * 256) = *reinterpret_cast<const f32x4*>(img + r * FLD + lane * 4) * sc;
-            }
-        } else {
-            // ---- the same slab, written through; then the row tile's S workgroups meet and fold ------------------------------------
-            // The consumer (the tail row chain) summed the S slabs of its rows itself: 32 slabs x 8 rows = 256 KB per workgroup, read by
-            // BOTH members of a pair -- 59 MB through the fabric in the first 10 us of a 48-us launch.  Here every chunk-workgroup sums
-            // ceil(rows / S) rows of its tile over all S slabs (slab order 0 .. S - 1 from +0: the consumer's own order, bit for bit)
-            // and the consumer reads ONE row block.
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(a.nscale + lane * 4);
-            const __amdgpu_buffer_rsrc_t slab_rs = __builtin_amdgcn_make_buffer_rsrc(a.P, 0, 0x7fffffff, 0x00020000);
-            const unsigned row_b = 1024u, slab_b = (unsigned)M * 1024u;                   // bytes (S * M * 1 KiB < 2^31: host-checked)
-            for (int r = wave; r < NFA * 32; r += 8) {
-                const int row = m0 + r;
-                if (row < M) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(img + r * FLD + lane * 4) * sc;
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), slab_rs, (int)((unsigned)chunk * slab_b + (unsigned)row * row_b + (unsigned)lane * 16u), 0, FOLD_CPOL);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every wave: its slab rows have left
-            __syncthreads();
-            if (a.debug_drop && rt == 0 && chunk == 1) return;
-            if (tid == 0) {
-                unsigned* const word = a.fold_sync + rt;
-                __hip_atomic_fetch_add(word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                unsigned n = 0;
-                while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)a.S) {
-                    __builtin_amdgcn_s_sleep(2);
-                    if (++n > FOLD_POLL_LIMIT) {
-                        __hip_atomic_fetch_add(&g_fold_timeouts, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        unsigned* const host_word = g_fold_fault_host;
-                        if (host_word) __hip_atomic_fetch_add(host_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        break;
-                    }
-                }
-            }
-            __syncthreads();
-            const int rp = (NFA * 32 + a.S - 1) / a.S;                // rows of the tile per chunk-workgroup (4 at 128 rows x 32 chunks)
-            for (int j = wave; j < rp; j += 8) {
-                const int r = chunk * rp + j, row = m0 + r;
-                if (r >= NFA * 32 || row >= M) continue;
-                f32x4 t = {0.f, 0.f, 0.f, 0.f};
-                const unsigned base_b = (unsigned)row * row_b + (unsigned)lane * 16u;
-                for (int z0 = 0; z0 < a.S; z0 += 32) {
-                    f32x4 q[32];
-#pragma unroll
-                    for (int z = 0; z < 32; ++z) {
-                        const int zz = z0 + z < a.S ? z0 + z : a.S - 1;
-                        q[z] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(slab_rs, (int)((unsigned)zz * slab_b + base_b), 0, FOLD_CPOL));
-                    }
-#pragma unroll
-                    for (int z = 0; z < 32; ++z) {
-                        const float m = z0 + z < a.S ? 1.f : 0.f;
-                        t[0] += q[z][0] * m; t[1] += q[z][1] * m; t[2] += q[z][2] * m; t[3] += q[z][3] * m;
-                    }
-                }
-                *reinterpret_cast<f32x4*>(a.folded + (long long)row * 256 + lane * 4) = t;
-            }
-        }
+        if (a.fold_sync == nullptr) image_rows_to_slab(a, SlabLane(a, t.chunk, lane), img, m0, NFA * 32, wave, lane);
+        else fold_slabs_in_launch(a, t, img, NFA * 32, tid, wave, lane);
         SBEV_WGTIME(3, 1)
     };
-    if (nfa == 4) run(std::integral_constant<int, 4>{});
-    else if (nfa == 3) run(std::integral_constant<int, 3>{});
-    else if (nfa == 2) run(std::integral_constant<int, 2>{});
-    else run(std::integral_constant<int, 1>{});
+    dispatch_nfa(t.nf, run);
 }
 
-// ---- out-projection, 256-row tiles (fp16 modes, pre-split X; round 6: from 1024 rows -- the batch shapes and the 1600-query config) -------------------------------------
+// ---- out-projection, 256-row tiles (round 6: from 1024 rows -- the batch shapes and the 1600-query config) -------------------------------
 // At 3200 / 3600 rows the 128-row kernel above reaches 0.28 / 0.31 of the matrix peak while the generator reaches 0.46 on the same rows:
 // every 128-row tile streams its K chunk of ALL 256 W rows through the L2 -> LDS path -- 25 tiles x 33.5 MB of W + 420 MB of X per launch at
 // 3200 rows -- and that delivery adds to the matrix time instead of hiding under it (DESIGN_HISTORY.md section 11.7).  Here a workgroup owns up to
@@ -1444,115 +1520,54 @@ template <int MODE>
 __global__ __launch_bounds__(512) void gemm_bf16s_out8_kernel(const Out4Args a) {
     typedef Fmt<MODE> PR;
     static_assert(PR::F16 && PR::NIMG == 2, "pre-split fp16 operands");
-    constexpr int NIMG = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr int IMG = 128 * 32;               // bytes of one image of one group's stage: 128 rows x 16 k
-    constexpr int HSTAGE = NIMG * IMG;
-    constexpr int NST = 3;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rh = wave >> 2, wc = wave & 3;    // row half of the tile = phase group, 64-column quarter
-    const unsigned logical = xcd_contiguous(blockIdx.x, gridDim.x);
-    const int chunk = (int)(logical / (unsigned)a.ntm), rt = (int)(logical % (unsigned)a.ntm);
-    const int M = a.M;
-    const int f0 = rt * a.base + (rt < a.rem ? rt : a.rem);
-    const int nf = a.base + (rt < a.rem ? 1 : 0);                // row fragments of this tile: 2 .. 8
-    const int nfa0 = (nf + 1) / 2, nfa1 = nf / 2;                // ... of row half 0 / 1
+    const PairTile t(a);
+    const int nfa0 = (t.nf + 1) / 2, nfa1 = t.nf / 2;            // row fragments of row half 0 / 1
     const int nfa = rh == 0 ? nfa0 : nfa1;
-    const int m0 = f0 * 32, mh = m0 + (rh == 0 ? 0 : nfa0 * 32);
-    const int KS = a.K / 16;
-    const int c0 = (int)((long long)KS * chunk / a.S), c1 = (int)((long long)KS * (chunk + 1) / a.S);
+    const int m0 = t.row0(), mh = m0 + (rh == 0 ? 0 : nfa0 * 32);
+    const int c0 = t.kstep0(a, t.chunk), c1 = t.kstep0(a, t.chunk + 1);
     const int n_all = c1 - c0;                  // both groups walk every k-step of the chunk
-
-    const int th = tid & 255;
-    const int srow = th >> 1, skq = th & 1;     // staging: thread -> (row of its half, 8-k half of the step)
-    int grow = mh + srow;
-    grow = grow < M ? grow : M - 1;
-    const unsigned* xp = a.Xp + (long long)grow * a.ldx + skq * 8;
-    const unsigned wofs = (unsigned)(srow * 32 + skq * 16);
-    unsigned char* hst = lds + rh * (NST * HSTAGE);              // this group's X stage ring
-    const int last = c1 - 1;
-    auto loadx = [&](int i, u32x4& v0, u32x4& v1) {              // k-step i (clamped: a dummy past the end)
-        int sl = c0 + i;
-        sl = sl < last ? sl : last;
-        const unsigned* p = xp + (long long)sl * 16;
-        v0 = *reinterpret_cast<const u32x4*>(p);
-        v1 = *reinterpret_cast<const u32x4*>(p + 4);
-    };
-    auto stagex = [&](int i, const u32x4 p, const u32x4 q) {     // k-step i -> ring slot i % 3: de-interleave hi | lo
-        unsigned char* st = hst + (i % NST) * HSTAGE + wofs;
-        *reinterpret_cast<u32x4*>(st) = (u32x4){__builtin_amdgcn_perm(p.y, p.x, 0x05040100u), __builtin_amdgcn_perm(p.w, p.z, 0x05040100u),
-                                                __builtin_amdgcn_perm(q.y, q.x, 0x05040100u), __builtin_amdgcn_perm(q.w, q.z, 0x05040100u)};
-        *reinterpret_cast<u32x4*>(st + IMG) = (u32x4){__builtin_amdgcn_perm(p.y, p.x, 0x07060302u), __builtin_amdgcn_perm(p.w, p.z, 0x07060302u),
-                                                      __builtin_amdgcn_perm(q.y, q.x, 0x07060302u), __builtin_amdgcn_perm(q.w, q.z, 0x07060302u)};
-    };
-    // W: ONE 3-slot ring per column quarter, filled by the quarter's group-0 wave, read by both of its waves
-    constexpr int WSLOT = 2 * NIMG * 1024;               // one step of one quarter: 2 column fragments x 2 images
-    constexpr int WRING0 = 2 * NST * HSTAGE;             // behind the two groups' X stages
-    const unsigned wring = (unsigned)(WRING0 + wc * (NST * WSLOT));
-    const unsigned char* wg0 = reinterpret_cast<const unsigned char*>(a.Wp) + (long long)(2 * wc) * KS * (NIMG * 1024);
-    const unsigned voff = (unsigned)lane * 16u;
-    auto issue_w = [&](int i) {                          // (group 0 only) k-step i (clamped) -> ring slot i % 3
-        int sl = c0 + i;
-        sl = sl < last ? sl : last;
-        const unsigned dst = wring + (unsigned)((i % NST) * WSLOT);
-        glds16_images<NIMG>(wg0 + (long long)sl * (NIMG * 1024), voff, dst);
-        glds16_images<NIMG>(wg0 + ((long long)KS + sl) * (NIMG * 1024), voff, dst + NIMG * 1024);
-    };
-    auto readw = [&](int i, bf16x8 (&w)[2][NIMG]) {
-        const unsigned char* src = lds + wring + (i % NST) * WSLOT + voff;
-#pragma unroll
-        for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-            for (int img = 0; img < NIMG; ++img) w[fb][img] = *reinterpret_cast<const bf16x8*>(src + (fb * NIMG + img) * 1024);
-    };
-    const int l31 = lane & 31, lh = lane >> 5;
-    const unsigned fo = (unsigned)l31 * 32u + (unsigned)lh * 16u;
+    const PairXRing<false> x(a, tid, mh, lds, rh);
+    const KSteps ks{c0, c1 - 1};
+    // W: ONE ring per column quarter, filled by the quarter's group-0 wave, read by both of its waves
+    const PairWRing<false> w(a, wc, lane, (unsigned)(PAIR_WRING0 + wc * (PAIR_NST * PAIR_WSLOT)));
+    const FragLane fl(lane);
 
     auto run = [&](auto nfa_c) {
         constexpr int NFA = decltype(nfa_c)::value;
         f32x16 acc[NFA][2];
-#pragma unroll
-        for (int fa = 0; fa < NFA; ++fa)
-#pragma unroll
-            for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[fa][fb][e] = 0.f;
-        u32x4 xa0, xa1, xb0, xb1;
-        bf16x8 wa[2][NIMG], xf[NFA][NIMG];
-        loadx(0, xa0, xa1);
-        loadx(1, xb0, xb1);
-        if (rh == 0) { issue_w(0); issue_w(1); }
-        stagex(0, xa0, xa1);
-        loadx(2, xa0, xa1);
-        stagex(1, xb0, xb1);
-        loadx(3, xb0, xb1);
+        clear_acc(acc);
+        u32x4 xa0, xa1, xb0, xb1;                             // X register ring, as in the 128-row kernel
+        bf16x8 wa[2][2], xf[NFA][2];
+        x.load(ks.at(0), xa0, xa1);
+        x.load(ks.at(1), xb0, xb1);
+        if (rh == 0) { w.issue(ks.at(0), 0); w.issue(ks.at(1), 1); }
+        x.stage(0, xa0, xa1);
+        x.load(ks.at(2), xa0, xa1);
+        x.stage(1, xb0, xb1);
+        x.load(ks.at(3), xb0, xb1);
         wait_vmcnt_imm<0>();
         __syncthreads();
         if (rh == 1) phase_barrier();                         // the second row half runs one phase behind
-#define SBEV_O8_STEP(S_, X0, X1)                                                                    \
+#define SBEV_O8_STEP(S_, X0, X1)                                                                            \
         {                                                                                                   \
-            {   /* FETCH */                                                                                 \
-                /* group 0: W of this step (its own request of two steps ago) has landed once at most the 8 younger requests are */ \
-                /* outstanding (X of step + 2, W of step + 1, X of step + 3); group 1 reads the slot one phase -- one barrier -- later */ \
-                wait_vmcnt_imm<8>();                                                                        \
-                readw((S_), wa);                                                                            \
-                const unsigned char* A = hst + ((S_) % NST) * HSTAGE + fo;                                  \
-                _Pragma("unroll") for (int img = 0; img < NIMG; ++img)                                      \
-                    _Pragma("unroll") for (int fa = 0; fa < NFA; ++fa)                                      \
-                        xf[fa][img] = *reinterpret_cast<const bf16x8*>(A + img * IMG + fa * 1024);          \
-                stagex((S_) + 2, X0, X1);                                                                   \
-                __builtin_amdgcn_sched_barrier(0);                                                          \
-                if (rh == 0) issue_w((S_) + 2);                                                             \
-                loadx((S_) + 4, X0, X1);                                                                    \
-                /* the slot read above is overwritten by group 0's request of the NEXT phase: the reads must have returned by the barrier */ \
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                          \
-            }                                                                                               \
+            /* FETCH.  Group 0: W of this step (its own request of two steps ago) has landed once at most the 8 younger requests are */ \
+            /* outstanding (X of step + 2, W of step + 1, X of step + 3); group 1 reads the slot one phase -- one barrier -- later    */ \
+            wait_vmcnt_imm<8>();                                                                            \
+            w.read(lds, (S_), wa);                                                                          \
+            read_x_frags(x.slot(S_), fl, xf);                                                               \
+            x.stage((S_) + 2, X0, X1);                                                                      \
+            __builtin_amdgcn_sched_barrier(0);                                                              \
+            if (rh == 0) w.issue(ks.at((S_) + 2), (S_) + 2);                                                \
+            x.load(ks.at((S_) + 4), X0, X1);                                                                \
+            /* the slot read above is overwritten by group 0's request of the NEXT phase: the reads must have returned by the barrier */ \
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                              \
             phase_barrier();                                                                                \
-            _Pragma("unroll") for (int p = 0; p < PR::N; ++p)                                               \
-                _Pragma("unroll") for (int fa = 0; fa < NFA; ++fa)                                          \
-                    _Pragma("unroll") for (int fb = 0; fb < 2; ++fb)                                        \
-                        acc[fa][fb] = SBEV_MFMA(wa[fb][PR::ib(p)], xf[fa][PR::ia(p)], acc[fa][fb]);         \
+            /* COMPUTE */                                                                                   \
+            mfma_step<PR>(wa, xf, acc);                                                                     \
             phase_barrier();                                                                                \
         }
         int sl = 0;
@@ -1563,40 +1578,20 @@ __global__ __launch_bounds__(512) void gemm_bf16s_out8_kernel(const Out4Args a) 
         if (sl < n_all) SBEV_O8_STEP(sl, xa0, xa1)
 #undef SBEV_O8_STEP
         if (rh == 0) phase_barrier();
-        // the chunk's slab: one row half at a time through an [m][n] image in LDS (a lane holds one output ROW m and 4-column pieces), all 8
-        // waves then read whole rows back and store 1 KiB per instruction
+        // the chunk's slab: one row half at a time through the [m][n] image
         wait_vmcnt_imm<0>();                                   // the last (dummy, clamped) W requests still write LDS this image reuses
         __syncthreads();
-        constexpr int FLD = 256 + 4;
         float* img = reinterpret_cast<float*>(lds);
-        const f32x4 sc = *reinterpret_cast<const f32x4*>(a.nscale + lane * 4);
-        float* out = a.P + (long long)chunk * M * 256 + lane * 4;
+        const SlabLane slab(a, t.chunk, lane);
 #pragma unroll
         for (int pass = 0; pass < 2; ++pass) {
-            if (rh == pass) {
-#pragma unroll
-                for (int fa = 0; fa < NFA; ++fa)
-#pragma unroll
-                    for (int fb = 0; fb < 2; ++fb)
-#pragma unroll
-                        for (int g = 0; g < 4; ++g)
-                            *reinterpret_cast<f32x4*>(img + (fa * 32 + l31) * FLD + wc * 64 + fb * 32 + 8 * g + 4 * lh) =
-                                (f32x4){acc[fa][fb][4 * g], acc[fa][fb][4 * g + 1], acc[fa][fb][4 * g + 2], acc[fa][fb][4 * g + 3]};
-            }
+            if (rh == pass) acc_to_image<false>(acc, img, wc, fl);
             __syncthreads();
-            const int prow0 = m0 + (pass == 0 ? 0 : nfa0 * 32), prows = (pass == 0 ? nfa0 : nfa1) * 32;
-            for (int r = wave; r < prows; r += 8) {
-                const int row = prow0 + r;
-                if (row < M SBEV_EXP_STORE_COND)
-                    *reinterpret_cast<f32x4*>(out + (long long)row * 256) = *reinterpret_cast<const f32x4*>(img + r * FLD + lane * 4) * sc;
-            }
+            image_rows_to_slab(a, slab, img, m0 + (pass == 0 ? 0 : nfa0 * 32), (pass == 0 ? nfa0 : nfa1) * 32, wave, lane);
             __syncthreads();
         }
     };
-    if (nfa == 4) run(std::integral_constant<int, 4>{});
-    else if (nfa == 3) run(std::integral_constant<int, 3>{});
-    else if (nfa == 2) run(std::integral_constant<int, 2>{});
-    else run(std::integral_constant<int, 1>{});
+    dispatch_nfa(nfa, run);
 }
 
 template <typename Kern>
