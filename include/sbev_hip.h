@@ -500,8 +500,8 @@ int sbev_copy_widen_f32(const void* src, int src_dtype, float* dst, int64_t n, s
  * sbev_adaptive_mixing_f32 on it -- bit-identical to the two launches, without the [B,Q,G,T*P,C] round trip through HBM.
  * Replaces: sampling_4d's gather + the middle of AdaptiveMixing.inner_forward (models/sparsebev_sampling.py:122-128,
  *           models/sparsebev_transformer.py:362-374).
- * Shapes covered: sbev_sample_mix_supported(L, C, P, T, gdiv, G) != 0  (L in {4,5}, C = 64, P = 4, gdiv = G, T*P in
- * {16, 32, 48, 64}); feats / strides / loc / weights as for sbev_msmv_fwd with B' = B*T*G; frame_slots NULL = dense
+ * Shapes covered: sbev_sample_mix_supported(L, C, P, T, gdiv, G) != 0  (L in {4,5}, C = 64, P in {4,8}, gdiv = G, T*P in
+ * 4..64 or 116..120); feats / strides / loc / weights as for sbev_msmv_fwd with B' = B*T*G; frame_slots NULL = dense
  * pyramid, else the online ring (n_slots, see sbev_msmv_fwd_ring); params [B*Q, G, C*C + Pout*T*P]; y [B*Q, G, Pout, C].
  */
 int sbev_sample_mix_supported(int L, int C, int P, int T, int gdiv, int G);

@@ -89,16 +89,23 @@ def msmv_sampling_kernel_semantics(feats_cl, loc, weights):
     if -1 < h_im < H and -1 < w_im < W (:126); each bilinear corner is zero outside the map (:47-66)."""
     Bp, N, _, _, C = feats_cl[0].shape
     Q, P = loc.shape[1:3]
+    # dtype-generic: everything is evaluated in the wider of the features' and loc's dtypes, except that the three products with the
+    # coordinates are formed in loc's OWN dtype first (the CUDA kernel is an fp32 kernel: an fp32 loc with fp64 features gives the
+    # kernel's h_im / w_im / view to the bit, so a high-precision evaluation picks the kernel's taps).  One dtype throughout (every
+    # recorded fixture): all of this is a no-op.
+    dt = torch.promote_types(feats_cl[0].dtype, loc.dtype)
+    feats_cl = [f.to(dt) for f in feats_cl]
+    weights = weights.to(dt)
     x, y = loc[..., 0], loc[..., 1]
-    z = loc[..., 2] * (N - 1)
+    z = (loc[..., 2] * (N - 1)).to(dt)
     view = torch.where(z >= 0, torch.floor(z + 0.5), torch.ceil(z - 0.5)).long()   # C round(): half away from zero
     view_ix = view.clamp(0, N - 1)
     b_ix = torch.arange(Bp)[:, None, None].expand(Bp, Q, P)
-    acc = torch.zeros(Bp, Q, P, C, dtype=feats_cl[0].dtype)
+    acc = torch.zeros(Bp, Q, P, C, dtype=dt)
     for l, f in enumerate(feats_cl):
         H, W = f.shape[2:4]
-        h_im = y * (H - 1)
-        w_im = x * (W - 1)
+        h_im = (y * (H - 1)).to(dt)
+        w_im = (x * (W - 1)).to(dt)
         ok = (h_im > -1) & (w_im > -1) & (h_im < H) & (w_im < W)
         h0 = torch.floor(h_im)
         w0 = torch.floor(w_im)

@@ -260,11 +260,16 @@ def query_order(query_bbox, pc_range):
     return order
 
 
-def sample_mix(levels, B, T, G, sampling_locations, scale_weights, params, out_points, frame_slots=None, n_slots=0, order=None):
+def sample_mix(levels, B, T, G, sampling_locations, scale_weights, params, out_points, frame_slots=None, n_slots=0, order=None, up_log2=None):
     """Gather + adaptive mixing in one launch (sbev_sample_mix_f32): levels as for msmv_sampling_nhwc (or the ring's
     buffers with frame_slots / n_slots), params [B,Q,G*(C*C + out_points*T*P)] -> mixed [B,Q,G*out_points*C].
     Bit-identical to msmv_sampling_nhwc(..., OUT_MIX) followed by the mixing kernel.  order (query_order(); any permutation of
-    the B*Q rows as int32): the workgroups' launch order -- a placement hint, the result does not depend on it."""
+    the B*Q rows as int32): the workgroups' launch order -- a placement hint, the result does not depend on it.
+    up_log2 (an int; None: fp32): the same launch writing the operand format of the fp16 out-projection (sbev_sample_mix_pairs_f16,
+    with an order sbev_sample_mix_pairs_f16_ordered) -- int32 of the same geometry, each word the (fp16 hi, fp16 lo) pair of
+    y 2^up_log2 with hi in the low half: dense.f16s_pairs(sample_mix(...), up_log2) bit for bit."""
+    if up_log2 is not None and (isinstance(up_log2, bool) or not isinstance(up_log2, int)):
+        raise RuntimeError('sample_mix: up_log2 must be an int (the power of two of the pair format) or None')
     feats = list(levels)
     _need_device(sampling_locations, scale_weights, params, *feats)
     _no_grad_only(sampling_locations, scale_weights, params, *feats)
@@ -278,17 +283,24 @@ def sample_mix(levels, B, T, G, sampling_locations, scale_weights, params, out_p
     params = params.contiguous()
     if params.dtype != torch.float32 or params.numel() != B * Q * G * (C * C + out_points * T * P):
         raise RuntimeError('sample_mix: params must be fp32 [B, Q, G*(C*C + out_points*T*P)]')
-    y = torch.empty(B, Q, G * out_points * C, device=params.device, dtype=torch.float32)
+    y = torch.empty(B, Q, G * out_points * C, device=params.device, dtype=torch.float32 if up_log2 is None else torch.int32)
     levels, strides = _pyramid(feats, N, G)
     c_slots = (ctypes.c_int32 * T)(*[int(v) for v in frame_slots]) if frame_slots is not None else None
     if order is not None:
         _need_device(order)
         if order.dtype != torch.int32 or order.numel() != B * Q or not order.is_contiguous():
             raise RuntimeError('sample_mix: order must be a contiguous int32 permutation of the B*Q rows')
-    st = _lib.load().sbev_sample_mix_f32_ordered(*levels, _feat_dtype(feats), B, N, Q, T, G, P, C, *strides[1:],
-                                                 _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), c_slots, n_slots,
-                                                 _ptr(params), _ptr(y), out_points, 1e-5, _ptr(order) if order is not None else None, _stream())
-    _lib.check(st, 'sbev_sample_mix_f32')
+    loc, weights = sampling_locations.contiguous(), scale_weights.contiguous()
+    lib = _lib.load()
+    head = (*levels, _feat_dtype(feats), B, N, Q, T, G, P, C, *strides[1:], _ptr(loc), _ptr(weights), c_slots, n_slots,
+            _ptr(params), _ptr(y), out_points, 1e-5)
+    if up_log2 is None:
+        st = lib.sbev_sample_mix_f32_ordered(*head, _ptr(order), _stream())
+    elif order is None:
+        st = lib.sbev_sample_mix_pairs_f16(*head, up_log2, _stream())
+    else:
+        st = lib.sbev_sample_mix_pairs_f16_ordered(*head, up_log2, _ptr(order), _stream())
+    _lib.check(st, 'sbev_sample_mix_f32' if up_log2 is None else 'sbev_sample_mix_pairs_f16')
     return y
 
 

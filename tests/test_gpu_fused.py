@@ -38,7 +38,12 @@ def mixing(x, params, out_points=128):
                                                (1, 20, 29, 'tiny', torch.float32, 4), (2, 9, 29, 'tiny5', torch.bfloat16, 4),
                                                # round 4: fp16 feature storage
                                                (1, 100, 8, 'tiny', torch.float16, 4), (2, 37, 4, 'tiny5', torch.float16, 4),
-                                               (1, 50, 15, 'tiny5', torch.float16, 8), (1, 64, 8, 'r50_704x256', torch.float16, 4)])
+                                               (1, 50, 15, 'tiny5', torch.float16, 8), (1, 64, 8, 'r50_704x256', torch.float16, 4),
+                                               # one frame (waves 1 .. 3 of the gather have none: 4 and 8 in-points), two frames (no second frame
+                                               # round), 120 in-points from 4-point chunks, one query per sample
+                                               (2, 9, 1, 'tiny', torch.float32, 4), (1, 9, 1, 'tiny5', torch.bfloat16, 8),
+                                               (1, 9, 2, 'tiny', torch.float16, 4), (1, 6, 30, 'tiny5', torch.float16, 4),
+                                               (3, 1, 8, 'tiny', torch.float32, 4)])
 def test_fused_launch_is_bit_identical_to_sampler_then_mixing(B, Q, T, pyr, dtype, P):
     ih, iw, sizes = S.PYRAMIDS[pyr]
     L, G, C = len(sizes), 4, 64
