@@ -118,7 +118,26 @@ int sbev_msmv_fwd_ring(const void* const* feats, const int32_t* hw, int L, int f
                        const float* loc, const float* weights, float* out,
                        int out_layout, int T, int G, const int32_t* frame_slots, int n_slots, sbev_stream_t stream);
 
-/* sbev_msmv_fwd / _ring gather through raw BUFFER loads whenever every level's (sample-batch) slab is below 2 GiB: an out-of-map
+/*
+ * sbev_msmv_fwd over a KEYED FRAME POOL: the ring's resident buffers [B, n_slots, N, H_l, W_l, G*C], with the mapping (sample b, logical
+ * frame t) -> slot in DEVICE memory instead of the kernel arguments: slot_table_dev = device int32 [B, T], frame t of sample b is read
+ * from slot slot_table_dev[b*T + t] of sample b.
+ * Replaces: the file-name keyed cache of simple_test_online (models/sparsebev.py:255-321): every sample has its own row (streams at
+ *           different phases of different scenes share a batch), a frame that appears twice in a window is ONE slot read twice (so
+ *           n_slots < T is legal), and the table's ADDRESS is what a captured launch holds -- refresh its contents in place and one
+ *           hipGraph serves every step.
+ * Same arguments as sbev_msmv_fwd_ring except the table; gdiv must equal G, 1 <= T <= SBEV_MAX_FRAMES, n_slots >= 1.  The table is read
+ * by the kernel (one scalar load per wave and item): the host cannot validate it, so an entry outside [0, n_slots) is CLAMPED to the
+ * nearest end -- a bad table reads the wrong frame, never memory outside the buffers.  Results are bit-identical to sbev_msmv_fwd on a
+ * dense pyramid holding the same frames.
+ */
+int sbev_msmv_fwd_pool(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
+                       int64_t Bp, int N, int C, int Q, int P,
+                       int gdiv, const int64_t* stride_slot, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
+                       const float* loc, const float* weights, float* out,
+                       int out_layout, int T, int G, const int32_t* slot_table_dev, int n_slots, sbev_stream_t stream);
+
+/* sbev_msmv_fwd / _ring / _pool gather through raw BUFFER loads whenever every level's (sample-batch) slab is below 2 GiB: an out-of-map
  * bilinear corner is an out-of-range buffer offset, answered with zeros by the hardware and never read -- the reference's semantics
  * (msmv_sampling_forward.cu:47-66) also for Inf / NaN border pixels.  Larger slabs take 64-bit global loads + a select (same
  * results).  sbev_msmv_buffer_taps(0) forces that path (tests, A/B; env SBEV_MSMV_NO_BUF=1); returns the previous setting. */
@@ -548,6 +567,17 @@ int sbev_sample_mix_pairs_f16_ordered(const void* const* feats, const int32_t* h
                                       const float* params, void* y, int Pout, float eps, int up_log2, const int32_t* order,
                                       sbev_stream_t stream);
 int sbev_decoder_query_order(int enable);
+/* The fused launch in its general form, and the one that takes a keyed frame pool (sbev_msmv_fwd_pool): slot_table_dev = device int32
+ * [B, T] (entries clamped to [0, n_slots) by the kernel; n_slots >= 1, may be below T) -- or frame_slots as for sbev_sample_mix_f32 --
+ * or neither (dense pyramid); both together are refused.  y_pairs == 0: y fp32 (sbev_sample_mix_f32); != 0: (fp16 hi, fp16 lo) pairs of
+ * y 2^up_log2 (sbev_sample_mix_pairs_f16); order: NULL or as for the _ordered forms.  Bit-identical to those four on the same frames;
+ * the slot of a frame is requested one unit ahead, with the unit's sample points.  Messages carry the sbev_sample_mix_f32 prefix. */
+int sbev_sample_mix_pool(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
+                         int64_t B, int N, int Q, int T, int G, int P, int C,
+                         const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
+                         const float* loc, const float* weights, const int32_t* frame_slots, const int32_t* slot_table_dev, int n_slots,
+                         const float* params, void* y, int Pout, float eps, int y_pairs, int up_log2, const int32_t* order,
+                         sbev_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Training: backward passes of the decoder layer.
@@ -694,7 +724,7 @@ typedef struct sbev_decoder_config {
     int32_t hw[SBEV_MAX_LEVELS][2];     /* (H_l, W_l) */
     float image_h, image_w, eps_homo;   /* img_shape and the 1e-5 of sampling_4d */
     int32_t gemm_mode;                  /* enum sbev_gemm_mode for the two large mixing GEMMs (0 = exact fp32) */
-    int32_t n_slots;                    /* 0: feats_nhwc[l] = [B*T*N, H, W, D] (dense); > 0: online frame ring [B, n_slots, N, H, W, D] */
+    int32_t n_slots;                    /* 0: feats_nhwc[l] = [B*T*N, H, W, D] (dense); > 0: online frame ring / keyed frame pool [B, n_slots, N, H, W, D] */
     int32_t frame_slots[SBEV_MAX_FRAMES]; /* ring only: physical slot of logical frame t (see sbev_msmv_fwd_ring) */
     int32_t overlap;                    /* != 0: run the parameter-generator GEMM and the classification branch on an
                                            internal second stream (created once per process) beside the sampling chain /
@@ -702,6 +732,10 @@ typedef struct sbev_decoder_config {
                                            its events are process-wide: calls with overlap != 0 must not run concurrently
                                            from several host threads (overlap == 0, the default, has no shared state) */
     double pc_range[6];
+    const int32_t* slot_table;          /* NULL: frame_slots above (or dense).  Else the keyed frame pool (sbev_msmv_fwd_pool): DEVICE int32
+                                           [B, T], frame t of sample b is read from slot slot_table[b*T + t]; needs n_slots > 0 (may be
+                                           below T), frame_slots is ignored.  The pointer is what a captured step holds: refresh the table
+                                           in place and one capture serves every step */
 } sbev_decoder_config;
 
 /* Device pointers of the shared decoder layer's parameters (reference state-dict names in comments, prefix
@@ -869,7 +903,8 @@ int sbev_nchw_to_nhwc_lazy(const void* const* table, const int32_t* index, const
 /*
  * hipGraph capture of one decoder step: the launch sequence of sbev_decoder_forward is static per (config, pointer
  * set), so it can be recorded once on `stream` (explicit, non-default; nothing executes during the capture) and
- * replayed per sample.  The graph reads its inputs through the captured device pointers: refresh them in place.
+ * replayed per sample.  The graph reads its inputs through the captured device pointers: refresh them in place
+ * (cfg->slot_table is one of them; cfg->frame_slots is captured BY VALUE: a new ring order needs a new capture).
  * The workspace and every input / output buffer must outlive the graph.  Replaces per-call Python/launch overhead
  * of the reference's eager module chain (models/sparsebev_transformer.py:86-97).
  */

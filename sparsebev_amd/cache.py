@@ -1,4 +1,5 @@
-"""Online (streaming) per-frame feature ring -- SURVEY.md section 8f rank 2.
+"""Online (streaming) per-frame feature caches -- SURVEY.md section 8f rank 2: the positional ring (FrameFeatureCache) and the keyed
+frame pool (FramePool).
 
 The reference's published FPS is measured in online mode: features of past frames are cached per frame and only
 the 6 new images go through the backbone (models/sparsebev.py:255-321) -- but every step it still ``torch.cat``s
@@ -6,6 +7,10 @@ all T cached frames (:297-303) and the decoder then regroup-copies them again (m
 73-85).  Here each level is ONE resident channels-last buffer ``[B, n_slots, 6, H, W, C]``; a new frame is
 relayouted (NCHW -> NHWC, one launch per level) straight into the slot of the evicted frame and the sampler reads
 logical frame t through a slot table (``sbev_msmv_fwd_ring``), so nothing older than the newest frame is ever moved.
+
+The ring has ONE slot order for the whole batch, passed to the kernels by value.  The pool keeps the same buffers but finds frames by
+key, per sample, through a device table the kernels read (``sbev_msmv_fwd_pool``): what the reference's file-name keyed cache does
+(duplicates in a window, scene changes as plain misses), for a batch of independent streams, with one captured graph per shape.
 """
 import ctypes
 
@@ -14,6 +19,47 @@ import torch
 from . import _lib, ops
 
 N_VIEWS = 6
+
+
+def _store_level(f, dsts, storage):
+    """One level of a new frame into resident slots: f [n, 6, C, H, W] (sample i -> dsts[i], a contiguous [6, H, W, C] slot view of
+    ``storage`` type).  fp32 NCHW memory is relayouted by the transpose kernel; channels-last memory (what a channels_last conv stack
+    emits; fp32 / fp16 / bf16) is already in the slot's layout and only copied (and widened); a 2-byte slot takes frames of its own
+    type only, moved as bytes.  Shared by FrameFeatureCache.push and FramePool.put."""
+    lib = _lib.load()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    n = len(dsts)
+    if storage != torch.float32:                        # 2-byte ring: frames of the ring's own type only, moved as bytes
+        if f.dtype != storage:
+            raise RuntimeError('a %s ring takes %s frames only (got %s)' % (storage, storage, f.dtype))
+        if f.stride(2) == 1 and f[0].is_contiguous(memory_format=torch.channels_last):
+            for b in range(n):
+                dsts[b].copy_(f[b].permute(0, 2, 3, 1))      # both sides contiguous [6, H, W, C]: a device memcpy
+        else:
+            f = f.contiguous()
+            C, H, W = f.shape[2:]
+            for b in range(n):
+                st = lib.sbev_nchw_to_nhwc_b16(ctypes.c_void_p(f[b].data_ptr()), ctypes.c_void_p(dsts[b].data_ptr()),
+                                               N_VIEWS, C, H * W, stream)
+                _lib.check(st, 'sbev_nchw_to_nhwc_b16')
+        return
+    if f.stride(2) == 1 and f[0].is_contiguous(memory_format=torch.channels_last):      # NHWC memory: zero relayout
+        code = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}.get(f.dtype)
+        if code is None:
+            raise RuntimeError('channels-last frame features must be fp32 / fp16 / bf16')
+        for b in range(n):          # f[b] is one contiguous [6, H, W, C] run in memory; so is dsts[b]
+            st = lib.sbev_copy_widen_f32(ctypes.c_void_p(f[b].data_ptr()), code, ctypes.c_void_p(dsts[b].data_ptr()),
+                                         dsts[b].numel(), stream)
+            _lib.check(st, 'sbev_copy_widen_f32')
+        return
+    if f.dtype != torch.float32:
+        raise RuntimeError('NCHW frame features must be fp32 (channels-last inputs may be fp16 / bf16)')
+    f = f.contiguous()
+    C, H, W = f.shape[2:]
+    for b in range(n):
+        st = lib.sbev_nchw_to_nhwc_f32(ctypes.c_void_p(f[b].data_ptr()), ctypes.c_void_p(dsts[b].data_ptr()),
+                                       N_VIEWS, C, H * W, stream)
+        _lib.check(st, 'sbev_nchw_to_nhwc_f32')
 
 
 class FrameFeatureCache:
@@ -46,42 +92,10 @@ class FrameFeatureCache:
         if self.buffers is None:
             self._alloc(frame_feats)
         slot = len(self.order) if len(self.order) < self.n_slots else self.order.pop()      # free slot, else evict the oldest
-        lib = _lib.load()
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         for f, buf in zip(frame_feats, self.buffers):
             if not f.is_cuda or f.shape[0] != self.B or f.shape[1] != N_VIEWS:
                 raise RuntimeError('frame features must be device tensors [B, 6, C, H, W]')
-            if self.dtype != torch.float32:                     # 2-byte ring: frames of the ring's own type only, moved as bytes
-                if f.dtype != self.dtype:
-                    raise RuntimeError('a %s ring takes %s frames only (got %s)' % (self.dtype, self.dtype, f.dtype))
-                if f.stride(2) == 1 and f[0].is_contiguous(memory_format=torch.channels_last):
-                    for b in range(self.B):
-                        buf[b, slot].copy_(f[b].permute(0, 2, 3, 1))      # both sides contiguous [6, H, W, C]: a device memcpy
-                else:
-                    f = f.contiguous()
-                    C, H, W = f.shape[2:]
-                    for b in range(self.B):
-                        st = lib.sbev_nchw_to_nhwc_b16(ctypes.c_void_p(f[b].data_ptr()), ctypes.c_void_p(buf[b, slot].data_ptr()),
-                                                       N_VIEWS, C, H * W, stream)
-                        _lib.check(st, 'sbev_nchw_to_nhwc_b16')
-                continue
-            if f.stride(2) == 1 and f[0].is_contiguous(memory_format=torch.channels_last):      # NHWC memory: zero relayout
-                code = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}.get(f.dtype)
-                if code is None:
-                    raise RuntimeError('channels-last frame features must be fp32 / fp16 / bf16')
-                for b in range(self.B):          # f[b] is one contiguous [6, H, W, C] run in memory; so is buf[b, slot]
-                    st = lib.sbev_copy_widen_f32(ctypes.c_void_p(f[b].data_ptr()), code, ctypes.c_void_p(buf[b, slot].data_ptr()),
-                                                 buf[b, slot].numel(), stream)
-                    _lib.check(st, 'sbev_copy_widen_f32')
-                continue
-            if f.dtype != torch.float32:
-                raise RuntimeError('NCHW frame features must be fp32 (channels-last inputs may be fp16 / bf16)')
-            f = f.contiguous()
-            C, H, W = f.shape[2:]
-            for b in range(self.B):
-                st = lib.sbev_nchw_to_nhwc_f32(ctypes.c_void_p(f[b].data_ptr()), ctypes.c_void_p(buf[b, slot].data_ptr()),
-                                               N_VIEWS, C, H * W, stream)
-                _lib.check(st, 'sbev_nchw_to_nhwc_f32')
+            _store_level(f, [buf[b, slot] for b in range(self.B)], self.dtype)
         self.order.insert(0, slot)
         del self.order[self.n_slots:]
 
@@ -103,3 +117,156 @@ class RingPyramid:
 
     def sample(self, loc, w_bp, T, G):
         return ops.msmv_sampling_ring(self.levels, self.B, T, G, self.frame_slots, self.n_slots, loc, w_bp)
+
+
+class SlotBook:
+    """The keyed frame pool's bookkeeping, host only (no torch, no device): per sample a map key -> slot in least-recently-used order,
+    the keys the current step needs, and the step's table (b, t) -> slot as a plain list of lists.  The counterpart of the reference's
+    file-name keyed cache (models/sparsebev.py:255-321), per sample instead of per process."""
+
+    def __init__(self, num_frames, n_slots):
+        if not 1 <= num_frames <= 16 or not 1 <= n_slots <= 16:
+            raise ValueError('need 1 <= num_frames <= 16 and 1 <= n_slots <= 16 (the reference evicts its cache at 16 frames)')
+        self.T, self.n_slots = num_frames, n_slots
+        self.B = None
+        self.slots = {}                # b -> {key: slot}, insertion order = least recently used first
+        self.needed = {}               # b -> the distinct keys of the step last announced (missing / table)
+
+    def _announce(self, keys):
+        """keys[b][t] of one step -> per sample its distinct keys in window order; validates the shape and what fits"""
+        keys = [list(row) for row in keys]
+        if not keys or any(len(row) != self.T for row in keys):
+            raise ValueError('keys must be [B][T] with T = %d' % self.T)
+        if self.B is None:
+            self.B = len(keys)
+        if len(keys) != self.B:
+            raise ValueError('this pool serves B = %d samples, got keys for %d' % (self.B, len(keys)))
+        for b, row in enumerate(keys):
+            distinct = list(dict.fromkeys(row))
+            if len(distinct) > self.n_slots:
+                raise RuntimeError('sample %d needs %d distinct frames in one step, the pool has %d slots' % (b, len(distinct), self.n_slots))
+            self.needed[b] = distinct
+        return keys
+
+    def missing(self, keys):
+        """The distinct (b, key) pairs of this step that are not resident, in (b, t) order: what the caller has to put()."""
+        self._announce(keys)
+        return [(b, k) for b in range(self.B) for k in self.needed[b] if k not in self.slots.get(b, {})]
+
+    def assign(self, b, key):
+        """(slot, evicted key or None) for ``key`` of sample b: its own slot if resident, else a free one, else the least recently used
+        one whose key the announced step does not need."""
+        if self.B is None or not 0 <= b < self.B:
+            raise ValueError('sample index %r outside the pool (announce the step with missing(keys) first)' % (b,))
+        mine = self.slots.setdefault(b, {})
+        if key in mine:
+            slot = mine.pop(key)
+            mine[key] = slot           # most recently used last
+            return slot, None
+        evicted = None
+        if len(mine) < self.n_slots:
+            slot = next(s for s in range(self.n_slots) if s not in set(mine.values()))
+        else:
+            need = set(self.needed.get(b, ()))
+            evicted = next((k for k in mine if k not in need), None)
+            if evicted is None:
+                raise RuntimeError('sample %d: every one of the %d slots holds a frame this step needs' % (b, self.n_slots))
+            slot = mine.pop(evicted)
+        mine[key] = slot
+        return slot, evicted
+
+    def table(self, keys):
+        """[B][T] slots of this step (every key must be resident); marks them most recently used, the window's newest frame last."""
+        keys = self._announce(keys)
+        rows = []
+        for b, row in enumerate(keys):
+            mine = self.slots.get(b, {})
+            absent = [k for k in self.needed[b] if k not in mine]
+            if absent:
+                raise KeyError('sample %d: frame %r is not in the pool (missing(keys) lists what to put() first)' % (b, absent[0]))
+            for k in reversed(self.needed[b]):
+                mine[k] = mine.pop(k)
+            rows.append([mine[k] for k in row])
+            assert all(0 <= s < self.n_slots for s in rows[-1])
+        return rows
+
+    def drop(self, b):
+        """Forget sample b's stream (its slots are free again)."""
+        self.slots.pop(b, None)
+        self.needed.pop(b, None)
+
+
+class FramePool:
+    """Keyed frame pool: the ring's resident buffers ``[B, n_slots, 6, H, W, C]`` per level, addressed by KEY per sample instead of by
+    ring position for the whole batch.  Per step: ``missing(keys)`` -> ``put(b, key, feats)`` for each pair -> ``pyramid(keys)``.  The
+    step's mapping (b, t) -> slot lives in ONE persistent device int32 table ``[B, T]`` that the sampler kernels read
+    (``sbev_msmv_fwd_pool``); ``pyramid`` refreshes its contents in place, so a captured decoder step replays for every phase, scene
+    change and mix of streams.  A frame that appears twice in a window is one slot read twice; eviction is per sample, least recently
+    used, never a frame the announced step needs.  ``dtype``: the slots' storage type, as for FrameFeatureCache."""
+
+    def __init__(self, num_frames, n_slots=16, dtype=torch.float32):
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError('pool storage must be fp32, fp16 or bf16')
+        self.dtype = dtype
+        self.book = SlotBook(num_frames, n_slots)
+        self.T, self.n_slots = num_frames, n_slots
+        self.buffers = None            # list[L] of [B, n_slots, 6, H, W, C]
+        self.slot_table = None         # device int32 [B, T]: allocated once with the buffers, refreshed in place per pyramid()
+
+    @property
+    def B(self):
+        return self.book.B
+
+    def missing(self, keys):
+        """keys[b][t]: hashable frame keys, t = 0 newest -> the distinct (b, key) pairs that are not resident."""
+        return self.book.missing(keys)
+
+    def put(self, b, key, frame_feats):
+        """One sample's frame into a slot of sample b.  frame_feats: list[L] of [6, C, H_l, W_l] device tensors, NCHW or channels-last
+        (dtype rules of FrameFeatureCache.push)."""
+        feats = list(frame_feats)
+        for f in feats:
+            if not (torch.is_tensor(f) and f.is_cuda and f.dim() == 4 and f.shape[0] == N_VIEWS):
+                raise RuntimeError('frame features must be device tensors [6, C, H, W]')
+        if self.buffers is None:
+            if self.book.B is None:
+                raise RuntimeError('announce the step with missing(keys) before the first put(): the batch size is taken from it')
+            self.buffers = [torch.empty(self.book.B, self.n_slots, N_VIEWS, f.shape[2], f.shape[3], f.shape[1], device=f.device, dtype=self.dtype)
+                            for f in feats]
+            self.slot_table = torch.zeros(self.book.B, self.T, device=feats[0].device, dtype=torch.int32)
+        if len(feats) != len(self.buffers) or any(tuple(buf.shape[3:]) != (f.shape[2], f.shape[3], f.shape[1]) for f, buf in zip(feats, self.buffers)):
+            raise RuntimeError('frame features do not match the pool\'s levels')
+        slot, _ = self.book.assign(b, key)
+        for f, buf in zip(feats, self.buffers):
+            _store_level(f[None], [buf[b, slot]], self.dtype)
+        return slot
+
+    def pyramid(self, keys):
+        """The step's view for the decoder (drop-in for transformer.FeaturePyramid): uploads the step's table into the persistent
+        device table through the pinned upload ring (asynchronous, no allocation) and returns a PoolPyramid over it."""
+        import numpy as np
+        from .transformer import _upload
+        rows = self.book.table(keys)
+        if self.buffers is None:
+            raise RuntimeError('the pool is empty')
+        _upload(np.asarray(rows, dtype=np.int32), self.slot_table.device, out=self.slot_table)
+        return PoolPyramid(self)
+
+    def drop(self, b):
+        """Forget sample b's stream: its next keys are all misses."""
+        self.book.drop(b)
+
+
+class PoolPyramid:
+    """(no ``frame_slots`` attribute: that marks the by-value ring; the pool is recognised by ``slot_table``)"""
+
+    def __init__(self, pool):
+        self.B, self.T = pool.B, pool.T
+        self.n_slots = pool.n_slots
+        self.slot_table = pool.slot_table
+        self.levels = [b.reshape(pool.B * pool.n_slots * N_VIEWS, b.shape[3], b.shape[4], b.shape[5]) for b in pool.buffers]
+        self.GC = pool.buffers[0].shape[-1]
+        self.copied = 0
+
+    def sample(self, loc, w_bp, T, G):
+        return ops.msmv_sampling_pool(self.levels, self.B, T, G, self.slot_table, self.n_slots, loc, w_bp)

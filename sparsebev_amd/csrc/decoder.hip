@@ -122,6 +122,8 @@ int validate(const sbev_decoder_config* c) {
     SBEV_REQUIRE(c->code_size == 10, "sbev_decoder: code_size %d (the box kernels are built for the 10-wide box code)", c->code_size);
     SBEV_REQUIRE(c->num_layers >= 1 && c->num_classes >= 1 && c->ffn % 4 == 0, "sbev_decoder: head sizes");
     SBEV_REQUIRE(c->gemm_mode >= SBEV_GEMM_F32 && c->gemm_mode <= SBEV_GEMM_F16X4, "sbev_decoder: gemm_mode %d", c->gemm_mode);
+    SBEV_REQUIRE(!c->slot_table || (c->n_slots > 0 && c->T <= SBEV_MAX_FRAMES), "sbev_decoder: slot_table (keyed frame pool) needs n_slots > 0 and T <= %d",
+                 SBEV_MAX_FRAMES);
     return SBEV_OK;
 }
 
@@ -150,14 +152,15 @@ inline int hip_ok(hipError_t e, const char* what) {
     return SBEV_ELAUNCH;
 }
 
-// The config's feature pyramid as the samplers' description: zero-copy NHWC levels [B*T*N, H, W, D] (or the ring's [B*n_slots*N, ...]),
+// The config's feature pyramid as the samplers' description: zero-copy NHWC levels [B*T*N, H, W, D] (or the ring's / the keyed frame
+// pool's [B*n_slots*N, ...]: slots by value from c.frame_slots, or read by the kernels from the device table c.slot_table),
 // group g = channel slice [g*Cg, (g+1)*Cg); sample points loc / weights of all B*T*G sample batches
 struct ConfigPyramid {
     int64_t sbo[SBEV_MAX_LEVELS], sv[SBEV_MAX_LEVELS];
     sbev::PyramidDesc d;
     ConfigPyramid(const sbev_decoder_config& c, const void* const* feats, const float* loc, const float* weights)
         : d{feats, &c.hw[0][0], c.L, c.feat_dtype, c.N, c.D / c.G, c.Q, c.P, c.G, sbo, c.D / c.G, sv, c.D, loc, weights,
-            c.n_slots > 0 ? c.frame_slots : nullptr, c.n_slots} {
+            c.n_slots > 0 && !c.slot_table ? c.frame_slots : nullptr, c.n_slots, c.slot_table} {
         for (int l = 0; l < c.L; ++l) {
             sv[l] = (int64_t)c.hw[l][0] * c.hw[l][1] * c.D;
             sbo[l] = sv[l] * c.N;
@@ -707,8 +710,10 @@ extern "C" int sbev_profile_sampler_read(float* ms, int max_n) { return sbev_pro
 
 // ---- hipGraph capture of one decoder step -----------------------------------------------------------------------
 // The launch sequence is static per (config, pointers): capture it once, replay it per sample.  Inputs are read
-// through the captured device pointers, so the caller refreshes them in place (new queries / matrices / features,
-// or -- with the frame ring -- a new slot table means a new capture per ring phase).
+// through the captured device pointers, so the caller refreshes them in place (new queries / matrices / features).  The frame ring's
+// slot order (cfg->frame_slots) is a by-value kernel argument: a new order is a new capture, one per ring phase.  The keyed frame
+// pool's table (cfg->slot_table) is device memory behind a captured pointer: refreshed in place like every other input, ONE capture
+// serves every phase, scene change and mix of streams.
 struct sbev_graph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;

@@ -141,7 +141,10 @@ constexpr int mix_min_waves() { return L > 0 ? SBEV_SAMPLE_MIX_WAVES : 1; }   //
 
 // PAD: Pin % 16 != 0 on the WIDE path (round 3; the last row tile of x and the last k block of S are partly padding) and, fused,
 // 4 or 8 points per frame -- a template parameter so that the Pin % 16 == 0, P = 4 instantiations stay exactly the tuned code of rounds 1-2
-template <int RT, bool WIDE, int L = 0, typename FT = float, bool PAD = false>
+// POOL (fused only): the frames' slots come from the keyed frame pool's device table (MsmvArgs::slot_tab) -- a template parameter that the
+// dense and by-value-ring instantiations do not take: read inside them, the table cost the 5-level ones 2 SGPRs past the 106 they
+// have (spills, a wave of occupancy at RT = 4), so they stay the code they were
+template <int RT, bool WIDE, int L = 0, typename FT = float, bool PAD = false, bool POOL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mix_min_waves<L, RT>()))) void adaptive_mixing_kernel(const typename MixArgsOf<L>::type a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int Pin = a.Pin;
@@ -273,15 +276,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mix_min_wav
                 if (lane >= 16 && lane < 16 + 4 * L) v = m.w[(it * Pq + h * 4) * L + (lane - 16)];
                 return v;
             };
+            // keyed frame pool (m.slot_tab, device [B, T]): a unit's slot is requested with its loc / weights, one unit ahead -- a scalar
+            // load (b, u: wave-uniform) whose round trip is over by the time the unit's buffer resources are built from it
+            auto fetch_slot = [&](int u) { return POOL ? m.slot_tab[b * (unsigned)T + (unsigned)(u >> pcs)] : 0; };
             float lv_next = wave < NU ? fetch_lv(wave) : 0.f;
+            [[maybe_unused]] int slot_next = POOL && wave < NU ? fetch_slot(wave) : 0;
 #pragma unroll 1
             for (int u = wave; u < NU; u += 4) {
                 if (u == 4) { MIX_STAMP(10) }                  // wave 0's second unit starts (its loc / weights were requested a unit ago)
                 const int t = u >> pcs;
                 const float lv = lv_next;
-                if (u + 4 < NU) lv_next = fetch_lv(u + 4);
+                [[maybe_unused]] const int slot = slot_next;
+                if (u + 4 < NU) {
+                    lv_next = fetch_lv(u + 4);
+                    if constexpr (POOL) slot_next = fetch_slot(u + 4);
+                }
                 unsigned ubo = b * (unsigned)T + (unsigned)t;
-                if (m.ring_T) ubo = b * (unsigned)m.n_slots + (unsigned)m.slots[t];
+                if constexpr (POOL) ubo = b * (unsigned)m.n_slots + msmv_pool_slot(slot, m.n_slots);
+                else if (m.ring_T) ubo = b * (unsigned)m.n_slots + (unsigned)m.slots[t];
                 long long slab[L];
 #pragma unroll
                 for (int l = 0; l < L; ++l) slab[l] = (long long)ubo * m.stride_bo[l] + (long long)g * m.stride_g;     // wave-uniform
@@ -525,7 +537,7 @@ int launch_mix(const MixArgs& a, hipStream_t s) {
     return a.Pin % 16 == 0 || !generic ? launch_mix_w<RT, true>(a, s) : launch_mix_w<RT, false>(a, s);
 }
 
-template <int RT, int L, typename FT>
+template <int RT, int L, typename FT, bool POOL>
 int launch_sample_mix(const SampleMixArgs& a, hipStream_t s) {
     const int Pin = a.Pin;
     // S, then the gathered x behind it; Pin > 64: S in two k halves of 64 + 4 columns, the gathered x ON that buffer (Pin <= 128 rows fit)
@@ -537,9 +549,9 @@ int launch_sample_mix(const SampleMixArgs& a, hipStream_t s) {
     static const int exp_pad = getenv("SBEV_EXP_MIX_PAD") ? atoi(getenv("SBEV_EXP_MIX_PAD")) : 0;
     bytes += (size_t)exp_pad;
 #endif
-    auto k = adaptive_mixing_kernel<RT, true, L, FT, true>;
+    auto k = adaptive_mixing_kernel<RT, true, L, FT, true, POOL>;
     if constexpr (RT <= 4) {
-        if (a.Pin % 16 == 0 && a.s.P == 4) k = adaptive_mixing_kernel<RT, true, L, FT>;      // the tuned instantiation (4 points per frame, whole row tiles)
+        if (a.Pin % 16 == 0 && a.s.P == 4) k = adaptive_mixing_kernel<RT, true, L, FT, false, POOL>;      // the tuned instantiation (4 points per frame, whole row tiles)
     }
     hipEvent_t e0, e1;
     const bool prof = sbev::profile_begin(s, &e0, &e1, 3);
@@ -548,15 +560,19 @@ int launch_sample_mix(const SampleMixArgs& a, hipStream_t s) {
     return sbev::check_launch("sbev_sample_mix_f32");
 }
 
+template <int L, typename FT, bool POOL>
+int launch_sample_mix_p(const SampleMixArgs& a, hipStream_t s) {
+    switch ((a.Pin + 15) / 16) {
+        case 1: return launch_sample_mix<1, L, FT, POOL>(a, s);
+        case 2: return launch_sample_mix<2, L, FT, POOL>(a, s);
+        case 3: return launch_sample_mix<3, L, FT, POOL>(a, s);
+        case 4: return launch_sample_mix<4, L, FT, POOL>(a, s);
+        default: return launch_sample_mix<8, L, FT, POOL>(a, s);
+    }
+}
 template <int L, typename FT>
 int launch_sample_mix_rt(const SampleMixArgs& a, hipStream_t s) {
-    switch ((a.Pin + 15) / 16) {
-        case 1: return launch_sample_mix<1, L, FT>(a, s);
-        case 2: return launch_sample_mix<2, L, FT>(a, s);
-        case 3: return launch_sample_mix<3, L, FT>(a, s);
-        case 4: return launch_sample_mix<4, L, FT>(a, s);
-        default: return launch_sample_mix<8, L, FT>(a, s);
-    }
+    return a.s.slot_tab ? launch_sample_mix_p<L, FT, true>(a, s) : launch_sample_mix_p<L, FT, false>(a, s);
 }
 
 }  // namespace
@@ -621,7 +637,7 @@ extern "C" int sbev_sample_mix_slabs_ok(const int32_t* hw, int L, int feat_dtype
     return 1;
 }
 
-// the implementation behind the four sbev_sample_mix_* entry points (d.C channels per group, d.gdiv == G), also called by the decoder step
+// the implementation behind the sbev_sample_mix_* entry points (d.C channels per group, d.gdiv == G), also called by the decoder step
 int sbev::sample_mix(const sbev::PyramidDesc& d, int64_t B, int T, int G, const float* params, float* y, int Pout, float eps, float out_up,
                      const int32_t* order, sbev_stream_t stream) {
     const char* who = "sbev_sample_mix_f32";
@@ -695,4 +711,19 @@ extern "C" int sbev_sample_mix_pairs_f16_ordered(const void* const* feats, const
     SBEV_REQUIRE(up_log2 >= -100 && up_log2 <= 100, "sbev_sample_mix_pairs_f16: up_log2=%d", up_log2);
     return sbev::sample_mix({feats, hw, L, feat_dtype, N, Cg, Q, P, G, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots},
                             B, T, G, params, static_cast<float*>(y), Pout, eps, ldexpf(1.f, up_log2), order, stream);
+}
+
+// The general form of the four entry points above, and the one that takes a keyed frame pool: slot_table_dev (device int32 [B, T]) instead
+// of the host frame_slots -- at most one of the two (neither: the dense pyramid).  y_pairs != 0: y as (fp16 hi, fp16 lo) pairs of
+// y 2^up_log2; order may be null
+extern "C" int sbev_sample_mix_pool(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
+                                    int64_t B, int N, int Q, int T, int G, int P, int Cg,
+                                    const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
+                                    const float* loc, const float* weights, const int32_t* frame_slots, const int32_t* slot_table_dev,
+                                    int n_slots, const float* params, void* y, int Pout, float eps, int y_pairs, int up_log2,
+                                    const int32_t* order, sbev_stream_t stream) {
+    SBEV_REQUIRE(!y_pairs || (up_log2 >= -100 && up_log2 <= 100), "sbev_sample_mix_pool: up_log2=%d", up_log2);
+    return sbev::sample_mix({feats, hw, L, feat_dtype, N, Cg, Q, P, G, stride_bo, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots,
+                             slot_table_dev},
+                            B, T, G, params, static_cast<float*>(y), Pout, eps, y_pairs ? ldexpf(1.f, up_log2) : 0.f, order, stream);
 }

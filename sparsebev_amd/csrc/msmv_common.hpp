@@ -19,7 +19,17 @@ struct MsmvArgs {
     // online frame ring (sbev_msmv_fwd_ring): logical frame t of a sample lives in physical slot slots[t] of n_slots
     int ring_T, n_slots;
     int slots[SBEV_MAX_FRAMES];
+    // keyed frame pool (sbev_msmv_fwd_pool): device table [B, ring_T], frame t of sample b lives in slot slot_tab[b * ring_T + t];
+    // null: slots[] above.  Its ADDRESS is the kernel argument, so a captured launch follows the table's contents
+    const int* slot_tab;
 };
+
+// a pool table entry -> a slot that exists: the host validates the tables it builds, a C caller owns its own, and a bad entry must read
+// the wrong MAPPED slot, never an unmapped address (negative values become large and clamp to the last slot).  Wave-uniform: the entry
+// is a scalar load; the readfirstlane says so where the compiler cannot see it (the buffer resource built from it needs no waterfall loop)
+__device__ __forceinline__ unsigned msmv_pool_slot(int entry, int n_slots) {
+    return min((unsigned)__builtin_amdgcn_readfirstlane(entry), (unsigned)n_slots - 1u);
+}
 
 typedef float msmv_f2 __attribute__((ext_vector_type(2)));      // a channel pair: the operand type of the packed fmas in msmv_chunk.inc
 
@@ -95,9 +105,20 @@ inline bool msmv_slab_fits_buffer(const sbev::PyramidDesc& d, int l) {
     const long long last = d.slab_span(l) + (d.C > 64 ? d.C : 64) + 4;
     return last * (d.feat_dtype == SBEV_F32 ? 4 : 2) < (long long)MSMV_BUF_RECORDS;
 }
-// host: the ring's slot table -> a.slots (no ring: nothing).  B' = B*T*G sample batches, `who`: the entry point, for its messages
+// host: the ring's slot table -> a.slots, or the pool's device table -> a.slot_tab (neither: nothing; both: refused).  B' = B*T*G sample
+// batches, `who`: the entry point, for its messages.  The pool has no n_slots >= T rule: two frames of a window may be one cached entry
 inline int msmv_fill_ring(MsmvArgs& a, const sbev::PyramidDesc& d, int64_t Bp, int T, int G, const char* who) {
-    if (!d.frame_slots) return SBEV_OK;
+    if (!d.frame_slots && !d.slot_table) return SBEV_OK;
+    SBEV_REQUIRE(!(d.frame_slots && d.slot_table), "%s: give frame_slots (host, by value) or slot_table (device), not both", who);
+    if (d.slot_table) {
+        SBEV_REQUIRE(T >= 1 && T <= SBEV_MAX_FRAMES && d.n_slots >= 1 && d.gdiv == G && Bp % ((int64_t)T * G) == 0,
+                     "%s: need 1 <= T <= %d, n_slots >= 1, gdiv == G, B' = B*T*G", who, SBEV_MAX_FRAMES);
+        SBEV_REQUIRE((((uintptr_t)d.slot_table) & 3) == 0, "%s: slot_table must be 4-byte aligned", who);
+        a.ring_T = T;
+        a.n_slots = d.n_slots;
+        a.slot_tab = d.slot_table;
+        return SBEV_OK;
+    }
     SBEV_REQUIRE(T >= 1 && T <= SBEV_MAX_FRAMES && d.n_slots >= T && d.gdiv == G && Bp % ((int64_t)T * G) == 0,
                  "%s: need 1 <= T <= %d, n_slots >= T, gdiv == G, B' = B*T*G", who, SBEV_MAX_FRAMES);
     a.ring_T = T;

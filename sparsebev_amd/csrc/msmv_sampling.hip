@@ -27,7 +27,9 @@ namespace {
 
 #include "msmv_common.hpp"
 
-template <int L, typename FT, int OUT, int QPW, bool BUF>
+// POOL: the slot of (b, t) comes from the keyed frame pool's device table (a.slot_tab) -- a template parameter the dense and by-value-ring
+// instantiations do not take (they stay the code they were: the table's pointer costs them up to 6 SGPRs, spills at 5 levels)
+template <int L, typename FT, int OUT, int QPW, bool BUF, bool POOL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(msmv_min_waves<L, FT>()))) void msmv_fwd_kernel(const MsmvArgs a) {
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -53,7 +55,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(msmv_min_wa
     const long long gi = bp - ubo * (unsigned)a.gdiv;
     if (a.ring_T) {                                          // (b, t) -> (b, slot[t]) in the per-frame feature ring
         const unsigned b = ubo / (unsigned)a.ring_T;
-        ubo = b * (unsigned)a.n_slots + (unsigned)a.slots[(int)(ubo - b * (unsigned)a.ring_T)];
+        // the pool's device table is [B, ring_T]: entry b * ring_T + t is entry ubo (wave-uniform: one scalar load per item)
+        if constexpr (POOL) ubo = b * (unsigned)a.n_slots + msmv_pool_slot(a.slot_tab[ubo], a.n_slots);
+        else ubo = b * (unsigned)a.n_slots + (unsigned)a.slots[(int)(ubo - b * (unsigned)a.ring_T)];
     }
     const long long bo = ubo;
     const int P = a.P, C = a.C;
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(msmv_min_wa
     }   // item loop
 }
 
-template <int L, typename FT, bool BUF>
+template <int L, typename FT, bool BUF, bool POOL>
 int launch_l(const MsmvArgs& a, int out_layout, hipStream_t s) {
     // pipelined items per wave when a query is a single chunk and there are enough items to keep every SIMD fed
     const bool pipe = a.P <= 4 && a.C <= 64 && a.n_waves >= 4LL * 1024 * SBEV_MSMV_QPW;
@@ -143,24 +147,24 @@ int launch_l(const MsmvArgs& a, int out_layout, hipStream_t s) {
     hipEvent_t e0, e1;
     const bool prof = sbev::profile_begin(s, &e0, &e1);
     if (out_layout == SBEV_OUT_REF) {
-        if (pipe) hipLaunchKernelGGL((msmv_fwd_kernel<L, FT, SBEV_OUT_REF, SBEV_MSMV_QPW, BUF>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((msmv_fwd_kernel<L, FT, SBEV_OUT_REF, 1, BUF>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        if (pipe) hipLaunchKernelGGL((msmv_fwd_kernel<L, FT, SBEV_OUT_REF, SBEV_MSMV_QPW, BUF, POOL>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((msmv_fwd_kernel<L, FT, SBEV_OUT_REF, 1, BUF, POOL>), dim3((unsigned)blocks), dim3(256), 0, s, a);
     } else {
-        if (pipe) hipLaunchKernelGGL((msmv_fwd_kernel<L, FT, SBEV_OUT_MIX, SBEV_MSMV_QPW, BUF>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((msmv_fwd_kernel<L, FT, SBEV_OUT_MIX, 1, BUF>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        if (pipe) hipLaunchKernelGGL((msmv_fwd_kernel<L, FT, SBEV_OUT_MIX, SBEV_MSMV_QPW, BUF, POOL>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((msmv_fwd_kernel<L, FT, SBEV_OUT_MIX, 1, BUF, POOL>), dim3((unsigned)blocks), dim3(256), 0, s, a);
     }
     if (prof) sbev::profile_end(s, e0, e1);
     return sbev::check_launch("sbev_msmv_fwd");
 }
 
-template <typename FT, bool BUF>
+template <typename FT, bool BUF, bool POOL>
 int launch_b(const MsmvArgs& a, int L, int out_layout, hipStream_t s) {
     switch (L) {
-        case 1: return launch_l<1, FT, BUF>(a, out_layout, s);
-        case 2: return launch_l<2, FT, BUF>(a, out_layout, s);
-        case 3: return launch_l<3, FT, BUF>(a, out_layout, s);
-        case 4: return launch_l<4, FT, BUF>(a, out_layout, s);
-        default: return launch_l<5, FT, BUF>(a, out_layout, s);
+        case 1: return launch_l<1, FT, BUF, POOL>(a, out_layout, s);
+        case 2: return launch_l<2, FT, BUF, POOL>(a, out_layout, s);
+        case 3: return launch_l<3, FT, BUF, POOL>(a, out_layout, s);
+        case 4: return launch_l<4, FT, BUF, POOL>(a, out_layout, s);
+        default: return launch_l<5, FT, BUF, POOL>(a, out_layout, s);
     }
 }
 // buffer-load taps (hardware zeros for an out-of-map corner) when every slab of every level is below 2 GiB;
@@ -168,13 +172,15 @@ int launch_b(const MsmvArgs& a, int L, int out_layout, hipStream_t s) {
 std::atomic<int> g_buffer_taps{getenv("SBEV_MSMV_NO_BUF") ? 0 : 1};
 template <typename FT>
 int launch_t(const MsmvArgs& a, int L, int out_layout, bool slabs_fit_buffer, hipStream_t s) {
-    return slabs_fit_buffer && g_buffer_taps.load(std::memory_order_relaxed) != 0 ? launch_b<FT, true>(a, L, out_layout, s)
-                                                                                   : launch_b<FT, false>(a, L, out_layout, s);
+    const bool buf = slabs_fit_buffer && g_buffer_taps.load(std::memory_order_relaxed) != 0;
+    if (a.slot_tab) return buf ? launch_b<FT, true, true>(a, L, out_layout, s) : launch_b<FT, false, true>(a, L, out_layout, s);
+    return buf ? launch_b<FT, true, false>(a, L, out_layout, s) : launch_b<FT, false, false>(a, L, out_layout, s);
 }
 
 }  // namespace
 
-// the implementation behind sbev_msmv_fwd and sbev_msmv_fwd_ring (d.frame_slots), also called by the decoder step
+// the implementation behind sbev_msmv_fwd, sbev_msmv_fwd_ring (d.frame_slots) and sbev_msmv_fwd_pool (d.slot_table), also called by the
+// decoder step
 int sbev::msmv_fwd(const sbev::PyramidDesc& d, int64_t Bp, float* out, int out_layout, int T, int G, sbev_stream_t stream) {
     const char* who = "sbev_msmv_fwd";
     if (int st = sbev::check_pyramid(d, who)) return st;
@@ -203,7 +209,7 @@ int sbev::msmv_fwd(const sbev::PyramidDesc& d, int64_t Bp, float* out, int out_l
     a.out = out;
     a.n_waves = Bp * d.Q;
     a.T = T; a.G = G;
-    if (int st = msmv_fill_ring(a, d, Bp, T, G, "sbev_msmv_fwd_ring")) return st;
+    if (int st = msmv_fill_ring(a, d, Bp, T, G, d.slot_table ? "sbev_msmv_fwd_pool" : "sbev_msmv_fwd_ring")) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return d.feat_dtype == SBEV_F32 ? launch_t<float>(a, d.L, out_layout, fit, s)
            : d.feat_dtype == SBEV_F16 ? launch_t<_Float16>(a, d.L, out_layout, fit, s)
@@ -234,5 +240,17 @@ extern "C" int sbev_msmv_fwd_ring(const void* const* feats, const int32_t* hw, i
                                   sbev_stream_t stream) {
     SBEV_REQUIRE(frame_slots != nullptr, "sbev_msmv_fwd_ring: frame_slots is null");
     return sbev::msmv_fwd({feats, hw, L, feat_dtype, N, C, Q, P, gdiv, stride_slot, stride_g, stride_v, stride_px, loc, weights, frame_slots, n_slots},
+                          Bp, out, out_layout, T, G, stream);
+}
+
+extern "C" int sbev_msmv_fwd_pool(const void* const* feats, const int32_t* hw, int L, int feat_dtype,
+                                  int64_t Bp, int N, int C, int Q, int P,
+                                  int gdiv, const int64_t* stride_slot, int64_t stride_g, const int64_t* stride_v,
+                                  int64_t stride_px, const float* loc, const float* weights, float* out,
+                                  int out_layout, int T, int G, const int32_t* slot_table_dev, int n_slots,
+                                  sbev_stream_t stream) {
+    SBEV_REQUIRE(slot_table_dev != nullptr, "sbev_msmv_fwd_pool: slot_table is null");
+    return sbev::msmv_fwd({feats, hw, L, feat_dtype, N, C, Q, P, gdiv, stride_slot, stride_g, stride_v, stride_px, loc, weights, nullptr, n_slots,
+                           slot_table_dev},
                           Bp, out, out_layout, T, G, stream);
 }

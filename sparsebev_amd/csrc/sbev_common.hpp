@@ -68,6 +68,8 @@ struct PyramidDesc {
     const float *loc, *weights;
     const int32_t* frame_slots;     // online frame ring (null: none): logical frame t lives in slot frame_slots[t] of n_slots
     int n_slots;
+    const int32_t* slot_table;      // keyed frame pool (null: none): DEVICE int32 [B, T], frame t of sample b lives in slot slot_table[b*T + t]
+                                    // of n_slots; at most one of frame_slots / slot_table
 
     // elements from the base of one (sample-batch) slab of level l to the last pixel of its last view; a limit adds its own tail
     int64_t slab_span(int l) const { return (int64_t)(N - 1) * stride_v[l] + ((int64_t)hw[2 * l] * hw[2 * l + 1] - 1) * stride_px; }
@@ -102,7 +104,7 @@ inline void fill_pyramid(Args& a, const PyramidDesc& d) {
     a.loc = d.loc; a.w = d.weights;
     a.N = d.N; a.C = d.C; a.Q = d.Q; a.P = d.P; a.gdiv = d.gdiv;
 }
-// msmv_sampling.hip / mixing.hip: the implementations behind sbev_msmv_fwd[_ring] (B' sample batches) and the four sbev_sample_mix_*
+// msmv_sampling.hip / mixing.hip: the implementations behind sbev_msmv_fwd[_ring / _pool] (B' sample batches) and the sbev_sample_mix_*
 // (B samples; out_up 0: y is fp32, 2^e: fp16 pairs; order may be null), for callers that hold a description (decoder.hip)
 int msmv_fwd(const PyramidDesc& d, int64_t Bp, float* out, int out_layout, int T, int G, sbev_stream_t stream);
 int sample_mix(const PyramidDesc& d, int64_t B, int T, int G, const float* params, float* y, int Pout, float eps, float out_up,

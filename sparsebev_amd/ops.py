@@ -242,6 +242,44 @@ def msmv_sampling_ring(levels, B, T, G, frame_slots, n_slots, sampling_locations
     return out
 
 
+def _check_slot_table(slot_table, B, T, n_slots, what):
+    if not (torch.is_tensor(slot_table) and slot_table.is_cuda and slot_table.dtype == torch.int32 and slot_table.is_contiguous()
+            and tuple(slot_table.shape) == (B, T)):
+        raise RuntimeError('%s: slot_table must be a contiguous device int32 [B, T] = [%d, %d]' % (what, B, T))
+    if n_slots < 1:
+        raise RuntimeError('%s: n_slots must be at least 1' % what)
+
+
+def msmv_sampling_pool(levels, B, T, G, slot_table, n_slots, sampling_locations, scale_weights, out_layout=OUT_MIX):
+    """Sampler over the keyed frame pool (cache.FramePool): levels[l] = [B*n_slots*6, H, W, G*C]; logical frame t of sample b is
+    read from physical slot slot_table[b, t] -- a DEVICE int32 [B, T] the kernel reads (sbev_msmv_fwd_pool; entries are clamped to
+    [0, n_slots) there, the caller keeps them in range).  n_slots may be below T: two frames of a window may share a slot."""
+    feats = list(levels)
+    _need_device(sampling_locations, scale_weights, *feats)
+    _no_grad_only(sampling_locations, scale_weights, *feats)
+    N = N_VIEWS
+    Bp = B * T * G
+    Q, P = _check_sampling_args(feats, sampling_locations, scale_weights, Bp, 'msmv_sampling_pool')
+    GC = feats[0].shape[-1]
+    if GC % G != 0 or (GC // G) % 4 != 0:
+        raise RuntimeError('pool feature channels %d must split into G=%d groups of a multiple of 4 channels' % (GC, G))
+    C = GC // G
+    _check_slot_table(slot_table, B, T, n_slots, 'msmv_sampling_pool')
+    for f in feats:
+        if not f.is_contiguous() or f.dim() != 4 or f.shape[0] != B * n_slots * N or f.shape[-1] != GC:
+            raise RuntimeError('pool feature level must be contiguous [B*n_slots*6, H, W, G*C]')
+    if out_layout == OUT_REF:
+        out = torch.empty(Bp, Q, C, P, device=feats[0].device, dtype=torch.float32)
+    else:
+        out = torch.empty(B, Q, G, T * P, C, device=feats[0].device, dtype=torch.float32)
+    levels, strides = _pyramid(feats, N, G)          # (stride_bo: one pool slot)
+    st = _lib.load().sbev_msmv_fwd_pool(*levels, _feat_dtype(feats), Bp, N, C, Q, P, *strides,
+                                        _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), _ptr(out),
+                                        out_layout, T, G, _ptr(slot_table), n_slots, _stream())
+    _lib.check(st, 'sbev_msmv_fwd_pool')
+    return out
+
+
 def sample_mix_supported(L, C, P, T, G):
     return bool(_lib.load().sbev_sample_mix_supported(L, C, P, T, G, G))
 
@@ -260,9 +298,11 @@ def query_order(query_bbox, pc_range):
     return order
 
 
-def sample_mix(levels, B, T, G, sampling_locations, scale_weights, params, out_points, frame_slots=None, n_slots=0, order=None, up_log2=None):
+def sample_mix(levels, B, T, G, sampling_locations, scale_weights, params, out_points, frame_slots=None, n_slots=0, order=None, up_log2=None,
+               slot_table=None):
     """Gather + adaptive mixing in one launch (sbev_sample_mix_f32): levels as for msmv_sampling_nhwc (or the ring's
-    buffers with frame_slots / n_slots), params [B,Q,G*(C*C + out_points*T*P)] -> mixed [B,Q,G*out_points*C].
+    buffers with frame_slots / n_slots, or the frame pool's with slot_table / n_slots: a device int32 [B, T], see
+    msmv_sampling_pool -- sbev_sample_mix_pool), params [B,Q,G*(C*C + out_points*T*P)] -> mixed [B,Q,G*out_points*C].
     Bit-identical to msmv_sampling_nhwc(..., OUT_MIX) followed by the mixing kernel.  order (query_order(); any permutation of
     the B*Q rows as int32): the workgroups' launch order -- a placement hint, the result does not depend on it.
     up_log2 (an int; None: fp32): the same launch writing the operand format of the fp16 out-projection (sbev_sample_mix_pairs_f16,
@@ -292,6 +332,17 @@ def sample_mix(levels, B, T, G, sampling_locations, scale_weights, params, out_p
             raise RuntimeError('sample_mix: order must be a contiguous int32 permutation of the B*Q rows')
     loc, weights = sampling_locations.contiguous(), scale_weights.contiguous()
     lib = _lib.load()
+    if slot_table is not None:
+        if frame_slots is not None:
+            raise RuntimeError('sample_mix: give frame_slots (the ring) or slot_table (the frame pool), not both')
+        _check_slot_table(slot_table, B, T, n_slots, 'sample_mix')
+        if any(f.shape[0] != B * n_slots * N for f in feats):
+            raise RuntimeError('sample_mix: pool feature levels must be [B*n_slots*6, H, W, G*C]')
+        st = lib.sbev_sample_mix_pool(*levels, _feat_dtype(feats), B, N, Q, T, G, P, C, *strides[1:], _ptr(loc), _ptr(weights), None,
+                                      _ptr(slot_table), n_slots, _ptr(params), _ptr(y), out_points, 1e-5,
+                                      0 if up_log2 is None else 1, up_log2 or 0, _ptr(order), _stream())
+        _lib.check(st, 'sbev_sample_mix_pool')
+        return y
     head = (*levels, _feat_dtype(feats), B, N, Q, T, G, P, C, *strides[1:], _ptr(loc), _ptr(weights), c_slots, n_slots,
             _ptr(params), _ptr(y), out_points, 1e-5)
     if up_log2 is None:

@@ -8,6 +8,7 @@ import warnings
 import torch
 
 from . import _lib
+from .utils import slot_resident
 
 MAX_LEVELS = 5
 GEMM_F32, GEMM_BF16X3, GEMM_BF16X6, GEMM_BF16X3S, GEMM_F16X3, GEMM_F16X4 = 0, 1, 2, 3, 4, 5      # sbev_gemm_mode
@@ -24,7 +25,7 @@ class DecoderConfig(ctypes.Structure):
                [('hw', (ctypes.c_int32 * 2) * MAX_LEVELS), ('image_h', ctypes.c_float), ('image_w', ctypes.c_float),
                 ('eps_homo', ctypes.c_float), ('gemm_mode', ctypes.c_int32), ('n_slots', ctypes.c_int32),
                 ('frame_slots', ctypes.c_int32 * 16), ('overlap', ctypes.c_int32),
-                ('pc_range', ctypes.c_double * 6)]
+                ('pc_range', ctypes.c_double * 6), ('slot_table', ctypes.c_void_p)]
 
 
 _WEIGHT_FIELDS = ['pe0_w', 'pe0_b', 'pe1_g', 'pe1_b', 'pe3_w', 'pe3_b', 'pe4_g', 'pe4_b',
@@ -204,7 +205,7 @@ class DecoderRuntime:
 
     def _config(self, B, Q, pyramid=None, ctx=None):
         """The sbev_decoder_config of a [B, Q] call with the bound weights; with ``pyramid`` and ``ctx`` also what a forward reads of
-        them (feature dtype and sizes, the frame ring's slots, image size, pc_range)."""
+        them (feature dtype and sizes, the frame ring's slots or the frame pool's device table, image size, pc_range)."""
         dec, layer = self.decoder, self.decoder.decoder_layer
         smp = layer.sampling
         cfg = DecoderConfig()
@@ -221,6 +222,12 @@ class DecoderRuntime:
             cfg.n_slots = pyramid.n_slots
             for t, sl in enumerate(slots):
                 cfg.frame_slots[t] = int(sl)
+        table = getattr(pyramid, 'slot_table', None)
+        if table is not None:                     # cache.PoolPyramid: the kernels read (b, t) -> slot from this device table
+            if not (table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and tuple(table.shape) == (B, cfg.T)):
+                raise RuntimeError('the frame pool\'s slot table must be a contiguous device int32 [B, T]')
+            cfg.n_slots = pyramid.n_slots
+            cfg.slot_table = table.data_ptr()
         if len(pyramid.levels) != cfg.L or pyramid.T != cfg.T or pyramid.B != B:
             raise RuntimeError('feature pyramid (L=%d, T=%d, B=%d) does not match the decoder config (L=%d, T=%d, B=%d)'
                                % (len(pyramid.levels), pyramid.T, pyramid.B, cfg.L, cfg.T, B))
@@ -422,11 +429,15 @@ class StepGraphs:
 
     def _feat_key(self, feats):
         """(key part, the tensors whose identity an address-keyed entry depends on, staged?)"""
-        if hasattr(feats, 'levels'):        # FeaturePyramid / RingPyramid: resident channels-last buffers (+ the ring's slot table);
+        if hasattr(feats, 'levels'):        # FeaturePyramid / RingPyramid / PoolPyramid: resident channels-last buffers;
             # their level tensors are views made per call, so there is no object identity to remember: MAX_WASTED bounds a caller
-            # that builds a new pyramid over new buffers every step
+            # that builds a new pyramid over new buffers every step.  The ring's slot order is a by-value kernel argument: its VALUES
+            # are part of the key (one graph per ring phase).  The pool's table is device memory the captured step reads on replay:
+            # its ADDRESS is, never its contents (one graph per shape)
+            table = getattr(feats, 'slot_table', None)
             return ('pyr', tuple((f.data_ptr(), tuple(f.shape), f.dtype) for f in feats.levels),
-                    tuple(getattr(feats, 'frame_slots', ())), getattr(feats, 'n_slots', 0)), [], False
+                    tuple(getattr(feats, 'frame_slots', ())), getattr(feats, 'n_slots', 0),
+                    None if table is None else (table.data_ptr(), tuple(table.shape))), [], False
         if all(self._relayout_ok(f) for f in feats):
             return ('nchw', tuple((tuple(f.shape), f.dtype) for f in feats)), [], True
         return ('list', tuple((f.data_ptr(), tuple(f.shape), tuple(f.stride()), f.dtype) for f in feats)), list(feats), False
@@ -456,7 +467,7 @@ class StepGraphs:
         e = self.entries.get(key, False)
         if e is False or (isinstance(e, _FirstSighting) and not e.same(ident)):
             # first sighting (or an address whose tensor died and was recycled): eager this time, capture if it comes again
-            if not staged and not hasattr(mlvl_feats, 'frame_slots') and self._unproven() >= self.MAX_WASTED:
+            if not staged and not slot_resident(mlvl_feats) and self._unproven() >= self.MAX_WASTED:
                 # not for the life of the runtime: every RETRY_EVERY-th refused call forgives one never-replayed capture, so a caller
                 # that starts re-using its buffers later gets its graph after all (one probe capture per RETRY_EVERY calls otherwise)
                 self._refused += 1
@@ -550,9 +561,9 @@ class StepGraphs:
                 pyramid.levels.append(nhwc.reshape(pyramid.B * TN, f.shape[3], f.shape[4], pyramid.GC))
         n_packed = (packed.size + 3) // 4 * 4                 # the table behind the constants, 16-byte aligned
         # 'replays' counts launches AFTER the capturing call's own; 'pinned': keyed on addresses of buffers a caller may not bring back
-        # (the online ring's buffers are persistent by construction)
+        # (the online ring's and the frame pool's buffers are persistent by construction)
         e = {'staged': staged, 'n_packed': n_packed, 'layout': layout, 'image': (ih, iw), 'replays': -1,
-             'pinned': not staged and not hasattr(mlvl_feats, 'frame_slots')}
+             'pinned': not staged and not slot_resident(mlvl_feats)}
         full = self._with_table(packed, e, query_bbox, query_feat, mlvl_feats, attn_mask, outs)
         ctx = TR.DecoderContext.from_packed(full, layout, ih, iw, dev)     # the graph reads constants AND table from this tensor on every replay
         table = ctypes.c_void_p(ctx.buffer.data_ptr() + 4 * n_packed)

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import autograd as AG
 from . import dense, ops
-from .utils import DUMP, VERSION
+from .utils import DUMP, VERSION, slot_resident
 
 try:  # optional: register with mmdet's registry when the OpenMMLab stack is present
     from mmcv.runner import BaseModule as _Base
@@ -508,9 +508,9 @@ class SparseBEVTransformerDecoder(_Base):
                                                              for f in (mlvl_feats if isinstance(mlvl_feats, (list, tuple)) else ()))))
         if not inference and not self.training:
             # eval() under enabled grad (a caller that forgot torch.no_grad()): inputs the autograd path cannot take -- the online
-            # frame ring, bf16 feature storage -- run the inference runtime with a one-time warning instead of raising
+            # frame ring / keyed frame pool, bf16 feature storage -- run the inference runtime with a one-time warning instead of raising
             lv = mlvl_feats.levels if hasattr(mlvl_feats, 'levels') else mlvl_feats
-            if hasattr(mlvl_feats, 'frame_slots') or any(torch.is_tensor(f) and f.dtype != torch.float32 for f in lv):
+            if slot_resident(mlvl_feats) or any(torch.is_tensor(f) and f.dtype != torch.float32 for f in lv):
                 if not getattr(self, '_warned_no_grad', False):
                     import warnings
                     warnings.warn('sparsebev_amd: eval-mode call with grad enabled on ring / bf16 features: running the inference '
@@ -542,7 +542,7 @@ class SparseBEVTransformerDecoder(_Base):
             # too -- only the feature units the sample points read are moved (runtime.forward_lazy; bit-identical to the dense pass)
             out = self._runtime.forward_lazy(query_bbox, query_feat, list(mlvl_feats), ctx, attn_mask, finish=_finish)[:2]
             return _Finished(out) if _finish else out
-        feats = mlvl_feats if hasattr(mlvl_feats, 'levels') else FeaturePyramid(mlvl_feats)   # FeaturePyramid / cache.RingPyramid pass through
+        feats = mlvl_feats if hasattr(mlvl_feats, 'levels') else FeaturePyramid(mlvl_feats)   # FeaturePyramid / cache.RingPyramid / cache.PoolPyramid pass through
         if not inference:
             return self.forward_differentiable(query_bbox, query_feat, mlvl_feats, feats, attn_mask, ctx)
         if not (layerwise or DUMP.enabled):
@@ -564,8 +564,8 @@ class SparseBEVTransformerDecoder(_Base):
         """Training / fine-tuning path (grad enabled and something requires grad): every op a HIP forward + HIP backward
         node; dropout only in train() mode.  Mirrors models/sparsebev_transformer.py:86-101 including the detach of the
         refined boxes between layers (:93)."""
-        if hasattr(feats, 'frame_slots'):
-            raise NotImplementedError('the online frame ring is an inference cache; train on [B, T*6, C, H, W] feature lists')
+        if slot_resident(feats):
+            raise NotImplementedError('the online frame ring / frame pool is an inference cache; train on [B, T*6, C, H, W] feature lists')
         if feats.levels[0].dtype != torch.float32:
             raise NotImplementedError('training needs fp32 feature maps (bf16 storage is an inference format)')
         orig = [f for f in mlvl_feats if torch.is_tensor(f)] if isinstance(mlvl_feats, (list, tuple)) else []

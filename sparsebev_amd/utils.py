@@ -56,3 +56,10 @@ class Version:
 
 
 VERSION = Version()
+
+
+def slot_resident(feats):
+    """True for the two pyramids that read resident per-frame slot buffers through a slot mapping -- the online ring's by-value order
+    (cache.RingPyramid: ``frame_slots``) and the keyed frame pool's device table (cache.PoolPyramid: ``slot_table``).  Both are
+    inference caches over persistent buffers: no training path, never counted as a caller's throw-away buffers."""
+    return hasattr(feats, 'frame_slots') or hasattr(feats, 'slot_table')
