@@ -106,14 +106,22 @@ class FrameFeatureCache:
         return RingPyramid(self)
 
 
-class RingPyramid:
-    def __init__(self, cache):
-        self.B, self.T = cache.B, cache.T
-        self.n_slots = cache.n_slots
-        self.frame_slots = list(cache.order[:cache.T])
-        self.levels = [b.reshape(cache.B * cache.n_slots * N_VIEWS, b.shape[3], b.shape[4], b.shape[5]) for b in cache.buffers]
-        self.GC = cache.buffers[0].shape[-1]
+class _SlotPyramid:
+    """What the ring's and the pool's view of a step share: every level's resident buffer as [B*n_slots*6, H, W, G*C].  The subclasses
+    add the slot mapping, which is also what utils.frame_source tells them apart by."""
+
+    def __init__(self, owner):
+        self.B, self.T = owner.B, owner.T
+        self.n_slots = owner.n_slots
+        self.levels = [b.reshape(owner.B * owner.n_slots * N_VIEWS, b.shape[3], b.shape[4], b.shape[5]) for b in owner.buffers]
+        self.GC = owner.buffers[0].shape[-1]
         self.copied = 0
+
+
+class RingPyramid(_SlotPyramid):
+    def __init__(self, cache):
+        super().__init__(cache)
+        self.frame_slots = list(cache.order[:cache.T])
 
     def sample(self, loc, w_bp, T, G):
         return ops.msmv_sampling_ring(self.levels, self.B, T, G, self.frame_slots, self.n_slots, loc, w_bp)
@@ -257,16 +265,12 @@ class FramePool:
         self.book.drop(b)
 
 
-class PoolPyramid:
-    """(no ``frame_slots`` attribute: that marks the by-value ring; the pool is recognised by ``slot_table``)"""
+class PoolPyramid(_SlotPyramid):
+    """(no ``frame_slots`` attribute: that is the by-value ring's mapping; the pool's is ``slot_table``)"""
 
     def __init__(self, pool):
-        self.B, self.T = pool.B, pool.T
-        self.n_slots = pool.n_slots
+        super().__init__(pool)
         self.slot_table = pool.slot_table
-        self.levels = [b.reshape(pool.B * pool.n_slots * N_VIEWS, b.shape[3], b.shape[4], b.shape[5]) for b in pool.buffers]
-        self.GC = pool.buffers[0].shape[-1]
-        self.copied = 0
 
     def sample(self, loc, w_bp, T, G):
         return ops.msmv_sampling_pool(self.levels, self.B, T, G, self.slot_table, self.n_slots, loc, w_bp)

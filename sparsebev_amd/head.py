@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import _lib
 from .transformer import SparseBEVTransformer, _Base
-from .utils import VERSION
+from .utils import VERSION, frame_source
 
 try:  # optional: register with the OpenMMLab registries when that stack is present
     from mmdet.core.bbox.builder import BBOX_CODERS as _CODERS
@@ -181,7 +181,7 @@ class SparseBEVHead(_Base):
         if self.training:
             raise NotImplementedError('sparsebev_amd.SparseBEVHead is the inference head: query denoising / losses '
                                       '(models/sparsebev_head.py:128-204,215-461) are out of scope -- call .eval()')
-        B = mlvl_feats.B if hasattr(mlvl_feats, 'levels') else mlvl_feats[0].shape[0]
+        B = mlvl_feats[0].shape[0] if frame_source(mlvl_feats).kind == 'list' else mlvl_feats.B
         with torch.no_grad():
             query_bbox, query_feat = head_prepare(self.init_query_bbox.weight, self.label_enc.weight, self.num_classes, B)
             cls_scores, bbox_preds = self.transformer(query_bbox, query_feat, mlvl_feats, attn_mask=None, img_metas=img_metas)

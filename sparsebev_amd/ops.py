@@ -9,6 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .utils import FrameSource
 
 N_VIEWS = 6           # models/sparsebev_sampling.py:45
 OUT_REF, OUT_MIX = 0, 1
@@ -160,30 +161,48 @@ def msmv_sampling(mlvl_feats, sampling_locations, scale_weights, out_layout=OUT_
     return _msmv_forward(feats, sampling_locations, scale_weights, out_layout, T, G)
 
 
+def _msmv_resident(word, levels, B, T, G, sampling_locations, scale_weights, out_layout, frame_slots=None, slot_table=None, n_slots=0):
+    """msmv_sampling_nhwc / _ring / _pool: the grouped sampler over resident channels-last levels, ``word`` the entry point's own in
+    the messages.  Frame t of sample b is image run b*T + t of a level, or slot frame_slots[t] / slot_table[b, t] of b's n_slots."""
+    what = 'msmv_sampling_' + word
+    feats = list(levels)
+    _need_device(sampling_locations, scale_weights, *feats)
+    _no_grad_only(sampling_locations, scale_weights, *feats)
+    N = N_VIEWS
+    Bp = B * T * G
+    Q, P = _check_sampling_args(feats, sampling_locations, scale_weights, Bp, what)
+    GC = feats[0].shape[-1]
+    if GC % G != 0 or (GC // G) % 4 != 0:
+        raise RuntimeError('%s feature channels %d must split into G=%d groups of a multiple of 4 channels' % (word, GC, G))
+    C = GC // G
+    src = FrameSource.of(frame_slots, slot_table, n_slots, (B, T), what, plain=None if word == 'pool' else 'dense')
+    frames, dims = (B * src.n_slots, 'B*n_slots*6') if src.resident else (B * T, 'B*T*6')
+    for f in feats:
+        if not f.is_contiguous() or f.dim() != 4 or f.shape[0] != frames * N or f.shape[-1] != GC:
+            raise RuntimeError('%s feature level must be contiguous [%s, H, W, G*C]' % (word, dims))
+    if src.kind == 'ring' and len(src.frame_slots) != T:
+        raise RuntimeError('frame_slots must name one slot per frame (T=%d)' % T)
+    if out_layout == OUT_REF:
+        out = torch.empty(Bp, Q, C, P, device=feats[0].device, dtype=torch.float32)
+    else:
+        out = torch.empty(B, Q, G, T * P, C, device=feats[0].device, dtype=torch.float32)
+    pyramid, strides = _pyramid(feats, N, G)         # (stride_bo: one image run of a frame, or one slot)
+    lib = _lib.load()
+    fn, name, tail = {'dense': (lib.sbev_msmv_fwd, 'sbev_msmv_fwd', ()),
+                      'ring': (lib.sbev_msmv_fwd_ring, 'sbev_msmv_fwd_ring', ((ctypes.c_int32 * len(src.frame_slots))(*src.frame_slots), n_slots)),
+                      'pool': (lib.sbev_msmv_fwd_pool, 'sbev_msmv_fwd_pool', (_ptr(slot_table), n_slots))}[src.kind]
+    st = fn(*pyramid, _feat_dtype(feats), Bp, N, C, Q, P, *strides, _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()),
+            _ptr(out), out_layout, T, G, *tail, _stream())
+    _lib.check(st, name)
+    return out
+
+
 def msmv_sampling_nhwc(feats_nhwc, B, T, G, sampling_locations, scale_weights, out_layout=OUT_MIX):
     """Zero-copy variant: feats_nhwc is a list of ``[B*T*N, H_l, W_l, G*C]``
     channels-last pyramids straight from an NHWC neck; group g of sample batch b' = (b*T+t)*G+g is the
     channel slice [g*C, (g+1)*C) -- the reference's regroup copy (models/sparsebev_transformer.py:73-85,
     2x the feature bytes per call) never happens."""
-    feats = list(feats_nhwc)
-    _need_device(sampling_locations, scale_weights, *feats)
-    _no_grad_only(sampling_locations, scale_weights, *feats)
-    N = N_VIEWS
-    Bp = B * T * G
-    Q, P = _check_sampling_args(feats, sampling_locations, scale_weights, Bp, 'msmv_sampling_nhwc')
-    GC = feats[0].shape[-1]
-    if GC % G != 0 or (GC // G) % 4 != 0:
-        raise RuntimeError('nhwc feature channels %d must split into G=%d groups of a multiple of 4 channels' % (GC, G))
-    C = GC // G
-    for f in feats:
-        if not f.is_contiguous() or f.dim() != 4 or f.shape[0] != B * T * N or f.shape[-1] != GC:
-            raise RuntimeError('nhwc feature level must be contiguous [B*T*6, H, W, G*C]')
-    if out_layout == OUT_REF:
-        out = torch.empty(Bp, Q, C, P, device=feats[0].device, dtype=torch.float32)
-    else:
-        out = torch.empty(B, Q, G, T * P, C, device=feats[0].device, dtype=torch.float32)
-    _msmv_launch(feats, Bp, N, C, G, sampling_locations.contiguous(), scale_weights.contiguous(), out, out_layout, T, G)
-    return out
+    return _msmv_resident('nhwc', feats_nhwc, B, T, G, sampling_locations, scale_weights, out_layout)
 
 
 def msmv_sampling_nhwc_backward(feats_nhwc, B, T, G, sampling_locations, scale_weights, grad_out, grad_feats=None,
@@ -214,70 +233,14 @@ def msmv_sampling_nhwc_backward(feats_nhwc, B, T, G, sampling_locations, scale_w
 def msmv_sampling_ring(levels, B, T, G, frame_slots, n_slots, sampling_locations, scale_weights, out_layout=OUT_MIX):
     """Sampler over the online frame ring (cache.FrameFeatureCache): levels[l] = [B*n_slots*6, H, W, G*C]; logical frame
     t of a sample is read from physical slot frame_slots[t] (sbev_msmv_fwd_ring)."""
-    feats = list(levels)
-    _need_device(sampling_locations, scale_weights, *feats)
-    _no_grad_only(sampling_locations, scale_weights, *feats)
-    N = N_VIEWS
-    Bp = B * T * G
-    Q, P = _check_sampling_args(feats, sampling_locations, scale_weights, Bp, 'msmv_sampling_ring')
-    GC = feats[0].shape[-1]
-    if GC % G != 0 or (GC // G) % 4 != 0:
-        raise RuntimeError('ring feature channels %d must split into G=%d groups of a multiple of 4 channels' % (GC, G))
-    C = GC // G
-    for f in feats:
-        if not f.is_contiguous() or f.dim() != 4 or f.shape[0] != B * n_slots * N or f.shape[-1] != GC:
-            raise RuntimeError('ring feature level must be contiguous [B*n_slots*6, H, W, G*C]')
-    if len(frame_slots) != T:
-        raise RuntimeError('frame_slots must name one slot per frame (T=%d)' % T)
-    if out_layout == OUT_REF:
-        out = torch.empty(Bp, Q, C, P, device=feats[0].device, dtype=torch.float32)
-    else:
-        out = torch.empty(B, Q, G, T * P, C, device=feats[0].device, dtype=torch.float32)
-    levels, strides = _pyramid(feats, N, G)          # (stride_bo: one ring slot)
-    c_slots = (ctypes.c_int32 * T)(*[int(s) for s in frame_slots])
-    st = _lib.load().sbev_msmv_fwd_ring(*levels, _feat_dtype(feats), Bp, N, C, Q, P, *strides,
-                                        _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), _ptr(out),
-                                        out_layout, T, G, c_slots, n_slots, _stream())
-    _lib.check(st, 'sbev_msmv_fwd_ring')
-    return out
-
-
-def _check_slot_table(slot_table, B, T, n_slots, what):
-    if not (torch.is_tensor(slot_table) and slot_table.is_cuda and slot_table.dtype == torch.int32 and slot_table.is_contiguous()
-            and tuple(slot_table.shape) == (B, T)):
-        raise RuntimeError('%s: slot_table must be a contiguous device int32 [B, T] = [%d, %d]' % (what, B, T))
-    if n_slots < 1:
-        raise RuntimeError('%s: n_slots must be at least 1' % what)
+    return _msmv_resident('ring', levels, B, T, G, sampling_locations, scale_weights, out_layout, frame_slots=list(frame_slots), n_slots=n_slots)
 
 
 def msmv_sampling_pool(levels, B, T, G, slot_table, n_slots, sampling_locations, scale_weights, out_layout=OUT_MIX):
     """Sampler over the keyed frame pool (cache.FramePool): levels[l] = [B*n_slots*6, H, W, G*C]; logical frame t of sample b is
     read from physical slot slot_table[b, t] -- a DEVICE int32 [B, T] the kernel reads (sbev_msmv_fwd_pool; entries are clamped to
     [0, n_slots) there, the caller keeps them in range).  n_slots may be below T: two frames of a window may share a slot."""
-    feats = list(levels)
-    _need_device(sampling_locations, scale_weights, *feats)
-    _no_grad_only(sampling_locations, scale_weights, *feats)
-    N = N_VIEWS
-    Bp = B * T * G
-    Q, P = _check_sampling_args(feats, sampling_locations, scale_weights, Bp, 'msmv_sampling_pool')
-    GC = feats[0].shape[-1]
-    if GC % G != 0 or (GC // G) % 4 != 0:
-        raise RuntimeError('pool feature channels %d must split into G=%d groups of a multiple of 4 channels' % (GC, G))
-    C = GC // G
-    _check_slot_table(slot_table, B, T, n_slots, 'msmv_sampling_pool')
-    for f in feats:
-        if not f.is_contiguous() or f.dim() != 4 or f.shape[0] != B * n_slots * N or f.shape[-1] != GC:
-            raise RuntimeError('pool feature level must be contiguous [B*n_slots*6, H, W, G*C]')
-    if out_layout == OUT_REF:
-        out = torch.empty(Bp, Q, C, P, device=feats[0].device, dtype=torch.float32)
-    else:
-        out = torch.empty(B, Q, G, T * P, C, device=feats[0].device, dtype=torch.float32)
-    levels, strides = _pyramid(feats, N, G)          # (stride_bo: one pool slot)
-    st = _lib.load().sbev_msmv_fwd_pool(*levels, _feat_dtype(feats), Bp, N, C, Q, P, *strides,
-                                        _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), _ptr(out),
-                                        out_layout, T, G, _ptr(slot_table), n_slots, _stream())
-    _lib.check(st, 'sbev_msmv_fwd_pool')
-    return out
+    return _msmv_resident('pool', levels, B, T, G, sampling_locations, scale_weights, out_layout, slot_table=slot_table, n_slots=n_slots)
 
 
 def sample_mix_supported(L, C, P, T, G):
@@ -324,34 +287,29 @@ def sample_mix(levels, B, T, G, sampling_locations, scale_weights, params, out_p
     if params.dtype != torch.float32 or params.numel() != B * Q * G * (C * C + out_points * T * P):
         raise RuntimeError('sample_mix: params must be fp32 [B, Q, G*(C*C + out_points*T*P)]')
     y = torch.empty(B, Q, G * out_points * C, device=params.device, dtype=torch.float32 if up_log2 is None else torch.int32)
-    levels, strides = _pyramid(feats, N, G)
-    c_slots = (ctypes.c_int32 * T)(*[int(v) for v in frame_slots]) if frame_slots is not None else None
     if order is not None:
         _need_device(order)
         if order.dtype != torch.int32 or order.numel() != B * Q or not order.is_contiguous():
             raise RuntimeError('sample_mix: order must be a contiguous int32 permutation of the B*Q rows')
     loc, weights = sampling_locations.contiguous(), scale_weights.contiguous()
+    src = FrameSource.of(frame_slots, slot_table, n_slots, (B, T), 'sample_mix')
+    if src.kind == 'pool' and any(f.shape[0] != B * n_slots * N for f in feats):
+        raise RuntimeError('sample_mix: pool feature levels must be [B*n_slots*6, H, W, G*C]')
+    pyramid, strides = _pyramid(feats, N, G)
+    c_slots = (ctypes.c_int32 * T)(*src.frame_slots) if src.kind == 'ring' else None
+    head = (*pyramid, _feat_dtype(feats), B, N, Q, T, G, P, C, *strides[1:], _ptr(loc), _ptr(weights), c_slots)
+    tail = (n_slots, _ptr(params), _ptr(y), out_points, 1e-5)
     lib = _lib.load()
-    if slot_table is not None:
-        if frame_slots is not None:
-            raise RuntimeError('sample_mix: give frame_slots (the ring) or slot_table (the frame pool), not both')
-        _check_slot_table(slot_table, B, T, n_slots, 'sample_mix')
-        if any(f.shape[0] != B * n_slots * N for f in feats):
-            raise RuntimeError('sample_mix: pool feature levels must be [B*n_slots*6, H, W, G*C]')
-        st = lib.sbev_sample_mix_pool(*levels, _feat_dtype(feats), B, N, Q, T, G, P, C, *strides[1:], _ptr(loc), _ptr(weights), None,
-                                      _ptr(slot_table), n_slots, _ptr(params), _ptr(y), out_points, 1e-5,
-                                      0 if up_log2 is None else 1, up_log2 or 0, _ptr(order), _stream())
-        _lib.check(st, 'sbev_sample_mix_pool')
-        return y
-    head = (*levels, _feat_dtype(feats), B, N, Q, T, G, P, C, *strides[1:], _ptr(loc), _ptr(weights), c_slots, n_slots,
-            _ptr(params), _ptr(y), out_points, 1e-5)
-    if up_log2 is None:
-        st = lib.sbev_sample_mix_f32_ordered(*head, _ptr(order), _stream())
+    if src.kind == 'pool':
+        name = 'sbev_sample_mix_pool'
+        st = lib.sbev_sample_mix_pool(*head, _ptr(slot_table), *tail, 0 if up_log2 is None else 1, up_log2 or 0, _ptr(order), _stream())
+    elif up_log2 is None:
+        name, st = 'sbev_sample_mix_f32', lib.sbev_sample_mix_f32_ordered(*head, *tail, _ptr(order), _stream())
     elif order is None:
-        st = lib.sbev_sample_mix_pairs_f16(*head, up_log2, _stream())
+        name, st = 'sbev_sample_mix_pairs_f16', lib.sbev_sample_mix_pairs_f16(*head, *tail, up_log2, _stream())
     else:
-        st = lib.sbev_sample_mix_pairs_f16_ordered(*head, up_log2, _ptr(order), _stream())
-    _lib.check(st, 'sbev_sample_mix_f32' if up_log2 is None else 'sbev_sample_mix_pairs_f16')
+        name, st = 'sbev_sample_mix_pairs_f16', lib.sbev_sample_mix_pairs_f16_ordered(*head, *tail, up_log2, _ptr(order), _stream())
+    _lib.check(st, name)
     return y
 
 

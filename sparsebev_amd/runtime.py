@@ -4,11 +4,12 @@ import ctypes
 import math
 import os
 import warnings
+from collections import namedtuple
 
 import torch
 
 from . import _lib
-from .utils import slot_resident
+from .utils import frame_source
 
 MAX_LEVELS = 5
 GEMM_F32, GEMM_BF16X3, GEMM_BF16X6, GEMM_BF16X3S, GEMM_F16X3, GEMM_F16X4 = 0, 1, 2, 3, 4, 5      # sbev_gemm_mode
@@ -217,17 +218,12 @@ class DecoderRuntime:
         if pyramid is None:
             return cfg
         cfg.feat_dtype = {torch.bfloat16: 1, torch.float16: 2}.get(pyramid.levels[0].dtype, 0)
-        slots = getattr(pyramid, 'frame_slots', None)
-        if slots is not None:
-            cfg.n_slots = pyramid.n_slots
-            for t, sl in enumerate(slots):
-                cfg.frame_slots[t] = int(sl)
-        table = getattr(pyramid, 'slot_table', None)
-        if table is not None:                     # cache.PoolPyramid: the kernels read (b, t) -> slot from this device table
-            if not (table.is_cuda and table.dtype == torch.int32 and table.is_contiguous() and tuple(table.shape) == (B, cfg.T)):
-                raise RuntimeError('the frame pool\'s slot table must be a contiguous device int32 [B, T]')
-            cfg.n_slots = pyramid.n_slots
-            cfg.slot_table = table.data_ptr()
+        src = frame_source(pyramid, (B, cfg.T))
+        cfg.n_slots = src.n_slots
+        for t, sl in enumerate(src.frame_slots):
+            cfg.frame_slots[t] = sl
+        if src.kind == 'pool':                    # the kernels read (b, t) -> slot from this device table
+            cfg.slot_table = src.slot_table.data_ptr()
         if len(pyramid.levels) != cfg.L or pyramid.T != cfg.T or pyramid.B != B:
             raise RuntimeError('feature pyramid (L=%d, T=%d, B=%d) does not match the decoder config (L=%d, T=%d, B=%d)'
                                % (len(pyramid.levels), pyramid.T, pyramid.B, cfg.L, cfg.T, B))
@@ -246,6 +242,8 @@ class DecoderRuntime:
 
     # -- forward -----------------------------------------------------------------------------------------
     def _prepare(self, query_bbox, query_feat, pyramid, ctx, attn_mask, own_workspace=False):
+        """(args of sbev_decoder_forward, what they point into, cls, box) on the runtime's workspace; ``own_workspace``: on a graph
+        workspace whose reference the caller now holds, its key (for _release_graph_ws) as a fifth result."""
         sig = self._ensure_bound()
         B, Q, D = query_feat.shape
         dev = query_feat.device
@@ -256,17 +254,9 @@ class DecoderRuntime:
         if need < 0:
             raise _lib.SbevError('sbev_decoder_workspace_bytes: ' + lib.sbev_last_error().decode())
         key = (str(dev), need)
-        if own_workspace:                   # captured graphs keep a workspace of their own (eager calls use the runtime's): ONE per size
-            # AND per stream -- graphs replayed on one stream run one after the other and may share the pair counters / exchange rows /
-            # order buffer carved from it; two streams (multi-stream serving) would race on them.  Released with the last
-            # graph that uses it (StepGraphs._release_ws).
+        if own_workspace:                   # captured graphs keep a workspace of their own (eager calls use the runtime's)
             key = key + (torch.cuda.current_stream(dev).cuda_stream,)
-            slot = self._graph_ws.get(key)
-            if slot is None:
-                slot = self._graph_ws[key] = [torch.zeros(need + 256, device=dev, dtype=torch.uint8), 0]      # (zeroed once: the on-demand relayout's flag words start clean)
-            slot[1] += 1
-            ws = slot[0]
-            self._last_graph_ws_key = key
+            ws = self._take_graph_ws(key, need, dev)
         else:
             if self._ws is None or self._ws_key != key:
                 self._ws = torch.zeros(need + 256, device=dev, dtype=torch.uint8)
@@ -282,7 +272,25 @@ class DecoderRuntime:
                 _ptr(ctx.time_diff), _ptr(ctx.lidar2img), _ptr(ctx.vel_div), _ptr(mask),
                 _ptr(cls), _ptr(box), ctypes.c_void_p(ws_ptr), need)
         keep = (cfg, feats, qb, qf, mask, pyramid, ctx, ws, self._keep)
-        return args, keep, cls, box
+        return (args, keep, cls, box, key) if own_workspace else (args, keep, cls, box)
+
+    def _take_graph_ws(self, key, need, dev):
+        """One more graph on the workspace of its (device, size, stream): ONE per size AND per stream -- graphs replayed on one stream
+        run one after the other and may share the pair counters / exchange rows / order buffer carved from it; two streams
+        (multi-stream serving) would race on them."""
+        slot = self._graph_ws.get(key)
+        if slot is None:
+            slot = self._graph_ws[key] = [torch.zeros(need + 256, device=dev, dtype=torch.uint8), 0]      # (zeroed once: the on-demand relayout's flag words start clean)
+        slot[1] += 1
+        return slot[0]
+
+    def _release_graph_ws(self, key):
+        """one graph less on its workspace; the last one frees it"""
+        slot = self._graph_ws.get(key)
+        if slot is not None:
+            slot[1] -= 1
+            if slot[1] <= 0:
+                del self._graph_ws[key]
 
     def launches_per_layer(self, B, Q):
         """What sbev_decoder_forward would enqueue per layer for a [B, Q] call with the bound weights (asks the library)."""
@@ -291,7 +299,8 @@ class DecoderRuntime:
         return int(_lib.load().sbev_decoder_launches_per_layer(ctypes.byref(cfg), ctypes.byref(self._weights)))
 
     def forward(self, query_bbox, query_feat, pyramid, ctx, attn_mask=None, finish=False):
-        """pyramid: transformer.FeaturePyramid; ctx: transformer.DecoderContext.  Returns (cls, bbox) stacked over
+        """pyramid: transformer.FeaturePyramid, cache.RingPyramid or cache.PoolPyramid (told apart by utils.frame_source, which also
+        validates the pool's table); ctx: transformer.DecoderContext.  Returns (cls, bbox) stacked over
         layers -- raw, or with ``finish`` nan_to_num'ed by one more launch of this library (sbev_finish_outputs: what
         SparseBEVTransformer.forward applies, models/sparsebev_transformer.py:35-36)."""
         check_pair_faults()                 # an earlier step lost a pair hand-off: raise before anything is enqueued on top of it
@@ -305,7 +314,7 @@ class DecoderRuntime:
     def lazy_ok(self, mlvl_feats):
         """whether a feature LIST qualifies for the on-demand relayout of the eager step: the switch is on, every level is a contiguous,
         16-byte aligned NCHW device tensor [B, T*6, 256, H, W] of one dtype (what StepGraphs stages), 4 groups of 64 channels"""
-        if not _STATE['lazy'] or hasattr(mlvl_feats, 'levels') or len(mlvl_feats) == 0:
+        if not _STATE['lazy'] or frame_source(mlvl_feats).kind != 'list' or len(mlvl_feats) == 0:
             return False
         f0 = mlvl_feats[0]
         return all(torch.is_tensor(f) and f.is_cuda and StepGraphs._relayout_ok(f) and f.dtype == f0.dtype and f.shape[2] == 256 for f in mlvl_feats) \
@@ -350,7 +359,123 @@ class DecoderRuntime:
         return DecoderGraph(handle, keep, cls, box)
 
 
-class StepGraphs:
+# What a captured step is keyed on (see StepGraphs): the queries' shapes, StepGraphs._feat_key (shapes of staged levels; addresses and the
+# slot mapping of levels read in place), the mask's shape or None, DecoderRuntime._signature() of the bound weights, the device,
+# _switch_key(), layer count and box range, the stream (a graph's workspace belongs to the stream it replays on) and ``finish``
+StepKey = namedtuple('StepKey', 'bbox feat feats mask weights device switches num_layers pc_range stream finish')
+# The tensors of one call whose addresses travel in the step's pointer table (outs: with ``finish`` the call's own (cls, bbox), else None)
+StepInputs = namedtuple('StepInputs', 'bbox feat feats mask outs')
+
+
+class CapturedStep:
+    """One captured step.  ``replays`` counts launches AFTER the capturing call's own; ``pinned``: keyed on addresses of buffers a caller
+    may not bring back (the online ring's and the frame pool's buffers are persistent by construction and are not)."""
+
+    def __init__(self, graph, pinned, staged=False, ctx_buf=None, n_packed=0, layout=None, image=None, ws_key=None):
+        self.graph, self.pinned, self.staged, self.ctx_buf = graph, pinned, staged, ctx_buf
+        self.n_packed, self.layout, self.image, self.ws_key = n_packed, layout, image, ws_key
+        self.replays = -1
+
+
+EAGER, SIGHTED, CAPTURE, REPLAY = 'eager', 'sighted', 'capture', 'replay'
+
+
+class StepBook:
+    """StepGraphs' admission policy and bookkeeping, host only (no tensor of its own, no library call; as cache.SlotBook is to
+    FramePool): which keys were seen once, which are captured, which graph goes when ``MAX`` are kept, and when a caller that never
+    brings its buffers back gets no further address-keyed graph.  Graphs are whatever the entries hold as ``graph`` (``replay()`` /
+    ``destroy()``); ``weights()`` is the current weight signature, ``release(step)`` gives a dropped step's workspace back."""
+
+    MAX = 8
+    MAX_WASTED = 3
+    RETRY_EVERY = 64
+
+    def __init__(self, weights, release):
+        self._weights, self._release = weights, release
+        self.entries = {}          # StepKey -> CapturedStep or _FirstSighting (seen once, not captured yet), least recently used first
+        self.replays = 0
+        self.captures = 0
+        self.wasted = 0            # address-keyed graphs evicted without a single replay (forgiven by a replay of one, or slowly by time)
+        self._refused = 0          # calls refused a capture because of them
+        self._warned = False
+
+    def clear(self):
+        for e in self.entries.values():
+            if isinstance(e, CapturedStep):
+                self._destroy(e)
+        self.entries.clear()
+
+    def _destroy(self, e):
+        e.graph.destroy()
+        self._release(e)
+
+    def _drop(self, key):
+        e = self.entries.pop(key)
+        if isinstance(e, CapturedStep):
+            # "captured and never replayed" only counts against the caller when the graph could still have been hit: an entry of a
+            # PREVIOUS weight signature (every optimizer step makes one) was orphaned by the weight update, not by the caller
+            # bringing new buffers (ADVICE r4: evaluate-between-optimizer-steps loops switched replay off for good)
+            if e.pinned and e.replays == 0 and key.weights == self._weights():
+                self.wasted += 1
+            self._destroy(e)
+
+    def _never_replayed(self):
+        """keys of the live address-keyed graphs of the CURRENT weight signature (as in _drop: ADVICE r5) that were captured and never replayed"""
+        sig = self._weights()
+        return [k for k, e in self.entries.items() if isinstance(e, CapturedStep) and e.pinned and e.replays == 0 and k.weights == sig]
+
+    def _unproven(self):
+        """address-keyed graphs (alive or already evicted) that were captured and never replayed afterwards"""
+        return max(self.wasted, 0) + len(self._never_replayed())
+
+    def admit(self, key, ident, pinned):
+        """What this call does, and the key's entry: (EAGER, None) -- refused; (SIGHTED, None) -- eager this time, remembered (with
+        ``ident``, the tensors an address-keyed entry depends on), captured if it comes again; (CAPTURE, its first sighting);
+        (REPLAY, the captured step)."""
+        e = self.entries.get(key)
+        sighted = isinstance(e, _FirstSighting)
+        if e is None or (sighted and not e.same(ident)):       # new (a recycled address of a dead tensor is not "the same input")
+            if pinned and self._unproven() >= self.MAX_WASTED:
+                self._refuse()
+                return EAGER, None
+            if e is None and len(self.entries) >= self.MAX:
+                self._drop(next(iter(self.entries)))
+            self.entries[key] = _FirstSighting(ident)
+            return SIGHTED, None
+        return (CAPTURE if sighted else REPLAY), e
+
+    def _refuse(self):
+        """Not for the life of the runtime: every RETRY_EVERY-th refused call forgives one never-replayed capture, so a caller that
+        starts re-using its buffers later gets its graph after all (one probe capture per RETRY_EVERY calls otherwise)."""
+        self._refused += 1
+        if self._refused % self.RETRY_EVERY == 0:
+            if self.wasted > 0:
+                self.wasted -= 1
+            else:
+                stale = next(iter(self._never_replayed()), None)
+                if stale is not None:
+                    self._drop(stale)         # (counts it as wasted ...)
+                    self.wasted = max(self.wasted - 1, 0)      # ... which this probe forgives: net zero, never negative
+        if not self._warned:
+            warnings.warn('sparsebev_amd: %d step graphs keyed on input addresses were captured and never replayed (the caller '
+                          'passes new channels-last / pyramid buffers every call): no further address-keyed graphs; pass fp32 '
+                          'NCHW feature lists or reuse the buffers' % self._unproven())
+            self._warned = True
+
+    def captured(self, key, step):
+        self.entries[key] = step             # (in its first sighting's place)
+        self.captures += 1
+
+    def launch(self, key, step):
+        self.entries[key] = self.entries.pop(key)            # most recently used last
+        step.graph.replay()
+        step.replays += 1
+        self.replays += 1
+        if step.pinned and step.replays > 0:
+            self.wasted = 0                  # the caller DOES bring its buffers back: earlier never-replayed captures are forgiven
+
+
+class StepGraphs(StepBook):
     """hipGraph replay of the whole per-call step: staging of the inputs, feature relayout and all decoder launches are ONE captured
     graph from the second call of a kind on; per call the host packs the per-sample constants (time_diff, lidar2img) and the
     input POINTERS into one small array, refreshes the graph's device copy of it through the pinned upload ring and launches.
@@ -374,69 +499,24 @@ class StepGraphs:
     freed with the last of them.
     Replaces per-call Python + launch overhead of the reference's eager module chain (models/sparsebev_transformer.py:86-97)."""
 
-    MAX = 8
-    MAX_WASTED = 3
-    RETRY_EVERY = 64
-
     def __init__(self, runtime):
+        super().__init__(lambda: runtime._sig, lambda step: runtime._release_graph_ws(step.ws_key))
         self.rt = runtime
-        self.entries = {}          # key -> dict(graph, ctx_buf, ...) or a _FirstSighting (seen once, not captured yet)
-        self.replays = 0
-        self.captures = 0
-        self.wasted = 0            # address-keyed graphs evicted without a single replay (forgiven by a replay of one, or slowly by time)
-        self._refused = 0          # calls refused a capture because of them
-        self._warned = False
-
-    def clear(self):
-        for e in self.entries.values():
-            if isinstance(e, dict):
-                e['graph'].destroy()
-                self._release_ws(e)
-        self.entries.clear()
-
-    def _release_ws(self, e):
-        """one graph less on its workspace; the last one frees it"""
-        slot = self.rt._graph_ws.get(e.get('ws_key'))
-        if slot is not None:
-            slot[1] -= 1
-            if slot[1] <= 0:
-                del self.rt._graph_ws[e['ws_key']]
-
-    def _drop(self, key):
-        e = self.entries.pop(key)
-        if isinstance(e, dict):
-            # "captured and never replayed" only counts against the caller when the graph could still have been hit: an entry of a
-            # PREVIOUS weight signature (key[4]; every optimizer step makes one) was orphaned by the weight update, not by the caller
-            # bringing new buffers (ADVICE r4: evaluate-between-optimizer-steps loops switched replay off for good)
-            if e['pinned'] and e['replays'] == 0 and key[4] == self.rt._sig:
-                self.wasted += 1
-            e['graph'].destroy()
-            self._release_ws(e)
-
-    def _never_replayed(self):
-        """keys of the live address-keyed graphs of the CURRENT weight signature that were captured and never replayed (an entry of an older
-        signature was orphaned by the weight update, not by the caller bringing new buffers: ADVICE r5)"""
-        return [k for k, e in self.entries.items() if isinstance(e, dict) and e['pinned'] and e['replays'] == 0 and k[4] == self.rt._sig]
-
-    def _unproven(self):
-        """address-keyed graphs (alive or already evicted) that were captured and never replayed afterwards"""
-        return max(self.wasted, 0) + len(self._never_replayed())
 
     @staticmethod
     def _relayout_ok(f):
         return f.dim() == 5 and f.dtype in (torch.float32, torch.bfloat16, torch.float16) and f.is_contiguous() and f.data_ptr() % 16 == 0 and \
             not f.permute(0, 1, 3, 4, 2).is_contiguous()
 
-    def _feat_key(self, feats):
+    def _feat_key(self, feats, src):
         """(key part, the tensors whose identity an address-keyed entry depends on, staged?)"""
-        if hasattr(feats, 'levels'):        # FeaturePyramid / RingPyramid / PoolPyramid: resident channels-last buffers;
+        if src.kind != 'list':              # FeaturePyramid / RingPyramid / PoolPyramid: resident channels-last buffers;
             # their level tensors are views made per call, so there is no object identity to remember: MAX_WASTED bounds a caller
             # that builds a new pyramid over new buffers every step.  The ring's slot order is a by-value kernel argument: its VALUES
             # are part of the key (one graph per ring phase).  The pool's table is device memory the captured step reads on replay:
             # its ADDRESS is, never its contents (one graph per shape)
-            table = getattr(feats, 'slot_table', None)
-            return ('pyr', tuple((f.data_ptr(), tuple(f.shape), f.dtype) for f in feats.levels),
-                    tuple(getattr(feats, 'frame_slots', ())), getattr(feats, 'n_slots', 0),
+            table = src.slot_table
+            return ('pyr', tuple((f.data_ptr(), tuple(f.shape), f.dtype) for f in feats.levels), src.frame_slots, src.n_slots,
                     None if table is None else (table.data_ptr(), tuple(table.shape))), [], False
         if all(self._relayout_ok(f) for f in feats):
             return ('nchw', tuple((tuple(f.shape), f.dtype) for f in feats)), [], True
@@ -454,181 +534,138 @@ class StepGraphs:
             return None
         if attn_mask is not None and not (attn_mask.is_cuda and attn_mask.dtype == torch.uint8 and attn_mask.is_contiguous() and attn_mask.data_ptr() % 16 == 0):
             return None                      # the runtime would convert it into a temporary: nothing stable to stage from
-        if not hasattr(mlvl_feats, 'levels') and not all(torch.is_tensor(f) and f.is_cuda for f in mlvl_feats):
+        src = frame_source(mlvl_feats)
+        if src.kind == 'list' and not all(torch.is_tensor(f) and f.is_cuda for f in mlvl_feats):
             return None
         from . import transformer as TR
         check_pair_faults()                 # (before a capture or replay is built on an invalid step; one host-memory read)
         sig = rt._ensure_bound()
-        fkey, ident, staged = self._feat_key(mlvl_feats)
-        key = (tuple(query_bbox.shape), tuple(query_feat.shape), fkey, None if attn_mask is None else tuple(attn_mask.shape), sig,
-               torch.cuda.current_device(), _switch_key(), rt.decoder.num_layers, tuple(rt.decoder.pc_range),
-               torch.cuda.current_stream(query_bbox.device).cuda_stream,      # per stream: a graph's workspace belongs to the stream it replays on
-               bool(finish))
-        e = self.entries.get(key, False)
-        if e is False or (isinstance(e, _FirstSighting) and not e.same(ident)):
-            # first sighting (or an address whose tensor died and was recycled): eager this time, capture if it comes again
-            if not staged and not slot_resident(mlvl_feats) and self._unproven() >= self.MAX_WASTED:
-                # not for the life of the runtime: every RETRY_EVERY-th refused call forgives one never-replayed capture, so a caller
-                # that starts re-using its buffers later gets its graph after all (one probe capture per RETRY_EVERY calls otherwise)
-                self._refused += 1
-                if self._refused % self.RETRY_EVERY == 0:
-                    if self.wasted > 0:
-                        self.wasted -= 1
-                    else:
-                        stale = next(iter(self._never_replayed()), None)
-                        if stale is not None:
-                            self._drop(stale)         # (counts it as wasted ...)
-                            self.wasted = max(self.wasted - 1, 0)      # ... which this probe forgives: net zero, never negative
-                if not self._warned:
-                    import warnings
-                    warnings.warn('sparsebev_amd: %d step graphs keyed on input addresses were captured and never replayed (the caller '
-                                  'passes new channels-last / pyramid buffers every call): no further address-keyed graphs; pass fp32 '
-                                  'NCHW feature lists or reuse the buffers' % self._unproven())
-                    self._warned = True
-                return None
-            if e is False and len(self.entries) >= self.MAX:
-                self._drop(next(iter(self.entries)))
-            self.entries[key] = _FirstSighting(ident)
+        fkey, ident, staged = self._feat_key(mlvl_feats, src)
+        key = StepKey(tuple(query_bbox.shape), tuple(query_feat.shape), fkey, None if attn_mask is None else tuple(attn_mask.shape), sig,
+                      torch.cuda.current_device(), _switch_key(), rt.decoder.num_layers, tuple(rt.decoder.pc_range),
+                      torch.cuda.current_stream(query_bbox.device).cuda_stream, bool(finish))
+        verdict, e = self.admit(key, ident, pinned=not staged and not src.resident)
+        if e is None:
             return None
-        B = query_bbox.shape[0]
-        packed, layout, ih, iw = TR.DecoderContext.pack(img_metas, B)
+        B, Q = query_bbox.shape[:2]
+        packed, layout, ih, iw = consts = TR.DecoderContext.pack(img_metas, B)
         outs = None
         if finish:                           # this call's own output tensors (the graph's last node writes them through the table)
             nl, nc, cs = rt.decoder.num_layers, rt.decoder.decoder_layer.num_classes, rt.decoder.decoder_layer.code_size
-            Q = query_bbox.shape[1]
             outs = (torch.empty(nl, B, Q, nc, device=query_bbox.device, dtype=torch.float32),
                     torch.empty(nl, B, Q, cs, device=query_bbox.device, dtype=torch.float32))
-        if isinstance(e, _FirstSighting):
-            e = self._capture(key, query_bbox, query_feat, mlvl_feats, attn_mask, B, packed, layout, ih, iw, staged, outs)
+        call = StepInputs(query_bbox, query_feat, mlvl_feats, attn_mask, outs)
+        if verdict == CAPTURE:
+            e = self._capture(key, call, consts, staged, src)
             if e is None:
                 return None
         else:
-            if layout != e['layout'] or (ih, iw) != e['image']:
+            if layout != e.layout or (ih, iw) != e.image:
                 return None                  # other camera count / image size: not this graph's step
-            TR._upload(self._with_table(packed, e, query_bbox, query_feat, mlvl_feats, attn_mask, outs), query_bbox.device, out=e['ctx_buf'])
-        self.entries[key] = self.entries.pop(key)            # most recently used last
-        e['graph'].replay()
-        e['replays'] += 1
-        self.replays += 1
-        if e['pinned'] and e['replays'] > 0:
-            self.wasted = 0                  # the caller DOES bring its buffers back: earlier never-replayed captures are forgiven
-        return outs if outs is not None else (e['graph'].cls, e['graph'].box)
+            TR._upload(self._with_table(packed, e.n_packed, e.staged, call), query_bbox.device, out=e.ctx_buf)
+        self.launch(key, e)
+        return outs if outs is not None else (e.graph.cls, e.graph.box)
 
     @staticmethod
-    def _with_table(packed, e, query_bbox, query_feat, mlvl_feats, attn_mask, outs=None):
+    def _with_table(packed, n_packed, staged, call):
         """packed per-sample constants + the pointer table of this call (int64 words viewed as fp32 pairs) in ONE upload.
         Table: 0 query_bbox, 1 query_feat, 2 mask, [3 .. 3 + L) the NCHW levels (staged entries), then -- ``finish`` entries -- the
         call's output tensors cls, bbox."""
         import numpy as np
-        ptrs = [query_bbox.data_ptr(), query_feat.data_ptr(), attn_mask.data_ptr() if attn_mask is not None else 0]
-        if e['staged']:
-            ptrs += [f.data_ptr() for f in mlvl_feats]
-        if outs is not None:
-            ptrs += [outs[0].data_ptr(), outs[1].data_ptr()]
-        full = np.empty(e['n_packed'] + 2 * len(ptrs), dtype=np.float32)
+        ptrs = [call.bbox.data_ptr(), call.feat.data_ptr(), call.mask.data_ptr() if call.mask is not None else 0]
+        if staged:
+            ptrs += [f.data_ptr() for f in call.feats]
+        if call.outs is not None:
+            ptrs += [call.outs[0].data_ptr(), call.outs[1].data_ptr()]
+        full = np.empty(n_packed + 2 * len(ptrs), dtype=np.float32)
         full[:packed.size] = packed
-        full[packed.size:e['n_packed']] = 0.0
-        full[e['n_packed']:].view(np.int64)[:] = ptrs
+        full[packed.size:n_packed] = 0.0
+        full[n_packed:].view(np.int64)[:] = ptrs
         return full
 
-    def _capture(self, key, query_bbox, query_feat, mlvl_feats, attn_mask, B, packed, layout, ih, iw, staged, outs=None):
-        import numpy as np
+    def _capture(self, key, call, consts, staged, src):
+        """Capture this call's step and book it; None: a feature layout neither read in place nor taken by the in-graph relayout
+        (eager path).  Any exception between taking the workspace reference and a successful capture gives it back."""
         from . import transformer as TR
-        rt, lib = self.rt, _lib.load()
-        dev = query_bbox.device
+        rt, dev = self.rt, call.bbox.device
+        packed, layout, ih, iw = consts
         # graph-owned staging buffers of the queries / mask (the decoder kernels read these)
-        qb = torch.empty_like(query_bbox)
-        qf = torch.empty_like(query_feat)
-        mask = torch.empty_like(attn_mask) if attn_mask is not None else None
-        relayout = []                                         # (table index, resident NHWC buffer, n_images, channels, hw)
-        if hasattr(mlvl_feats, 'levels'):
-            pyramid = mlvl_feats
-        else:
-            pyramid = TR.FeaturePyramid.__new__(TR.FeaturePyramid)
-            f0 = mlvl_feats[0]
-            pyramid.B, TN, pyramid.GC = f0.shape[0], f0.shape[1], f0.shape[2]
-            pyramid.T = TN // TR.N_VIEWS
-            pyramid.levels, pyramid.copied = [], 0
-            for l, f in enumerate(mlvl_feats):
-                nhwc = f.permute(0, 1, 3, 4, 2)
-                if staged:
-                    buf = torch.empty(f.shape[0], TN, f.shape[3], f.shape[4], pyramid.GC, device=dev, dtype=f.dtype)
-                    relayout.append((3 + l, buf, f.shape[0] * TN, pyramid.GC, f.shape[3] * f.shape[4]))
-                    nhwc = buf
-                    pyramid.copied += 1
-                elif not nhwc.is_contiguous():
-                    return None              # a layout neither read in place nor taken by the in-graph relayout kernel: eager path
-                pyramid.levels.append(nhwc.reshape(pyramid.B * TN, f.shape[3], f.shape[4], pyramid.GC))
+        qb, qf = torch.empty_like(call.bbox), torch.empty_like(call.feat)
+        mask = torch.empty_like(call.mask) if call.mask is not None else None
+        pyramid = TR.FeaturePyramid.for_graph(call.feats, staged) if src.kind == 'list' else call.feats
+        if pyramid is None:
+            return None
         n_packed = (packed.size + 3) // 4 * 4                 # the table behind the constants, 16-byte aligned
-        # 'replays' counts launches AFTER the capturing call's own; 'pinned': keyed on addresses of buffers a caller may not bring back
-        # (the online ring's and the frame pool's buffers are persistent by construction)
-        e = {'staged': staged, 'n_packed': n_packed, 'layout': layout, 'image': (ih, iw), 'replays': -1,
-             'pinned': not staged and not slot_resident(mlvl_feats)}
-        full = self._with_table(packed, e, query_bbox, query_feat, mlvl_feats, attn_mask, outs)
-        ctx = TR.DecoderContext.from_packed(full, layout, ih, iw, dev)     # the graph reads constants AND table from this tensor on every replay
-        table = ctypes.c_void_p(ctx.buffer.data_ptr() + 4 * n_packed)
-        args, keep, cls, box = rt._prepare(qb, qf, pyramid, ctx, mask, own_workspace=True)
-        e['ws_key'] = rt._last_graph_ws_key
-        try:                                 # (anything that raises before the capture proper must give the workspace reference back: ADVICE r5)
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream())
-            sp = ctypes.c_void_p(side.cuda_stream)
+        ctx = TR.DecoderContext.from_packed(self._with_table(packed, n_packed, staged, call), layout, ih, iw, dev)     # the graph reads constants AND table from this tensor on every replay
+        args, keep, cls, box, ws_key = rt._prepare(qb, qf, pyramid, ctx, mask, own_workspace=True)
+        try:
             segs = [(0, qb), (1, qf)] + ([(2, mask)] if mask is not None else [])
-            c_idx = (ctypes.c_int32 * len(segs))(*[i for i, _ in segs])
-            c_dst = (ctypes.c_void_p * len(segs))(*[t.data_ptr() for _, t in segs])
-            c_nb = (ctypes.c_int64 * len(segs))(*[t.numel() * t.element_size() for _, t in segs])
-            _lib.check(lib.sbev_capture_begin(sp), 'sbev_capture_begin')
+            relayout = [(3 + l, buf) for l, buf in enumerate(pyramid.levels)] if staged else []      # (table index, graph-owned NHWC buffer)
+            handle = self._record(args, ctypes.c_void_p(ctx.buffer.data_ptr() + 4 * n_packed), segs, relayout, (cls, box) if call.outs is not None else None)
         except BaseException:
-            self._release_ws(e)
+            rt._release_graph_ws(ws_key)
             raise
-        ok = True
-        st_fwd = 0
+        # what the graph's launches read or write: its own buffers, and -- address-keyed entries only -- the caller's feature buffers
+        graph = DecoderGraph(handle, (keep, qb, qf, mask, ctx, None if staged else (call.feats, pyramid)), cls, box)
+        e = CapturedStep(graph, not staged and not src.resident, staged, ctx.buffer, n_packed, layout, (ih, iw), ws_key)
+        self.captured(key, e)
+        return e
+
+    @staticmethod
+    def _record(args, table, segs, relayout, finish):
+        """The step's launches under stream capture -> the instantiated graph's handle: the in-graph copies of ``segs`` (table index,
+        graph-owned buffer), the relayout of the staged levels (on demand inside the step, all fp32 levels in one launch, or one launch
+        per level), the decoder step, and -- ``finish``: the graph's (cls, box) -- the nan_to_num into the call's own outputs.  Raises
+        when any of it fails, with the capture ended."""
+        lib = _lib.load()
+        side = torch.cuda.Stream(device=segs[0][1].device)
+        side.wait_stream(torch.cuda.current_stream())
+        sp = ctypes.c_void_p(side.cuda_stream)
+        c_idx = (ctypes.c_int32 * len(segs))(*[i for i, _ in segs])
+        c_dst = (ctypes.c_void_p * len(segs))(*[t.data_ptr() for _, t in segs])
+        c_nb = (ctypes.c_int64 * len(segs))(*[t.numel() * t.element_size() for _, t in segs])
+        n = len(relayout)
+        n_img, ch = relayout[0][1].shape[::3] if n else (0, 0)      # levels are [B*T*6, H, W, G*C]
+        hws = [buf.shape[1] * buf.shape[2] for _, buf in relayout]
+        _lib.check(lib.sbev_capture_begin(sp), 'sbev_capture_begin')
+        ok, st_fwd = True, 0
         try:
             ok = lib.sbev_copy_indirect(table, len(segs), c_idx, c_dst, c_nb, sp) == 0
             # on-demand relayout: no dense pass at all -- every layer moves the units its sample points marked (sbev_decoder_forward_lazy)
-            lazy = bool(relayout) and staged and len(relayout) == len(mlvl_feats) and _STATE['lazy'] and bool(lib.sbev_decoder_lazy_supported(args[0]))
-            multi = (not lazy and len(relayout) > 1 and all(r[1].dtype == torch.float32 and r[2] == relayout[0][2] and r[3] == relayout[0][3] and r[3] % 4 == 0
-                                               and r[4] % 4 == 0 for r in relayout) and len(relayout) <= MAX_LEVELS and _STATE['relayout_multi'])
+            lazy = n > 0 and _STATE['lazy'] and bool(lib.sbev_decoder_lazy_supported(args[0]))
+            multi = (not lazy and 1 < n <= MAX_LEVELS and ch % 4 == 0 and _STATE['relayout_multi']
+                     and all(buf.dtype == torch.float32 and hw % 4 == 0 for (_, buf), hw in zip(relayout, hws)))
             if multi:                        # every fp32 level of the pyramid in ONE launch (the coarse levels ride in the finest one's tail)
-                n = len(relayout)
-                c_ix = (ctypes.c_int32 * n)(*[r[0] for r in relayout])
-                c_out = (ctypes.c_void_p * n)(*[r[1].data_ptr() for r in relayout])
-                c_hw = (ctypes.c_int32 * n)(*[r[4] for r in relayout])
-                ok = ok and lib.sbev_nchw_to_nhwc_f32_multi_indirect(table, n, c_ix, c_out, relayout[0][2], relayout[0][3], c_hw, sp) == 0
+                c_ix = (ctypes.c_int32 * n)(*[i for i, _ in relayout])
+                c_out = (ctypes.c_void_p * n)(*[buf.data_ptr() for _, buf in relayout])
+                ok = ok and lib.sbev_nchw_to_nhwc_f32_multi_indirect(table, n, c_ix, c_out, n_img, ch, (ctypes.c_int32 * n)(*hws), sp) == 0
             elif not lazy:
-                for idx, buf, n_img, ch, hw in relayout:
+                for (idx, buf), hw in zip(relayout, hws):
                     fn = lib.sbev_nchw_to_nhwc_f32_indirect if buf.dtype == torch.float32 else lib.sbev_nchw_to_nhwc_b16_indirect
                     ok = ok and fn(table, idx, _ptr(buf), n_img, ch, hw, sp) == 0
             if lazy:
                 lz = LazyFeats()
                 lz.table = table
-                for l, r in enumerate(relayout):
-                    lz.index[l] = r[0]
+                for l, (idx, _) in enumerate(relayout):
+                    lz.index[l] = idx
                 st_fwd = lib.sbev_decoder_forward_lazy(args[0], args[1], args[2], ctypes.byref(lz), *args[3:], sp) if ok else 0
             else:
                 st_fwd = lib.sbev_decoder_forward(*args, sp) if ok else 0
             ok = ok and st_fwd == 0
-            if outs is not None:
-                i_out = 3 + (len(mlvl_feats) if staged else 0)
+            if finish is not None:
+                cls, box = finish
+                i_out = 3 + n
                 ok = ok and lib.sbev_finish_outputs_indirect(table, i_out, i_out + 1, _ptr(cls), _ptr(box), cls.numel(), box.numel(), sp) == 0
         finally:
             handle = ctypes.c_void_p()
             st = lib.sbev_capture_end(sp, ctypes.byref(handle) if ok else None)
-        if not ok or st != 0:
-            self._release_ws(e)
         if st_fwd == _lib.EFAULT:            # an EARLIER step lost a pair hand-off: the caller sees PairFaultError (pair mode off, acknowledged), as on the eager path
             _lib.check(st_fwd, 'sbev_decoder_forward (capture)')
         if not ok:
             raise _lib.SbevError('graph capture of the decoder step failed: ' + lib.sbev_last_error().decode())
         _lib.check(st, 'sbev_capture_end')
         torch.cuda.current_stream().wait_stream(side)
-        # what the graph's launches read or write: its own buffers, and -- address-keyed entries only -- the caller's feature buffers
-        pinned = None if staged else (mlvl_feats, pyramid)
-        graph = DecoderGraph(handle, (keep, [r[1] for r in relayout], qb, qf, mask, ctx, pinned), cls, box)
-        e.update(graph=graph, ctx_buf=ctx.buffer)
-        self.entries[key] = e
-        self.captures += 1
-        return e
+        return handle
 
 
 class _FirstSighting:

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import autograd as AG
 from . import dense, ops
-from .utils import DUMP, VERSION, slot_resident
+from .utils import DUMP, VERSION, frame_source, slot_resident
 
 try:  # optional: register with mmdet's registry when the OpenMMLab stack is present
     from mmcv.runner import BaseModule as _Base
@@ -318,31 +318,48 @@ class FeaturePyramid:
     [g*C, (g+1)*C) inside the kernel, so the reference's per-group regroup copy never exists."""
 
     def __init__(self, mlvl_feats):
-        self.levels = []
-        self.copied = 0
+        for f, shape in zip(mlvl_feats, self._geometry(mlvl_feats)):
+            if not f.is_cuda:
+                raise RuntimeError('SparseBEVTransformer (sparsebev_amd) needs device features; there is no CPU path')
+            level = self._in_place(f, shape)
+            if level is None:
+                level = dense.to_channels_last(f).reshape(shape)
+                self.copied += 1
+            self.levels.append(level)
+
+    def _geometry(self, mlvl_feats):
+        """B, T, G*C of the reference layout list[L] of [B, T*6, G*C, H, W] (and no level yet) -> every level's channels-last shape"""
         f0 = mlvl_feats[0]
         self.B, TN, self.GC = f0.shape[0], f0.shape[1], f0.shape[2]
         self.T = TN // N_VIEWS
-        for f in mlvl_feats:
-            if not f.is_cuda:
-                raise RuntimeError('SparseBEVTransformer (sparsebev_amd) needs device features; there is no CPU path')
-            nhwc = f.permute(0, 1, 3, 4, 2)
-            if not nhwc.is_contiguous():
-                nhwc = dense.to_channels_last(f)
-                self.copied += 1
-            self.levels.append(nhwc.reshape(self.B * TN, f.shape[3], f.shape[4], self.GC))
+        self.levels, self.copied = [], 0
+        return [(self.B * TN, f.shape[3], f.shape[4], self.GC) for f in mlvl_feats]
+
+    @staticmethod
+    def _in_place(f, shape):
+        """the channels-last view of a level whose memory already is, else None"""
+        nhwc = f.permute(0, 1, 3, 4, 2)
+        return nhwc.reshape(shape) if nhwc.is_contiguous() else None
 
     @classmethod
     def empty_like_nchw(cls, mlvl_feats):
         """Uninitialised channels-last buffers for the on-demand relayout (runtime.DecoderRuntime.forward_lazy): the step writes only
         the units its sample points read."""
         self = cls.__new__(cls)
-        f0 = mlvl_feats[0]
-        self.B, TN, self.GC = f0.shape[0], f0.shape[1], f0.shape[2]
-        self.T = TN // N_VIEWS
-        self.copied = 0
-        self.levels = [torch.empty(self.B * TN, f.shape[3], f.shape[4], self.GC, device=f.device, dtype=f.dtype) for f in mlvl_feats]
+        self.levels = [torch.empty(shape, device=f.device, dtype=f.dtype) for f, shape in zip(mlvl_feats, self._geometry(mlvl_feats))]
         return self
+
+    @classmethod
+    def for_graph(cls, mlvl_feats, staged):
+        """What a captured step reads (runtime.StepGraphs).  ``staged``: buffers the graph owns, relayouted into on every replay (every
+        level counts as copied); else the caller's channels-last memory in place -- None when a level is not channels-last."""
+        if staged:
+            self = cls.empty_like_nchw(mlvl_feats)
+            self.copied = len(self.levels)
+            return self
+        self = cls.__new__(cls)
+        self.levels = [self._in_place(f, shape) for f, shape in zip(mlvl_feats, self._geometry(mlvl_feats))]
+        return None if any(level is None for level in self.levels) else self
 
     def sample(self, loc, w_bp, T, G):
         return ops.msmv_sampling_nhwc(self.levels, self.B, T, G, loc, w_bp, out_layout=ops.OUT_MIX)
@@ -509,8 +526,9 @@ class SparseBEVTransformerDecoder(_Base):
         if not inference and not self.training:
             # eval() under enabled grad (a caller that forgot torch.no_grad()): inputs the autograd path cannot take -- the online
             # frame ring / keyed frame pool, bf16 feature storage -- run the inference runtime with a one-time warning instead of raising
-            lv = mlvl_feats.levels if hasattr(mlvl_feats, 'levels') else mlvl_feats
-            if slot_resident(mlvl_feats) or any(torch.is_tensor(f) and f.dtype != torch.float32 for f in lv):
+            src = frame_source(mlvl_feats)
+            lv = mlvl_feats if src.kind == 'list' else mlvl_feats.levels
+            if src.resident or any(torch.is_tensor(f) and f.dtype != torch.float32 for f in lv):
                 if not getattr(self, '_warned_no_grad', False):
                     import warnings
                     warnings.warn('sparsebev_amd: eval-mode call with grad enabled on ring / bf16 features: running the inference '
@@ -542,7 +560,7 @@ class SparseBEVTransformerDecoder(_Base):
             # too -- only the feature units the sample points read are moved (runtime.forward_lazy; bit-identical to the dense pass)
             out = self._runtime.forward_lazy(query_bbox, query_feat, list(mlvl_feats), ctx, attn_mask, finish=_finish)[:2]
             return _Finished(out) if _finish else out
-        feats = mlvl_feats if hasattr(mlvl_feats, 'levels') else FeaturePyramid(mlvl_feats)   # FeaturePyramid / cache.RingPyramid / cache.PoolPyramid pass through
+        feats = FeaturePyramid(mlvl_feats) if frame_source(mlvl_feats).kind == 'list' else mlvl_feats   # FeaturePyramid / cache.RingPyramid / cache.PoolPyramid pass through
         if not inference:
             return self.forward_differentiable(query_bbox, query_feat, mlvl_feats, feats, attn_mask, ctx)
         if not (layerwise or DUMP.enabled):

@@ -1,6 +1,7 @@
 """Module-level switches the reference exposes next to the hot path (models/utils.py:309-325)."""
 import os
 import tempfile
+from typing import NamedTuple
 
 import torch
 
@@ -58,8 +59,47 @@ class Version:
 VERSION = Version()
 
 
+class FrameSource(NamedTuple):
+    """Where a decoder step's frames live.  ``kind``: 'list' (a feature list, no pyramid object), 'dense' (transformer.FeaturePyramid:
+    frame t of sample b is image run b*T + t), 'ring' (cache.RingPyramid: slot ``frame_slots[t]`` of ``n_slots`` for the whole batch,
+    passed to the kernels by value) or 'pool' (cache.PoolPyramid: slot ``slot_table[b, t]`` of ``n_slots``, a device table the kernels read)."""
+    kind: str
+    frame_slots: tuple = ()
+    slot_table: object = None
+    n_slots: int = 0
+
+    @property
+    def resident(self):
+        return self.kind in ('ring', 'pool')
+
+    @classmethod
+    def of(cls, frame_slots=None, slot_table=None, n_slots=0, shape=None, what='the frame pool', plain='dense'):
+        """From the slot mapping itself (the operator layer is handed it as arguments); ``plain``: the kind without one (None: the
+        caller means the pool).  With ``shape = (B, T)`` the pool's table is validated -- here and nowhere else."""
+        if frame_slots is not None and slot_table is not None:
+            raise RuntimeError('%s: give frame_slots (the ring) or slot_table (the frame pool), not both' % what)
+        if frame_slots is not None:
+            return cls('ring', tuple(int(s) for s in frame_slots), None, n_slots)
+        if slot_table is None and plain is not None:
+            return cls(plain)
+        if shape is not None:
+            if not (torch.is_tensor(slot_table) and slot_table.is_cuda and slot_table.dtype == torch.int32 and slot_table.is_contiguous()
+                    and tuple(slot_table.shape) == tuple(shape)):
+                raise RuntimeError('%s: slot_table must be a contiguous device int32 [B, T] = [%d, %d]' % ((what,) + tuple(shape)))
+            if n_slots < 1:
+                raise RuntimeError('%s: n_slots must be at least 1' % what)
+        return cls('pool', (), slot_table, n_slots)
+
+
+def frame_source(feats, shape=None, what='the frame pool'):
+    """The FrameSource of whatever the decoder is handed as features -- the ONE place that looks at the ``levels`` / ``frame_slots`` /
+    ``slot_table`` attributes: ``frame_slots`` marks the ring, ``slot_table`` the pool (both: refused), ``levels`` alone a dense pyramid,
+    none of them a feature list."""
+    return FrameSource.of(getattr(feats, 'frame_slots', None), getattr(feats, 'slot_table', None), getattr(feats, 'n_slots', 0), shape, what,
+                          plain='dense' if hasattr(feats, 'levels') else 'list')
+
+
 def slot_resident(feats):
-    """True for the two pyramids that read resident per-frame slot buffers through a slot mapping -- the online ring's by-value order
-    (cache.RingPyramid: ``frame_slots``) and the keyed frame pool's device table (cache.PoolPyramid: ``slot_table``).  Both are
-    inference caches over persistent buffers: no training path, never counted as a caller's throw-away buffers."""
-    return hasattr(feats, 'frame_slots') or hasattr(feats, 'slot_table')
+    """True for the two pyramids that read resident per-frame slot buffers through a slot mapping (the online ring, the keyed frame
+    pool).  Both are inference caches over persistent buffers: no training path, never counted as a caller's throw-away buffers."""
+    return frame_source(feats).resident

@@ -247,13 +247,13 @@ def test_replayed_lazy_step_follows_fresh_tensors_and_equals_the_dense_step():
             assert torch.equal(eager_lazy[0], want[0]) and torch.equal(eager_lazy[1], want[1]), 'eager lazy step %d' % step
         sg = g.decoder._runtime.step_graphs
         assert sg.captures == 1 and sg.replays == 4
-        nodes_lazy = next(v for v in sg.entries.values() if isinstance(v, dict))['graph'].num_nodes
+        nodes_lazy = next(v for v in sg.entries.values() if isinstance(v, runtime.CapturedStep)).graph.num_nodes
         runtime.lazy_relayout(False)
         for step in range(3):
             got = g(bbox, feat, list(feats), None, m2)
             assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
         assert sg.captures == 2
-        nodes_dense = [v for v in sg.entries.values() if isinstance(v, dict)][-1]['graph'].num_nodes
+        nodes_dense = [v for v in sg.entries.values() if isinstance(v, runtime.CapturedStep)][-1].graph.num_nodes
         print('graph nodes: lazy %d, dense %d' % (nodes_lazy, nodes_dense))
         # one dense relayout launch less, one move launch more for layer 0; the scans of layers 1 .. 2 ride in the generator GEMM's prologue
         # (fp16 GEMM modes, <= 1024 rows: csrc/decoder.hip `scan_in_gen`)

@@ -181,7 +181,7 @@ def test_one_graph_for_every_phase_and_scene_change():
     B, Q, T, n_slots, steps = 1, 49, 4, 12, 30
     ih, iw, sizes = S.PYRAMIDS['tiny']
     g, e = build(T, len(sizes), 9, graph=True), build(T, len(sizes), 9)
-    from sparsebev_amd.runtime import StepGraphs
+    from sparsebev_amd.runtime import CapturedStep, StepGraphs
     assert n_slots > StepGraphs.MAX
     frames = Frames('tiny', 90)
     bbox, feat = [t.to(DEV) for t in S.make_queries(B, Q, seed=10)]
@@ -201,11 +201,11 @@ def test_one_graph_for_every_phase_and_scene_change():
         want = e(bbox, feat, frames.dense(keys), None, metas)
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), i
     sg = g.decoder._runtime.step_graphs
-    graphs = [v for v in sg.entries.values() if isinstance(v, dict)]
-    print('pool stream: %d steps, captures %d, graph launches %d, replays of the one graph %s' % (steps, sg.captures, sg.replays, [v['replays'] for v in graphs]))
+    graphs = [v for v in sg.entries.values() if isinstance(v, CapturedStep)]
+    print('pool stream: %d steps, captures %d, graph launches %d, replays of the one graph %s' % (steps, sg.captures, sg.replays, [v.replays for v in graphs]))
     # step 0 is the shape's first sighting (eager), step 1 captures and launches, every later step replays that one graph: the entry's
     # 'replays' counts launches after the capturing call's own (steps - 2), StepGraphs.replays every launch (steps - 1, as in test_gpu_stepgraph.py)
-    assert sg.captures == 1 and len(graphs) == 1 and graphs[0]['replays'] == steps - 2 and sg.replays == steps - 1, (sg.captures, sg.replays)
+    assert sg.captures == 1 and len(graphs) == 1 and graphs[0].replays == steps - 2 and sg.replays == steps - 1, (sg.captures, sg.replays)
 
 
 def test_sequential_keys_equal_the_ring():
