@@ -936,6 +936,24 @@ int sbev_profile_stride(int every_n_calls);
 /* Same for the other bracketed launches: kind 0 = sampler, 1 = parameter-generator GEMM, 2 = out-projection GEMM, 3 = fused gather + mixing. */
 int sbev_profile_read(int kind, float* ms, int max_n);
 
+/*
+ * The keyed frame pool's insert: a step's NEW frames into their slots, in one launch for all levels and samples, recordable inside a
+ * captured step.  Source level l is the backbone's NCHW map [B, n_views, channels, hw_pixels[l]] for the batch's newest images -- given
+ * as src[l] (table == NULL), or as table[index[l]] read on the device when the kernel starts (src == NULL; the device pointer table of a
+ * replayable step, see sbev_nchw_to_nhwc_f32_indirect); exactly one of the two forms.  Destination level l is the pool's resident
+ * buffer out[l] = [B, n_slots, n_views, hw_pixels[l], channels]; sample b goes to slot insert[b] (device int32 [B], refreshed by the host
+ * per step like the slot table of sbev_msmv_fwd_pool).  An entry outside [0, n_slots) -- use -1 -- means "no frame for this sample":
+ * nothing of that sample is read or written.  Entries are NOT clamped: this launch writes.  dtype (enum sbev_dtype) is the storage of
+ * both sides: fp32 -> fp32 slots, fp16 / bf16 -> slots of the same type, moved as bytes.  Any sizes (hw % 4 and channels % 4, or % 8
+ * for 2-byte storage, select the vector tile per level); sources and destinations 16-byte aligned.  index, src, out, hw_pixels: host
+ * arrays of n_levels entries (1 .. SBEV_MAX_LEVELS).  B == 0 is an empty call.
+ * Replaces: the per-frame extract-then-cat of the reference's online mode (models/sparsebev.py:255-321) for the newest frame, and this
+ *           library's own per-sample, per-level sbev_nchw_to_nhwc_* launches in front of a replayed step.
+ */
+int sbev_pool_insert(const void* const* table, const int32_t* index, const void* const* src, void* const* out, int n_levels,
+                     const int32_t* hw_pixels, int B, int n_views, int channels, int dtype, const int32_t* insert, int n_slots,
+                     sbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,27 @@ class SlotBook:
             assert all(0 <= s < self.n_slots for s in rows[-1])
         return rows
 
+    def plan_step(self, keys):
+        """(rows, insert) of a streaming step whose only new frame per sample is the window's newest: the step's [B][T] slot table (as
+        ``table``) and per sample the slot that receives ``keys[b][0]``, or -1 when that frame is resident.  The newest key is the only
+        one that may be missing; it gets a slot by ``assign``'s rules.  Any other missing key raises the KeyError of ``table`` (those
+        frames go through put() first) and leaves the book as it was."""
+        saved = (self.B, {b: dict(m) for b, m in self.slots.items()}, {b: list(k) for b, k in self.needed.items()})
+        try:
+            keys = self._announce(keys)
+            insert = []
+            for b, row in enumerate(keys):
+                mine = self.slots.get(b, {})
+                absent = [k for k in self.needed[b] if k not in mine]
+                late = [k for k in absent if k != row[0]]
+                if late:
+                    raise KeyError('sample %d: frame %r is not in the pool and is not the step\'s newest (missing(keys) lists what to put() first)' % (b, late[0]))
+                insert.append(self.assign(b, row[0])[0] if absent else -1)
+            return self.table(keys), insert
+        except BaseException:
+            self.B, self.slots, self.needed = saved
+            raise
+
     def drop(self, b):
         """Forget sample b's stream (its slots are free again)."""
         self.slots.pop(b, None)
@@ -210,7 +231,11 @@ class FramePool:
     step's mapping (b, t) -> slot lives in ONE persistent device int32 table ``[B, T]`` that the sampler kernels read
     (``sbev_msmv_fwd_pool``); ``pyramid`` refreshes its contents in place, so a captured decoder step replays for every phase, scene
     change and mix of streams.  A frame that appears twice in a window is one slot read twice; eviction is per sample, least recently
-    used, never a frame the announced step needs.  ``dtype``: the slots' storage type, as for FrameFeatureCache."""
+    used, never a frame the announced step needs.  ``dtype``: the slots' storage type, as for FrameFeatureCache.
+
+    The streaming step -- one new frame per sample, the window's newest -- is ``step(keys, frames)`` instead: the frames are not stored
+    by launches of this call but travel with the returned pyramid, and the decoder call moves them into their slots itself
+    (``sbev_pool_insert``, destinations read from a device row behind the slot table): inside the captured step when it is replayed."""
 
     def __init__(self, num_frames, n_slots=16, dtype=torch.float32):
         if dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -219,7 +244,10 @@ class FramePool:
         self.book = SlotBook(num_frames, n_slots)
         self.T, self.n_slots = num_frames, n_slots
         self.buffers = None            # list[L] of [B, n_slots, 6, H, W, C]
-        self.slot_table = None         # device int32 [B, T]: allocated once with the buffers, refreshed in place per pyramid()
+        self.slot_table = None         # device int32 [B, T]: allocated once with the buffers, refreshed in place per pyramid() / step()
+        self.insert_row = None         # device int32 [B] behind it in the same allocation (``_tables``): step()'s slot per sample, -1 = none
+        self._tables = None
+        self._live = None              # the pyramid handed out last: the next pyramid() / step() ends its validity
 
     @property
     def B(self):
@@ -239,15 +267,28 @@ class FramePool:
         if self.buffers is None:
             if self.book.B is None:
                 raise RuntimeError('announce the step with missing(keys) before the first put(): the batch size is taken from it')
-            self.buffers = [torch.empty(self.book.B, self.n_slots, N_VIEWS, f.shape[2], f.shape[3], f.shape[1], device=f.device, dtype=self.dtype)
-                            for f in feats]
-            self.slot_table = torch.zeros(self.book.B, self.T, device=feats[0].device, dtype=torch.int32)
+            self._alloc([tuple(f.shape[1:]) for f in feats], feats[0].device)
         if len(feats) != len(self.buffers) or any(tuple(buf.shape[3:]) != (f.shape[2], f.shape[3], f.shape[1]) for f, buf in zip(feats, self.buffers)):
             raise RuntimeError('frame features do not match the pool\'s levels')
         slot, _ = self.book.assign(b, key)
         for f, buf in zip(feats, self.buffers):
             _store_level(f[None], [buf[b, slot]], self.dtype)
         return slot
+
+    def _alloc(self, chw, device):
+        """buffers for levels of (C, H, W) and the two tables in ONE int32 allocation: [B, T] slot table, then the [B] insert row"""
+        B = self.book.B
+        self.buffers = [torch.empty(B, self.n_slots, N_VIEWS, h, w, c, device=device, dtype=self.dtype) for c, h, w in chw]
+        self._tables = torch.zeros(B * self.T + B, device=device, dtype=torch.int32)
+        self.slot_table = self._tables[:B * self.T].view(B, self.T)
+        self.insert_row = self._tables[B * self.T:]
+        self.insert_row.fill_(-1)
+
+    def _hand_out(self, pyr):
+        if self._live is not None:
+            self._live.insert = None          # (its frames are free again; the tables it reads now describe another step)
+        self._live = pyr
+        return pyr
 
     def pyramid(self, keys):
         """The step's view for the decoder (drop-in for transformer.FeaturePyramid): uploads the step's table into the persistent
@@ -258,7 +299,45 @@ class FramePool:
         if self.buffers is None:
             raise RuntimeError('the pool is empty')
         _upload(np.asarray(rows, dtype=np.int32), self.slot_table.device, out=self.slot_table)
-        return PoolPyramid(self)
+        return self._hand_out(PoolPyramid(self))
+
+    def _insert_takes(self, frames):
+        """whether sbev_pool_insert takes these frames: contiguous NCHW memory of the slots' own type, 16-byte aligned (a step's pointer
+        table carries the addresses).  Channels-last memory and fp16 / bf16 frames for fp32 slots are _store_level's."""
+        return all(f.dtype == self.dtype and f.is_contiguous() and f.data_ptr() % 16 == 0 for f in frames)
+
+    def step(self, keys, frames):
+        """One streaming step: ``frames`` = list[L] of [B, 6, C, H_l, W_l] device tensors, the backbone's output for the batch's newest
+        images (as FrameFeatureCache.push takes them); sample b's goes under ``keys[b][0]`` unless that key is resident.  Every other key
+        of the step must be resident (SlotBook.plan_step).  Slot table and insert row go up in one upload; the returned PoolPyramid carries
+        ``insert = (frames, insert row)``: the decoder call it is handed to moves the frames into their slots (sbev_pool_insert, inside
+        the captured step when that is replayed; PoolPyramid.materialise() for other readers).  The pyramid keeps the frames alive until
+        the next step() / pyramid(), which also ends its validity.  Frames the kernel does not take (channels-last memory, fp16 / bf16
+        for fp32 slots) are stored here and now as put() stores them, and the pyramid carries no insert."""
+        import numpy as np
+        from .transformer import _upload
+        frames = list(frames)
+        if not frames or not all(torch.is_tensor(f) and f.is_cuda and f.dim() == 5 and f.shape[1] == N_VIEWS and f.shape[0] == frames[0].shape[0]
+                                 for f in frames):
+            raise RuntimeError('frame features must be device tensors [B, 6, C, H, W]')
+        keys = [list(row) for row in keys]
+        if len(keys) != frames[0].shape[0]:
+            raise ValueError('keys for %d samples, frames for %d' % (len(keys), frames[0].shape[0]))
+        if self.buffers is not None and (len(frames) != len(self.buffers) or any(
+                tuple(buf.shape[3:]) != (f.shape[3], f.shape[4], f.shape[2]) for f, buf in zip(frames, self.buffers))):
+            raise RuntimeError('frame features do not match the pool\'s levels')
+        rows, insert = self.book.plan_step(keys)
+        if self.buffers is None:
+            self._alloc([tuple(f.shape[2:]) for f in frames], frames[0].device)
+        in_step = self._insert_takes(frames)
+        if not in_step:
+            for b, slot in enumerate(insert):
+                if slot >= 0:
+                    for f, buf in zip(frames, self.buffers):
+                        _store_level(f[b:b + 1], [buf[b, slot]], self.dtype)
+            insert = [-1] * len(insert)
+        _upload(np.asarray([s for row in rows for s in row] + insert, dtype=np.int32), self._tables.device, out=self._tables)
+        return self._hand_out(PoolPyramid(self, (frames, self.insert_row) if in_step else None))
 
     def drop(self, b):
         """Forget sample b's stream: its next keys are all misses."""
@@ -268,9 +347,46 @@ class FramePool:
 class PoolPyramid(_SlotPyramid):
     """(no ``frame_slots`` attribute: that is the by-value ring's mapping; the pool's is ``slot_table``)"""
 
-    def __init__(self, pool):
+    def __init__(self, pool, insert=None):
         super().__init__(pool)
         self.slot_table = pool.slot_table
+        self.insert = insert           # FramePool.step(): (frames list[L] of [B, 6, C, H, W], device int32 [B]) still to be moved into their slots
+
+    def resident(self):
+        """this view without the pending insert: what a captured step may hold (buffers and tables, none of the caller's frames)"""
+        import copy
+        pyr = copy.copy(self)
+        pyr.insert = None
+        return pyr
+
+    def materialise(self):
+        """Enqueue the pending insert on the current stream (sbev_pool_insert, direct sources).  Idempotent -- the same frames go to
+        the same slots -- and a no-op without one.  The decoder does this itself; for callers of ``sample`` outside it."""
+        if self.insert is None:
+            return
+        frames, row = self.insert
+        pool_insert(frames, self.levels, row, self.n_slots, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
 
     def sample(self, loc, w_bp, T, G):
         return ops.msmv_sampling_pool(self.levels, self.B, T, G, self.slot_table, self.n_slots, loc, w_bp)
+
+
+def pool_insert(frames, levels, row, n_slots, stream, table=None, index=None, check=True):
+    """sbev_pool_insert: ``frames`` list[L] of NCHW [B, 6, C, H_l, W_l] into the resident buffers ``levels`` ([B*n_slots*6, H_l, W_l, C] or
+    any view of the same memory), sample b into slot ``row[b]`` (device int32 [B]; outside [0, n_slots): none).  Sources are the frames'
+    own addresses, or -- ``table`` (device pointer table) and ``index`` (list[L]) -- read from the table when the kernel starts; the
+    frames then only give shapes and dtype.  ``check=False`` returns the status instead of raising on it (a caller inside a stream capture
+    has to end the capture first)."""
+    L, f0 = len(frames), frames[0]
+    code = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}[f0.dtype]
+    if len(levels) != L or any(f.dtype != f0.dtype or buf.dtype != f0.dtype for f, buf in zip(frames, levels)):
+        raise RuntimeError('pool insert: frames and slots must have one storage type')
+    src = None if table is not None else (ctypes.c_void_p * L)(*[f.data_ptr() for f in frames])
+    idx = (ctypes.c_int32 * L)(*index) if table is not None else None
+    out = (ctypes.c_void_p * L)(*[buf.data_ptr() for buf in levels])
+    hw = (ctypes.c_int32 * L)(*[f.shape[3] * f.shape[4] for f in frames])
+    st = _lib.load().sbev_pool_insert(table, idx, src, out, L, hw, f0.shape[0], f0.shape[1], f0.shape[2], code, ctypes.c_void_p(row.data_ptr()),
+                                      n_slots, stream)
+    if check:
+        _lib.check(st, 'sbev_pool_insert')
+    return st

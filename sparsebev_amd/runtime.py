@@ -360,11 +360,12 @@ class DecoderRuntime:
 
 
 # What a captured step is keyed on (see StepGraphs): the queries' shapes, StepGraphs._feat_key (shapes of staged levels; addresses and the
-# slot mapping of levels read in place), the mask's shape or None, DecoderRuntime._signature() of the bound weights, the device,
+# slot mapping of levels read in place; the shapes of a frame-pool step's new frames and the address of their insert row), the mask's shape or None, DecoderRuntime._signature() of the bound weights, the device,
 # _switch_key(), layer count and box range, the stream (a graph's workspace belongs to the stream it replays on) and ``finish``
 StepKey = namedtuple('StepKey', 'bbox feat feats mask weights device switches num_layers pc_range stream finish')
-# The tensors of one call whose addresses travel in the step's pointer table (outs: with ``finish`` the call's own (cls, bbox), else None)
-StepInputs = namedtuple('StepInputs', 'bbox feat feats mask outs')
+# The tensors of one call whose addresses travel in the step's pointer table (outs: with ``finish`` the call's own (cls, bbox), else None;
+# frames: the new frames of a frame-pool step (FrameSource.insert's list), else None)
+StepInputs = namedtuple('StepInputs', 'bbox feat feats mask outs frames', defaults=(None,))
 
 
 class CapturedStep:
@@ -489,6 +490,9 @@ class StepGraphs(StepBook):
       * fp32 NCHW feature lists (the reference's layout) go through the in-graph relayout, whose source address also comes from
         the table (sbev_nchw_to_nhwc_f32_indirect) -- any tensors of the same shapes replay the same graph, and the graph pins
         none of the caller's tensors;
+      * the frame pool's streaming step (cache.FramePool.step) brings the batch's newest frames as NCHW maps: one in-graph launch
+        moves them into their slots (sbev_pool_insert), sources from the table, destinations from a device row the pool refreshes
+        with its slot table -- one graph per shape, whichever tensors the backbone hands over;
       * inputs that are read IN PLACE by the decoder kernels -- channels-last lists, FeaturePyramid / the online ring's buffers --
         keep their addresses in the key.  A tensor list is only captured when the SAME tensor objects come back (weak
         references from the first sighting: a recycled address of a dead tensor is not "the same input"), and while
@@ -514,10 +518,13 @@ class StepGraphs(StepBook):
             # their level tensors are views made per call, so there is no object identity to remember: MAX_WASTED bounds a caller
             # that builds a new pyramid over new buffers every step.  The ring's slot order is a by-value kernel argument: its VALUES
             # are part of the key (one graph per ring phase).  The pool's table is device memory the captured step reads on replay:
-            # its ADDRESS is, never its contents (one graph per shape)
+            # its ADDRESS is, never its contents (one graph per shape).  A pool step's pending insert (FramePool.step) adds a launch to
+            # the step: the new frames' shapes and dtype and the ADDRESS of the insert row -- never the frames' addresses (they travel in
+            # the pointer table) nor the row's contents
             table = src.slot_table
+            ins = None if src.insert is None else (tuple((tuple(f.shape), f.dtype) for f in src.insert[0]), src.insert[1].data_ptr())
             return ('pyr', tuple((f.data_ptr(), tuple(f.shape), f.dtype) for f in feats.levels), src.frame_slots, src.n_slots,
-                    None if table is None else (table.data_ptr(), tuple(table.shape))), [], False
+                    None if table is None else (table.data_ptr(), tuple(table.shape)), ins), [], False
         if all(self._relayout_ok(f) for f in feats):
             return ('nchw', tuple((tuple(f.shape), f.dtype) for f in feats)), [], True
         return ('list', tuple((f.data_ptr(), tuple(f.shape), tuple(f.stride()), f.dtype) for f in feats)), list(feats), False
@@ -554,7 +561,7 @@ class StepGraphs(StepBook):
             nl, nc, cs = rt.decoder.num_layers, rt.decoder.decoder_layer.num_classes, rt.decoder.decoder_layer.code_size
             outs = (torch.empty(nl, B, Q, nc, device=query_bbox.device, dtype=torch.float32),
                     torch.empty(nl, B, Q, cs, device=query_bbox.device, dtype=torch.float32))
-        call = StepInputs(query_bbox, query_feat, mlvl_feats, attn_mask, outs)
+        call = StepInputs(query_bbox, query_feat, mlvl_feats, attn_mask, outs, None if src.insert is None else src.insert[0])
         if verdict == CAPTURE:
             e = self._capture(key, call, consts, staged, src)
             if e is None:
@@ -569,12 +576,14 @@ class StepGraphs(StepBook):
     @staticmethod
     def _with_table(packed, n_packed, staged, call):
         """packed per-sample constants + the pointer table of this call (int64 words viewed as fp32 pairs) in ONE upload.
-        Table: 0 query_bbox, 1 query_feat, 2 mask, [3 .. 3 + L) the NCHW levels (staged entries), then -- ``finish`` entries -- the
-        call's output tensors cls, bbox."""
+        Table: 0 query_bbox, 1 query_feat, 2 mask, [3 .. 3 + L) the NCHW levels (staged entries) or the new frames of a frame-pool
+        step (never both: the pool is read in place), then -- ``finish`` entries -- the call's output tensors cls, bbox."""
         import numpy as np
         ptrs = [call.bbox.data_ptr(), call.feat.data_ptr(), call.mask.data_ptr() if call.mask is not None else 0]
         if staged:
             ptrs += [f.data_ptr() for f in call.feats]
+        elif call.frames is not None:
+            ptrs += [f.data_ptr() for f in call.frames]
         if call.outs is not None:
             ptrs += [call.outs[0].data_ptr(), call.outs[1].data_ptr()]
         full = np.empty(n_packed + 2 * len(ptrs), dtype=np.float32)
@@ -595,28 +604,34 @@ class StepGraphs(StepBook):
         pyramid = TR.FeaturePyramid.for_graph(call.feats, staged) if src.kind == 'list' else call.feats
         if pyramid is None:
             return None
+        insert = None
+        if src.insert is not None:           # a frame-pool step: the graph holds the pool's buffers and tables, none of the caller's frames
+            pyramid = pyramid.resident()
+            insert = (list(range(3, 3 + len(call.frames))), call.frames, src.insert[1], pyramid)
         n_packed = (packed.size + 3) // 4 * 4                 # the table behind the constants, 16-byte aligned
         ctx = TR.DecoderContext.from_packed(self._with_table(packed, n_packed, staged, call), layout, ih, iw, dev)     # the graph reads constants AND table from this tensor on every replay
         args, keep, cls, box, ws_key = rt._prepare(qb, qf, pyramid, ctx, mask, own_workspace=True)
         try:
             segs = [(0, qb), (1, qf)] + ([(2, mask)] if mask is not None else [])
             relayout = [(3 + l, buf) for l, buf in enumerate(pyramid.levels)] if staged else []      # (table index, graph-owned NHWC buffer)
-            handle = self._record(args, ctypes.c_void_p(ctx.buffer.data_ptr() + 4 * n_packed), segs, relayout, (cls, box) if call.outs is not None else None)
+            handle = self._record(args, ctypes.c_void_p(ctx.buffer.data_ptr() + 4 * n_packed), segs, relayout, (cls, box) if call.outs is not None else None, insert)
         except BaseException:
             rt._release_graph_ws(ws_key)
             raise
         # what the graph's launches read or write: its own buffers, and -- address-keyed entries only -- the caller's feature buffers
-        graph = DecoderGraph(handle, (keep, qb, qf, mask, ctx, None if staged else (call.feats, pyramid)), cls, box)
+        graph = DecoderGraph(handle, (keep, qb, qf, mask, ctx, None if staged else (None if insert else call.feats, pyramid)), cls, box)
         e = CapturedStep(graph, not staged and not src.resident, staged, ctx.buffer, n_packed, layout, (ih, iw), ws_key)
         self.captured(key, e)
         return e
 
     @staticmethod
-    def _record(args, table, segs, relayout, finish):
+    def _record(args, table, segs, relayout, finish, insert=None):
         """The step's launches under stream capture -> the instantiated graph's handle: the in-graph copies of ``segs`` (table index,
         graph-owned buffer), the relayout of the staged levels (on demand inside the step, all fp32 levels in one launch, or one launch
-        per level), the decoder step, and -- ``finish``: the graph's (cls, box) -- the nan_to_num into the call's own outputs.  Raises
-        when any of it fails, with the capture ended."""
+        per level), -- ``insert``: (table indices, frames giving shapes and dtype, insert row, pool pyramid) -- the frame pool's new frames
+        into their slots (sbev_pool_insert, sources from the table), the decoder step, and -- ``finish``: the graph's (cls, box) -- the
+        nan_to_num into the call's own outputs.  All on the one capture stream, in this order.  Raises when any of it fails, with the
+        capture ended."""
         lib = _lib.load()
         side = torch.cuda.Stream(device=segs[0][1].device)
         side.wait_stream(torch.cuda.current_stream())
@@ -643,6 +658,10 @@ class StepGraphs(StepBook):
                 for (idx, buf), hw in zip(relayout, hws):
                     fn = lib.sbev_nchw_to_nhwc_f32_indirect if buf.dtype == torch.float32 else lib.sbev_nchw_to_nhwc_b16_indirect
                     ok = ok and fn(table, idx, _ptr(buf), n_img, ch, hw, sp) == 0
+            if insert is not None and ok:
+                from . import cache
+                idx, frames, row, pool_pyr = insert
+                ok = cache.pool_insert(frames, pool_pyr.levels, row, pool_pyr.n_slots, sp, table=table, index=idx, check=False) == 0
             if lazy:
                 lz = LazyFeats()
                 lz.table = table
@@ -654,7 +673,7 @@ class StepGraphs(StepBook):
             ok = ok and st_fwd == 0
             if finish is not None:
                 cls, box = finish
-                i_out = 3 + n
+                i_out = 3 + (n if insert is None else len(insert[0]))
                 ok = ok and lib.sbev_finish_outputs_indirect(table, i_out, i_out + 1, _ptr(cls), _ptr(box), cls.numel(), box.numel(), sp) == 0
         finally:
             handle = ctypes.c_void_p()

@@ -552,6 +552,10 @@ class SparseBEVTransformerDecoder(_Base):
                     if _finish:
                         return _Finished(out)
                     return out if _may_alias else (out[0].clone(), out[1].clone())
+        if inference and frame_source(mlvl_feats).insert is not None:
+            # a frame-pool step (cache.FramePool.step) that is not replayed -- first sighting, refused capture, graphs off, launch profiling,
+            # layerwise, DUMP: the new frames go into their slots now, ahead of the eager work (a replayed step does it inside the graph)
+            mlvl_feats.materialise()
         ctx = DecoderContext(img_metas, B, query_bbox.device)
         query_bbox = query_bbox.float().contiguous()
         query_feat = query_feat.float().contiguous()

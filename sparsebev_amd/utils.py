@@ -62,18 +62,21 @@ VERSION = Version()
 class FrameSource(NamedTuple):
     """Where a decoder step's frames live.  ``kind``: 'list' (a feature list, no pyramid object), 'dense' (transformer.FeaturePyramid:
     frame t of sample b is image run b*T + t), 'ring' (cache.RingPyramid: slot ``frame_slots[t]`` of ``n_slots`` for the whole batch,
-    passed to the kernels by value) or 'pool' (cache.PoolPyramid: slot ``slot_table[b, t]`` of ``n_slots``, a device table the kernels read)."""
+    passed to the kernels by value) or 'pool' (cache.PoolPyramid: slot ``slot_table[b, t]`` of ``n_slots``, a device table the kernels read).
+    ``insert`` (the pool only, else None): the step's pending insert ``(frames, insert row)`` -- list[L] of NCHW ``[B, 6, C, H_l, W_l]`` maps
+    the decoder call still has to move into slot ``row[b]`` of sample b (device int32 [B], -1: none) before any frame is read."""
     kind: str
     frame_slots: tuple = ()
     slot_table: object = None
     n_slots: int = 0
+    insert: object = None
 
     @property
     def resident(self):
         return self.kind in ('ring', 'pool')
 
     @classmethod
-    def of(cls, frame_slots=None, slot_table=None, n_slots=0, shape=None, what='the frame pool', plain='dense'):
+    def of(cls, frame_slots=None, slot_table=None, n_slots=0, shape=None, what='the frame pool', plain='dense', insert=None):
         """From the slot mapping itself (the operator layer is handed it as arguments); ``plain``: the kind without one (None: the
         caller means the pool).  With ``shape = (B, T)`` the pool's table is validated -- here and nowhere else."""
         if frame_slots is not None and slot_table is not None:
@@ -88,15 +91,15 @@ class FrameSource(NamedTuple):
                 raise RuntimeError('%s: slot_table must be a contiguous device int32 [B, T] = [%d, %d]' % ((what,) + tuple(shape)))
             if n_slots < 1:
                 raise RuntimeError('%s: n_slots must be at least 1' % what)
-        return cls('pool', (), slot_table, n_slots)
+        return cls('pool', (), slot_table, n_slots, insert)
 
 
 def frame_source(feats, shape=None, what='the frame pool'):
     """The FrameSource of whatever the decoder is handed as features -- the ONE place that looks at the ``levels`` / ``frame_slots`` /
-    ``slot_table`` attributes: ``frame_slots`` marks the ring, ``slot_table`` the pool (both: refused), ``levels`` alone a dense pyramid,
-    none of them a feature list."""
+    ``slot_table`` / ``insert`` attributes: ``frame_slots`` marks the ring, ``slot_table`` the pool (both: refused; ``insert`` is the pool's
+    alone), ``levels`` alone a dense pyramid, none of them a feature list."""
     return FrameSource.of(getattr(feats, 'frame_slots', None), getattr(feats, 'slot_table', None), getattr(feats, 'n_slots', 0), shape, what,
-                          plain='dense' if hasattr(feats, 'levels') else 'list')
+                          plain='dense' if hasattr(feats, 'levels') else 'list', insert=getattr(feats, 'insert', None))
 
 
 def slot_resident(feats):

@@ -2,9 +2,10 @@
 
 Both caches hold the same frames and take ONE new frame (6 NCHW images) per step, as ``bench.py --online`` does; the ring has
 n_slots = T = 8 (one captured graph per ring phase), the pool n_slots = 16 (one captured graph, the step's slot table uploaded into
-the pool's persistent device table).  The two run interleaved on one GPU, round by round, with the warm-up and timing discipline of
-bench.py: warm-up steps first (captures included), device synchronised, wall clock over ``--steps`` steps, device synchronised.
-Prints one JSON line.  Usage: python tools/bench_pool.py [--steps 50] [--warmup 40] [--rounds 3] [--config c2]"""
+the pool's persistent device table).  A third leg feeds a pool of its own through ``FramePool.step``: the new frame goes into its slot
+inside the captured step (sbev_pool_insert) instead of through ``put``'s eager launches in front of it.  The legs run interleaved on one
+GPU, round by round, with the warm-up and timing discipline of bench.py: warm-up steps first (captures included), device synchronised,
+wall clock over ``--steps`` steps, device synchronised.  Prints one JSON line.  Usage: python tools/bench_pool.py [--steps 50] [--warmup 40] [--rounds 3] [--config c2]"""
 import argparse
 import json
 import os
@@ -21,7 +22,7 @@ def parse_args(argv=None):
     ap.add_argument('--config', choices=sorted(CONFIGS), default='c2')
     ap.add_argument('--steps', type=int, default=50, help='timed steps per round and cache')
     ap.add_argument('--warmup', type=int, default=40, help='untimed steps per cache before the first round (the ring captures one graph per phase from its second lap on)')
-    ap.add_argument('--rounds', type=int, default=3, help='interleaved rounds: ring, pool, ring, pool, ...')
+    ap.add_argument('--rounds', type=int, default=3, help='interleaved rounds: ring, pool, pool fed through step(), ring, ...')
     ap.add_argument('--ring-slots', type=int, default=None, help='ring n_slots (default: T)')
     ap.add_argument('--pool-slots', type=int, default=16)
     args = ap.parse_args(argv)
@@ -32,12 +33,18 @@ def parse_args(argv=None):
     return args
 
 
-def summarise(ring_ms, pool_ms):
-    """the JSON line's figures from the per-round step times (ms)"""
+def summarise(ring_ms, pool_ms, pool_step_ms=None):
+    """the JSON line's figures from the per-round step times (ms); ``pool_step_ms``: the leg fed through FramePool.step, compared with
+    the ``put`` leg of the same run"""
     med = lambda v: sorted(v)[len(v) // 2]
     r, p = med(ring_ms), med(pool_ms)
-    return {'ring_ms_per_step': [round(v, 4) for v in ring_ms], 'pool_ms_per_step': [round(v, 4) for v in pool_ms],
-            'ring_median_ms': round(r, 4), 'pool_median_ms': round(p, 4), 'pool_over_ring': round(p / r, 4)}
+    out = {'ring_ms_per_step': [round(v, 4) for v in ring_ms], 'pool_ms_per_step': [round(v, 4) for v in pool_ms],
+           'ring_median_ms': round(r, 4), 'pool_median_ms': round(p, 4), 'pool_over_ring': round(p / r, 4)}
+    if pool_step_ms is not None:
+        s = med(pool_step_ms)
+        out.update({'pool_step_ms_per_step': [round(v, 4) for v in pool_step_ms], 'pool_step_median_ms': round(s, 4),
+                    'pool_step_over_pool': round(s / p, 4)})
+    return out
 
 
 def main(argv=None):
@@ -63,15 +70,16 @@ def main(argv=None):
     bbox, qfeat = [t.to(dev) for t in S.make_queries(B, Q, seed=0)]
     metas = S.make_img_metas(B, T, ih, iw)
 
-    m_ring, m_pool = model(), model()          # one runtime (and graph cache) each
+    m_ring, m_pool, m_step = model(), model(), model()          # one runtime (and graph cache) each
     ring = FrameFeatureCache(T, n_slots=args.ring_slots or T)
-    pool = FramePool(T, n_slots=args.pool_slots)
+    pool, pool_s = FramePool(T, n_slots=args.pool_slots), FramePool(T, n_slots=args.pool_slots)
     for fr in reversed(per_frame):
         ring.push(fr)
-    tick = {'ring': 0, 'pool': T - 1}
+    tick = {'ring': 0, 'pool': T - 1, 'step': T - 1}
     keys0 = [list(range(T - 1, -1, -1))]       # frame number = key; t = 0 newest
-    for b, k in pool.missing(keys0):
-        pool.put(b, k, [f[0] for f in per_frame[T - 1 - k]])
+    for p in (pool, pool_s):
+        for b, k in p.missing(keys0):
+            p.put(b, k, [f[0] for f in per_frame[T - 1 - k]])
 
     def ring_step():
         ring.push(per_frame[tick['ring'] % T])
@@ -86,6 +94,12 @@ def main(argv=None):
             pool.put(b, k, [f[0] for f in per_frame[(n - T) % T]])
         return m_pool(bbox, qfeat, pool.pyramid(keys), None, metas)
 
+    def pool_step_step():
+        tick['step'] += 1
+        n = tick['step']
+        keys = [[n - t for t in range(T)]]
+        return m_step(bbox, qfeat, pool_s.step(keys, per_frame[(n - T) % T]), None, metas)      # the new frame goes in inside the step
+
     def timed(step):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -97,17 +111,19 @@ def main(argv=None):
     for _ in range(args.warmup):
         ring_step()
         pool_step()
-    ring_ms, pool_ms = [], []
+        pool_step_step()
+    ring_ms, pool_ms, step_ms = [], [], []
     for _ in range(args.rounds):
         ring_ms.append(timed(ring_step))
         pool_ms.append(timed(pool_step))
+        step_ms.append(timed(pool_step_step))
     runtime.check_pair_faults()
     g = {name: {'captures': m.decoder._runtime.step_graphs.captures, 'replays': m.decoder._runtime.step_graphs.replays}
-         for name, m in (('ring', m_ring), ('pool', m_pool))}
+         for name, m in (('ring', m_ring), ('pool', m_pool), ('pool_step', m_step))}
     out = {'metric': 'streaming decoder step, frame pool vs frame ring', 'config': args.config, 'B': B, 'Q': Q, 'T': T, 'pyramid': pyr,
            'ring_slots': ring.n_slots, 'pool_slots': pool.n_slots, 'steps': args.steps, 'warmup': args.warmup, 'rounds': args.rounds,
            'graphs': g, 'device': torch.cuda.get_device_name(0)}
-    out.update(summarise(ring_ms, pool_ms))
+    out.update(summarise(ring_ms, pool_ms, step_ms))
     print(json.dumps(out))
     return out
 
