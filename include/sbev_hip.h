@@ -937,6 +937,28 @@ int sbev_profile_stride(int every_n_calls);
 int sbev_profile_read(int kind, float* ms, int max_n);
 
 /*
+ * The same insert for a step that brings SEVERAL frames per sample, in the memory the backbone emits: one launch for n_frames frame sets x
+ * n_levels levels x B samples.  Source (k, l) -- frame set k of the step's offered window positions, level l -- is src[k * n_levels + l]
+ * (table == NULL) or table[index[k * n_levels + l]] read on the device when the kernel starts (src == NULL); exactly one of the two forms,
+ * 1 <= n_frames <= SBEV_MAX_FRAMES.  src_layout (enum sbev_frames_layout), one value per call: SBEV_FRAMES_NCHW = [B, n_views, channels,
+ * hw_pixels[l]], SBEV_FRAMES_NHWC = channels-last [B, n_views, hw_pixels[l], channels].  insert is a device int32 [n_frames, B]: sample b's
+ * frame of set k goes to slot insert[k * B + b] of out[l] = [B, n_slots, n_views, hw_pixels[l], channels]; an entry outside [0, n_slots) --
+ * use -1 -- means none: nothing of that (k, b) is read or written.  Entries are NOT clamped: this launch writes.  Two live entries of one
+ * sample must name DIFFERENT slots -- the host planner's duty (cache.SlotBook.plan_frames); the kernel cannot check it, and two frame
+ * sets writing one slot race.  src_dtype -> dst_dtype (enum sbev_dtype): fp32 -> fp32; fp16 -> fp16 and bf16 -> bf16, moved as bytes;
+ * fp16 -> fp32 and bf16 -> fp32, widened exactly.  Everything else is SBEV_EINVAL: fp32 into 2-byte slots would be lossy, as would fp16
+ * into bf16.  Any sizes: per level the vector form where hw and channels allow it (NCHW: hw % 4 == 0 and channels % 4 == 0, % 8 for a
+ * 2-byte source; channels-last: one sample's n_views * hw * channels source bytes a multiple of 16), else a scalar form.  Sources and
+ * destinations 16-byte aligned.  B == 0 is an empty call.
+ * Replaces: the reference's per-frame extract-then-cat (models/sparsebev.py:255-321) for every missing frame of a window, and this library's
+ *           own B x L eager sbev_nchw_to_nhwc_* / sbev_copy_widen_f32 launches in front of a replayed step.
+ */
+enum sbev_frames_layout { SBEV_FRAMES_NCHW = 0, SBEV_FRAMES_NHWC = 1 };
+int sbev_pool_insert_frames(const void* const* table, const int32_t* index, const void* const* src, void* const* out, int n_frames,
+                            int n_levels, const int32_t* hw_pixels, int B, int n_views, int channels, int src_layout, int src_dtype,
+                            int dst_dtype, const int32_t* insert, int n_slots, sbev_stream_t stream);
+
+/*
  * The keyed frame pool's insert: a step's NEW frames into their slots, in one launch for all levels and samples, recordable inside a
  * captured step.  Source level l is the backbone's NCHW map [B, n_views, channels, hw_pixels[l]] for the batch's newest images -- given
  * as src[l] (table == NULL), or as table[index[l]] read on the device when the kernel starts (src == NULL; the device pointer table of a

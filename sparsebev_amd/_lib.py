@@ -231,6 +231,8 @@ SIGNATURES = {
     'sbev_sasa_bwd_f32_ds': (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.POINTER(ctypes.c_double), _vp, _vp, _vp, _vp, _vp,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_uint64, _vp, _vp]),
     'sbev_dropout_f32_ds': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_uint64, _vp, ctypes.c_float, _vp]),
+    'sbev_pool_insert_frames': (ctypes.c_int, [_vp, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, _c_i32p, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp]),
     'sbev_pool_insert': (ctypes.c_int, [_vp, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp]),
 }

@@ -17,6 +17,7 @@ import ctypes
 import torch
 
 from . import _lib, ops
+from .utils import FrameInsert
 
 N_VIEWS = 6
 
@@ -219,6 +220,36 @@ class SlotBook:
             self.B, self.slots, self.needed = saved
             raise
 
+    def plan_frames(self, keys, offered):
+        """(rows, insert) of a streaming step that brings the frames of the window positions ``offered`` (any iterable of t; the caller
+        has frame ``keys[b][t]`` for every sample at each of them): the step's [B][T] slot table (as ``table``) and ``insert[k][b]`` for
+        the offered positions in ascending t -- the slot that receives sample b's frame of position k, or -1.  A key that is missing and
+        offered gets a slot by ``assign``'s rules, at the lowest offered t that carries it and nowhere else (a key at several positions
+        is inserted once), in the order ``missing`` lists them; everything else is -1, so two live entries of one sample never share a
+        slot and no key the step needs is evicted.  A missing key that is not offered raises the KeyError of ``table``; any exception
+        leaves the book as it was."""
+        saved = (self.B, {b: dict(m) for b, m in self.slots.items()}, {b: list(k) for b, k in self.needed.items()})
+        try:
+            keys = self._announce(keys)
+            ts = sorted(set(offered))
+            if not ts or not all(isinstance(t, int) and 0 <= t < self.T for t in ts):
+                raise ValueError('offered window positions must be integers in [0, %d), at least one (got %r)' % (self.T, ts))
+            insert = [[-1] * self.B for _ in ts]
+            for b, row in enumerate(keys):
+                mine = self.slots.get(b, {})
+                absent = [k for k in self.needed[b] if k not in mine]
+                first = {k: next((i for i, t in enumerate(ts) if row[t] == k), None) for k in absent}
+                late = [k for k in absent if first[k] is None]
+                if late:
+                    raise KeyError('sample %d: frame %r is not in the pool and none of the offered positions %r carries it (missing(keys) lists what to put() first)'
+                                   % (b, late[0], ts))
+                for k in absent:
+                    insert[first[k]][b] = self.assign(b, k)[0]
+            return self.table(keys), insert
+        except BaseException:
+            self.B, self.slots, self.needed = saved
+            raise
+
     def drop(self, b):
         """Forget sample b's stream (its slots are free again)."""
         self.slots.pop(b, None)
@@ -235,7 +266,9 @@ class FramePool:
 
     The streaming step -- one new frame per sample, the window's newest -- is ``step(keys, frames)`` instead: the frames are not stored
     by launches of this call but travel with the returned pyramid, and the decoder call moves them into their slots itself
-    (``sbev_pool_insert``, destinations read from a device row behind the slot table): inside the captured step when it is replayed."""
+    (``sbev_pool_insert``, destinations read from a device row behind the slot table): inside the captured step when it is replayed.
+    ``stream(keys, frames)`` is the same for as many frames as the step lacks -- the scene's first window included -- in the memory the
+    backbone emits: NCHW or channels-last, 2-byte frames widened into fp32 slots (``sbev_pool_insert_frames``, still one launch)."""
 
     def __init__(self, num_frames, n_slots=16, dtype=torch.float32):
         if dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -247,6 +280,7 @@ class FramePool:
         self.slot_table = None         # device int32 [B, T]: allocated once with the buffers, refreshed in place per pyramid() / step()
         self.insert_row = None         # device int32 [B] behind it in the same allocation (``_tables``): step()'s slot per sample, -1 = none
         self._tables = None
+        self._rows = None              # the whole allocation: slot table, then T rows of [B] for stream() (row 0 = ``insert_row``)
         self._live = None              # the pyramid handed out last: the next pyramid() / step() ends its validity
 
     @property
@@ -279,10 +313,12 @@ class FramePool:
         """buffers for levels of (C, H, W) and the two tables in ONE int32 allocation: [B, T] slot table, then the [B] insert row"""
         B = self.book.B
         self.buffers = [torch.empty(B, self.n_slots, N_VIEWS, h, w, c, device=device, dtype=self.dtype) for c, h, w in chw]
-        self._tables = torch.zeros(B * self.T + B, device=device, dtype=torch.int32)
+        # (stream()'s [K, B] rows, K <= T, start where the insert row does: row 0 IS the insert row, rows 1 .. T - 1 lie behind it)
+        self._rows = torch.full((B * self.T + self.T * B,), -1, device=device, dtype=torch.int32)
+        self._rows[:B * self.T] = 0
+        self._tables = self._rows[:B * self.T + B]
         self.slot_table = self._tables[:B * self.T].view(B, self.T)
         self.insert_row = self._tables[B * self.T:]
-        self.insert_row.fill_(-1)
 
     def _hand_out(self, pyr):
         if self._live is not None:
@@ -339,6 +375,58 @@ class FramePool:
         _upload(np.asarray([s for row in rows for s in row] + insert, dtype=np.int32), self._tables.device, out=self._tables)
         return self._hand_out(PoolPyramid(self, (frames, self.insert_row) if in_step else None))
 
+    def _frames_layout(self, flat):
+        """what sbev_pool_insert_frames takes: frames of one type -- the slots' own, or fp16 / bf16 for fp32 slots -- in one layout, NCHW-
+        contiguous (False) or channels-last (True) memory, 16-byte aligned.  None: not taken (misaligned or non-contiguous memory, mixed
+        layouts or types, fp32 for 2-byte slots): those are _store_level's, which refuses what nothing here stores."""
+        dt = flat[0].dtype
+        if any(f.dtype != dt or f.data_ptr() % 16 for f in flat) or not (dt == self.dtype or (self.dtype == torch.float32 and dt in (torch.float16, torch.bfloat16))):
+            return None
+        if all(f.is_contiguous() for f in flat):
+            return False
+        if all(f.permute(0, 1, 3, 4, 2).is_contiguous() for f in flat):
+            return True
+        return None
+
+    def stream(self, keys, frames):
+        """One streaming step that takes the frames as the backbone emits them, as many as the step lacks: ``frames`` maps a window
+        position t to a list[L] of [B, 6, C, H_l, W_l] device tensors -- the batch's frames ``keys[b][t]`` -- NCHW-contiguous or channels-
+        last memory, fp32 / fp16 / bf16 (2-byte frames for fp32 slots are widened exactly), one layout and type per call.  Every key of
+        the step that is not resident must be at one of the given positions (SlotBook.plan_frames).  Slot table and the [K, B] destination
+        rows (K = len(frames), ascending t; row 0 at ``insert_row``'s address) go up in one upload; the returned PoolPyramid carries a
+        ``FrameInsert``: the decoder call it is handed to moves the frames into their slots in ONE launch (sbev_pool_insert_frames, inside
+        the captured step when that is replayed; PoolPyramid.materialise() for other readers).  The pyramid keeps the frames alive until
+        the next stream() / step() / pyramid(), which also ends its validity.  Frames the kernel does not take (_frames_layout) are stored
+        here and now as put() stores them, and the pyramid carries no insert; what put() refuses raises here too."""
+        import numpy as np
+        from .transformer import _upload
+        keys = [list(row) for row in keys]
+        ts = sorted(frames)
+        sets = [list(frames[t]) for t in ts]
+        flat = [f for fs in sets for f in fs]
+        if not flat or not all(torch.is_tensor(f) and f.is_cuda and f.dim() == 5 and f.shape[1] == N_VIEWS and f.shape[0] == len(keys) for f in flat):
+            raise RuntimeError('frame features must be device tensors [B, 6, C, H, W], B = %d' % len(keys))
+        chw = [tuple(f.shape[2:]) for f in sets[0]]
+        if any([tuple(f.shape[2:]) for f in fs] != chw for fs in sets) or (self.buffers is not None and (
+                len(chw) != len(self.buffers) or any(tuple(buf.shape[3:]) != (h, w, c) for (c, h, w), buf in zip(chw, self.buffers)))):
+            raise RuntimeError('frame features do not match the pool\'s levels')
+        rows, insert = self.book.plan_frames(keys, ts)
+        if self.buffers is None:
+            self._alloc(chw, flat[0].device)
+        nhwc = self._frames_layout(flat)
+        if nhwc is None:
+            for fs, row in zip(sets, insert):
+                for b, slot in enumerate(row):
+                    if slot >= 0:
+                        for f, buf in zip(fs, self.buffers):
+                            _store_level(f[b:b + 1], [buf[b, slot]], self.dtype)
+            insert = [[-1] * len(row) for row in insert]
+        B, K = len(keys), len(ts)
+        up = self._rows[:B * self.T + K * B]
+        _upload(np.asarray([s for row in rows for s in row] + [s for row in insert for s in row], dtype=np.int32), up.device, out=up)
+        pending = None if nhwc is None else FrameInsert(flat, up[B * self.T:].view(K, B), nhwc)
+        return self._hand_out(PoolPyramid(self, pending))
+
     def drop(self, b):
         """Forget sample b's stream: its next keys are all misses."""
         self.book.drop(b)
@@ -350,7 +438,7 @@ class PoolPyramid(_SlotPyramid):
     def __init__(self, pool, insert=None):
         super().__init__(pool)
         self.slot_table = pool.slot_table
-        self.insert = insert           # FramePool.step(): (frames list[L] of [B, 6, C, H, W], device int32 [B]) still to be moved into their slots
+        self.insert = insert           # FramePool.step(): (frames list[L] of [B, 6, C, H, W], device int32 [B]) still to be moved into their slots; stream(): a FrameInsert
 
     def resident(self):
         """this view without the pending insert: what a captured step may hold (buffers and tables, none of the caller's frames)"""
@@ -360,12 +448,11 @@ class PoolPyramid(_SlotPyramid):
         return pyr
 
     def materialise(self):
-        """Enqueue the pending insert on the current stream (sbev_pool_insert, direct sources).  Idempotent -- the same frames go to
+        """Enqueue the pending insert on the current stream (sbev_pool_insert / sbev_pool_insert_frames, direct sources).  Idempotent -- the same frames go to
         the same slots -- and a no-op without one.  The decoder does this itself; for callers of ``sample`` outside it."""
         if self.insert is None:
             return
-        frames, row = self.insert
-        pool_insert(frames, self.levels, row, self.n_slots, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        enqueue_insert(self.insert, self.levels, self.n_slots, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
 
     def sample(self, loc, w_bp, T, G):
         return ops.msmv_sampling_pool(self.levels, self.B, T, G, self.slot_table, self.n_slots, loc, w_bp)
@@ -390,3 +477,35 @@ def pool_insert(frames, levels, row, n_slots, stream, table=None, index=None, ch
     if check:
         _lib.check(st, 'sbev_pool_insert')
     return st
+
+
+def pool_insert_frames(frames, levels, rows, n_slots, stream, nhwc=False, table=None, index=None, check=True):
+    """sbev_pool_insert_frames: ``frames`` = K * L tensors [B, 6, C, H_l, W_l] (frame set k's levels at [k * L, (k + 1) * L)), all NCHW-
+    contiguous or -- ``nhwc`` -- all channels-last memory, of one type, into the resident buffers ``levels``: sample b's frame of set k into
+    slot ``rows[k, b]`` (device int32 [K, B]; outside [0, n_slots): none; two live entries of one sample must differ, SlotBook.plan_frames
+    sees to it).  fp16 / bf16 frames into fp32 buffers are widened.  Sources, ``table`` / ``index`` (K * L entries) and ``check`` as for
+    pool_insert."""
+    L, f0 = len(levels), frames[0]
+    K = rows.shape[0]
+    codes = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+    if len(frames) != K * L or any(f.dtype != f0.dtype for f in frames) or any(buf.dtype != levels[0].dtype for buf in levels):
+        raise RuntimeError('pool insert: K * L frames of one type into L levels of one storage type')
+    n = K * L
+    src = None if table is not None else (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
+    idx = (ctypes.c_int32 * n)(*index) if table is not None else None
+    out = (ctypes.c_void_p * L)(*[buf.data_ptr() for buf in levels])
+    hw = (ctypes.c_int32 * L)(*[f.shape[3] * f.shape[4] for f in frames[:L]])
+    st = _lib.load().sbev_pool_insert_frames(table, idx, src, out, K, L, hw, f0.shape[0], f0.shape[1], f0.shape[2], 1 if nhwc else 0, codes[f0.dtype],
+                                             codes[levels[0].dtype], ctypes.c_void_p(rows.data_ptr()), n_slots, stream)
+    if check:
+        _lib.check(st, 'sbev_pool_insert_frames')
+    return st
+
+
+def enqueue_insert(insert, levels, n_slots, stream, table=None, index=None, check=True):
+    """A pyramid's pending insert as its one launch: FramePool.step's pair through pool_insert, FramePool.stream's FrameInsert through
+    pool_insert_frames.  The one place that tells them apart (PoolPyramid.materialise and the captured step both come here)."""
+    if isinstance(insert, FrameInsert):
+        return pool_insert_frames(insert.frames, levels, insert.rows, n_slots, stream, insert.nhwc, table, index, check)
+    frames, row = insert
+    return pool_insert(frames, levels, row, n_slots, stream, table, index, check)

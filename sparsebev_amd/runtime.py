@@ -9,7 +9,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from .utils import frame_source
+from .utils import FrameInsert, frame_source
 
 MAX_LEVELS = 5
 GEMM_F32, GEMM_BF16X3, GEMM_BF16X6, GEMM_BF16X3S, GEMM_F16X3, GEMM_F16X4 = 0, 1, 2, 3, 4, 5      # sbev_gemm_mode
@@ -492,7 +492,9 @@ class StepGraphs(StepBook):
         none of the caller's tensors;
       * the frame pool's streaming step (cache.FramePool.step) brings the batch's newest frames as NCHW maps: one in-graph launch
         moves them into their slots (sbev_pool_insert), sources from the table, destinations from a device row the pool refreshes
-        with its slot table -- one graph per shape, whichever tensors the backbone hands over;
+        with its slot table -- one graph per shape, whichever tensors the backbone hands over; FramePool.stream brings K frames per
+        sample, NCHW or channels-last, 2-byte ones widened (sbev_pool_insert_frames, K * L table entries, [K, B] rows): one graph per
+        offered shape -- typically one for K = 1 and one for a scene's first window;
       * inputs that are read IN PLACE by the decoder kernels -- channels-last lists, FeaturePyramid / the online ring's buffers --
         keep their addresses in the key.  A tensor list is only captured when the SAME tensor objects come back (weak
         references from the first sighting: a recycled address of a dead tensor is not "the same input"), and while
@@ -522,7 +524,9 @@ class StepGraphs(StepBook):
             # the step: the new frames' shapes and dtype and the ADDRESS of the insert row -- never the frames' addresses (they travel in
             # the pointer table) nor the row's contents
             table = src.slot_table
-            ins = None if src.insert is None else (tuple((tuple(f.shape), f.dtype) for f in src.insert[0]), src.insert[1].data_ptr())
+            # (FramePool.stream's FrameInsert: K and the layout too -- with every frame's shape and dtype that is all the launch depends on)
+            ins = None if src.insert is None else (tuple((tuple(f.shape), f.dtype) for f in src.insert[0]), src.insert[1].data_ptr()) + (
+                (src.insert.K, src.insert.nhwc) if isinstance(src.insert, FrameInsert) else ())
             return ('pyr', tuple((f.data_ptr(), tuple(f.shape), f.dtype) for f in feats.levels), src.frame_slots, src.n_slots,
                     None if table is None else (table.data_ptr(), tuple(table.shape)), ins), [], False
         if all(self._relayout_ok(f) for f in feats):
@@ -577,7 +581,9 @@ class StepGraphs(StepBook):
     def _with_table(packed, n_packed, staged, call):
         """packed per-sample constants + the pointer table of this call (int64 words viewed as fp32 pairs) in ONE upload.
         Table: 0 query_bbox, 1 query_feat, 2 mask, [3 .. 3 + L) the NCHW levels (staged entries) or the new frames of a frame-pool
-        step (never both: the pool is read in place), then -- ``finish`` entries -- the call's output tensors cls, bbox."""
+        step (never both: the pool is read in place; FramePool.stream brings K * L of them, set k's levels at [3 + k * L, 3 + (k + 1) * L)),
+        then -- ``finish`` entries -- the call's output tensors cls, bbox.  The table is as long as the call needs: a step's buffer is
+        allocated at capture for its own K."""
         import numpy as np
         ptrs = [call.bbox.data_ptr(), call.feat.data_ptr(), call.mask.data_ptr() if call.mask is not None else 0]
         if staged:
@@ -607,7 +613,7 @@ class StepGraphs(StepBook):
         insert = None
         if src.insert is not None:           # a frame-pool step: the graph holds the pool's buffers and tables, none of the caller's frames
             pyramid = pyramid.resident()
-            insert = (list(range(3, 3 + len(call.frames))), call.frames, src.insert[1], pyramid)
+            insert = (list(range(3, 3 + len(call.frames))), src.insert, pyramid)
         n_packed = (packed.size + 3) // 4 * 4                 # the table behind the constants, 16-byte aligned
         ctx = TR.DecoderContext.from_packed(self._with_table(packed, n_packed, staged, call), layout, ih, iw, dev)     # the graph reads constants AND table from this tensor on every replay
         args, keep, cls, box, ws_key = rt._prepare(qb, qf, pyramid, ctx, mask, own_workspace=True)
@@ -628,8 +634,8 @@ class StepGraphs(StepBook):
     def _record(args, table, segs, relayout, finish, insert=None):
         """The step's launches under stream capture -> the instantiated graph's handle: the in-graph copies of ``segs`` (table index,
         graph-owned buffer), the relayout of the staged levels (on demand inside the step, all fp32 levels in one launch, or one launch
-        per level), -- ``insert``: (table indices, frames giving shapes and dtype, insert row, pool pyramid) -- the frame pool's new frames
-        into their slots (sbev_pool_insert, sources from the table), the decoder step, and -- ``finish``: the graph's (cls, box) -- the
+        per level), -- ``insert``: (table indices, the pyramid's pending insert: shapes, dtype, layout and rows, pool pyramid) -- the frame pool's new frames
+        into their slots (sbev_pool_insert / sbev_pool_insert_frames, sources from the table), the decoder step, and -- ``finish``: the graph's (cls, box) -- the
         nan_to_num into the call's own outputs.  All on the one capture stream, in this order.  Raises when any of it fails, with the
         capture ended."""
         lib = _lib.load()
@@ -660,8 +666,8 @@ class StepGraphs(StepBook):
                     ok = ok and fn(table, idx, _ptr(buf), n_img, ch, hw, sp) == 0
             if insert is not None and ok:
                 from . import cache
-                idx, frames, row, pool_pyr = insert
-                ok = cache.pool_insert(frames, pool_pyr.levels, row, pool_pyr.n_slots, sp, table=table, index=idx, check=False) == 0
+                idx, pending, pool_pyr = insert
+                ok = cache.enqueue_insert(pending, pool_pyr.levels, pool_pyr.n_slots, sp, table=table, index=idx, check=False) == 0
             if lazy:
                 lz = LazyFeats()
                 lz.table = table
