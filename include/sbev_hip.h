@@ -885,6 +885,33 @@ int sbev_decoder_forward_lazy(const sbev_decoder_config* cfg, const sbev_decoder
                               const float* time_diff, const float* lidar2img, const float* vel_div,
                               const uint8_t* attn_mask, float* cls_out, float* bbox_out,
                               void* workspace, int64_t workspace_bytes, sbev_stream_t stream);
+/*
+ * Prefix cache.  Three launches of layer 0 -- the position encoder + attention in-projection, the self attention and the parameter
+ * generator GEMM -- read the queries and the weights and nothing of the frame.  The reference builds the queries from two weight tensors
+ * on every call at eval (models/sparsebev_head.py:126-127, 217-218), so in real use they repeat bit for bit, in freshly allocated tensors.
+ * sbev_decoder_forward_cached is sbev_decoder_forward (lazy == NULL) / sbev_decoder_forward_lazy with `cache`: device memory of the
+ * caller's, 256-byte aligned, >= sbev_prefix_cache_bytes(cfg) bytes, NOT part of the workspace (workspaces may be shared between steps
+ * with other queries).  A first launch of the step compares this call's queries with the copy in the cache, 16 bytes at a time as
+ * integers, and refreshes the copy; where nothing differed the three launches return at once and the step reads their results of the
+ * step that stored them.  Outputs are bit-identical either way.  The cache is used only on row-chain steps with the weight-stationary
+ * generator, without attn_mask, without launch profiling and with 16-byte aligned queries (sbev_decoder_prefix_planned); on any other
+ * step it is not touched at all, so its contents always belong to the stored query copy.
+ * Layout: 32-bit words 0..3 are `armed`, `force`, `hits`, `misses`; the rest is private to the library.  The caller zeroes `armed`
+ * (with the device idle on the cache, or in stream order) before the first use and whenever ANYTHING but the queries and the frame changes
+ * under the same cache: weights, config, gemm mode, switches, pc_range, stream -- the next step then recomputes whatever the rest holds.
+ * `force` != 0 makes every step recompute (the uncached step with the same launches); `hits` / `misses` count the steps that skipped /
+ * recomputed.  cache == NULL: exactly sbev_decoder_forward / _lazy.  sbev_prefix_cache_bytes: -1 on an invalid config.
+ */
+int64_t sbev_prefix_cache_bytes(const sbev_decoder_config* cfg);
+int sbev_decoder_forward_cached(const sbev_decoder_config* cfg, const sbev_decoder_weights* weights, void* const* feats_nhwc,
+                                const sbev_lazy_feats* lazy, const float* query_bbox, const float* query_feat,
+                                const float* time_diff, const float* lidar2img, const float* vel_div,
+                                const uint8_t* attn_mask, float* cls_out, float* bbox_out,
+                                void* workspace, int64_t workspace_bytes, sbev_stream_t stream, void* cache, int64_t cache_bytes);
+/* Whether a step of this config / weight set under the current switches and profiling state would use a cache, given that one is passed
+ * (cache_given), a mask is (mask_given) and the on-demand relayout is (lazy_given).  Pure host function; -1 on an invalid config. */
+int sbev_decoder_prefix_planned(const sbev_decoder_config* cfg, const sbev_decoder_weights* weights, int cache_given, int mask_given,
+                                int lazy_given);
 /* The pieces, for callers that run the layers themselves: tiles of a pyramid (one 4-byte word of `need` and of `done` each; -1: shape not
  * covered); the marking form of sbev_sample_and_project (hw: [L][2] = (H_l, W_l); byte g of a tile's `need` word := 1 when a point of
  * group g reads one of its pixels); the move (first != 0: the step's first launch -- one workgroup per tile, `done` rebuilt from `need`;

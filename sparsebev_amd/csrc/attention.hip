@@ -47,6 +47,7 @@ struct AttnArgs {
     float* out;                 // [B, Q, H*HD]
     int B, Q, H, ld;
     float scale;                // 1/sqrt(HD)
+    const unsigned* skip_hdr;   // layer 0 of a step with a prefix cache (sbev_common.hpp: prefix_clean; no mask), else null
 };
 
 // All-reduce over the 4 lanes {fi, fi + 16, fi + 32, fi + 48} that hold one query's keys, without LDS: v_permlane32_swap(x, x) leaves
@@ -88,6 +89,9 @@ __global__ __launch_bounds__(64 * NWAVES) void sasa_kernel(const AttnArgs a) {
     __shared__ __attribute__((aligned(16))) float Vs[2 * KS * HD * LDV];
     __shared__ __attribute__((aligned(16))) float Cs[2 * KS * KT * 2];
 
+    if constexpr (!MASK) {      // prefix cache: the queries repeat bit for bit -> the attention output of the step that stored them stands
+        if (a.skip_hdr && sbev::prefix_clean(a.skip_hdr)) return;
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     SASA_STAMP(0)
@@ -318,6 +322,12 @@ __global__ __launch_bounds__(256) void refine_kernel(const MiscArgs a) { refine_
 
 extern "C" int sbev_sasa_f32(const float* qkvt, int64_t ld, const float* query_bbox, const double* pc_range,
                              const uint8_t* mask, float* out, int B, int Q, int H, int head_dim, sbev_stream_t stream) {
+    return sbev::launch_sasa(qkvt, ld, query_bbox, pc_range, mask, out, B, Q, H, head_dim, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sbev::launch_sasa(const float* qkvt, int64_t ld, const float* query_bbox, const double* pc_range, const uint8_t* mask, float* out, int B,
+                      int Q, int H, int head_dim, const uint32_t* skip_hdr, hipStream_t s) {
+    SBEV_REQUIRE(!(mask && skip_hdr), "sbev_sasa_f32: a masked call cannot skip");
     SBEV_REQUIRE(B >= 0 && Q >= 0 && H >= 1, "sbev_sasa_f32: bad sizes");
     SBEV_REQUIRE(head_dim == HD, "sbev_sasa_f32: built for head_dim 32 (got %d)", head_dim);
     SBEV_REQUIRE(ld >= 3 * H * HD + H && ld % 4 == 0, "sbev_sasa_f32: row stride %lld must be >= 3*H*32 + H and a multiple of 4", (long long)ld);
@@ -325,7 +335,7 @@ extern "C" int sbev_sasa_f32(const float* qkvt, int64_t ld, const float* query_b
     SBEV_REQUIRE(qkvt && query_bbox && pc_range && out, "sbev_sasa_f32: null pointer");
     SBEV_REQUIRE((((uintptr_t)qkvt) & 15) == 0 && (((uintptr_t)query_bbox) & 7) == 0, "sbev_sasa_f32: qkvt must be 16-byte, query_bbox 8-byte aligned");
     AttnArgs a{};
-    a.qkvt = qkvt; a.bbox = query_bbox; a.mask = mask; a.out = out;
+    a.qkvt = qkvt; a.bbox = query_bbox; a.mask = mask; a.out = out; a.skip_hdr = skip_hdr;
     a.B = B; a.Q = Q; a.H = H; a.ld = (int)ld; a.scale = 1.0f / sqrtf((float)HD);
     for (int i = 0; i < 2; ++i) {           // decode_bbox: python-float scalars cast to fp32 (models/bbox/utils.py:69-70)
         a.lo[i] = (float)pc_range[i];
@@ -333,7 +343,6 @@ extern "C" int sbev_sasa_f32(const float* qkvt, int64_t ld, const float* query_b
     }
     const long long blocks = (long long)B * H * ((Q + 16 * NQ - 1) / (16 * NQ));
     SBEV_REQUIRE(blocks <= 0x7fffffffLL, "sbev_sasa_f32: too many blocks");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (mask)
         hipLaunchKernelGGL(sasa_kernel<true>, dim3((unsigned)blocks), dim3(64 * NWAVES), 0, s, a);
     else

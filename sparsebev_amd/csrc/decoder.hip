@@ -90,6 +90,67 @@ Buffers carve(const sbev_decoder_config& c, void* ws) {
     return b;
 }
 
+// Prefix cache (include/sbev_hip.h: sbev_decoder_forward_cached): the caller's block as this file lays it out.  The header's first four
+// words are public (armed, force, hits, misses), then PFX_NW dirty words; the copies of the queries the rest was computed from; FRONT's x,
+// layer 0's attention output and layer 0's generated parameters.
+struct Prefix {
+    uint32_t* hdr;
+    float *qb, *qf, *x0, *att0, *params0;
+    size_t bytes;
+};
+Prefix carve_prefix(const sbev_decoder_config& c, void* cache) {
+    Carver k(cache);
+    const size_t BQ = (size_t)c.B * c.Q, D = c.D;
+    const int Cg = c.D / c.G, Pin = c.T * c.P;
+    Prefix f{};
+    f.hdr = reinterpret_cast<uint32_t*>(k.take(sbev::PFX_DIRTY + sbev::PFX_NW));
+    f.qb = k.take(BQ * 10);
+    f.qf = k.take(BQ * D);
+    f.x0 = k.take(BQ * D);
+    f.att0 = k.take(BQ * D);
+    f.params0 = k.take(BQ * (size_t)c.G * (Cg * Cg + Pin * c.out_points));
+    f.bytes = k.off;
+    return f;
+}
+
+// The step's first launch when it has a prefix cache: PFX_NW workgroups compare this call's queries with the stored copy, 16 bytes at a
+// time as integers (a NaN that repeats bit for bit is a repeat), and store a chunk that differs into the copy.  Every workgroup then
+// writes its own dirty word -- every slot is rewritten every step: no reset launch, no atomics -- and workgroup 0 arms the cache AFTER
+// it has read `armed`, so the first step after the caller zeroed the header is always dirty.
+struct WatchArgs {
+    const uint32_t* q[2];        // this call's query_bbox [BQ * 10 words], query_feat [BQ * D words]
+    uint32_t* copy[2];
+    uint32_t words[2];
+    uint32_t* hdr;
+};
+__global__ __launch_bounds__(256) void prefix_watch_kernel(const WatchArgs a) {
+    const uint32_t armed = a.hdr[sbev::PFX_ARMED], force = a.hdr[sbev::PFX_FORCE];
+    uint32_t differed = 0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const uint4* q = reinterpret_cast<const uint4*>(a.q[s]);
+        uint4* cp = reinterpret_cast<uint4*>(a.copy[s]);
+        const uint32_t n16 = a.words[s] / 4;
+        for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n16; i += sbev::PFX_NW * 256u) {
+            const uint4 v = q[i], o = cp[i];
+            if (((v.x ^ o.x) | (v.y ^ o.y)) | ((v.z ^ o.z) | (v.w ^ o.w))) {
+                cp[i] = v;
+                differed = 1;
+            }
+        }
+        const uint32_t t = 4 * n16 + threadIdx.x;      // an odd number of rows of 10 words leaves 2 words behind the last chunk
+        if (blockIdx.x == 0 && t < a.words[s] && a.q[s][t] != a.copy[s][t]) {
+            a.copy[s][t] = a.q[s][t];
+            differed = 1;
+        }
+    }
+    const int any = __syncthreads_or((int)differed);
+    if (threadIdx.x == 0) {
+        a.hdr[sbev::PFX_DIRTY + blockIdx.x] = (any != 0 || armed == 0 || force != 0) ? 1u : 0u;
+        if (blockIdx.x == 0) a.hdr[sbev::PFX_ARMED] = 1u;
+    }
+}
+
 // gather + mixing in one launch (sbev_sample_mix_f32) where supported; sbev_decoder_fuse_sample_mix(0) restores the two
 // launches (A/B measurements; results are bit-identical)
 std::atomic<int> g_fuse_sample_mix{1};
@@ -177,6 +238,8 @@ struct ConfigPyramid {
 
 }  // namespace
 
+static bool launch_profiling_on();      // sbev_profile_sampler's mask != 0 (below)
+
 namespace sbev {
 struct ProfCallScope {      // see sbev_profile_stride below
     bool prev;
@@ -237,11 +300,15 @@ struct StepPlan {
     bool scan_in_gen;        // on-demand relayout: the scans of layers 1.. ride in that kernel's prologue
     bool fold_wanted;        // the out-projection may fold its slabs inside its launch (the launcher decides: shape, device, fault word)
     bool grouped;            // op-by-op tail: independent small ops share launches
+    bool prefix;             // prefix cache: a watch launch first, layer 0's FRONT / attention / generator skip where the queries repeat
     int out8_min_rows;
     int launches_per_layer;
 };
 
-static StepPlan plan_step(const sbev_decoder_config& c, const sbev_decoder_weights& w, bool lazy, bool aux_ok, const sbev::Switches& sw) {
+// cache_usable: the caller passed a cache, no attn_mask, and launch profiling is off (with it on every launch stays a full one, so the
+// event figures stay what they were)
+static StepPlan plan_step(const sbev_decoder_config& c, const sbev_decoder_weights& w, bool lazy, bool aux_ok, const sbev::Switches& sw,
+                          bool cache_usable = false) {
     StepPlan p{};
     p.nimg = c.gemm_mode == SBEV_GEMM_BF16X6 ? 3 : c.gemm_mode == SBEV_GEMM_BF16X3S ? 2 : c.gemm_mode == SBEV_GEMM_F16X3 ? 4
              : c.gemm_mode == SBEV_GEMM_F16X4 ? 5 : 0;
@@ -281,6 +348,9 @@ static StepPlan plan_step(const sbev_decoder_config& c, const sbev_decoder_weigh
     // to the op-by-op path); large batches have enough tiles per linear anyway
     p.grouped = !p.fork && (D == 256 || D == 512) && ((p.BQ + 127) / 128) * ((D + 127) / 128) < 256;
     p.out8_min_rows = sw.out8_min_rows;
+    // the three launches that skip are the chain path's FRONT, the attention and the weight-stationary generator; layer 0's generator
+    // never carries a relayout scan (Step::layer_chain: ride = scan_in_gen && layer > 0)
+    p.prefix = cache_usable && p.chain && p.gen_ws;
     // chains: attention, attention chain, generator, gather + mixing, out-projection, tail (+ next front)
     // op by op: 17 with the fused gather + mixing (DESIGN_HISTORY.md section 4)
     // (+ the sort of every layer in order mode 1; mode 2 sorts once per STEP)
@@ -305,6 +375,17 @@ extern "C" int sbev_decoder_mixed_up_log2(const sbev_decoder_config* cfg) {
     return e;
 }
 
+extern "C" int64_t sbev_prefix_cache_bytes(const sbev_decoder_config* cfg) {
+    if (validate(cfg) != SBEV_OK) return -1;
+    return (int64_t)carve_prefix(*cfg, nullptr).bytes;
+}
+
+extern "C" int sbev_decoder_prefix_planned(const sbev_decoder_config* cfg, const sbev_decoder_weights* w, int cache_given, int mask_given,
+                                           int lazy_given) {
+    if (validate(cfg) != SBEV_OK || !w) return -1;
+    return plan_step(*cfg, *w, lazy_given != 0, true, read_switches(), cache_given && !mask_given && !launch_profiling_on()).prefix ? 1 : 0;
+}
+
 extern "C" int64_t sbev_decoder_workspace_bytes(const sbev_decoder_config* cfg) {
     if (validate(cfg) != SBEV_OK) return -1;
     sbev::chain_pair_prepare();            // (the one call every user makes before a forward or a capture)
@@ -326,6 +407,7 @@ struct Step {
     // on-demand relayout (sbev_decoder_forward_lazy): feats_nhwc are DESTINATIONS; every layer's point selection marks the units its
     // points read and one launch behind it moves the marked units that this step has not moved yet (csrc/layout.hip)
     const sbev_lazy_feats* lazy;
+    const Prefix* pf;                // the prefix cache when p.prefix, else null
     sbev_stream_t stream;            // the caller's stream ...
     Aux& ax;                         // ... and the aux stream + event ring, used only when p.fork
     hipStream_t s_main = reinterpret_cast<hipStream_t>(stream);
@@ -339,6 +421,8 @@ struct Step {
     const float* feat = query_feat;  // op by op: the layer's input features (query_feat, then x3)
     bool pe0_done = false;           // op by op: the previous layer's grouped tail already ran this layer's first position-encoder stage
     hipEvent_t ev_cls = nullptr;     // forked: end of the previous layer's classification branch on the aux stream
+    float* params = b.params;        // the layer's generated parameters: b.params, or the prefix cache's for layer 0
+    const uint32_t* skip = nullptr;  // layer 0 with a prefix cache: its header, for the launches that may skip
 
     float* cls_of(int layer) const { return cls_out + (int64_t)layer * p.BQ * c.num_classes; }
     float* box_of(int layer) const { return bbox_out + (int64_t)layer * p.BQ * c.code_size; }
@@ -364,10 +448,10 @@ struct Step {
 
     // parameter generator in the 3 x bf16 mode: x1 is split once per layer and streamed past W-stationary strips
     int generator_bf16x3(sbev_stream_t st) {
-        if (!p.pg_strip) return sbev_linear_bf16x3(b.x1, w.pg_w2, w.pg_b, nullptr, b.params, p.BQ, p.pgN, D, D, p.pgN, 0, st);
+        if (!p.pg_strip) return sbev_linear_bf16x3(b.x1, w.pg_w2, w.pg_b, nullptr, params, p.BQ, p.pgN, D, D, p.pgN, 0, st);
         uint16_t* x2 = reinterpret_cast<uint16_t*>(b.x1s);
         TRY(sbev_split_bf16x3_weights(b.x1, x2, p.BQ, D, st));
-        return sbev_linear_bf16x3_strip(x2, w.pg_w2, w.pg_b, b.params, p.BQ, p.pgN, D, p.pgN, 0, st);
+        return sbev_linear_bf16x3_strip(x2, w.pg_w2, w.pg_b, params, p.BQ, p.pgN, D, p.pgN, 0, st);
     }
     // split-image modes: x1 -> image fragments (a launch of its own unless the attention chain wrote them) -> Y = X W^T + b;
     // scan non-null: the layer's on-demand relayout scan inside the generator
@@ -379,13 +463,13 @@ struct Step {
             TRY(p.nimg >= 4 ? sbev_pack_f16s_frags(b.x1, D, xs, const_cast<float*>(w.pg_xscale), (int)p.BQ, D, 2, st)
                             : sbev_pack_bf16s_frags(b.x1, D, xs, (int)p.BQ, D, p.nimg, st));
         }
-        return sbev::linear_gen_split(xs, w.pg_xscale, w.pg_ws, w.pg_wdown, w.pg_b, b.params, p.BQ, p.pgN, D, p.pgN, 0, p.nimg, p.gen_ws, scan,
-                                      reinterpret_cast<hipStream_t>(st));
+        return sbev::linear_gen_split(xs, w.pg_xscale, w.pg_ws, w.pg_wdown, w.pg_b, params, p.BQ, p.pgN, D, p.pgN, 0, p.nimg, p.gen_ws, scan,
+                                      reinterpret_cast<hipStream_t>(st), skip);
     }
     int generator(sbev_stream_t st, const sbev::LazyScan* scan) {
         if (p.nimg) return generator_bf16s(st, scan);
         if (c.gemm_mode == SBEV_GEMM_BF16X3) return generator_bf16x3(st);
-        return sbev_linear_f32(b.x1, w.pg_w, w.pg_b, nullptr, b.params, p.BQ, p.pgN, D, D, D, p.pgN, 0, st);
+        return sbev_linear_f32(b.x1, w.pg_w, w.pg_b, nullptr, params, p.BQ, p.pgN, D, D, D, p.pgN, 0, st);
     }
 
     int gather(sbev_stream_t st) {      // the stand-alone sampler
@@ -398,9 +482,9 @@ struct Step {
     int gather_and_mix(sbev_stream_t st, const int32_t* order, hipEvent_t params_ready = nullptr) {
         if (!p.fused) TRY(gather(st));
         TRY(join(params_ready));
-        if (!p.fused && p.nimg >= 4) return sbev_adaptive_mixing_pairs_f16(b.sampled, b.params, b.mixed, p.BQ, c.G, Pin, Cg, c.out_points, eps, mixed_up, st);
-        if (!p.fused) return sbev_adaptive_mixing_f32(b.sampled, b.params, b.mixed, p.BQ, c.G, Pin, Cg, c.out_points, eps, st);
-        return sbev::sample_mix(pyramid.d, c.B, c.T, c.G, b.params, b.mixed, c.out_points, eps, p.nimg >= 4 ? ldexpf(1.f, mixed_up) : 0.f, order, st);
+        if (!p.fused && p.nimg >= 4) return sbev_adaptive_mixing_pairs_f16(b.sampled, params, b.mixed, p.BQ, c.G, Pin, Cg, c.out_points, eps, mixed_up, st);
+        if (!p.fused) return sbev_adaptive_mixing_f32(b.sampled, params, b.mixed, p.BQ, c.G, Pin, Cg, c.out_points, eps, st);
+        return sbev::sample_mix(pyramid.d, c.B, c.T, c.G, params, b.mixed, c.out_points, eps, p.nimg >= 4 ? ldexpf(1.f, mixed_up) : 0.f, order, st);
     }
 
     // out-projection, row chains: the split-K slabs are left for the tail chain (`used` of them), or folded inside the launch into ONE row block, b.folded
@@ -438,12 +522,19 @@ struct Step {
     // a layer as row chains (row_chain.hip): 6 launches instead of 17
     int layer_chain(int layer) {
         if (p.order_mode != 0 && (layer == 0 || p.order_mode == 1)) TRY(sbev_query_order(bbox, c.code_size, c.pc_range, c.B, c.Q, b.order, stream));
-        TRY(sbev_sasa_f32(b.qkvt, c.attn_in_rows, bbox, c.pc_range, attn_mask, b.att, c.B, c.Q, c.H, D / c.H, stream));
+        // prefix cache, layer 0: FRONT's x, the attention output and the generated parameters live in the cache (b.x / b.att / b.params
+        // are rewritten by the later layers); the attention chain below runs in full -- its points depend on the frame's matrices
+        const bool cached = pf && layer == 0;
+        float* att = cached ? pf->att0 : b.att;
+        params = cached ? pf->params0 : b.params;
+        skip = cached ? pf->hdr : nullptr;
+        TRY(sbev::launch_sasa(b.qkvt, c.attn_in_rows, bbox, c.pc_range, attn_mask, att, c.B, c.Q, c.H, D / c.H, skip, s_main));
         // (fp16 GEMM modes: the chain also leaves x1 as the generator's fragment operand -- no pack launch)
-        TRY(sbev::launch_chain_attn(c, w, b.att, b.x, b.x1, bbox, time_diff, lidar2img, b.loc, b.wbp, eps, s_main,
+        TRY(sbev::launch_chain_attn(c, w, att, cached ? pf->x0 : b.x, b.x1, bbox, time_diff, lidar2img, b.loc, b.wbp, eps, s_main,
                                     p.nimg >= 4 ? reinterpret_cast<uint16_t*>(b.x1s) : nullptr, p.nimg >= 4 ? w.pg_xscale : nullptr, b.pair_sync,
                                     lazy ? &lplan : nullptr, lazy ? b.touch_need : nullptr));
         const bool ride = p.scan_in_gen && layer > 0;
+        SBEV_REQUIRE(!(ride && skip), "sbev_decoder_forward: a generator that carries a relayout scan cannot skip");
         const sbev::LazyScan scan = lazy_scan(layer);
         if (!ride) TRY(lazy_move(scan, layer == 0));      // (layer 0's move behind the generator instead of in front of it: measured equal, 537-539 both ways)
         TRY(generator(stream, ride ? &scan : nullptr));
@@ -543,8 +634,17 @@ struct Step {
         return sbev_refine_bbox(bbox, b.reg, c.T > 1 ? vel_div : nullptr, box_of(layer), c.B, c.Q, c.code_size, stream);
     }
 
+    int prefix_watch() {
+        const WatchArgs a{{reinterpret_cast<const uint32_t*>(query_bbox), reinterpret_cast<const uint32_t*>(query_feat)},
+                          {reinterpret_cast<uint32_t*>(pf->qb), reinterpret_cast<uint32_t*>(pf->qf)},
+                          {(uint32_t)(p.BQ * 10), (uint32_t)(p.BQ * D)}, pf->hdr};
+        hipLaunchKernelGGL(prefix_watch_kernel, dim3(sbev::PFX_NW), dim3(256), 0, s_main, a);
+        return sbev::check_launch("prefix cache (watch)");
+    }
+
     int run() {
-        if (p.chain) TRY(sbev::launch_chain_front(c, w, query_bbox, query_feat, b.x, b.qkvt, eps, s_main));
+        if (pf) TRY(prefix_watch());
+        if (p.chain) TRY(sbev::launch_chain_front(c, w, query_bbox, query_feat, pf ? pf->x0 : b.x, b.qkvt, eps, s_main, pf ? pf->hdr : nullptr));
         for (int layer = 0; layer < c.num_layers; ++layer) TRY(p.chain ? layer_chain(layer) : layer_ops(layer));
         return join(ev_cls);      // final join
     }
@@ -556,7 +656,8 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
                                 const void* const* feats_nhwc, const float* query_bbox, const float* query_feat,
                                 const float* time_diff, const float* lidar2img, const float* vel_div,
                                 const uint8_t* attn_mask, float* cls_out, float* bbox_out,
-                                void* workspace, int64_t workspace_bytes, sbev_stream_t stream, const sbev_lazy_feats* lazy) {
+                                void* workspace, int64_t workspace_bytes, sbev_stream_t stream, const sbev_lazy_feats* lazy,
+                                void* cache = nullptr, int64_t cache_bytes = 0) {
     TRY(validate(cfg));
     const sbev_decoder_config& c = *cfg;
     SBEV_REQUIRE(w && feats_nhwc && query_bbox && query_feat && time_diff && lidar2img && cls_out && bbox_out && workspace,
@@ -571,7 +672,9 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
     }
     const sbev::ProfCallScope prof_scope;     // with sbev_profile_stride(n): only every n-th call's launches are bracketed
     Aux& ax = aux();
-    const StepPlan p = plan_step(c, *w, lazy != nullptr, ax.ok, read_switches());
+    // (the watch compares 16-byte chunks: queries at other addresses run the step without the cache)
+    const bool cache_usable = cache && !attn_mask && !launch_profiling_on() && ((((uintptr_t)query_bbox) | ((uintptr_t)query_feat)) & 15) == 0;
+    const StepPlan p = plan_step(c, *w, lazy != nullptr, ax.ok, read_switches(), cache_usable);
     SBEV_REQUIRE((((uintptr_t)workspace) & 255) == 0, "sbev_decoder_forward: workspace must be 256-byte aligned");
     SBEV_REQUIRE(cfg->gemm_mode != SBEV_GEMM_BF16X3 || (w->pg_w2 && w->op_w2), "sbev_decoder_forward: gemm_mode bf16x3 needs pg_w2 / op_w2");
     SBEV_REQUIRE(p.nimg == 0 || (w->pg_ws && w->op_wp), "sbev_decoder_forward: gemm_mode %d needs pg_ws / op_wp", cfg->gemm_mode);
@@ -579,7 +682,15 @@ static int decoder_forward_impl(const sbev_decoder_config* cfg, const sbev_decod
     const Buffers b = carve(c, workspace);
     SBEV_REQUIRE((int64_t)b.bytes <= workspace_bytes, "sbev_decoder_forward: workspace too small (%lld < %zu)", (long long)workspace_bytes, b.bytes);
 
-    Step step{c, *w, p, b, feats_nhwc, query_bbox, query_feat, time_diff, lidar2img, vel_div, attn_mask, cls_out, bbox_out, lazy, stream, ax};
+    Prefix pf{};
+    if (p.prefix) {
+        pf = carve_prefix(c, cache);
+        SBEV_REQUIRE((((uintptr_t)cache) & 255) == 0, "sbev_decoder_forward_cached: cache must be 256-byte aligned");
+        SBEV_REQUIRE((int64_t)pf.bytes <= cache_bytes, "sbev_decoder_forward_cached: cache too small (%lld < %zu)", (long long)cache_bytes, pf.bytes);
+        SBEV_REQUIRE(p.BQ * (int64_t)c.D < 0x7fffffffLL, "sbev_decoder_forward_cached: too many query words");
+    }
+    Step step{c, *w, p, b, feats_nhwc, query_bbox, query_feat, time_diff, lidar2img, vel_div, attn_mask, cls_out, bbox_out, lazy,
+              p.prefix ? &pf : nullptr, stream, ax};
     if (lazy) {
         SBEV_REQUIRE(lazy_plan_of(c, &step.lplan) && b.touch_need, "sbev_decoder_forward_lazy: config not covered (dense pyramid, 4 groups of 64 channels)");
         for (int l = 0; l < c.L; ++l)
@@ -616,6 +727,16 @@ extern "C" int sbev_decoder_forward_lazy(const sbev_decoder_config* cfg, const s
                                 cls_out, bbox_out, workspace, workspace_bytes, stream, lazy);
 }
 
+// Either of the two with a prefix cache (include/sbev_hip.h); cache == NULL: exactly those
+extern "C" int sbev_decoder_forward_cached(const sbev_decoder_config* cfg, const sbev_decoder_weights* w, void* const* feats_nhwc,
+                                           const sbev_lazy_feats* lazy, const float* query_bbox, const float* query_feat,
+                                           const float* time_diff, const float* lidar2img, const float* vel_div,
+                                           const uint8_t* attn_mask, float* cls_out, float* bbox_out,
+                                           void* workspace, int64_t workspace_bytes, sbev_stream_t stream, void* cache, int64_t cache_bytes) {
+    return decoder_forward_impl(cfg, w, const_cast<const void* const*>(feats_nhwc), query_bbox, query_feat, time_diff, lidar2img, vel_div, attn_mask,
+                                cls_out, bbox_out, workspace, workspace_bytes, stream, lazy, cache, cache_bytes);
+}
+
 extern "C" int sbev_decoder_lazy_supported(const sbev_decoder_config* cfg) {
     sbev::LazyPlan p;
     return cfg && validate(cfg) == SBEV_OK && lazy_plan_of(*cfg, &p) ? 1 : 0;
@@ -645,6 +766,11 @@ void profile_end(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int kind) {
     g_prof_events.push_back({e0, e1, kind});
 }
 }  // namespace sbev
+
+static bool launch_profiling_on() {
+    std::lock_guard<std::mutex> lk(sbev::g_prof_mu);
+    return sbev::g_prof_mask != 0;
+}
 
 // decides at the top of a decoder call whether its launches are bracketed; restores the flag on every exit path
 namespace sbev {

@@ -707,6 +707,7 @@ struct GenWsArgs {
     // the marks and the gather that does not touch the features): one round trip for the flags, a wave per found unit.
     int lazy_on, lazy_esize;
     LazyArgs lazy;
+    const uint32_t* skip_hdr;    // layer 0 of a step with a prefix cache (sbev_common.hpp: prefix_clean; never with lazy_on), else null
 };
 
 #ifndef SBEV_WS_NCH
@@ -730,6 +731,8 @@ __global__ __launch_bounds__(512) void gemm_f16s_gen_ws_kernel(const GenWsArgs a
     static_assert(PR::NIMG == 2, "two-image modes only: the stationary weights are 128 registers");
     constexpr bool F16 = PR::F16;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];    // the only LDS object: [WS_SLOTS][WS_FRAG]
+    // prefix cache: the queries repeat bit for bit -> x1 is what it was and Y of the step that stored it stands
+    if (a.skip_hdr && sbev::prefix_clean(a.skip_hdr)) return;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
@@ -1764,7 +1767,7 @@ static auto gen3_kernel(int nimg, int rf) -> void (*)(GenArgs) {             // 
 
 static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias, float* Y, int64_t M, int N, int K, int64_t ldy, int relu,
                       int nimg, const float* xscale, const float* colscale, bool weight_stationary, sbev_stream_t stream,
-                      const sbev::LazyScan* lz = nullptr) {
+                      const sbev::LazyScan* lz = nullptr, const uint32_t* skip_hdr = nullptr) {
     SBEV_REQUIRE(M >= 0 && sbev_linear_bf16s_gen_ok(M > 0 ? M : 1, N, K), "sbev_linear_bf16s_gen: needs N %% 256 == 0, K %% 32 == 0, K <= 4096 (M=%lld N=%d K=%d)", (long long)M, N, K);
     if (M == 0) return SBEV_OK;
     SBEV_REQUIRE(Xs && Ws && Y && ldy >= N && ldy % 4 == 0, "sbev_linear_bf16s_gen: bad pointers / leading dimension");
@@ -1774,6 +1777,7 @@ static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias,
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool ws = weight_stationary && sbev::gen_ws_shape_ok(M, K, ldy, nimg);
     SBEV_REQUIRE(!lz || ws, "generator: the on-demand relayout's scan rides in the weight-stationary kernel only");
+    SBEV_REQUIRE(!skip_hdr || (ws && !lz), "generator: only the weight-stationary kernel skips, and never with a relayout scan riding in it");
     if (ws) {
         // row splits: tasks = column tiles x splits walked by <= one workgroup per CU; a task costs its fragments + ~4 fragments' worth
         // of weight load (256 KB that nothing overlaps).  c2 (29 fragments, 128 column tiles): 2 splits = 256 tasks of 15 / 14 fragments
@@ -1785,7 +1789,7 @@ static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias,
             const double cost = (double)((tasks + cus - 1) / cus) * ((nfrag + r - 1) / r + 4.0);
             if (cost < best - 1e-9) { best = cost; nrs = r; }
         }
-        GenWsArgs w{Xs, Ws, bias, Y, (int)M, N, (long long)ldy, relu, nrs, nfrag / nrs, nfrag % nrs, nct * nrs, colscale, xscale, 0, 4, {}};
+        GenWsArgs w{Xs, Ws, bias, Y, (int)M, N, (long long)ldy, relu, nrs, nfrag / nrs, nfrag % nrs, nct * nrs, colscale, xscale, 0, 4, {}, skip_hdr};
         if (lz) {
             w.lazy_on = 1; w.lazy_esize = lz->esize;
             fill_lazy_args(w.lazy, *lz, false);
@@ -1849,11 +1853,12 @@ extern "C" int sbev_linear_f16s_gen(const uint16_t* Xs, const float* xscale, con
 
 namespace sbev {
 int linear_gen_split(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y, int64_t M,
-                     int N, int K, int64_t ldy, int relu, int nimg, bool weight_stationary, const LazyScan* lz, hipStream_t stream) {
+                     int N, int K, int64_t ldy, int relu, int nimg, bool weight_stationary, const LazyScan* lz, hipStream_t stream,
+                     const uint32_t* skip_hdr) {
     SBEV_REQUIRE(nimg >= 2 && nimg <= 5, "sbev_linear_bf16s_gen: nimg=%d (2 = bf16x3, 3 = bf16x6, 4 / 5 = fp16 with 3 / 4 image products)", nimg);
     SBEV_REQUIRE(nimg < 4 || M == 0 || (xscale && wdown), "sbev_linear_f16s_gen: null scale pointer");
     return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nimg, nimg >= 4 ? xscale : nullptr, nimg >= 4 ? wdown : nullptr, weight_stationary,
-                      reinterpret_cast<sbev_stream_t>(stream), lz);
+                      reinterpret_cast<sbev_stream_t>(stream), lz, skip_hdr);
 }
 }  // namespace sbev
 

@@ -106,6 +106,7 @@ struct ChainArgs {
     float* so; int soN;          // so: null when the sample points are projected in here (proj.loc_bp set)
     sbev_ops::SamplePointArgs proj;
     float eps;
+    uint32_t* skip_hdr;          // PRE_FRONT of a step with a prefix cache (sbev_common.hpp: prefix_clean), else null; read by that instantiation only
 };
 
 // ---- the weight stream --------------------------------------------------------------------------------------------------
@@ -502,6 +503,18 @@ __global__ __launch_bounds__(64 * NWAVE) void row_chain_kernel(const ChainArgs a
     float* const px = PAIR ? a.pair_x + (long long)pair * (3 * R * DM) : nullptr;       // [3][R][256]
     const long long row0 = (long long)pair * R;
     float* P = smem + OFF_P;
+    if constexpr (PRE == PRE_FRONT) {
+        // prefix cache: the queries repeat bit for bit -> x and qkvt of the step that stored them stand; workgroup 0's first thread is the
+        // single writer of the two counters
+        if (a.skip_hdr) {
+            const bool clean = sbev::prefix_clean(a.skip_hdr);
+            if (blockIdx.x == 0 && threadIdx.x == 0) {
+                uint32_t* n = a.skip_hdr + (clean ? sbev::PFX_HITS : sbev::PFX_MISSES);
+                *n = *n + 1u;
+            }
+            if (clean) return;
+        }
+    }
     if (PRE == PRE_ATT && a.zero_words && blockIdx.x == 0)
         for (int i = threadIdx.x; i < a.n_zero; i += 64 * NWAVE) a.zero_words[i] = 0u;
 
@@ -1144,12 +1157,12 @@ static int launch(const ChainArgs& a, int rg, hipStream_t s, const char* what) {
 
 // position encoder + attention in-projection of the FIRST layer (the later layers' run at the end of the previous tail)
 int launch_chain_front(const sbev_decoder_config& c, const sbev_decoder_weights& w, const float* bbox, const float* feat, float* x,
-                       float* qkvt, float eps, hipStream_t s) {
+                       float* qkvt, float eps, hipStream_t s, uint32_t* skip_hdr) {
     const PackMap m = pack_map(c);
     ChainArgs a{};
     fill_common(a, c, eps);
     a.pre = PRE_FRONT;
-    a.bbox = bbox; a.feat = feat; a.x = x; a.qkvt = qkvt;
+    a.bbox = bbox; a.feat = feat; a.x = x; a.qkvt = qkvt; a.skip_hdr = skip_hdr;
     const int rg = row_groups(a.M);
     a.n_units = add_front(a, 0, c, w.chain_pack, m, rg);
     a.warm = w.chain_pack + m.pe3;

@@ -178,15 +178,20 @@ struct LazyScan {
 // weight_stationary: the caller's reading of sbev_linear_gen_weight_stationary -- the weight-stationary kernel runs where it is set AND
 // gen_ws_shape_ok; lz (non-null: this layer's scan in the kernel's prologue) needs both
 bool gen_ws_shape_ok(int64_t M, int K, int64_t ldy, int nimg);
+// skip_hdr (non-null: layer 0 of a step with a prefix cache, weight-stationary kernel only, never together with lz): see prefix_clean
 int linear_gen_split(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y, int64_t M,
-                     int N, int K, int64_t ldy, int relu, int nimg, bool weight_stationary, const LazyScan* lz, hipStream_t stream);
+                     int N, int K, int64_t ldy, int relu, int nimg, bool weight_stationary, const LazyScan* lz, hipStream_t stream,
+                     const uint32_t* skip_hdr = nullptr);
 int launch_lazy_relayout(const LazyScan& scan, bool first, hipStream_t s);      // first: the step's first move (every marked unit is new)
 
 // row_chain.hip: the row-local op chains of a decoder layer as single launches (weights pre-packed: sbev_decoder_chain_pack)
 bool row_chain_supported(const sbev_decoder_config& c);
 bool row_chain_pays(long long rows);
 int launch_chain_front(const sbev_decoder_config& c, const sbev_decoder_weights& w, const float* bbox, const float* feat, float* x,
-                       float* qkvt, float eps, hipStream_t s);
+                       float* qkvt, float eps, hipStream_t s, uint32_t* skip_hdr = nullptr);      // skip_hdr: see prefix_clean
+// attention.hip: sbev_sasa_f32 for callers that hold a prefix cache (skip_hdr, mask == null only)
+int launch_sasa(const float* qkvt, int64_t ld, const float* query_bbox, const double* pc_range, const uint8_t* mask, float* out, int B, int Q,
+                int H, int head_dim, const uint32_t* skip_hdr, hipStream_t s);
 int launch_chain_attn(const sbev_decoder_config& c, const sbev_decoder_weights& w, const float* att, const float* x, float* x1,
                       const float* bbox, const float* time_diff, const float* lidar2img, float* loc_bp, float* w_bp, float eps,
                       hipStream_t s, uint16_t* x1_frag = nullptr, const float* x1_scale = nullptr, uint32_t* pair_sync = nullptr,
@@ -238,6 +243,23 @@ int launch_sasa_bwd_mfma(const float* qkvt, int64_t ld, const float* bbox, const
 // optional HIP-event bracket around sampler launches (decoder.hip; switched by sbev_profile_sampler)
 bool profile_begin(hipStream_t s, hipEvent_t* e0, hipEvent_t* e1, int kind = 0);
 void profile_end(hipStream_t s, hipEvent_t e0, hipEvent_t e1, int kind = 0);   // kind: 0 sampler, 1 generator GEMM, 2 out-projection GEMM
+
+// Prefix cache (decoder.hip): the header of the caller's cache block, 32-bit words.  The step's first launch (prefix_watch_kernel)
+// rewrites every dirty word on every step; the three launches of layer 0 that read only the queries and the weights leave at once
+// where none is set.
+constexpr int PFX_ARMED = 0, PFX_FORCE = 1, PFX_HITS = 2, PFX_MISSES = 3, PFX_DIRTY = 4, PFX_NW = 64;
+// nothing this step's queries changed: the OR of the dirty words, read with wave-uniform loads (hdr is a kernel argument); the caller
+// returns on true before its first barrier, LDS-DMA request or store
+__device__ __forceinline__ bool prefix_clean(const uint32_t* hdr) {
+    const uint4* d = reinterpret_cast<const uint4*>(hdr + PFX_DIRTY);
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < PFX_NW / 4; ++i) {
+        const uint4 v = d[i];
+        acc |= (v.x | v.y) | (v.z | v.w);
+    }
+    return acc == 0;
+}
 
 // Sum over the 64 lanes of a wave without LDS traffic (ds_bpermute-based __shfl_xor costs an LDS round trip per
 // step, which is pure exposed latency when only a few waves share a SIMD): 4 DPP steps reduce each 16-lane row

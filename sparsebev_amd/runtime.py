@@ -50,6 +50,52 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+class PrefixCache:
+    """The device block of sbev_decoder_forward_cached (include/sbev_hip.h): layer 0's position encoder + in-projection, self attention
+    and generated parameters read the queries and the weights only, and the reference builds the queries from two weight tensors on
+    every call (models/sparsebev_head.py:126-127, 217-218) -- so a step whose queries repeat bit for bit skips those three launches and
+    reads what the step that stored them left here.  Header words: 0 ``armed``, 1 ``force``, 2 ``hits``, 3 ``misses``.  One per captured
+    step (dies with it) and one per DecoderRuntime for the eager path (header zeroed whenever anything but queries and frame changes)."""
+
+    _live = None      # weak set of every cache alive: runtime.prefix_cache() writes their force words
+
+    def __init__(self, nbytes, dev):
+        import weakref
+        self.nbytes, self.device = nbytes, dev
+        self.buf = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
+        off = (-self.buf.data_ptr()) % 256
+        self.ptr = self.buf.data_ptr() + off
+        self.hdr = self.buf[off:off + 16].view(torch.int32)
+        self.reset()
+        if PrefixCache._live is None:
+            PrefixCache._live = weakref.WeakSet()
+        PrefixCache._live.add(self)
+
+    def reset(self):
+        """disarm: the next step recomputes whatever the rest of the block holds (stream-ordered on the current stream)"""
+        self.hdr.zero_()
+        self.force(_STATE['prefix_off'])
+
+    def force(self, on):
+        self.hdr[1:2].fill_(1 if on else 0)
+
+    def counters(self):
+        """(hits, misses) since the last reset; synchronises"""
+        h = self.hdr.cpu()
+        return int(h[2]), int(h[3])
+
+
+def _prefix_cache_for(cfg, weights, mask, lazy, dev):
+    """Bytes of the prefix cache a step of this config would use, or 0: the library's plan says it would not (op-by-op path, exact GEMM
+    mode, a mask, launch profiling), or the block is above ``SBEV_PREFIX_CACHE_MAX_MB`` (default 1024)."""
+    lib = _lib.load()
+    if _STATE['profile'] or lib.sbev_decoder_prefix_planned(ctypes.byref(cfg), ctypes.byref(weights), 1, int(mask is not None), int(bool(lazy))) != 1:
+        return 0
+    need = int(lib.sbev_prefix_cache_bytes(ctypes.byref(cfg)))
+    limit = float(os.environ.get('SBEV_PREFIX_CACHE_MAX_MB', '1024')) * 2 ** 20
+    return need if 0 < need <= limit else 0
+
+
 class DecoderRuntime:
     """Binds a SparseBEVTransformerDecoder's parameters (by pointer) to the C++ runtime and owns the workspace.
     Re-binds automatically when a parameter is replaced or modified in place (``_version`` / ``data_ptr`` change)."""
@@ -73,6 +119,8 @@ class DecoderRuntime:
         self.mode_eff = gemm_mode
         self.f16_headroom_log2 = 0.0
         self.step_graphs = StepGraphs(self)
+        self._prefix = None        # the eager path's PrefixCache ...
+        self._prefix_key = None    # ... and what its contents were computed under (None: disarm before the next use)
 
     # -- weights -----------------------------------------------------------------------------------------
     def _signature(self):
@@ -203,6 +251,7 @@ class DecoderRuntime:
                               % lib.sbev_last_error().decode('utf-8', 'replace'))
                 DecoderRuntime._warned_chain = True
         self._keep, self._weights = keep, w
+        self._prefix_key = None             # (also a re-bind asked for by hand under an unchanged signature: invalidate_caches)
 
     def _config(self, B, Q, pyramid=None, ctx=None):
         """The sbev_decoder_config of a [B, Q] call with the bound weights; with ``pyramid`` and ``ctx`` also what a forward reads of
@@ -298,6 +347,37 @@ class DecoderRuntime:
         cfg = self._config(B, Q)
         return int(_lib.load().sbev_decoder_launches_per_layer(ctypes.byref(cfg), ctypes.byref(self._weights)))
 
+    def _eager_prefix(self, cfg, sig, mask, lazy, dev):
+        """(pointer, bytes) of the eager path's prefix cache for this call, or (None, 0).  Its header is zeroed when the weight signature,
+        the shapes, the gemm mode, the switches, pc_range, the layer count, the device or the stream are not what its contents were
+        computed under, and after a forward that raised."""
+        need = _prefix_cache_for(cfg, self._weights, mask, lazy, dev)
+        if need == 0:
+            return None, 0
+        key = (sig, cfg.B, cfg.Q, cfg.D, cfg.T, cfg.P, cfg.G, cfg.out_points, self.mode_eff, _switch_key(), tuple(self.decoder.pc_range),
+               cfg.num_layers, str(dev), torch.cuda.current_stream(dev).cuda_stream, need)
+        if self._prefix is None or self._prefix.nbytes != need or self._prefix.device != dev:
+            self._prefix, self._prefix_key = None, None      # (free the old block first)
+            self._prefix = PrefixCache(need, dev)
+        elif key != self._prefix_key:
+            self._prefix.reset()
+        self._prefix_key = key
+        return ctypes.c_void_p(self._prefix.ptr), need
+
+    def _step(self, args, lz, stream, prefix):
+        """sbev_decoder_forward / _lazy of ``args`` (what _prepare returned) with the prefix cache ``prefix`` = (pointer, bytes)"""
+        st = _lib.load().sbev_decoder_forward_cached(args[0], args[1], args[2], ctypes.byref(lz) if lz is not None else None, *args[3:], stream,
+                                                     prefix[0], prefix[1])
+        if st != 0:
+            self._prefix_key = None      # whatever the failed step left: disarm before the next use
+        return st
+
+    def prefix_counters(self):
+        """(hits, misses) summed over this runtime's live prefix caches -- the eager one and every captured step's; synchronises"""
+        caches = [self._prefix] + [e.prefix for e in self.step_graphs.entries.values() if isinstance(e, CapturedStep)]
+        pairs = [c.counters() for c in caches if c is not None]
+        return sum(h for h, _ in pairs), sum(m for _, m in pairs)
+
     def forward(self, query_bbox, query_feat, pyramid, ctx, attn_mask=None, finish=False):
         """pyramid: transformer.FeaturePyramid, cache.RingPyramid or cache.PoolPyramid (told apart by utils.frame_source, which also
         validates the pool's table); ctx: transformer.DecoderContext.  Returns (cls, bbox) stacked over
@@ -306,8 +386,7 @@ class DecoderRuntime:
         check_pair_faults()                 # an earlier step lost a pair hand-off: raise before anything is enqueued on top of it
         args, _keep, cls, box = self._prepare(query_bbox, query_feat, pyramid, ctx, attn_mask)
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        lib = _lib.load()
-        st = lib.sbev_decoder_forward(*args, stream)
+        st = self._step(args, None, stream, self._eager_prefix(_keep[0], self._sig, attn_mask, False, query_feat.device))
         _lib.check(st, 'sbev_decoder_forward')
         return self._finished(cls, box, stream) if finish else (cls, box)
 
@@ -337,7 +416,7 @@ class DecoderRuntime:
                 raise RuntimeError('forward_lazy needs contiguous, 16-byte aligned device NCHW levels of the buffers\' dtype')
             lz.src[l] = f.data_ptr()
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        st = lib.sbev_decoder_forward_lazy(args[0], args[1], args[2], ctypes.byref(lz), *args[3:], stream)
+        st = self._step(args, lz, stream, self._eager_prefix(_keep[0], self._sig, attn_mask, True, query_feat.device))
         _lib.check(st, 'sbev_decoder_forward_lazy')
         if finish:
             cls, box = self._finished(cls, box, stream)
@@ -372,9 +451,10 @@ class CapturedStep:
     """One captured step.  ``replays`` counts launches AFTER the capturing call's own; ``pinned``: keyed on addresses of buffers a caller
     may not bring back (the online ring's and the frame pool's buffers are persistent by construction and are not)."""
 
-    def __init__(self, graph, pinned, staged=False, ctx_buf=None, n_packed=0, layout=None, image=None, ws_key=None):
+    def __init__(self, graph, pinned, staged=False, ctx_buf=None, n_packed=0, layout=None, image=None, ws_key=None, prefix=None):
         self.graph, self.pinned, self.staged, self.ctx_buf = graph, pinned, staged, ctx_buf
         self.n_packed, self.layout, self.image, self.ws_key = n_packed, layout, image, ws_key
+        self.prefix = prefix       # the step's own PrefixCache (or None): workspaces are shared between steps, this is not
         self.replays = -1
 
 
@@ -620,28 +700,34 @@ class StepGraphs(StepBook):
         try:
             segs = [(0, qb), (1, qf)] + ([(2, mask)] if mask is not None else [])
             relayout = [(3 + l, buf) for l, buf in enumerate(pyramid.levels)] if staged else []      # (table index, graph-owned NHWC buffer)
-            handle = self._record(args, ctypes.c_void_p(ctx.buffer.data_ptr() + 4 * n_packed), segs, relayout, (cls, box) if call.outs is not None else None, insert)
+            # the step's own prefix cache, header zeroed here: the replays' watch launch compares the staged queries with its copy
+            lazy = len(relayout) > 0 and _STATE['lazy'] and bool(_lib.load().sbev_decoder_lazy_supported(args[0]))
+            need = _prefix_cache_for(keep[0], rt._weights, mask, lazy, dev)
+            prefix = PrefixCache(need, dev) if need else None
+            handle = self._record(args, ctypes.c_void_p(ctx.buffer.data_ptr() + 4 * n_packed), segs, relayout, (cls, box) if call.outs is not None else None, insert,
+                                  prefix)
         except BaseException:
             rt._release_graph_ws(ws_key)
             raise
         # what the graph's launches read or write: its own buffers, and -- address-keyed entries only -- the caller's feature buffers
         graph = DecoderGraph(handle, (keep, qb, qf, mask, ctx, None if staged else (None if insert else call.feats, pyramid)), cls, box)
-        e = CapturedStep(graph, not staged and not src.resident, staged, ctx.buffer, n_packed, layout, (ih, iw), ws_key)
+        e = CapturedStep(graph, not staged and not src.resident, staged, ctx.buffer, n_packed, layout, (ih, iw), ws_key, prefix)
         self.captured(key, e)
         return e
 
     @staticmethod
-    def _record(args, table, segs, relayout, finish, insert=None):
+    def _record(args, table, segs, relayout, finish, insert=None, prefix=None):
         """The step's launches under stream capture -> the instantiated graph's handle: the in-graph copies of ``segs`` (table index,
         graph-owned buffer), the relayout of the staged levels (on demand inside the step, all fp32 levels in one launch, or one launch
         per level), -- ``insert``: (table indices, the pyramid's pending insert: shapes, dtype, layout and rows, pool pyramid) -- the frame pool's new frames
         into their slots (sbev_pool_insert / sbev_pool_insert_frames, sources from the table), the decoder step, and -- ``finish``: the graph's (cls, box) -- the
-        nan_to_num into the call's own outputs.  All on the one capture stream, in this order.  Raises when any of it fails, with the
-        capture ended."""
+        nan_to_num into the call's own outputs.  All on the one capture stream, in this order.  ``prefix``: the step's PrefixCache or None.
+        Raises when any of it fails, with the capture ended."""
         lib = _lib.load()
         side = torch.cuda.Stream(device=segs[0][1].device)
         side.wait_stream(torch.cuda.current_stream())
         sp = ctypes.c_void_p(side.cuda_stream)
+        pfx = (ctypes.c_void_p(prefix.ptr), prefix.nbytes) if prefix is not None else (None, 0)
         c_idx = (ctypes.c_int32 * len(segs))(*[i for i, _ in segs])
         c_dst = (ctypes.c_void_p * len(segs))(*[t.data_ptr() for _, t in segs])
         c_nb = (ctypes.c_int64 * len(segs))(*[t.numel() * t.element_size() for _, t in segs])
@@ -673,9 +759,9 @@ class StepGraphs(StepBook):
                 lz.table = table
                 for l, (idx, _) in enumerate(relayout):
                     lz.index[l] = idx
-                st_fwd = lib.sbev_decoder_forward_lazy(args[0], args[1], args[2], ctypes.byref(lz), *args[3:], sp) if ok else 0
+                st_fwd = lib.sbev_decoder_forward_cached(args[0], args[1], args[2], ctypes.byref(lz), *args[3:], sp, *pfx) if ok else 0
             else:
-                st_fwd = lib.sbev_decoder_forward(*args, sp) if ok else 0
+                st_fwd = lib.sbev_decoder_forward_cached(args[0], args[1], args[2], None, *args[3:], sp, *pfx) if ok else 0
             ok = ok and st_fwd == 0
             if finish is not None:
                 cls, box = finish
@@ -749,6 +835,7 @@ class _State(dict):
 
 # ('order' is kept for reports only -- query_order() writes it, nothing here decides by it)
 _STATE = _State(profile=0,
+                prefix_off=_os.environ.get('SBEV_NO_PREFIX_CACHE') == '1',        # prefix caches are created with their force word set
                 lazy=not _os.environ.get('SBEV_NO_SPARSE_RELAYOUT'),      # staged NCHW pyramids: on-demand relayout of the units the sample points read
                 relayout_multi=not _os.environ.get('SBEV_NO_RELAYOUT_MULTI'))      # staged fp32 NCHW pyramids: all levels in one launch (A/B switch)
 
@@ -769,6 +856,18 @@ def out_fold(enable):
     results either way.  OFF by default -- at config 2 it costs the out-projection 12.6 us and saves the tail 4 (DESIGN.md section 4.4);
     ``SBEV_OUT_FOLD=1`` starts with it on.  Returns the previous setting."""
     return bool(_lib.load().sbev_decoder_out_fold(int(bool(enable))))
+
+
+def prefix_cache(enable):
+    """Steps whose queries repeat bit for bit skip layer 0's three query-only launches (PrefixCache; default on, ``SBEV_NO_PREFIX_CACHE=1``
+    starts with it off).  Off writes the ``force`` word of every live cache, stream-ordered on the current stream: the same captured
+    steps then recompute everything on every replay -- no re-capture, no new key, bit-identical results.  Returns the previous setting."""
+    prev = not _STATE['prefix_off']
+    _STATE['prefix_off'] = not enable
+    for c in list(PrefixCache._live or ()):
+        with torch.cuda.device(c.device):
+            c.force(not enable)
+    return prev
 
 
 def lazy_relayout(enable):
