@@ -60,6 +60,39 @@ def make_img_metas(B, T, image_h, image_w, frame_dt=0.5):
     return metas
 
 
+# Inputs without the symmetries of the defaults above (tests/test_gpu_asym.py, fixture G14): x and y extents differ and no
+# axis has lo == -hi, so swapped axes or a dropped offset move every query; class counts other than the box width 10
+# (1, an odd one, one past a wavefront's half, the row chains' largest).
+PC_RANGE_ASYM = [-40.0, -61.2, -4.0, 62.4, 31.2, 4.0]
+CLASS_COUNTS = (1, 7, 23, 64)
+
+
+def ego_pose(b):
+    """Sample b's lidar-from-ego transform, float64 [4,4]: yaw 0.37 b rad, translation (1.5 b, -0.8 b, 0.1 b) m."""
+    yaw = 0.37 * b
+    c, sn = math.cos(yaw), math.sin(yaw)
+    E = np.eye(4)
+    E[:3, :3] = [[c, -sn, 0.0], [sn, c, 0.0], [0.0, 0.0, 1.0]]
+    E[:3, 3] = [1.5 * b, -0.8 * b, 0.1 * b]
+    return E
+
+
+def make_img_metas_per_sample(B, T, image_h, image_w):
+    """make_img_metas with nothing shared between the samples of a batch: sample b has its own ego pose (ego_pose(b),
+    right-multiplied into every lidar2img), its own frame spacing 0.5 + 0.15 b s -- time_diff[b, 1], the velocity divisor,
+    differs by 0.15 s from one sample to the next -- and a per-camera timestamp jitter 0.003 ((7 i + 3 b) mod (5 + b)) s
+    whose mean over the 6 cameras of a frame changes with b."""
+    rig = camera_rig(T, image_h, image_w)
+    metas = []
+    for b in range(B):
+        E, dt = ego_pose(b), 0.5 + 0.15 * b
+        ts = [1.6e9 + 10.0 * b - dt * (i // N_VIEWS) + 0.003 * ((7 * i + 3 * b) % (5 + b)) for i in range(T * N_VIEWS)]
+        metas.append(dict(img_timestamp=ts,
+                          lidar2img=[rig[i] @ E for i in range(T * N_VIEWS)],
+                          img_shape=[(image_h, image_w, 3)] * (T * N_VIEWS)))
+    return metas
+
+
 def make_queries(B, Q, embed_dims=256, seed=0, z_norm=0.5):
     """query_bbox [B,Q,10], query_feat [B,Q,D] (fp32, CPU).  xy on the sqrt(Q) grid exactly as the head
     initialises them; z at `z_norm` of the range (-1 m: roughly ground level under the lidar -- with the

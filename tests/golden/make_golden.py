@@ -501,6 +501,47 @@ def main_yardstick():
              params_checksum=S.checksum(params), feats_checksum=S.checksum(feats), **d)
 
 
+def main_asym():
+    """G14: the reference's SparseBEVTransformer.forward, 2 layers, on inputs that share nothing between the samples of the batch and
+    have no x / y symmetry (sparsebev_amd.synthetic.make_img_metas_per_sample, PC_RANGE_ASYM) and 7 classes beside the 10 box
+    columns: B = 3, Q = 36, T = 2, `tiny` pyramid.  In G7's layout, plus the matrices and the range.  Prints the camera-hit statistics
+    per sample (layer 0's sample points).  `python tests/golden/make_golden.py asym` writes only G14."""
+    import copy
+    torch.manual_seed(0)
+    torch.set_num_threads(8)
+    tr, smp, wrap, utils = import_reference()
+    assert wrap.MSMV_CUDA is False
+    B, Q, T, L, NC, pyr = 3, 36, 2, 4, 7, 'tiny'
+    seeds = [18, 181, 182]      # kept because fp32 and fp64 oracle agree to 3e-6 here (tests/test_gpu_asym.py asserts 1e-5): no sample point within fp32 reach of an image border
+    ih, iw, sizes = S.PYRAMIDS[pyr]
+    params = S.make_params(seeds[0], embed_dims=256, num_frames=T, num_points=4, num_levels=L, num_classes=NC, code_size=10)
+    m = tr.SparseBEVTransformer(256, num_frames=T, num_points=4, num_layers=2, num_levels=L, num_classes=NC, code_size=10,
+                                pc_range=S.PC_RANGE_ASYM)
+    m.load_state_dict({PREFIX + k: v for k, v in params.items()}, strict=True)
+    m.eval()
+    metas = S.make_img_metas_per_sample(B, T, ih, iw)
+    bbox, feat = S.make_queries(B, Q, seed=seeds[1])
+    feats = S.make_features(B, T, sizes, seed=seeds[2])
+    per_layer = []
+    hook = m.decoder.decoder_layer.register_forward_hook(lambda mod, inp, out: per_layer.append(out[0].clone()))
+    utils.DUMP.enabled = True
+    utils.DUMP.stage_count = 0
+    with torch.no_grad():
+        cls, box = m(bbox, feat, [f.clone() for f in feats], None, copy.deepcopy(metas))
+    utils.DUMP.enabled = False
+    hook.remove()
+    valid = torch.load('%s/sample_points_cam_valid_mask_stage0.pth' % utils.DUMP.out_dir)          # [B, T, 6, Q, G*P]
+    nh = valid.sum(2)
+    for b in range(B):
+        print('  G14 sample %d hits: none %.3f one %.3f two+ %.3f' % (b, (nh[b] == 0).float().mean(), (nh[b] == 1).float().mean(), (nh[b] >= 2).float().mean()))
+    assert cls.shape == (2, B, Q, NC) and box.shape == (2, B, Q, 10)
+    save('g14_decoder_asym', query_bbox=bbox, query_feat=feat, out_cls=cls, out_bbox=box, out_feat=torch.stack(per_layer),
+         cfg=np.array([B, Q, T, L]), num_classes=np.array(NC), pyramid=np.array(pyr), seeds=np.array(seeds),
+         lidar2img=np.asarray([mm['lidar2img'] for mm in metas], dtype=np.float64),
+         timestamps=np.array([mm['img_timestamp'] for mm in metas]), pc_range=np.array(S.PC_RANGE_ASYM),
+         params_checksum=S.checksum(params), feats_checksum=S.checksum(feats))
+
+
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'head':
         main_head()
@@ -512,6 +553,8 @@ if __name__ == '__main__':
         main_nonfinite()
     elif len(sys.argv) > 1 and sys.argv[1] == 'yardstick':
         main_yardstick()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'asym':
+        main_asym()
     else:
         main()
         main_head()
@@ -519,3 +562,4 @@ if __name__ == '__main__':
         main_train()
         main_nonfinite()
         main_yardstick()
+        main_asym()

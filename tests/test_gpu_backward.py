@@ -356,10 +356,10 @@ def test_refine_bbox_function_vs_torch():
     assert ((bd.grad[..., :3].cpu().double() - bc.grad[..., :3]).abs()[inner]).max() < 1e-4 * bc.grad.abs().max()
 
 
-def build(T, L, seed, num_layers, num_points=4):
-    params = S.make_params(seed, embed_dims=256, num_frames=T, num_points=num_points, num_levels=L)
-    m = SparseBEVTransformer(256, num_frames=T, num_points=num_points, num_layers=num_layers, num_levels=L, num_classes=10,
-                             code_size=10, pc_range=S.PC_RANGE)
+def build(T, L, seed, num_layers, num_points=4, num_classes=10, pc_range=S.PC_RANGE):
+    params = S.make_params(seed, embed_dims=256, num_frames=T, num_points=num_points, num_levels=L, num_classes=num_classes)
+    m = SparseBEVTransformer(256, num_frames=T, num_points=num_points, num_layers=num_layers, num_levels=L, num_classes=num_classes,
+                             code_size=10, pc_range=pc_range)
     m.load_state_dict({PREFIX + k: v for k, v in params.items()}, strict=True)
     return m.to(DEV)
 

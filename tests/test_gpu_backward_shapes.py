@@ -275,6 +275,114 @@ def _relu_inputs_recorded(fn):
     return out, seen
 
 
+class TrainedLayer:
+    """One decoder layer in train() mode (dropouts at 0), forward + backward on the device and under fp64 autograd in the oracle, for
+    cotangents (cc, cb) on (cls, box): ``device`` / ``oracle`` return (cls, box, [(name, gradient)]) over query_feat, the 48 parameters
+    and the feature maps, in the same order.  The oracle's forward is evaluated once (``pre``: its ReLU inputs, in call order)."""
+
+    def __init__(self, B, Q, T, pyr, P, mode, use_mask, seed, metas=None, num_classes=10, pc_range=S.PC_RANGE):
+        from oracle import sparsebev_oracle as O
+        self.O, self.B, self.Q, self.T, self.P, self.mode, self.use_mask = O, B, Q, T, P, mode, use_mask
+        self.num_classes, self.pc_range = num_classes, pc_range
+        ih, iw, sizes = S.PYRAMIDS[pyr]
+        self.L = L = len(sizes)
+        self.params = S.make_params(seed, embed_dims=256, num_frames=T, num_points=P, num_levels=L, num_classes=num_classes)
+        self.model = model = build(T, L, seed, 1, num_points=P, num_classes=num_classes, pc_range=pc_range).train()
+        model.decoder.decoder_layer.self_attn.attn_drop = 0.0
+        model.decoder.decoder_layer.ffn_drop = 0.0
+        model.decoder.gemm_mode = mode
+        self.feats = S.make_features(B, T, sizes, seed=seed + 1)
+        self.bbox, self.feat = S.make_queries(B, Q, seed=seed + 2)
+        self.metas = S.make_img_metas(B, T, ih, iw) if metas is None else metas
+        self.mask = _dn_mask(Q) if use_mask else None
+        self.md = self.mask.to(DEV) if use_mask else None
+        g = torch.Generator().manual_seed(seed + 3)
+        self.cc, self.cb = torch.randn(1, B, Q, num_classes, generator=g), torch.randn(1, B, Q, 10, generator=g)
+        self._oracle = None
+
+    def camera_choices_differing(self):
+        """the camera choices of the device's sample points vs the oracle's (fp32: the projection is bit-exact with the device's)"""
+        import os
+        import tempfile
+        from sparsebev_amd.utils import DUMP
+        taps = []
+        with tempfile.TemporaryDirectory() as tmp:
+            DUMP.enabled, DUMP.out_dir = True, tmp
+            try:
+                with torch.no_grad():
+                    self.model.eval()(self.bbox.to(DEV), self.feat.to(DEV), [f.to(DEV) for f in self.feats], self.md, copy.deepcopy(self.metas))
+            finally:
+                DUMP.enabled = False
+                self.model.train()
+            valid = torch.load(os.path.join(tmp, 'sample_points_cam_valid_mask_stage0.pth'))
+        with torch.no_grad():
+            self.O.decoder(self.params, self.bbox, self.feat, self.feats, self.metas, self.pc_range, num_layers=1, num_points=self.P,
+                           pre_attn_mask=self.mask, taps=taps)
+        return (valid.cpu() != taps[0]['valid']).sum(dim=(1, 2, 3, 4)).tolist()           # per sample
+
+    def device(self, cc, cb):
+        model = self.model
+        model.zero_grad(set_to_none=True)
+        fd = self.feat.to(DEV).requires_grad_(True)
+        fsd = [f.to(DEV).requires_grad_(True) for f in self.feats]
+        cls, box = model(self.bbox.to(DEV), fd, list(fsd), self.md, copy.deepcopy(self.metas))
+        ((cls * cc.to(DEV)).sum() + (box * cb.to(DEV)).sum()).backward()
+        grads = [('query_feat', fd.grad)] + [(k_[len(PREFIX):], p.grad) for k_, p in model.named_parameters()]
+        grads += [('feat%d' % i, a.grad) for i, a in enumerate(fsd)]
+        return cls, box, [(k_, None if g_ is None else g_.detach().clone()) for k_, g_ in grads]
+
+    def oracle(self, cc, cb):
+        if self._oracle is None:
+            fo = self.feat.double().requires_grad_(True)
+            fso = [f.double().requires_grad_(True) for f in self.feats]
+            po = {k_: v_.double().requires_grad_(True) for k_, v_ in self.params.items()}
+            (c2, b2, _), self.pre = _relu_inputs_recorded(
+                lambda: self.O.decoder(po, self.bbox.double(), fo, fso, self.metas, self.pc_range, num_layers=1, num_points=self.P,
+                                       pre_attn_mask=self.mask))
+            names = ['query_feat'] + [k_[len(PREFIX):] for k_, _ in self.model.named_parameters()] + ['feat%d' % i for i in range(self.L)]
+            leaves = [fo] + [po[k_] for k_ in names[1:1 + len(po)]] + fso
+            self._oracle = (c2, b2, names, leaves)
+        c2, b2, names, leaves = self._oracle
+        grads = torch.autograd.grad((c2 * cc.double()).sum() + (b2 * cb.double()).sum(), leaves, retain_graph=True, allow_unused=True)
+        return c2, b2, list(zip(names, grads))
+
+
+def rel_l2(a, b):
+    a, b = a.detach().cpu().double(), b.detach().cpu().double()
+    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+
+
+def _one_layer_trained_vs_oracle(case, label):
+    """The recipe of test_one_layer_trained_at_the_trainval_shapes_vs_oracle_autograd (its docstring gives the reasons and the measured
+    figures) on a TrainedLayer: camera-hit masks equal first; then the outputs and the tensors with no mixing / camera decision between
+    them and the loss (norm3, both branches) to 1e-5, every tensor norm-wise to 5e-3, max-abs median 5e-3 and worst 5e-2 -- and, when no
+    mixing ReLU input lies within fp32 reach of zero, every tensor to 1e-4.  Returns the number of such ReLU inputs."""
+    n_cam = case.camera_choices_differing()
+    assert sum(n_cam) == 0, 'camera choices differ, per sample: %s' % n_cam
+    cls, box, got = case.device(case.cc, case.cb)
+    c2, b2, want = case.oracle(case.cc, case.cb)
+    assert len(case.pre) == 9                   # position encoder 2, mixing 2, FFN 1, cls branch 2, reg branch 2
+    mix_near = sum(int(((t != 0) & (t.abs() < 1e-5)).sum()) for t in case.pre[2:4])
+    out_err = max(rel(cls, c2), rel(box, b2))
+    pairs = [(k_, a, b) for (k_, a), (k2, b) in zip(got, want)]
+    assert [k_ for k_, _ in got] == [k_ for k_, _ in want]
+    assert len(pairs) == 1 + 48 + case.L and all(a is not None and b is not None for _, a, b in pairs)
+    l2 = {k_: rel_l2(a, b) for k_, a, b in pairs}
+    mx = {k_: rel(a, b) for k_, a, b in pairs}
+    down = {k_: v_ for k_, v_ in mx.items() if 'cls_branch' in k_ or 'reg_branch' in k_ or 'norm3' in k_}
+    vals = sorted(mx.values())
+    report = sorted(((k_, l2[k_], mx[k_]) for k_ in l2), key=lambda t: -t[1])[:4]
+    print('train layer %s T=%d P=%d %s mask=%d: mixing ReLU inputs 0 < |h| < 1e-5: %d; out %.2e  downstream %.2e  worst l2 %.2e  '
+          'median max-abs %.2e  worst max-abs %.2e  %s' % (label, case.T, case.P, case.mode, case.use_mask, mix_near, out_err, max(down.values()),
+                                                           max(l2.values()), vals[len(vals) // 2], vals[-1], report))
+    if mix_near == 0:
+        assert vals[-1] < 1e-4 and out_err < 1e-4, report
+    assert out_err < 1e-5 and max(down.values()) < 1e-5, report
+    assert max(l2.values()) < 5e-3, report
+    assert vals[len(vals) // 2] < 5e-3 and vals[-1] < 5e-2, report
+    return mix_near
+
+
 @torch.enable_grad()
 @pytest.mark.parametrize('P,mode,use_mask', [(4, 'f16x3', False), (4, 'f32', True), (8, 'f16x3', True), (8, 'f32', False)])
 def test_one_layer_trained_at_the_trainval_shapes_vs_oracle_autograd(P, mode, use_mask):
@@ -296,72 +404,5 @@ def test_one_layer_trained_at_the_trainval_shapes_vs_oracle_autograd(P, mode, us
     them and the loss (norm3, both branches) to 1e-5 (measured worst 1.4e-6), every tensor NORM-wise to 5e-3 (measured worst 9.8e-4),
     max-abs median tensor 5e-3 (measured 5.0e-4) and worst 5e-2 (measured 1.4e-2, the generator weight); when none exist, every
     tensor to G11's 1e-4."""
-    import os
-    import tempfile
-    from oracle import sparsebev_oracle as O
-    from sparsebev_amd.utils import DUMP
-    B, Q, T, L = 2, 49, 15, 5
-    ih, iw, sizes = S.PYRAMIDS['tiny5']
     seed = 600 + 10 * P + use_mask
-    params = S.make_params(seed, embed_dims=256, num_frames=T, num_points=P, num_levels=L)
-    model = build(T, L, seed, 1, num_points=P).train()
-    model.decoder.decoder_layer.self_attn.attn_drop = 0.0
-    model.decoder.decoder_layer.ffn_drop = 0.0
-    model.decoder.gemm_mode = mode
-    feats = S.make_features(B, T, sizes, seed=seed + 1)
-    bbox, feat = S.make_queries(B, Q, seed=seed + 2)
-    metas = S.make_img_metas(B, T, ih, iw)
-    mask = _dn_mask(Q) if use_mask else None
-    md = mask.to(DEV) if use_mask else None
-    # (1) the camera choices of the device's sample points vs the oracle's (fp32: the projection is bit-exact with the device's)
-    taps = []
-    with tempfile.TemporaryDirectory() as tmp:
-        DUMP.enabled, DUMP.out_dir = True, tmp
-        try:
-            with torch.no_grad():
-                model.eval()(bbox.to(DEV), feat.to(DEV), [f.to(DEV) for f in feats], md, copy.deepcopy(metas))
-        finally:
-            DUMP.enabled = False
-            model.train()
-        valid = torch.load(os.path.join(tmp, 'sample_points_cam_valid_mask_stage0.pth'))
-    with torch.no_grad():
-        O.decoder(params, bbox, feat, feats, metas, S.PC_RANGE, num_layers=1, num_points=P, pre_attn_mask=mask, taps=taps)
-    n_cam = int((valid.cpu() != taps[0]['valid']).sum())
-    assert n_cam == 0, n_cam
-    # forward + backward on the device
-    g = torch.Generator().manual_seed(seed + 3)
-    cc, cb = torch.randn(1, B, Q, 10, generator=g), torch.randn(1, B, Q, 10, generator=g)
-    fd = feat.to(DEV).requires_grad_(True)
-    fsd = [f.to(DEV).requires_grad_(True) for f in feats]
-    cls, box = model(bbox.to(DEV), fd, list(fsd), md, copy.deepcopy(metas))
-    ((cls * cc.to(DEV)).sum() + (box * cb.to(DEV)).sum()).backward()
-    # the fp64 oracle, its ReLU inputs recorded
-    fo = feat.double().requires_grad_(True)
-    fso = [f.double().requires_grad_(True) for f in feats]
-    po = {k_: v_.double().requires_grad_(True) for k_, v_ in params.items()}
-    (c2, b2, _), pre = _relu_inputs_recorded(
-        lambda: O.decoder(po, bbox.double(), fo, fso, metas, S.PC_RANGE, num_layers=1, num_points=P, pre_attn_mask=mask))
-    ((c2 * cc.double()).sum() + (b2 * cb.double()).sum()).backward()
-    assert len(pre) == 9                        # position encoder 2, mixing 2, FFN 1, cls branch 2, reg branch 2
-    mix_near = sum(int(((t != 0) & (t.abs() < 1e-5)).sum()) for t in pre[2:4])
-    out_err = max(rel(cls, c2), rel(box, b2))
-
-    def rel_l2(a, b):
-        a, b = a.detach().cpu().double(), b.detach().cpu().double()
-        return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
-    pairs = [('query_feat', fd.grad, fo.grad)] + [(k_[len(PREFIX):], p.grad, po[k_[len(PREFIX):]].grad) for k_, p in model.named_parameters()]
-    pairs += [('feat%d' % i, a.grad, b.grad) for i, (a, b) in enumerate(zip(fsd, fso))]
-    assert len(pairs) == 1 + 48 + L and all(a is not None and b is not None for _, a, b in pairs)
-    l2 = {k_: rel_l2(a, b) for k_, a, b in pairs}
-    mx = {k_: rel(a, b) for k_, a, b in pairs}
-    down = {k_: v_ for k_, v_ in mx.items() if 'cls_branch' in k_ or 'reg_branch' in k_ or 'norm3' in k_}
-    vals = sorted(mx.values())
-    report = sorted(((k_, l2[k_], mx[k_]) for k_ in l2), key=lambda t: -t[1])[:4]
-    print('train layer T=%d P=%d %s mask=%d: mixing ReLU inputs 0 < |h| < 1e-5: %d; out %.2e  downstream %.2e  worst l2 %.2e  '
-          'median max-abs %.2e  worst max-abs %.2e  %s' % (T, P, mode, use_mask, mix_near, out_err, max(down.values()), max(l2.values()),
-                                                           vals[len(vals) // 2], vals[-1], report))
-    if mix_near == 0:
-        assert vals[-1] < 1e-4 and out_err < 1e-4, report
-    assert out_err < 1e-5 and max(down.values()) < 1e-5, report
-    assert max(l2.values()) < 5e-3, report
-    assert vals[len(vals) // 2] < 5e-3 and vals[-1] < 5e-2, report
+    _one_layer_trained_vs_oracle(TrainedLayer(2, 49, 15, 'tiny5', P, mode, use_mask, seed), 'trainval')

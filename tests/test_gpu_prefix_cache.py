@@ -3,7 +3,8 @@ attention and parameter generator read the queries and the weights only; a step 
 launches and reads what the step that stored them left in the cache.  The reference for every comparison is the SAME model with the
 cache forced off (runtime.prefix_cache(False): the force word, same launches, same captures); outputs are compared as int32 views.
 Shapes: `tiny` pyramid, T = 2, 2 layers; Q = 36, B = 1 (one 32-row fragment + 4, a 4-row chain tail) and Q = 49, B = 2 (98 rows: the
-sample boundary falls inside a 32-query attention block).  Every case runs on the eager runtime and on replayed steps."""
+sample boundary falls inside a 32-query attention block); the watch launch's second pass and leftover words at Q = 289, B = 1.  Every
+case runs on the eager runtime and on replayed steps."""
 import copy
 
 import pytest
@@ -250,3 +251,40 @@ def test_queries_with_a_nan_repeat_bit_for_bit(B, Q, graph):
     n0 = r.counters()
     assert same(r.call(), want) and same(r.call(bbox=r.bbox.clone(), feat=r.feat.clone()), want)
     assert r.delta(n0) == (2, 0)
+
+
+def test_one_bit_changes_where_the_watch_launch_loops_and_in_its_leftover_words(graph):
+    """B = 1, Q = 289 (17 x 17): the watch launch compares 16 bytes per thread with 64 workgroups of 256 threads, so query_feat -- 289 * 256
+    words = 18 496 chunks -- takes a second pass from chunk 16 384 on (word 65 536), every workgroup sees data, and query_bbox -- an odd
+    number of rows of 10 words -- leaves words 2888 and 2889 behind its last chunk.  One word at a time changes by its lowest mantissa
+    bit, or from +0.0 to -0.0 (equal as floats, another bit pattern): each must count as exactly one miss, give the outputs of the same
+    call with the cache off, and be followed by a hit on clones of the changed queries."""
+    B, Q = 1, 289
+    r = Rig(B, Q, graph)
+    n_bbox, n_feat = B * Q * 10, B * Q * 256
+    assert n_bbox % 4 == 2 and n_feat // 4 > 64 * 256
+    zero_feat, zero_bbox = 70000, n_bbox - 1                        # a second-pass word and the last leftover word start as +0.0
+    r.feat.view(-1)[zero_feat] = 0.0
+    r.bbox.view(-1)[zero_bbox] = 0.0
+    want = r.ref()
+    r.settle()
+    n0 = r.counters()
+    assert same(r.call(bbox=r.bbox.clone(), feat=r.feat.clone()), want)
+    assert r.delta(n0) == (1, 0)
+    LOW, SIGN = 1, -0x80000000
+    flips = [('bbox', 0, LOW), ('bbox', n_bbox - 2, LOW), ('bbox', zero_bbox, SIGN),
+             ('feat', 65535, LOW), ('feat', 65536, LOW), ('feat', 63 * 256 * 4, LOW), ('feat', n_feat - 1, LOW), ('feat', zero_feat, SIGN)]
+    for which, word, bit in flips:
+        bbox, feat = r.bbox.clone(), r.feat.clone()
+        t = (bbox if which == 'bbox' else feat).view(-1).view(torch.int32)
+        before = int(t[word])
+        t[word] = t[word] ^ bit
+        assert int(t[word]) != before and (bit == LOW or (before == 0 and float((bbox if which == 'bbox' else feat).view(-1)[word]) == 0.0))
+        n0 = r.counters()
+        got = r.call(bbox=bbox, feat=feat)
+        assert r.delta(n0) == (0, 1), (which, word, 'a changed word went unnoticed' if r.delta(n0)[1] == 0 else 'more than one miss')
+        assert same(got, r.ref(bbox=bbox, feat=feat)), (which, word)
+        n0 = r.counters()
+        assert same(r.call(bbox=bbox.clone(), feat=feat.clone()), got), (which, word)
+        assert r.delta(n0) == (1, 0), (which, word, 'the call after a miss')
+        r.bbox, r.feat = bbox, feat

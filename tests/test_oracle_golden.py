@@ -164,6 +164,49 @@ def forced_layer_inputs(g):
     return [(g['query_bbox'], g['query_feat'])] + [(g['out_bbox'][i - 1], g['out_feat'][i - 1]) for i in range(1, n)]
 
 
+def g14_inputs():
+    """Fixture G14 and the inputs it was recorded on: (g, params, feats, metas, pc_range, num_classes).  The metas are rebuilt from
+    the stored float64 matrices and timestamps; that synthetic.make_img_metas_per_sample still produces them is asserted."""
+    g = load_golden('g14_decoder_asym')
+    B, Q, T, L = [int(v) for v in g['cfg']]
+    seeds = [int(v) for v in g['seeds']]
+    nc = int(g['num_classes'])
+    ih, iw, sizes = S.PYRAMIDS[str(g['pyramid'])]
+    params = S.make_params(seeds[0], embed_dims=256, num_frames=T, num_points=4, num_levels=L, num_classes=nc)
+    assert abs(S.checksum(params) - float(g['params_checksum'])) < 1e-6 * float(g['params_checksum'])
+    feats = S.make_features(B, T, sizes, seed=seeds[2])
+    assert abs(S.checksum(feats) - float(g['feats_checksum'])) < 1e-6 * float(g['feats_checksum'])
+    l2i, ts = g['lidar2img'].numpy(), g['timestamps'].numpy()
+    assert l2i.dtype == np.float64 and l2i.shape == (B, T * 6, 4, 4)
+    metas = [dict(img_timestamp=[float(v) for v in ts[b]], lidar2img=[l2i[b, i].copy() for i in range(T * 6)],
+                  img_shape=[(ih, iw, 3)] * (T * 6)) for b in range(B)]
+    again = S.make_img_metas_per_sample(B, T, ih, iw)
+    assert np.array_equal(np.asarray([m['lidar2img'] for m in again]), l2i)
+    assert np.array_equal(np.array([m['img_timestamp'] for m in again]), ts)
+    pc_range = [float(v) for v in g['pc_range']]
+    assert pc_range == S.PC_RANGE_ASYM
+    return g, params, feats, metas, pc_range, nc
+
+
+def test_g14_decoder_per_sample_cameras_asymmetric_range_seven_classes():
+    """Fixture G14 = the reference's SparseBEVTransformer.forward, 2 layers, B = 3 with a camera pose and a frame spacing per sample,
+    an x / y-asymmetric pc_range and 7 classes beside the 10 box columns: both samplers of the oracle, teacher-forced and free-running,
+    at G7's bound (measured worst: grid_sample 1.4e-6 cls / 3.3e-7 box / 4.8e-6 feat, kernel semantics 2.4e-6 / 8.6e-7 / 1.2e-5)."""
+    g, params, feats, metas, pc_range, nc = g14_inputs()
+    B, Q, T, L = [int(v) for v in g['cfg']]
+    assert g['out_cls'].shape == (2, B, Q, nc) and g['out_bbox'].shape == (2, B, Q, 10)
+    td = O.time_diff_from_metas(metas, B)
+    assert float((td[1:, 1] - td[:-1, 1]).abs().min()) >= 0.1            # the velocity divisor differs from sample to sample
+    for sampler in (O.msmv_sampling_gridsample, O.msmv_sampling_kernel_semantics):
+        for forced in (forced_layer_inputs(g), None):
+            cls, box, feat = O.decoder(params, g['query_bbox'], g['query_feat'], feats, metas, pc_range, num_layers=2,
+                                       sampler=sampler, forced_inputs=forced)
+            for what, a, r in (('cls', cls, g['out_cls']), ('box', box, g['out_bbox']), ('feat', feat, g['out_feat'])):
+                err = (a - r).abs().amax(dim=(0, 2, 3))
+                assert err.max() < TOL, '%s %s %s: worst sample %d, per sample %s' % (
+                    sampler.__name__, 'forced' if forced else 'free', what, int(err.argmax()), err.tolist())
+
+
 # ---- the C half of the oracle (oracle/msmv_oracle.c) against the same golden vectors ----------------------
 @pytest.mark.parametrize('tag', ['L4_C8', 'L5_C64', 'L4_C16_P7'])
 def test_c_oracle_sampler(tag):
