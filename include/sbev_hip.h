@@ -964,12 +964,15 @@ int sbev_profile_stride(int every_n_calls);
 int sbev_profile_read(int kind, float* ms, int max_n);
 
 /*
- * The same insert for a step that brings SEVERAL frames per sample, in the memory the backbone emits: one launch for n_frames frame sets x
- * n_levels levels x B samples.  Source (k, l) -- frame set k of the step's offered window positions, level l -- is src[k * n_levels + l]
- * (table == NULL) or table[index[k * n_levels + l]] read on the device when the kernel starts (src == NULL); exactly one of the two forms,
- * 1 <= n_frames <= SBEV_MAX_FRAMES.  src_layout (enum sbev_frames_layout), one value per call: SBEV_FRAMES_NCHW = [B, n_views, channels,
- * hw_pixels[l]], SBEV_FRAMES_NHWC = channels-last [B, n_views, hw_pixels[l], channels].  insert is a device int32 [n_frames, B]: sample b's
- * frame of set k goes to slot insert[k * B + b] of out[l] = [B, n_slots, n_views, hw_pixels[l], channels]; an entry outside [0, n_slots) --
+ * The keyed frame pool's insert: a step's NEW frames into their slots, in the memory the backbone emits, recordable inside a captured step:
+ * one launch for n_frames frame sets x n_levels levels x B samples.  Source (k, l) -- frame set k of the step's offered window positions,
+ * level l -- is src[k * n_levels + l] (table == NULL) or table[index[k * n_levels + l]] read on the device when the kernel starts (src ==
+ * NULL; the device pointer table of a replayable step, see sbev_nchw_to_nhwc_f32_indirect); exactly one of the two forms,
+ * 1 <= n_frames <= SBEV_MAX_FRAMES, 1 <= n_levels <= SBEV_MAX_LEVELS; index and src are host arrays of n_frames * n_levels entries, out and
+ * hw_pixels of n_levels.  src_layout (enum sbev_frames_layout), one value per call: SBEV_FRAMES_NCHW = [B, n_views, channels,
+ * hw_pixels[l]], SBEV_FRAMES_NHWC = channels-last [B, n_views, hw_pixels[l], channels].  insert is a device int32 [n_frames, B], refreshed
+ * by the host per step like the slot table of sbev_msmv_fwd_pool: sample b's frame of set k goes to slot insert[k * B + b] of the pool's
+ * resident buffer out[l] = [B, n_slots, n_views, hw_pixels[l], channels]; an entry outside [0, n_slots) --
  * use -1 -- means none: nothing of that (k, b) is read or written.  Entries are NOT clamped: this launch writes.  Two live entries of one
  * sample must name DIFFERENT slots -- the host planner's duty (cache.SlotBook.plan_frames); the kernel cannot check it, and two frame
  * sets writing one slot race.  src_dtype -> dst_dtype (enum sbev_dtype): fp32 -> fp32; fp16 -> fp16 and bf16 -> bf16, moved as bytes;
@@ -986,18 +989,9 @@ int sbev_pool_insert_frames(const void* const* table, const int32_t* index, cons
                             int dst_dtype, const int32_t* insert, int n_slots, sbev_stream_t stream);
 
 /*
- * The keyed frame pool's insert: a step's NEW frames into their slots, in one launch for all levels and samples, recordable inside a
- * captured step.  Source level l is the backbone's NCHW map [B, n_views, channels, hw_pixels[l]] for the batch's newest images -- given
- * as src[l] (table == NULL), or as table[index[l]] read on the device when the kernel starts (src == NULL; the device pointer table of a
- * replayable step, see sbev_nchw_to_nhwc_f32_indirect); exactly one of the two forms.  Destination level l is the pool's resident
- * buffer out[l] = [B, n_slots, n_views, hw_pixels[l], channels]; sample b goes to slot insert[b] (device int32 [B], refreshed by the host
- * per step like the slot table of sbev_msmv_fwd_pool).  An entry outside [0, n_slots) -- use -1 -- means "no frame for this sample":
- * nothing of that sample is read or written.  Entries are NOT clamped: this launch writes.  dtype (enum sbev_dtype) is the storage of
- * both sides: fp32 -> fp32 slots, fp16 / bf16 -> slots of the same type, moved as bytes.  Any sizes (hw % 4 and channels % 4, or % 8
- * for 2-byte storage, select the vector tile per level); sources and destinations 16-byte aligned.  index, src, out, hw_pixels: host
- * arrays of n_levels entries (1 .. SBEV_MAX_LEVELS).  B == 0 is an empty call.
- * Replaces: the per-frame extract-then-cat of the reference's online mode (models/sparsebev.py:255-321) for the newest frame, and this
- *           library's own per-sample, per-level sbev_nchw_to_nhwc_* launches in front of a replayed step.
+ * One frame per sample: sbev_pool_insert_frames with n_frames = 1, SBEV_FRAMES_NCHW, src_dtype = dst_dtype = dtype and insert = [B] -- the
+ * same kernel, the same bytes.  Its refusals are worded for itself ("sbev_pool_insert: ...", "dtype", "level l", "plane too large"), and
+ * its size bound is channels * hw_pixels[l] <= INT32_MAX where the frames entry bounds channels * hw_pixels[l] * n_views.
  */
 int sbev_pool_insert(const void* const* table, const int32_t* index, const void* const* src, void* const* out, int n_levels,
                      const int32_t* hw_pixels, int B, int n_views, int channels, int dtype, const int32_t* insert, int n_slots,

@@ -200,25 +200,10 @@ class SlotBook:
         return rows
 
     def plan_step(self, keys):
-        """(rows, insert) of a streaming step whose only new frame per sample is the window's newest: the step's [B][T] slot table (as
-        ``table``) and per sample the slot that receives ``keys[b][0]``, or -1 when that frame is resident.  The newest key is the only
-        one that may be missing; it gets a slot by ``assign``'s rules.  Any other missing key raises the KeyError of ``table`` (those
-        frames go through put() first) and leaves the book as it was."""
-        saved = (self.B, {b: dict(m) for b, m in self.slots.items()}, {b: list(k) for b, k in self.needed.items()})
-        try:
-            keys = self._announce(keys)
-            insert = []
-            for b, row in enumerate(keys):
-                mine = self.slots.get(b, {})
-                absent = [k for k in self.needed[b] if k not in mine]
-                late = [k for k in absent if k != row[0]]
-                if late:
-                    raise KeyError('sample %d: frame %r is not in the pool and is not the step\'s newest (missing(keys) lists what to put() first)' % (b, late[0]))
-                insert.append(self.assign(b, row[0])[0] if absent else -1)
-            return self.table(keys), insert
-        except BaseException:
-            self.B, self.slots, self.needed = saved
-            raise
+        """(rows, insert) of a streaming step whose only new frame per sample is the window's newest: ``plan_frames(keys, [0])`` with its
+        one insert row unwrapped -- per sample the slot that receives ``keys[b][0]``, or -1 when that frame is resident."""
+        rows, insert = self.plan_frames(keys, [0])
+        return rows, insert[0]
 
     def plan_frames(self, keys, offered):
         """(rows, insert) of a streaming step that brings the frames of the window positions ``offered`` (any iterable of t; the caller
@@ -266,9 +251,10 @@ class FramePool:
 
     The streaming step -- one new frame per sample, the window's newest -- is ``step(keys, frames)`` instead: the frames are not stored
     by launches of this call but travel with the returned pyramid, and the decoder call moves them into their slots itself
-    (``sbev_pool_insert``, destinations read from a device row behind the slot table): inside the captured step when it is replayed.
-    ``stream(keys, frames)`` is the same for as many frames as the step lacks -- the scene's first window included -- in the memory the
-    backbone emits: NCHW or channels-last, 2-byte frames widened into fp32 slots (``sbev_pool_insert_frames``, still one launch)."""
+    (``sbev_pool_insert_frames``, destinations read from device rows behind the slot table): inside the captured step when it is
+    replayed.  ``stream(keys, frames)`` is the same for as many frames as the step lacks -- the scene's first window included -- in the
+    memory the backbone emits: NCHW or channels-last, 2-byte frames widened into fp32 slots (the same launch, still one); ``step`` is its
+    K = 1 case with a narrower rule for what travels."""
 
     def __init__(self, num_frames, n_slots=16, dtype=torch.float32):
         if dtype not in (torch.float32, torch.float16, torch.bfloat16):
@@ -338,20 +324,17 @@ class FramePool:
         return self._hand_out(PoolPyramid(self))
 
     def _insert_takes(self, frames):
-        """whether sbev_pool_insert takes these frames: contiguous NCHW memory of the slots' own type, 16-byte aligned (a step's pointer
-        table carries the addresses).  Channels-last memory and fp16 / bf16 frames for fp32 slots are _store_level's."""
+        """whether step() lets these frames travel with the pyramid: contiguous NCHW memory of the slots' own type, 16-byte aligned (a
+        step's pointer table carries the addresses).  Channels-last memory and fp16 / bf16 frames for fp32 slots are _store_level's."""
         return all(f.dtype == self.dtype and f.is_contiguous() and f.data_ptr() % 16 == 0 for f in frames)
 
     def step(self, keys, frames):
         """One streaming step: ``frames`` = list[L] of [B, 6, C, H_l, W_l] device tensors, the backbone's output for the batch's newest
         images (as FrameFeatureCache.push takes them); sample b's goes under ``keys[b][0]`` unless that key is resident.  Every other key
-        of the step must be resident (SlotBook.plan_step).  Slot table and insert row go up in one upload; the returned PoolPyramid carries
-        ``insert = (frames, insert row)``: the decoder call it is handed to moves the frames into their slots (sbev_pool_insert, inside
-        the captured step when that is replayed; PoolPyramid.materialise() for other readers).  The pyramid keeps the frames alive until
-        the next step() / pyramid(), which also ends its validity.  Frames the kernel does not take (channels-last memory, fp16 / bf16
-        for fp32 slots) are stored here and now as put() stores them, and the pyramid carries no insert."""
-        import numpy as np
-        from .transformer import _upload
+        of the step must be resident (SlotBook.plan_step).  It is ``stream(keys, {0: frames})`` with its own argument check and a
+        narrower rule for what travels (_insert_takes): the returned PoolPyramid carries ``FrameInsert(frames, insert row as [1, B],
+        False)``, and frames the rule does not take (channels-last memory, fp16 / bf16 for fp32 slots) are stored here and now as put()
+        stores them, the pyramid carrying no insert."""
         frames = list(frames)
         if not frames or not all(torch.is_tensor(f) and f.is_cuda and f.dim() == 5 and f.shape[1] == N_VIEWS and f.shape[0] == frames[0].shape[0]
                                  for f in frames):
@@ -359,26 +342,13 @@ class FramePool:
         keys = [list(row) for row in keys]
         if len(keys) != frames[0].shape[0]:
             raise ValueError('keys for %d samples, frames for %d' % (len(keys), frames[0].shape[0]))
-        if self.buffers is not None and (len(frames) != len(self.buffers) or any(
-                tuple(buf.shape[3:]) != (f.shape[3], f.shape[4], f.shape[2]) for f, buf in zip(frames, self.buffers))):
-            raise RuntimeError('frame features do not match the pool\'s levels')
-        rows, insert = self.book.plan_step(keys)
-        if self.buffers is None:
-            self._alloc([tuple(f.shape[2:]) for f in frames], frames[0].device)
-        in_step = self._insert_takes(frames)
-        if not in_step:
-            for b, slot in enumerate(insert):
-                if slot >= 0:
-                    for f, buf in zip(frames, self.buffers):
-                        _store_level(f[b:b + 1], [buf[b, slot]], self.dtype)
-            insert = [-1] * len(insert)
-        _upload(np.asarray([s for row in rows for s in row] + insert, dtype=np.int32), self._tables.device, out=self._tables)
-        return self._hand_out(PoolPyramid(self, (frames, self.insert_row) if in_step else None))
+        return self._feed(keys, [0], [frames], False if self._insert_takes(frames) else None)
 
     def _frames_layout(self, flat):
-        """what sbev_pool_insert_frames takes: frames of one type -- the slots' own, or fp16 / bf16 for fp32 slots -- in one layout, NCHW-
-        contiguous (False) or channels-last (True) memory, 16-byte aligned.  None: not taken (misaligned or non-contiguous memory, mixed
-        layouts or types, fp32 for 2-byte slots): those are _store_level's, which refuses what nothing here stores."""
+        """what stream() lets travel with the pyramid, which is all sbev_pool_insert_frames takes: frames of one type -- the slots' own,
+        or fp16 / bf16 for fp32 slots -- in one layout, NCHW-contiguous (False) or channels-last (True) memory, 16-byte aligned.  None: not
+        taken (misaligned or non-contiguous memory, mixed layouts or types, fp32 for 2-byte slots): those are _store_level's, which
+        refuses what nothing here stores."""
         dt = flat[0].dtype
         if any(f.dtype != dt or f.data_ptr() % 16 for f in flat) or not (dt == self.dtype or (self.dtype == torch.float32 and dt in (torch.float16, torch.bfloat16))):
             return None
@@ -392,20 +362,27 @@ class FramePool:
         """One streaming step that takes the frames as the backbone emits them, as many as the step lacks: ``frames`` maps a window
         position t to a list[L] of [B, 6, C, H_l, W_l] device tensors -- the batch's frames ``keys[b][t]`` -- NCHW-contiguous or channels-
         last memory, fp32 / fp16 / bf16 (2-byte frames for fp32 slots are widened exactly), one layout and type per call.  Every key of
-        the step that is not resident must be at one of the given positions (SlotBook.plan_frames).  Slot table and the [K, B] destination
-        rows (K = len(frames), ascending t; row 0 at ``insert_row``'s address) go up in one upload; the returned PoolPyramid carries a
-        ``FrameInsert``: the decoder call it is handed to moves the frames into their slots in ONE launch (sbev_pool_insert_frames, inside
-        the captured step when that is replayed; PoolPyramid.materialise() for other readers).  The pyramid keeps the frames alive until
-        the next stream() / step() / pyramid(), which also ends its validity.  Frames the kernel does not take (_frames_layout) are stored
-        here and now as put() stores them, and the pyramid carries no insert; what put() refuses raises here too."""
-        import numpy as np
-        from .transformer import _upload
+        the step that is not resident must be at one of the given positions (SlotBook.plan_frames).  Frames the kernel does not take
+        (_frames_layout) are stored here and now as put() stores them, and the pyramid carries no insert; what put() refuses raises here
+        too."""
         keys = [list(row) for row in keys]
         ts = sorted(frames)
         sets = [list(frames[t]) for t in ts]
         flat = [f for fs in sets for f in fs]
         if not flat or not all(torch.is_tensor(f) and f.is_cuda and f.dim() == 5 and f.shape[1] == N_VIEWS and f.shape[0] == len(keys) for f in flat):
             raise RuntimeError('frame features must be device tensors [B, 6, C, H, W], B = %d' % len(keys))
+        return self._feed(keys, ts, sets, self._frames_layout(flat))
+
+    def _feed(self, keys, ts, sets, nhwc):
+        """What step() and stream() do alike once their arguments are checked: ``sets[k]`` = the list[L] of frames for window position
+        ``ts[k]`` (ascending), ``nhwc`` = their layout for the insert kernel (False NCHW, True channels-last) or None where they take the
+        eager store.  Slot table and the [K, B] destination rows (row 0 at ``insert_row``'s address) go up in one upload; the returned
+        PoolPyramid carries a ``FrameInsert``: the decoder call it is handed to moves the frames into their slots in ONE launch
+        (sbev_pool_insert_frames, inside the captured step when that is replayed; PoolPyramid.materialise() for other readers).  The
+        pyramid keeps the frames alive until the next stream() / step() / pyramid(), which also ends its validity."""
+        import numpy as np
+        from .transformer import _upload
+        flat = [f for fs in sets for f in fs]
         chw = [tuple(f.shape[2:]) for f in sets[0]]
         if any([tuple(f.shape[2:]) for f in fs] != chw for fs in sets) or (self.buffers is not None and (
                 len(chw) != len(self.buffers) or any(tuple(buf.shape[3:]) != (h, w, c) for (c, h, w), buf in zip(chw, self.buffers)))):
@@ -413,7 +390,6 @@ class FramePool:
         rows, insert = self.book.plan_frames(keys, ts)
         if self.buffers is None:
             self._alloc(chw, flat[0].device)
-        nhwc = self._frames_layout(flat)
         if nhwc is None:
             for fs, row in zip(sets, insert):
                 for b, slot in enumerate(row):
@@ -422,7 +398,7 @@ class FramePool:
                             _store_level(f[b:b + 1], [buf[b, slot]], self.dtype)
             insert = [[-1] * len(row) for row in insert]
         B, K = len(keys), len(ts)
-        up = self._rows[:B * self.T + K * B]
+        up = self._rows[:B * self.T + K * B]         # (K = 1: ``_tables``)
         _upload(np.asarray([s for row in rows for s in row] + [s for row in insert for s in row], dtype=np.int32), up.device, out=up)
         pending = None if nhwc is None else FrameInsert(flat, up[B * self.T:].view(K, B), nhwc)
         return self._hand_out(PoolPyramid(self, pending))
@@ -438,7 +414,7 @@ class PoolPyramid(_SlotPyramid):
     def __init__(self, pool, insert=None):
         super().__init__(pool)
         self.slot_table = pool.slot_table
-        self.insert = insert           # FramePool.step(): (frames list[L] of [B, 6, C, H, W], device int32 [B]) still to be moved into their slots; stream(): a FrameInsert
+        self.insert = insert           # FramePool.step() / stream(): the FrameInsert (frames and their device rows) still to be moved into the slots
 
     def resident(self):
         """this view without the pending insert: what a captured step may hold (buffers and tables, none of the caller's frames)"""
@@ -448,18 +424,20 @@ class PoolPyramid(_SlotPyramid):
         return pyr
 
     def materialise(self):
-        """Enqueue the pending insert on the current stream (sbev_pool_insert / sbev_pool_insert_frames, direct sources).  Idempotent -- the same frames go to
-        the same slots -- and a no-op without one.  The decoder does this itself; for callers of ``sample`` outside it."""
+        """Enqueue the pending insert on the current stream (sbev_pool_insert_frames, direct sources).  Idempotent -- the same frames go
+        to the same slots -- and a no-op without one.  The decoder does this itself; for callers of ``sample`` outside it."""
         if self.insert is None:
             return
-        enqueue_insert(self.insert, self.levels, self.n_slots, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        ins = self.insert
+        pool_insert_frames(ins.frames, self.levels, ins.rows, self.n_slots, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), ins.nhwc)
 
     def sample(self, loc, w_bp, T, G):
         return ops.msmv_sampling_pool(self.levels, self.B, T, G, self.slot_table, self.n_slots, loc, w_bp)
 
 
 def pool_insert(frames, levels, row, n_slots, stream, table=None, index=None, check=True):
-    """sbev_pool_insert: ``frames`` list[L] of NCHW [B, 6, C, H_l, W_l] into the resident buffers ``levels`` ([B*n_slots*6, H_l, W_l, C] or
+    """sbev_pool_insert, the C entry for one NCHW frame set of the slots' own type (the pool itself goes through pool_insert_frames):
+    ``frames`` list[L] of NCHW [B, 6, C, H_l, W_l] into the resident buffers ``levels`` ([B*n_slots*6, H_l, W_l, C] or
     any view of the same memory), sample b into slot ``row[b]`` (device int32 [B]; outside [0, n_slots): none).  Sources are the frames'
     own addresses, or -- ``table`` (device pointer table) and ``index`` (list[L]) -- read from the table when the kernel starts; the
     frames then only give shapes and dtype.  ``check=False`` returns the status instead of raising on it (a caller inside a stream capture
@@ -500,12 +478,3 @@ def pool_insert_frames(frames, levels, rows, n_slots, stream, nhwc=False, table=
     if check:
         _lib.check(st, 'sbev_pool_insert_frames')
     return st
-
-
-def enqueue_insert(insert, levels, n_slots, stream, table=None, index=None, check=True):
-    """A pyramid's pending insert as its one launch: FramePool.step's pair through pool_insert, FramePool.stream's FrameInsert through
-    pool_insert_frames.  The one place that tells them apart (PoolPyramid.materialise and the captured step both come here)."""
-    if isinstance(insert, FrameInsert):
-        return pool_insert_frames(insert.frames, levels, insert.rows, n_slots, stream, insert.nhwc, table, index, check)
-    frames, row = insert
-    return pool_insert(frames, levels, row, n_slots, stream, table, index, check)

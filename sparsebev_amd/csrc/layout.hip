@@ -376,144 +376,16 @@ __global__ __launch_bounds__(256) void copy_indirect_kernel(const CopySegs a) {
     }
 }
 
-// ---- the frame pool's insert (sbev_pool_insert): a step's new frames into their slots, inside the captured step -------------------------
-// The backbone's output for the batch's newest images, level l = NCHW [B, n_views, R, S_l] (direct pointers, or table[index[l]] read when
-// the kernel starts: the replayable form), goes into the pool's resident buffers [B, n_slots, n_views, S_l, R]: sample b into slot
-// insert[b], a device int32 the host refreshes per step like the slot table the frames are later read through.  An entry outside
-// [0, n_slots) means "no frame for this sample": its workgroups return at once.  NOT clamped (msmv_pool_slot clamps a READ; a clamped
-// write would overwrite someone else's frame).  All levels and samples in ONE launch, blocks mapped as in transpose_tiles_multi_kernel;
-// the tile code is a second copy of transpose_tiles_kernel / transpose_tiles16_kernel, vector or scalar form chosen per level (bit l of
-// `vec`), so that those kernels come out of the compiler as they were.
-struct PoolInsertArgs {
-    const void* const* table;                    // null: src[] direct
-    int index[SBEV_MAX_LEVELS];
-    const void* src[SBEV_MAX_LEVELS];            // [B, n_views, R, S_l]
-    void* out[SBEV_MAX_LEVELS];                  // [B, n_slots, n_views, S_l, R]
-    const int* insert;                           // [B]
-    int S[SBEV_MAX_LEVELS];
-    unsigned tiles_s[SBEV_MAX_LEVELS];           // ceil(S / 64)
-    unsigned first_block[SBEV_MAX_LEVELS + 1];   // level l owns blocks [first_block[l], first_block[l + 1])
-    int n_levels, R, n_slots, n_views;
-    unsigned tiles_r;                            // ceil(R / 64) (fp32), ceil(R / 128) (2-byte)
-    unsigned vec;                                // bit l: level l takes the vector form
-};
-
-__device__ __forceinline__ void pool_insert_tile(const float* in, float* out, int R, int S, int r0, int s0, bool vec, float* tile) {
-    const int tid = threadIdx.x;
-    if (vec) {   // S % 4 == 0 and R % 4 == 0
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = r0 + (tid >> 4) + 16 * i, s = s0 + (tid & 15) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < R && s < S) v = *reinterpret_cast<const float4*>(in + (long long)r * S + s);
-            const int lr = (tid >> 4) + 16 * i, ls = (tid & 15) * 4;
-            tile[(ls + 0) * TLD + lr] = v.x;
-            tile[(ls + 1) * TLD + lr] = v.y;
-            tile[(ls + 2) * TLD + lr] = v.z;
-            tile[(ls + 3) * TLD + lr] = v.w;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int ls = (tid >> 4) + 16 * i, lr = (tid & 15) * 4;
-            const int s = s0 + ls, r = r0 + lr;
-            if (s < S && r < R) {
-                const float4 v = make_float4(tile[ls * TLD + lr], tile[ls * TLD + lr + 1], tile[ls * TLD + lr + 2], tile[ls * TLD + lr + 3]);
-                *reinterpret_cast<float4*>(out + (long long)s * R + r) = v;
-            }
-        }
-    } else {
-        for (int i = tid; i < TS * TS; i += 256) {
-            const int lr = i / TS, ls = i % TS;
-            const int r = r0 + lr, s = s0 + ls;
-            tile[ls * TLD + lr] = (r < R && s < S) ? in[(long long)r * S + s] : 0.f;
-        }
-        __syncthreads();
-        for (int i = tid; i < TS * TS; i += 256) {
-            const int ls = i / TS, lr = i % TS;
-            const int r = r0 + lr, s = s0 + ls;
-            if (r < R && s < S) out[(long long)s * R + r] = tile[ls * TLD + lr];
-        }
-    }
-}
-// 2-byte channels: 64 channel pairs x 64 pixels, the pair interleave of transpose_tiles16_kernel
-__device__ __forceinline__ void pool_insert_tile(const unsigned short* in, unsigned short* out, int R, int S, int r0, int s0, bool vec, float* tilef) {
-    unsigned* tile = reinterpret_cast<unsigned*>(tilef);             // tile[pixel][channel pair], T16_PX x T16_LD words
-    const int tid = threadIdx.x;
-    if (vec) {   // S % 4 == 0 and R % 8 == 0
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int cp = (tid >> 4) + 16 * i, q = tid & 15;
-            const int r = r0 + 2 * cp, s = s0 + 4 * q;
-            uint2 lo = make_uint2(0u, 0u), hi = make_uint2(0u, 0u);
-            if (r < R && s < S) {                                    // (R is even: r + 1 < R too)
-                lo = *reinterpret_cast<const uint2*>(in + (long long)r * S + s);
-                hi = *reinterpret_cast<const uint2*>(in + (long long)(r + 1) * S + s);
-            }
-            tile[(4 * q + 0) * T16_LD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x05040100u);
-            tile[(4 * q + 1) * T16_LD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x07060302u);
-            tile[(4 * q + 2) * T16_LD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x05040100u);
-            tile[(4 * q + 3) * T16_LD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x07060302u);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int px = (tid >> 4) + 16 * i, k = tid & 15;
-            const int s = s0 + px, r = r0 + 8 * k;
-            if (s < S && r < R) {
-                const unsigned* t = &tile[px * T16_LD + 4 * k];
-                *reinterpret_cast<uint4*>(out + (long long)s * R + r) = make_uint4(t[0], t[1], t[2], t[3]);
-            }
-        }
-    } else {
-        unsigned short* t16 = reinterpret_cast<unsigned short*>(tile);      // [pixel][2 * T16_LD] halves
-        for (int i = tid; i < 2 * T16_CP * T16_PX; i += 256) {
-            const int lr = i / T16_PX, ls = i % T16_PX;
-            const int r = r0 + lr, s = s0 + ls;
-            t16[ls * (2 * T16_LD) + lr] = (r < R && s < S) ? in[(long long)r * S + s] : (unsigned short)0;
-        }
-        __syncthreads();
-        for (int i = tid; i < 2 * T16_CP * T16_PX; i += 256) {
-            const int ls = i / (2 * T16_CP), lr = i % (2 * T16_CP);
-            const int r = r0 + lr, s = s0 + ls;
-            if (r < R && s < S) out[(long long)s * R + r] = t16[ls * (2 * T16_LD) + lr];
-        }
-    }
-}
-
-template <typename ET>
-__global__ __launch_bounds__(256) void pool_insert_kernel(const PoolInsertArgs a) {
-    static_assert(T16_PX * T16_LD == TS * TLD, "one LDS tile serves both element sizes");
-    __shared__ float tile[TS * TLD];
-    constexpr int TR = sizeof(ET) == 4 ? TS : 2 * T16_CP;            // channels per tile
-    int l = 0;
-#pragma unroll
-    for (int j = 1; j < SBEV_MAX_LEVELS; ++j)
-        if (j < a.n_levels && blockIdx.x >= a.first_block[j]) l = j;
-    unsigned rel = blockIdx.x - a.first_block[l];
-    const unsigned ts = a.tiles_s[l];
-    const unsigned per_img = ts * a.tiles_r;
-    const unsigned img = rel / per_img;                              // b * n_views + view
-    const unsigned b = img / (unsigned)a.n_views;
-    const int slot = __builtin_amdgcn_readfirstlane(a.insert[b]);    // one value per workgroup
-    if ((unsigned)slot >= (unsigned)a.n_slots) return;               // no frame for this sample: nothing read, nothing written
-    rel -= img * per_img;
-    const int r0 = (int)(rel / ts) * TR, s0 = (int)(rel % ts) * TS;
-    const int R = a.R, S = a.S[l];
-    const long long plane = (long long)R * S;
-    const ET* in = static_cast<const ET*>(a.table ? a.table[a.index[l]] : a.src[l]) + (long long)img * plane;
-    const long long dst_img = ((long long)b * a.n_slots + slot) * a.n_views + (img - b * (unsigned)a.n_views);
-    ET* out = static_cast<ET*>(a.out[l]) + dst_img * plane;
-    pool_insert_tile(in, out, R, S, r0, s0, ((a.vec >> l) & 1u) != 0u, tile);
-}
-
-// ---- several frames per step, channels-last and widened (sbev_pool_insert_frames) ------------------------------------------------------
-// The same launch for K frame sets: source (k, l) = the backbone's map of level l for window position k of the step's offered frames, NCHW
-// [B, n_views, R, S_l] or channels-last [B, n_views, S_l, R] (one layout per call), direct or table[index[k * L + l]]; sample b's frame of
-// set k goes to slot rows[k * B + b] -- outside [0, n_slots): none, its workgroups return at once; never clamped.  Two live entries of one
-// sample naming one slot would race: the host planner (cache.SlotBook.plan_frames) never produces them, the kernel cannot check.
+// ---- the frame pool's insert (sbev_pool_insert_frames, sbev_pool_insert): new frames into their slots, inside the captured step ---------
+// The backbone's output for K frame sets goes into the pool's resident buffers [B, n_slots, n_views, S_l, R]: source (k, l) = the map of
+// level l for window position k of the step's offered frames, NCHW [B, n_views, R, S_l] or channels-last [B, n_views, S_l, R] (one layout
+// per call), direct or table[index[k * L + l]] read when the kernel starts (the replayable form); sample b's frame of set k goes to slot
+// rows[k * B + b], a device int32 the host refreshes per step like the slot table the frames are later read through -- outside
+// [0, n_slots): none, its workgroups return at once.  NOT clamped (msmv_pool_slot clamps a READ; a clamped write would overwrite someone
+// else's frame).  Two live entries of one sample naming one slot would race: the host planner (cache.SlotBook.plan_frames) never produces
+// them, the kernel cannot check.  All sets, levels and samples in ONE launch, blocks of a set mapped as in transpose_tiles_multi_kernel.
 // MODE: 0 fp32 -> fp32, 1 two-byte -> the same two-byte type (bytes), 2 bf16 -> fp32, 3 fp16 -> fp32 (both exact).
-// NCHW goes through an LDS tile as in pool_insert_kernel (modes 2 and 3: the 2-byte tile, widened on the way out); channels-last is already in the slot's layout: 16 source bytes per thread straight through, no LDS.  grid = (blocks of one set, K).
+// NCHW goes through an LDS tile, vector or scalar form chosen per level (bit l of `vec`; modes 2 and 3: the 2-byte tile, widened on the way out); channels-last is already in the slot's layout: 16 source bytes per thread straight through, no LDS.  grid = (blocks of one set, K).
 struct PoolFramesArgs {
     const void* const* table;                                        // null: src[] direct
     int index[SBEV_MAX_FRAMES * SBEV_MAX_LEVELS];                    // [K][L]
@@ -543,8 +415,8 @@ __device__ __forceinline__ float4 widen_words(unsigned a, unsigned b) {      // 
                        widen_bits<F16>((unsigned short)(b & 0xffffu)), widen_bits<F16>((unsigned short)(b >> 16)));
 }
 
-// The NCHW tile code is this kernel's own copy, as pool_insert_kernel's is of the transpose kernels': sharing one inlined function between
-// two kernels moves the older kernel's register figures (profiles/pool_frames.json).  fp32: pool_insert_tile as it is.
+// The NCHW tile code is this kernel's own copy of transpose_tiles_kernel's / transpose_tiles16_kernel's: sharing one inlined function
+// between two kernels moves the older kernel's register figures (profiles/pool_frames.json).  fp32: that tile as it is.
 __device__ __forceinline__ void pool_frames_tile(const float* in, float* out, int R, int S, int r0, int s0, bool vec, float* tile) {
     const int tid = threadIdx.x;
     if (vec) {   // S % 4 == 0 and R % 4 == 0
@@ -583,7 +455,7 @@ __device__ __forceinline__ void pool_frames_tile(const float* in, float* out, in
         }
     }
 }
-// 2-byte channels in: pool_insert_tile's read phase (64 channel pairs x 64 pixels); on the way out a thread writes the 8 channels of its
+// 2-byte channels in: transpose_tiles16_kernel's read phase (64 channel pairs x 64 pixels, its pair interleave); on the way out a thread writes the 8 channels of its
 // pixel as they are (DT 2-byte: one 16-byte store) or widened (DT float: two)
 template <typename DT, bool F16>
 __device__ __forceinline__ void pool_frames_tile(const unsigned short* in, DT* out, int R, int S, int r0, int s0, bool vec, float* tilef) {
@@ -830,65 +702,27 @@ extern "C" int sbev_copy_indirect(const void* const* table, int nseg, const int3
     return sbev::check_launch("sbev_copy_indirect");
 }
 
-// The frame pool's insert (see PoolInsertArgs).  Every argument is checked before the first HIP call; B == 0 is an empty call.
-extern "C" int sbev_pool_insert(const void* const* table, const int32_t* index, const void* const* src, void* const* out, int n_levels,
-                                const int32_t* hw_pixels, int B, int n_views, int channels, int dtype, const int32_t* insert, int n_slots,
-                                sbev_stream_t stream) {
-    SBEV_REQUIRE(out && hw_pixels && insert, "sbev_pool_insert: null pointer");
-    SBEV_REQUIRE(n_levels >= 1 && n_levels <= SBEV_MAX_LEVELS, "sbev_pool_insert: L=%d not in 1..%d", n_levels, SBEV_MAX_LEVELS);
-    SBEV_REQUIRE(n_slots >= 1, "sbev_pool_insert: n_slots must be at least 1 (got %d)", n_slots);
-    SBEV_REQUIRE(dtype == SBEV_F32 || dtype == SBEV_BF16 || dtype == SBEV_F16, "sbev_pool_insert: dtype %d", dtype);
-    SBEV_REQUIRE((table != nullptr) != (src != nullptr), "sbev_pool_insert: give the sources as table + index or as src, not %s", table ? "both" : "neither");
-    SBEV_REQUIRE(!table || index, "sbev_pool_insert: null pointer (table without index)");
-    SBEV_REQUIRE(!table || (((uintptr_t)table) & 7) == 0, "sbev_pool_insert: unaligned pointer table");
-    SBEV_REQUIRE((((uintptr_t)insert) & 3) == 0, "sbev_pool_insert: insert must be 4-byte aligned");
-    SBEV_REQUIRE(B >= 0 && n_views >= 1 && channels >= 1, "sbev_pool_insert: bad sizes");
-    const int esize = dtype == SBEV_F32 ? 4 : 2;
-    const int tile_r = esize == 4 ? TS : 2 * T16_CP;
-    PoolInsertArgs a{};
-    a.table = table; a.insert = insert; a.n_levels = n_levels; a.R = channels; a.n_slots = n_slots; a.n_views = n_views;
-    a.tiles_r = (unsigned)((channels + tile_r - 1) / tile_r);
-    long long blocks = 0;
-    for (int l = 0; l < n_levels; ++l) {
-        SBEV_REQUIRE(hw_pixels[l] >= 1 && out[l] && (((uintptr_t)out[l]) & 15) == 0 && (table ? index[l] >= 0 : (src[l] && (((uintptr_t)src[l]) & 15) == 0)),
-                     "sbev_pool_insert: level %d (hw >= 1, 16-byte aligned source and destination)", l);
-        SBEV_REQUIRE((long long)channels * hw_pixels[l] <= 0x7fffffffLL, "sbev_pool_insert: level %d: plane too large", l);
-        if (table) a.index[l] = index[l]; else a.src[l] = src[l];
-        a.out[l] = out[l]; a.S[l] = hw_pixels[l];
-        if (hw_pixels[l] % 4 == 0 && channels % (esize == 4 ? 4 : 8) == 0) a.vec |= 1u << l;
-        a.tiles_s[l] = (unsigned)((hw_pixels[l] + TS - 1) / TS);
-        a.first_block[l] = (unsigned)blocks;
-        blocks += (long long)a.tiles_s[l] * a.tiles_r * B * n_views;
-        SBEV_REQUIRE(blocks <= 0x7fffffffLL, "sbev_pool_insert: too many tiles for one launch");
-    }
-    a.first_block[n_levels] = (unsigned)blocks;
-    if (B == 0) return SBEV_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (esize == 4) hipLaunchKernelGGL(pool_insert_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(pool_insert_kernel<unsigned short>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    return sbev::check_launch("sbev_pool_insert");
-}
-
-// K frame sets per step, NCHW or channels-last, same type or widened to fp32 (see PoolFramesArgs).  Every argument is checked before the
-// first HIP call; B == 0 is an empty call.
-extern "C" int sbev_pool_insert_frames(const void* const* table, const int32_t* index, const void* const* src, void* const* out, int n_frames,
-                                       int n_levels, const int32_t* hw_pixels, int B, int n_views, int channels, int src_layout, int src_dtype,
-                                       int dst_dtype, const int32_t* insert, int n_slots, sbev_stream_t stream) {
-    SBEV_REQUIRE(out && hw_pixels && insert, "sbev_pool_insert_frames: null pointer");
-    SBEV_REQUIRE(n_frames >= 1 && n_frames <= SBEV_MAX_FRAMES, "sbev_pool_insert_frames: K=%d not in 1..%d", n_frames, SBEV_MAX_FRAMES);
-    SBEV_REQUIRE(n_levels >= 1 && n_levels <= SBEV_MAX_LEVELS, "sbev_pool_insert_frames: L=%d not in 1..%d", n_levels, SBEV_MAX_LEVELS);
-    SBEV_REQUIRE(n_slots >= 1, "sbev_pool_insert_frames: n_slots must be at least 1 (got %d)", n_slots);
-    SBEV_REQUIRE(src_layout == SBEV_FRAMES_NCHW || src_layout == SBEV_FRAMES_NHWC, "sbev_pool_insert_frames: src_layout %d", src_layout);
-    SBEV_REQUIRE(src_dtype == SBEV_F32 || src_dtype == SBEV_BF16 || src_dtype == SBEV_F16, "sbev_pool_insert_frames: src_dtype %d", src_dtype);
-    SBEV_REQUIRE(dst_dtype == SBEV_F32 || dst_dtype == SBEV_BF16 || dst_dtype == SBEV_F16, "sbev_pool_insert_frames: dst_dtype %d", dst_dtype);
+// The frame pool's insert behind both entries (see PoolFramesArgs): K frame sets per step, NCHW or channels-last, same type or widened to
+// fp32.  Every argument is checked before the first HIP call; B == 0 is an empty call.  `single` (sbev_pool_insert) chooses only the
+// wording of a refusal and the size bound (one plane against one sample's frame), so that each entry refuses what it always has.
+static int pool_insert_impl(const char* who, bool single, const void* const* table, const int32_t* index, const void* const* src,
+                            void* const* out, int n_frames, int n_levels, const int32_t* hw_pixels, int B, int n_views, int channels,
+                            int src_layout, int src_dtype, int dst_dtype, const int32_t* insert, int n_slots, sbev_stream_t stream) {
+    SBEV_REQUIRE(out && hw_pixels && insert, "%s: null pointer", who);
+    SBEV_REQUIRE(n_frames >= 1 && n_frames <= SBEV_MAX_FRAMES, "%s: K=%d not in 1..%d", who, n_frames, SBEV_MAX_FRAMES);
+    SBEV_REQUIRE(n_levels >= 1 && n_levels <= SBEV_MAX_LEVELS, "%s: L=%d not in 1..%d", who, n_levels, SBEV_MAX_LEVELS);
+    SBEV_REQUIRE(n_slots >= 1, "%s: n_slots must be at least 1 (got %d)", who, n_slots);
+    SBEV_REQUIRE(src_layout == SBEV_FRAMES_NCHW || src_layout == SBEV_FRAMES_NHWC, "%s: src_layout %d", who, src_layout);
+    SBEV_REQUIRE(src_dtype == SBEV_F32 || src_dtype == SBEV_BF16 || src_dtype == SBEV_F16, single ? "%s: dtype %d" : "%s: src_dtype %d", who, src_dtype);
+    SBEV_REQUIRE(dst_dtype == SBEV_F32 || dst_dtype == SBEV_BF16 || dst_dtype == SBEV_F16, "%s: dst_dtype %d", who, dst_dtype);
     SBEV_REQUIRE(dst_dtype == src_dtype || dst_dtype == SBEV_F32,
-                 "sbev_pool_insert_frames: src_dtype %d into dst_dtype %d (slots take their own type, fp32 slots also fp16 / bf16 widened; nothing is narrowed)",
-                 src_dtype, dst_dtype);
-    SBEV_REQUIRE((table != nullptr) != (src != nullptr), "sbev_pool_insert_frames: give the sources as table + index or as src, not %s", table ? "both" : "neither");
-    SBEV_REQUIRE(!table || index, "sbev_pool_insert_frames: null pointer (table without index)");
-    SBEV_REQUIRE(!table || (((uintptr_t)table) & 7) == 0, "sbev_pool_insert_frames: unaligned pointer table");
-    SBEV_REQUIRE((((uintptr_t)insert) & 3) == 0, "sbev_pool_insert_frames: insert must be 4-byte aligned");
-    SBEV_REQUIRE(B >= 0 && n_views >= 1 && channels >= 1, "sbev_pool_insert_frames: bad sizes");
+                 "%s: src_dtype %d into dst_dtype %d (slots take their own type, fp32 slots also fp16 / bf16 widened; nothing is narrowed)",
+                 who, src_dtype, dst_dtype);
+    SBEV_REQUIRE((table != nullptr) != (src != nullptr), "%s: give the sources as table + index or as src, not %s", who, table ? "both" : "neither");
+    SBEV_REQUIRE(!table || index, "%s: null pointer (table without index)", who);
+    SBEV_REQUIRE(!table || (((uintptr_t)table) & 7) == 0, "%s: unaligned pointer table", who);
+    SBEV_REQUIRE((((uintptr_t)insert) & 3) == 0, "%s: insert must be 4-byte aligned", who);
+    SBEV_REQUIRE(B >= 0 && n_views >= 1 && channels >= 1, "%s: bad sizes", who);
     const bool nhwc = src_layout == SBEV_FRAMES_NHWC;
     const int ssize = src_dtype == SBEV_F32 ? 4 : 2;
     const int tile_r = ssize == 4 ? TS : 2 * T16_CP;
@@ -898,8 +732,9 @@ extern "C" int sbev_pool_insert_frames(const void* const* table, const int32_t* 
     long long blocks = 0;
     for (int l = 0; l < n_levels; ++l) {
         SBEV_REQUIRE(hw_pixels[l] >= 1 && out[l] && (((uintptr_t)out[l]) & 15) == 0,
-                     "sbev_pool_insert_frames: level %d (hw >= 1, 16-byte aligned destination)", l);
-        SBEV_REQUIRE((long long)channels * hw_pixels[l] * n_views <= 0x7fffffffLL, "sbev_pool_insert_frames: level %d: frame too large", l);
+                     single ? "%s: level %d (hw >= 1, 16-byte aligned source and destination)" : "%s: level %d (hw >= 1, 16-byte aligned destination)", who, l);
+        SBEV_REQUIRE((long long)channels * hw_pixels[l] * (single ? 1 : n_views) <= 0x7fffffffLL,
+                     single ? "%s: level %d: plane too large" : "%s: level %d: frame too large", who, l);
         a.out[l] = out[l]; a.S[l] = hw_pixels[l];
         a.first_block[l] = (unsigned)blocks;
         if (nhwc) {
@@ -912,12 +747,13 @@ extern "C" int sbev_pool_insert_frames(const void* const* table, const int32_t* 
             a.tiles_s[l] = (unsigned)((hw_pixels[l] + TS - 1) / TS);
             blocks += (long long)a.tiles_s[l] * a.tiles_r * B * n_views;
         }
-        SBEV_REQUIRE(blocks <= 0x7fffffffLL, "sbev_pool_insert_frames: too many tiles for one launch");
+        SBEV_REQUIRE(blocks <= 0x7fffffffLL, "%s: too many tiles for one launch", who);
     }
     a.first_block[n_levels] = (unsigned)blocks;
     for (int i = 0; i < n_frames * n_levels; ++i) {
-        SBEV_REQUIRE(table ? index[i] >= 0 : (src[i] && (((uintptr_t)src[i]) & 15) == 0),
-                     "sbev_pool_insert_frames: frame set %d level %d (16-byte aligned source, table index >= 0)", i / n_levels, i % n_levels);
+        const bool ok = table ? index[i] >= 0 : (src[i] && (((uintptr_t)src[i]) & 15) == 0);
+        if (single) SBEV_REQUIRE(ok, "%s: level %d (hw >= 1, 16-byte aligned source and destination)", who, i);
+        else SBEV_REQUIRE(ok, "%s: frame set %d level %d (16-byte aligned source, table index >= 0)", who, i / n_levels, i % n_levels);
         if (table) a.index[i] = index[i]; else a.src[i] = src[i];
     }
     if (B == 0) return SBEV_OK;
@@ -934,7 +770,22 @@ extern "C" int sbev_pool_insert_frames(const void* const* table, const int32_t* 
         default: SBEV_POOL_FRAMES_LAUNCH(3); break;
     }
 #undef SBEV_POOL_FRAMES_LAUNCH
-    return sbev::check_launch("sbev_pool_insert_frames");
+    return sbev::check_launch(who);
+}
+
+extern "C" int sbev_pool_insert_frames(const void* const* table, const int32_t* index, const void* const* src, void* const* out, int n_frames,
+                                       int n_levels, const int32_t* hw_pixels, int B, int n_views, int channels, int src_layout, int src_dtype,
+                                       int dst_dtype, const int32_t* insert, int n_slots, sbev_stream_t stream) {
+    return pool_insert_impl("sbev_pool_insert_frames", false, table, index, src, out, n_frames, n_levels, hw_pixels, B, n_views, channels,
+                            src_layout, src_dtype, dst_dtype, insert, n_slots, stream);
+}
+
+// One frame set, NCHW, of the slots' own type; `insert` = [B]
+extern "C" int sbev_pool_insert(const void* const* table, const int32_t* index, const void* const* src, void* const* out, int n_levels,
+                                const int32_t* hw_pixels, int B, int n_views, int channels, int dtype, const int32_t* insert, int n_slots,
+                                sbev_stream_t stream) {
+    return pool_insert_impl("sbev_pool_insert", true, table, index, src, out, 1, n_levels, hw_pixels, B, n_views, channels, SBEV_FRAMES_NCHW,
+                            dtype, dtype, insert, n_slots, stream);
 }
 
 // ---- the decoder step's last launch: stacked cls / bbox -> the caller's tensors, nan_to_num'ed ----------------------------------------

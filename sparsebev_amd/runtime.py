@@ -9,7 +9,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from .utils import FrameInsert, frame_source
+from .utils import frame_source
 
 MAX_LEVELS = 5
 GEMM_F32, GEMM_BF16X3, GEMM_BF16X6, GEMM_BF16X3S, GEMM_F16X3, GEMM_F16X4 = 0, 1, 2, 3, 4, 5      # sbev_gemm_mode
@@ -439,11 +439,11 @@ class DecoderRuntime:
 
 
 # What a captured step is keyed on (see StepGraphs): the queries' shapes, StepGraphs._feat_key (shapes of staged levels; addresses and the
-# slot mapping of levels read in place; the shapes of a frame-pool step's new frames and the address of their insert row), the mask's shape or None, DecoderRuntime._signature() of the bound weights, the device,
+# slot mapping of levels read in place; the shapes of a frame-pool step's new frames, the address of their insert rows, their count per sample and layout), the mask's shape or None, DecoderRuntime._signature() of the bound weights, the device,
 # _switch_key(), layer count and box range, the stream (a graph's workspace belongs to the stream it replays on) and ``finish``
 StepKey = namedtuple('StepKey', 'bbox feat feats mask weights device switches num_layers pc_range stream finish')
 # The tensors of one call whose addresses travel in the step's pointer table (outs: with ``finish`` the call's own (cls, bbox), else None;
-# frames: the new frames of a frame-pool step (FrameSource.insert's list), else None)
+# frames: the new frames of a frame-pool step (FrameSource.insert.frames), else None)
 StepInputs = namedtuple('StepInputs', 'bbox feat feats mask outs frames', defaults=(None,))
 
 
@@ -570,11 +570,11 @@ class StepGraphs(StepBook):
       * fp32 NCHW feature lists (the reference's layout) go through the in-graph relayout, whose source address also comes from
         the table (sbev_nchw_to_nhwc_f32_indirect) -- any tensors of the same shapes replay the same graph, and the graph pins
         none of the caller's tensors;
-      * the frame pool's streaming step (cache.FramePool.step) brings the batch's newest frames as NCHW maps: one in-graph launch
-        moves them into their slots (sbev_pool_insert), sources from the table, destinations from a device row the pool refreshes
-        with its slot table -- one graph per shape, whichever tensors the backbone hands over; FramePool.stream brings K frames per
-        sample, NCHW or channels-last, 2-byte ones widened (sbev_pool_insert_frames, K * L table entries, [K, B] rows): one graph per
-        offered shape -- typically one for K = 1 and one for a scene's first window;
+      * the frame pool's streaming step (cache.FramePool.stream) brings K new frames per sample, NCHW or channels-last, 2-byte ones
+        widened: one in-graph launch moves them into their slots (sbev_pool_insert_frames), K * L sources from the table, destinations
+        from [K, B] device rows the pool refreshes with its slot table -- one graph per offered shape, whichever tensors the backbone
+        hands over: typically one for K = 1 and one for a scene's first window.  FramePool.step is the K = 1 NCHW case and shares that
+        graph;
       * inputs that are read IN PLACE by the decoder kernels -- channels-last lists, FeaturePyramid / the online ring's buffers --
         keep their addresses in the key.  A tensor list is only captured when the SAME tensor objects come back (weak
         references from the first sighting: a recycled address of a dead tensor is not "the same input"), and while
@@ -600,13 +600,12 @@ class StepGraphs(StepBook):
             # their level tensors are views made per call, so there is no object identity to remember: MAX_WASTED bounds a caller
             # that builds a new pyramid over new buffers every step.  The ring's slot order is a by-value kernel argument: its VALUES
             # are part of the key (one graph per ring phase).  The pool's table is device memory the captured step reads on replay:
-            # its ADDRESS is, never its contents (one graph per shape).  A pool step's pending insert (FramePool.step) adds a launch to
-            # the step: the new frames' shapes and dtype and the ADDRESS of the insert row -- never the frames' addresses (they travel in
-            # the pointer table) nor the row's contents
+            # its ADDRESS is, never its contents (one graph per shape).  A pool step's pending insert (FramePool.step / stream) adds a
+            # launch to the step: the new frames' shapes and dtype, the ADDRESS of the insert rows, K and the layout -- all the launch
+            # depends on; never the frames' addresses (they travel in the pointer table) nor the rows' contents
             table = src.slot_table
-            # (FramePool.stream's FrameInsert: K and the layout too -- with every frame's shape and dtype that is all the launch depends on)
-            ins = None if src.insert is None else (tuple((tuple(f.shape), f.dtype) for f in src.insert[0]), src.insert[1].data_ptr()) + (
-                (src.insert.K, src.insert.nhwc) if isinstance(src.insert, FrameInsert) else ())
+            fi = src.insert
+            ins = None if fi is None else (tuple((tuple(f.shape), f.dtype) for f in fi.frames), fi.rows.data_ptr(), fi.K, fi.nhwc)
             return ('pyr', tuple((f.data_ptr(), tuple(f.shape), f.dtype) for f in feats.levels), src.frame_slots, src.n_slots,
                     None if table is None else (table.data_ptr(), tuple(table.shape)), ins), [], False
         if all(self._relayout_ok(f) for f in feats):
@@ -645,7 +644,7 @@ class StepGraphs(StepBook):
             nl, nc, cs = rt.decoder.num_layers, rt.decoder.decoder_layer.num_classes, rt.decoder.decoder_layer.code_size
             outs = (torch.empty(nl, B, Q, nc, device=query_bbox.device, dtype=torch.float32),
                     torch.empty(nl, B, Q, cs, device=query_bbox.device, dtype=torch.float32))
-        call = StepInputs(query_bbox, query_feat, mlvl_feats, attn_mask, outs, None if src.insert is None else src.insert[0])
+        call = StepInputs(query_bbox, query_feat, mlvl_feats, attn_mask, outs, None if src.insert is None else src.insert.frames)
         if verdict == CAPTURE:
             e = self._capture(key, call, consts, staged, src)
             if e is None:
@@ -719,8 +718,8 @@ class StepGraphs(StepBook):
     def _record(args, table, segs, relayout, finish, insert=None, prefix=None):
         """The step's launches under stream capture -> the instantiated graph's handle: the in-graph copies of ``segs`` (table index,
         graph-owned buffer), the relayout of the staged levels (on demand inside the step, all fp32 levels in one launch, or one launch
-        per level), -- ``insert``: (table indices, the pyramid's pending insert: shapes, dtype, layout and rows, pool pyramid) -- the frame pool's new frames
-        into their slots (sbev_pool_insert / sbev_pool_insert_frames, sources from the table), the decoder step, and -- ``finish``: the graph's (cls, box) -- the
+        per level), -- ``insert``: (table indices, the pyramid's pending FrameInsert, pool pyramid) -- the frame pool's new frames
+        into their slots (sbev_pool_insert_frames, sources from the table), the decoder step, and -- ``finish``: the graph's (cls, box) -- the
         nan_to_num into the call's own outputs.  All on the one capture stream, in this order.  ``prefix``: the step's PrefixCache or None.
         Raises when any of it fails, with the capture ended."""
         lib = _lib.load()
@@ -753,7 +752,7 @@ class StepGraphs(StepBook):
             if insert is not None and ok:
                 from . import cache
                 idx, pending, pool_pyr = insert
-                ok = cache.enqueue_insert(pending, pool_pyr.levels, pool_pyr.n_slots, sp, table=table, index=idx, check=False) == 0
+                ok = cache.pool_insert_frames(pending.frames, pool_pyr.levels, pending.rows, pool_pyr.n_slots, sp, pending.nhwc, table, idx, check=False) == 0
             if lazy:
                 lz = LazyFeats()
                 lz.table = table

@@ -60,9 +60,8 @@ VERSION = Version()
 
 
 class FrameInsert(NamedTuple):
-    """The pending insert of cache.FramePool.stream (FramePool.step's is the plain pair ``(frames, insert row)``; both read as
-    ``insert[0]`` = the tensors whose addresses travel in a step's pointer table, ``insert[1]`` = the device rows).  ``frames``: K * L
-    device tensors ``[B, 6, C, H_l, W_l]``, frame set k's levels at ``[k * L, (k + 1) * L)``, sets in ascending window position; ``rows``:
+    """The pending insert of cache.FramePool.stream and FramePool.step (K = 1, NCHW): ``frames`` = the tensors whose addresses travel in
+    a step's pointer table, ``rows`` = the device rows that say where they go.  ``frames``: K * L device tensors ``[B, 6, C, H_l, W_l]``, frame set k's levels at ``[k * L, (k + 1) * L)``, sets in ascending window position; ``rows``:
     device int32 ``[K, B]``, the slot sample b's frame of set k goes to (-1: none); ``nhwc``: the frames are channels-last memory (else
     NCHW-contiguous), one layout and one dtype per insert."""
     frames: list
@@ -78,9 +77,8 @@ class FrameSource(NamedTuple):
     """Where a decoder step's frames live.  ``kind``: 'list' (a feature list, no pyramid object), 'dense' (transformer.FeaturePyramid:
     frame t of sample b is image run b*T + t), 'ring' (cache.RingPyramid: slot ``frame_slots[t]`` of ``n_slots`` for the whole batch,
     passed to the kernels by value) or 'pool' (cache.PoolPyramid: slot ``slot_table[b, t]`` of ``n_slots``, a device table the kernels read).
-    ``insert`` (the pool only, else None): the step's pending insert ``(frames, insert row)`` -- list[L] of NCHW ``[B, 6, C, H_l, W_l]`` maps
-    the decoder call still has to move into slot ``row[b]`` of sample b (device int32 [B], -1: none) before any frame is read -- or a
-    ``FrameInsert`` (FramePool.stream: K frame sets, either layout)."""
+    ``insert`` (the pool only, else None): the step's pending ``FrameInsert`` -- K frame sets of ``[B, 6, C, H_l, W_l]`` maps the decoder
+    call still has to move into slot ``rows[k, b]`` of sample b (device int32 [K, B], -1: none) before any frame is read."""
     kind: str
     frame_slots: tuple = ()
     slot_table: object = None

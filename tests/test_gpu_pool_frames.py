@@ -262,6 +262,39 @@ def test_two_byte_pool_through_stream_equals_put():
         FramePool(T, n_slots=6, dtype=F16).stream(keys, {t: Frames(331, F32).at(keys, t) for t in range(T)})
 
 
+def test_step_and_stream_k1_share_one_graph():
+    """step(keys, new) is stream(keys, {0: new}): once the window is full, even steps go through step() and odd ones through stream(), new
+    frame tensors every step.  Both hand out a FrameInsert with K = 1, NCHW, the rows at the insert row's address, so the one graph
+    captured at step 1 (through stream()) is replayed by both; outputs are bitwise those of a put()-fed twin model at every step."""
+    B, Q, T, n_slots, steps = 2, 49, 4, 6, 8
+    ih, iw, _ = S.PYRAMIDS['tiny']
+    m_put, m_new = build(T, 29, graph=True), build(T, 29, graph=True)
+    frames = Frames(370)
+    bbox, feat = [t.to(DEV) for t in S.make_queries(B, Q, seed=30)]
+    metas = S.make_img_metas(B, T, ih, iw)
+    p_put, pool = FramePool(T, n_slots=n_slots), FramePool(T, n_slots=n_slots)
+    alive, through_step = [], []
+    for i in range(steps):
+        keys = [[(b, 0, max(i - t, 0)) for t in range(T)] for b in range(B)]      # one new frame per sample and step, no scene change
+        want = m_put(bbox, feat, put_feed(p_put, frames, keys), None, metas)
+        new = frames.at(keys, 0)                                         # allocated for this step and kept: no address comes back
+        alive.append(new)
+        through_step.append(i >= T - 1 and i % 2 == 0)
+        pyr = pool.step(keys, new) if through_step[-1] else pool.stream(keys, {0: new})
+        assert isinstance(pyr.insert, FrameInsert) and pyr.insert.K == 1 and pyr.insert.nhwc is False
+        assert pyr.insert.rows.data_ptr() == pool.insert_row.data_ptr() and tuple(pyr.insert.rows.shape) == (1, B)
+        assert all(s >= 0 for s in pyr.insert.rows.tolist()[0])
+        got = m_new(bbox, feat, pyr, None, metas)
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), i
+        assert torch.equal(pool.slot_table, p_put.slot_table) and got[0].abs().max() > 0
+    assert len({f[0].data_ptr() for f in alive}) == steps and through_step.count(True) >= 2
+    from sparsebev_amd.runtime import CapturedStep
+    sg = m_new.decoder._runtime.step_graphs
+    graphs = [v for v in sg.entries.values() if isinstance(v, CapturedStep)]
+    # step 0 is the shape's first sighting (eager), step 1 captures and launches, every later step replays -- whichever method fed it
+    assert sg.captures == 1 and len(graphs) == 1 and graphs[0].replays == steps - 2
+
+
 # ---- 3. the captured step holds none of the caller's frames --------------------------------------------------------------------------
 
 def test_captured_step_holds_none_of_the_callers_frames():

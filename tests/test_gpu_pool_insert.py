@@ -31,7 +31,8 @@ def stream():
 # ---- 1. the kernel against torch ---------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize('indirect', [False, True])
-@pytest.mark.parametrize('dtype,C', [(torch.float32, 256), (torch.float16, 256), (torch.bfloat16, 256), (torch.bfloat16, 64)])
+@pytest.mark.parametrize('dtype,C', [(torch.float32, 256), (torch.float16, 256), (torch.bfloat16, 256), (torch.bfloat16, 64),
+                                     (torch.float32, 7), (torch.bfloat16, 12)])          # (the last two: the scalar channel forms)
 def test_pool_insert_kernel_equals_torch(dtype, C, indirect):
     B, n_slots = 3, 4
     assert list(SIZES) == [(8, 22), (4, 11), (2, 6), (1, 3)]
@@ -59,6 +60,15 @@ def test_pool_insert_kernel_equals_torch(dtype, C, indirect):
         want[2, 0] = f[2].permute(0, 2, 3, 1).contiguous().view(ity)
         assert torch.equal(buf[0, 2], f[0].permute(0, 2, 3, 1)) and torch.equal(buf[2, 0], f[2].permute(0, 2, 3, 1))
         assert torch.equal(buf.view(ity), want)                                # ... and every other element of the buffer is untouched
+    # the frames entry with K = 1, NCHW, the same type is the same call: the same bytes in every level, untouched ones included
+    twins = [torch.empty_like(buf) for buf in bufs]
+    for twin in twins:
+        twin.view(ity).fill_(pat)
+    row = torch.tensor([2, -1, 0], device=DEV, dtype=torch.int32)
+    cache.pool_insert_frames(frames, twins, row.view(1, B), n_slots, stream())
+    torch.cuda.synchronize()
+    for buf, twin in zip(bufs, twins):
+        assert torch.equal(buf.view(ity), twin.view(ity))
     run([n_slots, -5, -1])                                                     # outside [0, n_slots): nothing is written, nothing is clamped
     for buf in bufs:
         assert bool((buf.view(ity) == pat).all())

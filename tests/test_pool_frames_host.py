@@ -117,7 +117,8 @@ def test_plan_frames_against_plan_step():
 
 def test_step_key_holds_k_shapes_dtype_layout_and_the_rows_address_not_the_frames():
     """what a captured step of FramePool.stream is keyed on (StepGraphs._feat_key), on host tensors: fresh frames of one shape give one
-    key; K, dtype, layout and the rows' address each give another; so does FramePool.step's pair over the same frames"""
+    key; K, dtype, layout and the rows' address each give another; FramePool.step's form of the insert -- the insert row viewed as [1, B] --
+    gives the key of stream()'s K = 1 form: the same address, one graph"""
     import torch
     from sparsebev_amd.runtime import StepGraphs
     from sparsebev_amd.utils import FrameInsert, frame_source
@@ -128,11 +129,11 @@ def test_step_key_holds_k_shapes_dtype_layout_and_the_rows_address_not_the_frame
     level, table, rows = torch.zeros(2 * 4 * 6, 2, 3, 8), torch.zeros(2, T, dtype=torch.int32), torch.zeros(T, 2, dtype=torch.int32)
     other_rows = torch.zeros(T, 2, dtype=torch.int32)
 
-    def key(K=1, nhwc=False, dtype=torch.float32, rows=rows, pair=False):
+    def key(K=1, nhwc=False, dtype=torch.float32, rows=rows, step=False):
         pyr = Pyr()
         pyr.levels, pyr.slot_table, pyr.n_slots = [level], table, 4
         frames = [torch.zeros(2, 6, 8, 2, 3, dtype=dtype) for _ in range(K)]          # new tensors every call
-        pyr.insert = (frames, rows[0]) if pair else FrameInsert(frames, rows[:K], nhwc)
+        pyr.insert = FrameInsert(frames, rows[0].view(1, -1) if step else rows[:K], nhwc)
         src = frame_source(pyr)
         assert src.kind == 'pool' and src.insert is pyr.insert
         part, ident, staged = StepGraphs._feat_key(None, pyr, src)
@@ -140,7 +141,8 @@ def test_step_key_holds_k_shapes_dtype_layout_and_the_rows_address_not_the_frame
         return part
 
     assert key() == key() and key(K=3) == key(K=3)
-    distinct = [key(), key(K=3), key(nhwc=True), key(dtype=torch.float16), key(rows=other_rows), key(pair=True)]
+    assert key(step=True) == key()
+    distinct = [key(), key(K=3), key(nhwc=True), key(dtype=torch.float16), key(rows=other_rows)]
     assert len(set(distinct)) == len(distinct)
     assert FrameInsert([], rows[:3], True).K == 3
 

@@ -3,9 +3,9 @@
 Both caches hold the same frames and take ONE new frame (6 NCHW images) per step, as ``bench.py --online`` does; the ring has
 n_slots = T = 8 (one captured graph per ring phase), the pool n_slots = 16 (one captured graph, the step's slot table uploaded into
 the pool's persistent device table).  A third leg feeds a pool of its own through ``FramePool.step``: the new frame goes into its slot
-inside the captured step (sbev_pool_insert) instead of through ``put``'s eager launches in front of it.  Two more legs take the frame as
-a channels_last fp16 backbone hands it over -- channels-last fp16 memory for fp32 slots: through ``FramePool.stream`` (one in-graph launch,
-sbev_pool_insert_frames, widening on the way) and, beside it, through ``FramePool.step``, which stores such frames by eager launches in
+inside the captured step (sbev_pool_insert_frames, K = 1) instead of through ``put``'s eager launches in front of it.  Two more legs take
+the frame as a channels_last fp16 backbone hands it over -- channels-last fp16 memory for fp32 slots: through ``FramePool.stream`` (the same
+in-graph launch, widening on the way) and, beside it, through ``FramePool.step``, which stores such frames by eager launches in
 front of the replay (B x L of them).  The legs run interleaved on one
 GPU, round by round, with the warm-up and timing discipline of bench.py: warm-up steps first (captures included), device synchronised,
 wall clock over ``--steps`` steps, device synchronised.  Prints one JSON line.  Usage: python tools/bench_pool.py [--steps 50] [--warmup 40] [--rounds 3] [--config c2]"""
