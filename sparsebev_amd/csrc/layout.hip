@@ -15,6 +15,153 @@ namespace {
 using sbev_ops::PosArgs;
 using sbev_ops::lin3_rows;
 
+// ---- the workgroup tile movers: every NCHW -> channels-last kernel of this file is address arithmetic plus one call ----------------------
+// A 256-thread workgroup moves one tile of the plane in[R][S] (R channels, S pixels) to out[S][R] through LDS.  The read phase and the
+// write phase each have a vector and a scalar form, chosen by two independent flags (constants in the dense kernels, per level in the
+// lazy and pool kernels): both read forms leave the same LDS image, so either composes with either write form behind the one barrier.
+// `vread` needs S % 4 == 0 and rows aligned to the access, `vwrite` needs R % 4 == 0 (2-byte input: R % 8 == 0) and a 16-byte aligned
+// `out`.  A mover does not end with a barrier: a caller that reuses its tile adds one.
+constexpr int TS = 64, TLD = 65;
+
+// widening of a 2-byte channel to fp32: bf16 (F16 false) or fp16 (F16 true), both exact
+template <bool F16>
+__device__ __forceinline__ float widen_bits(unsigned short v) {
+    if (F16) {
+        _Float16 h;
+        __builtin_memcpy(&h, &v, 2);
+        return (float)h;
+    }
+    return __uint_as_float((unsigned)v << 16);
+}
+template <bool F16>
+__device__ __forceinline__ float4 widen_words(unsigned a, unsigned b) {      // two words = four consecutive 2-byte channels
+    return make_float4(widen_bits<F16>((unsigned short)(a & 0xffffu)), widen_bits<F16>((unsigned short)(a >> 16)),
+                       widen_bits<F16>((unsigned short)(b & 0xffffu)), widen_bits<F16>((unsigned short)(b >> 16)));
+}
+
+// fp32: channels [r0, r0 + 64) x pixels [s0, s0 + 64); tile[pixel][channel], TS x TLD floats; 16-byte accesses in the vector forms
+__device__ __forceinline__ void move_tile_f32(const float* in, float* out, int R, int S, int r0, int s0, bool vread, bool vwrite, float* tile) {
+    const int tid = threadIdx.x;
+    if (vread) {
+        // thread -> (channel = tid/16 + 16*i, 4 pixels at (tid%16)*4)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = r0 + (tid >> 4) + 16 * i, s = s0 + (tid & 15) * 4;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (r < R && s < S) v = *reinterpret_cast<const float4*>(in + (long long)r * S + s);
+            const int lr = (tid >> 4) + 16 * i, ls = (tid & 15) * 4;
+            tile[(ls + 0) * TLD + lr] = v.x;
+            tile[(ls + 1) * TLD + lr] = v.y;
+            tile[(ls + 2) * TLD + lr] = v.z;
+            tile[(ls + 3) * TLD + lr] = v.w;
+        }
+    } else {                                   // e.g. a 10 x 25 level: rows that are not 16-byte aligned
+        for (int i = tid; i < TS * TS; i += 256) {
+            const int lr = i / TS, ls = i % TS;
+            const int r = r0 + lr, s = s0 + ls;
+            tile[ls * TLD + lr] = (r < R && s < S) ? in[(long long)r * S + s] : 0.f;
+        }
+    }
+    __syncthreads();
+    if (vwrite) {
+        // thread -> (pixel = tid/16 + 16*i, 4 channels at (tid%16)*4)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int ls = (tid >> 4) + 16 * i, lr = (tid & 15) * 4;
+            const int s = s0 + ls, r = r0 + lr;
+            if (s < S && r < R) {
+                const float4 v = make_float4(tile[ls * TLD + lr], tile[ls * TLD + lr + 1], tile[ls * TLD + lr + 2], tile[ls * TLD + lr + 3]);
+                *reinterpret_cast<float4*>(out + (long long)s * R + r) = v;
+            }
+        }
+    } else {
+        for (int i = tid; i < TS * TS; i += 256) {
+            const int ls = i / TS, lr = i % TS;
+            const int r = r0 + lr, s = s0 + ls;
+            if (r < R && s < S) out[(long long)s * R + r] = tile[ls * TLD + lr];
+        }
+    }
+}
+
+// 2-byte channels in (bf16 / fp16 STORAGE: bytes are moved, never interpreted): CP channel PAIRS [r0 / 2, r0 / 2 + CP) x 64 pixels;
+// tile[pixel][channel pair], 64 x (CP + 1) words.  A thread reads 4 consecutive pixels (8 bytes) of TWO neighbouring channels and
+// interleaves them into four (channel pair) words -- in NHWC the pair is adjacent, so the transposition itself is a plain 32-bit one --
+// and writes the 8 channels of one pixel: as they are (DT 2-byte: one 16-byte store) or widened (DT float, F16 says from which type:
+// two).  CP = 64: 128-byte runs on the read side, 256-byte runs on the write side.  The scalar read form stores the halves of those
+// very words.
+template <int CP, typename DT, bool F16>
+__device__ __forceinline__ void move_tile_b16(const unsigned short* in, DT* out, int R, int S, int r0, int s0, bool vread, bool vwrite, unsigned* tile) {
+    constexpr int LD = CP + 1, KP = CP / 4;                          // row stride in words, 16-byte pieces of a pixel's row
+    unsigned short* t16 = reinterpret_cast<unsigned short*>(tile);   // [pixel][2 * LD] halves
+    const int tid = threadIdx.x;
+    if (vread) {
+#pragma unroll
+        for (int i = 0; i < CP / 16; ++i) {
+            const int cp = (tid >> 4) + 16 * i, q = tid & 15;        // channel pair of the tile, pixel quad
+            const int r = r0 + 2 * cp, s = s0 + 4 * q;
+            uint2 lo = make_uint2(0u, 0u), hi = make_uint2(0u, 0u);
+            if (r < R && s < S) {                                    // (R is even: r + 1 < R too)
+                lo = *reinterpret_cast<const uint2*>(in + (long long)r * S + s);
+                hi = *reinterpret_cast<const uint2*>(in + (long long)(r + 1) * S + s);
+            }
+            // lo = channel r at pixels s .. s+3 (two per word), hi = channel r + 1: word (pixel) = lo16 | hi16 << 16
+            tile[(4 * q + 0) * LD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x05040100u);
+            tile[(4 * q + 1) * LD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x07060302u);
+            tile[(4 * q + 2) * LD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x05040100u);
+            tile[(4 * q + 3) * LD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x07060302u);
+        }
+    } else {
+        for (int i = tid; i < 2 * CP * TS; i += 256) {
+            const int lr = i / TS, ls = i % TS;
+            const int r = r0 + lr, s = s0 + ls;
+            t16[ls * (2 * LD) + lr] = (r < R && s < S) ? in[(long long)r * S + s] : (unsigned short)0;
+        }
+    }
+    __syncthreads();
+    if (vwrite) {
+#pragma unroll
+        for (int i = 0; i < CP / 16; ++i) {
+            const int px = tid / KP + (256 / KP) * i, k = tid % KP;  // pixel of the tile, 16-byte piece (4 pairs = 8 channels)
+            const int s = s0 + px, r = r0 + 8 * k;
+            if (s < S && r < R) {
+                const unsigned* t = &tile[px * LD + 4 * k];
+                DT* o = out + (long long)s * R + r;
+                if constexpr (sizeof(DT) == 2) {
+                    *reinterpret_cast<uint4*>(o) = make_uint4(t[0], t[1], t[2], t[3]);
+                } else {
+                    *reinterpret_cast<float4*>(o) = widen_words<F16>(t[0], t[1]);
+                    *reinterpret_cast<float4*>(o + 4) = widen_words<F16>(t[2], t[3]);
+                }
+            }
+        }
+    } else {
+        for (int i = tid; i < 2 * CP * TS; i += 256) {
+            const int ls = i / (2 * CP), lr = i % (2 * CP);
+            const int r = r0 + lr, s = s0 + ls;
+            if (r < R && s < S) {
+                if constexpr (sizeof(DT) == 2) out[(long long)s * R + r] = t16[ls * (2 * LD) + lr];
+                else out[(long long)s * R + r] = widen_bits<F16>(t16[ls * (2 * LD) + lr]);
+            }
+        }
+    }
+}
+
+// several segments (levels, copies) in one launch: segment j owns blocks [first[j], first[j + 1]); block_segment finds this block's.
+// The ranges go in BY VALUE: a kernel argument whose address is handed to a function keeps the pointers later loaded through it
+// generic (flat instead of global loads).
+template <int N>
+struct BlockRanges {
+    unsigned first[N + 1];
+};
+template <int N>
+__device__ __forceinline__ int block_segment(const BlockRanges<N> r, int n) {
+    int l = 0;
+#pragma unroll
+    for (int j = 1; j < N; ++j)
+        if (j < n && blockIdx.x >= r.first[j]) l = j;
+    return l;
+}
+
 struct TrArgs {
     const float* in;   // [N, R, S]   (R = channels, S = H*W pixels)
     float* out;        // [N, S, R]
@@ -25,77 +172,33 @@ struct TrArgs {
     int index;
 };
 
-constexpr int TS = 64, TLD = 65;
-
 template <bool VEC>
 __global__ __launch_bounds__(256) void transpose_tiles_kernel(const TrArgs a) {
-    __shared__ float tile[TS * TLD];                    // tile[pixel][channel]
-    const int tid = threadIdx.x;
-    const int s0 = blockIdx.x * TS, r0 = blockIdx.y * TS;
+    __shared__ float tile[TS * TLD];
     const long long img = blockIdx.z;
     const float* in = (a.table ? static_cast<const float*>(a.table[a.index]) : a.in) + img * a.R * a.S;
-    float* out = a.out + img * a.R * a.S;
-    if (VEC) {   // S % 4 == 0 and R % 4 == 0
-        // read: thread -> (channel = tid/16 + 16*i, 4 pixels at (tid%16)*4)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = r0 + (tid >> 4) + 16 * i, s = s0 + (tid & 15) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < a.R && s < a.S) v = *reinterpret_cast<const float4*>(in + (long long)r * a.S + s);
-            const int lr = (tid >> 4) + 16 * i, ls = (tid & 15) * 4;
-            tile[(ls + 0) * TLD + lr] = v.x;
-            tile[(ls + 1) * TLD + lr] = v.y;
-            tile[(ls + 2) * TLD + lr] = v.z;
-            tile[(ls + 3) * TLD + lr] = v.w;
-        }
-        __syncthreads();
-        // write: thread -> (pixel = tid/16 + 16*i, 4 channels at (tid%16)*4)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int ls = (tid >> 4) + 16 * i, lr = (tid & 15) * 4;
-            const int s = s0 + ls, r = r0 + lr;
-            if (s < a.S && r < a.R) {
-                const float4 v = make_float4(tile[ls * TLD + lr], tile[ls * TLD + lr + 1], tile[ls * TLD + lr + 2], tile[ls * TLD + lr + 3]);
-                *reinterpret_cast<float4*>(out + (long long)s * a.R + r) = v;
-            }
-        }
-    } else {
-        for (int i = tid; i < TS * TS; i += 256) {
-            const int lr = i / TS, ls = i % TS;
-            const int r = r0 + lr, s = s0 + ls;
-            tile[ls * TLD + lr] = (r < a.R && s < a.S) ? in[(long long)r * a.S + s] : 0.f;
-        }
-        __syncthreads();
-        for (int i = tid; i < TS * TS; i += 256) {
-            const int ls = i / TS, lr = i % TS;
-            const int r = r0 + lr, s = s0 + ls;
-            if (r < a.R && s < a.S) out[(long long)s * a.R + r] = tile[ls * TLD + lr];
-        }
-    }
+    // VEC: S % 4 == 0 and R % 4 == 0, 16-byte aligned planes
+    move_tile_f32(in, a.out + img * a.R * a.S, a.R, a.S, blockIdx.y * TS, blockIdx.x * TS, VEC, VEC, tile);
 }
 
 // All levels of a pyramid in ONE launch (round 5): the per-level launches of a step (4 at r50, 5 at r101 / eva02) spend a launch boundary each
 // and the small levels cannot fill the chip (8 x 22 pixels x 48 images: one short round); here block b belongs to the level whose block range
-// holds it -- levels in the caller's order, finest first, so that the coarse levels' few blocks run in the tail of the big one.  Same tile
-// code (transpose_tiles_kernel<true>: every level S % 4 == 0, R % 4 == 0), sources from the pointer table.
+// holds it -- levels in the caller's order, finest first, so that the coarse levels' few blocks run in the tail of the big one.  The vector
+// forms throughout (every level S % 4 == 0, R % 4 == 0), sources from the pointer table.
 struct TrMultiArgs {
     const void* const* table;
     int index[SBEV_MAX_LEVELS];
     float* out[SBEV_MAX_LEVELS];
     int S[SBEV_MAX_LEVELS];
     unsigned tiles_s[SBEV_MAX_LEVELS];           // ceil(S / TS)
-    unsigned first_block[SBEV_MAX_LEVELS + 1];   // level l owns blocks [first_block[l], first_block[l + 1])
+    BlockRanges<SBEV_MAX_LEVELS> blocks;         // level l's blocks
     int n_levels, R;
     unsigned tiles_r;                            // ceil(R / TS)
 };
 __global__ __launch_bounds__(256) void transpose_tiles_multi_kernel(const TrMultiArgs a) {
     __shared__ float tile[TS * TLD];
-    const int tid = threadIdx.x;
-    int l = 0;
-#pragma unroll
-    for (int j = 1; j < SBEV_MAX_LEVELS; ++j)
-        if (j < a.n_levels && blockIdx.x >= a.first_block[j]) l = j;
-    unsigned rel = blockIdx.x - a.first_block[l];
+    const int l = block_segment(a.blocks, a.n_levels);
+    unsigned rel = blockIdx.x - a.blocks.first[l];
     const unsigned ts = a.tiles_s[l];
     const unsigned per_img = ts * a.tiles_r;
     const long long img = rel / per_img;
@@ -103,35 +206,11 @@ __global__ __launch_bounds__(256) void transpose_tiles_multi_kernel(const TrMult
     const int r0 = (int)(rel / ts) * TS, s0 = (int)(rel % ts) * TS;
     const int R = a.R, S = a.S[l];
     const float* in = static_cast<const float*>(a.table[a.index[l]]) + img * R * S;
-    float* out = a.out[l] + img * R * S;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = r0 + (tid >> 4) + 16 * i, sx = s0 + (tid & 15) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (r < R && sx < S) v = *reinterpret_cast<const float4*>(in + (long long)r * S + sx);
-        const int lr = (tid >> 4) + 16 * i, ls = (tid & 15) * 4;
-        tile[(ls + 0) * TLD + lr] = v.x;
-        tile[(ls + 1) * TLD + lr] = v.y;
-        tile[(ls + 2) * TLD + lr] = v.z;
-        tile[(ls + 3) * TLD + lr] = v.w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int ls = (tid >> 4) + 16 * i, lr = (tid & 15) * 4;
-        const int sx = s0 + ls, r = r0 + lr;
-        if (sx < S && r < R) {
-            const float4 v = make_float4(tile[ls * TLD + lr], tile[ls * TLD + lr + 1], tile[ls * TLD + lr + 2], tile[ls * TLD + lr + 3]);
-            *reinterpret_cast<float4*>(out + (long long)sx * R + r) = v;
-        }
-    }
+    move_tile_f32(in, a.out[l] + img * R * S, R, S, r0, s0, true, true, tile);
 }
 
-// ---- the same relayout for 2-byte elements (bf16 / fp16 STORAGE: pure byte movement) ------------------------------------------------
-// An fp16 backbone (the reference's eval mode, val.py:115) or a bf16 neck emits [N, R, S] maps of 2-byte channels.  A workgroup moves
-// 128 channels x 64 pixels: a thread reads 4 consecutive pixels (8 bytes) of TWO neighbouring channels, interleaves them into four
-// (channel pair) words -- in NHWC the pair is adjacent, so the transposition itself is a plain 32-bit one through LDS -- and writes 16
-// bytes = 8 channels of one pixel: 128-byte runs on the read side, 256-byte runs on the write side.
+// ---- the same relayout for 2-byte elements: an fp16 backbone (the reference's eval mode, val.py:115) or a bf16 neck emits [N, R, S]
+// maps of 2-byte channels.  A workgroup moves 128 channels x 64 pixels (move_tile_b16).
 struct Tr16Args {
     const unsigned short* in;   // [N, R, S]
     unsigned short* out;        // [N, S, R]
@@ -140,55 +219,15 @@ struct Tr16Args {
     int index;
 };
 constexpr int T16_CP = 64, T16_PX = 64, T16_LD = T16_CP + 1;      // channel PAIRS x pixels per tile
+static_assert(T16_PX == TS && T16_PX * T16_LD == TS * TLD, "one LDS tile serves both element sizes");
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void transpose_tiles16_kernel(const Tr16Args a) {
-    __shared__ unsigned tile[T16_PX * T16_LD];                      // tile[pixel][channel pair]
-    const int tid = threadIdx.x;
-    const int s0 = blockIdx.x * T16_PX, r0 = blockIdx.y * (2 * T16_CP);
+    __shared__ unsigned tile[T16_PX * T16_LD];
     const long long img = blockIdx.z;
     const unsigned short* in = (a.table ? static_cast<const unsigned short*>(a.table[a.index]) : a.in) + img * a.R * a.S;
-    unsigned short* out = a.out + img * a.R * a.S;
-    if (VEC) {   // S % 4 == 0, R % 8 == 0, 8-byte aligned planes, 16-byte aligned output
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int cp = (tid >> 4) + 16 * i, q = tid & 15;       // channel pair of the tile, pixel quad
-            const int r = r0 + 2 * cp, s = s0 + 4 * q;
-            uint2 lo = make_uint2(0u, 0u), hi = make_uint2(0u, 0u);
-            if (r < a.R && s < a.S) {                               // (R is even: r + 1 < R too)
-                lo = *reinterpret_cast<const uint2*>(in + (long long)r * a.S + s);
-                hi = *reinterpret_cast<const uint2*>(in + (long long)(r + 1) * a.S + s);
-            }
-            // lo = channel r at pixels s .. s+3 (two per word), hi = channel r + 1: word (pixel) = lo16 | hi16 << 16
-            tile[(4 * q + 0) * T16_LD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x05040100u);
-            tile[(4 * q + 1) * T16_LD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x07060302u);
-            tile[(4 * q + 2) * T16_LD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x05040100u);
-            tile[(4 * q + 3) * T16_LD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x07060302u);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int px = (tid >> 4) + 16 * i, k = tid & 15;       // pixel of the tile, 16-byte piece (4 pairs = 8 channels)
-            const int s = s0 + px, r = r0 + 8 * k;
-            if (s < a.S && r < a.R) {
-                const unsigned* t = &tile[px * T16_LD + 4 * k];
-                *reinterpret_cast<uint4*>(out + (long long)s * a.R + r) = make_uint4(t[0], t[1], t[2], t[3]);
-            }
-        }
-    } else {
-        unsigned short* t16 = reinterpret_cast<unsigned short*>(tile);      // [pixel][2 * T16_LD] halves
-        for (int i = tid; i < 2 * T16_CP * T16_PX; i += 256) {
-            const int lr = i / T16_PX, ls = i % T16_PX;
-            const int r = r0 + lr, s = s0 + ls;
-            t16[ls * (2 * T16_LD) + lr] = (r < a.R && s < a.S) ? in[(long long)r * a.S + s] : (unsigned short)0;
-        }
-        __syncthreads();
-        for (int i = tid; i < 2 * T16_CP * T16_PX; i += 256) {
-            const int ls = i / (2 * T16_CP), lr = i % (2 * T16_CP);
-            const int r = r0 + lr, s = s0 + ls;
-            if (r < a.R && s < a.S) out[(long long)s * a.R + r] = t16[ls * (2 * T16_LD) + lr];
-        }
-    }
+    // VEC: S % 4 == 0, R % 8 == 0, 8-byte aligned planes, 16-byte aligned output
+    move_tile_b16<T16_CP, unsigned short, false>(in, a.out + img * a.R * a.S, a.R, a.S, blockIdx.y * (2 * T16_CP), blockIdx.x * T16_PX, VEC, VEC, tile);
 }
 
 // ---- on-demand ("lazy") relayout: only the units a sample point will read (round 6) -----------------------------------------------------
@@ -205,89 +244,20 @@ __global__ __launch_bounds__(256) void transpose_tiles16_kernel(const Tr16Args a
 // Plain loads / stores only: `need` bytes are written by idempotent stores, `done` words by the one thread that owns the tile.  A stale or
 // uninitialised `need` (first step on a new workspace, an aborted step) only moves MORE units; `done` is rebuilt by every step's first launch.
 // Untouched units of the NHWC buffers keep whatever an earlier step left there: no tap ever reads them.
-// one unit: channels [64 g, 64 g + 64) x pixels [64 ts, 64 ts + 64) of image `img` of level l.  fp32: the dense tile code.
-__device__ __forceinline__ void lazy_move_unit(const LazyArgs& a, int l, long long img, int ts, int g, float* tile, const float*) {
-    const int tid = threadIdx.x;
+// one unit: channels [64 g, 64 g + 64) x pixels [64 ts, 64 ts + 64) of image `img` of level l: the dense fp32 tile, or 32 channel PAIRS
+// of 2-byte channels (128-byte runs in, 128-byte runs out).  A plane whose rows are not aligned (S % 4 != 0, e.g. a 10 x 25 level) is
+// read in scalar form; the write is always the 16-byte one (R = 256, destinations checked to be 16-byte aligned).
+template <typename ET>
+__device__ __forceinline__ void lazy_move_unit(const LazyArgs& a, int l, long long img, int ts, int g, float* tile) {
     const int R = a.R, S = a.S[l];
-    const int r0 = g * TS, s0 = ts * TS;
-    const float* in = static_cast<const float*>(a.table ? a.table[a.index[l]] : a.src[l]) + img * R * S;
-    float* out = static_cast<float*>(a.out[l]) + img * R * S;
-    if ((S & 3) == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = r0 + (tid >> 4) + 16 * i, sx = s0 + (tid & 15) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (sx < S) v = *reinterpret_cast<const float4*>(in + (long long)r * S + sx);
-            const int lr = (tid >> 4) + 16 * i, ls = (tid & 15) * 4;
-            tile[(ls + 0) * TLD + lr] = v.x;
-            tile[(ls + 1) * TLD + lr] = v.y;
-            tile[(ls + 2) * TLD + lr] = v.z;
-            tile[(ls + 3) * TLD + lr] = v.w;
-        }
-    } else {                                   // planes whose rows are not 16-byte aligned (e.g. a 10 x 25 level): scalar reads
-        for (int i = tid; i < TS * TS; i += 256) {
-            const int lr = i >> 6, ls = i & 63, sx = s0 + ls;
-            tile[ls * TLD + lr] = sx < S ? in[(long long)(r0 + lr) * S + sx] : 0.f;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int ls = (tid >> 4) + 16 * i, lr = (tid & 15) * 4;
-        const int sx = s0 + ls;
-        if (sx < S) {
-            const float4 v = make_float4(tile[ls * TLD + lr], tile[ls * TLD + lr + 1], tile[ls * TLD + lr + 2], tile[ls * TLD + lr + 3]);
-            *reinterpret_cast<float4*>(out + (long long)sx * R + r0 + lr) = v;
-        }
-    }
-    __syncthreads();
+    const ET* in = static_cast<const ET*>(a.table ? a.table[a.index[l]] : a.src[l]) + img * R * S;
+    ET* out = static_cast<ET*>(a.out[l]) + img * R * S;
+    __builtin_assume(R == 4 * TS);             // (lazy_plan takes 256 channels only: the mover's r < R tests fold away, as in the dense full tile)
+    const bool vread = (S & 3) == 0;
+    if constexpr (sizeof(ET) == 4) move_tile_f32(in, out, R, S, g * TS, ts * TS, vread, true, tile);
+    else move_tile_b16<32, ET, false>(in, out, R, S, g * 64, ts * TS, vread, true, reinterpret_cast<unsigned*>(tile));
+    __syncthreads();                           // the tile is reused by the next group
 }
-// 2-byte channels (bf16 / fp16 storage: bytes are moved, never interpreted): 32 channel PAIRS x 64 pixels, the pair interleave of
-// transpose_tiles16_kernel; 128-byte runs in, 128-byte runs out
-__device__ __forceinline__ void lazy_move_unit(const LazyArgs& a, int l, long long img, int ts, int g, float* tilef, const unsigned short*) {
-    unsigned* tile = reinterpret_cast<unsigned*>(tilef);          // tile[pixel][pair], row stride 33 words
-    constexpr int PLD = 33;
-    const int tid = threadIdx.x;
-    const int R = a.R, S = a.S[l];
-    const int r0 = g * 64, s0 = ts * 64;
-    const unsigned short* in = static_cast<const unsigned short*>(a.table ? a.table[a.index[l]] : a.src[l]) + img * R * S;
-    unsigned short* out = static_cast<unsigned short*>(a.out[l]) + img * R * S;
-    if ((S & 3) == 0) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int cp = (tid >> 4) + 16 * i, q = tid & 15;     // channel pair of the unit, pixel quad
-            const int r = r0 + 2 * cp, sx = s0 + 4 * q;
-            uint2 lo = make_uint2(0u, 0u), hi = make_uint2(0u, 0u);
-            if (sx < S) {
-                lo = *reinterpret_cast<const uint2*>(in + (long long)r * S + sx);
-                hi = *reinterpret_cast<const uint2*>(in + (long long)(r + 1) * S + sx);
-            }
-            tile[(4 * q + 0) * PLD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x05040100u);
-            tile[(4 * q + 1) * PLD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x07060302u);
-            tile[(4 * q + 2) * PLD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x05040100u);
-            tile[(4 * q + 3) * PLD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x07060302u);
-        }
-    } else {
-        for (int i = tid; i < 32 * 64; i += 256) {
-            const int cp = i >> 6, ls = i & 63, sx = s0 + ls;
-            unsigned w = 0u;
-            if (sx < S) w = (unsigned)in[(long long)(r0 + 2 * cp) * S + sx] | ((unsigned)in[(long long)(r0 + 2 * cp + 1) * S + sx] << 16);
-            tile[ls * PLD + cp] = w;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int px = (tid >> 3) + 32 * i, k = tid & 7;          // pixel of the unit, 16-byte piece (4 pairs = 8 channels)
-        const int sx = s0 + px;
-        if (sx < S) {
-            const unsigned* t = &tile[px * PLD + 4 * k];
-            *reinterpret_cast<uint4*>(out + (long long)sx * R + r0 + 8 * k) = make_uint4(t[0], t[1], t[2], t[3]);
-        }
-    }
-    __syncthreads();
-}
-
 
 // the step's FIRST lazy launch: one workgroup per tile, `done` is rebuilt from `need`
 template <typename ET>
@@ -304,7 +274,7 @@ __global__ __launch_bounds__(256) void lazy_tiles_kernel(const LazyArgs a) {
     long long img;
     lazy_locate(a, t, l, img, ts);
     for (int g = 0; g < 4; ++g)
-        if ((pend >> g) & 1u) lazy_move_unit(a, l, img, ts, g, tile, static_cast<const ET*>(nullptr));
+        if ((pend >> g) & 1u) lazy_move_unit<ET>(a, l, img, ts, g, tile);
 }
 
 // later launches of the step: a thread per tile finds what the layer's sample points marked and no earlier launch moved.  The units a
@@ -358,17 +328,14 @@ struct CopySegs {
     int index[4];
     unsigned char* dst[4];
     long long nbytes[4];
-    unsigned first_block[5];     // segment k owns blocks [first_block[k], first_block[k + 1])
+    BlockRanges<4> blocks;       // segment k's blocks
 };
 __global__ __launch_bounds__(256) void copy_indirect_kernel(const CopySegs a) {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < 4; ++j)
-        if (j < a.nseg && blockIdx.x >= a.first_block[j]) k = j;
+    const int k = block_segment(a.blocks, a.nseg);
     const unsigned char* __restrict__ src = static_cast<const unsigned char*>(a.table[a.index[k]]);
     unsigned char* __restrict__ dst = a.dst[k];
     const long long nbytes = a.nbytes[k];
-    const long long i = ((long long)(blockIdx.x - a.first_block[k]) * 256 + threadIdx.x) * 16;
+    const long long i = ((long long)(blockIdx.x - a.blocks.first[k]) * 256 + threadIdx.x) * 16;
     if (i + 16 <= nbytes) {
         *reinterpret_cast<uint4*>(dst + i) = *reinterpret_cast<const uint4*>(src + i);
     } else {
@@ -385,7 +352,7 @@ __global__ __launch_bounds__(256) void copy_indirect_kernel(const CopySegs a) {
 // else's frame).  Two live entries of one sample naming one slot would race: the host planner (cache.SlotBook.plan_frames) never produces
 // them, the kernel cannot check.  All sets, levels and samples in ONE launch, blocks of a set mapped as in transpose_tiles_multi_kernel.
 // MODE: 0 fp32 -> fp32, 1 two-byte -> the same two-byte type (bytes), 2 bf16 -> fp32, 3 fp16 -> fp32 (both exact).
-// NCHW goes through an LDS tile, vector or scalar form chosen per level (bit l of `vec`; modes 2 and 3: the 2-byte tile, widened on the way out); channels-last is already in the slot's layout: 16 source bytes per thread straight through, no LDS.  grid = (blocks of one set, K).
+// NCHW goes through an LDS tile (move_tile_f32 / move_tile_b16), both phases in vector or both in scalar form, chosen per level (bit l of `vec`; modes 2 and 3: the 2-byte tile, widened on the way out); channels-last is already in the slot's layout: 16 source bytes per thread straight through, no LDS.  grid = (blocks of one set, K).
 struct PoolFramesArgs {
     const void* const* table;                                        // null: src[] direct
     int index[SBEV_MAX_FRAMES * SBEV_MAX_LEVELS];                    // [K][L]
@@ -394,122 +361,11 @@ struct PoolFramesArgs {
     const int* rows;                                                 // [K, B]
     int S[SBEV_MAX_LEVELS];
     unsigned tiles_s[SBEV_MAX_LEVELS];           // NCHW: ceil(S / 64); channels-last: 4096-byte source chunks of one sample's n_views * S * R run
-    unsigned first_block[SBEV_MAX_LEVELS + 1];   // level l owns blocks [first_block[l], first_block[l + 1]) of a set
+    BlockRanges<SBEV_MAX_LEVELS> blocks;         // level l's blocks of a set
     int n_levels, B, R, n_slots, n_views;
     unsigned tiles_r;                            // NCHW: ceil(R / 64) (fp32 source), ceil(R / 128) (2-byte source)
     unsigned vec;                                // bit l: level l takes the vector form
 };
-
-template <bool F16>
-__device__ __forceinline__ float widen_bits(unsigned short v) {
-    if (F16) {
-        _Float16 h;
-        __builtin_memcpy(&h, &v, 2);
-        return (float)h;
-    }
-    return __uint_as_float((unsigned)v << 16);
-}
-template <bool F16>
-__device__ __forceinline__ float4 widen_words(unsigned a, unsigned b) {      // two words = four consecutive 2-byte channels
-    return make_float4(widen_bits<F16>((unsigned short)(a & 0xffffu)), widen_bits<F16>((unsigned short)(a >> 16)),
-                       widen_bits<F16>((unsigned short)(b & 0xffffu)), widen_bits<F16>((unsigned short)(b >> 16)));
-}
-
-// The NCHW tile code is this kernel's own copy of transpose_tiles_kernel's / transpose_tiles16_kernel's: sharing one inlined function
-// between two kernels moves the older kernel's register figures (profiles/pool_frames.json).  fp32: that tile as it is.
-__device__ __forceinline__ void pool_frames_tile(const float* in, float* out, int R, int S, int r0, int s0, bool vec, float* tile) {
-    const int tid = threadIdx.x;
-    if (vec) {   // S % 4 == 0 and R % 4 == 0
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = r0 + (tid >> 4) + 16 * i, s = s0 + (tid & 15) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r < R && s < S) v = *reinterpret_cast<const float4*>(in + (long long)r * S + s);
-            const int lr = (tid >> 4) + 16 * i, ls = (tid & 15) * 4;
-            tile[(ls + 0) * TLD + lr] = v.x;
-            tile[(ls + 1) * TLD + lr] = v.y;
-            tile[(ls + 2) * TLD + lr] = v.z;
-            tile[(ls + 3) * TLD + lr] = v.w;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int ls = (tid >> 4) + 16 * i, lr = (tid & 15) * 4;
-            const int s = s0 + ls, r = r0 + lr;
-            if (s < S && r < R) {
-                const float4 v = make_float4(tile[ls * TLD + lr], tile[ls * TLD + lr + 1], tile[ls * TLD + lr + 2], tile[ls * TLD + lr + 3]);
-                *reinterpret_cast<float4*>(out + (long long)s * R + r) = v;
-            }
-        }
-    } else {
-        for (int i = tid; i < TS * TS; i += 256) {
-            const int lr = i / TS, ls = i % TS;
-            const int r = r0 + lr, s = s0 + ls;
-            tile[ls * TLD + lr] = (r < R && s < S) ? in[(long long)r * S + s] : 0.f;
-        }
-        __syncthreads();
-        for (int i = tid; i < TS * TS; i += 256) {
-            const int ls = i / TS, lr = i % TS;
-            const int r = r0 + lr, s = s0 + ls;
-            if (r < R && s < S) out[(long long)s * R + r] = tile[ls * TLD + lr];
-        }
-    }
-}
-// 2-byte channels in: transpose_tiles16_kernel's read phase (64 channel pairs x 64 pixels, its pair interleave); on the way out a thread writes the 8 channels of its
-// pixel as they are (DT 2-byte: one 16-byte store) or widened (DT float: two)
-template <typename DT, bool F16>
-__device__ __forceinline__ void pool_frames_tile(const unsigned short* in, DT* out, int R, int S, int r0, int s0, bool vec, float* tilef) {
-    unsigned* tile = reinterpret_cast<unsigned*>(tilef);             // tile[pixel][channel pair], T16_PX x T16_LD words
-    const int tid = threadIdx.x;
-    if (vec) {   // S % 4 == 0 and R % 8 == 0
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int cp = (tid >> 4) + 16 * i, q = tid & 15;
-            const int r = r0 + 2 * cp, s = s0 + 4 * q;
-            uint2 lo = make_uint2(0u, 0u), hi = make_uint2(0u, 0u);
-            if (r < R && s < S) {                                    // (R is even: r + 1 < R too)
-                lo = *reinterpret_cast<const uint2*>(in + (long long)r * S + s);
-                hi = *reinterpret_cast<const uint2*>(in + (long long)(r + 1) * S + s);
-            }
-            tile[(4 * q + 0) * T16_LD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x05040100u);
-            tile[(4 * q + 1) * T16_LD + cp] = __builtin_amdgcn_perm(hi.x, lo.x, 0x07060302u);
-            tile[(4 * q + 2) * T16_LD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x05040100u);
-            tile[(4 * q + 3) * T16_LD + cp] = __builtin_amdgcn_perm(hi.y, lo.y, 0x07060302u);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int px = (tid >> 4) + 16 * i, k = tid & 15;
-            const int s = s0 + px, r = r0 + 8 * k;
-            if (s < S && r < R) {
-                const unsigned* t = &tile[px * T16_LD + 4 * k];
-                DT* o = out + (long long)s * R + r;
-                if constexpr (sizeof(DT) == 2) {
-                    *reinterpret_cast<uint4*>(o) = make_uint4(t[0], t[1], t[2], t[3]);
-                } else {
-                    *reinterpret_cast<float4*>(o) = widen_words<F16>(t[0], t[1]);
-                    *reinterpret_cast<float4*>(o + 4) = widen_words<F16>(t[2], t[3]);
-                }
-            }
-        }
-    } else {
-        unsigned short* t16 = reinterpret_cast<unsigned short*>(tile);      // [pixel][2 * T16_LD] halves
-        for (int i = tid; i < 2 * T16_CP * T16_PX; i += 256) {
-            const int lr = i / T16_PX, ls = i % T16_PX;
-            const int r = r0 + lr, s = s0 + ls;
-            t16[ls * (2 * T16_LD) + lr] = (r < R && s < S) ? in[(long long)r * S + s] : (unsigned short)0;
-        }
-        __syncthreads();
-        for (int i = tid; i < 2 * T16_CP * T16_PX; i += 256) {
-            const int ls = i / (2 * T16_CP), lr = i % (2 * T16_CP);
-            const int r = r0 + lr, s = s0 + ls;
-            if (r < R && s < S) {
-                if constexpr (sizeof(DT) == 2) out[(long long)s * R + r] = t16[ls * (2 * T16_LD) + lr];
-                else out[(long long)s * R + r] = widen_bits<F16>(t16[ls * (2 * T16_LD) + lr]);
-            }
-        }
-    }
-}
 
 template <int MODE>
 struct PoolFramesTypes {
@@ -532,11 +388,8 @@ __global__ __launch_bounds__(256) void pool_frames_kernel(const PoolFramesArgs a
     using ST = typename PoolFramesTypes<MODE>::ST;
     using DT = typename PoolFramesTypes<MODE>::DT;
     const unsigned k = blockIdx.y;
-    int l = 0;
-#pragma unroll
-    for (int j = 1; j < SBEV_MAX_LEVELS; ++j)
-        if (j < a.n_levels && blockIdx.x >= a.first_block[j]) l = j;
-    unsigned rel = blockIdx.x - a.first_block[l];
+    const int l = block_segment(a.blocks, a.n_levels);
+    unsigned rel = blockIdx.x - a.blocks.first[l];
     const unsigned ts = a.tiles_s[l];
     const int R = a.R, S = a.S[l];
     const bool vec = ((a.vec >> l) & 1u) != 0u;
@@ -568,7 +421,6 @@ __global__ __launch_bounds__(256) void pool_frames_kernel(const PoolFramesArgs a
             }
         }
     } else {
-        static_assert(T16_PX * T16_LD == TS * TLD, "one LDS tile serves both element sizes");
         __shared__ float tile[TS * TLD];
         constexpr int TR = sizeof(ST) == 4 ? TS : 2 * T16_CP;            // channels per tile
         const unsigned per_img = ts * a.tiles_r;
@@ -582,8 +434,8 @@ __global__ __launch_bounds__(256) void pool_frames_kernel(const PoolFramesArgs a
         const ST* in = static_cast<const ST*>(a.table ? a.table[a.index[kl]] : a.src[kl]) + (long long)img * plane;
         const long long dst_img = ((long long)b * a.n_slots + slot) * a.n_views + (img - b * (unsigned)a.n_views);
         DT* out = static_cast<DT*>(a.out[l]) + dst_img * plane;
-        if constexpr (MODE == 0) pool_frames_tile(in, out, R, S, r0, s0, vec, tile);
-        else pool_frames_tile<DT, MODE == 3>(in, out, R, S, r0, s0, vec, tile);
+        if constexpr (MODE == 0) move_tile_f32(in, out, R, S, r0, s0, vec, vec, tile);
+        else move_tile_b16<T16_CP, DT, MODE == 3>(in, out, R, S, r0, s0, vec, vec, reinterpret_cast<unsigned*>(tile));
     }
 }
 
@@ -633,6 +485,22 @@ __global__ __launch_bounds__(ORDER_THREADS) void query_order_kernel(const OrderA
 
 }  // namespace
 
+// NCHW -> NHWC for fp32 behind both entries (each has checked its own pointers): `in` NULL: the source address is table[index], read on
+// the device (required to be 16-byte aligned by its caller)
+static int nchw_to_nhwc_f32(const float* in, const void* const* table, int index, float* out, int64_t n_images, int channels, int hw,
+                            sbev_stream_t stream, const char* who) {
+    SBEV_REQUIRE(n_images <= 65535, "%s: at most 65535 images per call", who);
+    TrArgs a{in, out, channels, hw, in ? nullptr : table, index};
+    dim3 grid((hw + TS - 1) / TS, (channels + TS - 1) / TS, (unsigned)n_images);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool vec = (hw % 4 == 0) && (channels % 4 == 0) && ((((uintptr_t)in | (uintptr_t)out) & 15) == 0);
+    if (vec)
+        hipLaunchKernelGGL(transpose_tiles_kernel<true>, grid, dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL(transpose_tiles_kernel<false>, grid, dim3(256), 0, s, a);
+    return sbev::check_launch(who);
+}
+
 // The two staging launches of a replayable step (runtime.StepGraphs): their SOURCE pointer is table[index], read on the device when
 // the kernel starts -- table is a device array the host refreshes before every graph launch, so a caller may hand in newly allocated
 // tensors of the same shape each step (the reference's timing.py / val.py loops do) and still replay ONE captured graph.
@@ -642,16 +510,7 @@ extern "C" int sbev_nchw_to_nhwc_f32_indirect(const void* const* table, int inde
     SBEV_REQUIRE(n_images >= 0 && channels >= 1 && hw >= 1 && index >= 0, "sbev_nchw_to_nhwc_f32_indirect: bad sizes");
     if (n_images == 0) return SBEV_OK;
     SBEV_REQUIRE(table && out && (((uintptr_t)table) & 7) == 0, "sbev_nchw_to_nhwc_f32_indirect: null / unaligned pointer");
-    SBEV_REQUIRE(n_images <= 65535, "sbev_nchw_to_nhwc_f32_indirect: at most 65535 images per call");
-    TrArgs a{nullptr, out, channels, hw, table, index};
-    dim3 grid((hw + TS - 1) / TS, (channels + TS - 1) / TS, (unsigned)n_images);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool vec = (hw % 4 == 0) && (channels % 4 == 0) && ((((uintptr_t)out) & 15) == 0);
-    if (vec)
-        hipLaunchKernelGGL(transpose_tiles_kernel<true>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(transpose_tiles_kernel<false>, grid, dim3(256), 0, s, a);
-    return sbev::check_launch("sbev_nchw_to_nhwc_f32_indirect");
+    return nchw_to_nhwc_f32(nullptr, table, index, out, n_images, channels, hw, stream, "sbev_nchw_to_nhwc_f32_indirect");
 }
 
 // every level of one pyramid in one launch (the levels share n_images and channels: [n_images, channels, hw[l]] each).  Returns
@@ -670,11 +529,11 @@ extern "C" int sbev_nchw_to_nhwc_f32_multi_indirect(const void* const* table, in
                      "sbev_nchw_to_nhwc_f32_multi_indirect: level %d (hw %% 4 == 0, 16-byte aligned destination)", l);
         a.index[l] = index[l]; a.out[l] = out[l]; a.S[l] = hw[l];
         a.tiles_s[l] = (unsigned)((hw[l] + TS - 1) / TS);
-        a.first_block[l] = (unsigned)blocks;
+        a.blocks.first[l] = (unsigned)blocks;
         blocks += (long long)a.tiles_s[l] * a.tiles_r * n_images;
         SBEV_REQUIRE(blocks <= 0x7fffffffLL, "sbev_nchw_to_nhwc_f32_multi_indirect: too many tiles for one launch");
     }
-    a.first_block[n_levels] = (unsigned)blocks;
+    a.blocks.first[n_levels] = (unsigned)blocks;
     hipLaunchKernelGGL(transpose_tiles_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return sbev::check_launch("sbev_nchw_to_nhwc_f32_multi_indirect");
 }
@@ -693,11 +552,11 @@ extern "C" int sbev_copy_indirect(const void* const* table, int nseg, const int3
         a.index[k] = index[k];
         a.dst[k] = static_cast<unsigned char*>(dst[k]);
         a.nbytes[k] = nbytes[k];
-        a.first_block[k] = (unsigned)blocks;
+        a.blocks.first[k] = (unsigned)blocks;
         blocks += (nbytes[k] + 4095) / 4096;
         SBEV_REQUIRE(blocks <= 0x7fffffffLL, "sbev_copy_indirect: too many bytes for one launch");
     }
-    a.first_block[nseg] = (unsigned)blocks;
+    a.blocks.first[nseg] = (unsigned)blocks;
     hipLaunchKernelGGL(copy_indirect_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return sbev::check_launch("sbev_copy_indirect");
 }
@@ -736,7 +595,7 @@ static int pool_insert_impl(const char* who, bool single, const void* const* tab
         SBEV_REQUIRE((long long)channels * hw_pixels[l] * (single ? 1 : n_views) <= 0x7fffffffLL,
                      single ? "%s: level %d: plane too large" : "%s: level %d: frame too large", who, l);
         a.out[l] = out[l]; a.S[l] = hw_pixels[l];
-        a.first_block[l] = (unsigned)blocks;
+        a.blocks.first[l] = (unsigned)blocks;
         if (nhwc) {
             const long long bytes = (long long)n_views * hw_pixels[l] * channels * ssize;      // one sample's run in the source
             if (bytes % 16 == 0) a.vec |= 1u << l;
@@ -749,7 +608,7 @@ static int pool_insert_impl(const char* who, bool single, const void* const* tab
         }
         SBEV_REQUIRE(blocks <= 0x7fffffffLL, "%s: too many tiles for one launch", who);
     }
-    a.first_block[n_levels] = (unsigned)blocks;
+    a.blocks.first[n_levels] = (unsigned)blocks;
     for (int i = 0; i < n_frames * n_levels; ++i) {
         const bool ok = table ? index[i] >= 0 : (src[i] && (((uintptr_t)src[i]) & 15) == 0);
         if (single) SBEV_REQUIRE(ok, "%s: level %d (hw >= 1, 16-byte aligned source and destination)", who, i);
@@ -853,16 +712,7 @@ extern "C" int sbev_nchw_to_nhwc_f32(const float* in, float* out, int64_t n_imag
     SBEV_REQUIRE(n_images >= 0 && channels >= 1 && hw >= 1, "sbev_nchw_to_nhwc_f32: bad sizes");
     if (n_images == 0) return SBEV_OK;
     SBEV_REQUIRE(in && out && in != out, "sbev_nchw_to_nhwc_f32: null or aliased pointers");
-    SBEV_REQUIRE(n_images <= 65535, "sbev_nchw_to_nhwc_f32: at most 65535 images per call");
-    TrArgs a{in, out, channels, hw, nullptr, 0};
-    dim3 grid((hw + TS - 1) / TS, (channels + TS - 1) / TS, (unsigned)n_images);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool vec = (hw % 4 == 0) && (channels % 4 == 0) && ((((uintptr_t)in | (uintptr_t)out) & 15) == 0);
-    if (vec)
-        hipLaunchKernelGGL(transpose_tiles_kernel<true>, grid, dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL(transpose_tiles_kernel<false>, grid, dim3(256), 0, s, a);
-    return sbev::check_launch("sbev_nchw_to_nhwc_f32");
+    return nchw_to_nhwc_f32(in, nullptr, 0, out, n_images, channels, hw, stream, "sbev_nchw_to_nhwc_f32");
 }
 
 extern "C" int sbev_linear3_ln_relu_f32(const float* x, int64_t ldx, const float* w, const float* b,

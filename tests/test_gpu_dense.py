@@ -114,6 +114,63 @@ def test_nchw_to_nhwc(shape):
     assert torch.equal(y, x.permute(0, 1, 3, 4, 2).contiguous())
 
 
+def _stream():
+    import ctypes
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def test_nchw_to_nhwc_all_levels_with_a_partial_channel_tile():
+    """sbev_nchw_to_nhwc_f32_multi_indirect away from 256 channels: 68 is a multiple of 4 (the vector forms) but not of the 64-channel
+    tile, so every level's second channel tile is partial; levels of three, two and one pixel tile, the last one 4 pixels wide."""
+    import ctypes
+    from sparsebev_amd import _lib
+    lib = _lib.load()
+    g = torch.Generator().manual_seed(68)
+    n_img, ch, hws = 3, 68, [132, 68, 4]
+    n = len(hws)
+    srcs = [torch.randn(n_img, ch, hw, generator=g).to(DEV) for hw in hws]
+    outs = [torch.full((n_img, hw, ch), float('nan'), device=DEV) for hw in hws]
+    table = torch.tensor([0] + [t.data_ptr() for t in srcs], dtype=torch.int64, device=DEV)
+    st = lib.sbev_nchw_to_nhwc_f32_multi_indirect(ctypes.c_void_p(table.data_ptr()), n, (ctypes.c_int32 * n)(*range(1, 1 + n)),
+                                                  (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), n_img, ch, (ctypes.c_int32 * n)(*hws), _stream())
+    assert st == 0, lib.sbev_last_error()
+    for src, out in zip(srcs, outs):
+        assert torch.equal(out, src.permute(0, 2, 1).contiguous())
+
+
+@pytest.mark.parametrize('offset', [0, 1])
+def test_nchw_to_nhwc_destination_not_16_byte_aligned(offset):
+    """A vector shape (68 channels, 12 pixels) into a destination that starts one float past a 16-byte boundary (the host then chooses the
+    scalar form) and the same shape aligned beside it: every element arrives and nothing around the destination is written.  Which form
+    ran is not observable here."""
+    import ctypes
+    from sparsebev_amd import _lib
+    lib = _lib.load()
+    n_img, ch, hw = 2, 68, 12
+    x = torch.randn(n_img, ch, hw, generator=torch.Generator().manual_seed(12)).to(DEV)
+    buf = torch.full((n_img * hw * ch + 4,), float('nan'), device=DEV)
+    out = buf[offset:offset + n_img * hw * ch].view(n_img, hw, ch)
+    assert buf.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 4 * offset
+    st = lib.sbev_nchw_to_nhwc_f32(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), n_img, ch, hw, _stream())
+    assert st == 0, lib.sbev_last_error()
+    assert torch.equal(out, x.permute(0, 2, 1).contiguous())
+    assert torch.isnan(buf[:offset]).all() and torch.isnan(buf[offset + out.numel():]).all()       # nothing written around it
+
+
+def test_nchw_to_nhwc_scalar_form_through_the_pointer_table():
+    """sbev_nchw_to_nhwc_f32_indirect at 100 channels x 63 pixels: the scalar form, its source read from a table slot."""
+    import ctypes
+    from sparsebev_amd import _lib
+    lib = _lib.load()
+    n_img, ch, hw = 1, 100, 63
+    x = torch.randn(n_img, ch, hw, generator=torch.Generator().manual_seed(63)).to(DEV)
+    out = torch.full((n_img, hw, ch), float('nan'), device=DEV)
+    table = torch.tensor([0, 0, x.data_ptr()], dtype=torch.int64, device=DEV)
+    st = lib.sbev_nchw_to_nhwc_f32_indirect(ctypes.c_void_p(table.data_ptr()), 2, ctypes.c_void_p(out.data_ptr()), n_img, ch, hw, _stream())
+    assert st == 0, lib.sbev_last_error()
+    assert torch.equal(out, x.permute(0, 2, 1).contiguous())
+
+
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize('shape', [(3, 256, 8, 22), (2, 256, 10, 25), (5, 64, 64, 176), (1, 100, 7, 9), (2, 256, 64, 176), (1, 136, 4, 8), (2, 8, 1, 4)])
 def test_nchw_to_nhwc_two_byte_channels(shape, dtype):
