@@ -427,13 +427,20 @@ def denormalize_bbox(nb):
 
 def nms_free_decode_single(cls_scores, bbox_preds, num_classes, max_num, score_threshold, post_center_range):
     """models/bbox/coders/nms_free_coder.py:37-88.  cls_scores [Q,NC] logits, bbox_preds [Q,10] head format.
-    Ties in the top-k are resolved by (score desc, flat index asc) -- torch.topk leaves them unspecified."""
+    Ties in the top-k are resolved by (score desc, flat index asc) -- torch.topk leaves them unspecified.  A NaN logit of either
+    sign ranks before every real one, as in torch.topk, and NaNs among themselves by flat index (a NaN sort key would leave
+    the order to the sort's implementation)."""
     s = cls_scores.sigmoid().reshape(-1)
-    order = sorted(range(s.numel()), key=lambda i: (-float(s[i]), i))[:max_num] if s.numel() <= 4096 else None
-    if order is None:                       # large inputs: stable argsort on the logits (same total order unless
-        key = cls_scores.reshape(-1)        # distinct logits collapse to one fp32 sigmoid value)
-        order = torch.argsort(-key.double(), stable=True)[:max_num].tolist()
-    idx = torch.tensor(order, dtype=torch.long)
+    nan = torch.isnan(s)
+    if s.numel() <= 4096:
+        isnan, val = nan.tolist(), s.tolist()
+        order = sorted(range(s.numel()), key=lambda i: (0, 0.0, i) if isnan[i] else (1, -val[i], i))
+    else:                                   # large inputs: stable argsort on the logits (same total order unless
+        key = -cls_scores.reshape(-1).double()      # distinct logits collapse to one fp32 sigmoid value)
+        key[nan] = -math.inf
+        order = torch.argsort(key, stable=True)
+        order = torch.cat([order[nan[order]], order[~nan[order]]]).tolist()   # stable: +inf logits stay behind the NaNs
+    idx = torch.tensor(order[:max_num], dtype=torch.long)
     scores = s[idx]
     labels = idx % num_classes
     boxes = denormalize_bbox(bbox_preds[torch.div(idx, num_classes, rounding_mode='trunc')])

@@ -73,9 +73,12 @@ struct DecodeArgs {
     float lim[6];
 };
 
-// ascending u32 order == descending float order (NaN logits sort first, as "largest", like torch.topk)
+// ascending u32 order == descending float order.  ANY NaN logit, whatever its sign bit (inf - inf and 0 / 0 give 0xffc00000 on x86 hosts,
+// float('nan') is 0x7fc00000), maps to key 0, below +inf's 0x007fffff: NaNs sort first, as "largest", like torch.topk, and among
+// themselves by flat index.  -0 takes +0's key: the two are one logit and one score (0.5), so their order is the flat index's as well.
 __device__ __forceinline__ unsigned desc_key(float x) {
-    const unsigned u = __float_as_uint(x);
+    if (x != x) return 0u;
+    const unsigned u = x == 0.f ? 0u : __float_as_uint(x);
     const unsigned asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ~asc;
 }
