@@ -596,7 +596,8 @@ int sbev_gemm_f32(const float* A, int a_kmajor, int64_t lda, const float* B, int
                   float* workspace, sbev_stream_t stream);
 /* The same reduction over up to 8 operand pairs of identical layout and shape in ONE launch (+ the slab sum): C (+)= sum_s A_s B_s --
  * the weight gradient of a Linear shared by several decoder layers.  A / B: host arrays of nseg device pointers;
- * workspace: sbev_gemm_f32_multi_workspace(M, N, K, nseg) bytes (always needed).  Bit-reproducible. */
+ * workspace: sbev_gemm_f32_multi_workspace(M, N, K, nseg) bytes (always needed).  Bit-reproducible.  K = 0 is an empty sum in both:
+ * C = 0, or C unchanged under accumulate. */
 int64_t sbev_gemm_f32_multi_workspace(int64_t M, int N, int64_t K, int nseg);
 int sbev_gemm_f32_multi(const float* const* A, int a_kmajor, int64_t lda, const float* const* B, int b_kmajor, int64_t ldb,
                         int nseg, float* C, int64_t ldc, int64_t M, int N, int64_t K, int accumulate,

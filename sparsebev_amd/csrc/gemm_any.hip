@@ -322,15 +322,19 @@ extern "C" int sbev_gemm_f32_multi(const float* const* A, int a_kmajor, int64_t 
         a.Aseg[i] = A[i]; a.Bseg[i] = B[i];
         vec = vec && (reinterpret_cast<uintptr_t>(A[i]) & 15) == 0 && (reinterpret_cast<uintptr_t>(B[i]) & 15) == 0;
     }
-    int sps = multi_splits(M, N, K, nseg);
-    a.k_per_split = ((K + sps - 1) / sps + TK - 1) / TK * TK;
-    sps = (int)((K + a.k_per_split - 1) / a.k_per_split);
-    a.nseg = nseg; a.splits_per_seg = sps;
-    a.C = workspace; a.ldc = N;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int st = vec ? launch_layout<true>(a, a_kmajor, b_kmajor, nseg * sps, s) : launch_layout<false>(a, a_kmajor, b_kmajor, nseg * sps, s);
-    if (st != SBEV_OK) return st;
+    int slabs = 0;                     // K == 0: an empty reduction -- the slab sum over no slabs writes C = 0 (or leaves it under accumulate), as sbev_gemm_f32 does
+    if (K > 0) {
+        int sps = multi_splits(M, N, K, nseg);
+        a.k_per_split = ((K + sps - 1) / sps + TK - 1) / TK * TK;
+        sps = (int)((K + a.k_per_split - 1) / a.k_per_split);
+        a.nseg = nseg; a.splits_per_seg = sps;
+        a.C = workspace; a.ldc = N;
+        slabs = nseg * sps;
+        const int st = vec ? launch_layout<true>(a, a_kmajor, b_kmajor, slabs, s) : launch_layout<false>(a, a_kmajor, b_kmajor, slabs, s);
+        if (st != SBEV_OK) return st;
+    }
     const long long n = M * N;
-    hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, workspace, C, M, N, ldc, nseg * sps, accumulate);
+    hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, workspace, C, M, N, ldc, slabs, accumulate);
     return sbev::check_launch("sbev_gemm_f32_multi (slab sum)");
 }
