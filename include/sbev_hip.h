@@ -455,6 +455,17 @@ int sbev_linear_bf16s_gen(const uint16_t* Xs, const uint16_t* Ws, const float* b
                           int64_t ldy, int relu, int nimg, sbev_stream_t stream);
 int sbev_linear_bf16s_out_ok(int64_t M, int N, int K);
 int sbev_linear_bf16s_out_plan(int64_t M, int N, int K);
+/* What a generator call of this shape launches (sbev_linear_bf16s_gen: nimg 2 / 3; sbev_linear_f16s_gen: nimg = nprod + 1), a pure host
+ * function: weight_stationary = the setting of sbev_linear_gen_weight_stationary to plan for, cus = the device's compute units
+ * (0: ask the current device).  Writes 7 + 4 L int32 words and returns their count; SBEV_EINVAL for a shape the kernels do not
+ * cover or capacity < that count.
+ *   out[0]  kernel: 0 = weight-stationary, 2 / 4 = tiled with 128- / 256-row tiles (row fragments per wave)
+ *   out[1]  row splits (weight-stationary) / row tiles, over which the ceil(M / 32) row fragments are spread:
+ *   out[2], out[3]  base, rem -- the first rem own base + 1 fragments, the others base
+ *   out[4]  weight-stationary: tasks (column tiles x row splits); tiled: workgroups per row tile
+ *   out[5]  tiled: column tiles a workgroup may walk in one launch (weight-stationary: 0)
+ *   out[6]  L launches, each out[7 + 4 i ..]: first column tile (of 256 columns), column tiles, workgroups, dynamic LDS bytes */
+int sbev_linear_gen_plan(int64_t M, int N, int K, int64_t ldy, int nimg, int weight_stationary, int cus, int32_t* out, int capacity);
 int sbev_linear_splitk_bf16s(const float* X, const uint16_t* Wp, const float* bias, const float* residual,
                              const float* ln_w, const float* ln_b, float ln_eps, float* Y,
                              int64_t M, int N, int K, int64_t ldx, int relu, int nimg, float* workspace,

@@ -463,8 +463,8 @@ struct Step {
             TRY(p.nimg >= 4 ? sbev_pack_f16s_frags(b.x1, D, xs, const_cast<float*>(w.pg_xscale), (int)p.BQ, D, 2, st)
                             : sbev_pack_bf16s_frags(b.x1, D, xs, (int)p.BQ, D, p.nimg, st));
         }
-        return sbev::linear_gen_split(xs, w.pg_xscale, w.pg_ws, w.pg_wdown, w.pg_b, params, p.BQ, p.pgN, D, p.pgN, 0, p.nimg, p.gen_ws, scan,
-                                      reinterpret_cast<hipStream_t>(st), skip);
+        return sbev::launch_gen_gemm({{xs, w.pg_xscale}, {w.pg_ws, w.pg_wdown}, w.pg_b, params, p.BQ, p.pgN, D, p.pgN, 0, p.nimg, p.gen_ws, scan, skip},
+                                     reinterpret_cast<hipStream_t>(st));
     }
     int generator(sbev_stream_t st, const sbev::LazyScan* scan) {
         if (p.nimg) return generator_bf16s(st, scan);

@@ -283,50 +283,36 @@ inline int next_scale_slot() {
 // ---- LDS-DMA: 1 KiB per wave-instruction, LDS destination = M0 + 16 lane (lane-linear), source = sbase + voff per lane ----------
 // (M0 is written inside the asm block; hipcc uses M0 nowhere else in these kernels -- no LDS instruction needs it on gfx9+,
 // there is no dynamic register indexing; checked in the ISA, as for row_chain.hip.)
-__device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigned lds_byte) {
+// PIECES (1 .. 4) requests 1 KiB apart in memory AND in LDS -- the images of one (32-row block, k-step), a wave's 4 KiB of an X
+// fragment -- behind ONE M0 / base set-up
+template <int PIECES>
+__device__ __forceinline__ void lds_dma(const void* sbase, unsigned voff, unsigned lds_byte) {
+    static_assert(PIECES >= 1 && PIECES <= 4, "1 .. 4 pieces per request block");
     // wave-uniform by construction; readfirstlane makes them SGPRs whatever the divergence analysis concluded
     lds_byte = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_byte);
     const unsigned long long sb = (unsigned long long)sbase;
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sb);
     const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sb >> 32));
     sbase = reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
-    asm volatile(
-        "s_mov_b32 m0, %0\n\t"
-        "s_nop 4\n\t"                       // M0 write -> LDS-DMA (1 state) and a readfirstlane'd base -> VMEM (5 states)
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        :
-        : "s"(lds_byte), "v"(voff), "s"(sbase)
-        : "memory");
+    // one asm block per instantiation: M0 write -> LDS-DMA (1 wait state) and a readfirstlane'd base -> VMEM (5 states), then the loads
+#define SBEV_GLDS(OFFSET_) "global_load_lds_dwordx4 %1, %2" OFFSET_ "\n\t"
+#define SBEV_LDS_DMA(LOADS_) asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\t" LOADS_ : : "s"(lds_byte), "v"(voff), "s"(sbase) : "memory")
+    if constexpr (PIECES == 1) SBEV_LDS_DMA(SBEV_GLDS(""));
+    else if constexpr (PIECES == 2) SBEV_LDS_DMA(SBEV_GLDS("") SBEV_GLDS(" offset:1024"));
+    else if constexpr (PIECES == 3) SBEV_LDS_DMA(SBEV_GLDS("") SBEV_GLDS(" offset:1024") SBEV_GLDS(" offset:2048"));
+    else SBEV_LDS_DMA(SBEV_GLDS("") SBEV_GLDS(" offset:1024") SBEV_GLDS(" offset:2048") SBEV_GLDS(" offset:3072"));
+#undef SBEV_LDS_DMA
+#undef SBEV_GLDS
 }
 
-// the NIMG images of one (32-row block, k-step): 1 KiB apart in memory AND in the LDS stage -> one M0 / base set-up for all of them
-template <int NIMG>
-__device__ __forceinline__ void glds16_images(const void* sbase, unsigned voff, unsigned lds_byte) {
-    lds_byte = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_byte);
-    const unsigned long long sb = (unsigned long long)sbase;
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sb);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sb >> 32));
-    sbase = reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
-    if constexpr (NIMG == 3)
-        asm volatile(
-            "s_mov_b32 m0, %0\n\t"
-            "s_nop 4\n\t"
-            "global_load_lds_dwordx4 %1, %2\n\t"
-            "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-            "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-            :
-            : "s"(lds_byte), "v"(voff), "s"(sbase)
-            : "memory");
-    else
-        asm volatile(
-            "s_mov_b32 m0, %0\n\t"
-            "s_nop 4\n\t"
-            "global_load_lds_dwordx4 %1, %2\n\t"
-            "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-            :
-            : "s"(lds_byte), "v"(voff), "s"(sbase)
-            : "memory");
-}
+// `nfrag` row fragments of 32 rows over n tiles (or row splits), balanced: the first `rem` own base + 1 fragments, the others `base`.
+// Sits in the kernel argument blocks where `base, rem` sat.
+struct RowSplit {
+    int base, rem;
+    __host__ __device__ __forceinline__ int first(int i) const { return i * base + __builtin_elementwise_min(i, rem); }
+    __host__ __device__ __forceinline__ int count(int i) const { return base + (i < rem ? 1 : 0); }
+};
+inline RowSplit row_split(int nfrag, int n) { return {nfrag / n, nfrag % n}; }
 
 // ==== generator-shaped GEMM ======================================================================================================
 struct GenArgs {
@@ -337,12 +323,32 @@ struct GenArgs {
     int M, N, K;
     long long ldy;
     int relu;
-    int ntm, base, rem;          // row tiles: the first `rem` have base + 1 fragments of 32 rows, the others `base`
+    int ntm; RowSplit rows;      // row tiles and their fragments of 32 rows
     const float* colscale;       // fp16 modes: [N] 2^-ew of W's rows (the output columns); null otherwise
     const float* xscale;         // fp16 modes: {2^ex, 2^-ex} of X (device memory: written by the pack launch before this one)
 };
 
 constexpr int G_COLS = 256;                     // columns of a workgroup tile (8 fragments); rows: 128 or 256 (RF)
+
+// The tiled kernel's dynamic LDS for (images per operand, RF), stated ONCE -- the kernel takes its constants from here, gen_plan its sizes:
+//   [ring: depth() stages of (2 RF row + 8 column) fragments x images KiB] [patch_bytes()] [per column tile the workgroup walks: 256 bias
+//   floats, all tiles] [fp16 modes: as many slices of column scales]
+struct Gen3Lds {
+    int images, rf;
+    static constexpr int BUDGET = 160 * 1024;      // of the CU's LDS
+    static constexpr int EPI_LD = 36;              // patch row stride in floats (16-byte aligned rows, 4-bank shift per row)
+    static constexpr int MAX_TILES = 16;           // column tiles per workgroup and launch (wider matrices: several launches over column ranges)
+    constexpr int stage() const { return images * (2 * rf + 8) * 1024; }
+    constexpr int depth() const { return rf == 2 ? 4 : 3; }
+    constexpr bool patches() const { return images == 2 && rf == 4; }      // the epilogue's per-wave 32 x 32 transpose patches
+    constexpr int patch_bytes() const { return patches() ? 8 * 32 * EPI_LD * 4 : 0; }
+    constexpr int slices_at() const { return depth() * stage() + patch_bytes(); }
+    static constexpr int slice_bytes(bool f16) { return G_COLS * 4 * (f16 ? 2 : 1); }      // one column tile's bias (+ scales)
+    constexpr int max_tiles(bool f16) const {      // ... whose slices fit
+        const int fit = (BUDGET - slices_at()) / slice_bytes(f16);
+        return fit > MAX_TILES ? MAX_TILES : fit;
+    }
+};
 
 // ---- generator -----------------------------------------------------------------------------------------------------------------
 // History (c2, bf16x6; DESIGN_HISTORY.md section 4), every step measured on the MI355X:
@@ -404,20 +410,20 @@ __global__ __launch_bounds__(512) void gemm_bf16s_gen3_kernel(const GenArgs a) {
     constexpr int NIMG = PR::NIMG;
     constexpr bool F16 = PR::F16;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];    // the only LDS object: its byte address is 0
+    constexpr Gen3Lds L{NIMG, RF};
     constexpr int AF = 2 * RF;                                       // row fragments of a tile (A side); 8 column fragments (B side)
-    constexpr int ST_A = AF * 1024, ST_B = 8 * 1024;                 // bytes of one image of one 16-k stage
-    constexpr int STAGE = NIMG * (ST_A + ST_B);
+    constexpr int STAGE = L.stage();                                 // one 16-k stage: (AF + 8) KiB per image
     // LDS ring depth; loads run NST - 1 stages ahead.  256-row tiles: 3 stages of 48 KB with three images; with two images (32 KB) a
     // fourth fits, and the f16x3 trace wants it: its 24 MFMAs per stage no longer cover the landing of a stage issued 2 stages ago
     // (380 cycles of vmcnt wait in every FETCH phase, FETCH 1050 > COMPUTE 830)
-    constexpr int NST = RF == 2 ? 4 : 3;        // (a 4th stage for two images x 256 rows fits but measured nothing: 57.2 -> 58.3 us)
+    constexpr int NST = L.depth();              // (a 4th stage for two images x 256 rows fits but measured nothing: 57.2 -> 58.3 us)
     // Two images x 256-row tiles: the LDS the third image would take carries a per-wave 32 x 32 transpose patch for the epilogue.
     // The direct epilogue (a lane owns ONE output column: 128 dword stores of two 128-byte lines per wave and tile) held the tile
     // boundary for 5.3k cycles per phase group -- with the partner group idle at the barrier, 2 x 2 x 5.3k of a 90k-cycle
     // workgroup (f16x3 trace).  Through the patch a wave stores 32 x dwordx4 (8 full 128-byte row segments per instruction).
-    constexpr bool EPI_LDS = NIMG == 2 && RF == 4;
-    constexpr int EPI_LD = 36;                                       // patch row stride in floats (16-byte aligned rows, 4-bank shift per row)
-    constexpr int EPI_BYTES = EPI_LDS ? 8 * 32 * EPI_LD * 4 : 0;
+    constexpr bool EPI_LDS = L.patches();
+    constexpr int EPI_LD = Gen3Lds::EPI_LD;
+    constexpr int SLICES = L.slices_at();                            // the bias / column-scale slices lie behind ring and patches
     // Experiment kept as a switch: the LDS-DMA requests of the stage NST - 1 ahead issued in the COMPUTE phase, between the MFMAs (they
     // touch no vector register), instead of in the FETCH phase, because with 24 MFMAs per stage FETCH (issue 380 + reads 190 + wait +
     // barrier) is longer than COMPUTE (816) and sets the pace.
@@ -435,8 +441,7 @@ __global__ __launch_bounds__(512) void gemm_bf16s_gen3_kernel(const GenArgs a) {
     const int my_tiles = ct0 < nct ? (nct - ct0 + cstep - 1) / cstep : 0;
     const int G = my_tiles * nk;                                     // stages of this workgroup
     if (G == 0) return;
-    const int f0 = rt * a.base + (rt < a.rem ? rt : a.rem);
-    const int nf = a.base + (rt < a.rem ? 1 : 0);
+    const int f0 = a.rows.first(rt), nf = a.rows.count(rt);
     const int m0 = f0 * 32;
     int nfa = nf - RF * wr;                                          // this wave's row fragments: 0 .. RF (fixed for its life)
     nfa = nfa < 0 ? 0 : (nfa > RF ? RF : nfa);
@@ -470,7 +475,7 @@ __global__ __launch_bounds__(512) void gemm_bf16s_gen3_kernel(const GenArgs a) {
 #pragma unroll
         for (int j = 0; j < NLMAX; ++j) {
 #ifndef SBEV_EXP_NOGLDS
-            if (j < nlb) glds16_images<NIMG>(gbase[j], voff, sb + ldst[j]);
+            if (j < nlb) lds_dma<NIMG>(gbase[j], voff, sb + ldst[j]);
 #endif
             gbase[j] += NIMG * 1024;
         }
@@ -499,7 +504,7 @@ __global__ __launch_bounds__(512) void gemm_bf16s_gen3_kernel(const GenArgs a) {
 #pragma unroll
             for (int fb = 0; fb < 2; ++fb) {
                 // (fp16 modes: the accumulators are in scaled units -- bias and the 2^-(ex + ew) factor are applied by store_tile)
-                const float bv = F16 ? 0.f : reinterpret_cast<const float*>(lds + NST * STAGE + EPI_BYTES)[ti * G_COLS + (wc * 2 + fb) * 32 + l31];
+                const float bv = F16 ? 0.f : reinterpret_cast<const float*>(lds + SLICES)[ti * G_COLS + (wc * 2 + fb) * 32 + l31];
 #pragma unroll
                 for (int fa = 0; fa < NFR; ++fa)
 #pragma unroll
@@ -512,7 +517,7 @@ __global__ __launch_bounds__(512) void gemm_bf16s_gen3_kernel(const GenArgs a) {
         auto store_tile = [&](int n0, int tix) {                     // acc already holds hi x hi + small products
             if constexpr (NFA > 0) {
                 if constexpr (F16) {                                 // y = acc 2^-(ex + ew[n]) + b[n]: a lane holds two output columns
-                    const float* bs = reinterpret_cast<const float*>(lds + NST * STAGE + EPI_BYTES) + tix * G_COLS + wc * 64 + l31;
+                    const float* bs = reinterpret_cast<const float*>(lds + SLICES) + tix * G_COLS + wc * 64 + l31;
                     const float* cs = bs + my_tiles * G_COLS;
                     const float b0 = bs[0], b1 = bs[32], c0 = cs[0], c1 = cs[32];
 #pragma unroll
@@ -587,9 +592,9 @@ __global__ __launch_bounds__(512) void gemm_bf16s_gen3_kernel(const GenArgs a) {
         // make hipcc wait vmcnt(0) in the middle of the LDS-DMA pipeline
         for (int i = tid; i < my_tiles * G_COLS; i += 512) {
             const int t = i / G_COLS, c = i - t * G_COLS;
-            reinterpret_cast<float*>(lds + NST * STAGE + EPI_BYTES)[i] = a.bias ? a.bias[(ct0 + t * cstep) * G_COLS + c] : 0.f;
+            reinterpret_cast<float*>(lds + SLICES)[i] = a.bias ? a.bias[(ct0 + t * cstep) * G_COLS + c] : 0.f;
             if constexpr (F16)        // behind the bias slices: the columns' output scales 2^-ew[n] 2^-ex
-                reinterpret_cast<float*>(lds + NST * STAGE + EPI_BYTES)[my_tiles * G_COLS + i] = a.colscale[(ct0 + t * cstep) * G_COLS + c] * a.xscale[1];
+                reinterpret_cast<float*>(lds + SLICES)[my_tiles * G_COLS + i] = a.colscale[(ct0 + t * cstep) * G_COLS + c] * a.xscale[1];
         }
         __syncthreads();
         init_acc(0);
@@ -697,7 +702,7 @@ struct GenWsArgs {
     int M, N;
     long long ldy;
     int relu;
-    int nrs, base, rem;          // row splits: the first `rem` own base + 1 fragments, the others `base`
+    int nrs; RowSplit rows;      // row splits and their fragments of 32 rows
     int ntask;                   // (N / 256) * nrs
     const float* colscale;       // fp16 modes: [N] 2^-ew; null otherwise
     const float* xscale;         // fp16 modes: {2^ex, 2^-ex}
@@ -716,6 +721,8 @@ struct GenWsArgs {
 constexpr int WS_KS = 16;                        // k-steps of 16: K = 256
 constexpr int WS_FRAG = WS_KS * 2 * 1024;        // bytes of one row fragment of X (all K, both images)
 constexpr int WS_SLOTS = 4;
+constexpr int WS_LDS = WS_SLOTS * WS_FRAG;       // the kernel's dynamic LDS: the X ring, nothing else
+static_assert(WS_LDS <= Gen3Lds::BUDGET, "the X ring fits the CU's LDS");
 
 // workgroup barrier with LDS-DMA in flight: a bare s_barrier behind this wave's LDS traffic -- __syncthreads()' release fence would
 // also wait vmcnt(0) for the compiler-visible Y stores (and with them for the prefetched fragments)
@@ -768,8 +775,7 @@ __global__ __launch_bounds__(512) void gemm_f16s_gen_ws_kernel(const GenWsArgs a
     {
         for (int task = (int)xcd_contiguous(blockIdx.x, gridDim.x); task < a.ntask; task += (int)gridDim.x) {
             const int ct = task / a.nrs, rs = task - ct * a.nrs;
-            const int f0 = rs * a.base + (rs < a.rem ? rs : a.rem);
-            const int nf = a.base + (rs < a.rem ? 1 : 0);
+            const int f0 = a.rows.first(rs), nf = a.rows.count(rs);
             if (nf <= 0) continue;
             const int n = ct * G_COLS + wave * 32 + l31;                   // this lane's output column
             const float bv = a.bias ? a.bias[n] : 0.f;
@@ -778,25 +784,9 @@ __global__ __launch_bounds__(512) void gemm_f16s_gen_ws_kernel(const GenWsArgs a
             // ---- X stream: fragment f0 + i -> slot i % 4; wave w copies pieces 4 w .. 4 w + 3 (4 KB, contiguous on both sides)
             const unsigned char* xg = reinterpret_cast<const unsigned char*>(a.Xs) + (long long)f0 * WS_FRAG + wave * 4096;
             auto issue = [&](int i) {                                     // (callers guarantee i < nf)
-                {
-                    const unsigned long long sb = (unsigned long long)(xg + (long long)i * WS_FRAG);
-                    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sb);
-                    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sb >> 32));
-                    const void* sbase = reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
-                    const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((i % WS_SLOTS) * WS_FRAG + wave * 4096);
 #ifndef SBEV_EXP_NOGLDS
-                    asm volatile(
-                        "s_mov_b32 m0, %0\n\t"
-                        "s_nop 4\n\t"
-                        "global_load_lds_dwordx4 %1, %2\n\t"
-                        "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                        "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                        "global_load_lds_dwordx4 %1, %2 offset:3072\n\t"
-                        :
-                        : "s"(dst), "v"(voff), "s"(sbase)
-                        : "memory");
+                lds_dma<4>(xg + (long long)i * WS_FRAG, voff, (unsigned)((i % WS_SLOTS) * WS_FRAG + wave * 4096));
 #endif
-                }
             };
             issue(0);
             if (nf > 1) issue(1);
@@ -1146,7 +1136,8 @@ struct Out4Args {
     float* P;                    // [S, M, 256] partial slabs
     int M, K;
     long long ldx;
-    int ntm, base, rem, S;       // row tiles: the first `rem` have base + 1 fragments of 32 rows, the others `base`; K chunks
+    int ntm; RowSplit rows;      // row tiles and their fragments of 32 rows
+    int S;                       // K chunks
     const float* nscale;         // [256] 2^-ew[n] 2^-ex
     // in-launch fold of the S slabs (round 6): the S chunk-workgroups of a row tile are co-resident (one round of workgroups: host-checked),
     // meet at fold_sync[row tile] and each sums a share of the tile's rows over all slabs, in slab order, into `folded` [M, 256]
@@ -1179,8 +1170,7 @@ struct PairTile {
         const unsigned logical = xcd_contiguous(blockIdx.x, gridDim.x);
         const int c = (int)(logical / (unsigned)a.ntm), r = (int)(logical % (unsigned)a.ntm);
         chunk = c, rt = r;
-        f0 = r * a.base + (r < a.rem ? r : a.rem);
-        nf = a.base + (r < a.rem ? 1 : 0);
+        f0 = a.rows.first(r), nf = a.rows.count(r);
     }
     __device__ __forceinline__ int row0() const { return f0 * 32; }
     // the k-steps of 16 of K chunk ch are [kstep0(a, ch), kstep0(a, ch + 1))
@@ -1267,8 +1257,8 @@ struct PairWRing {
         if (HOOKS) sl = sl & 7;
 #endif
         const unsigned dst = base + (unsigned)((i % PAIR_NST) * PAIR_WSLOT);
-        glds16_images<2>(wg0 + (long long)sl * (2 * 1024), voff, dst);
-        glds16_images<2>(wg0 + ((long long)KS + sl) * (2 * 1024), voff, dst + 2 * 1024);
+        lds_dma<2>(wg0 + (long long)sl * (2 * 1024), voff, dst);
+        lds_dma<2>(wg0 + ((long long)KS + sl) * (2 * 1024), voff, dst + 2 * 1024);
     }
     __device__ __forceinline__ void read(const unsigned char* lds, int i, bf16x8 (&w)[2][2]) const {
         const unsigned char* src = lds + base + (i % PAIR_NST) * PAIR_WSLOT + voff;
@@ -1654,13 +1644,12 @@ int out_chunks(long long M, int K) {
 // k-steps of 16.  128-row kernel: 4 fragments, whole rounds.  256-row kernel: 8 fragments (taken from >= 2 per tile), ONE round
 // (measured, samples/s with / without: 3200 rows 1289 / 1189, 3600 rows 506 / 481, 1600 rows 194.6 / 187.2; 900 rows 536.6 / 538.8 -- the
 // kernel itself is 4 us faster there too, but 4 row tiles x 64 chunks leave the tail 64 slabs to sum instead of 32: from 1024 rows)
-struct Out4Plan { int ntm, base, rem, S; };
+struct Out4Plan { int ntm; RowSplit rows; int S; };
 Out4Plan out_plan(long long M, int K, int max_frags, bool one_round) {
     const int nfrag = (int)((M + 31) / 32);
     Out4Plan p{};
     p.ntm = (nfrag + max_frags - 1) / max_frags;
-    p.base = nfrag / p.ntm;
-    p.rem = nfrag % p.ntm;
+    p.rows = row_split(nfrag, p.ntm);
     p.S = fill_rounds(p.ntm, K / 16 / 8, one_round);
     return p;
 }
@@ -1672,7 +1661,7 @@ std::atomic<int> g_out8_min_rows{out8_clamp(getenv("SBEV_OUT8_MIN_ROWS") ? atoi(
 bool out8_takes(long long M, int K, int mr) {      // mr: the caller's reading of g_out8_min_rows
     if (mr <= 0 || M < mr) return false;
     const Out4Plan p = out8_plan(M, K);
-    return p.base >= 2 && p.ntm <= 256;
+    return p.rows.base >= 2 && p.ntm <= 256;
 }
 
 }  // namespace
@@ -1765,81 +1754,112 @@ static auto gen3_kernel(int nimg, int rf) -> void (*)(GenArgs) {             // 
     }
 }
 
-static int gen_launch(const uint16_t* Xs, const uint16_t* Ws, const float* bias, float* Y, int64_t M, int N, int K, int64_t ldy, int relu,
-                      int nimg, const float* xscale, const float* colscale, bool weight_stationary, sbev_stream_t stream,
-                      const sbev::LazyScan* lz = nullptr, const uint32_t* skip_hdr = nullptr) {
-    SBEV_REQUIRE(M >= 0 && sbev_linear_bf16s_gen_ok(M > 0 ? M : 1, N, K), "sbev_linear_bf16s_gen: needs N %% 256 == 0, K %% 32 == 0, K <= 4096 (M=%lld N=%d K=%d)", (long long)M, N, K);
-    if (M == 0) return SBEV_OK;
-    SBEV_REQUIRE(Xs && Ws && Y && ldy >= N && ldy % 4 == 0, "sbev_linear_bf16s_gen: bad pointers / leading dimension");
-    SBEV_REQUIRE((((uintptr_t)Xs | (uintptr_t)Ws | (uintptr_t)Y) & 15) == 0 && (!bias || (((uintptr_t)bias) & 15) == 0), "sbev_linear_bf16s_gen: 16-byte alignment");
+// Everything a generator launch needs, decided on the host from the shape alone (sbev_linear_gen_plan reports it; tests/test_gen_plan_host.py)
+struct GenLaunch { int c0, nc; unsigned grid; int lds; };      // column tiles [c0, c0 + nc), workgroups, dynamic LDS bytes
+struct GenPlan {
+    int rf;                      // 0: the weight-stationary kernel; 2 / 4: the tiled kernel with 128- / 256-row tiles
+    int ntm;                     // row splits (weight-stationary) / row tiles ...
+    RowSplit rows;               // ... and their fragments
+    int nct;                     // column tiles
+    int ntask;                   // weight-stationary: nct * ntm tasks walked by ...
+    unsigned ws_grid;            // ... <= one workgroup per CU
+    int per, tiles_per_wg;       // tiled: workgroups per row tile; column tiles one of them may walk per launch (their slices wait in LDS)
+    int lds_fixed, lds_slice;    // LDS bytes of every launch + per column tile a workgroup walks
+    int nlaunch;                 // tiled: launches over column ranges of per * tiles_per_wg tiles (weight-stationary: 1)
+    bool ws() const { return rf == 0; }
+    GenLaunch launch(int i) const {
+        if (ws()) return {0, nct, ws_grid, lds_fixed};
+        const int max_ct = per * tiles_per_wg, c0 = i * max_ct;
+        const int nc = nct - c0 < max_ct ? nct - c0 : max_ct, pc = per < nc ? per : nc;
+        // one row tile per workgroup for life: grid = a multiple of ntm, at most the tile count
+        return {c0, nc, (unsigned)(pc * ntm), lds_fixed + (nc + pc - 1) / pc * lds_slice};
+    }
+};
+// shape: covered (sbev_linear_bf16s_gen_ok, M >= 1, nimg 2 .. 5); weight_stationary: the caller's reading of the switch
+static GenPlan gen_plan(int64_t M, int N, int K, int64_t ldy, int nimg, bool weight_stationary, int cus) {
     const int nfrag = (int)((M + 31) / 32);
-    const int cus = device_cus(256);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool ws = weight_stationary && sbev::gen_ws_shape_ok(M, K, ldy, nimg);
-    SBEV_REQUIRE(!lz || ws, "generator: the on-demand relayout's scan rides in the weight-stationary kernel only");
-    SBEV_REQUIRE(!skip_hdr || (ws && !lz), "generator: only the weight-stationary kernel skips, and never with a relayout scan riding in it");
-    if (ws) {
+    GenPlan p{};
+    p.nct = N / G_COLS;
+    if (weight_stationary && sbev::gen_ws_shape_ok(M, K, ldy, nimg)) {
         // row splits: tasks = column tiles x splits walked by <= one workgroup per CU; a task costs its fragments + ~4 fragments' worth
         // of weight load (256 KB that nothing overlaps).  c2 (29 fragments, 128 column tiles): 2 splits = 256 tasks of 15 / 14 fragments
-        const int nct = N / G_COLS;
-        int nrs = 1;
+        p.ntm = 1;
         double best = 1e30;
         for (int r = 1; r <= 16 && r <= nfrag; ++r) {
-            const long long tasks = (long long)nct * r;
+            const long long tasks = (long long)p.nct * r;
             const double cost = (double)((tasks + cus - 1) / cus) * ((nfrag + r - 1) / r + 4.0);
-            if (cost < best - 1e-9) { best = cost; nrs = r; }
+            if (cost < best - 1e-9) { best = cost; p.ntm = r; }
         }
-        GenWsArgs w{Xs, Ws, bias, Y, (int)M, N, (long long)ldy, relu, nrs, nfrag / nrs, nfrag % nrs, nct * nrs, colscale, xscale, 0, 4, {}, skip_hdr};
-        if (lz) {
-            w.lazy_on = 1; w.lazy_esize = lz->esize;
-            fill_lazy_args(w.lazy, *lz, false);
-        }
-        const unsigned grid = (unsigned)(w.ntask < cus ? w.ntask : cus);
-        const int st = launch_lds(gen_ws_kernel(nimg, relu != 0), grid, WS_SLOTS * WS_FRAG, s, w, "sbev_linear_bf16s_gen", 1);
-        if (st != SBEV_OK) return st;
-        return sbev::check_launch("sbev_linear_bf16s_gen");
+        p.rows = row_split(nfrag, p.ntm);
+        p.ntask = p.nct * p.ntm;
+        p.ws_grid = (unsigned)(p.ntask < cus ? p.ntask : cus);
+        p.lds_fixed = WS_LDS;
+        p.nlaunch = 1;
+        return p;
     }
     // 256-row tiles (wave = 128 x 64) carry 1.5x the MFMA work per operand byte; 128-row tiles only where they fill the chip
     // better (few rows) -- SBEV_BF16S_GEN_RF=2/4 forces one (A/B runs)
     static const int forced_rf = getenv("SBEV_BF16S_GEN_RF") ? atoi(getenv("SBEV_BF16S_GEN_RF")) : 0;
-    const int rf = forced_rf == 2 || forced_rf == 4 ? forced_rf : (nfrag > 4 ? 4 : 2);
-    const int tf = 2 * rf;
-    const int ntm = (nfrag + tf - 1) / tf;
-    GenArgs a{Xs, Ws, bias, Y, (int)M, N, K, (long long)ldy, relu, ntm, nfrag / ntm, nfrag % ntm, colscale, xscale};
-    const int nim = nimg == 3 ? 3 : 2;          // images per operand
-    // one row tile per workgroup for life: grid = a multiple of ntm, at most the CU count, at most the tile count
-    long long per = cus / ntm < 1 ? 1 : cus / ntm;
-    if (per > N / G_COLS) per = N / G_COLS;
-    // the bias slices of a workgroup's column tiles wait in LDS behind the stage ring: at most 16 tiles (16 KiB) per launch,
-    // wider matrices take several launches over column ranges
-    const int nct = N / G_COLS;
-    const int nst = rf == 2 ? 4 : 3;
-    const int ring_bytes = nst * nim * (tf + 8) * 1024 + (nim == 2 && rf == 4 ? 8 * 32 * 36 * 4 : 0);      // + the epilogue's transpose patches
-    int tiles_per_wg = (160 * 1024 - ring_bytes) / (G_COLS * 4 * (nimg >= 4 ? 2 : 1));      // bias (+ scale) slices behind the ring
-    tiles_per_wg = tiles_per_wg > 16 ? 16 : tiles_per_wg;
-    const long long max_ct = per * tiles_per_wg;
-    for (long long c0 = 0; c0 < nct; c0 += max_ct) {
-        const int nc = (int)(nct - c0 < max_ct ? nct - c0 : max_ct);
+    p.rf = forced_rf == 2 || forced_rf == 4 ? forced_rf : (nfrag > 4 ? 4 : 2);
+    const Gen3Lds lds{nimg == 3 ? 3 : 2, p.rf};
+    p.ntm = (nfrag + 2 * p.rf - 1) / (2 * p.rf);
+    p.rows = row_split(nfrag, p.ntm);
+    // at most the CU count (where it holds a workgroup per row tile at all), at most the tile count
+    p.per = cus / p.ntm < 1 ? 1 : cus / p.ntm;
+    if (p.per > p.nct) p.per = p.nct;
+    p.tiles_per_wg = lds.max_tiles(nimg >= 4);
+    p.lds_fixed = lds.slices_at();
+    p.lds_slice = Gen3Lds::slice_bytes(nimg >= 4);
+    const long long max_ct = (long long)p.per * p.tiles_per_wg;
+    p.nlaunch = (int)((p.nct + max_ct - 1) / max_ct);
+    return p;
+}
+
+namespace sbev {
+// checks in one order (mode, fp16 scales, shape, empty call, pointers, alignment), plan, fill the argument block, launch
+int launch_gen_gemm(const GenGemm& g, hipStream_t s) {
+    const bool f16 = g.nimg >= 4;
+    SBEV_REQUIRE(mode_ok(g.nimg), "sbev_linear_bf16s_gen: nimg=%d (2 = bf16x3, 3 = bf16x6, 4 / 5 = fp16 with 3 / 4 image products)", g.nimg);
+    SBEV_REQUIRE(!f16 || g.M == 0 || (g.X.scale && g.W.scale), "sbev_linear_f16s_gen: null scale pointer");
+    SBEV_REQUIRE(g.M >= 0 && sbev_linear_bf16s_gen_ok(g.M > 0 ? g.M : 1, g.N, g.K), "sbev_linear_bf16s_gen: needs N %% 256 == 0, K %% 32 == 0, K <= 4096 (M=%lld N=%d K=%d)", (long long)g.M, g.N, g.K);
+    if (g.M == 0) return SBEV_OK;
+    SBEV_REQUIRE(g.X.frags && g.W.frags && g.Y && g.ldy >= g.N && g.ldy % 4 == 0, "sbev_linear_bf16s_gen: bad pointers / leading dimension");
+    SBEV_REQUIRE((((uintptr_t)g.X.frags | (uintptr_t)g.W.frags | (uintptr_t)g.Y) & 15) == 0 && (!g.bias || (((uintptr_t)g.bias) & 15) == 0), "sbev_linear_bf16s_gen: 16-byte alignment");
+    const GenPlan p = gen_plan(g.M, g.N, g.K, g.ldy, g.nimg, g.weight_stationary, device_cus(256));
+    SBEV_REQUIRE(!g.scan || p.ws(), "generator: the on-demand relayout's scan rides in the weight-stationary kernel only");
+    SBEV_REQUIRE(!g.skip_hdr || (p.ws() && !g.scan), "generator: only the weight-stationary kernel skips, and never with a relayout scan riding in it");
+    const float *xscale = f16 ? g.X.scale : nullptr, *colscale = f16 ? g.W.scale : nullptr;      // (the bf16 kernels read neither)
+    if (p.ws()) {
+        const GenLaunch l = p.launch(0);
+        GenWsArgs w{g.X.frags, g.W.frags, g.bias, g.Y, (int)g.M, g.N, (long long)g.ldy, g.relu, p.ntm, p.rows, p.ntask, colscale, xscale, 0, 4, {}, g.skip_hdr};
+        if (g.scan) {
+            w.lazy_on = 1; w.lazy_esize = g.scan->esize;
+            fill_lazy_args(w.lazy, *g.scan, false);
+        }
+        const int st = launch_lds(gen_ws_kernel(g.nimg, g.relu != 0), l.grid, l.lds, s, w, "sbev_linear_bf16s_gen", 1);
+        return st != SBEV_OK ? st : check_launch("sbev_linear_bf16s_gen");
+    }
+    const GenArgs a{g.X.frags, g.W.frags, g.bias, g.Y, (int)g.M, g.N, g.K, (long long)g.ldy, g.relu, p.ntm, p.rows, colscale, xscale};
+    for (int i = 0; i < p.nlaunch; ++i) {
+        const GenLaunch l = p.launch(i);
         GenArgs ac = a;
-        ac.Ws = Ws + c0 * 8 * (long long)(K / 16) * nim * 512;       // 8 fragment blocks of 32 columns per tile
-        ac.colscale = colscale ? colscale + c0 * G_COLS : nullptr;
-        ac.bias = bias ? bias + c0 * G_COLS : nullptr;
-        ac.Y = Y + c0 * G_COLS;
-        ac.N = nc * G_COLS;
-        const long long pc = per < nc ? per : nc;
-        const unsigned gridc = (unsigned)(pc * ntm);
-        const int bias_bytes = (int)((nc + pc - 1) / pc) * G_COLS * 4 * (nimg >= 4 ? 2 : 1);     // (fp16 modes: + the column scales)
-        const int lds = ring_bytes + bias_bytes;
-        const int st = launch_lds(gen3_kernel(nimg, rf), gridc, lds, s, ac, "sbev_linear_bf16s_gen", 1);
+        ac.Ws = a.Ws + (long long)l.c0 * 8 * (g.K / 16) * (g.nimg == 3 ? 3 : 2) * 512;      // 8 fragment blocks of 32 columns per tile
+        ac.colscale = colscale ? colscale + (long long)l.c0 * G_COLS : nullptr;
+        ac.bias = g.bias ? g.bias + (long long)l.c0 * G_COLS : nullptr;
+        ac.Y = g.Y + (long long)l.c0 * G_COLS;
+        ac.N = l.nc * G_COLS;
+        const int st = launch_lds(gen3_kernel(g.nimg, p.rf), l.grid, l.lds, s, ac, "sbev_linear_bf16s_gen", 1);
         if (st != SBEV_OK) return st;
     }
-    return sbev::check_launch("sbev_linear_bf16s_gen");
+    return check_launch("sbev_linear_bf16s_gen");
 }
+}  // namespace sbev
 
 extern "C" int sbev_linear_bf16s_gen(const uint16_t* Xs, const uint16_t* Ws, const float* bias, float* Y, int64_t M, int N, int K,
                                      int64_t ldy, int relu, int nimg, sbev_stream_t stream) {
     SBEV_REQUIRE(nimg == 2 || nimg == 3, "sbev_linear_bf16s_gen: nimg=%d (2 = bf16x3, 3 = bf16x6)", nimg);
-    return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nimg, nullptr, nullptr, sbev::gen_weight_stationary_enabled(), stream);
+    return sbev::launch_gen_gemm({{Xs, nullptr}, {Ws, nullptr}, bias, Y, M, N, K, ldy, relu, nimg, sbev::gen_weight_stationary_enabled(), nullptr, nullptr},
+                                 reinterpret_cast<hipStream_t>(stream));
 }
 
 // fp16 hi + lo images (sbev_pack_f16s_frags): xscale = X's {up, down} (per tensor), wdown = the [N] down-scales of W's rows;
@@ -1847,20 +1867,21 @@ extern "C" int sbev_linear_bf16s_gen(const uint16_t* Xs, const uint16_t* Ws, con
 extern "C" int sbev_linear_f16s_gen(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y,
                                     int64_t M, int N, int K, int64_t ldy, int relu, int nprod, sbev_stream_t stream) {
     SBEV_REQUIRE(nprod == 3 || nprod == 4, "sbev_linear_f16s_gen: nprod=%d (3 or 4 image products)", nprod);
-    SBEV_REQUIRE(M == 0 || (xscale && wdown), "sbev_linear_f16s_gen: null scale pointer");
-    return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nprod + 1, xscale, wdown, sbev::gen_weight_stationary_enabled(), stream);
+    return sbev::launch_gen_gemm({{Xs, xscale}, {Ws, wdown}, bias, Y, M, N, K, ldy, relu, nprod + 1, sbev::gen_weight_stationary_enabled(), nullptr, nullptr},
+                                 reinterpret_cast<hipStream_t>(stream));
 }
 
-namespace sbev {
-int linear_gen_split(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y, int64_t M,
-                     int N, int K, int64_t ldy, int relu, int nimg, bool weight_stationary, const LazyScan* lz, hipStream_t stream,
-                     const uint32_t* skip_hdr) {
-    SBEV_REQUIRE(nimg >= 2 && nimg <= 5, "sbev_linear_bf16s_gen: nimg=%d (2 = bf16x3, 3 = bf16x6, 4 / 5 = fp16 with 3 / 4 image products)", nimg);
-    SBEV_REQUIRE(nimg < 4 || M == 0 || (xscale && wdown), "sbev_linear_f16s_gen: null scale pointer");
-    return gen_launch(Xs, Ws, bias, Y, M, N, K, ldy, relu, nimg, nimg >= 4 ? xscale : nullptr, nimg >= 4 ? wdown : nullptr, weight_stationary,
-                      reinterpret_cast<sbev_stream_t>(stream), lz, skip_hdr);
+// gen_plan's answer as int32 words (layout: include/sbev_hip.h); cus = 0: the current device's.  Touches no device otherwise
+extern "C" int sbev_linear_gen_plan(int64_t M, int N, int K, int64_t ldy, int nimg, int weight_stationary, int cus, int32_t* out, int capacity) {
+    SBEV_REQUIRE(mode_ok(nimg) && M >= 1 && sbev_linear_bf16s_gen_ok(M, N, K) && ldy >= N && cus >= 0, "sbev_linear_gen_plan: shape not covered (M=%lld N=%d K=%d nimg=%d)", (long long)M, N, K, nimg);
+    const GenPlan p = gen_plan(M, N, K, ldy, nimg, weight_stationary != 0, cus > 0 ? cus : device_cus(256));
+    const long long words = 7 + 4LL * p.nlaunch;
+    SBEV_REQUIRE(out && capacity >= words, "sbev_linear_gen_plan: %lld words needed", words);
+    for (int v : {p.rf, p.ntm, p.rows.base, p.rows.rem, p.ws() ? p.ntask : p.per, p.tiles_per_wg, p.nlaunch}) *out++ = v;
+    for (int i = 0; i < p.nlaunch; ++i)
+        for (int v : {p.launch(i).c0, p.launch(i).nc, (int)p.launch(i).grid, p.launch(i).lds}) *out++ = v;
+    return (int)words;
 }
-}  // namespace sbev
 
 extern "C" int sbev_linear_bf16s_out_ok(int64_t M, int N, int K) {
     return M >= 1 && M <= 0x7fffffffLL / 512 && N == 256 && K >= 256 && K % 32 == 0;
@@ -1929,7 +1950,7 @@ int launch_out_proj_slabs(const OutProj& o, OutProjResult* r, hipStream_t s) {
         const Out4Plan pl = big ? out8_plan(M, K) : out4_plan(M, K);
         r->folded = !big && o.fold_sync && o.folded && out_fold_shape_ok(M, K);       // (the caller asked AND the shape / device allow it: else S slabs as before)
         r->used = r->folded ? 1 : pl.S;                                               // folded: the consumer reads `folded` as ONE slab
-        const Out4Args a4{reinterpret_cast<const unsigned*>(o.X.x), o.Wp, o.slabs, (int)M, K, (long long)o.X.ldx, pl.ntm, pl.base, pl.rem, pl.S, o.nscale,
+        const Out4Args a4{reinterpret_cast<const unsigned*>(o.X.x), o.Wp, o.slabs, (int)M, K, (long long)o.X.ldx, pl.ntm, pl.rows, pl.S, o.nscale,
                           r->folded ? o.fold_sync : nullptr, r->folded ? o.folded : nullptr, g_out_fold_drop.load(std::memory_order_relaxed)};
         const long long wgs4 = (long long)pl.ntm * pl.S;
         SBEV_REQUIRE(wgs4 <= 0x7fffffffLL, "sbev_linear_splitk_f16s: too many workgroups");

@@ -174,14 +174,27 @@ struct LazyScan {
     uint32_t *need, *done;
     bool last;
 };
-// the split-image generator GEMM behind sbev_linear_bf16s_gen (nimg 2 / 3; xscale = wdown = null) and sbev_linear_f16s_gen (nimg 4 / 5);
-// weight_stationary: the caller's reading of sbev_linear_gen_weight_stationary -- the weight-stationary kernel runs where it is set AND
-// gen_ws_shape_ok; lz (non-null: this layer's scan in the kernel's prologue) needs both
+// gemm_bf16s.hip: the split-image generator GEMM Y [M, ldy] = X W^T + bias behind sbev_linear_bf16s_gen (nimg 2 / 3) and
+// sbev_linear_f16s_gen (nimg 4 / 5) as ONE description (the entry points build it from their positional arguments, decoder.hip once
+// per layer).  An operand is its image fragments WITH its fp16 scale (read in the fp16 modes only)
+struct SplitFrags {
+    const uint16_t* frags;     // [ceil(rows/32)][K/16][images][64][8] (sbev_pack_bf16s_frags / sbev_pack_f16s_frags)
+    const float* scale;        // X: {2^ex, 2^-ex} in device memory; W: the [N] down-scales 2^-ew of its rows
+};
+struct GenGemm {
+    SplitFrags X, W;
+    const float* bias;         // [N] or null
+    float* Y;
+    int64_t M;
+    int N, K;
+    int64_t ldy;
+    int relu, nimg;            // nimg 2 / 3: bf16x3 / bf16x6; 4 / 5: fp16 with 3 / 4 image products
+    bool weight_stationary;    // the caller's reading of sbev_linear_gen_weight_stationary: that kernel runs where it is set AND gen_ws_shape_ok
+    const LazyScan* scan;      // non-null: this layer's relayout scan in the kernel's prologue (weight-stationary kernel only)
+    const uint32_t* skip_hdr;  // non-null: layer 0 of a step with a prefix cache (weight-stationary kernel only, never with scan): prefix_clean
+};
 bool gen_ws_shape_ok(int64_t M, int K, int64_t ldy, int nimg);
-// skip_hdr (non-null: layer 0 of a step with a prefix cache, weight-stationary kernel only, never together with lz): see prefix_clean
-int linear_gen_split(const uint16_t* Xs, const float* xscale, const uint16_t* Ws, const float* wdown, const float* bias, float* Y, int64_t M,
-                     int N, int K, int64_t ldy, int relu, int nimg, bool weight_stationary, const LazyScan* lz, hipStream_t stream,
-                     const uint32_t* skip_hdr = nullptr);
+int launch_gen_gemm(const GenGemm& g, hipStream_t s);
 int launch_lazy_relayout(const LazyScan& scan, bool first, hipStream_t s);      // first: the step's first move (every marked unit is new)
 
 // row_chain.hip: the row-local op chains of a decoder layer as single launches (weights pre-packed: sbev_decoder_chain_pack)
