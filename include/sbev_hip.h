@@ -688,6 +688,35 @@ int sbev_msmv_bwd_ex(const void* const* feats, void* const* grad_feats, const in
                      const float* loc, const float* weights, const float* grad_out, int grad_out_layout, int T, int G,
                      float* grad_loc, float* grad_weights, sbev_stream_t stream);
 
+/* The feature gradient of sbev_msmv_bwd_ex WITHOUT float atomics, bit-reproducible (msmv_sampling_det.hip).  Replaces the grad_value
+ * atomics of ms_deformable_col2im_bilinear_gm (models/csrc/msmv_sampling/msmv_sampling_backward.cu:29-105) in three steps; grad_loc and
+ * grad_weights come from sbev_msmv_bwd_ex with grad_feats == NULL, as before.
+ *   Taps of a call are numbered i = (((b'*Q + q)*P + p)*L + l)*4 + k, k = 2*kh + kw the bilinear corner; n = sbev_msmv_bwd_tap_count.
+ *   Tap i is LIVE iff sbev_msmv_bwd would issue its atomic: level l passes the -1 < h_im < H, -1 < w_im < W test and the corner lies
+ *   inside the map.  Its destination is (l, off), off the element offset of the corner's channel row in grad_feats[l]; its scalar is
+ *   coef_i = (ch * cwid) * wl (two fp32 roundings).
+ *   Result, for every destination and channel c:  acc = +0;  for the destination's live taps in ascending i:
+ *   acc = acc + coef_i * grad_out[b', q, p, c] (product rounded, then the sum);  grad_feats[l][off + c] += acc  (ONE addition: the call
+ *   accumulates, like the atomic path).  Nothing else -- launch geometry, CU count, other streams, eager or graph replay -- reaches
+ *   the bits.
+ * sbev_msmv_bwd_tap_count: pure host function, n = B'*Q*P*L*4; -1 for negative sizes, P > SBEV_MAX_POINTS, L outside
+ *   1..SBEV_MAX_LEVELS, or n > INT64_MAX / 4.
+ * sbev_msmv_bwd_taps: the pyramid arguments of sbev_msmv_bwd_ex (feats[l] are not read) -> keys[n] (device int64: (l << 56) | off of a
+ *   live tap, INT64_MAX of a dead one) and coefs[n] (device fp32; 0 of a dead tap).  Needs stride_px >= C, stride_g >= C where
+ *   gdiv > 1, no negative stride and offsets below 2^56: every destination row has one writer.
+ * sbev_msmv_bwd_sum_sorted: sorted_keys[n] = the keys in ascending order, order[n] = the tap index at each sorted position (device
+ *   int64 both).  They MUST come from a STABLE sort of keys (ties in ascending tap index): that order is the summation order.  This
+ *   library does not sort; torch.sort(keys, stable=True) does.  grad_out as in sbev_msmv_bwd_ex (either layout; T, G read for
+ *   SBEV_OUT_MIX), any C >= 1; n must equal sbev_msmv_bwd_tap_count(Bp, Q, P, L). */
+int64_t sbev_msmv_bwd_tap_count(int64_t Bp, int Q, int P, int L);
+int sbev_msmv_bwd_taps(const void* const* feats, const int32_t* hw, int L,
+                       int64_t Bp, int N, int C, int Q, int P,
+                       int gdiv, const int64_t* stride_bo, int64_t stride_g, const int64_t* stride_v, int64_t stride_px,
+                       const float* loc, const float* weights, int64_t* keys, float* coefs, sbev_stream_t stream);
+int sbev_msmv_bwd_sum_sorted(void* const* grad_feats, int L, const int64_t* sorted_keys, const int64_t* order,
+                             const float* coefs, int64_t n, const float* grad_out, int grad_out_layout,
+                             int64_t Bp, int C, int Q, int P, int T, int G, sbev_stream_t stream);
+
 /* Backward of sbev_project_select: grad_loc [B*T*G,Q,P,3] -> grad_points [B,Q,T,G*P,3] through the camera the forward
  * selected (re-selected bit-exactly).  models/sparsebev_sampling.py:49-114. */
 int sbev_project_select_bwd(const float* sample_points, const float* lidar2img, const float* grad_loc,

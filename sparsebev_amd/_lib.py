@@ -225,6 +225,13 @@ SIGNATURES = {
                                         ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, _c_i64p, ctypes.c_int64, _c_i64p, ctypes.c_int64,
                                         _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    'sbev_msmv_bwd_tap_count': (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'sbev_msmv_bwd_taps': (ctypes.c_int, [ctypes.POINTER(_vp), _c_i32p, ctypes.c_int,
+                                          ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, _c_i64p, ctypes.c_int64, _c_i64p, ctypes.c_int64,
+                                          _vp, _vp, _vp, _vp, _vp]),
+    'sbev_msmv_bwd_sum_sorted': (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int,
+                                                ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
     'sbev_project_select_bwd': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp, _vp]),
     'sbev_sampling_front_bwd': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_double),

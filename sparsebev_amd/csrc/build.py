@@ -17,6 +17,8 @@ UNITS = {
     'msmv_sampling.hip': [],
     # hardware float atomics (global_atomic_add_f32) for the grad_value scatter instead of a CAS loop
     'msmv_sampling_bwd.hip': ['-munsafe-fp-atomics'],
+    # the atomics-free feature gradient: "product rounded, then sum rounded" is its definition -- no FMA contraction in this file
+    'msmv_sampling_det.hip': ['-ffp-contract=off'],
     'gemm.hip': [],
     # VGPR-form MFMAs: the kernel fits 256 VGPRs, AGPR-form costs 144 accumulator copies per loop iteration
     'gemm_regtile.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form=1'],

@@ -11,6 +11,7 @@
 //     covers four 64-byte runs (one per corner) instead of 64 scattered dwords.
 // grad wrt the view coordinate is zero by definition (the reference never writes it, :102-104).
 #include "sbev_common.hpp"
+#include "msmv_bwd_geom.hpp"
 
 namespace {
 
@@ -63,8 +64,7 @@ __global__ __launch_bounds__(256) void msmv_bwd_kernel(const BwdArgs a) {
 
     for (int p = 0; p < P; ++p) {
         const float x = locq[p * 3 + 0], y = locq[p * 3 + 1];
-        int view = (int)roundf(locq[p * 3 + 2] * nm1);
-        view = min(max(view, 0), a.N - 1);
+        const int view = sbev::msmv_view(locq[p * 3 + 2], nm1, a.N);
         float gx = 0.f, gy = 0.f, gwl[L];
 #pragma unroll
         for (int l = 0; l < L; ++l) gwl[l] = 0.f;
@@ -80,12 +80,11 @@ __global__ __launch_bounds__(256) void msmv_bwd_kernel(const BwdArgs a) {
 #pragma unroll
             for (int l = 0; l < L; ++l) {
                 const int H = a.H[l], W = a.W[l];
-                const float h_im = y * (float)(H - 1), w_im = x * (float)(W - 1);
-                const bool lvl_ok = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-                if (!lvl_ok) continue;                                   // wave-uniform
-                const float hf = floorf(h_im), wf = floorf(w_im);
-                const float lh = h_im - hf, lw = w_im - wf;
-                const int hc = (int)hf + kh, wc = (int)wf + kw;
+                const sbev::MsmvLevelPos t = sbev::msmv_level_pos(x, y, H, W);
+                if (!t.lvl_ok) continue;                                 // wave-uniform
+                const sbev::MsmvLevelFrac fr = sbev::msmv_level_frac(t);
+                const float lh = fr.lh, lw = fr.lw;
+                const int hc = (int)fr.hf + kh, wc = (int)fr.wf + kw;
                 const bool inb = hc >= 0 && hc <= H - 1 && wc >= 0 && wc <= W - 1;
                 const float ch = kh ? lh : 1.f - lh, cwid = kw ? lw : 1.f - lw;
                 const float cw = ch * cwid;
@@ -165,19 +164,19 @@ __global__ __launch_bounds__(256) void msmv_bwd_c64_kernel(const BwdArgs a) {
 
     for (int p = 0; p < P; ++p) {
         const float x = locq[p * 3 + 0], y = locq[p * 3 + 1];
-        int view = (int)roundf(locq[p * 3 + 2] * nm1);
-        view = min(max(view, 0), a.N - 1);
+        const int view = sbev::msmv_view(locq[p * 3 + 2], nm1, a.N);
         const float g = gq[p * gs_p];
         float v[L][4], lhs[L], lws[L];
         int off[L][4], msk[L];
 #pragma unroll
         for (int l = 0; l < L; ++l) {
             const int H = a.H[l], W = a.W[l];
-            const float h_im = y * (float)(H - 1), w_im = x * (float)(W - 1);
-            const bool lvl_ok = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
-            const float hf = floorf(h_im), wf = floorf(w_im);
-            lhs[l] = h_im - hf;
-            lws[l] = w_im - wf;
+            const sbev::MsmvLevelPos t = sbev::msmv_level_pos(x, y, H, W);
+            const sbev::MsmvLevelFrac fr = sbev::msmv_level_frac(t);
+            const bool lvl_ok = t.lvl_ok;
+            const float hf = fr.hf, wf = fr.wf;
+            lhs[l] = fr.lh;
+            lws[l] = fr.lw;
             const int vb = view * (int)a.stride_v[l];
             int mk = 0;
 #pragma unroll

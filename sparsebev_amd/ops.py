@@ -5,6 +5,7 @@ done by hand-written gfx950 kernels in libsbev_hip.so.  Tensors must live on a H
 CPU path (calling these with CPU tensors raises).
 """
 import ctypes
+import os
 
 import torch
 
@@ -104,9 +105,62 @@ def _msmv_forward(feats, sampling_locations, scale_weights, out_layout, T, G):
     return out
 
 
+_DET_FEAT_GRAD = os.environ.get('SBEV_DET_FEAT_GRAD', '0') == '1'
+
+
+def deterministic_feature_grad(enable=None):
+    """Process-wide switch of the sampler's feature gradient: off (default) = float atomics (sbev_msmv_bwd[_ex]), on = the atomics-free,
+    bit-reproducible sum over a sorted tap list (sbev_msmv_bwd_taps / torch.sort / sbev_msmv_bwd_sum_sorted).  ``SBEV_DET_FEAT_GRAD=1``
+    in the environment starts with it on.  ``enable`` None: query only.  Returns the previous setting.  The mode a backward runs in is
+    ``deterministic_feature_grad_active()``, read when the backward runs."""
+    global _DET_FEAT_GRAD
+    prev = _DET_FEAT_GRAD
+    if enable is not None:
+        _DET_FEAT_GRAD = bool(enable)
+    return prev
+
+
+def deterministic_feature_grad_active():
+    """The switch, or torch.use_deterministic_algorithms(True)."""
+    return _DET_FEAT_GRAD or torch.are_deterministic_algorithms_enabled()
+
+
+def _msmv_backward(feats, N, G, Bp, C, loc, weights, grad_out, grad_feats, grad_layout, T, Gout, deterministic):
+    """Every sampler backward of this package: (grad_loc, grad_weights) of ``feats`` as _pyramid(feats, N, G) describes them, the feature
+    gradient ACCUMULATED into ``grad_feats`` (None: frozen features, no feature gradient).  ``deterministic`` None: the switch."""
+    lib = _lib.load()
+    Q, P = loc.shape[1:3]
+    loc, weights, grad_out = loc.contiguous(), weights.contiguous(), grad_out.contiguous()
+    gloc = torch.empty_like(loc)
+    gw = torch.empty_like(weights)
+    (c_feats, c_hw, L), strides = _pyramid(feats, N, G)
+    if deterministic is None:
+        deterministic = deterministic_feature_grad_active()
+    det = bool(deterministic) and grad_feats is not None
+    c_gfeats = _level_ptrs(grad_feats) if grad_feats is not None else None
+    st = lib.sbev_msmv_bwd_ex(c_feats, None if det else c_gfeats, c_hw, L, Bp, N, C, Q, P, *strides, _ptr(loc), _ptr(weights), _ptr(grad_out),
+                              grad_layout, T, Gout, _ptr(gloc), _ptr(gw), _stream())
+    _lib.check(st, 'sbev_msmv_bwd_ex')
+    if det:
+        n = lib.sbev_msmv_bwd_tap_count(Bp, Q, P, L)
+        if n < 0:
+            raise RuntimeError("deterministic feature gradient: B'*Q*P*L*4 is too large")
+        if n > 0:
+            keys = torch.empty(n, device=loc.device, dtype=torch.int64)
+            coefs = torch.empty(n, device=loc.device, dtype=torch.float32)
+            st = lib.sbev_msmv_bwd_taps(c_feats, c_hw, L, Bp, N, C, Q, P, *strides, _ptr(loc), _ptr(weights), _ptr(keys), _ptr(coefs), _stream())
+            _lib.check(st, 'sbev_msmv_bwd_taps')
+            # THE index: a stable ascending sort -- integer work (no execution order in its result), ties keep ascending tap index
+            sorted_keys, order = torch.sort(keys, stable=True)
+            st = lib.sbev_msmv_bwd_sum_sorted(c_gfeats, L, _ptr(sorted_keys), _ptr(order), _ptr(coefs), n, _ptr(grad_out), grad_layout,
+                                              Bp, C, Q, P, T, Gout, _stream())
+            _lib.check(st, 'sbev_msmv_bwd_sum_sorted')
+    return gloc, gw
+
+
 class MSMVSampling(torch.autograd.Function):
     """Autograd wrapper, the counterpart of MSMVSamplingC2345 / C23456 (models/csrc/wrapper.py:41-84): forward and
-    backward are both HIP kernels (sbev_msmv_fwd / sbev_msmv_bwd); fp32 features, reference layout."""
+    backward are both HIP kernels (sbev_msmv_fwd / sbev_msmv_bwd_ex, see _msmv_backward); fp32 features, reference layout."""
 
     @staticmethod
     def forward(ctx, sampling_locations, scale_weights, *feats):
@@ -121,13 +175,8 @@ class MSMVSampling(torch.autograd.Function):
         grad_output = grad_output.contiguous().float()
         Bp, N, _, _, C = feats[0].shape
         _, Q, P, _ = loc.shape
-        gfeats = [torch.zeros_like(f) for f in feats]              # the op accumulates with atomics
-        gloc = torch.empty_like(loc)
-        gw = torch.empty_like(weights)
-        (c_feats, c_hw, L), strides = _pyramid(feats, N)
-        st = _lib.load().sbev_msmv_bwd(c_feats, _level_ptrs(gfeats), c_hw, L, Bp, N, C, Q, P, *strides,
-                                       _ptr(loc), _ptr(weights), _ptr(grad_output), _ptr(gloc), _ptr(gw), _stream())
-        _lib.check(st, 'sbev_msmv_bwd')
+        gfeats = [torch.zeros_like(f) for f in feats]              # the op accumulates (atomics, or one addition per row)
+        gloc, gw = _msmv_backward(feats, N, None, Bp, C, loc, weights, grad_output, gfeats, OUT_REF, 1, 1, None)
         return (gloc, gw, *gfeats)
 
 
@@ -206,28 +255,22 @@ def msmv_sampling_nhwc(feats_nhwc, B, T, G, sampling_locations, scale_weights, o
 
 
 def msmv_sampling_nhwc_backward(feats_nhwc, B, T, G, sampling_locations, scale_weights, grad_out, grad_feats=None,
-                                grad_layout=OUT_MIX):
+                                grad_layout=OUT_MIX, deterministic=None):
     """Backward of msmv_sampling_nhwc (sbev_msmv_bwd_ex): grad_out in the forward's output layout ->
-    (grad_loc [B',Q,P,3], grad_weights [B',Q,P,L]); grad wrt the features is ACCUMULATED (atomics) into ``grad_feats``
-    (list of fp32 buffers shaped like feats_nhwc) or skipped entirely when it is None (frozen features)."""
+    (grad_loc [B',Q,P,3], grad_weights [B',Q,P,L]); grad wrt the features is ACCUMULATED into ``grad_feats`` (list of fp32 buffers
+    shaped like feats_nhwc) or skipped entirely when it is None (frozen features).  How it is accumulated: ``deterministic`` False =
+    float atomics (the sum's order changes from run to run); True = the bit-reproducible sorted-tap sum (four launches: the kernel
+    above without feature buffers, sbev_msmv_bwd_taps, torch.sort, sbev_msmv_bwd_sum_sorted); None = deterministic_feature_grad_active()."""
     feats = list(feats_nhwc)
     _need_device(sampling_locations, scale_weights, grad_out, *feats)
     if _feat_dtype(feats) != _F32:
         raise NotImplementedError('the sampling backward needs fp32 feature maps (bf16 storage is an inference format)')
     N = N_VIEWS
     Bp = B * T * G
-    Q, P = _check_sampling_args(feats, sampling_locations, scale_weights, Bp, 'msmv_sampling_nhwc_backward')
+    _check_sampling_args(feats, sampling_locations, scale_weights, Bp, 'msmv_sampling_nhwc_backward')
     GC = feats[0].shape[-1]
     C = GC // G
-    gloc = torch.empty_like(sampling_locations)
-    gw = torch.empty_like(scale_weights)
-    (c_feats, c_hw, L), strides = _pyramid(feats, N, G)
-    c_gfeats = _level_ptrs(grad_feats) if grad_feats is not None else None
-    st = _lib.load().sbev_msmv_bwd_ex(c_feats, c_gfeats, c_hw, L, Bp, N, C, Q, P, *strides,
-                                      _ptr(sampling_locations.contiguous()), _ptr(scale_weights.contiguous()), _ptr(grad_out.contiguous()),
-                                      grad_layout, T, G, _ptr(gloc), _ptr(gw), _stream())
-    _lib.check(st, 'sbev_msmv_bwd_ex')
-    return gloc, gw
+    return _msmv_backward(feats, N, G, Bp, C, sampling_locations, scale_weights, grad_out, grad_feats, grad_layout, T, G, deterministic)
 
 
 def msmv_sampling_ring(levels, B, T, G, frame_slots, n_slots, sampling_locations, scale_weights, out_layout=OUT_MIX):

@@ -15,6 +15,9 @@ step's.  This is torch.cuda.graphs' whole-network recipe; what this module adds 
     memory, and ``replay`` draws a new word (one small torch launch, torch's CUDA generator) before it replays the graph.  Forward and
     backward of a step see the same word.
 
+  * the feature-gradient mode (ops.deterministic_feature_grad, or torch.use_deterministic_algorithms) is whatever is on at capture;
+    ``replay`` refuses to run the graph under the other one.
+
 Inputs are STATIC tensors: write the next batch into them with ``copy_()`` (the features, the queries), pass the next ``img_metas`` to
 ``replay``.  Gradients land in the same ``.grad`` tensors every replay and OVERWRITE them (they were ``None`` at capture): run the
 optimizer after ``replay()``, and never ``zero_grad(set_to_none=True)`` -- that would detach ``.grad`` from the graph's buffers.
@@ -27,6 +30,7 @@ import warnings
 import torch
 
 from . import autograd as AG
+from . import ops
 from .transformer import DecoderContext, FeaturePyramid, _upload
 from .utils import VERSION
 
@@ -57,6 +61,8 @@ class CapturedTrainStep:
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device).random_() if self.dropout else None
         self._leaves = [p for p in dec.parameters() if p.requires_grad]
         self._leaves += [t for t in [query_feat, query_bbox] + self.mlvl_feats if t.requires_grad]
+        # captured-under setting: the graph holds the launches of ONE feature-gradient mode (atomics, or the sorted-tap sum)
+        self.det_feat_grad = ops.deterministic_feature_grad_active()
         self.stream = torch.cuda.Stream(device=self.device)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(self.stream):
@@ -102,6 +108,10 @@ class CapturedTrainStep:
         counts) refreshes the camera matrices / time stamps first; with dropout on, new masks are drawn unless ``new_masks=False``
         (``seed_dev`` may also be set by hand).  Returns the graph's own (loss, cls_scores, bbox_preds) tensors -- clone what has to
         survive the next replay."""
+        if ops.deterministic_feature_grad_active() != self.det_feat_grad:
+            raise RuntimeError('CapturedTrainStep.replay: the step was captured with the deterministic feature gradient %s and it is %s now '
+                               '(ops.deterministic_feature_grad / torch.use_deterministic_algorithms); capture a new step'
+                               % (('off', 'on')[self.det_feat_grad], ('on', 'off')[self.det_feat_grad]))
         if img_metas is not None:
             packed, layout, image_h, image_w = DecoderContext.pack(img_metas, self.B)
             if layout != self.ctx.layout or (image_h, image_w) != (self.ctx.image_h, self.ctx.image_w):
