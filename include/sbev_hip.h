@@ -350,6 +350,89 @@ int sbev_nms_free_decode(const float* cls_scores, const float* bbox_preds, int B
                          int bottom_center, float* boxes, float* scores, int32_t* labels, int32_t* count,
                          sbev_stream_t stream);
 
+/* ---- detection head, training side (csrc/head_train.hip): fp32, no float atomics, bit-equal from run to run -------- */
+
+/*
+ * Decoder inputs in training: denoising queries in front of the matching queries, and the attention mask.
+ * Replaces: SparseBEVHead.prepare_for_dn_input's training branch (models/sparsebev_head.py:124-207) with encode_bbox
+ *           (models/bbox/utils.py:46-60): ~40 torch ops and two Python loops become one launch.
+ * Ground truth of the batch concatenated sample-major: gt_boxes [G,9] (gravity centre, w, l, h, rot, vx, vy), gt_labels [G],
+ * gt_offsets [B+1] (device; prefix sums of the per-sample counts).  Noise, one row per known query j = r*G + i (group r, gt i):
+ * u_box [N*G,3] in [-1,1), u_lab [N*G] in [0,1), new_lab [N*G] in [0,num_classes).  single = the largest per-sample count,
+ * pad = single*N.  query_bbox [B,pad+Q,10], query_feat [B,pad+Q,D]: row (b, r*single + k) for the k-th gt of sample b holds
+ * the centre c + (u * (wlh / 2)) * box_noise_scale, encoded with pc_range and clamped to [0,1], log(wlh), sin, cos, velocity;
+ * feature [label_enc[lab'], 1] with lab' = new_lab if u_lab < label_noise_scale else the gt label (written to noised_label [N*G]).
+ * A scale of 0 switches that noise off.  Unused pad rows are zero; rows pad.. are sbev_head_prepare's.
+ * attn_mask [pad+Q, pad+Q] bytes, 1 = may not attend: a matching row sees no dn column, a dn row its own group's and all matching ones.
+ */
+int sbev_head_dn_prepare(const float* init_query_bbox, const float* label_enc, const float* gt_boxes, const int32_t* gt_labels,
+                         const int32_t* gt_offsets, const float* u_box, const float* u_lab, const int32_t* new_lab,
+                         const double* pc_range, float box_noise_scale, float label_noise_scale, int B, int Q, int D,
+                         int num_classes, int G, int N, int single, float* query_bbox, float* query_feat,
+                         int32_t* noised_label, uint8_t* attn_mask, sbev_stream_t stream);
+
+/*
+ * Backward of sbev_head_dn_prepare for its two parameters (ground truth and noise get no gradient).
+ * Replaces: autograd through the embedding lookup, cat, repeat and index_put of models/sparsebev_head.py:126-127,175-193.
+ * grad_init_query_bbox [Q,10] = sum over b of the matching rows of grad_query_bbox; grad_label_enc [num_classes+1, D-1]: row
+ * num_classes = sum over all matching rows of grad_query_feat[..., :D-1], row c = sum over the known queries with noised label c.
+ * One owner per output element, sums in a fixed order.
+ */
+int sbev_head_dn_prepare_bwd(const float* grad_query_bbox, const float* grad_query_feat, const int32_t* noised_label,
+                             const int32_t* gt_offsets, int B, int Q, int D, int num_classes, int G, int N, int single,
+                             float* grad_init_query_bbox, float* grad_label_enc, sbev_stream_t stream);
+
+/*
+ * Matching cost of every decoder layer and sample in one launch.
+ * Replaces: HungarianAssigner3D.assign steps 2-3 up to the nan_to_num (models/bbox/assigners/hungarian_assigner_3d.py:54-74)
+ *           with BBox3DL1Cost (models/bbox/match_costs/match_cost.py:6-27), normalize_bbox (models/bbox/utils.py:4-20) and
+ *           mmdet's FocalLossCost, called per layer and sample by _get_target_single (models/sparsebev_head.py:301-311).
+ * cls_scores / bbox_preds: [L,B,ld_rows,*] with the pointer at the first of the Q matching rows of each sample (ld_rows >= Q).
+ * cost [L,B,Q,Gmax] = w_cls * (pos(p) - neg(p)) + w_reg * sum_k |pred_k*cw_k - ngt_k*cw_k|, nan -> 100, +inf -> 100, -inf -> -100;
+ * columns g >= the sample's count are 0.
+ */
+int sbev_head_match_cost(const float* cls_scores, const float* bbox_preds, int64_t ld_rows, const float* gt_boxes,
+                         const int32_t* gt_labels, const int32_t* gt_offsets, const float* code_weights, float w_cls,
+                         float w_reg, float alpha, float gamma, int L, int B, int Q, int num_classes, int Gmax, float* cost,
+                         sbev_stream_t stream);
+
+/*
+ * Rectangular linear sum assignment on the host (no GPU call): shortest augmenting paths (Jonker-Volgenant).
+ * Replaces: scipy.optimize.linear_sum_assignment in HungarianAssigner3D.assign (hungarian_assigner_3d.py:80).
+ * cost: row-major [n_rows, ld >= n_cols].  col_of_row [n_rows]: the column of each row, -1 for unmatched; min(n_rows, n_cols)
+ * pairs at minimum total cost.  SBEV_EINVAL on a non-finite cost or ld < n_cols.
+ */
+int sbev_lsa_solve(const float* cost, int64_t ld, int n_rows, int n_cols, int32_t* col_of_row);
+
+/*
+ * The assignment table of a step from the host copy of sbev_head_match_cost's output (no GPU call).
+ * Replaces: the per-layer, per-sample solver calls and index bookkeeping of hungarian_assigner_3d.py:80-91 / sparsebev_head.py:329-347.
+ * cost [L,B,Q,Gmax], gt_counts [B] (host).  assign [L,B,Q]: -1 = background, g = index of the matched gt of that sample.
+ */
+int sbev_head_assign(const float* cost, const int32_t* gt_counts, int L, int B, int Q, int Gmax, int32_t* assign);
+
+/* Bytes of workspace PER LAYER for sbev_head_set_loss (-1 on bad sizes). */
+int64_t sbev_head_set_loss_workspace(int B, int rows);
+
+/*
+ * Sigmoid focal loss + L1 loss of all decoder layers and their gradients for unit upstream gradient: two launches.
+ * Replaces: loss_single / dn_loss_single with the target construction of _get_target_single and prepare_for_dn_loss's gather
+ *           (models/sparsebev_head.py:224-275,301-402) and mmdet's FocalLoss (sigmoid) and L1Loss.
+ * cls_scores / bbox_preds: [L,B,ld_rows,*] with the pointer at the first of the `rows` rows of each sample.  codes: int32
+ * [B,rows] per layer (layer l at codes + l*code_layer_stride; 0 = one table for all layers): -2 skip the row, -1 background,
+ * g >= 0 target gt g of sample b (class gt_labels, box normalize_bbox(gt_boxes)).  A code at or above the sample's gt count, or below
+ * -2, is a caller's error: it is treated as -2 (the row is skipped, its gradients are zero) so that nothing is read out of bounds.
+ * loss [L,2]: scale * nan_to_num(w_focal * sum focal / max(A_cls,1)), scale * nan_to_num(w_l1 * sum_{g >= 0, target finite}
+ * sum_k |pred_k - ngt_k| * cw_k / max(A_box,1)) with A_cls, A_box = avg_factors[0..1] read on the device; loss_finite [L,2] = 1
+ * where the value was finite before nan_to_num.  grad_cls [L,B,rows,NC], grad_bbox [L,B,rows,10]: d loss / d input, every
+ * element written by one thread.  workspace: L * sbev_head_set_loss_workspace(B, rows) bytes.
+ */
+int sbev_head_set_loss(const float* cls_scores, const float* bbox_preds, int64_t ld_rows, const int32_t* codes,
+                       int64_t code_layer_stride, const float* gt_boxes, const int32_t* gt_labels, const int32_t* gt_offsets,
+                       const float* code_weights, const float* avg_factors, float w_focal, float alpha, float gamma,
+                       float w_l1, float scale, int L, int B, int rows, int num_classes, float* loss, float* loss_finite,
+                       float* grad_cls, float* grad_bbox, float* workspace, sbev_stream_t stream);
+
 
 /*
  * Batched NCHW -> NHWC relayout of one pyramid level: in [n_images, channels, hw] -> out [n_images, hw, channels].

@@ -8,4 +8,15 @@ operator modules without the built library raises -- there is no CPU / PyTorch f
 """
 from ._lib import load as load_library, SbevError, LIB_PATH   # noqa: F401
 
-__all__ = ['load_library', 'SbevError', 'LIB_PATH']
+__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead']
+
+
+def __getattr__(name):
+    # the heads pull in the whole operator stack: imported on first use
+    if name == 'SparseBEVHead':
+        from .head import SparseBEVHead
+        return SparseBEVHead
+    if name == 'SparseBEVTrainHead':
+        from .head_train import SparseBEVTrainHead
+        return SparseBEVTrainHead
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -161,6 +161,15 @@ SIGNATURES = {
     'sbev_head_denorm': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double), _vp, ctypes.c_int64, _vp]),
     'sbev_nms_free_decode': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                             ctypes.POINTER(ctypes.c_double), ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    'sbev_head_dn_prepare': (ctypes.c_int, [_vp] * 8 + [ctypes.POINTER(ctypes.c_double), ctypes.c_float, ctypes.c_float] + [ctypes.c_int] * 7
+                             + [_vp] * 5),
+    'sbev_head_dn_prepare_bwd': (ctypes.c_int, [_vp] * 4 + [ctypes.c_int] * 7 + [_vp] * 3),
+    'sbev_head_match_cost': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp] + [ctypes.c_float] * 4 + [ctypes.c_int] * 5 + [_vp, _vp]),
+    'sbev_lsa_solve': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
+    'sbev_head_assign': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp]),
+    'sbev_head_set_loss_workspace': (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
+    'sbev_head_set_loss': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp] + [ctypes.c_float] * 5
+                           + [ctypes.c_int] * 4 + [_vp] * 6),
     'sbev_profile_read': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int]),
     'sbev_linear_splitk_plan': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'sbev_linear_group_f32': (ctypes.c_int, [_vp, ctypes.c_int, _vp]),

@@ -12,7 +12,7 @@ Interface parity with the reference:
     ``label_enc.weight``, ``code_weights``, ``transformer.*``), same ``forward(mlvl_feats, img_metas) -> outs`` dict
     (``models/sparsebev_head.py:69-117``) and ``get_bboxes(preds_dicts, img_metas)`` (``:463-482``; boxes are returned
     as a plain ``[n, 9]`` tensor -- mmdet3d's ``LiDARInstance3DBoxes`` wrapper is the caller's).
-Training-only parts (query denoising, Hungarian assignment, losses: ``:128-204,215-461``) are out of scope and raise.
+Training-only parts (query denoising, Hungarian assignment, losses: ``:128-204,215-461``) raise here; ``head_train.SparseBEVTrainHead`` has them.
 """
 import ctypes
 import math
