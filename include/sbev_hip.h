@@ -411,6 +411,29 @@ int sbev_lsa_solve(const float* cost, int64_t ld, int n_rows, int n_cols, int32_
  */
 int sbev_head_assign(const float* cost, const int32_t* gt_counts, int L, int B, int Q, int Gmax, int32_t* assign);
 
+/*
+ * The same table solved on the device: one launch, one workgroup per problem (l, b), no device -> host copy and no synchronisation,
+ * so the launch can sit inside a captured graph.
+ * Replaces: sbev_head_assign together with the copy of the costs to the host, the stream synchronisation in front of it and the
+ *           upload of the table behind it (scipy.optimize.linear_sum_assignment on .cpu() costs in hungarian_assigner_3d.py:74-91).
+ * It is sbev_lsa_solve's algorithm restated in parallel with the same fp64 arithmetic in the same order and the same tie rule (among
+ * equally short columns the last free one in scan order, otherwise the first), so the table is sbev_head_assign's bit for bit.
+ * cost [L,B,Q,Gmax] (device, as sbev_head_match_cost writes it), gt_offsets [B+1] (device): the counts are read there, and one that
+ * is negative or above Gmax is clamped into 0..Gmax and flagged.  Only the Q x count block of a problem is read.
+ * assign [L,B,Q] int32: -1 background, g = matched gt of that sample.
+ * status [L*B] int32 (may be null): 0 solved; 1 non-finite cost in the block, a count out of range, or no feasible assignment:
+ * that problem's row is all -1 and the other problems are untouched.
+ * workspace: sbev_head_assign_device_workspace(L, B, Q, Gmax) bytes (-1 on bad sizes), 16-byte aligned; may be null where that is 0.
+ * sbev_head_assign_device_plan(Q, Gmax): what the launch will do -- 0: the per-problem solver state (29 bytes per column, 13 per row)
+ * stays in LDS, 1: it lives in the workspace, -1: bad sizes.  Both are pure host functions.
+ * Checked before any GPU call: sizes >= 0, Q <= 32767, Q * Gmax < 2^31, null pointers at non-zero sizes; L*B*Q == 0 is SBEV_OK
+ * without a launch.
+ */
+int64_t sbev_head_assign_device_workspace(int L, int B, int Q, int Gmax);
+int sbev_head_assign_device_plan(int Q, int Gmax);
+int sbev_head_assign_device(const float* cost, const int32_t* gt_offsets, int L, int B, int Q, int Gmax,
+                            int32_t* assign, int32_t* status, void* workspace, sbev_stream_t stream);
+
 /* Bytes of workspace PER LAYER for sbev_head_set_loss (-1 on bad sizes). */
 int64_t sbev_head_set_loss_workspace(int B, int rows);
 

@@ -38,6 +38,8 @@ UNITS = {
     'head.hip': ['-ffp-contract=off'],   # __fmul_rn / __fadd_rn are plain * and + in HIP: keep them unfused
     # the noised centre and the box normalisation round like the reference's separate torch ops; fixed-order sums
     'head_train.hip': ['-ffp-contract=off'],
+    # the host solver of head_train.hip restated on the device: the same fp64 additions in the same order, nothing contracted
+    'head_assign.hip': ['-ffp-contract=off'],
     'decoder.hip': [],
     'row_chain.hip': [],                 # the row-local op chains of a layer (4x4x1 MFMA with A broadcast)
     # bit-exact projection: no FMA contraction anywhere in this file

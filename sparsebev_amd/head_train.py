@@ -13,7 +13,9 @@ In ``train()``:
   * ``loss(gt_bboxes_list, gt_labels_list, preds_dicts)`` (``:405-460``): one cost launch for all layers and samples, ONE
     device -> host copy into pinned memory and ONE synchronisation, the linear sum assignment on the host (the library's own
     solver, as the reference solves it on the host with scipy), then two launches per loss pair (matching, denoising) that
-    produce the ``2 * L`` scalars and their gradients together.
+    produce the ``2 * L`` scalars and their gradients together.  With ``assign_on='device'`` the assignment is one more launch
+    (csrc/head_assign.hip: the host solver restated in parallel, the same table bit for bit) and ``loss()`` makes no device ->
+    host copy and no synchronisation.
 
 mmdet's sigmoid ``FocalLoss``, ``L1Loss`` and ``FocalLossCost`` are restated in the kernels (mmdet is not vendored by the
 reference: parity is unpinned at that third-party boundary, as the mmcv attention is).
@@ -266,6 +268,31 @@ class _Assigner:
         return out
 
 
+def assign_device(cost, gt, status=None):
+    """int32 [L,B,Q] on the device: the table ``sbev_head_assign`` returns for the same costs (-1 background, g matched gt of the sample),
+    solved by one launch with one workgroup per (layer, sample) that reads the counts from ``gt.offsets`` on the device.  No host copy,
+    no synchronisation.  ``status``: an int32 [L*B] device tensor to receive 0 (solved) / 1 (non-finite cost or infeasible: the row is
+    all -1), or None."""
+    _dev(cost)
+    _i32(gt.offsets)
+    if cost.dim() != 4 or cost.shape[1] != gt.B:
+        raise RuntimeError('assign_device: cost %s is not [L, B=%d, Q, Gmax]' % (tuple(cost.shape), gt.B))
+    L, B, Q, Gmax = cost.shape
+    if status is not None:
+        _i32(status)
+        if status.numel() != L * B or not status.is_contiguous():
+            raise RuntimeError('assign_device: status must be a contiguous int32 tensor of L * B = %d elements' % (L * B))
+    lib, cost = _lib.load(), cost.contiguous()
+    nbytes = lib.sbev_head_assign_device_workspace(L, B, Q, Gmax)
+    if nbytes < 0:
+        raise RuntimeError('assign_device: sizes L=%d B=%d Q=%d Gmax=%d are out of range' % (L, B, Q, Gmax))
+    ws = torch.empty(max(1, nbytes), device=cost.device, dtype=torch.uint8)
+    out = torch.empty(L, B, Q, device=cost.device, dtype=torch.int32)
+    st = lib.sbev_head_assign_device(_p(cost), _p(gt.offsets), L, B, Q, Gmax, _p(out), _p(status), _p(ws), _stream())
+    _lib.check(st, 'sbev_head_assign_device')
+    return out
+
+
 class _SetLoss(torch.autograd.Function):
     """sbev_head_set_loss: the [L,2] losses and, from the same launch, their gradients for unit upstream gradient."""
 
@@ -327,7 +354,9 @@ class SparseBEVTrainHead(SparseBEVHead):
     ``sbev_head_denorm`` behind an autograd Function whose backward is a column permutation and scale in torch ops."""
 
     def __init__(self, *args, loss_cls=None, loss_bbox=None, loss_iou=None, sync_cls_avg_factor=True, bg_cls_weight=0.0,
-                 train_cfg=None, **kwargs):
+                 train_cfg=None, assign_on='host', **kwargs):
+        if assign_on not in ('host', 'device'):
+            raise ValueError("sparsebev_amd.SparseBEVTrainHead: assign_on is 'host' or 'device', not %r" % (assign_on,))
         _, fl = _typed(loss_cls, 'FocalLoss', ('FocalLoss',), 'loss_cls')
         if not fl.get('use_sigmoid', True):
             raise ValueError('sparsebev_amd.SparseBEVTrainHead: loss_cls must be the sigmoid FocalLoss')
@@ -352,6 +381,9 @@ class SparseBEVTrainHead(SparseBEVHead):
         self.sync_cls_avg_factor, self.bg_cls_weight = bool(sync_cls_avg_factor), float(bg_cls_weight)
         self.dn_weight, self.dn_bbox_noise_scale, self.dn_label_noise_scale = 1.0, 0.5, 0.5        # :45-47
         self._assigner = _Assigner()
+        # where the linear sum assignment is solved: 'host' (one copy + one synchronisation per step) or 'device' (one launch, neither)
+        self.assign_on = assign_on
+        self.assign_status = None            # 'device': the last launch's int32 [L*B] status; nobody reads it on the hot path
 
     # ---- section 1: denoising queries ------------------------------------------------------------------------------
     def draw_noise(self, G, device):
@@ -410,6 +442,9 @@ class SparseBEVTrainHead(SparseBEVHead):
             return torch.full((L, B, Q), -1, dtype=torch.int32, device=all_cls_scores.device)
         cost = match_cost(all_cls_scores, all_bbox_preds, gt, self.code_weights, self.cls_cost_weight, self.reg_cost_weight,
                           self.cost_alpha, self.cost_gamma)
+        if self.assign_on == 'device':
+            self.assign_status = torch.empty(L * B, dtype=torch.int32, device=cost.device)
+            return assign_device(cost, gt, self.assign_status)
         return self._assigner(cost, gt)
 
     def _avg(self, a_cls, a_box, device, sync_cls, sync_box):

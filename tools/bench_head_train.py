@@ -5,9 +5,13 @@ per layer and sample ~40 cost ops -> .cpu() -> solver, target construction in Py
 events, medians of --steps: `loss()` alone on fixed head outputs, and the whole step (forward + loss + backward; the forward and
 the decoder backward are the same HIP path on both sides).  Nobody has measured either side before: the record is the point, no
 ratio is required.  Writes one JSON line (default profiles/head_train.json) that also carries the compiler's per-kernel resource
-figures of csrc/head_train.hip (VGPRs, SGPRs, scratch, LDS).
+figures of csrc/head_train.hip and csrc/head_assign.hip (VGPRs, SGPRs, scratch, LDS).
 
-    python tools/bench_head_train.py [--steps 50] [--out profiles/head_train.json]
+--assign-on device times the head with the assignment solved on the device (csrc/head_assign.hip) instead of on the host; both adds
+`loss_hip_device` / `step_hip_device` legs to the same timed loop, alternating with the host legs, after asserting that the two heads
+return identical loss dicts.
+
+    python tools/bench_head_train.py [--steps 50] [--assign-on host|device|both] [--out profiles/head_train.json]
     python tools/bench_head_train.py --resources-only          (no GPU needed)
 """
 import argparse
@@ -29,18 +33,19 @@ import torch.nn.functional as F               # noqa: E402
 def kernel_resources():
     """{kernel: {vgprs, sgprs, scratch_bytes_per_lane, lds_bytes_per_block}} from hipcc's kernel-resource-usage remarks."""
     from sparsebev_amd.csrc import build
-    src = os.path.join(build.HERE, 'head_train.hip')
+    text = ''
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = [build._hipcc()] + build.COMMON + build.UNITS['head_train.hip'] + ['-Rpass-analysis=kernel-resource-usage', '-c', src,
-                                                                                  '-o', os.path.join(tmp, 'head_train.o')]
-        text = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, check=True).stdout.decode()
+        for unit in ('head_train.hip', 'head_assign.hip'):
+            cmd = [build._hipcc()] + build.COMMON + build.UNITS[unit] + ['-Rpass-analysis=kernel-resource-usage', '-c',
+                                                                         os.path.join(build.HERE, unit), '-o', os.path.join(tmp, 'unit.o')]
+            text += subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, check=True).stdout.decode()
     out, cur = {}, None
     keys = {'VGPRs': 'vgprs', 'TotalSGPRs': 'sgprs', 'ScratchSize [bytes/lane]': 'scratch_bytes_per_lane', 'LDS Size [bytes/block]': 'lds_bytes_per_block'}
     for line in text.splitlines():
         m = re.search(r'Function Name: (\S+)', line)
         if m:
             name = subprocess.run(['c++filt', m.group(1)], stdout=subprocess.PIPE).stdout.decode().strip() or m.group(1)
-            cur = out.setdefault((re.findall(r'(\w+)\(', name) or [name])[0], {})
+            cur = out.setdefault((re.findall(r'(\w+(?:<[^()]*>)?)\(', name) or [name])[0], {})      # `kernel` or `kernel<template arguments>`
             continue
         for k, v in keys.items():
             m = re.search(r'remark:\s+' + re.escape(k) + r': (\d+)', line)
@@ -144,6 +149,7 @@ def main():
     ap.add_argument('--groups', type=int, default=10)
     ap.add_argument('--pyr', default='r50_704x256')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'head_train.json'))
+    ap.add_argument('--assign-on', choices=('host', 'device', 'both'), default='host')
     ap.add_argument('--resources-only', action='store_true')
     a = ap.parse_args()
     res = kernel_resources()
@@ -170,7 +176,7 @@ def main():
                               transformer=dict(type='SparseBEVTransformer', embed_dims=256, num_frames=a.t, num_points=4, num_layers=6,
                                                num_levels=len(sizes), num_classes=10, code_size=10, pc_range=S.PC_RANGE),
                               bbox_coder=dict(type='NMSFreeCoder', post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0], max_num=300,
-                                              num_classes=10, pc_range=S.PC_RANGE))
+                                              num_classes=10, pc_range=S.PC_RANGE), assign_on='device' if a.assign_on == 'device' else 'host')
     head.init_weights()
     S.randomize_zero_init(head.transformer, std=0.02, seed=0)
     with torch.no_grad():
@@ -200,7 +206,7 @@ def main():
         e1.synchronize()
         return e0.elapsed_time(e1)
 
-    def step(loss_fn):
+    def step(loss_fn, head=head):
         for p in head.parameters():
             p.grad = None
         outs = head(feats, copy.deepcopy(metas))
@@ -217,9 +223,19 @@ def main():
     worst = max(abs(la[k].item() - lb[k].item()) / max(1.0, abs(lb[k].item())) for k in lb)
     assert sorted(la) == sorted(lb) and worst < 1e-4, (worst, la, lb)
     times = {'loss_hip': [], 'loss_torch': [], 'step_hip': [], 'step_torch': []}
+    if a.assign_on == 'both':       # a second head on the same parameters (the modules are shared, nothing is copied) that solves on the device
+        twin = copy.copy(head)
+        twin.assign_on = 'device'
+        ours_device = lambda outs: twin.loss(gt_boxes, gt_labels, outs)
+        ld = ours_device(fixed)
+        assert sorted(ld) == sorted(la) and all(torch.equal(ld[k], la[k]) for k in la), (ld, la)
+        assert bool((twin.assign_status == 0).all())
+        times.update(loss_hip_device=[], step_hip_device=[])
     for i in range(a.warmup + a.steps):
         row = {'loss_hip': timed(lambda: ours(fixed)), 'loss_torch': timed(lambda: theirs(fixed)),
                'step_hip': timed(lambda: step(ours)), 'step_torch': timed(lambda: step(theirs))}
+        if a.assign_on == 'both':
+            row.update(loss_hip_device=timed(lambda: ours_device(fixed)), step_hip_device=timed(lambda: step(ours_device, twin)))
         if i >= a.warmup:
             for k, v in row.items():
                 times[k].append(v)
@@ -228,6 +244,8 @@ def main():
            'median_ms': {k: round(statistics.median(v), 4) for k, v in times.items()},
            'min_ms': {k: round(min(v), 4) for k, v in times.items()},
            'kernel_resources': res}
+    if a.assign_on != 'host':
+        rec['assign_on'] = a.assign_on
     assert all(r.get('scratch_bytes_per_lane') == 0 for r in res.values()), res
     line = json.dumps(rec)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
