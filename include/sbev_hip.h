@@ -359,7 +359,8 @@ int sbev_nms_free_decode(const float* cls_scores, const float* bbox_preds, int B
  * Ground truth of the batch concatenated sample-major: gt_boxes [G,9] (gravity centre, w, l, h, rot, vx, vy), gt_labels [G],
  * gt_offsets [B+1] (device; prefix sums of the per-sample counts).  Noise, one row per known query j = r*G + i (group r, gt i):
  * u_box [N*G,3] in [-1,1), u_lab [N*G] in [0,1), new_lab [N*G] in [0,num_classes).  single = the largest per-sample count,
- * pad = single*N.  query_bbox [B,pad+Q,10], query_feat [B,pad+Q,D]: row (b, r*single + k) for the k-th gt of sample b holds
+ * pad = single*N.  At a fixed capacity (sbev_head_capacity_plan): single = the capacity per sample and G = B*capacity >= gt_offsets[B];
+ * the rows of gt_boxes / gt_labels / the noise behind gt_offsets[B] are not read and their noised_label words are not written.  query_bbox [B,pad+Q,10], query_feat [B,pad+Q,D]: row (b, r*single + k) for the k-th gt of sample b holds
  * the centre c + (u * (wlh / 2)) * box_noise_scale, encoded with pc_range and clamped to [0,1], log(wlh), sin, cos, velocity;
  * feature [label_enc[lab'], 1] with lab' = new_lab if u_lab < label_noise_scale else the gt label (written to noised_label [N*G]).
  * A scale of 0 switches that noise off.  Unused pad rows are zero; rows pad.. are sbev_head_prepare's.
@@ -376,7 +377,8 @@ int sbev_head_dn_prepare(const float* init_query_bbox, const float* label_enc, c
  * Replaces: autograd through the embedding lookup, cat, repeat and index_put of models/sparsebev_head.py:126-127,175-193.
  * grad_init_query_bbox [Q,10] = sum over b of the matching rows of grad_query_bbox; grad_label_enc [num_classes+1, D-1]: row
  * num_classes = sum over all matching rows of grad_query_feat[..., :D-1], row c = sum over the known queries with noised label c.
- * One owner per output element, sums in a fixed order.
+ * One owner per output element, sums in a fixed order over the N * gt_offsets[B] known queries (not over N * G: the order does not
+ * depend on a capacity behind gt_offsets[B]).
  */
 int sbev_head_dn_prepare_bwd(const float* grad_query_bbox, const float* grad_query_feat, const int32_t* noised_label,
                              const int32_t* gt_offsets, int B, int Q, int D, int num_classes, int G, int N, int single,
@@ -433,6 +435,22 @@ int64_t sbev_head_assign_device_workspace(int L, int B, int Q, int Gmax);
 int sbev_head_assign_device_plan(int Q, int Gmax);
 int sbev_head_assign_device(const float* cost, const int32_t* gt_offsets, int L, int B, int Q, int Gmax,
                             int32_t* assign, int32_t* status, void* workspace, sbev_stream_t stream);
+
+/*
+ * The training step's plan at a fixed ground-truth capacity, from the per-sample counts in gt_offsets on the device: one launch, no
+ * host value follows the counts, so the launch can sit inside a captured graph whose ground truth changes between replays.
+ * Replaces: prepare_for_dn_loss's gather indices (models/sparsebev_head.py:224-237) and the host arithmetic of num_total_pos /
+ *           cls_avg_factor / num_tgt (:247,371-384,:239-275) that SparseBEVTrainHead.loss() does with numpy at a dynamic shape.
+ * gt_offsets [B+1] (device).  count[b] = offsets[b+1] - offsets[b], clamped into 0..capacity for everything written here.
+ * codes [B, N*capacity] int32: k at (b, r*capacity + k) for k < count[b], -2 elsewhere -- sbev_head_set_loss's codes of the denoising rows.
+ * avg_factors [2,2] fp32: row 0 = (num_pos + num_neg * bg_cls_weight, num_pos) with num_pos = sum_b min(count[b], Q) and
+ * num_neg = B*Q - num_pos; row 1 = (N * sum_b count[b]) twice.  Integer sums, the factors formed in double and rounded once.
+ * status [1] int32: 0, or the sum of 1 (a count above capacity), 2 (offsets[0] != 0 or a negative count), 4 (offsets[B] > B*capacity).
+ * One owner per output, plain stores, no atomics.  Checked before any GPU call: B, Q, capacity >= 0, N >= 1, B*N*capacity < 2^31,
+ * null pointers (codes may be null where B*N*capacity == 0).
+ */
+int sbev_head_capacity_plan(const int32_t* gt_offsets, int B, int Q, int capacity, int N, double bg_cls_weight, int32_t* codes,
+                            float* avg_factors, int32_t* status, sbev_stream_t stream);
 
 /* Bytes of workspace PER LAYER for sbev_head_set_loss (-1 on bad sizes). */
 int64_t sbev_head_set_loss_workspace(int B, int rows);

@@ -170,6 +170,7 @@ SIGNATURES = {
     'sbev_head_assign_device_workspace': (ctypes.c_int64, [ctypes.c_int] * 4),
     'sbev_head_assign_device_plan': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     'sbev_head_assign_device': (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    'sbev_head_capacity_plan': (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [ctypes.c_double] + [_vp] * 4),
     'sbev_head_set_loss_workspace': (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
     'sbev_head_set_loss': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp] + [ctypes.c_float] * 5
                            + [ctypes.c_int] * 4 + [_vp] * 6),

@@ -9,6 +9,9 @@
 //   set_loss_kernel + set_loss_finish_kernel
 //                           sigmoid focal loss + L1 loss of all layers AND their gradients for unit upstream gradient
 //                           (models/sparsebev_head.py:239-275,349-402; mmdet FocalLoss / L1Loss restated)
+//   capacity_plan_kernel    at a fixed ground-truth capacity: the dn codes, the four averaging factors and a status word from the
+//                           device's gt_offsets, so that no host value follows the per-sample counts (models/sparsebev_head.py:
+//                           224-237,247,371-384)
 //   lsa_solve               rectangular linear sum assignment on the host (shortest augmenting paths, Jonker-Volgenant); no GPU call
 //
 // fp32 throughout, plain vector stores, NO float atomics: every sum has one owner and a fixed order (a serial loop, or a
@@ -143,10 +146,15 @@ __global__ __launch_bounds__(1024) void dn_prepare_bwd_kernel(const DnBwdArgs a)
                     s += a.g_qfeat[((long long)b * T + pad + q) * a.D + d];
                 }
             } else {                                            // the known queries whose noised label is this class
-                const int n = a.N * a.G;
-                for (int j = slice; j < n; j += 4) {
-                    if (a.noised_label[j] != cls) continue;
-                    const int r = j / a.G, gi = j % a.G;
+                // The known queries are the (group r, gt gi) with gi < gt_offsets[B]; rows behind that of a fixed-capacity ground truth
+                // are capacity, and the forward wrote no label for them.  The slices split the USED pairs, so the order of the sum
+                // does not depend on the capacity (with G == gt_offsets[B], jc is j).
+                int used = a.B > 0 ? a.gt_offsets[a.B] : 0;
+                used = used < 0 ? 0 : (used > a.G ? a.G : used);
+                const int n = a.N * used;
+                for (int jc = slice; jc < n; jc += 4) {
+                    const int r = jc / used, gi = jc % used;
+                    if (a.noised_label[r * a.G + gi] != cls) continue;
                     int b = 0;
                     while (b + 1 < a.B && a.gt_offsets[b + 1] <= gi) ++b;
                     const int k = gi - a.gt_offsets[b];
@@ -348,6 +356,52 @@ __global__ void set_loss_finish_kernel(const FinishArgs a) {
     a.finite[i] = fin ? 1.f : 0.f;
 }
 
+// ---- the step's plan at a fixed ground-truth capacity -------------------------------------------------------------------
+
+struct PlanArgs {
+    const int* gt_offsets;     // [B + 1]
+    int* codes;                // [B, N * capacity]: k for k < count[b], else -2, tiled over the N groups
+    float* avg;                // [2, 2]: (A_cls, A_box) of the matching loss, (A, A) of the denoising loss
+    int* status;               // [1]: 0, or kPlan* bits
+    int B, Q, capacity, N;
+    double bg_cls_weight;
+};
+
+constexpr int kPlanCountAboveCapacity = 1, kPlanOffsetsNotMonotone = 2, kPlanTotalAboveCapacity = 4;
+constexpr int kPlanThreads = 256;
+
+__device__ __forceinline__ int plan_count(const int* offsets, int b, int capacity) {
+    const int n = offsets[b + 1] - offsets[b];
+    return n < 0 ? 0 : (n > capacity ? capacity : n);          // clamped: nothing this kernel writes follows a count out of range
+}
+
+// one thread per code; thread 0 of the launch also owns the four factors and the status: a serial loop over the samples, integer
+// sums, the factors formed in double and rounded once to fp32 (what numpy does with the host's python floats)
+__global__ __launch_bounds__(kPlanThreads) void capacity_plan_kernel(const PlanArgs a) {
+    const long long i = (long long)blockIdx.x * kPlanThreads + threadIdx.x;
+    const long long row = (long long)a.N * a.capacity;
+    if (i < a.B * row) {
+        const int b = (int)(i / row), k = (int)((i % row) % a.capacity);
+        a.codes[i] = k < plan_count(a.gt_offsets, b, a.capacity) ? k : -2;
+    }
+    if (i != 0) return;
+    long long num_pos = 0, total = 0;
+    int st = a.gt_offsets[0] != 0 ? kPlanOffsetsNotMonotone : 0;
+    for (int b = 0; b < a.B; ++b) {
+        const int raw = a.gt_offsets[b + 1] - a.gt_offsets[b], n = plan_count(a.gt_offsets, b, a.capacity);
+        if (raw > a.capacity) st |= kPlanCountAboveCapacity;
+        if (raw < 0) st |= kPlanOffsetsNotMonotone;
+        num_pos += n < a.Q ? n : a.Q;
+        total += n;
+    }
+    if ((long long)a.gt_offsets[a.B] > (long long)a.B * a.capacity) st |= kPlanTotalAboveCapacity;
+    const long long num_neg = (long long)a.B * a.Q - num_pos;
+    a.avg[0] = (float)((double)num_pos * 1.0 + (double)num_neg * a.bg_cls_weight);
+    a.avg[1] = (float)(double)num_pos;
+    a.avg[2] = a.avg[3] = (float)(double)((long long)a.N * total);
+    a.status[0] = st;
+}
+
 // ---- the host solver --------------------------------------------------------------------------------------------------
 
 // Assign every one of `nr` <= `nc` rows to its own column at minimum total cost: shortest augmenting paths with dual variables
@@ -494,6 +548,20 @@ extern "C" int sbev_head_match_cost(const float* cls_scores, const float* bbox_p
                w_cls, w_reg, alpha, gamma};
     hipLaunchKernelGGL(match_cost_kernel, dim3(blocks_of(total, 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return sbev::check_launch("sbev_head_match_cost");
+}
+
+extern "C" int sbev_head_capacity_plan(const int32_t* gt_offsets, int B, int Q, int capacity, int N, double bg_cls_weight, int32_t* codes,
+                                       float* avg_factors, int32_t* status, sbev_stream_t stream) {
+    SBEV_REQUIRE(B >= 0 && Q >= 0 && capacity >= 0 && N >= 1, "sbev_head_capacity_plan: bad sizes B=%d Q=%d capacity=%d N=%d", B, Q, capacity, N);
+    const long long total = (long long)B * N * capacity;
+    SBEV_REQUIRE(total <= 0x7fffffffLL && (long long)B * capacity <= 0x7fffffffLL && (long long)B * Q <= 0x7fffffffLL,
+                 "sbev_head_capacity_plan: B=%d Q=%d capacity=%d N=%d is too large", B, Q, capacity, N);
+    SBEV_REQUIRE(gt_offsets && avg_factors && status, "sbev_head_capacity_plan: null pointer");
+    SBEV_REQUIRE(total == 0 || codes, "sbev_head_capacity_plan: null codes");
+    PlanArgs a{gt_offsets, codes, avg_factors, status, B, Q, capacity, N, bg_cls_weight};
+    const unsigned grid = total > 0 ? blocks_of(total, kPlanThreads) : 1u;       // the factors and the status are written at any size
+    hipLaunchKernelGGL(capacity_plan_kernel, dim3(grid), dim3(kPlanThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return sbev::check_launch("sbev_head_capacity_plan");
 }
 
 extern "C" int sbev_lsa_solve(const float* cost, int64_t ld, int n_rows, int n_cols, int32_t* col_of_row) {

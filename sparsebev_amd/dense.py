@@ -45,7 +45,11 @@ def _rows(x, width=None):
 
 
 def _ws(nbytes, device):
-    """Reusable split-K workspace (one per device; grown on demand, stream-ordered reuse)."""
+    """Reusable split-K workspace (one per device; grown on demand, stream-ordered reuse).  Under a torch graph capture the workspace
+    is the capture's own, from its memory pool: a captured launch keeps its pointer, while the shared buffer is replaced -- freed -- as
+    soon as a larger call comes along (a second captured step at a larger shape), and the next capture's empty_cache() unmaps it."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)
     key = str(device)
     buf = _WORKSPACES.get(key)
     if buf is None or buf.numel() * 4 < nbytes:

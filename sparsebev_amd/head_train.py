@@ -17,6 +17,12 @@ In ``train()``:
     (csrc/head_assign.hip: the host solver restated in parallel, the same table bit for bit) and ``loss()`` makes no device ->
     host copy and no synchronisation.
 
+``SparseBEVTrainHead(gt_capacity=C, assign_on='device')`` runs the same launches at shapes that do not follow the batch: the ground
+truth lives in a ``GroundTruthSlab`` (``C`` boxes per sample at a fixed address, refreshed in place), ``pad_size`` is ``C * N`` always,
+and one more launch (``capacity_plan``) derives the dn codes and the averaging factors from the counts on the device -- what
+``train_graph.CapturedHeadTrainStep`` needs to replay the whole step as one graph.  It is the dynamic path with ``single`` forced to
+``C``: unused pad rows are zero rows inside their group's attention, and a batch without ground truth keeps its ``*_dn`` keys, at 0.
+
 mmdet's sigmoid ``FocalLoss``, ``L1Loss`` and ``FocalLossCost`` are restated in the kernels (mmdet is not vendored by the
 reference: parity is unpinned at that third-party boundary, as the mmcv attention is).
 """
@@ -80,24 +86,35 @@ def _i32(t):
         raise RuntimeError('sparsebev_amd.head_train needs int32 index tensors (got %s)' % t.dtype)
 
 
+def _gt_tensors(boxes_list, labels_list):
+    """(boxes as [n,9] tensors, labels as [n] tensors, counts) of what a head is handed as ground truth"""
+    boxes = []
+    for bx in boxes_list:
+        if hasattr(bx, 'gravity_center') and hasattr(bx, 'tensor'):          # duck-typed LiDARInstance3DBoxes (:131-132,421-423)
+            bx = torch.cat([bx.gravity_center, bx.tensor[:, 3:]], dim=1)
+        bx = torch.as_tensor(bx)
+        if bx.dim() != 2 or bx.shape[1] != 9:
+            raise ValueError('ground-truth boxes must be [n, 9] (gravity centre, w, l, h, rot, vx, vy), got %s' % (tuple(bx.shape),))
+        boxes.append(bx.detach())
+    labels = [torch.as_tensor(lb).detach().reshape(-1) for lb in labels_list]
+    counts = [int(b.shape[0]) for b in boxes]
+    if counts != [int(lb.shape[0]) for lb in labels]:
+        raise ValueError('ground-truth boxes and labels disagree in length')
+    return boxes, labels, counts
+
+
+def _same_objects(src, boxes_list, labels_list):
+    return src is not None and len(src[0]) == len(boxes_list) and len(src[1]) == len(labels_list) \
+        and all(a is b for a, b in zip(src[0], boxes_list)) and all(a is b for a, b in zip(src[1], labels_list))
+
+
 class GroundTruth:
     """The batch's ground truth concatenated sample-major on the device: boxes [G,9] fp32, labels [G] int32, offsets [B+1] int32
     and the per-sample counts on the host.  Host-resident ground truth (the data loader's normal case) is concatenated on the host and
     goes over with the offsets in ONE asynchronous pinned upload; device-resident ground truth is concatenated where it is."""
 
     def __init__(self, boxes_list, labels_list, device):
-        boxes = []
-        for bx in boxes_list:
-            if hasattr(bx, 'gravity_center') and hasattr(bx, 'tensor'):          # duck-typed LiDARInstance3DBoxes (:131-132,421-423)
-                bx = torch.cat([bx.gravity_center, bx.tensor[:, 3:]], dim=1)
-            bx = torch.as_tensor(bx)
-            if bx.dim() != 2 or bx.shape[1] != 9:
-                raise ValueError('ground-truth boxes must be [n, 9] (gravity centre, w, l, h, rot, vx, vy), got %s' % (tuple(bx.shape),))
-            boxes.append(bx.detach())
-        labels = [torch.as_tensor(lb).detach().reshape(-1) for lb in labels_list]
-        self.counts = [int(b.shape[0]) for b in boxes]
-        if self.counts != [int(lb.shape[0]) for lb in labels]:
-            raise ValueError('ground-truth boxes and labels disagree in length')
+        boxes, labels, self.counts = _gt_tensors(boxes_list, labels_list)
         self.B, self.G, self.single = len(boxes), sum(self.counts), max(self.counts) if boxes else 0
         self.offsets_host = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int32)
         if all(not t.is_cuda for t in boxes + labels):
@@ -111,9 +128,7 @@ class GroundTruth:
 
     def same_as(self, boxes_list, labels_list):
         """whether these lists hold the very objects this ground truth was built from (``from_metas`` records them)"""
-        src = getattr(self, 'source', None)
-        return src is not None and len(src[0]) == len(boxes_list) and all(a is b for a, b in zip(src[0], boxes_list)) \
-            and all(a is b for a, b in zip(src[1], labels_list))
+        return _same_objects(getattr(self, 'source', None), boxes_list, labels_list)
 
     @classmethod
     def from_metas(cls, img_metas, device):
@@ -121,6 +136,62 @@ class GroundTruth:
         gt = cls(boxes, labels, device)
         gt.source = (boxes, labels)          # loss() reuses this ground truth when it is handed the same objects
         return gt
+
+
+class GroundTruthSlab:
+    """``GroundTruth`` at a fixed capacity: boxes [B*capacity, 9] fp32, labels [B*capacity] int32 and offsets [B+1] int32 live in ONE
+    device buffer whose address never changes, so a captured graph can read them on every replay.  The samples stay concatenated
+    sample-major, as every kernel reads them; the rows behind ``offsets[B]`` are capacity (zero, never read).  ``single`` is the
+    capacity and ``G`` is ``B * capacity``: every tensor and launch that is sized by them has the same shape whatever the batch holds,
+    and the per-sample counts in ``offsets`` on the device are the only thing that changes.  ``counts`` / ``offsets_host`` are kept for
+    host callers; nothing on the capacity path sizes a tensor or a launch by them."""
+
+    def __init__(self, B, capacity, device):
+        B, capacity = int(B), int(capacity)
+        if B < 0 or capacity < 0:
+            raise ValueError('GroundTruthSlab: B = %d, capacity = %d' % (B, capacity))
+        self.B, self.capacity, self.single, self.G, self.device = B, capacity, capacity, B * capacity, torch.device(device)
+        sizes, self._segs, n = (self.G * 9, self.G, B + 1), [], 0
+        for k in sizes:                                  # int32 words, segments padded to 16 bytes
+            self._segs.append(n)
+            n += (k + 3) // 4 * 4
+        self._words = n
+        self.buffer = torch.zeros(n, dtype=torch.int32, device=self.device)
+        o = self._segs
+        self.boxes = self.buffer[o[0]:o[0] + sizes[0]].view(torch.float32).view(self.G, 9)
+        self.labels = self.buffer[o[1]:o[1] + sizes[1]]
+        self.offsets = self.buffer[o[2]:o[2] + sizes[2]]
+        self.counts, self.offsets_host, self.source = [0] * B, np.zeros(B + 1, dtype=np.int32), None
+
+    def __deepcopy__(self, memo):                        # a copy of the head starts with an empty slab of its own
+        return GroundTruthSlab(self.B, self.capacity, self.device)
+
+    def update(self, boxes_list, labels_list):
+        """Refresh the three buffers in place from one batch (what ``GroundTruth`` accepts; device-resident lists are brought to the
+        host, which waits for them): packed on the host, ONE pinned asynchronous upload.  ``ValueError`` before any copy or launch when
+        the batch does not fit."""
+        boxes, labels, counts = _gt_tensors(boxes_list, labels_list)
+        if len(counts) != self.B:
+            raise ValueError('ground truth of %d samples for a slab of %d' % (len(counts), self.B))
+        if any(c > self.capacity for c in counts):
+            raise ValueError('a sample has %d ground-truth boxes, the capacity is %d' % (max(counts), self.capacity))
+        if self.device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('GroundTruthSlab.update inside a graph capture: update the slab before the capture / the replay')
+        from .transformer import _upload
+        host = np.zeros(self._words, dtype=np.int32)
+        total, o = sum(counts), self._segs
+        if total:
+            host[o[0]:o[0] + total * 9].view(np.float32)[:] = torch.cat([b.float().cpu() for b in boxes]).numpy().reshape(-1)
+            host[o[1]:o[1] + total] = torch.cat([lb.to(torch.int32).cpu() for lb in labels]).numpy()
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        host[o[2]:o[2] + self.B + 1] = offsets
+        _upload(host, self.device, out=self.buffer)
+        self.counts, self.offsets_host, self.source = counts, offsets, (list(boxes_list), list(labels_list))
+        return self
+
+    def same_as(self, boxes_list, labels_list):
+        """whether the slab holds the very objects of these lists (the last ``update``'s)"""
+        return _same_objects(self.source, boxes_list, labels_list)
 
 
 class _DnQueries(torch.autograd.Function):
@@ -146,14 +217,15 @@ class _DnQueries(torch.autograd.Function):
                                               float(box_scale), float(label_scale), B, Q, D, NC, G, N, single,
                                               _p(qb), _p(qf), _p(noised), _p(mask), _stream())
         _lib.check(st, 'sbev_head_dn_prepare')
-        ctx.save_for_backward(noised, gt_offsets)
+        ctx.save_for_backward(noised)
+        ctx.gt_offsets = gt_offsets      # an input without gradient; not a saved tensor: a GroundTruthSlab is refreshed in place between steps
         ctx.dims = (B, Q, D, NC, G, N, single)
         ctx.mark_non_differentiable(mask, noised)
         return qb, qf, mask, noised
 
     @staticmethod
     def backward(ctx, g_qb, g_qf, _gm, _gn):
-        noised, gt_offsets = ctx.saved_tensors
+        (noised,), gt_offsets = ctx.saved_tensors, ctx.gt_offsets
         B, Q, D, NC, G, N, single = ctx.dims
         T, dev = single * N + Q, noised.device
         g_qb = torch.zeros(B, T, 10, device=dev) if g_qb is None else g_qb.contiguous()
@@ -186,9 +258,22 @@ class _Denorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        r = ctx.pc_range
-        scale = g.new_tensor([r[3] - r[0], r[4] - r[1], r[5] - r[2]] + [1.0] * 7)
-        return g[..., list(_PERM_INV)] * scale, None
+        perm, scale = _denorm_constants(g, ctx.pc_range)
+        return g.index_select(-1, perm) * scale, None
+
+
+_DENORM_CONSTANTS = {}
+
+
+def _denorm_constants(g, r):
+    """(column permutation, ten scales) of _Denorm's backward on g's device: uploaded once per range, so that a captured backward holds
+    no host -> device copy"""
+    key = (g.device, g.dtype, tuple(float(v) for v in r))
+    c = _DENORM_CONSTANTS.get(key)
+    if c is None:
+        c = _DENORM_CONSTANTS[key] = (torch.tensor(_PERM_INV, dtype=torch.long, device=g.device),
+                                      g.new_tensor([r[3] - r[0], r[4] - r[1], r[5] - r[2]] + [1.0] * 7))
+    return c
 
 
 def _rows_view(t, last):
@@ -341,6 +426,33 @@ def set_loss(cls_scores, bbox_preds, codes, gt, code_weights, avg, w_fl=2.0, alp
                           (float(w_fl), float(alpha), float(gamma), float(w_l1), float(scale)))
 
 
+PLAN_COUNT_ABOVE_CAPACITY, PLAN_OFFSETS_NOT_MONOTONE, PLAN_TOTAL_ABOVE_CAPACITY = 1, 2, 4      # bits of capacity_plan's status
+
+
+def capacity_plan(gt_offsets, B, Q, capacity, N, bg_cls_weight=0.0):
+    """(codes int32 [B, N*capacity], avg fp32 [2,2], status int32 [1]) of a step at a fixed ground-truth capacity, from the counts in
+    ``gt_offsets`` on the device (sbev_head_capacity_plan): the denoising rows' codes, (A_cls, A_box) of the matching and of the
+    denoising loss, and 0 or PLAN_* bits.  One launch, no host copy."""
+    _i32(gt_offsets)
+    if gt_offsets.numel() != B + 1 or not gt_offsets.is_contiguous():
+        raise RuntimeError('capacity_plan: gt_offsets must be a contiguous int32 tensor of B + 1 = %d elements' % (B + 1))
+    dev = gt_offsets.device
+    codes = torch.empty(B, N * capacity, device=dev, dtype=torch.int32)
+    avg = torch.empty(2, 2, device=dev, dtype=torch.float32)
+    status = torch.empty(1, device=dev, dtype=torch.int32)
+    st = _lib.load().sbev_head_capacity_plan(_p(gt_offsets), B, Q, capacity, N, float(bg_cls_weight), _p(codes), _p(avg), _p(status), _stream())
+    _lib.check(st, 'sbev_head_capacity_plan')
+    return codes, avg, status
+
+
+def _named(out, losses, suffix):
+    """the reference's keys for an [L,2] loss tensor: the last layer's pair first, then d0.. (:290-297,448-460)"""
+    L = losses.shape[0]
+    out['loss_cls' + suffix], out['loss_bbox' + suffix] = losses[L - 1, 0], losses[L - 1, 1]
+    for i in range(L - 1):
+        out['d%d.loss_cls%s' % (i, suffix)], out['d%d.loss_bbox%s' % (i, suffix)] = losses[i, 0], losses[i, 1]
+
+
 def _typed(cfg, default_type, allowed, what):
     cfg = dict(cfg or {})
     kind = cfg.pop('type', default_type)
@@ -354,9 +466,14 @@ class SparseBEVTrainHead(SparseBEVHead):
     ``sbev_head_denorm`` behind an autograd Function whose backward is a column permutation and scale in torch ops."""
 
     def __init__(self, *args, loss_cls=None, loss_bbox=None, loss_iou=None, sync_cls_avg_factor=True, bg_cls_weight=0.0,
-                 train_cfg=None, assign_on='host', **kwargs):
+                 train_cfg=None, assign_on='host', gt_capacity=None, **kwargs):
         if assign_on not in ('host', 'device'):
             raise ValueError("sparsebev_amd.SparseBEVTrainHead: assign_on is 'host' or 'device', not %r" % (assign_on,))
+        if gt_capacity is not None:
+            if isinstance(gt_capacity, bool) or not isinstance(gt_capacity, (int, np.integer)) or gt_capacity < 0:
+                raise ValueError('sparsebev_amd.SparseBEVTrainHead: gt_capacity is None or a non-negative integer, not %r' % (gt_capacity,))
+            if assign_on != 'device':
+                raise ValueError("sparsebev_amd.SparseBEVTrainHead: gt_capacity needs assign_on='device' (the host solver reads the counts)")
         _, fl = _typed(loss_cls, 'FocalLoss', ('FocalLoss',), 'loss_cls')
         if not fl.get('use_sigmoid', True):
             raise ValueError('sparsebev_amd.SparseBEVTrainHead: loss_cls must be the sigmoid FocalLoss')
@@ -384,6 +501,13 @@ class SparseBEVTrainHead(SparseBEVHead):
         # where the linear sum assignment is solved: 'host' (one copy + one synchronisation per step) or 'device' (one launch, neither)
         self.assign_on = assign_on
         self.assign_status = None            # 'device': the last launch's int32 [L*B] status; nobody reads it on the hot path
+        # None: every shape follows the batch's ground truth.  An integer: the ground truth lives in a GroundTruthSlab of that many boxes
+        # per sample, pad_size is gt_capacity * dn_group_num always, and the counts are read on the device only
+        self.gt_capacity = None if gt_capacity is None else int(gt_capacity)
+        self.plan_status = None              # gt_capacity: the last plan launch's int32 [1] status (PLAN_* bits)
+        self.dn_noise = None                 # (u_box, u_lab, new_lab) for forward() to read instead of drawing (a captured step's static tensors)
+        self.decoder_ctx = None              # a transformer.DecoderContext for forward() to use instead of uploading img_metas (the same)
+        self._slab = None
 
     # ---- section 1: denoising queries ------------------------------------------------------------------------------
     def draw_noise(self, G, device):
@@ -397,9 +521,13 @@ class SparseBEVTrainHead(SparseBEVHead):
         device = init_query_bbox.device
         label_w = label_enc.weight if hasattr(label_enc, 'weight') else label_enc
         dn = self.training and self.dn_enabled
+        if dn and self.gt_capacity is not None:
+            return self._prepare_at_capacity(batch_size, init_query_bbox, label_w, img_metas, noise)
         gt = GroundTruth.from_metas(img_metas, device) if dn else GroundTruth([torch.zeros(0, 9)] * batch_size,
                                                                               [torch.zeros(0, dtype=torch.int32)] * batch_size, device)
         N = self.dn_group_num if dn else 1
+        if noise is None and dn and self.dn_noise is not None:
+            noise = self.dn_noise
         if noise is None:
             noise = self.draw_noise(gt.G, device) if dn else (torch.zeros(0, 3, device=device), torch.zeros(0, device=device),
                                                               torch.zeros(0, dtype=torch.int32, device=device))
@@ -419,13 +547,42 @@ class SparseBEVTrainHead(SparseBEVHead):
                      'gt': gt}
         return qb, qf, mask, mask_dict
 
+    def gt_slab(self, B, device):
+        """the head's GroundTruthSlab for batches of B samples (gt_capacity boxes each), made on first use"""
+        device = torch.device(device)
+        if self._slab is None or self._slab.B != B or self._slab.device != device:
+            self._slab = GroundTruthSlab(B, self.gt_capacity, device)
+        return self._slab
+
+    def _prepare_at_capacity(self, batch_size, init_query_bbox, label_w, img_metas, noise):
+        """prepare_for_dn_input with ``single`` = gt_capacity: the same launch at shapes that do not follow the counts.  The mask_dict
+        holds pad_size and the slab; the index tensors of the dynamic path exist for interface parity only and are left out."""
+        device = init_query_bbox.device
+        slab = self.gt_slab(batch_size, device)
+        boxes, labels = [m['gt_bboxes_3d'] for m in img_metas], [m['gt_labels_3d'] for m in img_metas]
+        if not (torch.cuda.is_current_stream_capturing() and slab.same_as(boxes, labels)):
+            slab.update(boxes, labels)               # under capture the slab holds these objects already, or update() refuses
+        N = self.dn_group_num
+        if noise is None:
+            noise = self.dn_noise if self.dn_noise is not None else self.draw_noise(slab.G, device)
+        u_box, u_lab, new_lab = [t.to(device) for t in noise]
+        qb, qf, mask, _ = dn_prepare(init_query_bbox, label_w, slab, u_box.float(), u_lab.float(), new_lab.to(torch.int32), batch_size, N,
+                                     self.num_classes, self.pc_range, self.dn_bbox_noise_scale, self.dn_label_noise_scale)
+        return qb, qf, mask, {'pad_size': slab.single * N, 'gt': slab}
+
     # ---- section 2: training forward ------------------------------------------------------------------------------------
     def forward(self, mlvl_feats, img_metas):
         if not self.training:
             return super().forward(mlvl_feats, img_metas)
         B = mlvl_feats[0].shape[0] if frame_source(mlvl_feats).kind == 'list' else mlvl_feats.B
         query_bbox, query_feat, attn_mask, mask_dict = self.prepare_for_dn_input(B, self.init_query_bbox.weight, self.label_enc, img_metas)
-        cls_scores, bbox_preds = self.transformer(query_bbox, query_feat, mlvl_feats, attn_mask=attn_mask, img_metas=img_metas)
+        if self.decoder_ctx is None:
+            cls_scores, bbox_preds = self.transformer(query_bbox, query_feat, mlvl_feats, attn_mask=attn_mask, img_metas=img_metas)
+        else:                                    # SparseBEVTransformer.forward's training path on an uploaded context
+            from .transformer import FeaturePyramid
+            cls_scores, bbox_preds = self.transformer.decoder.forward_differentiable(query_bbox, query_feat, mlvl_feats, FeaturePyramid(list(mlvl_feats)),
+                                                                                     attn_mask, self.decoder_ctx)
+            cls_scores, bbox_preds = torch.nan_to_num(cls_scores), torch.nan_to_num(bbox_preds)
         bbox_preds = _Denorm.apply(bbox_preds, self.pc_range)
         outs = {'all_cls_scores': cls_scores, 'all_bbox_preds': bbox_preds, 'enc_cls_scores': None, 'enc_bbox_preds': None}
         if mask_dict is not None and mask_dict['pad_size'] > 0:
@@ -461,6 +618,8 @@ class SparseBEVTrainHead(SparseBEVHead):
         all_cls, all_box = preds_dicts['all_cls_scores'], preds_dicts['all_bbox_preds']
         L, B, Q, _ = all_cls.shape
         md = preds_dicts.get('dn_mask_dict')
+        if self.gt_capacity is not None:
+            return self._loss_at_capacity(gt_bboxes_list, gt_labels_list, all_cls, all_box, md)
         if md is not None and md['gt'].same_as(gt_bboxes_list, gt_labels_list):
             gt = md['gt']                    # the forward's upload of the same objects
         else:
@@ -490,6 +649,34 @@ class SparseBEVTrainHead(SparseBEVHead):
         out['loss_cls'], out['loss_bbox'] = losses[L - 1, 0], losses[L - 1, 1]
         for i in range(L - 1):
             out['d%d.loss_cls' % i], out['d%d.loss_bbox' % i] = losses[i, 0], losses[i, 1]
+        return out
+
+    def _loss_at_capacity(self, gt_bboxes_list, gt_labels_list, all_cls, all_box, md):
+        """loss() with the ground truth in the slab: the same launches at ``single = Gmax = gt_capacity`` plus the plan launch, which
+        builds the dn codes and the averaging factors from the device's counts.  No host value here follows the counts."""
+        L, B, Q, _ = all_cls.shape
+        slab = md['gt'] if md is not None else self.gt_slab(B, all_cls.device)
+        if slab.B != B:
+            raise ValueError('ground truth of %d samples for a batch of %d' % (slab.B, B))
+        if not slab.same_as(gt_bboxes_list, gt_labels_list):
+            slab.update(gt_bboxes_list, gt_labels_list)
+        assign = self.assign(all_cls, all_box, slab)
+        N = md['pad_size'] // max(slab.single, 1) if md is not None else 1
+        codes, avg, self.plan_status = capacity_plan(slab.offsets, B, Q, slab.single, max(N, 1), self.bg_cls_weight)
+        m_avg, dn_avg = avg[0], reduce_mean(avg[1])
+        if self.sync_cls_avg_factor:
+            m_avg = reduce_mean(m_avg)
+        else:
+            m_avg = torch.stack([m_avg[0], reduce_mean(m_avg[1:2])[0]])
+        losses = set_loss(all_cls, all_box, assign, slab, self.code_weights, m_avg, self.loss_cls_weight, self.focal_alpha, self.focal_gamma,
+                          self.loss_bbox_weight, 1.0)
+        out = {}
+        if md is not None:
+            dn_cls, dn_box = md['output_known_lbs_bboxes']
+            dn = set_loss(dn_cls, dn_box, codes, slab, self.code_weights, dn_avg, self.loss_cls_weight, self.focal_alpha, self.focal_gamma,
+                          self.loss_bbox_weight, self.dn_weight)
+            _named(out, dn, '_dn')
+        _named(out, losses, '')
         return out
 
 

@@ -22,6 +22,10 @@ Inputs are STATIC tensors: write the next batch into them with ``copy_()`` (the 
 ``replay``.  Gradients land in the same ``.grad`` tensors every replay and OVERWRITE them (they were ``None`` at capture): run the
 optimizer after ``replay()``, and never ``zero_grad(set_to_none=True)`` -- that would detach ``.grad`` from the graph's buffers.
 
+``CapturedHeadTrainStep`` does the same for the training head's whole step (dn prepare, decoder forward + backward, denorm, matching
+cost, assignment, plan, both set-loss calls, the embeddings' backward) on a ``SparseBEVTrainHead(gt_capacity=...)``: there the ground
+truth is one more per-call constant, a ``head_train.GroundTruthSlab`` refreshed in place outside the graph, with the dn noise beside it.
+
 Reference counterpart: the training loop around SparseBEVTransformer.forward (models/sparsebev_transformer.py:86-101) and its
 backward through msmv_sampling (models/csrc/wrapper.py:51-61); the reference has no graph capture.
 """
@@ -34,7 +38,64 @@ from . import ops
 from .transformer import DecoderContext, FeaturePyramid, _upload
 from .utils import VERSION
 
-class CapturedTrainStep:
+class _CapturedStep:
+    """What the captured steps share: ONE side stream for warm-up, capture and replay, the warm-up that watches for torch's
+    stream-mismatch warning, the dropout word in device memory, and the refusal to replay under another feature-gradient mode.
+    A subclass sets ``device``, ``_leaves`` and ``dropout``, implements ``_run()`` (one step: forward, loss, backward; returns what
+    ``replay`` hands out) and calls ``_capture(warmup)`` once.  ``captures`` counts the graph captures of the object."""
+
+    captures = 0
+
+    def _capture(self, warmup):
+        who = type(self).__name__
+        # the part of the dropout seeds that changes from replay to replay (see the module text); None without dropout
+        self.seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device).random_() if self.dropout else None
+        # captured-under setting: the graph holds the launches of ONE feature-gradient mode (atomics, or the sorted-tap sum)
+        self.det_feat_grad = ops.deterministic_feature_grad_active()
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            mismatch = False
+            for i in range(max(1, warmup)):
+                self._clear_grads()
+                with warnings.catch_warnings(record=True) as seen:
+                    warnings.simplefilter('always')
+                    self._step()
+                mismatch = any('AccumulateGrad' in str(w.message) and 'stream' in str(w.message) for w in seen)
+            if mismatch:
+                raise RuntimeError("%s: a parameter's AccumulateGrad node still belongs to another stream (an autograd graph "
+                                   'of an earlier eager step is alive); capturing now would crash inside HIP.  Drop the references to earlier '
+                                   'losses / outputs, or build the captured step before the first eager step.' % who)
+            self._clear_grads()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=self.stream):
+                out = self._step()
+            self.captures += 1
+        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        return out
+
+    def _clear_grads(self):
+        for t in self._leaves:
+            t.grad = None
+
+    def _step(self):
+        with AG.device_seed(self.seed_dev):
+            return self._run()
+
+    def _check_feature_grad_mode(self):
+        if ops.deterministic_feature_grad_active() != self.det_feat_grad:
+            raise RuntimeError('%s.replay: the step was captured with the deterministic feature gradient %s and it is %s now '
+                               '(ops.deterministic_feature_grad / torch.use_deterministic_algorithms); capture a new step'
+                               % (type(self).__name__, ('off', 'on')[self.det_feat_grad], ('on', 'off')[self.det_feat_grad]))
+
+    def _refresh_cameras(self, img_metas):
+        packed, layout, image_h, image_w = DecoderContext.pack(img_metas, self.B)
+        if layout != self.ctx.layout or (image_h, image_w) != (self.ctx.image_h, self.ctx.image_w):
+            raise ValueError('%s.replay: img_metas with another shape than the captured step (frames, cameras, image size)' % type(self).__name__)
+        _upload(packed, self.device, out=self.ctx.buffer)          # in place: the graph reads this buffer
+
+
+class CapturedTrainStep(_CapturedStep):
     """``step = CapturedTrainStep(model, query_bbox, query_feat, mlvl_feats, img_metas, loss_fn)`` captures
     ``loss_fn(*model(...)).backward()``; ``loss, cls_scores, bbox_preds = step.replay(img_metas)`` runs it again on the current contents
     of the (static) input tensors.  ``step.grads`` maps parameter names to the static gradient tensors, ``step.input_grads`` holds
@@ -57,41 +118,11 @@ class CapturedTrainStep:
         self.B = query_bbox.shape[0]
         self.device = query_bbox.device
         self.ctx = DecoderContext(img_metas, self.B, self.device)          # host -> device: outside the graph
-        # the part of the dropout seeds that changes from replay to replay (see the module text); None without dropout
-        self.seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device).random_() if self.dropout else None
         self._leaves = [p for p in dec.parameters() if p.requires_grad]
         self._leaves += [t for t in [query_feat, query_bbox] + self.mlvl_feats if t.requires_grad]
-        # captured-under setting: the graph holds the launches of ONE feature-gradient mode (atomics, or the sorted-tap sum)
-        self.det_feat_grad = ops.deterministic_feature_grad_active()
-        self.stream = torch.cuda.Stream(device=self.device)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self.stream):
-            mismatch = False
-            for i in range(max(1, warmup)):
-                self._clear_grads()
-                with warnings.catch_warnings(record=True) as seen:
-                    warnings.simplefilter('always')
-                    self._step()
-                mismatch = any('AccumulateGrad' in str(w.message) and 'stream' in str(w.message) for w in seen)
-            if mismatch:
-                raise RuntimeError("CapturedTrainStep: a parameter's AccumulateGrad node still belongs to another stream (an autograd graph "
-                                   'of an earlier eager step is alive); capturing now would crash inside HIP.  Drop the references to earlier '
-                                   'losses / outputs, or build the captured step before the first eager step.')
-            self._clear_grads()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=self.stream):
-                self.loss, self.cls_scores, self.bbox_preds = self._step()
-        torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        self.loss, self.cls_scores, self.bbox_preds = self._capture(warmup)
         self.grads = {n: p.grad for n, p in dec.named_parameters() if p.grad is not None}
         self.input_grads = {'query_feat': query_feat.grad, 'mlvl_feats': [f.grad for f in self.mlvl_feats]}
-
-    def _clear_grads(self):
-        for t in self._leaves:
-            t.grad = None
-
-    def _step(self):
-        with AG.device_seed(self.seed_dev):
-            return self._run()
 
     def _run(self):
         dec = self.decoder
@@ -108,16 +139,92 @@ class CapturedTrainStep:
         counts) refreshes the camera matrices / time stamps first; with dropout on, new masks are drawn unless ``new_masks=False``
         (``seed_dev`` may also be set by hand).  Returns the graph's own (loss, cls_scores, bbox_preds) tensors -- clone what has to
         survive the next replay."""
-        if ops.deterministic_feature_grad_active() != self.det_feat_grad:
-            raise RuntimeError('CapturedTrainStep.replay: the step was captured with the deterministic feature gradient %s and it is %s now '
-                               '(ops.deterministic_feature_grad / torch.use_deterministic_algorithms); capture a new step'
-                               % (('off', 'on')[self.det_feat_grad], ('on', 'off')[self.det_feat_grad]))
+        self._check_feature_grad_mode()
         if img_metas is not None:
-            packed, layout, image_h, image_w = DecoderContext.pack(img_metas, self.B)
-            if layout != self.ctx.layout or (image_h, image_w) != (self.ctx.image_h, self.ctx.image_w):
-                raise ValueError('CapturedTrainStep.replay: img_metas with another shape than the captured step (frames, cameras, image size)')
-            _upload(packed, self.device, out=self.ctx.buffer)          # in place: the graph reads this buffer
+            self._refresh_cameras(img_metas)
         if self.seed_dev is not None and new_masks:
             self.seed_dev.random_()
         self.graph.replay()
         return self.loss, self.cls_scores, self.bbox_preds
+
+
+class CapturedHeadTrainStep(_CapturedStep):
+    """``step = CapturedHeadTrainStep(head, mlvl_feats, img_metas)`` captures the training head's whole step --
+    ``outs = head(mlvl_feats, img_metas)``, ``losses = head.loss(gt_bboxes, gt_labels, outs)``, ``sum(losses.values()).backward()`` -- as
+    one graph: the dn prepare, the decoder forward and backward, the denorm, the matching cost, the assignment, the plan, both set-loss
+    calls and the embeddings' backward.  ``head``: a ``SparseBEVTrainHead(gt_capacity=...)`` in ``train()`` with denoising on; the
+    ground truth is ``img_metas[i]['gt_bboxes_3d'] / ['gt_labels_3d']``.  What changes from step to step lives in static device memory
+    that ``replay`` refreshes OUTSIDE the graph: the head's ``GroundTruthSlab``, the camera block, the dn noise, the dropout word; the
+    features are the static tensors of ``mlvl_feats`` (write the next batch into them with ``copy_()``).
+
+    ``step.grads`` maps every trainable parameter of the head (``init_query_bbox.weight`` and ``label_enc.weight`` included) to its
+    static gradient tensor; ``step.captures`` stays 1.  One capacity per object: the graph owns the parameters' ``.grad``, and several
+    capacity buckets would have to share them.  A process group of more than one rank is refused: the averaging factors' all-reduce
+    would have to be captured."""
+
+    def __init__(self, head, mlvl_feats, img_metas, warmup=3):
+        from .head_train import SparseBEVTrainHead
+        if not torch.is_grad_enabled():
+            raise RuntimeError('CapturedHeadTrainStep: grad is disabled')
+        VERSION.require_supported()
+        if not isinstance(head, SparseBEVTrainHead) or head.gt_capacity is None:
+            raise ValueError('CapturedHeadTrainStep: the head must be a SparseBEVTrainHead(gt_capacity=...): at a dynamic shape nothing can be replayed')
+        if not (head.training and head.dn_enabled):
+            raise ValueError('CapturedHeadTrainStep: the head must be in train() mode with query denoising on')
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise RuntimeError('CapturedHeadTrainStep: a process group of %d ranks: the all-reduce of the averaging factors cannot be captured '
+                               '(run the eager step)' % torch.distributed.get_world_size())
+        self.head = head
+        self.mlvl_feats = list(mlvl_feats)
+        if not all(torch.is_tensor(f) and f.is_cuda and f.dtype == torch.float32 for f in self.mlvl_feats):
+            raise ValueError('CapturedHeadTrainStep: mlvl_feats must be a list of fp32 CUDA tensors (they are read in place)')
+        self.B, self.device = self.mlvl_feats[0].shape[0], self.mlvl_feats[0].device
+        layer = head.transformer.decoder.decoder_layer
+        self.dropout = bool(layer.self_attn.attn_drop > 0 or layer.ffn_drop > 0)
+        self.slab = head.gt_slab(self.B, self.device)
+        self._set_ground_truth([m['gt_bboxes_3d'] for m in img_metas], [m['gt_labels_3d'] for m in img_metas])
+        self.ctx = DecoderContext(img_metas, self.B, self.device)          # host -> device: outside the graph
+        self.noise = head.draw_noise(self.slab.G, self.device)            # static: replay() writes the next draw into these
+        self._leaves = [p for p in head.parameters() if p.requires_grad] + [f for f in self.mlvl_feats if f.requires_grad]
+        self.losses = self._capture(warmup)
+        self.grads = {n: p.grad for n, p in head.named_parameters() if p.grad is not None}
+        self.input_grads = {'mlvl_feats': [f.grad for f in self.mlvl_feats]}
+
+    def _set_ground_truth(self, boxes, labels):
+        if len(boxes) != self.B or len(labels) != self.B:
+            raise ValueError('CapturedHeadTrainStep: ground truth of %d samples for a batch of %d' % (len(boxes), self.B))
+        self.slab.update(boxes, labels)                                    # ValueError above the capacity, before anything is enqueued
+        self._boxes, self._labels = list(boxes), list(labels)
+        self._metas = [{'gt_bboxes_3d': b, 'gt_labels_3d': l} for b, l in zip(boxes, labels)]
+
+    def _run(self):
+        head = self.head
+        saved = (head.dn_noise, head.decoder_ctx)
+        head.dn_noise, head.decoder_ctx = self.noise, self.ctx
+        try:
+            outs = head(self.mlvl_feats, self._metas)
+            losses = head.loss(self._boxes, self._labels, outs)
+            sum(losses.values()).backward()
+        finally:
+            head.dn_noise, head.decoder_ctx = saved
+        return {k: v.detach() for k, v in losses.items()}
+
+    def replay(self, gt_bboxes_list, gt_labels_list, img_metas=None, new_masks=True, noise=None):
+        """Run the captured step on the next batch: the slab and (with ``img_metas``) the camera block are refreshed in place, new dn
+        noise is drawn into the static noise tensors (or ``noise`` = (u_box, u_lab, new_lab) at capacity is copied in; ``noise=False``
+        keeps the last one), with dropout on a new word unless ``new_masks=False``, then the graph runs.  Returns the graph's own loss
+        dict -- clone what has to survive the next replay.  ``ValueError`` before anything is enqueued when a sample is above the
+        capacity."""
+        self._check_feature_grad_mode()
+        self._set_ground_truth(gt_bboxes_list, gt_labels_list)
+        if img_metas is not None:
+            self._refresh_cameras(img_metas)
+        if noise is None:
+            noise = self.head.draw_noise(self.slab.G, self.device)
+        if noise is not False:
+            for dst, src in zip(self.noise, noise):
+                dst.copy_(src.to(self.device))
+        if self.seed_dev is not None and new_masks:
+            self.seed_dev.random_()
+        self.graph.replay()
+        return self.losses

@@ -12,6 +12,7 @@ figures of csrc/head_train.hip and csrc/head_assign.hip (VGPRs, SGPRs, scratch, 
 return identical loss dicts.
 
     python tools/bench_head_train.py [--steps 50] [--assign-on host|device|both] [--out profiles/head_train.json]
+    python tools/bench_head_train.py --captured [--steps 50]   (the captured step beside the eager one -> profiles/head_step_captured.json)
     python tools/bench_head_train.py --resources-only          (no GPU needed)
 """
 import argparse
@@ -138,6 +139,102 @@ def torch_loss(head, gt_boxes, gt_labels, preds, solver):
     return out
 
 
+def make_gt(B, gts, seed, dev):
+    g = torch.Generator().manual_seed(seed)
+    gt_boxes, gt_labels = [], []
+    for _ in range(B):
+        bx = torch.empty(gts, 9)
+        bx[:, 0:2] = (torch.rand(gts, 2, generator=g) * 2 - 1) * 50
+        bx[:, 2] = torch.rand(gts, generator=g) * 6 - 4.5
+        bx[:, 3:6] = torch.rand(gts, 3, generator=g) * 4 + 0.4
+        bx[:, 6] = (torch.rand(gts, generator=g) * 2 - 1) * 3.1
+        bx[:, 7:9] = torch.randn(gts, 2, generator=g)
+        gt_boxes.append(bx.to(dev))
+        gt_labels.append(torch.randint(0, 10, (gts,), generator=g).to(dev))
+    return gt_boxes, gt_labels
+
+
+def captured(a, res):
+    """--captured: the head's whole training step as ONE graph (train_graph.CapturedHeadTrainStep on SparseBEVTrainHead(gt_capacity=...))
+    beside the eager assign_on='device' step of the same tree at the same counts, interleaved in one run, at both recorded shapes (B = 1
+    with 40 boxes, B = 2 with 200) and with the capacity at the batch's maximum and at twice it.  The eager step gets its ground truth
+    device-resident, as the recorded runs did; the replay gets it host-resident (the loader's case: the slab packs on the host)."""
+    from sparsebev_amd import synthetic as S
+    from sparsebev_amd.head_train import SparseBEVTrainHead
+    from sparsebev_amd.train_graph import CapturedHeadTrainStep
+    dev = 'cuda:0'
+    ih, iw, sizes = S.PYRAMIDS[a.pyr]
+
+    def make_head(**kw):
+        return SparseBEVTrainHead(num_classes=10, in_channels=256, num_query=a.q, query_denoising_groups=a.groups, code_size=10,
+                                  code_weights=[2.0, 2.0] + [1.0] * 8,
+                                  transformer=dict(type='SparseBEVTransformer', embed_dims=256, num_frames=a.t, num_points=4, num_layers=6,
+                                                   num_levels=len(sizes), num_classes=10, code_size=10, pc_range=S.PC_RANGE),
+                                  bbox_coder=dict(type='NMSFreeCoder', post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0], max_num=300,
+                                                  num_classes=10, pc_range=S.PC_RANGE), assign_on='device', **kw)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    eager = make_head()
+    eager.init_weights()
+    S.randomize_zero_init(eager.transformer, std=0.02, seed=0)
+    with torch.no_grad():
+        eager.init_query_bbox.weight[:, 2] = 0.5
+    state = eager.state_dict()
+    eager = eager.to(dev).train()
+    shapes = []
+    for B, gts in ((1, 40), (2, 200)):
+        feats = S.make_features(B, a.t, sizes, seed=0, device=dev)
+        gt_boxes, gt_labels = make_gt(B, gts, 1, dev)
+        host_boxes, host_labels = [t.cpu() for t in gt_boxes], [t.cpu() for t in gt_labels]
+        metas = S.make_img_metas(B, a.t, ih, iw)
+        host_metas = copy.deepcopy(metas)
+        for m, hm, bx, lb, hb, hl in zip(metas, host_metas, gt_boxes, gt_labels, host_boxes, host_labels):
+            m['gt_bboxes_3d'], m['gt_labels_3d'] = bx, lb
+            hm['gt_bboxes_3d'], hm['gt_labels_3d'] = hb, hl
+        steps = {}
+        for cap in (gts, 2 * gts):
+            head = make_head(gt_capacity=cap)
+            head.load_state_dict(state, strict=True)
+            steps[cap] = CapturedHeadTrainStep(head.to(dev).train(), feats, host_metas)
+
+        def eager_step():
+            for p in eager.parameters():
+                p.grad = None
+            outs = eager(feats, copy.deepcopy(metas))
+            sum(eager.loss(gt_boxes, gt_labels, outs).values()).backward()
+
+        times = {'step_eager_device': []}
+        times.update({'step_captured_cap%d' % cap: [] for cap in steps})
+        for i in range(a.warmup + a.steps):
+            row = {'step_eager_device': timed(eager_step)}
+            for cap, st in steps.items():
+                row['step_captured_cap%d' % cap] = timed(lambda: st.replay(host_boxes, host_labels, host_metas))
+            if i >= a.warmup:
+                for k, v in row.items():
+                    times[k].append(v)
+        for cap, st in steps.items():
+            assert st.captures == 1 and st.head.plan_status.tolist() == [0] and all(bool(torch.isfinite(v)) for v in st.losses.values())
+        shapes.append({'B': B, 'gts': gts, 'capacities': sorted(steps), 'pad_sizes': {str(cap): cap * a.groups for cap in sorted(steps)},
+                       'median_ms': {k: round(statistics.median(v), 4) for k, v in times.items()},
+                       'min_ms': {k: round(min(v), 4) for k, v in times.items()}})
+        del steps
+    rec = {'tool': 'bench_head_train --captured', 'device': torch.cuda.get_device_name(0), 'Q': a.q, 'T': a.t, 'layers': 6, 'dn_groups': a.groups,
+           'steps': a.steps, 'dropout': 'on', 'timing': 'HIP events around each step, eager and captured interleaved in one run',
+           'shapes': shapes, 'kernel_resources': res}
+    line = json.dumps(rec)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(line + '\n')
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=50)
@@ -151,10 +248,17 @@ def main():
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'head_train.json'))
     ap.add_argument('--assign-on', choices=('host', 'device', 'both'), default='host')
     ap.add_argument('--resources-only', action='store_true')
+    ap.add_argument('--captured', action='store_true', help='time the step captured as one graph beside the eager device-assignment step, at both '
+                                                            'recorded shapes and two capacities (default --out profiles/head_step_captured.json)')
     a = ap.parse_args()
     res = kernel_resources()
     if a.resources_only:
         print(json.dumps(res))
+        return
+    if a.captured:
+        if a.out == ap.get_default('out'):
+            a.out = os.path.join(ROOT, 'profiles', 'head_step_captured.json')
+        captured(a, res)
         return
     from sparsebev_amd import synthetic as S
     from sparsebev_amd.head_train import SparseBEVTrainHead, lsa_solve
@@ -183,17 +287,7 @@ def main():
         head.init_query_bbox.weight[:, 2] = 0.5
     head = head.to(dev).train()
     feats = S.make_features(a.b, a.t, sizes, seed=0, device=dev)
-    g = torch.Generator().manual_seed(1)
-    gt_boxes, gt_labels = [], []
-    for _ in range(a.b):
-        bx = torch.empty(a.gts, 9)
-        bx[:, 0:2] = (torch.rand(a.gts, 2, generator=g) * 2 - 1) * 50
-        bx[:, 2] = torch.rand(a.gts, generator=g) * 6 - 4.5
-        bx[:, 3:6] = torch.rand(a.gts, 3, generator=g) * 4 + 0.4
-        bx[:, 6] = (torch.rand(a.gts, generator=g) * 2 - 1) * 3.1
-        bx[:, 7:9] = torch.randn(a.gts, 2, generator=g)
-        gt_boxes.append(bx.to(dev))
-        gt_labels.append(torch.randint(0, 10, (a.gts,), generator=g).to(dev))
+    gt_boxes, gt_labels = make_gt(a.b, a.gts, 1, dev)
     metas = S.make_img_metas(a.b, a.t, ih, iw)
     for m, bx, lb in zip(metas, gt_boxes, gt_labels):
         m['gt_bboxes_3d'], m['gt_labels_3d'] = bx, lb
