@@ -452,6 +452,46 @@ int sbev_head_assign_device(const float* cost, const int32_t* gt_offsets, int L,
 int sbev_head_capacity_plan(const int32_t* gt_offsets, int B, int Q, int capacity, int N, double bg_cls_weight, int32_t* codes,
                             float* avg_factors, int32_t* status, sbev_stream_t stream);
 
+/*
+ * AdamW with global-norm gradient clipping, a static loss scale and the skip of a non-finite step over a list of fp32 tensors: three
+ * launches per step on `stream` -- no host synchronisation, no device -> host copy, no atomics -- so the step can be captured.
+ * Replaces: the optimizer and optimizer_config of the training recipe (configs/r50_nuimg_704x256.py:186-200: AdamW, grad_clip
+ *           max_norm 35, static loss scale 512 with the step skipped on overflow), i.e. torch.optim.AdamW.step,
+ *           torch.nn.utils.clip_grad_norm_ and the overflow check of mmcv's Fp16OptimizerHook.
+ * Tensor addresses and sizes are host arrays that travel BY VALUE in the launches' argument blocks (at most SBEV_OPTIM_MAX_TENSORS per
+ * call; a longer list is several calls of _sumsq and _adamw, each with its own slice of `partials`).  What changes between steps is
+ * read from device memory:
+ *   hyper  [SBEV_OPTIM_HYPER_FLOATS] fp32: [0] inv_scale (1 / loss scale), [1] max_norm (<= 0: no clipping), [2] hold (non-zero: the
+ *          step is skipped whatever the norm), [3] unused, then per group g at [4 + 4g]: lr, weight_decay, lr multiplier, unused.
+ *   header SBEV_OPTIM_HEADER_BYTES, 8-byte aligned, written by sbev_optim_finish only: double beta1^t, beta2^t (running products; the
+ *          caller initialises both to 1); int64 step t, skipped; float norm, clip, 1 - beta1^t, sqrt(1 - beta2^t); int32 skip; 12 unused.
+ * A chunk is SBEV_OPTIM_CHUNK consecutive elements of one tensor.  sbev_optim_plan (pure host): out[0] = chunks of the list,
+ * out[1] = calls of _sumsq / _adamw that launch (groups of SBEV_OPTIM_MAX_TENSORS tensors with any element), out[2] = bytes of `partials`.
+ *
+ * sbev_optim_sumsq:  partials[c] = sum over chunk c of (g * inv_scale)^2, summed in fp64 in a fixed order, rounded once.
+ * sbev_optim_finish: norm = sqrt(sum of the n_partials partials in index order, fp64); clip = min(1, max_norm / (norm + 1e-6));
+ *                    skip = norm not finite, or hold.  Not skipped: t += 1 and the beta powers advance.  Skipped: skipped += 1 only.
+ * sbev_optim_adamw:  with g' = g * inv_scale * clip and lr = lr_g * multiplier_g:  p *= 1 - lr * wd;  m += (g' - m) * (1 - beta1);
+ *                    v = v * beta2 + g' * g' * (1 - beta2);  p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps),
+ *                    every operation rounded to fp32 on its own.  Nothing is stored when the header says skip.
+ * Bit-reproducible: neither the chunking nor any order of summation depends on the device or on the alignment of a tensor.
+ * Checked before any GPU call (SBEV_EINVAL): null arrays / pointers, n > SBEV_OPTIM_MAX_TENSORS, a negative numel, a base that is not
+ * 4-byte aligned, a group outside 0..n_groups-1, n_groups > SBEV_OPTIM_MAX_GROUPS, betas outside [0, 1).  A list without elements is
+ * SBEV_OK without a launch.  p / m / v of the list must not overlap each other.
+ */
+#define SBEV_OPTIM_CHUNK 8192
+#define SBEV_OPTIM_MAX_TENSORS 64
+#define SBEV_OPTIM_MAX_GROUPS 16
+#define SBEV_OPTIM_HYPER_FLOATS 68
+#define SBEV_OPTIM_HEADER_BYTES 64
+int sbev_optim_plan(const int64_t* numel, int n, int64_t* out);
+int sbev_optim_sumsq(const void* const* g, const int64_t* numel, int n, const float* hyper, float* partials, sbev_stream_t stream);
+int sbev_optim_finish(const float* partials, int64_t n_partials, const float* hyper, void* header, double beta1, double beta2,
+                      sbev_stream_t stream);
+int sbev_optim_adamw(void* const* p, const void* const* g, void* const* m, void* const* v, const int64_t* numel, const int32_t* group,
+                     int n, int n_groups, double beta1, double beta2, double eps, const float* hyper, const void* header,
+                     sbev_stream_t stream);
+
 /* Bytes of workspace PER LAYER for sbev_head_set_loss (-1 on bad sizes). */
 int64_t sbev_head_set_loss_workspace(int B, int rows);
 

@@ -8,7 +8,7 @@ operator modules without the built library raises -- there is no CPU / PyTorch f
 """
 from ._lib import load as load_library, SbevError, LIB_PATH   # noqa: F401
 
-__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead']
+__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW']
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == 'SparseBEVTrainHead':
         from .head_train import SparseBEVTrainHead
         return SparseBEVTrainHead
+    if name == 'FusedAdamW':
+        from .optim import FusedAdamW
+        return FusedAdamW
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -174,6 +174,11 @@ SIGNATURES = {
     'sbev_head_set_loss_workspace': (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
     'sbev_head_set_loss': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp] + [ctypes.c_float] * 5
                            + [ctypes.c_int] * 4 + [_vp] * 6),
+    'sbev_optim_plan': (ctypes.c_int, [_c_i64p, ctypes.c_int, _c_i64p]),
+    'sbev_optim_sumsq': (ctypes.c_int, [ctypes.POINTER(_vp), _c_i64p, ctypes.c_int, _vp, _vp, _vp]),
+    'sbev_optim_finish': (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp]),
+    'sbev_optim_adamw': (ctypes.c_int, [ctypes.POINTER(_vp)] * 4 + [_c_i64p, _c_i32p, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 3
+                         + [_vp, _vp, _vp]),
     'sbev_profile_read': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int]),
     'sbev_linear_splitk_plan': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'sbev_linear_group_f32': (ctypes.c_int, [_vp, ctypes.c_int, _vp]),

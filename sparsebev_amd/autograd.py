@@ -72,21 +72,30 @@ def _transposed(w):
     # cache never keeps a tensor alive, a recycled id never matches.  Parameters live across steps; the packed q | k | v | tau and
     # sampling weights are one tensor per decoder call shared by its layers (layer.packed_train_weights) and hit here from the second
     # layer's backward on.  Writes through ``.data`` do not bump ``_version``: see invalidate_caches().
-    cacheable = True
-    if cacheable:
+    # Inside step_images() (the captured steps) the image belongs to the step instead, and a capture never touches this cache.
+    def make():
+        N, K = w.shape
+        wt = torch.empty(K, N, device=w.device, dtype=torch.float32)
+        st = _lib.load().sbev_nchw_to_nhwc_f32(_p(_c(w.detach())), _p(wt), 1, N, K, _stream())      # [1, R = N, S = K] -> [1, S, R]
+        _lib.check(st, 'sbev_nchw_to_nhwc_f32 (weight transpose)')
+        return wt
+
+    def lookup():
         hit = _WT_CACHE.get(id(w))
         if hit is not None and hit[0]() is w and hit[1] == w._version and hit[2].device == w.device:
             return hit[2]
-    N, K = w.shape
-    wt = torch.empty(K, N, device=w.device, dtype=torch.float32)
-    st = _lib.load().sbev_nchw_to_nhwc_f32(_p(_c(w.detach())), _p(wt), 1, N, K, _stream())      # [1, R = N, S = K] -> [1, S, R]
-    _lib.check(st, 'sbev_nchw_to_nhwc_f32 (weight transpose)')
-    if cacheable:
+        return None
+
+    def store(wt):
         if len(_WT_CACHE) >= 64:                    # drop the entries of parameters that are gone
             for k in [k for k, v in _WT_CACHE.items() if v[0]() is None]:
                 del _WT_CACHE[k]
         _WT_CACHE[id(w)] = (weakref.ref(w), w._version, wt)
-    return wt
+
+    return dense.derived_image(True, 'wt', (w,), make, lookup, store)
+
+
+step_images = dense.step_images
 
 
 class Tap:
@@ -283,17 +292,23 @@ def _f16_frags(w, transposed=False):
     """The fp16 hi + lo fragment image (dense.pack_f16s_frags) of a Linear weight [N, K] -- or of W^T, the operand of grad_x = grad_y . W
     as a generator-shaped GEMM -- cached until the weight is modified in place (like _transposed: one pack per weight update)."""
     key = (id(w), bool(transposed))
-    hit = _F16_CACHE.get(key)
-    if hit is not None and hit[0]() is w and hit[1] == w._version and hit[2].device == w.device:
-        return hit[2], hit[3]
-    src = _transposed(w) if transposed else _c(w.detach())
-    frags, scales = dense.pack_f16s_frags(src)
-    if w.is_leaf:
+
+    def make():
+        return dense.pack_f16s_frags(_transposed(w) if transposed else _c(w.detach()))
+
+    def lookup():
+        hit = _F16_CACHE.get(key)
+        if hit is not None and hit[0]() is w and hit[1] == w._version and hit[2].device == w.device:
+            return hit[2], hit[3]
+        return None
+
+    def store(image):
         if len(_F16_CACHE) >= 64:
             for k in [k for k, v in _F16_CACHE.items() if v[0]() is None]:
                 del _F16_CACHE[k]
-        _F16_CACHE[key] = (weakref.ref(w), w._version, frags, scales)
-    return frags, scales
+        _F16_CACHE[key] = (weakref.ref(w), w._version) + tuple(image)
+
+    return dense.derived_image(w.is_leaf, 'f16t' if transposed else 'f16', (w,), make, lookup, store)
 
 
 def _mixed_up_log2(n):

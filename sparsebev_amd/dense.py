@@ -4,6 +4,7 @@ box refinement, NCHW->NHWC relayout) on the device.
 Every op here is a hand-written gfx950 kernel in libsbev_hip.so (``NATIVE`` names the kernel behind each);
 nothing runs through rocBLAS / ATen, and every function requires device tensors -- there is no CPU path.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -328,21 +329,68 @@ def linear_ln_relu(x, w, b, lnw, lnb):
 
 
 _CAT_CACHE = {}
+_STEP_IMAGES = None     # inside step_images(): key -> (source tensors, derived image); otherwise None
+
+
+@contextlib.contextmanager
+def step_images():
+    """The scope of ONE training step in which every derived weight image (autograd._transposed, autograd._f16_frags, _cat_rows) is
+    derived once, by launches of the step itself, and shared by the step's layers -- instead of coming from the process-wide caches
+    keyed on the parameters' ``_version``.  The captured steps (train_graph) run warm-up, capture and therefore every replay under it:
+    a graph captured on warm caches would record no transpose and no pack, and go on reading the images of the weights as they were at
+    capture after an optimizer has moved them.  Under a capture the images come from the capture's memory pool.  Nests: an inner scope
+    shares the outer one's images."""
+    global _STEP_IMAGES
+    outer = _STEP_IMAGES
+    if outer is None:
+        _STEP_IMAGES = {}
+    try:
+        yield
+    finally:
+        _STEP_IMAGES = outer
+
+
+def derived_image(cache_ok, kind, tensors, make, lookup, store):
+    """One derived image of ``tensors`` by ``make()``: from the step's scope inside step_images(); from the process-wide cache
+    (``lookup()`` -> image or None, ``store(image)``) in eager code; and while the current stream is capturing outside a scope the caches
+    are neither read nor filled -- an image cached at capture would be read by every replay, whatever the weights have become."""
+    scope = _STEP_IMAGES
+    if scope is not None:
+        key = (kind,) + tuple(id(t) for t in tensors)
+        hit = scope.get(key)
+        if hit is not None and all(a is b for a, b in zip(hit[0], tensors)):
+            return hit[1]
+        out = make()
+        scope[key] = (tensors, out)       # keeps the sources alive for the step: a recycled id cannot match
+        return out
+    if not cache_ok or (tensors[0].is_cuda and torch.cuda.is_current_stream_capturing()):
+        return make()
+    out = lookup()
+    if out is None:
+        out = make()
+        store(out)
+    return out
 
 
 def _cat_rows(*tensors):
     """torch.cat(tensors, 0), cached until any source is modified in place (parameters are static at inference).
     The entry keeps its source tensors alive and is matched by object identity, so a recycled device address can
-    never alias a stale entry."""
-    key = tuple(id(t) for t in tensors)
-    hit = _CAT_CACHE.get(key)
+    never alias a stale entry.  Inside step_images() / under a capture: see derived_image()."""
+    return derived_image(True, 'cat', tensors, lambda: torch.cat([t.detach() for t in tensors], 0).contiguous(),
+                         lambda: _cat_lookup(tensors), lambda out: _cat_store(tensors, out))
+
+
+def _cat_lookup(tensors):
+    hit = _CAT_CACHE.get(tuple(id(t) for t in tensors))
     if hit is not None and all(a is b and a._version == v for a, b, v in zip(hit[0], tensors, hit[1])):
         return hit[2]
+    return None
+
+
+def _cat_store(tensors, out):
     if len(_CAT_CACHE) > 64:
         _CAT_CACHE.clear()
-    out = torch.cat([t.detach() for t in tensors], 0).contiguous()
-    _CAT_CACHE[key] = (tensors, tuple(t._version for t in tensors), out)
-    return out
+    _CAT_CACHE[tuple(id(t) for t in tensors)] = (tensors, tuple(t._version for t in tensors), out)
 
 
 def scale_adaptive_self_attention(query_bbox, x, pc_range, num_heads, in_w, in_b, out_w, out_b, tau_w, tau_b,

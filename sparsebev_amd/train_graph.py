@@ -18,9 +18,24 @@ step's.  This is torch.cuda.graphs' whole-network recipe; what this module adds 
   * the feature-gradient mode (ops.deterministic_feature_grad, or torch.use_deterministic_algorithms) is whatever is on at capture;
     ``replay`` refuses to run the graph under the other one.
 
+  * derived weight images: W^T for grad_x, the fp16 fragment images of the two mixing weights and the packed rows are cached per
+    process, keyed on the parameters' ``_version`` (autograd._transposed / _f16_frags, dense._cat_rows).  A capture on warm caches
+    would record no transpose and no pack and replay on the images of the weights AS THEY WERE AT CAPTURE, whatever an optimizer has
+    done since.  So warm-up, capture and therefore every replay run inside ``autograd.step_images()``: each image is derived once per
+    step by launches of the step itself, from the capture's pool, and the caches are neither read nor filled.
+
 Inputs are STATIC tensors: write the next batch into them with ``copy_()`` (the features, the queries), pass the next ``img_metas`` to
-``replay``.  Gradients land in the same ``.grad`` tensors every replay and OVERWRITE them (they were ``None`` at capture): run the
-optimizer after ``replay()``, and never ``zero_grad(set_to_none=True)`` -- that would detach ``.grad`` from the graph's buffers.
+``replay``.  Gradients land in the same ``.grad`` tensors every replay and OVERWRITE them (they were ``None`` at capture); never
+``zero_grad(set_to_none=True)`` -- that would detach ``.grad`` from the graph's buffers.
+
+The parameter update: either any optimizer after ``replay()`` (in-place updates are seen by the next replay, see above), or
+``optimizer=optim.FusedAdamW(...)`` over exactly the captured parameters, whose three launches (gradient norm, header, AdamW with
+clipping / loss scale / overflow skip: csrc/optim.hip) then END the captured step.  The warm-up runs them with the optimizer's ``hold``
+word set -- the skip path a non-finite norm takes: kernels loaded and exercised, nothing written -- and the capture pass executes
+nothing, so construction leaves parameters, moments and counters bit-identical (``skipped`` is reset).  ``replay`` refreshes lr /
+weight_decay / scale in the optimizer's device buffer from ``param_groups`` next to the camera block, and bumps every parameter's
+``_version`` after the graph (the launches write through raw pointers).  ``step.grads`` after a replay are the gradients the update
+consumed.  With ``optimizer=`` a process group of more than one rank is refused: DDP's gradient all-reduce is not in the graph.
 
 ``CapturedHeadTrainStep`` does the same for the training head's whole step (dn prepare, decoder forward + backward, denorm, matching
 cost, assignment, plan, both set-loss calls, the embeddings' backward) on a ``SparseBEVTrainHead(gt_capacity=...)``: there the ground
@@ -46,8 +61,34 @@ class _CapturedStep:
 
     captures = 0
 
+    optimizer = None
+
+    def _refuse_ranks(self, optimizer):
+        """First thing in a constructor: DDP's gradient all-reduce is not in the graph, so an in-graph optimizer would step on one
+        rank's gradients."""
+        if optimizer is not None and torch.distributed.is_available() and torch.distributed.is_initialized() \
+                and torch.distributed.get_world_size() > 1:
+            raise RuntimeError('%s: optimizer= with a process group of %d ranks: the gradient all-reduce is not in the graph (run the '
+                               'optimizer after replay() and the all-reduce)' % (type(self).__name__, torch.distributed.get_world_size()))
+
+    def _bind_optimizer(self, optimizer, params):
+        """``optimizer=``: a FusedAdamW over exactly the captured parameters becomes the tail of the step."""
+        if optimizer is None:
+            return
+        from .optim import FusedAdamW
+        who = type(self).__name__
+        if not isinstance(optimizer, FusedAdamW):
+            raise TypeError('%s: optimizer= takes a sparsebev_amd.optim.FusedAdamW (its three launches are capturable); run any other '
+                            'optimizer after replay()' % who)
+        mine, theirs = {id(p) for p in params}, {id(p) for p, _ in optimizer._params()}
+        if mine != theirs:
+            raise ValueError('%s: the optimizer must hold exactly the captured trainable parameters (%d captured, %d in the optimizer, '
+                             '%d in both)' % (who, len(mine), len(theirs), len(mine & theirs)))
+        self.optimizer = optimizer
+
     def _capture(self, warmup):
         who = type(self).__name__
+        opt = self.optimizer
         # the part of the dropout seeds that changes from replay to replay (see the module text); None without dropout
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=self.device).random_() if self.dropout else None
         # captured-under setting: the graph holds the launches of ONE feature-gradient mode (atomics, or the sorted-tap sum)
@@ -55,6 +96,9 @@ class _CapturedStep:
         self.stream = torch.cuda.Stream(device=self.device)
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(self.stream):
+            if opt is not None:      # warm-up steps run the optimizer's launches on the skip path: loaded and exercised, nothing written
+                opt.hold = True
+                opt.push_hyper()
             mismatch = False
             for i in range(max(1, warmup)):
                 self._clear_grads()
@@ -71,6 +115,10 @@ class _CapturedStep:
             with torch.cuda.graph(self.graph, stream=self.stream):
                 out = self._step()
             self.captures += 1
+            if opt is not None:
+                opt.hold = False
+                opt.push_hyper()
+                opt.skipped.zero_()          # the warm-up's skips are not the caller's
         torch.cuda.current_stream(self.device).wait_stream(self.stream)
         return out
 
@@ -79,8 +127,20 @@ class _CapturedStep:
             t.grad = None
 
     def _step(self):
-        with AG.device_seed(self.seed_dev):
-            return self._run()
+        # step_images: every derived weight image (W^T, fp16 fragments, packed rows) is made by launches of the step itself, so a replay
+        # reads the weights as they are then -- never an image cached before the capture
+        with AG.device_seed(self.seed_dev), AG.step_images():
+            out = self._run()
+            if self.optimizer is not None:
+                self.optimizer.step()
+            return out
+
+    def _replay_graph(self):
+        if self.optimizer is not None:
+            self.optimizer.push_hyper()      # lr / weight_decay / scale from the groups: outside the graph, like the camera block
+        self.graph.replay()
+        if self.optimizer is not None:
+            self.optimizer.bump_versions()   # the graph wrote the parameters through raw pointers
 
     def _check_feature_grad_mode(self):
         if ops.deterministic_feature_grad_active() != self.det_feat_grad:
@@ -99,9 +159,11 @@ class CapturedTrainStep(_CapturedStep):
     """``step = CapturedTrainStep(model, query_bbox, query_feat, mlvl_feats, img_metas, loss_fn)`` captures
     ``loss_fn(*model(...)).backward()``; ``loss, cls_scores, bbox_preds = step.replay(img_metas)`` runs it again on the current contents
     of the (static) input tensors.  ``step.grads`` maps parameter names to the static gradient tensors, ``step.input_grads`` holds
-    ``query_feat.grad`` / the feature gradients where those inputs require grad."""
+    ``query_feat.grad`` / the feature gradients where those inputs require grad.  ``optimizer``: a FusedAdamW over the decoder's
+    trainable parameters; its update becomes the tail of the graph (module text)."""
 
-    def __init__(self, model, query_bbox, query_feat, mlvl_feats, img_metas, loss_fn, attn_mask=None, warmup=3):
+    def __init__(self, model, query_bbox, query_feat, mlvl_feats, img_metas, loss_fn, attn_mask=None, warmup=3, optimizer=None):
+        self._refuse_ranks(optimizer)
         if not torch.is_grad_enabled():
             raise RuntimeError('CapturedTrainStep: grad is disabled')
         VERSION.require_supported()
@@ -119,6 +181,7 @@ class CapturedTrainStep(_CapturedStep):
         self.device = query_bbox.device
         self.ctx = DecoderContext(img_metas, self.B, self.device)          # host -> device: outside the graph
         self._leaves = [p for p in dec.parameters() if p.requires_grad]
+        self._bind_optimizer(optimizer, self._leaves)
         self._leaves += [t for t in [query_feat, query_bbox] + self.mlvl_feats if t.requires_grad]
         self.loss, self.cls_scores, self.bbox_preds = self._capture(warmup)
         self.grads = {n: p.grad for n, p in dec.named_parameters() if p.grad is not None}
@@ -144,7 +207,7 @@ class CapturedTrainStep(_CapturedStep):
             self._refresh_cameras(img_metas)
         if self.seed_dev is not None and new_masks:
             self.seed_dev.random_()
-        self.graph.replay()
+        self._replay_graph()
         return self.loss, self.cls_scores, self.bbox_preds
 
 
@@ -160,10 +223,12 @@ class CapturedHeadTrainStep(_CapturedStep):
     ``step.grads`` maps every trainable parameter of the head (``init_query_bbox.weight`` and ``label_enc.weight`` included) to its
     static gradient tensor; ``step.captures`` stays 1.  One capacity per object: the graph owns the parameters' ``.grad``, and several
     capacity buckets would have to share them.  A process group of more than one rank is refused: the averaging factors' all-reduce
-    would have to be captured."""
+    would have to be captured.  ``optimizer``: a FusedAdamW over the head's trainable parameters; its update becomes the tail of the
+    graph (module text)."""
 
-    def __init__(self, head, mlvl_feats, img_metas, warmup=3):
+    def __init__(self, head, mlvl_feats, img_metas, warmup=3, optimizer=None):
         from .head_train import SparseBEVTrainHead
+        self._refuse_ranks(optimizer)
         if not torch.is_grad_enabled():
             raise RuntimeError('CapturedHeadTrainStep: grad is disabled')
         VERSION.require_supported()
@@ -185,6 +250,7 @@ class CapturedHeadTrainStep(_CapturedStep):
         self._set_ground_truth([m['gt_bboxes_3d'] for m in img_metas], [m['gt_labels_3d'] for m in img_metas])
         self.ctx = DecoderContext(img_metas, self.B, self.device)          # host -> device: outside the graph
         self.noise = head.draw_noise(self.slab.G, self.device)            # static: replay() writes the next draw into these
+        self._bind_optimizer(optimizer, [p for p in head.parameters() if p.requires_grad])
         self._leaves = [p for p in head.parameters() if p.requires_grad] + [f for f in self.mlvl_feats if f.requires_grad]
         self.losses = self._capture(warmup)
         self.grads = {n: p.grad for n, p in head.named_parameters() if p.grad is not None}
@@ -226,5 +292,5 @@ class CapturedHeadTrainStep(_CapturedStep):
                 dst.copy_(src.to(self.device))
         if self.seed_dev is not None and new_masks:
             self.seed_dev.random_()
-        self.graph.replay()
+        self._replay_graph()
         return self.losses
