@@ -49,16 +49,41 @@ def gemm(A, a_kmajor, lda, B, b_kmajor, ldb, M, N, K, out=None, ldc=None, accumu
 
 import weakref
 
-_WT_CACHE = {}      # id(parameter) -> (weak reference to it, version, W^T); a dead or recycled id never matches (`ref() is w`)
+# (id(parameter), kind) -> (weak reference to it, version, device, image); kind 'wt': W^T, 'f16' / 'f16t': pack_f16s_frags of W / W^T.
+# A dead or recycled id never matches (`ref() is w`).
+_WEIGHT_IMAGES = {}
 
 
 def invalidate_caches():
-    """Drop every cached W^T.  Needed after writes that do not bump a tensor's ``_version`` -- ``p.data.copy_(...)`` as mmcv's
-    Fp16OptimizerHook / EMA hooks do -- before the next backward; ordinary optimizers (in-place ops on the parameter) are
+    """Drop every cached W^T and fragment image.  Needed after writes that do not bump a tensor's ``_version`` -- ``p.data.copy_(...)``
+    as mmcv's Fp16OptimizerHook / EMA hooks do -- before the next backward; ordinary optimizers (in-place ops on the parameter) are
     detected through ``_version`` and need nothing.  ``SparseBEVTransformerDecoder.invalidate_caches()`` calls this and
     re-binds the inference runtime's packed weight images."""
-    _WT_CACHE.clear()
-    _F16_CACHE.clear()
+    _WEIGHT_IMAGES.clear()
+
+
+def _weight_image(cache_ok, kind, w, make):
+    """One derived image (``kind``) of the weight ``w`` by ``make()``, cached until the weight is modified in place."""
+    # keyed by id() with a weak reference to the tensor OBJECT beside it (a WeakKeyDictionary would compare tensors with ==): the
+    # cache never keeps a tensor alive, a recycled id never matches.  Parameters live across steps; the packed q | k | v | tau and
+    # sampling weights are one tensor per decoder call shared by its layers (layer.packed_train_weights) and hit here from the second
+    # layer's backward on.  Writes through ``.data`` do not bump ``_version``: see invalidate_caches().
+    # Inside step_images() (the captured steps) the image belongs to the step instead, and a capture never touches this cache.
+    key = (id(w), kind)
+
+    def lookup():
+        hit = _WEIGHT_IMAGES.get(key)
+        if hit is not None and hit[0]() is w and hit[1] == w._version and hit[2] == w.device:
+            return hit[3]
+        return None
+
+    def store(image):
+        if len(_WEIGHT_IMAGES) >= 64:               # drop the entries of parameters that are gone
+            for k in [k for k, v in _WEIGHT_IMAGES.items() if v[0]() is None]:
+                del _WEIGHT_IMAGES[k]
+        _WEIGHT_IMAGES[key] = (weakref.ref(w), w._version, w.device, image)
+
+    return dense.derived_image(cache_ok, kind, (w,), make, lookup, store)
 
 
 def _transposed(w):
@@ -68,11 +93,6 @@ def _transposed(w):
     instead of a 128 x 128-tile split-K launch + slab sum: 33 us), the strip kernel for grad_mixed (K = 256 -> 32 768 columns),
     the register-tile split-K kernel for the generator's input gradient (K = 32 768).  Costs one 2 x 33.5 MB transpose per
     big weight and optimizer step (12 us each)."""
-    # keyed by id() with a weak reference to the tensor OBJECT beside it (a WeakKeyDictionary would compare tensors with ==): the
-    # cache never keeps a tensor alive, a recycled id never matches.  Parameters live across steps; the packed q | k | v | tau and
-    # sampling weights are one tensor per decoder call shared by its layers (layer.packed_train_weights) and hit here from the second
-    # layer's backward on.  Writes through ``.data`` do not bump ``_version``: see invalidate_caches().
-    # Inside step_images() (the captured steps) the image belongs to the step instead, and a capture never touches this cache.
     def make():
         N, K = w.shape
         wt = torch.empty(K, N, device=w.device, dtype=torch.float32)
@@ -80,19 +100,14 @@ def _transposed(w):
         _lib.check(st, 'sbev_nchw_to_nhwc_f32 (weight transpose)')
         return wt
 
-    def lookup():
-        hit = _WT_CACHE.get(id(w))
-        if hit is not None and hit[0]() is w and hit[1] == w._version and hit[2].device == w.device:
-            return hit[2]
-        return None
+    return _weight_image(True, 'wt', w, make)
 
-    def store(wt):
-        if len(_WT_CACHE) >= 64:                    # drop the entries of parameters that are gone
-            for k in [k for k, v in _WT_CACHE.items() if v[0]() is None]:
-                del _WT_CACHE[k]
-        _WT_CACHE[id(w)] = (weakref.ref(w), w._version, wt)
 
-    return dense.derived_image(True, 'wt', (w,), make, lookup, store)
+def _f16_frags(w, transposed=False):
+    """The fp16 hi + lo fragment image (dense.pack_f16s_frags) of a Linear weight [N, K] -- or of W^T, the operand of grad_x = grad_y . W
+    as a generator-shaped GEMM -- cached until the weight is modified in place (like _transposed: one pack per weight update)."""
+    return _weight_image(w.is_leaf, 'f16t' if transposed else 'f16', w,
+                         lambda: dense.pack_f16s_frags(_transposed(w) if transposed else _c(w.detach())))
 
 
 step_images = dense.step_images
@@ -105,7 +120,7 @@ class Tap:
     None to autograd; ``ParamTap`` -- one node per call, which autograd runs after every node holding its token -- hands the buffers
     over.  Replaces 5 torch `add` launches per parameter and step (48 parameters: 240 of a step's launches), and
     an ``AccumulateGrad`` hook (DDP) sees each parameter once, complete.  Like FeatureTap there is no forward-time counter: partial
-    losses and repeated backward passes work."""
+    losses and repeated backward passes work.  The buffers are reached through ``sink`` (before a launch) and ``commit`` (after it)."""
 
     def __init__(self, params):
         self.ids = {id(p) for p in params if p.requires_grad}
@@ -128,6 +143,8 @@ class Tap:
         ParamTap has not run in between -- a node runs once per pass, nested passes run other node objects (the recomputed graph's),
         so this is a new pass over the same graph and the pending sums are an aborted pass's.  (Not covered: an aborted pass whose
         every tapped node sat inside a reentrant checkpoint, retried -- the recomputed nodes are new objects; build a new forward.)"""
+        if self.token is None:              # nothing to collect (no tap, or no parameter needs a gradient): nothing is ever recorded
+            return
         get_node = getattr(torch._C, '_current_autograd_node', None)
         node = get_node() if get_node is not None else None
         if node is None:
@@ -150,10 +167,45 @@ class Tap:
         self.fresh_pass()                   # (every tapped backward node asks this first)
         return pid in self.ids
 
+    def filled(self, pid):
+        """does the parameter already have a buffer in this pass (the next launch for it accumulates)"""
+        return pid in self.bufs
+
+    def sink(self, tapped, pid, like, shape=None):
+        """Where a backward launch writes the gradient of parameter ``pid``, and its accumulate flag: the parameter's buffer and 1 when a
+        tapped one has a buffer already; else a fresh fp32 tensor (``shape`` on ``like``'s device, or like ``like``) and 0."""
+        buf = self.bufs.get(pid) if tapped else None
+        if buf is not None:
+            return buf, 1
+        return (torch.empty_like(like) if shape is None else torch.empty(shape, device=like.device, dtype=torch.float32)), 0
+
+    def commit(self, tapped, pid, buf):
+        """After the launch's status check: a tapped parameter's buffer is registered for ParamTap's hand-over; returns what the node
+        returns to autograd for the parameter -- None then, the fresh gradient itself when it is not tapped."""
+        if not tapped:
+            return buf
+        self.bufs[pid] = buf
+        return None
+
     def token_grad(self):
+        """the token's (empty) gradient a tapped node returns; None for a node that took no token"""
+        if self.token is None:
+            return None
         if self._empty is None:
             self._empty = self.token.new_empty(0)
         return self._empty
+
+
+_NO_TAP = Tap(())       # what a node without a tap holds instead: has() is False, sink() / commit() hand a fresh tensor through
+
+
+def token_args(tap):
+    """the ``(tap, token)`` tail of a tapped Function's ``apply``; empty without a tap or when none of its parameters needs a gradient"""
+    return (tap, tap.token) if (tap is not None and tap.token is not None) else ()
+
+
+def _pc6(pc_range):
+    return (ctypes.c_double * 6)(*[float(v) for v in pc_range])
 
 
 class ParamTap(torch.autograd.Function):
@@ -176,34 +228,38 @@ class ParamTap(torch.autograd.Function):
             tap.deferred, tap.deferred_bias, tap.deferred_ln, tap._seen = {}, {}, {}, {}
 
 
+def _plan_launches(jobs, max_jobs, max_segs=8):
+    """The grouped reductions' launches.  ``jobs``: one ``(key, rows, number of segments, already has a buffer)`` per parameter in
+    recording order; returns ``[(rows, [(key, seg_start, seg_stop, accumulate), ...]), ...]``: at most ``max_segs`` segments per entry,
+    at most ``max_jobs`` entries and one row count per launch.  The second chunk of a parameter (more than ``max_segs`` layers) adds to
+    what the first one wrote, so it goes into a LATER launch.  Plain values in and out: no tensor, no library."""
+    rounds = {}                         # (chunk start, rows) -> entries, in recording order
+    for key, rows, nseg, filled in jobs:
+        for s0 in range(0, nseg, max_segs):
+            rounds.setdefault((s0, rows), []).append((key, s0, min(s0 + max_segs, nseg), s0 > 0 or bool(filled)))
+    return [(rows, part[j0:j0 + max_jobs]) for (_, rows), part in sorted(rounds.items()) for j0 in range(0, len(part), max_jobs)]
+
+
 def _group_bias_grads(tap):
     """the recorded biases' gradients: column sums over all layers' grad_y matrices, <= 16 biases per sbev_colsum_group launch"""
-    if not tap.deferred_bias:
-        return
-    lib = _lib.load()
-    by_rows = {}
-    for b_id, gs in tap.deferred_bias.items():
-        if gs:
-            by_rows.setdefault(gs[0].shape[0], []).append((b_id, gs))
-    for M, items in by_rows.items():
-        rounds = {}                     # chunk index -> [(bias id, <= 8 matrices, accumulate)]: the second chunk of a bias (more than 8
-        for b_id, gs in items:          # layers) adds to what the first one wrote, so it goes into a LATER launch
-            for s0 in range(0, len(gs), 8):
-                rounds.setdefault(s0, []).append((b_id, gs[s0:s0 + 8], s0 > 0 or b_id in tap.bufs))
-        parts = [jobs[j0:j0 + 16] for _, jobs in sorted(rounds.items()) for j0 in range(0, len(jobs), 16)]
-        for part in parts:
-            ng = len(part)
-            segs = (ctypes.c_void_p * (ng * 8))()
-            outs = (ctypes.c_void_p * ng)()
-            Ns, nsegs, accs = (ctypes.c_int32 * ng)(), (ctypes.c_int32 * ng)(), (ctypes.c_int32 * ng)()
-            for i, (b_id, gs, acc) in enumerate(part):
-                N = gs[0].shape[1]
-                if b_id not in tap.bufs:
-                    tap.bufs[b_id] = torch.empty(N, device=gs[0].device, dtype=torch.float32)
-                for k, g in enumerate(gs):
-                    segs[i * 8 + k] = g.data_ptr()
-                outs[i], Ns[i], nsegs[i], accs[i] = tap.bufs[b_id].data_ptr(), N, len(gs), int(acc)
-            _lib.check(lib.sbev_colsum_group(segs, outs, Ns, nsegs, accs, ng, M, _stream()), 'sbev_colsum_group')
+    rec = tap.deferred_bias
+    jobs = [(b_id, gs[0].shape[0], len(gs), tap.filled(b_id)) for b_id, gs in rec.items() if gs]
+    for M, part in _plan_launches(jobs, 16):
+        ng = len(part)
+        segs = (ctypes.c_void_p * (ng * 8))()
+        outs = (ctypes.c_void_p * ng)()
+        Ns, nsegs, accs = (ctypes.c_int32 * ng)(), (ctypes.c_int32 * ng)(), (ctypes.c_int32 * ng)()
+        bufs = []
+        for i, (b_id, s0, s1, acc) in enumerate(part):
+            gs = rec[b_id][s0:s1]
+            N = gs[0].shape[1]
+            bufs.append(tap.sink(True, b_id, gs[0], (N,))[0])
+            for k, g in enumerate(gs):
+                segs[i * 8 + k] = g.data_ptr()
+            outs[i], Ns[i], nsegs[i], accs[i] = bufs[i].data_ptr(), N, len(gs), int(acc)
+        _lib.check(_lib.load().sbev_colsum_group(segs, outs, Ns, nsegs, accs, ng, M, _stream()), 'sbev_colsum_group')
+        for (b_id, _, _, _), buf in zip(part, bufs):
+            tap.commit(True, b_id, buf)
 
 
 _LN_GROUP = os.environ.get('SBEV_NO_LN_GROUP', '0') != '1'   # A/B switch: LayerNorm parameter gradients per layer (1) or grouped per call
@@ -211,33 +267,28 @@ _LN_GROUP = os.environ.get('SBEV_NO_LN_GROUP', '0') != '1'   # A/B switch: Layer
 
 def _group_ln_grads(tap):
     """the recorded LayerNorms' dgamma / dbeta: sums over all layers' (grad_y, x, statistics), <= 8 LayerNorms per launch"""
-    if not tap.deferred_ln:
-        return
-    lib = _lib.load()
-    jobs = []
-    for (g_id, b_id), (g, b, relu, segs) in tap.deferred_ln.items():
-        for s0 in range(0, len(segs), 8):
-            jobs.append((g_id, b_id, g, b, relu, segs[s0:s0 + 8], s0 > 0 or g_id in tap.bufs, s0))
-    by_rows = {}                        # (chunk index, rows) -> jobs: a LayerNorm's second chunk (more than 8 layers) accumulates into what
-    for j in jobs:                      # its first one wrote and must run in a later launch
-        by_rows.setdefault((j[7], j[5][0][0].shape[0]), []).append(j)
+    rec = tap.deferred_ln
+    jobs = [(ids, v[3][0][0].shape[0], len(v[3]), tap.filled(ids[0])) for ids, v in rec.items() if v[3]]
     VP = ctypes.c_void_p
-    for (_, M), items in sorted(by_rows.items(), key=lambda kv: kv[0]):
-        for j0 in range(0, len(items), 8):
-            part = items[j0:j0 + 8]
-            ng = len(part)
-            dYs, Xs, Ss = (VP * (ng * 8))(), (VP * (ng * 8))(), (VP * (ng * 8))()
-            gam, bet, dgs, dbs = (VP * ng)(), (VP * ng)(), (VP * ng)(), (VP * ng)()
-            Ns, nsegs, relus, accs = [(ctypes.c_int32 * ng)() for _ in range(4)]
-            for i, (g_id, b_id, g, b, relu, segs, acc, _) in enumerate(part):
-                if g_id not in tap.bufs:
-                    tap.bufs[g_id], tap.bufs[b_id] = torch.empty_like(g), torch.empty_like(b)
-                for k, (gy, x, st) in enumerate(segs):
-                    dYs[i * 8 + k], Xs[i * 8 + k], Ss[i * 8 + k] = gy.data_ptr(), x.data_ptr(), st.data_ptr()
-                gam[i], bet[i], dgs[i], dbs[i] = g.data_ptr(), b.data_ptr(), tap.bufs[g_id].data_ptr(), tap.bufs[b_id].data_ptr()
-                Ns[i], nsegs[i], relus[i], accs[i] = g.shape[0], len(segs), int(relu), int(acc)
-            _lib.check(lib.sbev_layer_norm_param_group(dYs, Xs, Ss, gam, bet, dgs, dbs, Ns, nsegs, relus, accs, ng, M, _stream()),
-                       'sbev_layer_norm_param_group')
+    for M, part in _plan_launches(jobs, 8):
+        ng = len(part)
+        dYs, Xs, Ss = (VP * (ng * 8))(), (VP * (ng * 8))(), (VP * (ng * 8))()
+        gam, bet, dgs, dbs = (VP * ng)(), (VP * ng)(), (VP * ng)(), (VP * ng)()
+        Ns, nsegs, relus, accs = [(ctypes.c_int32 * ng)() for _ in range(4)]
+        bufs = []
+        for i, ((g_id, b_id), s0, s1, acc) in enumerate(part):
+            g, b, relu, segs = rec[(g_id, b_id)]
+            dg, dbeta = tap.sink(True, g_id, g)[0], tap.sink(True, b_id, b)[0]
+            bufs.append((dg, dbeta))
+            for k, (gy, x, st) in enumerate(segs[s0:s1]):
+                dYs[i * 8 + k], Xs[i * 8 + k], Ss[i * 8 + k] = gy.data_ptr(), x.data_ptr(), st.data_ptr()
+            gam[i], bet[i], dgs[i], dbs[i] = g.data_ptr(), b.data_ptr(), dg.data_ptr(), dbeta.data_ptr()
+            Ns[i], nsegs[i], relus[i], accs[i] = g.shape[0], s1 - s0, int(relu), int(acc)
+        _lib.check(_lib.load().sbev_layer_norm_param_group(dYs, Xs, Ss, gam, bet, dgs, dbs, Ns, nsegs, relus, accs, ng, M, _stream()),
+                   'sbev_layer_norm_param_group')
+        for ((g_id, b_id), _, _, _), (dg, dbeta) in zip(part, bufs):
+            tap.commit(True, g_id, dg)
+            tap.commit(True, b_id, dbeta)
 
 
 def _multi_wgrad(tap, pid, segs):
@@ -249,16 +300,13 @@ def _multi_wgrad(tap, pid, segs):
     for s0 in range(0, len(segs), 8):
         part = segs[s0:s0 + 8]
         n = len(part)
-        buf = tap.bufs.get(pid)
-        acc = buf is not None
-        if buf is None:
-            buf = torch.empty(N, K, device=gy0.device, dtype=torch.float32)
+        buf, acc = tap.sink(True, pid, gy0, (N, K))
         A = (ctypes.c_void_p * n)(*[g.data_ptr() for g, _ in part])
         Bp = (ctypes.c_void_p * n)(*[x.data_ptr() for _, x in part])
         ws = torch.empty(max(lib.sbev_gemm_f32_multi_workspace(N, K, M, n) // 4, 1), device=gy0.device, dtype=torch.float32)
-        st = lib.sbev_gemm_f32_multi(A, 1, N, Bp, 1, K, n, _p(buf), K, N, K, M, int(acc), _p(ws), _stream())
+        st = lib.sbev_gemm_f32_multi(A, 1, N, Bp, 1, K, n, _p(buf), K, N, K, M, acc, _p(ws), _stream())
         _lib.check(st, 'sbev_gemm_f32_multi')
-        tap.bufs[pid] = buf
+        tap.commit(True, pid, buf)
 
 
 _DEFER_MAX = 1 << 18      # weight gradients up to 512 x 512 wait for the end of the call (their operands are < 2 MB per layer)
@@ -270,45 +318,21 @@ def _defers(tap, pid, A, a_km, lda, b_km, ldb, M, N, K):
                 and (not tap.deferred.get(pid) or tap.deferred[pid][0][0].shape == A.shape))
 
 
-def _tap_gemm(tap, pid, *gemm_args):
-    """grad_W (+)= into the tapped parameter's buffer; gemm_args as for gemm() without out / ldc / accumulate.  Small gradients
-    (grad_y^T . x with both operands k-major) are only recorded here: ParamTap reduces all layers' pairs in one launch."""
-    A, a_km, lda, B, b_km, ldb, M, N, K = gemm_args
+def _wgrad(tap, pid, tapped, gz, x2, ld, K=None):
+    """grad_W [N, K] = grad_z^T . x of a Linear from grad_z [M, N] and x [M, ld] (K = ld unless the Linear reads only x's first K columns).
+    Tapped: (+)= into the parameter's buffer, None returned -- small gradients (both operands k-major, see _defers) are only recorded
+    here: ParamTap reduces all layers' pairs in one launch.  Not tapped: returned as a new tensor."""
+    M, N = gz.shape
+    K = ld if K is None else K
+    if not tapped:
+        return gemm(gz, True, N, x2, True, ld, N, K, M)                     # grad_z^T . x
     tap.fresh_pass()
-    if _defers(tap, pid, A, a_km, lda, b_km, ldb, M, N, K):
-        tap.deferred.setdefault(pid, []).append((A, B))
-        return
-    buf = tap.bufs.get(pid)
-    if buf is None:
-        tap.bufs[pid] = gemm(*gemm_args)
-    else:
-        gemm(*gemm_args, out=buf, ldc=gemm_args[7], accumulate=True)
-
-
-_F16_CACHE = {}     # (id(parameter), transposed) -> (weak reference, version, fragments, scales): pack_f16s_frags of W or W^T
-
-
-def _f16_frags(w, transposed=False):
-    """The fp16 hi + lo fragment image (dense.pack_f16s_frags) of a Linear weight [N, K] -- or of W^T, the operand of grad_x = grad_y . W
-    as a generator-shaped GEMM -- cached until the weight is modified in place (like _transposed: one pack per weight update)."""
-    key = (id(w), bool(transposed))
-
-    def make():
-        return dense.pack_f16s_frags(_transposed(w) if transposed else _c(w.detach()))
-
-    def lookup():
-        hit = _F16_CACHE.get(key)
-        if hit is not None and hit[0]() is w and hit[1] == w._version and hit[2].device == w.device:
-            return hit[2], hit[3]
+    if _defers(tap, pid, gz, True, N, True, ld, N, K, M):
+        tap.deferred.setdefault(pid, []).append((gz, x2))
         return None
-
-    def store(image):
-        if len(_F16_CACHE) >= 64:
-            for k in [k for k, v in _F16_CACHE.items() if v[0]() is None]:
-                del _F16_CACHE[k]
-        _F16_CACHE[key] = (weakref.ref(w), w._version) + tuple(image)
-
-    return dense.derived_image(w.is_leaf, 'f16t' if transposed else 'f16', (w,), make, lookup, store)
+    buf, acc = tap.sink(True, pid, gz, (N, K))
+    gemm(gz, True, N, x2, True, ld, N, K, M, out=buf, ldc=K, accumulate=acc)
+    return tap.commit(True, pid, buf)
 
 
 def _mixed_up_log2(n):
@@ -340,48 +364,57 @@ _GQ_F16 = os.environ.get('SBEV_NO_GQ_F16', '0') != '1'          # A/B switch: gr
 
 def _wgrad_tn_f16(tap, pid, tapped, A, lda, a_scale, B, ldb, b_scale, M, N, K):
     """grad_W [M, N] = A^T B on the fp16 hi + lo kernel: into the tapped parameter's buffer (returns None) or as a new tensor"""
-    if not tapped:
-        return dense.gemm_tn_f16s(A, lda, a_scale, B, ldb, b_scale, M, N, K)
-    buf = tap.bufs.get(pid)
-    if buf is None:
-        tap.bufs[pid] = dense.gemm_tn_f16s(A, lda, a_scale, B, ldb, b_scale, M, N, K)
-    else:
-        dense.gemm_tn_f16s(A, lda, a_scale, B, ldb, b_scale, M, N, K, out=buf, ldc=N, accumulate=True)
-    return None
+    buf, acc = tap.sink(tapped, pid, A, (M, N))
+    dense.gemm_tn_f16s(A, lda, a_scale, B, ldb, b_scale, M, N, K, out=buf, ldc=N, accumulate=acc)
+    return tap.commit(tapped, pid, buf)
 
 
-def _linear_grads(gy2, x2, w, need_x, need_w):
-    """gy2 [M,N], x2 [M,K], w [N,K] -> (grad_x [M,K] | None, grad_w [N,K] | None)"""
-    M, N = gy2.shape
+def _linear_grads(gz, w):
+    """grad_x [M, K] = grad_z . W from grad_z [M, N] and w [N, K] (the weight's own gradient: _wgrad)"""
+    M, N = gz.shape
     K = w.shape[1]
-    gx = None
-    if need_x:
-        if N % 4 == 0 and K % 4 == 0:
-            gx = dense.linear(gy2, _transposed(w), None)                        # grad_y . W as a forward Linear with W^T
-        else:
-            gx = gemm(gy2, False, N, w, True, K, M, K, N)                       # 10-wide heads: the layout-generic kernel
-    gw = gemm(gy2, True, N, x2, True, K, N, K, M) if need_w else None           # grad_y^T . x
-    return gx, gw
+    if N % 4 == 0 and K % 4 == 0:
+        return dense.linear(gz, _transposed(w), None)                           # grad_y . W as a forward Linear with W^T
+    return gemm(gz, False, N, w, True, K, M, K, N)                              # 10-wide heads: the layout-generic kernel
 
 
-def _bias_relu_bwd(gy2, y2, want_db, tap=None, pid=None):
+def _bias_relu_bwd(gy2, y2, want_db, tap=_NO_TAP, pid=None):
     """(masked grad, bias grad): gy * (y > 0) when y2 is the ReLU output (else gy itself) and its column sums.  With a Tap holding the
     bias (pid) the sums are added to its buffer and None is returned for them."""
     M, N = gy2.shape
     if y2 is None and not want_db:
         return gy2, None
     gz = torch.empty_like(gy2) if y2 is not None else None
-    tapped = want_db and tap is not None and tap.has(pid)
-    acc = tapped and pid in tap.bufs
-    db = (tap.bufs[pid] if acc else torch.empty(N, device=gy2.device, dtype=torch.float32)) if want_db else None
+    tapped = want_db and tap.has(pid)
+    db, acc = tap.sink(tapped, pid, gy2, (N,)) if want_db else (None, 0)
     lib = _lib.load()
     ws = torch.empty(max(lib.sbev_colsum_workspace(M, N) // 4, 1), device=gy2.device, dtype=torch.float32) if want_db else None
-    st = lib.sbev_bias_relu_bwd_acc(_p(gy2), _p(y2), _p(gz), _p(db), M, N, N, _p(ws), int(acc), _stream())
+    st = lib.sbev_bias_relu_bwd_acc(_p(gy2), _p(y2), _p(gz), _p(db), M, N, N, _p(ws), acc, _stream())
     _lib.check(st, 'sbev_bias_relu_bwd')
-    if tapped:
-        tap.bufs[pid] = db
-        db = None
-    return (gz if gz is not None else gy2), db
+    return (gz if gz is not None else gy2), tap.commit(tapped, pid, db)
+
+
+def _linear_member_bwd(tap, w_id, b_id, gy, x, y, w, relu, need_w, want_db):
+    """One Linear's backward up to grad_x: -> (grad_z [M, N], grad_W | None, grad_b | None) from the cotangent, the input, the ReLU
+    output (None without ReLU) and the weight.  grad_z is the (masked) cotangent grad_x is made of; a tapped parameter's gradient goes
+    into the tap and comes back as None."""
+    N, K = w.shape
+    gy2 = _c(gy).reshape(-1, N)
+    x2 = _c(x).reshape(-1, K)
+    y2 = y.reshape(-1, N) if relu else None
+    w_tapped = need_w and tap.has(w_id)
+    tap.fresh_pass()
+    recorded = tap.deferred_bias.get(b_id)
+    if (w_tapped and want_db and tap.has(b_id) and gy2.shape[0] * N <= _BIAS_DEFER_MAX and gy2.is_contiguous()
+            and (not recorded or recorded[0].shape == gy2.shape)):
+        # the bias gradient = column sums of this node's (masked) grad_y, recorded in the bias's own list and summed over all layers
+        # at the end (a ReLU Linear: only the mask now -- a fully parallel elementwise launch; the one-launch mask + column sum has
+        # N / 64 workgroups, 4 for a 256-wide layer, and took 10 us on the layer's critical path)
+        gz, db = (_bias_relu_bwd(gy2, y2, False)[0] if relu else gy2), None
+        tap.deferred_bias.setdefault(b_id, []).append(gz)
+    else:
+        gz, db = _bias_relu_bwd(gy2, y2, want_db, tap, b_id)
+    return gz, (_wgrad(tap, w_id, w_tapped, gz, x2, K) if need_w else None), db
 
 
 class Linear(torch.autograd.Function):
@@ -397,41 +430,20 @@ class Linear(torch.autograd.Function):
         ctx.has_res = residual is not None
         ctx.save_for_backward(x, w, y if relu else None)
         ctx.has_b = b is not None
-        ctx.tap, ctx.w_id, ctx.b_id = tap, id(w), id(b)
+        ctx.tap, ctx.w_id, ctx.b_id = tap or _NO_TAP, id(w), id(b)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, w, y = ctx.saved_tensors
-        N, K = w.shape
-        tap = ctx.tap
-        gy2 = _c(gy).reshape(-1, N)
-        x2 = _c(x).reshape(-1, K)
-        w_tapped = ctx.needs_input_grad[1] and tap is not None and tap.has(ctx.w_id)
-        want_db = ctx.has_b and ctx.needs_input_grad[2]
-        if tap is not None:
-            tap.fresh_pass()
-        recorded = tap.deferred_bias.get(ctx.b_id) if tap is not None else None
-        if (w_tapped and want_db and tap.has(ctx.b_id) and gy2.shape[0] * N <= _BIAS_DEFER_MAX and gy2.is_contiguous()
-                and (not recorded or recorded[0].shape == gy2.shape)):
-            # the bias gradient = column sums of this node's (masked) grad_y, recorded in the bias's own list and summed over all layers
-            # at the end (a ReLU Linear: only the mask now -- a fully parallel elementwise launch; the one-launch mask + column sum has
-            # N / 64 workgroups, 4 for a 256-wide layer, and took 10 us on the layer's critical path)
-            gz, db = (_bias_relu_bwd(gy2, y.reshape(-1, N), False)[0] if ctx.relu else gy2), None
-            tap.deferred_bias.setdefault(ctx.b_id, []).append(gz)
-        else:
-            gz, db = _bias_relu_bwd(gy2, y.reshape(-1, N) if ctx.relu else None, want_db, tap, ctx.b_id)
-        gx, gw = _linear_grads(gz, x2, _c(w), ctx.needs_input_grad[0], ctx.needs_input_grad[1] and not w_tapped)
-        if w_tapped:
-            _tap_gemm(tap, ctx.w_id, gz, True, N, x2, True, K, N, K, gz.shape[0])
-        return (gx.reshape(x.shape) if gx is not None else None, gw, db, None, gy if ctx.has_res and ctx.needs_input_grad[4] else None,
-                None, tap.token_grad() if (tap is not None and tap.token is not None) else None)
+        gz, gw, db = _linear_member_bwd(ctx.tap, ctx.w_id, ctx.b_id, gy, x, y, w, ctx.relu, ctx.needs_input_grad[1],
+                                        ctx.has_b and ctx.needs_input_grad[2])
+        gx = _linear_grads(gz, _c(w)).reshape(x.shape) if ctx.needs_input_grad[0] else None
+        return gx, gw, db, None, gy if ctx.has_res and ctx.needs_input_grad[4] else None, None, ctx.tap.token_grad()
 
 
 def linear(x, w, b, relu=False, residual=None, tap=None):
-    if tap is not None and tap.token is not None:
-        return Linear.apply(x, w, b, relu, residual, tap, tap.token)
-    return Linear.apply(x, w, b, relu, residual)
+    return Linear.apply(x, w, b, relu, residual, *token_args(tap))
 
 
 class LinearPair(torch.autograd.Function):
@@ -448,40 +460,21 @@ class LinearPair(torch.autograd.Function):
         ctx.relu = (bool(relu_a), bool(relu_b))
         ctx.save_for_backward(xa, wa, ya if relu_a else None, xb, wb, yb if relu_b else None)
         ctx.has_b = (ba is not None, bb is not None)
-        ctx.tap, ctx.w_id, ctx.b_id = tap, (id(wa), id(wb)), (id(ba), id(bb))
+        ctx.tap, ctx.w_id, ctx.b_id = tap or _NO_TAP, (id(wa), id(wb)), (id(ba), id(bb))
         return ya, yb
 
     @staticmethod
     def backward(ctx, gya, gyb):
         xa, wa, ya, xb, wb, yb = ctx.saved_tensors
-        tap = ctx.tap
-        if tap is not None:
-            tap.fresh_pass()
         xs, ws, ys, gys = (xa, xb), (wa, wb), (ya, yb), (gya, gyb)
         need_x = (ctx.needs_input_grad[0], ctx.needs_input_grad[4])
         need_w = (ctx.needs_input_grad[1], ctx.needs_input_grad[5])
         need_b = (ctx.needs_input_grad[2], ctx.needs_input_grad[6])
-        gz, gw, db, x2s = [None, None], [None, None], [None, None], [None, None]
+        gz, gw, db = [None, None], [None, None], [None, None]
         for i in range(2):
-            N, K = ws[i].shape
-            if gys[i] is None:
-                continue
-            gy2 = _c(gys[i]).reshape(-1, N)
-            x2s[i] = _c(xs[i]).reshape(-1, K)
-            w_tapped = need_w[i] and tap is not None and tap.has(ctx.w_id[i])
-            want_db = ctx.has_b[i] and need_b[i]
-            recorded = tap.deferred_bias.get(ctx.b_id[i]) if tap is not None else None
-            y2 = ys[i].reshape(-1, N) if ctx.relu[i] else None
-            if (w_tapped and want_db and tap.has(ctx.b_id[i]) and gy2.shape[0] * N <= _BIAS_DEFER_MAX and gy2.is_contiguous()
-                    and (not recorded or recorded[0].shape == gy2.shape)):
-                gz[i] = _bias_relu_bwd(gy2, y2, False)[0] if ctx.relu[i] else gy2
-                tap.deferred_bias.setdefault(ctx.b_id[i], []).append(gz[i])
-            else:
-                gz[i], db[i] = _bias_relu_bwd(gy2, y2, want_db, tap, ctx.b_id[i])
-            if w_tapped:
-                _tap_gemm(tap, ctx.w_id[i], gz[i], True, N, x2s[i], True, K, N, K, gz[i].shape[0])
-            elif need_w[i]:
-                gw[i] = gemm(gz[i], True, N, x2s[i], True, K, N, K, gz[i].shape[0])
+            if gys[i] is not None:
+                gz[i], gw[i], db[i] = _linear_member_bwd(ctx.tap, ctx.w_id[i], ctx.b_id[i], gys[i], xs[i], ys[i], ws[i], ctx.relu[i],
+                                                         need_w[i], ctx.has_b[i] and need_b[i])
         # grad_x = grad_y . W of both members: one grouped launch when both are small-tile shapes (N, K multiples of 4), else one by one
         gx = [None, None]
         both = all(need_x[i] and gz[i] is not None and ws[i].shape[0] % 4 == 0 and ws[i].shape[1] % 4 == 0 for i in range(2)) \
@@ -491,17 +484,28 @@ class LinearPair(torch.autograd.Function):
         else:
             for i in range(2):
                 if need_x[i] and gz[i] is not None:
-                    gx[i] = _linear_grads(gz[i], x2s[i], _c(ws[i]), True, False)[0]
+                    gx[i] = _linear_grads(gz[i], _c(ws[i]))
         gxa = gx[0].reshape(xa.shape) if gx[0] is not None else None
         gxb = gx[1].reshape(xb.shape) if gx[1] is not None else None
-        return (gxa, gw[0], db[0], None, gxb, gw[1], db[1], None, None,
-                tap.token_grad() if (tap is not None and tap.token is not None) else None)
+        return gxa, gw[0], db[0], None, gxb, gw[1], db[1], None, None, ctx.tap.token_grad()
 
 
 def linear_pair(xa, wa, ba, relu_a, xb, wb, bb, relu_b, tap=None):
-    if tap is not None and tap.token is not None:
-        return LinearPair.apply(xa, wa, ba, relu_a, xb, wb, bb, relu_b, tap, tap.token)
-    return LinearPair.apply(xa, wa, ba, relu_a, xb, wb, bb, relu_b)
+    return LinearPair.apply(xa, wa, ba, relu_a, xb, wb, bb, relu_b, *token_args(tap))
+
+
+def _layer_norm_bwd_acc(tap, tapped, g_id, b_id, gy2, x2, g, b, relu):
+    """relu?(LayerNorm) backward in one launch (sbev_layer_norm_bwd_acc): -> (grad_x, dgamma, dbeta) from grad_y [M, N] and the input
+    x [M, N]; tapped: dgamma / dbeta are added to the parameters' buffers and come back as None."""
+    M, N = x2.shape
+    gx = torch.empty_like(x2)
+    (dg, acc), (dbeta, acc_b) = tap.sink(tapped, g_id, g), tap.sink(tapped, b_id, b)
+    lib = _lib.load()
+    stats = torch.empty(max(lib.sbev_layer_norm_bwd_workspace(M, N) // 4, 1), device=x2.device, dtype=torch.float32)
+    st = lib.sbev_layer_norm_bwd_acc(_p(gy2), _p(x2), _p(_c(g)), _p(_c(b)), _EPS, int(relu), _p(gx), _p(dg), _p(dbeta), _p(stats),
+                                     M, N, acc & acc_b, _stream())
+    _lib.check(st, 'sbev_layer_norm_bwd')
+    return gx, tap.commit(tapped, g_id, dg), tap.commit(tapped, b_id, dbeta)
 
 
 class LayerNorm(torch.autograd.Function):
@@ -513,7 +517,7 @@ class LayerNorm(torch.autograd.Function):
         ctx.relu = bool(relu)
         ctx.has_add = add_after is not None
         ctx.save_for_backward(x, g, b)
-        ctx.tap, ctx.g_id, ctx.b_id = tap, id(g), id(b)
+        ctx.tap, ctx.g_id, ctx.b_id = tap or _NO_TAP, id(g), id(b)
         return y
 
     @staticmethod
@@ -522,37 +526,27 @@ class LayerNorm(torch.autograd.Function):
         N = x.shape[-1]
         gy2, x2 = _c(gy).reshape(-1, N), _c(x).reshape(-1, N)
         M = x2.shape[0]
-        gx = torch.empty_like(x2)
         tap = ctx.tap
-        tapped = tap is not None and tap.has(ctx.g_id) and tap.has(ctx.b_id)
+        tapped = tap.has(ctx.g_id) and tap.has(ctx.b_id)
         if tapped:
             tap.fresh_pass()
         rec = tap.deferred_ln.get((ctx.g_id, ctx.b_id)) if tapped else None
-        if (tapped and _LN_GROUP and ctx.g_id not in tap.bufs and g.is_contiguous() and b.is_contiguous()
+        if (tapped and _LN_GROUP and not tap.filled(ctx.g_id) and g.is_contiguous() and b.is_contiguous()
                 and (rec is None or not rec[3] or rec[3][0][0].shape == gy2.shape)):
             # shared LayerNorm: dX and the row statistics now, dgamma / dbeta of all layers in one grouped launch at the end of the call
+            gx = torch.empty_like(x2)
             stats = torch.empty(2 * M, device=x.device, dtype=torch.float32)
             st = _lib.load().sbev_layer_norm_bwd_rows(_p(gy2), _p(x2), _p(g), _p(b), _EPS, int(ctx.relu), _p(gx), _p(stats), M, N, _stream())
             _lib.check(st, 'sbev_layer_norm_bwd_rows')
             tap.deferred_ln.setdefault((ctx.g_id, ctx.b_id), [g, b, ctx.relu, []])[3].append((gy2, x2, stats))
-            return (gx.reshape(x.shape), None, None, None, gy if ctx.has_add and ctx.needs_input_grad[4] else None, None, tap.token_grad())
-        acc = tapped and ctx.g_id in tap.bufs and ctx.b_id in tap.bufs
-        dg, dbeta = (tap.bufs[ctx.g_id], tap.bufs[ctx.b_id]) if acc else (torch.empty_like(g), torch.empty_like(b))
-        stats = torch.empty(max(_lib.load().sbev_layer_norm_bwd_workspace(M, N) // 4, 1), device=x.device, dtype=torch.float32)
-        st = _lib.load().sbev_layer_norm_bwd_acc(_p(gy2), _p(x2), _p(_c(g)), _p(_c(b)), _EPS, int(ctx.relu), _p(gx), _p(dg), _p(dbeta),
-                                                 _p(stats), M, N, int(acc), _stream())
-        _lib.check(st, 'sbev_layer_norm_bwd')
-        if tapped:
-            tap.bufs[ctx.g_id], tap.bufs[ctx.b_id] = dg, dbeta
             dg = dbeta = None
-        return (gx.reshape(x.shape), dg, dbeta, None, gy if ctx.has_add and ctx.needs_input_grad[4] else None,
-                None, tap.token_grad() if (tap is not None and tap.token is not None) else None)
+        else:
+            gx, dg, dbeta = _layer_norm_bwd_acc(tap, tapped, ctx.g_id, ctx.b_id, gy2, x2, g, b, ctx.relu)
+        return gx.reshape(x.shape), dg, dbeta, None, gy if ctx.has_add and ctx.needs_input_grad[4] else None, None, tap.token_grad()
 
 
 def layer_norm(x, g, b, relu=False, add_after=None, tap=None):
-    if tap is not None and tap.token is not None:
-        return LayerNorm.apply(x, g, b, relu, add_after, tap, tap.token)
-    return LayerNorm.apply(x, g, b, relu, add_after)
+    return LayerNorm.apply(x, g, b, relu, add_after, *token_args(tap))
 
 
 class Linear3LnRelu(torch.autograd.Function):
@@ -560,7 +554,7 @@ class Linear3LnRelu(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, bbox, w, b, lnw, lnb, tap=None, token=None):
-        ctx.tap, ctx.pids = tap, (id(w), id(b), id(lnw), id(lnb))
+        ctx.tap, ctx.pids = tap or _NO_TAP, (id(w), id(b), id(lnw), id(lnb))
         N = w.shape[0]
         ld = bbox.shape[-1]
         x2 = _c(bbox).reshape(-1, ld)
@@ -579,31 +573,17 @@ class Linear3LnRelu(torch.autograd.Function):
         N = w.shape[0]
         M, ld = x2.shape
         gy2 = _c(gy).reshape(-1, N)
-        gpre = torch.empty_like(pre)
         tap = ctx.tap
         w_id, b_id, g_id, be_id = ctx.pids
-        ln_tapped = tap is not None and tap.has(g_id) and tap.has(be_id)
-        acc = ln_tapped and g_id in tap.bufs and be_id in tap.bufs
-        dg, dbeta = (tap.bufs[g_id], tap.bufs[be_id]) if acc else (torch.empty_like(lnw), torch.empty_like(lnb))
-        lib = _lib.load()
-        stats = torch.empty(max(lib.sbev_layer_norm_bwd_workspace(M, N) // 4, 1), device=gy.device, dtype=torch.float32)
-        _lib.check(lib.sbev_layer_norm_bwd_acc(_p(gy2), _p(pre), _p(_c(lnw)), _p(_c(lnb)), _EPS, 1, _p(gpre), _p(dg), _p(dbeta), _p(stats),
-                                               M, N, int(acc), _stream()), 'sbev_layer_norm_bwd')
-        if ln_tapped:
-            tap.bufs[g_id], tap.bufs[be_id] = dg, dbeta
-            dg = dbeta = None
+        gpre, dg, dbeta = _layer_norm_bwd_acc(tap, tap.has(g_id) and tap.has(be_id), g_id, be_id, gy2, pre, lnw, lnb, True)
         _, db = _bias_relu_bwd(gpre, None, True, tap, b_id)
-        if tap is not None and tap.has(w_id):
-            _tap_gemm(tap, w_id, gpre, True, N, x2, True, ld, N, 3, M)
-            gw = None
-        else:
-            gw = gemm(gpre, True, N, x2, True, ld, N, 3, M)                # grad_pre^T [N,M] . bbox[:, :3]
+        gw = _wgrad(tap, w_id, tap.has(w_id), gpre, x2, ld, 3)              # grad_pre^T [N,M] . bbox[:, :3]
         gb = None
         if ctx.needs_input_grad[0]:
             gb = torch.zeros(M, ld, device=gy.device, dtype=torch.float32)
             gemm(gpre, False, N, _c(w), True, 3, M, 3, N, out=gb, ldc=ld)  # grad_pre . W -> columns 0..2 of the box grad
             gb = gb.reshape(ctx.bshape)
-        return gb, gw, db, dg, dbeta, None, tap.token_grad() if (tap is not None and tap.token is not None) else None
+        return gb, gw, db, dg, dbeta, None, tap.token_grad()
 
 
 # Dropout under graph capture: a captured training step freezes the host seeds of its dropout sites; with a device seed installed
@@ -641,7 +621,7 @@ class SasaCore(torch.autograd.Function):
         hd = 32
         Dm = num_heads * hd
         att = torch.empty(B, Q, Dm, device=qkvt.device, dtype=torch.float32)
-        pc = (ctypes.c_double * 6)(*[float(v) for v in pc_range])
+        pc = _pc6(pc_range)
         lib = _lib.load()
         ds = _DEVICE_SEED[0] if attn_drop > 0.0 else None
         if attn_drop > 0.0:
@@ -661,7 +641,7 @@ class SasaCore(torch.autograd.Function):
         B, Q, ld = qkvt.shape
         gq = torch.empty_like(qkvt)
         ws = torch.empty(2 * B * H * Q, device=qkvt.device, dtype=torch.float32)
-        pc = (ctypes.c_double * 6)(*[float(v) for v in pc_range])
+        pc = _pc6(pc_range)
         st = _lib.load().sbev_sasa_bwd_f32_ds(_p(qkvt), ld, _p(bbox), pc, _p(mask), _p(att), _p(_c(gatt)), _p(gq), _p(ws), B, Q, H, 32,
                                               p, seed, _p(ds), _stream())
         _lib.check(st, 'sbev_sasa_bwd_f32')
@@ -678,7 +658,7 @@ class AdaptiveMixing(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, query, pg_w, pg_b, op_w, op_b, out_points, recompute, gemm_f16=False, tap=None, token=None):
-        ctx.tap, ctx.pids = tap, (id(pg_w), id(pg_b), id(op_w), id(op_b))
+        ctx.tap, ctx.pids = tap or _NO_TAP, (id(pg_w), id(pg_b), id(op_w), id(op_b))
         B, Q, G, Pin, C = x.shape
         D = query.shape[-1]
         BQ = B * Q
@@ -733,8 +713,7 @@ class AdaptiveMixing(torch.autograd.Function):
                        'sbev_adaptive_mixing_f32')
         tap = ctx.tap
         pgw_id, pgb_id, opw_id, opb_id = ctx.pids
-        opw_tapped = tap is not None and tap.has(opw_id)
-        pgw_tapped = tap is not None and tap.has(pgw_id)
+        opw_tapped, pgw_tapped = tap.has(opw_id), tap.has(pgw_id)
         # out-projection backward
         _, gb_op = _bias_relu_bwd(gy2, None, True, tap, opb_id)
         NM, NP = mixed.shape[1], params.shape[1]
@@ -743,15 +722,12 @@ class AdaptiveMixing(torch.autograd.Function):
         wg_f16 = ctx.f16 and _WGRAD_F16 and bool(lib.sbev_gemm_tn_f16s_ok(D, NM, BQ)) and bool(lib.sbev_gemm_tn_f16s_ok(NP, D, BQ))
         if ctx.f16:      # grad_mixed = grad_y . W_op: generator-shaped (K = 256 -> 32768 columns) with the fragments of W_op^T
             gmixed, gy_scale = dense.linear_f16s_gen(gy2, *_f16_frags(op_w, transposed=True), None, return_scale=True)
-            gw_op = None
-            if wg_f16:
-                gw_op = _wgrad_tn_f16(tap, opw_id, opw_tapped, gy2, D, gy_scale, mixed, NM, _const_scale(x.device, _mixed_up_log2(ctx.out_points * C)), D, NM, BQ)
-            elif not opw_tapped:
-                _, gw_op = _linear_grads(gy2, mixed, _c(op_w), False, True)
         else:
-            gmixed, gw_op = _linear_grads(gy2, mixed, _c(op_w), True, not opw_tapped)
-        if opw_tapped and not wg_f16:
-            _tap_gemm(tap, opw_id, gy2, True, D, mixed, True, NM, D, NM, BQ)
+            gmixed = _linear_grads(gy2, _c(op_w))
+        if wg_f16:
+            gw_op = _wgrad_tn_f16(tap, opw_id, opw_tapped, gy2, D, gy_scale, mixed, NM, _const_scale(x.device, _mixed_up_log2(ctx.out_points * C)), D, NM, BQ)
+        else:
+            gw_op = _wgrad(tap, opw_id, opw_tapped, gy2, mixed, NM)
         del mixed
         # mixing core backward
         gx = torch.empty_like(x)
@@ -766,21 +742,17 @@ class AdaptiveMixing(torch.autograd.Function):
         del gmixed, params
         # parameter generator backward
         _, gb_pg = _bias_relu_bwd(gparams, None, True, tap, pgb_id)
-        gw_pg = None
         if wg_f16:
             gp_scale = dense.f16s_tensor_scale(item_max)
             gw_pg = _wgrad_tn_f16(tap, pgw_id, pgw_tapped, gparams, NP, gp_scale, q2, D, ctx.q_scale, NP, D, BQ)
-        elif pgw_tapped:
-            _tap_gemm(tap, pgw_id, gparams, True, gparams.shape[1], q2, True, D, gparams.shape[1], D, BQ)
         else:
-            _, gw_pg = _linear_grads(gparams, q2, _c(pg_w), False, True)
+            gw_pg = _wgrad(tap, pgw_id, pgw_tapped, gparams, q2, D)
         # grad_query = grad_y (the `query +` residual) + grad_params . W_pg: the forward split-K Linear with W_pg^T, residual fused
         if wg_f16 and _GQ_F16 and bool(lib.sbev_linear_bf16s_out_ok(BQ, D, NP)):       # the same product on the fp16 split-K kernel, scale from the maxima
             gq = dense.linear_splitk_f16s(gparams, *_f16_frags(pg_w, transposed=True), None, residual=gy2, x_scale=gp_scale).reshape(query.shape)
         else:
             gq = dense.linear(gparams, _transposed(pg_w), None, residual=gy2).reshape(query.shape)
-        return (gx, gq, gw_pg, gb_pg, gw_op, gb_op, None, None, None, None,
-                tap.token_grad() if (tap is not None and tap.token is not None) else None)
+        return gx, gq, gw_pg, gb_pg, gw_op, gb_op, None, None, None, None, tap.token_grad()
 
 
 class FeatureTap(torch.autograd.Function):
@@ -853,7 +825,7 @@ class Sampling(torch.autograd.Function):
                                                float(dctx.image_h), float(dctx.image_w), 1e-5, _p(gpts), _stream()), 'sbev_project_select_bwd')
         gboth = torch.empty(B, Q, both.shape[-1], device=bbox.device, dtype=torch.float32)     # offsets | logits, packed like `both`
         gbbox = torch.empty(B, Q, 10, device=bbox.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        pc = (ctypes.c_double * 6)(*[float(v) for v in pc_range])
+        pc = _pc6(pc_range)
         ld = both.shape[-1]
         st = lib.sbev_sampling_front_bwd(_p(bbox), _p(both), ld, ctypes.c_void_p(both.data_ptr() + 4 * n_off), ld, pc, B, Q, T, G, P, L,
                                          _p(gpts), _p(gw), _p(gboth), ctypes.c_void_p(gboth.data_ptr() + 4 * n_off), ld, _p(gbbox), _stream())

@@ -224,7 +224,7 @@ class SparseBEVTransformerDecoderLayer(_Base):
         pe, sa, smp, mix = self.position_encoder, self.self_attn, self.sampling, self.mixing
         att = sa.attention.attn
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (sa.attn_drop > 0 or self.ffn_drop > 0) else 0
-        tk = (tap, tap.token) if (tap is not None and tap.token is not None) else ()
+        tk = AG.token_args(tap)
         pos = AG.Linear3LnRelu.apply(query_bbox, pe[0].weight, pe[0].bias, pe[1].weight, pe[1].bias, *tk)
         x = AG.layer_norm(AG.linear(pos, pe[3].weight, pe[3].bias, tap=tap), pe[4].weight, pe[4].bias, relu=True, add_after=query_feat, tap=tap)
         # self attention (+ identity), norm1

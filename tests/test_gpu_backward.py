@@ -751,6 +751,58 @@ def test_tap_survives_nested_backward_passes_of_reentrant_checkpointing(reentran
 
 
 @torch.enable_grad()
+def test_linear_pair_members_and_single_linears_share_one_backward_bit_for_bit():
+    """autograd.Linear and both members of autograd.LinearPair run ONE member backward (the bias-deferral rule, the mask, the weight
+    gradient's way into the Tap).  Four parameters shared by nine calls, so the deferred lists cross the 8-segment chunk: member a a
+    256 -> 256 ReLU Linear at 36 rows, member b a 256 -> 10 Linear at 20 rows without ReLU (N % 4 != 0: the one-by-one grad_x branch).
+    As nine AG.linear calls per member, as nine AG.linear_pair calls (a, b) and as nine with the members swapped, each under its own Tap:
+    every way records the same (grad_z, x) segments in the same order and the reducing kernels repeat bit for bit, so the weight and
+    bias gradients are bit-equal between the three; and equal to torch.autograd.grad of the F.linear restatement to the Tap tests'
+    2e-5."""
+    g = torch.Generator().manual_seed(80)
+    wa = (torch.randn(256, 256, generator=g) / 16).to(DEV).requires_grad_(True)
+    ba = torch.randn(256, generator=g).to(DEV).requires_grad_(True)
+    wb = (torch.randn(10, 256, generator=g) / 16).to(DEV).requires_grad_(True)
+    bb = torch.randn(10, generator=g).to(DEV).requires_grad_(True)
+    params, names = [wa, ba, wb, bb], ['weight a', 'bias a', 'weight b', 'bias b']
+    xa = [torch.randn(36, 256, generator=g).to(DEV).requires_grad_(True) for _ in range(9)]
+    xb = [torch.randn(20, 256, generator=g).to(DEV).requires_grad_(True) for _ in range(9)]
+    ca = [torch.randn(36, 256, generator=g).to(DEV) for _ in range(9)]
+    cb = [torch.randn(20, 10, generator=g).to(DEV) for _ in range(9)]
+
+    def loss_of(call):
+        outs = [call(i) for i in range(9)]
+        return sum((ya * ca[i]).sum() + (yb * cb[i]).sum() for i, (ya, yb) in enumerate(outs))
+
+    want = torch.autograd.grad(loss_of(lambda i: (F.relu(F.linear(xa[i], wa, ba)), F.linear(xb[i], wb, bb))), params + xa + xb)
+
+    def run(way):
+        tap = AG.Tap(params)
+        if way == 'single':
+            call = lambda i: (AG.linear(xa[i], wa, ba, relu=True, tap=tap), AG.linear(xb[i], wb, bb, tap=tap))
+        elif way == 'pair':
+            call = lambda i: AG.linear_pair(xa[i], wa, ba, True, xb[i], wb, bb, False, tap=tap)
+        else:
+            call = lambda i: AG.linear_pair(xb[i], wb, bb, False, xa[i], wa, ba, True, tap=tap)[::-1]
+        for t in params + xa + xb:
+            t.grad = None
+        loss_of(call).backward()
+        assert all(t.grad is not None for t in params + xa + xb)
+        return [t.grad.clone() for t in params + xa + xb]
+
+    got = {way: run(way) for way in ('single', 'pair', 'swapped')}
+    for way, grads in got.items():
+        for i, (a, r) in enumerate(zip(grads, want)):
+            name = names[i] if i < 4 else 'x%d' % (i - 4)
+            err = (a - r).abs().max().item()
+            print(way, name, 'max abs err %.3e of %.3e' % (err, r.abs().max().item()))
+            assert err <= 2e-5 * r.abs().max().item(), (way, name)
+    for i, name in enumerate(names):
+        assert torch.equal(got['single'][i], got['pair'][i]), name
+        assert torch.equal(got['pair'][i], got['swapped'][i]), name
+
+
+@torch.enable_grad()
 def test_eval_mode_with_grad_is_differentiable_and_matches_the_inference_runtime():
     """Grad enabled + something requires grad -> the module is differentiable like the reference's (no silent detached
     outputs); its forward values equal the fused inference runtime's to rounding; under no_grad the runtime runs."""

@@ -330,3 +330,59 @@ def test_every_switch_is_in_the_step_graph_key():
     assert R._switch_key() == base
     # the one report-only entry that stays in _STATE follows query_order() and starts from the library's value
     assert R._STATE['order'] == base[4]
+
+
+def _planner_cases():
+    one_row = lambda n, segs=6: [('p%d' % i, 36, segs, False) for i in range(n)]
+    cases = {'decoder-16': (one_row(40), 16), 'decoder-8': (one_row(40), 8)}
+    for n in (8, 9, 16, 17):
+        cases['%d-segments' % n] = ([('k', 36, n, False)], 16)
+    cases['17-keys'] = (one_row(17), 16)
+    cases['9-keys'] = (one_row(9), 8)
+    cases['two-row-counts'] = ([('p%d' % i, 36 if i % 2 else 20, 9, False) for i in range(20)], 8)
+    cases['has-buffer'] = ([('a', 36, 6, False), ('b', 36, 6, True), ('c', 36, 17, True)], 16)
+    cases['zero-segments'] = ([('a', 36, 6, False), ('z', 36, 0, False), ('b', 36, 9, False)], 16)
+    cases['empty'] = ([], 16)
+    return [pytest.param(jobs, mj, id=name) for name, (jobs, mj) in cases.items()]
+
+
+@pytest.mark.parametrize('jobs,max_jobs', _planner_cases())
+def test_grouped_reduction_planner_covers_every_segment_once_and_orders_a_parameters_chunks(jobs, max_jobs):
+    """autograd._plan_launches (what _group_bias_grads and _group_ln_grads marshal): every segment of every parameter in exactly one
+    entry, <= 8 segments per entry, <= max_jobs entries and one row count per launch, a parameter at most once per launch and its
+    chunks in increasing order over the launches (a later chunk adds to what the earlier one wrote), accumulate exactly for a later
+    chunk or a parameter that had a buffer already."""
+    from sparsebev_amd.autograd import _plan_launches
+    max_segs = 8
+    launches = _plan_launches(jobs, max_jobs, max_segs)
+    rows_of = {k: r for k, r, _, _ in jobs}
+    filled = {k: f for k, _, _, f in jobs}
+    covered = {k: [] for k, _, n, _ in jobs}
+    last_start = {}
+    for rows, entries in launches:
+        assert 1 <= len(entries) <= max_jobs
+        keys = [e[0] for e in entries]
+        assert len(set(keys)) == len(keys)
+        for key, s0, s1, acc in entries:
+            assert rows_of[key] == rows
+            assert 0 < s1 - s0 <= max_segs
+            assert s0 > last_start.get(key, -1)
+            last_start[key] = s0
+            assert acc == (s0 > 0 or filled[key])
+            covered[key] += range(s0, s1)
+    for key, _, nseg, _ in jobs:
+        assert covered[key] == list(range(nseg)), key
+    if not any(n for _, _, n, _ in jobs):
+        assert launches == []
+
+
+def test_grouped_reduction_planner_literal_case():
+    """three parameters with 9, 2 and 1 segments, two of them at 36 rows and one at 20: the launch list spelled out -- the ninth segment
+    of `a` accumulates in a launch AFTER the one that wrote its first eight"""
+    from sparsebev_amd.autograd import _plan_launches
+    jobs = [('a', 36, 9, False), ('b', 20, 2, False), ('c', 36, 1, False)]
+    assert _plan_launches(jobs, 16) == [(20, [('b', 0, 2, False)]),
+                                        (36, [('a', 0, 8, False), ('c', 0, 1, False)]),
+                                        (36, [('a', 8, 9, True)])]
+    assert _plan_launches(jobs, 1) == [(20, [('b', 0, 2, False)]), (36, [('a', 0, 8, False)]), (36, [('c', 0, 1, False)]),
+                                       (36, [('a', 8, 9, True)])]
