@@ -498,8 +498,19 @@ __global__ __launch_bounds__(256) void front_bwd_kernel(const FrontBwdArgs a) {
     float gb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (a.gpts) {
         const float s = bb[6], c = bb[7];
-        const float yaw = atan2f(s, c);
-        const float cs = cosf(yaw), sn_raw = sinf(yaw), sn = a.rot_sign * sn_raw;
+        // cos, sin of atan2(s, c) are c / r, s / r.  Going through the fp32 angle rounds it by up to half an ulp of pi (1.2e-7), and
+        // the yaw gradient multiplies that by the un-cancelled sums over the points of g_cs, g_sn -- several times the column's own
+        // rounding error.  Only where r2 leaves the normal range (or s = c = 0) the angle is taken, as the forward takes it.
+        const float r2 = s * s + c * c;
+        float cs, sn_raw;
+        if (r2 > 1e-30f && r2 < 1e30f) {
+            const float r = sqrtf(r2);
+            cs = c / r; sn_raw = s / r;
+        } else {
+            const float yaw = atan2f(s, c);
+            cs = cosf(yaw); sn_raw = sinf(yaw);
+        }
+        const float sn = a.rot_sign * sn_raw;
         const float ew = expf(bb[3]), el = expf(bb[4]), eh = expf(bb[5]);
         float g_yaw = 0.f;
         if (act) {
@@ -522,7 +533,6 @@ __global__ __launch_bounds__(256) void front_bwd_kernel(const FrontBwdArgs a) {
 #pragma unroll
         for (int d = 0; d < 6; ++d) gb[d] = sbev::wave_sum_dpp(gb[d]);
         g_yaw = sbev::wave_sum_dpp(g_yaw);
-        const float r2 = s * s + c * c;
         gb[6] = g_yaw * c / r2;
         gb[7] = -g_yaw * s / r2;
         gb[0] *= a.pc_span[0]; gb[1] *= a.pc_span[1]; gb[2] *= a.pc_span[2];
