@@ -151,7 +151,8 @@ int sbev_msmv_buffer_taps(int enable);
  * Same feature addressing as sbev_msmv_fwd.  grad_feats[l] (fp32, same layout as feats[l]) is ACCUMULATED into with
  * float atomics -- the caller zero-fills it (the reference's host code does `zeros_like`, :244-249).
  * grad_out [B',Q,C,P]; grad_loc [B',Q,P,3] (x, y scaled by (W_l-1), (H_l-1) like :102-104; the view component is
- * written as 0) and grad_weights [B',Q,P,L] are fully overwritten, without atomics.
+ * written as 0) and grad_weights [B',Q,P,L] are fully overwritten, without atomics.  A point with a non-finite x or y (NaN, +-Inf)
+ * reads no level, like the reference's (:170): its grad_loc and grad_weights rows are exactly 0 and it writes no feature gradient.
  */
 int sbev_msmv_bwd(const void* const* feats, void* const* grad_feats, const int32_t* hw, int L,
                   int64_t Bp, int N, int C, int Q, int P,

@@ -146,7 +146,9 @@ def msmv_sampling_backward(feats_cl, loc, weights, grad_out):
         h_im, w_im = y * (H - 1), x * (W - 1)
         ok = (h_im > -1) & (w_im > -1) & (h_im < H) & (w_im < W)
         h0f, w0f = torch.floor(h_im), torch.floor(w_im)
-        lh, lw = h_im - h0f, w_im - w0f
+        # a level that is not read (:170) contributes exact zeros: without this, a NaN / Inf coordinate leaves NaN fractions and the
+        # masked corner values below give 0 * NaN
+        lh, lw = torch.where(ok, h_im - h0f, torch.zeros_like(h_im)), torch.where(ok, w_im - w0f, torch.zeros_like(w_im))
         hh, hw = 1 - lh, 1 - lw
         h0, w0 = h0f.long(), w0f.long()
         gf = torch.zeros_like(f)

@@ -1,11 +1,10 @@
 // The tap geometry of the sampler's backward, stated once: shared by the atomic kernels (msmv_sampling_bwd.hip) and the tap list of the
 // atomics-free feature gradient (msmv_sampling_det.hip), so that both decide "is this level read" and "which pixel is this corner" from
 // the same expressions (msmv_sampling_backward.cu:29-105 / the forward's msmv_sampling_forward.cu:41-66).
-// Contraction is the INCLUDING translation unit's: msmv_sampling_bwd.hip is built with the compiler's default and its kernels fuse
-// lh = y * (H - 1) - floor(.) into one fma -- a `#pragma clang fp contract(off)` in these bodies (as sample_point.hpp has) would undo
-// that and change the bits of grad_loc / grad_weights; msmv_sampling_det.hip is built with -ffp-contract=off, so every product and
-// difference of its tap list is individually rounded.  The two agree on every decision (lvl_ok, floors, corners: none of them reads a
-// contracted value) and differ by at most one rounding in the bilinear fractions.
+// The bilinear fractions differ between the two: msmv_sampling_bwd.hip forms each fraction and its complement with one explicit fma on
+// the exact product (corner_frac there: one rounding each) and does not read lh / lw below; msmv_sampling_det.hip is built with
+// -ffp-contract=off, so every product and difference of its tap list is individually rounded.  The two agree on every decision
+// (lvl_ok, floors, corners: all of them read the fp32 product) and differ by at most one rounding in the bilinear fractions.
 #pragma once
 #include <cmath>
 
