@@ -17,11 +17,13 @@ In ``train()``:
     (csrc/head_assign.hip: the host solver restated in parallel, the same table bit for bit) and ``loss()`` makes no device ->
     host copy and no synchronisation.
 
-``SparseBEVTrainHead(gt_capacity=C, assign_on='device')`` runs the same launches at shapes that do not follow the batch: the ground
-truth lives in a ``GroundTruthSlab`` (``C`` boxes per sample at a fixed address, refreshed in place), ``pad_size`` is ``C * N`` always,
-and one more launch (``capacity_plan``) derives the dn codes and the averaging factors from the counts on the device -- what
-``train_graph.CapturedHeadTrainStep`` needs to replay the whole step as one graph.  It is the dynamic path with ``single`` forced to
-``C``: unused pad rows are zero rows inside their group's attention, and a batch without ground truth keeps its ``*_dn`` keys, at 0.
+Both methods have ONE body that reads the ground truth through one of two sources (``_GroundTruthSource``).  ``GroundTruth`` is the
+batch's own upload: every shape follows its counts, and the step's plan (dn codes, averaging factors) is host arithmetic that goes over
+in one copy.  ``SparseBEVTrainHead(gt_capacity=C, assign_on='device')`` reads a ``GroundTruthSlab`` instead (``C`` boxes per sample at a
+fixed address, refreshed in place): ``single`` is ``C`` and ``pad_size`` is ``C * N`` always, and the plan is one more launch
+(``capacity_plan``) that reads the counts on the device -- what ``train_graph.CapturedHeadTrainStep`` needs to replay the whole step as
+one graph.  So the capacity path is the dynamic path with ``single`` forced to ``C``: unused pad rows are zero rows inside their
+group's attention, and a batch without ground truth keeps its ``*_dn`` keys, at 0.
 
 mmdet's sigmoid ``FocalLoss``, ``L1Loss`` and ``FocalLossCost`` are restated in the kernels (mmdet is not vendored by the
 reference: parity is unpinned at that third-party boundary, as the mmcv attention is).
@@ -103,20 +105,42 @@ def _gt_tensors(boxes_list, labels_list):
     return boxes, labels, counts
 
 
-def _same_objects(src, boxes_list, labels_list):
-    return src is not None and len(src[0]) == len(boxes_list) and len(src[1]) == len(labels_list) \
-        and all(a is b for a, b in zip(src[0], boxes_list)) and all(a is b for a, b in zip(src[1], labels_list))
+class _GroundTruthSource:
+    """What the head's kernels and ``loss()`` read of a batch's ground truth, whichever way it reached the device:
+
+      * device tensors ``boxes`` [G,9] fp32, ``labels`` [G] int32 and ``offsets`` [B+1] int32, the samples concatenated sample-major;
+      * ``B`` samples, ``G`` rows, and ``single``, the per-sample row count that every tensor and launch is sized by;
+      * on the host ``counts`` (a list of B ints) and ``offsets_host`` (numpy int32 [B+1]), and ``source``: the (boxes, labels) lists
+        the contents were built from, where those were recorded.
+
+    ``plan(Q, N, bg_cls_weight)`` is the step's plan: (codes int32 [B, N*single], avg fp32 [2,2], status).  ``codes`` are the denoising
+    rows' codes (k at (b, r*single + k) for k < counts[b], -2 elsewhere: prepare_for_dn_loss's gather, :224-237), row 0 of ``avg`` is
+    (A_cls, A_box) of the matching loss and row 1 (A, A) of the denoising loss, both before the reduction over the ranks
+    (:247,371-384), and ``status`` is None or an int32 [1] tensor of PLAN_* bits."""
+
+    def _set_host(self, counts, source=None):
+        self.counts, self.offsets_host, self.source = counts, np.concatenate([[0], np.cumsum(counts)]).astype(np.int32), source
+
+    def same_as(self, boxes_list, labels_list):
+        """whether these lists hold the very objects this ground truth was built from (``from_metas`` / ``update`` record them)"""
+        src = self.source
+        return src is not None and len(src[0]) == len(boxes_list) and len(src[1]) == len(labels_list) \
+            and all(a is b for a, b in zip(src[0], boxes_list)) and all(a is b for a, b in zip(src[1], labels_list))
+
+    def dn_indices(self, N):
+        """the mask_dict's index tensors (interface parity with the reference's; nothing here reads them): none by default"""
+        return {}
 
 
-class GroundTruth:
+class GroundTruth(_GroundTruthSource):
     """The batch's ground truth concatenated sample-major on the device: boxes [G,9] fp32, labels [G] int32, offsets [B+1] int32
     and the per-sample counts on the host.  Host-resident ground truth (the data loader's normal case) is concatenated on the host and
     goes over with the offsets in ONE asynchronous pinned upload; device-resident ground truth is concatenated where it is."""
 
     def __init__(self, boxes_list, labels_list, device):
-        boxes, labels, self.counts = _gt_tensors(boxes_list, labels_list)
-        self.B, self.G, self.single = len(boxes), sum(self.counts), max(self.counts) if boxes else 0
-        self.offsets_host = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int32)
+        boxes, labels, counts = _gt_tensors(boxes_list, labels_list)
+        self._set_host(counts)
+        self.B, self.G, self.single = len(boxes), sum(counts), max(counts) if boxes else 0
         if all(not t.is_cuda for t in boxes + labels):
             hb = torch.cat([b.float() for b in boxes]).numpy() if boxes else np.zeros((0, 9), np.float32)
             hl = torch.cat([lb.to(torch.int32) for lb in labels]).numpy() if labels else np.zeros(0, np.int32)
@@ -126,10 +150,6 @@ class GroundTruth:
             self.labels = torch.cat([lb.to(device=device, dtype=torch.int32) for lb in labels]).contiguous()
             self.offsets, = _stage([self.offsets_host], device)
 
-    def same_as(self, boxes_list, labels_list):
-        """whether these lists hold the very objects this ground truth was built from (``from_metas`` records them)"""
-        return _same_objects(getattr(self, 'source', None), boxes_list, labels_list)
-
     @classmethod
     def from_metas(cls, img_metas, device):
         boxes, labels = [m['gt_bboxes_3d'] for m in img_metas], [m['gt_labels_3d'] for m in img_metas]
@@ -137,8 +157,27 @@ class GroundTruth:
         gt.source = (boxes, labels)          # loss() reuses this ground truth when it is handed the same objects
         return gt
 
+    def plan(self, Q, N, bg_cls_weight=0.0):
+        """the plan from the host's counts: numpy's code table and python doubles rounded once to fp32, in ONE pinned upload"""
+        k = np.arange(self.single, dtype=np.int32)
+        codes = np.array([np.tile(np.where(k < c, k, -2), N) for c in self.counts], dtype=np.int32).reshape(self.B, N * self.single)
+        num_pos = sum(min(c, Q) for c in self.counts)
+        num_neg = self.B * Q - num_pos
+        num_tgt = float(N * self.G)
+        avg = np.array([[num_pos * 1.0 + num_neg * bg_cls_weight, float(num_pos)], [num_tgt, num_tgt]], dtype=np.float32)
+        return (*_stage([codes, avg], self.offsets.device), None)
 
-class GroundTruthSlab:
+    def dn_indices(self, N):
+        G, idx = self.G, np.arange(self.G, dtype=np.int64)
+        within = idx - np.repeat(self.offsets_host[:-1].astype(np.int64), self.counts)
+        pack = np.concatenate([np.tile(idx, N), np.repeat(np.arange(self.B, dtype=np.int64), self.counts),
+                               np.concatenate([within + self.single * r for r in range(N)]) if N else idx[:0]])
+        pack, = _stage([pack], self.offsets.device)
+        return {'known_indice': pack[:N * G], 'batch_idx': pack[N * G:N * G + G], 'map_known_indice': pack[N * G + G:],
+                'known_lbs_bboxes': (self.labels.long().repeat(N), self.boxes.repeat(N, 1))}
+
+
+class GroundTruthSlab(_GroundTruthSource):
     """``GroundTruth`` at a fixed capacity: boxes [B*capacity, 9] fp32, labels [B*capacity] int32 and offsets [B+1] int32 live in ONE
     device buffer whose address never changes, so a captured graph can read them on every replay.  The samples stay concatenated
     sample-major, as every kernel reads them; the rows behind ``offsets[B]`` are capacity (zero, never read).  ``single`` is the
@@ -161,7 +200,7 @@ class GroundTruthSlab:
         self.boxes = self.buffer[o[0]:o[0] + sizes[0]].view(torch.float32).view(self.G, 9)
         self.labels = self.buffer[o[1]:o[1] + sizes[1]]
         self.offsets = self.buffer[o[2]:o[2] + sizes[2]]
-        self.counts, self.offsets_host, self.source = [0] * B, np.zeros(B + 1, dtype=np.int32), None
+        self._set_host([0] * B)
 
     def __deepcopy__(self, memo):                        # a copy of the head starts with an empty slab of its own
         return GroundTruthSlab(self.B, self.capacity, self.device)
@@ -183,15 +222,14 @@ class GroundTruthSlab:
         if total:
             host[o[0]:o[0] + total * 9].view(np.float32)[:] = torch.cat([b.float().cpu() for b in boxes]).numpy().reshape(-1)
             host[o[1]:o[1] + total] = torch.cat([lb.to(torch.int32).cpu() for lb in labels]).numpy()
-        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
-        host[o[2]:o[2] + self.B + 1] = offsets
+        host[o[2] + 1:o[2] + self.B + 1] = np.cumsum(counts)
         _upload(host, self.device, out=self.buffer)
-        self.counts, self.offsets_host, self.source = counts, offsets, (list(boxes_list), list(labels_list))
+        self._set_host(counts, (list(boxes_list), list(labels_list)))
         return self
 
-    def same_as(self, boxes_list, labels_list):
-        """whether the slab holds the very objects of these lists (the last ``update``'s)"""
-        return _same_objects(self.source, boxes_list, labels_list)
+    def plan(self, Q, N, bg_cls_weight=0.0):
+        """the plan from the device's counts: one launch, no host value follows the counts"""
+        return capacity_plan(self.offsets, self.B, Q, self.single, N, bg_cls_weight)
 
 
 class _DnQueries(torch.autograd.Function):
@@ -286,14 +324,22 @@ def _rows_view(t, last):
     return t.contiguous(), R
 
 
+def _rows_views(cls_scores, bbox_preds):
+    """(cls, box, rows per sample of both buffers) of a step's [L,B,R,NC] scores and [L,B,R,10] boxes, detached: the two views where they
+    agree on the leading dimension, two contiguous copies where they do not"""
+    R, NC = cls_scores.shape[2:]
+    cls, ld = _rows_view(cls_scores.detach(), NC)
+    box, ld2 = _rows_view(bbox_preds.detach(), 10)
+    if ld != ld2:
+        cls, box, ld = cls.contiguous(), box.contiguous(), R
+    return cls, box, ld
+
+
 def match_cost(cls_scores, bbox_preds, gt, code_weights, w_cls=2.0, w_reg=0.25, alpha=0.25, gamma=2.0):
     """cost [L,B,Q,Gmax] of all decoder layers and samples in one launch (sbev_head_match_cost)."""
     _dev(cls_scores, bbox_preds, code_weights)
     L, B, Q, NC = cls_scores.shape
-    cls, ld = _rows_view(cls_scores.detach(), NC)
-    box, ld2 = _rows_view(bbox_preds.detach(), 10)
-    if ld != ld2:
-        cls, box, ld = cls.contiguous(), box.contiguous(), Q
+    cls, box, ld = _rows_views(cls_scores, bbox_preds)
     cost = torch.empty(L, B, Q, gt.single, device=cls.device, dtype=torch.float32)
     st = _lib.load().sbev_head_match_cost(_p(cls), _p(box), ld, _p(gt.boxes), _p(gt.labels), _p(gt.offsets), _p(code_weights.contiguous()),
                                           w_cls, w_reg, alpha, gamma, L, B, Q, NC, gt.single, _p(cost), _stream())
@@ -395,10 +441,7 @@ class _SetLoss(torch.autograd.Function):
             stride = B * R
         else:
             raise RuntimeError('set_loss: codes %s is neither [B,R] nor [L,B,R]' % (tuple(codes.shape),))
-        cls, ld = _rows_view(cls_scores.detach(), NC)
-        box, ld2 = _rows_view(bbox_preds.detach(), 10)
-        if ld != ld2:
-            cls, box, ld = cls.contiguous(), box.contiguous(), R
+        cls, box, ld = _rows_views(cls_scores, bbox_preds)
         dev, lib = cls.device, _lib.load()
         loss = torch.empty(L, 2, device=dev, dtype=torch.float32)
         finite = torch.empty(L, 2, device=dev, dtype=torch.float32)
@@ -443,6 +486,12 @@ def capacity_plan(gt_offsets, B, Q, capacity, N, bg_cls_weight=0.0):
     st = _lib.load().sbev_head_capacity_plan(_p(gt_offsets), B, Q, capacity, N, float(bg_cls_weight), _p(codes), _p(avg), _p(status), _stream())
     _lib.check(st, 'sbev_head_capacity_plan')
     return codes, avg, status
+
+
+def reduce_avg(pair, sync_cls=True):
+    """a device [A_cls, A_box] averaged over the ranks where the reference does (:247,371-384): A_box always, A_cls with
+    ``sync_cls_avg_factor`` (the denoising pair: always)"""
+    return reduce_mean(pair) if sync_cls else torch.stack([pair[0], reduce_mean(pair[1:2])[0]])
 
 
 def _named(out, losses, suffix):
@@ -516,17 +565,35 @@ class SparseBEVTrainHead(SparseBEVHead):
         return (torch.rand(n, 3, device=device) * 2 - 1.0, torch.rand(n, device=device),
                 torch.randint(0, self.num_classes, (n,), device=device, dtype=torch.int32))
 
+    def gt_slab(self, B, device):
+        """the head's GroundTruthSlab for batches of B samples (gt_capacity boxes each), made on first use"""
+        device = torch.device(device)
+        if self._slab is None or self._slab.B != B or self._slab.device != device:
+            self._slab = GroundTruthSlab(B, self.gt_capacity, device)
+        return self._slab
+
+    def _forward_gt(self, batch_size, img_metas, device, dn):
+        """the ground-truth source of a forward: an empty one without denoising, the batch's own upload, or at ``gt_capacity`` the head's
+        slab refreshed in place"""
+        if not dn:
+            return GroundTruth([torch.zeros(0, 9)] * batch_size, [torch.zeros(0, dtype=torch.int32)] * batch_size, device)
+        if self.gt_capacity is None:
+            return GroundTruth.from_metas(img_metas, device)
+        slab = self.gt_slab(batch_size, device)
+        boxes, labels = [m['gt_bboxes_3d'] for m in img_metas], [m['gt_labels_3d'] for m in img_metas]
+        if not (torch.cuda.is_current_stream_capturing() and slab.same_as(boxes, labels)):
+            slab.update(boxes, labels)               # under capture the slab holds these objects already, or update() refuses
+        return slab
+
     def prepare_for_dn_input(self, batch_size, init_query_bbox, label_enc, img_metas, noise=None):
-        """:119-222 -> (query_bbox, query_feat, attn_mask, mask_dict).  ``noise``: (u_box, u_lab, new_lab) to replay a recorded case."""
+        """:119-222 -> (query_bbox, query_feat, attn_mask, mask_dict).  ``noise``: (u_box, u_lab, new_lab) to replay a recorded case.
+        The mask_dict holds pad_size (``single * N``), the source (``'gt'``) and, where the source has them, the reference's index tensors."""
         device = init_query_bbox.device
         label_w = label_enc.weight if hasattr(label_enc, 'weight') else label_enc
         dn = self.training and self.dn_enabled
-        if dn and self.gt_capacity is not None:
-            return self._prepare_at_capacity(batch_size, init_query_bbox, label_w, img_metas, noise)
-        gt = GroundTruth.from_metas(img_metas, device) if dn else GroundTruth([torch.zeros(0, 9)] * batch_size,
-                                                                              [torch.zeros(0, dtype=torch.int32)] * batch_size, device)
+        gt = self._forward_gt(batch_size, img_metas, device, dn)
         N = self.dn_group_num if dn else 1
-        if noise is None and dn and self.dn_noise is not None:
+        if noise is None and dn:
             noise = self.dn_noise
         if noise is None:
             noise = self.draw_noise(gt.G, device) if dn else (torch.zeros(0, 3, device=device), torch.zeros(0, device=device),
@@ -536,39 +603,7 @@ class SparseBEVTrainHead(SparseBEVHead):
                                      self.num_classes, self.pc_range, self.dn_bbox_noise_scale, self.dn_label_noise_scale)
         if not dn:
             return qb, qf, None, None
-        G, single = gt.G, gt.single
-        idx = np.arange(G, dtype=np.int64)
-        within = idx - np.repeat(gt.offsets_host[:-1].astype(np.int64), gt.counts)
-        pack = np.concatenate([np.tile(idx, N), np.repeat(np.arange(gt.B, dtype=np.int64), gt.counts),
-                               np.concatenate([within + single * r for r in range(N)]) if N else idx[:0]])
-        pack, = _stage([pack], device)
-        mask_dict = {'known_indice': pack[:N * G], 'batch_idx': pack[N * G:N * G + G], 'map_known_indice': pack[N * G + G:],
-                     'known_lbs_bboxes': (gt.labels.long().repeat(N), gt.boxes.repeat(N, 1)), 'pad_size': single * N,
-                     'gt': gt}
-        return qb, qf, mask, mask_dict
-
-    def gt_slab(self, B, device):
-        """the head's GroundTruthSlab for batches of B samples (gt_capacity boxes each), made on first use"""
-        device = torch.device(device)
-        if self._slab is None or self._slab.B != B or self._slab.device != device:
-            self._slab = GroundTruthSlab(B, self.gt_capacity, device)
-        return self._slab
-
-    def _prepare_at_capacity(self, batch_size, init_query_bbox, label_w, img_metas, noise):
-        """prepare_for_dn_input with ``single`` = gt_capacity: the same launch at shapes that do not follow the counts.  The mask_dict
-        holds pad_size and the slab; the index tensors of the dynamic path exist for interface parity only and are left out."""
-        device = init_query_bbox.device
-        slab = self.gt_slab(batch_size, device)
-        boxes, labels = [m['gt_bboxes_3d'] for m in img_metas], [m['gt_labels_3d'] for m in img_metas]
-        if not (torch.cuda.is_current_stream_capturing() and slab.same_as(boxes, labels)):
-            slab.update(boxes, labels)               # under capture the slab holds these objects already, or update() refuses
-        N = self.dn_group_num
-        if noise is None:
-            noise = self.dn_noise if self.dn_noise is not None else self.draw_noise(slab.G, device)
-        u_box, u_lab, new_lab = [t.to(device) for t in noise]
-        qb, qf, mask, _ = dn_prepare(init_query_bbox, label_w, slab, u_box.float(), u_lab.float(), new_lab.to(torch.int32), batch_size, N,
-                                     self.num_classes, self.pc_range, self.dn_bbox_noise_scale, self.dn_label_noise_scale)
-        return qb, qf, mask, {'pad_size': slab.single * N, 'gt': slab}
+        return qb, qf, mask, dict(gt.dn_indices(N), pad_size=gt.single * N, gt=gt)
 
     # ---- section 2: training forward ------------------------------------------------------------------------------------
     def forward(self, mlvl_feats, img_metas):
@@ -604,77 +639,37 @@ class SparseBEVTrainHead(SparseBEVHead):
             return assign_device(cost, gt, self.assign_status)
         return self._assigner(cost, gt)
 
-    def _avg(self, a_cls, a_box, device, sync_cls, sync_box):
-        """[A_cls, A_box] as a device tensor, averaged over the ranks where the reference does (:247,371-384)."""
-        t, = _stage([np.array([a_cls, a_box], dtype=np.float32)], device)
-        if sync_cls and sync_box:
-            return reduce_mean(t)
-        if sync_box:
-            t = torch.stack([t[0], reduce_mean(t[1:2])[0]])
-        return t
-
     def loss(self, gt_bboxes_list, gt_labels_list, preds_dicts, gt_bboxes_ignore=None):
+        """:405-460.  The matching pair reads the ground truth of these arguments, the denoising pair the forward's (``md['gt']``, as
+        the reference reads its mask dict).  They are one source when the forward was handed the same objects, and always at
+        ``gt_capacity``, where the slab is refreshed in place; then there is one plan."""
         assert gt_bboxes_ignore is None, '%s only supports for gt_bboxes_ignore setting to None.' % self.__class__.__name__
         all_cls, all_box = preds_dicts['all_cls_scores'], preds_dicts['all_bbox_preds']
         L, B, Q, _ = all_cls.shape
         md = preds_dicts.get('dn_mask_dict')
-        if self.gt_capacity is not None:
-            return self._loss_at_capacity(gt_bboxes_list, gt_labels_list, all_cls, all_box, md)
-        if md is not None and md['gt'].same_as(gt_bboxes_list, gt_labels_list):
-            gt = md['gt']                    # the forward's upload of the same objects
-        else:
+        at_capacity = self.gt_capacity is not None
+        gt = md['gt'] if md is not None else self.gt_slab(B, all_cls.device) if at_capacity else None
+        if not at_capacity and (gt is None or not gt.same_as(gt_bboxes_list, gt_labels_list)):
             gt = GroundTruth(gt_bboxes_list, gt_labels_list, all_cls.device)
         if gt.B != B:
             raise ValueError('ground truth of %d samples for a batch of %d' % (gt.B, B))
+        if at_capacity and not gt.same_as(gt_bboxes_list, gt_labels_list):
+            gt.update(gt_bboxes_list, gt_labels_list)
         assign = self.assign(all_cls, all_box, gt)
-        num_pos = sum(min(c, Q) for c in gt.counts)
-        num_neg = B * Q - num_pos
-        avg = self._avg(num_pos * 1.0 + num_neg * self.bg_cls_weight, float(num_pos), all_cls.device, self.sync_cls_avg_factor, True)
-        losses = set_loss(all_cls, all_box, assign, gt, self.code_weights, avg, self.loss_cls_weight, self.focal_alpha, self.focal_gamma,
-                          self.loss_bbox_weight, 1.0)
+        dgt = md['gt'] if md is not None else gt
+        N = max(md['pad_size'] // max(dgt.single, 1), 1) if md is not None else 1
+        codes, avg, status = gt.plan(Q, N, self.bg_cls_weight)
+        if status is not None:
+            self.plan_status = status
+        # other objects than the forward's: the dn pair keeps the forward's codes and factors
+        dn_codes, dn_avg = (codes, avg) if dgt is gt else dgt.plan(Q, N, self.bg_cls_weight)[:2]
+        losses = set_loss(all_cls, all_box, assign, gt, self.code_weights, reduce_avg(avg[0], self.sync_cls_avg_factor), self.loss_cls_weight,
+                          self.focal_alpha, self.focal_gamma, self.loss_bbox_weight, 1.0)
         out = {}
         if md is not None:
             dn_cls, dn_box = md['output_known_lbs_bboxes']
-            dgt, pad = md['gt'], md['pad_size']
-            single, N = dgt.single, pad // max(dgt.single, 1)
-            k = np.arange(single, dtype=np.int32)
-            codes = np.stack([np.tile(np.where(k < c, k, -2).astype(np.int32), N) for c in dgt.counts])       # prepare_for_dn_loss's gather (:224-237)
-            num_tgt = float(N * dgt.G)
-            dn_avg = self._avg(num_tgt, num_tgt, all_cls.device, True, True)
-            dn = set_loss(dn_cls, dn_box, _stage([codes], all_cls.device)[0], dgt, self.code_weights, dn_avg,
-                          self.loss_cls_weight, self.focal_alpha, self.focal_gamma, self.loss_bbox_weight, self.dn_weight)
-            out['loss_cls_dn'], out['loss_bbox_dn'] = dn[L - 1, 0], dn[L - 1, 1]
-            for i in range(L - 1):
-                out['d%d.loss_cls_dn' % i], out['d%d.loss_bbox_dn' % i] = dn[i, 0], dn[i, 1]
-        out['loss_cls'], out['loss_bbox'] = losses[L - 1, 0], losses[L - 1, 1]
-        for i in range(L - 1):
-            out['d%d.loss_cls' % i], out['d%d.loss_bbox' % i] = losses[i, 0], losses[i, 1]
-        return out
-
-    def _loss_at_capacity(self, gt_bboxes_list, gt_labels_list, all_cls, all_box, md):
-        """loss() with the ground truth in the slab: the same launches at ``single = Gmax = gt_capacity`` plus the plan launch, which
-        builds the dn codes and the averaging factors from the device's counts.  No host value here follows the counts."""
-        L, B, Q, _ = all_cls.shape
-        slab = md['gt'] if md is not None else self.gt_slab(B, all_cls.device)
-        if slab.B != B:
-            raise ValueError('ground truth of %d samples for a batch of %d' % (slab.B, B))
-        if not slab.same_as(gt_bboxes_list, gt_labels_list):
-            slab.update(gt_bboxes_list, gt_labels_list)
-        assign = self.assign(all_cls, all_box, slab)
-        N = md['pad_size'] // max(slab.single, 1) if md is not None else 1
-        codes, avg, self.plan_status = capacity_plan(slab.offsets, B, Q, slab.single, max(N, 1), self.bg_cls_weight)
-        m_avg, dn_avg = avg[0], reduce_mean(avg[1])
-        if self.sync_cls_avg_factor:
-            m_avg = reduce_mean(m_avg)
-        else:
-            m_avg = torch.stack([m_avg[0], reduce_mean(m_avg[1:2])[0]])
-        losses = set_loss(all_cls, all_box, assign, slab, self.code_weights, m_avg, self.loss_cls_weight, self.focal_alpha, self.focal_gamma,
-                          self.loss_bbox_weight, 1.0)
-        out = {}
-        if md is not None:
-            dn_cls, dn_box = md['output_known_lbs_bboxes']
-            dn = set_loss(dn_cls, dn_box, codes, slab, self.code_weights, dn_avg, self.loss_cls_weight, self.focal_alpha, self.focal_gamma,
-                          self.loss_bbox_weight, self.dn_weight)
+            dn = set_loss(dn_cls, dn_box, dn_codes, dgt, self.code_weights, reduce_avg(dn_avg[1]), self.loss_cls_weight, self.focal_alpha,
+                          self.focal_gamma, self.loss_bbox_weight, self.dn_weight)
             _named(out, dn, '_dn')
         _named(out, losses, '')
         return out

@@ -63,13 +63,14 @@ class _CapturedStep:
 
     optimizer = None
 
-    def _refuse_ranks(self, optimizer):
-        """First thing in a constructor: DDP's gradient all-reduce is not in the graph, so an in-graph optimizer would step on one
-        rank's gradients."""
-        if optimizer is not None and torch.distributed.is_available() and torch.distributed.is_initialized() \
-                and torch.distributed.get_world_size() > 1:
-            raise RuntimeError('%s: optimizer= with a process group of %d ranks: the gradient all-reduce is not in the graph (run the '
-                               'optimizer after replay() and the all-reduce)' % (type(self).__name__, torch.distributed.get_world_size()))
+    def _refuse_ranks(self, optimizer, always=None):
+        """First thing in a constructor, in a process group of more than one rank: DDP's gradient all-reduce is not in the graph, so an
+        in-graph optimizer would step on one rank's gradients; ``always`` is a step's reason to refuse such a group without one too."""
+        dist = torch.distributed
+        if (optimizer is not None or always) and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            what, why = ('', always) if optimizer is None else \
+                ('optimizer= with ', 'the gradient all-reduce is not in the graph (run the optimizer after replay() and the all-reduce)')
+            raise RuntimeError('%s: %sa process group of %d ranks: %s' % (type(self).__name__, what, dist.get_world_size(), why))
 
     def _bind_optimizer(self, optimizer, params):
         """``optimizer=``: a FusedAdamW over exactly the captured parameters becomes the tail of the step."""
@@ -228,7 +229,7 @@ class CapturedHeadTrainStep(_CapturedStep):
 
     def __init__(self, head, mlvl_feats, img_metas, warmup=3, optimizer=None):
         from .head_train import SparseBEVTrainHead
-        self._refuse_ranks(optimizer)
+        self._refuse_ranks(optimizer, always='the all-reduce of the averaging factors cannot be captured (run the eager step)')
         if not torch.is_grad_enabled():
             raise RuntimeError('CapturedHeadTrainStep: grad is disabled')
         VERSION.require_supported()
@@ -236,9 +237,6 @@ class CapturedHeadTrainStep(_CapturedStep):
             raise ValueError('CapturedHeadTrainStep: the head must be a SparseBEVTrainHead(gt_capacity=...): at a dynamic shape nothing can be replayed')
         if not (head.training and head.dn_enabled):
             raise ValueError('CapturedHeadTrainStep: the head must be in train() mode with query denoising on')
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            raise RuntimeError('CapturedHeadTrainStep: a process group of %d ranks: the all-reduce of the averaging factors cannot be captured '
-                               '(run the eager step)' % torch.distributed.get_world_size())
         self.head = head
         self.mlvl_feats = list(mlvl_feats)
         if not all(torch.is_tensor(f) and f.is_cuda and f.dtype == torch.float32 for f in self.mlvl_feats):
@@ -250,8 +248,9 @@ class CapturedHeadTrainStep(_CapturedStep):
         self._set_ground_truth([m['gt_bboxes_3d'] for m in img_metas], [m['gt_labels_3d'] for m in img_metas])
         self.ctx = DecoderContext(img_metas, self.B, self.device)          # host -> device: outside the graph
         self.noise = head.draw_noise(self.slab.G, self.device)            # static: replay() writes the next draw into these
-        self._bind_optimizer(optimizer, [p for p in head.parameters() if p.requires_grad])
-        self._leaves = [p for p in head.parameters() if p.requires_grad] + [f for f in self.mlvl_feats if f.requires_grad]
+        params = [p for p in head.parameters() if p.requires_grad]
+        self._bind_optimizer(optimizer, params)
+        self._leaves = params + [f for f in self.mlvl_feats if f.requires_grad]
         self.losses = self._capture(warmup)
         self.grads = {n: p.grad for n, p in head.named_parameters() if p.grad is not None}
         self.input_grads = {'mlvl_feats': [f.grad for f in self.mlvl_feats]}

@@ -237,6 +237,20 @@ def dn_codes(counts, N):
     return torch.stack([torch.where(k < c, k, torch.full_like(k, -2)).repeat(N) for c in counts]) if counts else torch.zeros(0, 0, dtype=torch.long)
 
 
+def host_plan(counts, Q, cap, N, bg):
+    """A step's plan restated: (codes int32 [B, N * cap], avg fp32 [2,2]) -- the numpy code table at ``single = cap`` and the two pairs
+    of averaging factors, (A_cls, A_box) of the matching loss and (A, A) of the denoising loss, as np.float32 of python doubles.  What
+    ``GroundTruth.plan`` computes on the host and ``capacity_plan`` on the device."""
+    B = len(counts)
+    k = np.arange(cap, dtype=np.int32)
+    codes = np.stack([np.tile(np.where(k < c, k, -2).astype(np.int32), N) for c in counts]).reshape(B, N * cap)
+    num_pos = sum(min(c, Q) for c in counts)
+    num_neg = B * Q - num_pos
+    num_tgt = float(N * sum(counts))
+    avg = np.array([[num_pos * 1.0 + num_neg * bg, float(num_pos)], [num_tgt, num_tgt]], dtype=np.float32)
+    return torch.from_numpy(codes), torch.from_numpy(avg)
+
+
 def loss_dict(all_cls, all_box, dn_cls, dn_box, boxes, labels, cw, N, dn_weight=1.0, **kw):
     """The head's loss dict (:290-297,434-460) from the split outputs; dn_cls None = no dn_mask_dict.  bg_cls_weight = 0."""
     L, B, Q, _ = all_cls.shape

@@ -35,16 +35,19 @@ def untouched(buf, n, sentinel):
     return bool((buf[:T.GUARD] == sentinel).all()) and bool((buf[T.GUARD + n:] == sentinel).all())
 
 
-def host_plan(counts, Q, cap, N, bg):
-    """sparsebev_amd/head_train.py's loss() restated: the numpy code table and the two `_avg` pairs as np.float32 of python doubles"""
-    B = len(counts)
-    k = np.arange(cap, dtype=np.int32)
-    codes = np.stack([np.tile(np.where(k < c, k, -2).astype(np.int32), N) for c in counts]).reshape(B, N * cap)
-    num_pos = sum(min(c, Q) for c in counts)
-    num_neg = B * Q - num_pos
-    num_tgt = float(N * sum(counts))
-    avg = np.array([[num_pos * 1.0 + num_neg * bg, float(num_pos)], [num_tgt, num_tgt]], dtype=np.float32)
-    return torch.from_numpy(codes), torch.from_numpy(avg)
+host_plan = C.host_plan
+
+
+def force_single(monkeypatch, single):
+    """the dynamic path with every ``GroundTruth.single`` forced to ``single`` (legal for its kernels while single <= G) -- patched here,
+    not in the product"""
+    init = HT.GroundTruth.__init__
+
+    def forced(self, *a, **kw):
+        init(self, *a, **kw)
+        self.single = single
+
+    monkeypatch.setattr(HT.GroundTruth, '__init__', forced)
 
 
 def raw_plan(offsets, B, Q, cap, N, bg):
@@ -217,19 +220,76 @@ def test_capacity_above_the_batch_maximum(monkeypatch):
     for k, v in ref.items():
         print('capacity %d %-16s restatement %.6f  rel err %.2e' % (CAP, k, v.item(), abs(l_cap[k].item() - v.item()) / abs(v.item())))
         assert abs(l_cap[k].item() - v.item()) < T.FUNC_TOL * abs(v.item()), (k, l_cap[k].item(), v.item())
-    # (b) the dynamic path with gt.single forced to the capacity (legal for its kernels: 7 <= G = 8) -- patched here, not in the product
-    init = HT.GroundTruth.__init__
-
-    def forced(self, *a, **kw):
-        init(self, *a, **kw)
-        self.single = CAP
-
-    monkeypatch.setattr(HT.GroundTruth, '__init__', forced)
+    # (b) the dynamic path with gt.single forced to the capacity (legal for its kernels: 7 <= G = 8)
+    force_single(monkeypatch, CAP)
     dyn = make(state, N)
     l_dyn, g_dyn, o_dyn = step(dyn, feats, metas, boxes, labels, noise)
     assert o_dyn['dn_mask_dict']['pad_size'] == CAP * N
     assert_same(l_cap, l_dyn, 'loss')
     assert_same(g_cap, g_dyn, 'gradient')
+
+
+# ---- 3b. loss() handed other objects than the forward ---------------------------------------------------------------------------
+
+def forward_on(head, feats, metas, noise):
+    head.dn_noise = tuple(t.to(DEV) for t in noise)
+    with torch.enable_grad():
+        return head(feats, metas)
+
+
+def dn_keys(losses):
+    return {k: v for k, v in losses.items() if k.endswith('_dn')}
+
+
+def test_other_objects_in_loss_dynamic_path():
+    """The matching pair reads loss()'s arguments, the dn pair keeps the forward's ground truth (md['gt']): codes, factors, boxes, labels."""
+    N = 3
+    state, feats, metas, boxes_a, labels_a = setup((5, 3))
+    boxes_b, labels_b = C.make_gt((4, 3), 10, 99)
+    head = make(state, N)
+    metas = copy.deepcopy(metas)
+    own_a = [m['gt_bboxes_3d'] for m in metas], [m['gt_labels_3d'] for m in metas]       # the very objects the forward reads
+    outs = forward_on(head, feats, metas, C.make_noise(N, 8, 10, 64))
+    plain = {k: v for k, v in outs.items() if k != 'dn_mask_dict'}
+    assert outs['dn_mask_dict']['gt'].same_as(*own_a) and not outs['dn_mask_dict']['gt'].same_as(boxes_a, labels_a)
+    with torch.enable_grad():
+        l_own, l_a = head.loss(*own_a, outs), head.loss(boxes_a, labels_a, outs)         # one source; an equal upload next to it
+        l_b, l_b_plain = head.loss(boxes_b, labels_b, outs), head.loss(boxes_b, labels_b, plain)
+    assert len(l_b) == 8 and len(l_b_plain) == 4 and not dn_keys(l_b_plain) and head.plan_status is None
+    assert_same(l_own, l_a, 'the same objects vs copies of them')
+    assert_same({k: v for k, v in l_b.items() if k not in dn_keys(l_b)}, l_b_plain, 'matching pair: the arguments')
+    assert_same(dn_keys(l_b), dn_keys(l_a), "dn pair: the forward's")
+    assert all(not torch.equal(l_b[k], l_a[k]) for k in l_b_plain)
+
+
+def test_other_objects_in_loss_capacity_path(monkeypatch):
+    """One slab, refreshed in place: both pairs read loss()'s arguments."""
+    N, CAP = 3, 7
+    state, feats, metas, boxes_a, labels_a = setup((5, 3))
+    boxes_b, labels_b = C.make_gt((4, 3), 10, 99)
+    cap = make(state, N, gt_capacity=CAP)
+    outs = forward_on(cap, feats, copy.deepcopy(metas), scatter_noise(C.make_noise(N, 8, 10, 64), (5, 3), CAP, N))
+    slab = outs['dn_mask_dict']['gt']
+    with torch.enable_grad():
+        l_a = cap.loss(boxes_a, labels_a, outs)
+        l_b = cap.loss(boxes_b, labels_b, outs)
+    assert slab is cap.gt_slab(2, DEV) and slab.same_as(boxes_b, labels_b) and slab.counts == [4, 3] and cap.plan_status.tolist() == [0]
+
+    def no_update(*a, **kw):
+        raise AssertionError('the slab holds these objects: no second update')
+
+    with monkeypatch.context() as mp, torch.enable_grad():
+        mp.setattr(slab, 'update', no_update)
+        assert_same(cap.loss(boxes_b, labels_b, outs), l_b, 'a second loss() on the same objects')
+    assert all(not torch.equal(l_b[k], l_a[k]) for k in l_b)
+    # the same predictions through the dynamic path, its md['gt'] built from B at single = CAP (7 <= G = 7)
+    force_single(monkeypatch, CAP)
+    md = dict(outs['dn_mask_dict'], gt=HT.GroundTruth(boxes_b, labels_b, DEV))
+    assert md['gt'].single == CAP and md['pad_size'] == CAP * N
+    with torch.enable_grad():
+        l_dyn = make(state, N).loss(boxes_b, labels_b, dict(outs, dn_mask_dict=md))
+    assert_same(dn_keys(l_b), dn_keys(l_dyn), 'dn pair at capacity: the arguments')
+    assert_same(l_b, l_dyn, 'both pairs')
 
 
 def test_dn_backward_at_capacity_vs_restatement():

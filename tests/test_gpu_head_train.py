@@ -425,8 +425,9 @@ def test_loss_dict_vs_reference_recording(g15, tag):
     assert local.sync_cls_avg_factor is False
     other = local.loss(c['boxes'], c['labels'], preds)
     assert sorted(other) == sorted(losses) and all(torch.equal(other[k], losses[k]) for k in losses)
-    avg = local._avg(3.0, 0.25, DEV, False, True)
-    assert avg.shape == (2,) and avg.tolist() == [3.0, 0.25] and local._avg(3.0, 0.25, DEV, True, True).tolist() == [3.0, 0.25]
+    pair, = HT._stage([np.array([3.0, 0.25], dtype=np.float32)], DEV)
+    avg = HT.reduce_avg(pair, False)
+    assert avg.shape == (2,) and avg.tolist() == [3.0, 0.25] and HT.reduce_avg(pair, True).tolist() == [3.0, 0.25]
     with pytest.raises(AssertionError):
         head.loss(c['boxes'], c['labels'], preds, gt_bboxes_ignore=[])
 

@@ -60,6 +60,39 @@ def test_train_head_capacity_constructor():
         CapturedHeadTrainStep(H.make_head(assign_on='device').train(), [], [])
 
 
+@pytest.mark.parametrize('bg', [0.0, 0.1])
+@pytest.mark.parametrize('counts,Q,N', [((0,), 36, 2), ((0, 5, 2), 36, 3), ((5,), 3, 2), ((43, 0, 17), 36, 2)],
+                         ids=['c0', 'c0-5-2', 'c5_q3', 'c43-0-17'])
+def test_host_plan_vs_restatement(counts, Q, N, bg):
+    """``GroundTruth.plan`` on the host's counts against the written-down restatement the device's plan launch is held to
+    (test_gpu_head_capacity.py), at the batch's own ``single`` and at a ``single`` above it, bit for bit."""
+    boxes, labels = C.make_gt(counts, 10, 7)
+    gt = HT.GroundTruth(boxes, labels, 'cpu')
+    assert gt.single == max(counts) and gt.counts == list(counts)
+    for single in (max(counts), max(counts) + 2):
+        gt.single = single
+        codes, avg, status = gt.plan(Q, N, bg)
+        want_codes, want_avg = C.host_plan(counts, Q, single, N, bg)
+        assert status is None and codes.dtype == torch.int32 and avg.dtype == torch.float32
+        assert codes.shape == (len(counts), N * single) and avg.shape == (2, 2)
+        assert torch.equal(codes, want_codes)
+        assert torch.equal(avg, want_avg), (avg.tolist(), want_avg.tolist())
+        assert bool((codes.view(len(counts), N, single)[:, :, max(counts):] == -2).all())
+
+
+def test_same_as_is_one_body():
+    assert HT.GroundTruth.same_as is HT.GroundTruthSlab.same_as
+    boxes, labels = C.make_gt((3, 0, 2), 10, 5)
+    assert not HT.GroundTruth(boxes, labels, 'cpu').same_as(boxes, labels)            # the plain constructor records no objects
+    gt = HT.GroundTruth.from_metas([{'gt_bboxes_3d': b, 'gt_labels_3d': l} for b, l in zip(boxes, labels)], 'cpu')
+    assert gt.same_as(boxes, labels)
+    assert not gt.same_as([b.clone() for b in boxes], labels) and not gt.same_as(boxes, [l.clone() for l in labels])
+    assert not gt.same_as(boxes[:2], labels[:2])
+    slab = HT.GroundTruthSlab(3, 4, 'cpu')
+    assert not slab.same_as(boxes, labels) and slab.update(boxes, labels).same_as(boxes, labels)
+    assert not slab.same_as([b.clone() for b in boxes], labels)
+
+
 def test_slab_host_half():
     """On a CPU device the slab packs and validates exactly as on the GPU (the upload is a plain copy): layout, counts, refusals."""
     boxes, labels = C.make_gt((3, 0, 2), 10, 5)
