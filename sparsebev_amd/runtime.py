@@ -4,6 +4,7 @@ import ctypes
 import math
 import os
 import warnings
+import weakref
 from collections import namedtuple
 
 import torch
@@ -50,6 +51,18 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _forward_cached(args, lazy, stream, prefix):
+    """sbev_decoder_forward_cached of a prepared step -> status.  ``lazy``: None, or the NCHW sources of the on-demand relayout as (values,
+    table): the levels' direct pointers (table None) or their indices into that device pointer table -- the one place that fills a LazyFeats (the
+    library takes it right after the feature pointers); ``prefix``: the step's PrefixCache or None"""
+    lz = None
+    if lazy is not None:
+        lz = LazyFeats(table=lazy[1])
+        (lz.src if lazy[1] is None else lz.index)[:len(lazy[0])] = lazy[0]
+    pfx = (ctypes.c_void_p(prefix.ptr), prefix.nbytes) if prefix is not None else (None, 0)
+    return _lib.load().sbev_decoder_forward_cached(*args[:_AFTER_FEATS], ctypes.byref(lz) if lz is not None else None, *args[_AFTER_FEATS:], stream, *pfx)
+
+
 class PrefixCache:
     """The device block of sbev_decoder_forward_cached (include/sbev_hip.h): layer 0's position encoder + in-projection, self attention
     and generated parameters read the queries and the weights only, and the reference builds the queries from two weight tensors on
@@ -60,7 +73,6 @@ class PrefixCache:
     _live = None      # weak set of every cache alive: runtime.prefix_cache() writes their force words
 
     def __init__(self, nbytes, dev):
-        import weakref
         self.nbytes, self.device = nbytes, dev
         self.buf = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
         off = (-self.buf.data_ptr()) % 256
@@ -157,13 +169,9 @@ class DecoderRuntime:
                 raise RuntimeError('sparsebev_amd runtime needs fp32 parameters on the device (call .to("cuda"))')
         pe, sa, smp, mix = layer.position_encoder, layer.self_attn, layer.sampling, layer.mixing
         att = sa.attention.attn
-        D, H = layer.embed_dims, sa.num_heads
-        pad = (-(3 * D + H)) % 4
-        with torch.no_grad():
-            attn_in_w = torch.cat([att.in_proj_weight, sa.gen_tau.weight] + ([att.in_proj_weight.new_zeros(pad, D)] if pad else []), 0).contiguous()
-            attn_in_b = torch.cat([att.in_proj_bias, sa.gen_tau.bias] + ([att.in_proj_bias.new_zeros(pad)] if pad else []), 0).contiguous()
-            samp_w = torch.cat([smp.sampling_offset.weight, smp.scale_weights.weight], 0).contiguous()
-            samp_b = torch.cat([smp.sampling_offset.bias, smp.scale_weights.bias], 0).contiguous()
+        D = layer.embed_dims
+        with torch.no_grad():               # the padded q | k | v | tau rows and the two sampling generators' rows: the layer's one recipe
+            attn_in_w, attn_in_b, samp_w, samp_b = layer.packed_train_weights()
         self._attn_in_rows = attn_in_w.shape[0]
         cb, rb, ffn = layer.cls_branch, layer.reg_branch, layer.ffn.layers
         t = dict(
@@ -291,8 +299,8 @@ class DecoderRuntime:
 
     # -- forward -----------------------------------------------------------------------------------------
     def _prepare(self, query_bbox, query_feat, pyramid, ctx, attn_mask, own_workspace=False):
-        """(args of sbev_decoder_forward, what they point into, cls, box) on the runtime's workspace; ``own_workspace``: on a graph
-        workspace whose reference the caller now holds, its key (for _release_graph_ws) as a fifth result."""
+        """(StepArgs, StepKeep, cls, box) on the runtime's workspace; ``own_workspace``: on a graph workspace whose reference the caller
+        now holds (``keep.ws_key``)."""
         sig = self._ensure_bound()
         B, Q, D = query_feat.shape
         dev = query_feat.device
@@ -317,11 +325,10 @@ class DecoderRuntime:
         feats = (ctypes.c_void_p * cfg.L)(*[f.data_ptr() for f in pyramid.levels])
         mask = attn_mask.to(device=dev, dtype=torch.uint8).contiguous() if attn_mask is not None else None
         qb, qf = query_bbox.contiguous(), query_feat.contiguous()
-        args = (ctypes.byref(cfg), ctypes.byref(self._weights), feats, _ptr(qb), _ptr(qf),
-                _ptr(ctx.time_diff), _ptr(ctx.lidar2img), _ptr(ctx.vel_div), _ptr(mask),
-                _ptr(cls), _ptr(box), ctypes.c_void_p(ws_ptr), need)
-        keep = (cfg, feats, qb, qf, mask, pyramid, ctx, ws, self._keep)
-        return (args, keep, cls, box, key) if own_workspace else (args, keep, cls, box)
+        args = StepArgs(ctypes.byref(cfg), ctypes.byref(self._weights), feats, _ptr(qb), _ptr(qf),
+                        _ptr(ctx.time_diff), _ptr(ctx.lidar2img), _ptr(ctx.vel_div), _ptr(mask),
+                        _ptr(cls), _ptr(box), ctypes.c_void_p(ws_ptr), need)
+        return args, StepKeep(cfg, feats, qb, qf, mask, pyramid, ctx, ws, self._keep, key if own_workspace else None), cls, box
 
     def _take_graph_ws(self, key, need, dev):
         """One more graph on the workspace of its (device, size, stream): ONE per size AND per stream -- graphs replayed on one stream
@@ -348,12 +355,12 @@ class DecoderRuntime:
         return int(_lib.load().sbev_decoder_launches_per_layer(ctypes.byref(cfg), ctypes.byref(self._weights)))
 
     def _eager_prefix(self, cfg, sig, mask, lazy, dev):
-        """(pointer, bytes) of the eager path's prefix cache for this call, or (None, 0).  Its header is zeroed when the weight signature,
+        """The eager path's prefix cache for this call, or None.  Its header is zeroed when the weight signature,
         the shapes, the gemm mode, the switches, pc_range, the layer count, the device or the stream are not what its contents were
         computed under, and after a forward that raised."""
         need = _prefix_cache_for(cfg, self._weights, mask, lazy, dev)
         if need == 0:
-            return None, 0
+            return None
         key = (sig, cfg.B, cfg.Q, cfg.D, cfg.T, cfg.P, cfg.G, cfg.out_points, self.mode_eff, _switch_key(), tuple(self.decoder.pc_range),
                cfg.num_layers, str(dev), torch.cuda.current_stream(dev).cuda_stream, need)
         if self._prefix is None or self._prefix.nbytes != need or self._prefix.device != dev:
@@ -362,15 +369,25 @@ class DecoderRuntime:
         elif key != self._prefix_key:
             self._prefix.reset()
         self._prefix_key = key
-        return ctypes.c_void_p(self._prefix.ptr), need
+        return self._prefix
 
-    def _step(self, args, lz, stream, prefix):
-        """sbev_decoder_forward / _lazy of ``args`` (what _prepare returned) with the prefix cache ``prefix`` = (pointer, bytes)"""
-        st = _lib.load().sbev_decoder_forward_cached(args[0], args[1], args[2], ctypes.byref(lz) if lz is not None else None, *args[3:], stream,
-                                                     prefix[0], prefix[1])
+    def _eager(self, query_bbox, query_feat, pyramid, ctx, attn_mask, finish, lazy_from=None):
+        """The eager step of ``forward`` and ``forward_lazy`` (after their pair-fault check) -> (cls, box).  ``lazy_from``: the NCHW levels
+        that ``pyramid``'s channels-last buffers are filled from on demand, else ``pyramid`` is read as it is."""
+        args, keep, cls, box = self._prepare(query_bbox, query_feat, pyramid, ctx, attn_mask)
+        lazy = None
+        if lazy_from is not None:
+            if not _lib.load().sbev_decoder_lazy_supported(args.config):
+                raise _lib.SbevError('sbev_decoder_forward_lazy does not cover this pyramid (4 groups x 64 channels; no frame ring)')
+            if not all(f.is_cuda and f.is_contiguous() and f.data_ptr() % 16 == 0 and f.dtype == pyramid.levels[l].dtype for l, f in enumerate(lazy_from)):
+                raise RuntimeError('forward_lazy needs contiguous, 16-byte aligned device NCHW levels of the buffers\' dtype')
+            lazy = ([f.data_ptr() for f in lazy_from], None)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _forward_cached(args, lazy, stream, self._eager_prefix(keep.cfg, self._sig, attn_mask, lazy is not None, query_feat.device))
         if st != 0:
             self._prefix_key = None      # whatever the failed step left: disarm before the next use
-        return st
+        _lib.check(st, 'sbev_decoder_forward' if lazy is None else 'sbev_decoder_forward_lazy')
+        return self._finished(cls, box, stream) if finish else (cls, box)
 
     def prefix_counters(self):
         """(hits, misses) summed over this runtime's live prefix caches -- the eager one and every captured step's; synchronises"""
@@ -384,16 +401,12 @@ class DecoderRuntime:
         layers -- raw, or with ``finish`` nan_to_num'ed by one more launch of this library (sbev_finish_outputs: what
         SparseBEVTransformer.forward applies, models/sparsebev_transformer.py:35-36)."""
         check_pair_faults()                 # an earlier step lost a pair hand-off: raise before anything is enqueued on top of it
-        args, _keep, cls, box = self._prepare(query_bbox, query_feat, pyramid, ctx, attn_mask)
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        st = self._step(args, None, stream, self._eager_prefix(_keep[0], self._sig, attn_mask, False, query_feat.device))
-        _lib.check(st, 'sbev_decoder_forward')
-        return self._finished(cls, box, stream) if finish else (cls, box)
+        return self._eager(query_bbox, query_feat, pyramid, ctx, attn_mask, finish)
 
-    def lazy_ok(self, mlvl_feats):
+    def lazy_ok(self, mlvl_feats, src=None):
         """whether a feature LIST qualifies for the on-demand relayout of the eager step: the switch is on, every level is a contiguous,
         16-byte aligned NCHW device tensor [B, T*6, 256, H, W] of one dtype (what StepGraphs stages), 4 groups of 64 channels"""
-        if not _STATE['lazy'] or frame_source(mlvl_feats).kind != 'list' or len(mlvl_feats) == 0:
+        if not _STATE['lazy'] or (src or frame_source(mlvl_feats)).kind != 'list' or len(mlvl_feats) == 0:
             return False
         f0 = mlvl_feats[0]
         return all(torch.is_tensor(f) and f.is_cuda and StepGraphs._relayout_ok(f) and f.dtype == f0.dtype and f.shape[2] == 256 for f in mlvl_feats) \
@@ -406,21 +419,7 @@ class DecoderRuntime:
         from . import transformer as TR
         check_pair_faults()
         pyramid = buffers if buffers is not None else TR.FeaturePyramid.empty_like_nchw(mlvl_feats)
-        args, _keep, cls, box = self._prepare(query_bbox, query_feat, pyramid, ctx, attn_mask)
-        lib = _lib.load()
-        if not lib.sbev_decoder_lazy_supported(args[0]):
-            raise _lib.SbevError('sbev_decoder_forward_lazy does not cover this pyramid (4 groups x 64 channels; no frame ring)')
-        lz = LazyFeats()
-        for l, f in enumerate(mlvl_feats):
-            if not (f.is_cuda and f.is_contiguous() and f.data_ptr() % 16 == 0 and f.dtype == pyramid.levels[l].dtype):
-                raise RuntimeError('forward_lazy needs contiguous, 16-byte aligned device NCHW levels of the buffers\' dtype')
-            lz.src[l] = f.data_ptr()
-        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        st = self._step(args, lz, stream, self._eager_prefix(_keep[0], self._sig, attn_mask, True, query_feat.device))
-        _lib.check(st, 'sbev_decoder_forward_lazy')
-        if finish:
-            cls, box = self._finished(cls, box, stream)
-        return cls, box, pyramid
+        return (*self._eager(query_bbox, query_feat, pyramid, ctx, attn_mask, finish, lazy_from=mlvl_feats), pyramid)
 
     def capture(self, query_bbox, query_feat, pyramid, ctx, attn_mask=None):
         """Record one decoder step into a hipGraph (sbev_decoder_capture) and return a DecoderGraph.  The graph reads
@@ -445,6 +444,11 @@ StepKey = namedtuple('StepKey', 'bbox feat feats mask weights device switches nu
 # The tensors of one call whose addresses travel in the step's pointer table (outs: with ``finish`` the call's own (cls, bbox), else None;
 # frames: the new frames of a frame-pool step (FrameSource.insert.frames), else None)
 StepInputs = namedtuple('StepInputs', 'bbox feat feats mask outs frames', defaults=(None,))
+# A prepared step (_prepare).  StepArgs: the leading arguments of sbev_decoder_forward / _capture in include/sbev_hip.h's order (``*args`` is the
+# call).  StepKeep: what they point into; ``ws_key``: the key of a graph workspace the caller now holds a reference of (_release_graph_ws), else None
+StepArgs = namedtuple('StepArgs', 'config weights feats query_bbox query_feat time_diff lidar2img vel_div mask cls box workspace workspace_bytes')
+StepKeep = namedtuple('StepKeep', 'cfg feats query_bbox query_feat mask pyramid ctx workspace weights ws_key')
+_AFTER_FEATS = StepArgs._fields.index('feats') + 1
 
 
 class CapturedStep:
@@ -612,11 +616,11 @@ class StepGraphs(StepBook):
             return ('nchw', tuple((tuple(f.shape), f.dtype) for f in feats)), [], True
         return ('list', tuple((f.data_ptr(), tuple(f.shape), tuple(f.stride()), f.dtype) for f in feats)), list(feats), False
 
-    def run(self, query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, finish=False):
+    def run(self, query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, finish=False, src=None):
         """(cls, box) of the graph's own output buffers (the caller clones or post-processes out of place), or None when this
         call has to take the eager path.  ``finish``: the graph's last node (sbev_finish_outputs_indirect) writes the nan_to_num'ed
         outputs into tensors allocated for THIS call, whose addresses travel in the pointer table -- nothing runs after the replay,
-        and what is returned belongs to the caller."""
+        and what is returned belongs to the caller.  ``src``: the caller's frame_source(mlvl_feats), where it has read it already."""
         rt = self.rt
         if _STATE['profile'] or not (query_bbox.is_cuda and query_bbox.is_contiguous() and query_feat.is_contiguous()):
             return None                      # (bracketing launches with HIP events needs the eager enqueue)
@@ -624,7 +628,7 @@ class StepGraphs(StepBook):
             return None
         if attn_mask is not None and not (attn_mask.is_cuda and attn_mask.dtype == torch.uint8 and attn_mask.is_contiguous() and attn_mask.data_ptr() % 16 == 0):
             return None                      # the runtime would convert it into a temporary: nothing stable to stage from
-        src = frame_source(mlvl_feats)
+        src = src or frame_source(mlvl_feats)
         if src.kind == 'list' and not all(torch.is_tensor(f) and f.is_cuda for f in mlvl_feats):
             return None
         from . import transformer as TR
@@ -695,30 +699,30 @@ class StepGraphs(StepBook):
             insert = (list(range(3, 3 + len(call.frames))), src.insert, pyramid)
         n_packed = (packed.size + 3) // 4 * 4                 # the table behind the constants, 16-byte aligned
         ctx = TR.DecoderContext.from_packed(self._with_table(packed, n_packed, staged, call), layout, ih, iw, dev)     # the graph reads constants AND table from this tensor on every replay
-        args, keep, cls, box, ws_key = rt._prepare(qb, qf, pyramid, ctx, mask, own_workspace=True)
+        args, keep, cls, box = rt._prepare(qb, qf, pyramid, ctx, mask, own_workspace=True)
         try:
             segs = [(0, qb), (1, qf)] + ([(2, mask)] if mask is not None else [])
             relayout = [(3 + l, buf) for l, buf in enumerate(pyramid.levels)] if staged else []      # (table index, graph-owned NHWC buffer)
             # the step's own prefix cache, header zeroed here: the replays' watch launch compares the staged queries with its copy
-            lazy = len(relayout) > 0 and _STATE['lazy'] and bool(_lib.load().sbev_decoder_lazy_supported(args[0]))
-            need = _prefix_cache_for(keep[0], rt._weights, mask, lazy, dev)
+            lazy = len(relayout) > 0 and _STATE['lazy'] and bool(_lib.load().sbev_decoder_lazy_supported(args.config))      # (decided once: _record is told)
+            need = _prefix_cache_for(keep.cfg, rt._weights, mask, lazy, dev)
             prefix = PrefixCache(need, dev) if need else None
-            handle = self._record(args, ctypes.c_void_p(ctx.buffer.data_ptr() + 4 * n_packed), segs, relayout, (cls, box) if call.outs is not None else None, insert,
-                                  prefix)
+            handle = self._record(args, ctypes.c_void_p(ctx.buffer.data_ptr() + 4 * n_packed), segs, relayout, lazy,
+                                  (cls, box) if call.outs is not None else None, insert, prefix)
         except BaseException:
-            rt._release_graph_ws(ws_key)
+            rt._release_graph_ws(keep.ws_key)
             raise
         # what the graph's launches read or write: its own buffers, and -- address-keyed entries only -- the caller's feature buffers
         graph = DecoderGraph(handle, (keep, qb, qf, mask, ctx, None if staged else (None if insert else call.feats, pyramid)), cls, box)
-        e = CapturedStep(graph, not staged and not src.resident, staged, ctx.buffer, n_packed, layout, (ih, iw), ws_key, prefix)
+        e = CapturedStep(graph, not staged and not src.resident, staged, ctx.buffer, n_packed, layout, (ih, iw), keep.ws_key, prefix)
         self.captured(key, e)
         return e
 
     @staticmethod
-    def _record(args, table, segs, relayout, finish, insert=None, prefix=None):
+    def _record(args, table, segs, relayout, lazy, finish, insert=None, prefix=None):
         """The step's launches under stream capture -> the instantiated graph's handle: the in-graph copies of ``segs`` (table index,
-        graph-owned buffer), the relayout of the staged levels (on demand inside the step, all fp32 levels in one launch, or one launch
-        per level), -- ``insert``: (table indices, the pyramid's pending FrameInsert, pool pyramid) -- the frame pool's new frames
+        graph-owned buffer), the relayout of the staged levels (``lazy``, _capture's decision: on demand inside the step; else all fp32
+        levels in one launch, or one launch per level), -- ``insert``: (table indices, the pyramid's pending FrameInsert, pool pyramid) -- the frame pool's new frames
         into their slots (sbev_pool_insert_frames, sources from the table), the decoder step, and -- ``finish``: the graph's (cls, box) -- the
         nan_to_num into the call's own outputs.  All on the one capture stream, in this order.  ``prefix``: the step's PrefixCache or None.
         Raises when any of it fails, with the capture ended."""
@@ -726,7 +730,6 @@ class StepGraphs(StepBook):
         side = torch.cuda.Stream(device=segs[0][1].device)
         side.wait_stream(torch.cuda.current_stream())
         sp = ctypes.c_void_p(side.cuda_stream)
-        pfx = (ctypes.c_void_p(prefix.ptr), prefix.nbytes) if prefix is not None else (None, 0)
         c_idx = (ctypes.c_int32 * len(segs))(*[i for i, _ in segs])
         c_dst = (ctypes.c_void_p * len(segs))(*[t.data_ptr() for _, t in segs])
         c_nb = (ctypes.c_int64 * len(segs))(*[t.numel() * t.element_size() for _, t in segs])
@@ -737,8 +740,7 @@ class StepGraphs(StepBook):
         ok, st_fwd = True, 0
         try:
             ok = lib.sbev_copy_indirect(table, len(segs), c_idx, c_dst, c_nb, sp) == 0
-            # on-demand relayout: no dense pass at all -- every layer moves the units its sample points marked (sbev_decoder_forward_lazy)
-            lazy = n > 0 and _STATE['lazy'] and bool(lib.sbev_decoder_lazy_supported(args[0]))
+            # ``lazy``, the on-demand relayout: no dense pass at all -- every layer moves the units its sample points marked (sbev_decoder_forward_lazy)
             multi = (not lazy and 1 < n <= MAX_LEVELS and ch % 4 == 0 and _STATE['relayout_multi']
                      and all(buf.dtype == torch.float32 and hw % 4 == 0 for (_, buf), hw in zip(relayout, hws)))
             if multi:                        # every fp32 level of the pyramid in ONE launch (the coarse levels ride in the finest one's tail)
@@ -753,14 +755,7 @@ class StepGraphs(StepBook):
                 from . import cache
                 idx, pending, pool_pyr = insert
                 ok = cache.pool_insert_frames(pending.frames, pool_pyr.levels, pending.rows, pool_pyr.n_slots, sp, pending.nhwc, table, idx, check=False) == 0
-            if lazy:
-                lz = LazyFeats()
-                lz.table = table
-                for l, (idx, _) in enumerate(relayout):
-                    lz.index[l] = idx
-                st_fwd = lib.sbev_decoder_forward_cached(args[0], args[1], args[2], ctypes.byref(lz), *args[3:], sp, *pfx) if ok else 0
-            else:
-                st_fwd = lib.sbev_decoder_forward_cached(args[0], args[1], args[2], None, *args[3:], sp, *pfx) if ok else 0
+            st_fwd = _forward_cached(args, ([idx for idx, _ in relayout], table) if lazy else None, sp, prefix) if ok else 0
             ok = ok and st_fwd == 0
             if finish is not None:
                 cls, box = finish
@@ -786,7 +781,6 @@ class _FirstSighting:
     eager for good, without a word -- ADVICE r4).  A storage's Python object lives exactly as long as some tensor uses it."""
 
     def __init__(self, tensors):
-        import weakref
         self.refs = [(weakref.ref(t.untyped_storage()), t.storage_offset(), tuple(t.shape), tuple(t.stride()), t.dtype) for t in tensors]
 
     def same(self, tensors):
@@ -822,9 +816,6 @@ class DecoderGraph:
 
 
 # The process-wide switches live in the LIBRARY (sbev_decoder_switches reports them, however each was set); Python owns only these:
-import os as _os
-
-
 class _State(dict):
     def __missing__(self, key):
         if key != 'order':
@@ -834,9 +825,9 @@ class _State(dict):
 
 # ('order' is kept for reports only -- query_order() writes it, nothing here decides by it)
 _STATE = _State(profile=0,
-                prefix_off=_os.environ.get('SBEV_NO_PREFIX_CACHE') == '1',        # prefix caches are created with their force word set
-                lazy=not _os.environ.get('SBEV_NO_SPARSE_RELAYOUT'),      # staged NCHW pyramids: on-demand relayout of the units the sample points read
-                relayout_multi=not _os.environ.get('SBEV_NO_RELAYOUT_MULTI'))      # staged fp32 NCHW pyramids: all levels in one launch (A/B switch)
+                prefix_off=os.environ.get('SBEV_NO_PREFIX_CACHE') == '1',        # prefix caches are created with their force word set
+                lazy=not os.environ.get('SBEV_NO_SPARSE_RELAYOUT'),      # staged NCHW pyramids: on-demand relayout of the units the sample points read
+                relayout_multi=not os.environ.get('SBEV_NO_RELAYOUT_MULTI'))      # staged fp32 NCHW pyramids: all levels in one launch (A/B switch)
 
 
 def _switch_key():
@@ -914,7 +905,6 @@ def _on_pair_fault():
     lib = _lib.load()
     lib.sbev_decoder_chain_pair(0)
     lib.sbev_decoder_chain_pair_faults_ack()
-    import warnings
     warnings.warn('sparsebev_amd: a pair-mode tail hand-off timed out (GPU shared / preempted?); pair mode is off for the rest of the process')
 
 

@@ -16,13 +16,16 @@ all when the neck already produces channels-last features).
 """
 import math
 import os
+import warnings
+from collections import namedtuple
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import autograd as AG
-from . import dense, ops
+from . import _lib, dense, ops
+from .runtime import GEMM_F16X3, GEMM_F16X4, GEMM_MODES, DecoderRuntime
 from .utils import DUMP, VERSION, frame_source, slot_resident
 
 try:  # optional: register with mmdet's registry when the OpenMMLab stack is present
@@ -204,7 +207,7 @@ class SparseBEVTransformerDecoderLayer(_Base):
     def packed_train_weights(self):
         """The two concatenated Linears of the differentiable path (attention in-projection | gen_tau, sampling_offset | scale_weights),
         built ONCE per decoder call and shared by its layers (the 6 layers share the parameters): 4 `cat` launches and 2 W^T transposes
-        per step instead of 24 and 12; gradients reach the parameters through the one cat node each."""
+        per step instead of 24 and 12; gradients reach the parameters through the one cat node each.  DecoderRuntime._bind binds the same four."""
         sa, smp = self.self_attn, self.sampling
         att = sa.attention.attn
         D, H = self.embed_dims, sa.num_heads
@@ -215,12 +218,12 @@ class SparseBEVTransformerDecoderLayer(_Base):
         samp_b = torch.cat([smp.sampling_offset.bias, smp.scale_weights.bias], 0)
         return in_w, in_b, samp_w, samp_b
 
-    def forward_train(self, query_bbox, query_feat, feats, attn_mask, ctx, feat_token=None, packed=None, tap=None):
+    def forward_train(self, query_bbox, query_feat, feats, attn_mask, ctx, feat_token=None, packed=None, tap=None, gemm_f16=False):
         """The same layer with every op as a differentiable node (sparsebev_amd.autograd: HIP forward + HIP backward),
         unfused where a fused inference launch would hide an activation the backward needs.  Dropout (attention
         probabilities 0.1, the two FFN dropouts 0.1 -- mmcv defaults the reference's layer is built with,
         models/sparsebev_transformer.py:125,202) is active like in the reference's train() mode; set ``self.self_attn.attn_drop``
-        / ``self.ffn_drop`` to 0 for deterministic gradients."""
+        / ``self.ffn_drop`` to 0 for deterministic gradients.  ``gemm_f16``: the decoder's GEMM mode is an fp16 one (autograd.AdaptiveMixing)."""
         pe, sa, smp, mix = self.position_encoder, self.self_attn, self.sampling, self.mixing
         att = sa.attention.attn
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (sa.attn_drop > 0 or self.ffn_drop > 0) else 0
@@ -241,7 +244,7 @@ class SparseBEVTransformerDecoderLayer(_Base):
         # adaptive mixing (+ identity), norm2
         x = AG.layer_norm(AG.AdaptiveMixing.apply(sampled, x, mix.parameter_generator.weight, mix.parameter_generator.bias,
                                                   mix.out_proj.weight, mix.out_proj.bias, mix.out_points, self.recompute_mixing,
-                                                  getattr(self, 'train_gemm_f16', False), *tk),
+                                                  gemm_f16, *tk),
                           self.norm2.weight, self.norm2.bias, tap=tap)
         # FFN (+ identity), norm3
         f0, f1 = self.ffn.layers[0][0], self.ffn.layers[1]
@@ -475,6 +478,11 @@ class _Finished(tuple):
     """(cls, bbox) that already went through the runtime's nan_to_num launch (sbev_finish_outputs) and belong to the caller."""
 
 
+# Which way one decoder call goes (SparseBEVTransformerDecoder._route).  ``path``: 'train', 'layerwise' or 'runtime'; ``graphs``: the runtime call
+# may try a replay (StepGraphs.run); ``src``: the call's one reading of where its frames live (utils.FrameSource); ``demoted``: see _route
+DecoderRoute = namedtuple('DecoderRoute', 'path graphs src demoted')
+
+
 class SparseBEVTransformerDecoder(_Base):
     """models/sparsebev_transformer.py:41-101 (one shared layer applied num_layers times)."""
 
@@ -501,73 +509,75 @@ class SparseBEVTransformerDecoder(_Base):
         self.decoder_layer = SparseBEVTransformerDecoderLayer(embed_dims, num_frames, num_points, num_levels,
                                                               num_classes, code_size, pc_range=pc_range)
 
-    def _split_gemm_covers(self, rows):
-        """whether csrc/gemm_bf16s.hip covers this layer's generator / out-projection shapes (N % 256 == 0, K % 32 == 0, 256 columns out)"""
-        from . import _lib
-        mix = self.decoder_layer.mixing
-        pg, op = mix.parameter_generator.weight, mix.out_proj.weight
-        lib = _lib.load()
-        return bool(lib.sbev_linear_bf16s_gen_ok(rows, pg.shape[0], pg.shape[1]) and lib.sbev_linear_bf16s_out_ok(rows, op.shape[0], op.shape[1]))
-
     @torch.no_grad()
     def init_weights(self):
         self.decoder_layer.init_weights()
+
+    def _route(self, query_bbox, query_feat, mlvl_feats, layerwise=False):
+        """The DecoderRoute of a call, decided here and nowhere else -- host only (no library call, nothing read from the device)."""
+        src = frame_source(mlvl_feats)
+        needs_grad = torch.is_grad_enabled() and (query_bbox.requires_grad or query_feat.requires_grad
+                                                  or any(p.requires_grad for p in self.parameters())
+                                                  or any(torch.is_tensor(f) and f.requires_grad
+                                                         for f in (mlvl_feats if isinstance(mlvl_feats, (list, tuple)) else ())))
+        # eval() under enabled grad (a caller that forgot torch.no_grad()): inputs the autograd path cannot take -- the online
+        # frame ring / keyed frame pool, bf16 feature storage -- run the inference runtime with a one-time warning instead of raising
+        demoted = needs_grad and not self.training and (src.resident or any(
+            torch.is_tensor(f) and f.dtype != torch.float32 for f in (mlvl_feats if src.kind == 'list' else mlvl_feats.levels)))
+        if demoted and not getattr(self, '_warned_no_grad', False):
+            warnings.warn('sparsebev_amd: eval-mode call with grad enabled on ring / bf16 features: running the inference '
+                          'runtime (outputs carry no grad_fn); wrap inference in torch.no_grad()')
+            self._warned_no_grad = True
+        path = 'train' if needs_grad and not demoted else 'layerwise' if layerwise or DUMP.enabled else 'runtime'      # (training ignores ``layerwise``)
+        return DecoderRoute(path, path == 'runtime' and self.static_graph and query_bbox.dtype == query_feat.dtype == torch.float32, src, demoted)
+
+    def _gemm_mode_code(self, rows=None):
+        """``self.gemm_mode`` -- a name of runtime.GEMM_MODES or its code -- as the code.  With ``rows`` (the runtime path, B * Q) an unknown mode
+        raises, and a split mode csrc/gemm_bf16s.hip does not cover at the layer's shapes (N % 256 == 0, K % 32 == 0, 256 columns out) runs 'f32'."""
+        mode = GEMM_MODES.get(self.gemm_mode, self.gemm_mode)
+        if rows is not None and mode not in GEMM_MODES.values():
+            raise ValueError('gemm_mode %r: expected one of %s' % (self.gemm_mode, sorted(GEMM_MODES)))
+        if rows is not None and mode >= 2:
+            lib, mix = _lib.load(), self.decoder_layer.mixing
+            pg, op = mix.parameter_generator.weight, mix.out_proj.weight
+            if not (lib.sbev_linear_bf16s_gen_ok(rows, pg.shape[0], pg.shape[1]) and lib.sbev_linear_bf16s_out_ok(rows, op.shape[0], op.shape[1])):
+                mode = 0                        # (the exact kernels: same arithmetic class)
+        return mode
 
     def forward(self, query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, layerwise=False, _may_alias=False, _finish=False):
         """Default: the C++ runtime enqueues all layers from one call (csrc/decoder.hip); a caller that passes the SAME
         tensors again (a serving loop refreshing its inputs in place) gets the whole step -- feature relayout + 6 layers -- as
         ONE hipGraph replay from the second identical call on (``static_graph``; runtime.StepGraphs).  ``layerwise=True``
         (and the DUMP debug taps) run the same kernels one Python call at a time -- the path the per-op tests use."""
-        B = query_bbox.shape[0]
-        inference = not (torch.is_grad_enabled() and (query_bbox.requires_grad or query_feat.requires_grad
-                                                      or any(p.requires_grad for p in self.parameters())
-                                                      or any(torch.is_tensor(f) and f.requires_grad
-                                                             for f in (mlvl_feats if isinstance(mlvl_feats, (list, tuple)) else ()))))
-        if not inference and not self.training:
-            # eval() under enabled grad (a caller that forgot torch.no_grad()): inputs the autograd path cannot take -- the online
-            # frame ring / keyed frame pool, bf16 feature storage -- run the inference runtime with a one-time warning instead of raising
-            src = frame_source(mlvl_feats)
-            lv = mlvl_feats if src.kind == 'list' else mlvl_feats.levels
-            if src.resident or any(torch.is_tensor(f) and f.dtype != torch.float32 for f in lv):
-                if not getattr(self, '_warned_no_grad', False):
-                    import warnings
-                    warnings.warn('sparsebev_amd: eval-mode call with grad enabled on ring / bf16 features: running the inference '
-                                  'runtime (outputs carry no grad_fn); wrap inference in torch.no_grad()')
-                    self._warned_no_grad = True
-                inference = True
-        if inference and not (layerwise or DUMP.enabled):
-            from .runtime import DecoderRuntime, GEMM_MODES
-            mode = GEMM_MODES.get(self.gemm_mode, self.gemm_mode)
-            if mode not in GEMM_MODES.values():
-                raise ValueError('gemm_mode %r: expected one of %s' % (self.gemm_mode, sorted(GEMM_MODES)))
-            if mode >= 2 and not self._split_gemm_covers(B * query_bbox.shape[1]):
-                mode = 0                        # shapes outside the split kernels' coverage: the exact kernels (same arithmetic class)
+        route = self._route(query_bbox, query_feat, mlvl_feats, layerwise)
+        if route.path == 'runtime':
+            mode = self._gemm_mode_code(query_bbox.shape[0] * query_bbox.shape[1])
             if self._runtime is None or self._runtime.gemm_mode != mode or self._runtime.overlap != self.overlap:
                 self._runtime = DecoderRuntime(self, mode, self.overlap)
-            if self.static_graph and query_bbox.dtype == torch.float32 and query_feat.dtype == torch.float32:
-                # _finish (SparseBEVTransformer.forward): the outputs come back nan_to_num'ed in tensors of this call's own, written by
-                # the step's last launch -- no torch kernel runs on the inference step
-                out = self._runtime.step_graphs.run(query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, finish=_finish)
-                if out is not None:
-                    if _finish:
-                        return _Finished(out)
-                    return out if _may_alias else (out[0].clone(), out[1].clone())
-        if inference and frame_source(mlvl_feats).insert is not None:
+        if route.graphs:
+            # _finish (SparseBEVTransformer.forward): the outputs come back nan_to_num'ed in tensors of this call's own, written by
+            # the step's last launch -- no torch kernel runs on the inference step
+            out = self._runtime.step_graphs.run(query_bbox, query_feat, mlvl_feats, attn_mask, img_metas, finish=_finish, src=route.src)
+            if out is not None:
+                if _finish:
+                    return _Finished(out)
+                return out if _may_alias else (out[0].clone(), out[1].clone())
+        if route.path != 'train' and route.src.insert is not None:
             # a frame-pool step (cache.FramePool.step) that is not replayed -- first sighting, refused capture, graphs off, launch profiling,
             # layerwise, DUMP: the new frames go into their slots now, ahead of the eager work (a replayed step does it inside the graph)
             mlvl_feats.materialise()
-        ctx = DecoderContext(img_metas, B, query_bbox.device)
+        ctx = DecoderContext(img_metas, query_bbox.shape[0], query_bbox.device)
         query_bbox = query_bbox.float().contiguous()
         query_feat = query_feat.float().contiguous()
-        if inference and not (layerwise or DUMP.enabled) and self._runtime.lazy_ok(mlvl_feats):
+        if route.path == 'runtime' and self._runtime.lazy_ok(mlvl_feats, route.src):
             # the eager step on the reference's NCHW lists (first sighting of a shape, graphs off, launch profiling): on-demand relayout
             # too -- only the feature units the sample points read are moved (runtime.forward_lazy; bit-identical to the dense pass)
             out = self._runtime.forward_lazy(query_bbox, query_feat, list(mlvl_feats), ctx, attn_mask, finish=_finish)[:2]
             return _Finished(out) if _finish else out
-        feats = FeaturePyramid(mlvl_feats) if frame_source(mlvl_feats).kind == 'list' else mlvl_feats   # FeaturePyramid / cache.RingPyramid / cache.PoolPyramid pass through
-        if not inference:
+        feats = FeaturePyramid(mlvl_feats) if route.src.kind == 'list' else mlvl_feats   # FeaturePyramid / cache.RingPyramid / cache.PoolPyramid pass through
+        if route.path == 'train':
             return self.forward_differentiable(query_bbox, query_feat, mlvl_feats, feats, attn_mask, ctx)
-        if not (layerwise or DUMP.enabled):
+        if route.path == 'runtime':
             out = self._runtime.forward(query_bbox, query_feat, feats, ctx, attn_mask, finish=_finish)
             return _Finished(out) if _finish else out
         with torch.no_grad():
@@ -593,8 +603,7 @@ class SparseBEVTransformerDecoder(_Base):
         orig = [f for f in mlvl_feats if torch.is_tensor(f)] if isinstance(mlvl_feats, (list, tuple)) else []
         token = AG.feature_token(feats, orig)       # ONE node hands the shared feature-gradient buffers to autograd (or None)
         layer = self.decoder_layer
-        from .runtime import GEMM_MODES, GEMM_F16X3, GEMM_F16X4
-        layer.train_gemm_f16 = GEMM_MODES.get(self.gemm_mode, self.gemm_mode) in (GEMM_F16X3, GEMM_F16X4)     # autograd.AdaptiveMixing
+        gemm_f16 = self._gemm_mode_code() in (GEMM_F16X3, GEMM_F16X4)      # (no error and no coverage rule here: autograd.AdaptiveMixing has its own)
         saved = (layer.self_attn.attn_drop, layer.ffn_drop)
         if not self.training:
             layer.self_attn.attn_drop, layer.ffn_drop = 0.0, 0.0
@@ -605,7 +614,7 @@ class SparseBEVTransformerDecoder(_Base):
             # (the packed q | k | v | tau and sampling tensors too: their gradient reaches the parameters through the one cat node each)
             tap = AG.Tap([p for p in layer.parameters()] + [t for t in packed if t.requires_grad]) if self.tap_param_grads else None
             for i in range(self.num_layers):
-                query_feat, cls_score, bbox_pred = layer.forward_train(query_bbox, query_feat, feats, attn_mask, ctx, token, packed, tap)
+                query_feat, cls_score, bbox_pred = layer.forward_train(query_bbox, query_feat, feats, attn_mask, ctx, token, packed, tap, gemm_f16=gemm_f16)
                 query_bbox = bbox_pred.detach()
                 cls_scores.append(cls_score)
                 bbox_preds.append(bbox_pred)
