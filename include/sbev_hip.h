@@ -216,6 +216,17 @@ int sbev_sampling_front(const float* query_bbox, const float* offset, int64_t ld
 int sbev_linear_f32(const float* X, const float* W, const float* bias, const float* residual, float* Y,
                     int64_t M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldy, int relu,
                     sbev_stream_t stream);
+/* Which kernel sbev_linear_f32 launches for a call (a pure host function; the launcher switches on it): has_residual = residual != NULL,
+ * y_bias_aligned = Y and a non-NULL bias are 16-byte aligned.  SBEV_EINVAL for M, N or K < 1 or ldy < N. */
+enum sbev_linear_path {
+    SBEV_LINEAR_STRIP = 0,     /* K == 256, N % 128 == 0, N >= 24576, ldy % 4 == 0, aligned, no residual: W strips stationary in registers */
+    SBEV_LINEAR_RAGGED64 = 1,  /* K % 32 != 0: 64 x 64 tiles, the K tail staged element by element */
+    SBEV_LINEAR_BIG128 = 2,    /* at least 256 tiles of 128 x 128 */
+    SBEV_LINEAR_SMALL256 = 3,  /* K == 256: 32 x 32 tiles, K split over the 4 waves */
+    SBEV_LINEAR_SMALL512 = 4,  /* K == 512: the same */
+    SBEV_LINEAR_TILE64 = 5     /* every other K % 32 == 0: 64 x 64 tiles */
+};
+int sbev_linear_f32_path(int64_t M, int N, int K, int64_t ldy, int has_residual, int y_bias_aligned);
 
 /*
  * Up to 3 independent small Linear layers (K = 256 or 512, same K) in ONE launch, e.g. the classification and the
@@ -241,6 +252,16 @@ int sbev_linear_splitk_f32(const float* X, const float* W, const float* bias, co
                            const float* ln_w, const float* ln_b, float ln_eps, float* Y,
                            int64_t M, int N, int K, int64_t ldx, int64_t ldw, int relu,
                            int splits, float* workspace, sbev_stream_t stream);
+/* Which kernel writes the partial slabs of sbev_linear_splitk_f32 for a call, and into *used (may be NULL) how many slabs the reducer
+ * then sums (a pure host function; the launcher switches on it; reads the SBEV_NO_SPLIT_FOLD switch as the launcher does).
+ * SBEV_EINVAL for M, N, K or splits < 1. */
+enum sbev_linear_splitk_path_id {
+    SBEV_SPLITK_REGTILE_FOLD2 = 0,    /* N % 128 == 0, K % 32 == 0, K >= 2048, splits <= K / 32 and even: register tiles, pairs of splits summed */
+    SBEV_SPLITK_REGTILE_FOLD1 = 1,    /* the same with an odd splits: one slab per split */
+    SBEV_SPLITK_SPLIT128 = 2,         /* every other K % 32 == 0: 128 x 128 tiles x ceil(K / (32 ceil(K / splits / 32))) <= splits slabs */
+    SBEV_SPLITK_SPLIT128_RAGGED = 3   /* K % 32 != 0: the same tiles, the K tail staged element by element */
+};
+int sbev_linear_splitk_path(int64_t M, int N, int K, int splits, int32_t* used);
 
 /* Row LayerNorm (+ optional ReLU) (+ optional add_after [M,N], e.g. query_feat + position encoding, :167) of X [M,N],
  * N % 4 == 0, N <= 1024.

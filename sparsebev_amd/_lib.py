@@ -181,6 +181,8 @@ SIGNATURES = {
                          + [_vp, _vp, _vp]),
     'sbev_profile_read': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int]),
     'sbev_linear_splitk_plan': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'sbev_linear_f32_path': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
+    'sbev_linear_splitk_path': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p]),
     'sbev_linear_group_f32': (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
     'sbev_copy_widen_f32': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int64, _vp]),
     'sbev_msmv_buffer_taps': (ctypes.c_int, [ctypes.c_int]),

@@ -546,14 +546,14 @@ int launch_ln_and_linear(const float* X, const float* ln_w, const float* ln_b, f
     PairArgs p{};
     p.kind_a = PAIR_GEMM; p.kind_b = PAIR_REDUCE;       // the GEMM tiles first: they are the longer workgroups
     p.gemm = GemmArgs{Xg, W, bias, nullptr, Yg, M, Ng, K, K, K, Ng, K, relu};
-    p.red = ReduceArgs{X, nullptr, nullptr, ln_w, ln_b, nullptr, Yln, M, N, 1, ln_relu, eps};
+    p.red = ReduceArgs{X, nullptr, nullptr, ln_w, ln_b, nullptr, Yln, M, N, 1, 0, eps, ln_relu};
     return launch_pair(p, s, "sbev_decoder (LayerNorm || Linear)");
 }
 int launch_ln_and_refine(const float* X, const float* ln_w, const float* ln_b, float eps, int ln_relu, float* Yln, int64_t M, int N,
                          const float* bbox, const float* reg, const float* vel_div, float* out, int Q, int code, hipStream_t s) {
     PairArgs p{};
     p.kind_a = PAIR_REDUCE; p.kind_b = PAIR_REFINE;
-    p.red = ReduceArgs{X, nullptr, nullptr, ln_w, ln_b, nullptr, Yln, M, N, 1, ln_relu, eps};
+    p.red = ReduceArgs{X, nullptr, nullptr, ln_w, ln_b, nullptr, Yln, M, N, 1, 0, eps, ln_relu};
     p.refine = sbev_ops::MiscArgs{bbox, reg, vel_div, out, M, Q, code};
     return launch_pair(p, s, "sbev_decoder (LayerNorm || refine_bbox)");
 }
@@ -568,6 +568,20 @@ int launch_linear_and_lin3(const float* Xg, const float* W, const float* bias, f
 }
 }  // namespace sbev
 
+// Which kernel sbev_linear_f32 launches: the one place that decides it (the launcher below switches on the result).
+extern "C" int sbev_linear_f32_path(int64_t M, int N, int K, int64_t ldy, int has_residual, int y_bias_aligned) {
+    SBEV_REQUIRE(M >= 1 && N >= 1 && K >= 1 && ldy >= N, "sbev_linear_f32_path: bad sizes M=%lld N=%d K=%d ldy=%lld", (long long)M, N, K,
+                 (long long)ldy);
+    // parameter-generator shape: W strips stationary in registers, all rows stream past (see the kernel's header)
+    if (K == 256 && N % 128 == 0 && N / 128 >= 192 && M < (1 << 24) && ldy % 4 == 0 && y_bias_aligned && !has_residual)
+        return SBEV_LINEAR_STRIP;
+    if (K % BK != 0) return SBEV_LINEAR_RAGGED64;     // slow path (never taken by the decoder: its K are 256 / 512 / 32768)
+    if (((M + 127) / 128) * ((N + 127) / 128) >= 256) return SBEV_LINEAR_BIG128;      // enough 128x128 tiles to fill the 256 CUs
+    if (K == 256) return SBEV_LINEAR_SMALL256;        // the decoder's small linears: 32x32 tiles, K split over the 4 waves
+    if (K == 512) return SBEV_LINEAR_SMALL512;
+    return SBEV_LINEAR_TILE64;
+}
+
 extern "C" int sbev_linear_f32(const float* X, const float* W, const float* bias, const float* residual, float* Y,
                                int64_t M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldy, int relu,
                                sbev_stream_t stream) {
@@ -581,28 +595,37 @@ extern "C" int sbev_linear_f32(const float* X, const float* W, const float* bias
     const long long big = ((M + 127) / 128) * ((N + 127) / 128);
     SBEV_REQUIRE(big <= 0x3fffffffLL, "sbev_linear_f32: too many tiles");
     const long long small = ((M + 63) / 64) * ((N + 63) / 64);
-    if (K == 256 && N % 128 == 0 && N / 128 >= 192 && M < (1 << 24) && ldy % 4 == 0 && ((uintptr_t)Y & 15) == 0 &&
-        (!bias || ((uintptr_t)bias & 15) == 0) && !residual) {
-        // parameter-generator shape: W strips stationary in registers, all rows stream past (see the kernel's header)
-        hipEvent_t e0, e1;
-        const bool prof = sbev::profile_begin(s, &e0, &e1, 1);
-        if (relu)
-            hipLaunchKernelGGL(gemm_nt_f32_strip_kernel<true>, dim3((unsigned)(N / 128)), dim3(256), 0, s, a);
-        else
-            hipLaunchKernelGGL(gemm_nt_f32_strip_kernel<false>, dim3((unsigned)(N / 128)), dim3(256), 0, s, a);
-        if (prof) sbev::profile_end(s, e0, e1, 1);
-    } else if (K % BK != 0) {  // slow path (never taken by the decoder: its K are 256 / 512 / 32768)
-        hipLaunchKernelGGL((gemm_nt_f32_kernel<false, 1, 1, true>), dim3((unsigned)small), dim3(256), 0, s, a);
-    } else if (big >= 256) {   // enough 128x128 tiles to fill the 256 CUs
-        hipLaunchKernelGGL((gemm_nt_f32_kernel<false, 2, 2, false>), dim3((unsigned)big), dim3(256), 0, s, a);
-    } else if (K == 256 || K == 512) {   // the decoder's small linears: 32x32 tiles, K split over the 4 waves
-        const long long t32 = ((M + 31) / 32) * ((N + 31) / 32);
-        if (K == 256)
+    const long long t32 = ((M + 31) / 32) * ((N + 31) / 32);
+    const int aligned = ((uintptr_t)Y & 15) == 0 && (!bias || ((uintptr_t)bias & 15) == 0);
+    const int path = sbev_linear_f32_path(M, N, K, ldy, residual != nullptr, aligned);
+    switch (path) {
+        case SBEV_LINEAR_STRIP: {
+            hipEvent_t e0, e1;
+            const bool prof = sbev::profile_begin(s, &e0, &e1, 1);
+            if (relu)
+                hipLaunchKernelGGL(gemm_nt_f32_strip_kernel<true>, dim3((unsigned)(N / 128)), dim3(256), 0, s, a);
+            else
+                hipLaunchKernelGGL(gemm_nt_f32_strip_kernel<false>, dim3((unsigned)(N / 128)), dim3(256), 0, s, a);
+            if (prof) sbev::profile_end(s, e0, e1, 1);
+            break;
+        }
+        case SBEV_LINEAR_RAGGED64:
+            hipLaunchKernelGGL((gemm_nt_f32_kernel<false, 1, 1, true>), dim3((unsigned)small), dim3(256), 0, s, a);
+            break;
+        case SBEV_LINEAR_BIG128:
+            hipLaunchKernelGGL((gemm_nt_f32_kernel<false, 2, 2, false>), dim3((unsigned)big), dim3(256), 0, s, a);
+            break;
+        case SBEV_LINEAR_SMALL256:
             hipLaunchKernelGGL((gemm_nt_f32_small_kernel<8>), dim3((unsigned)t32), dim3(256), 0, s, a);
-        else
+            break;
+        case SBEV_LINEAR_SMALL512:
             hipLaunchKernelGGL((gemm_nt_f32_small_kernel<16>), dim3((unsigned)t32), dim3(256), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((gemm_nt_f32_kernel<false, 1, 1, false>), dim3((unsigned)small), dim3(256), 0, s, a);
+            break;
+        case SBEV_LINEAR_TILE64:
+            hipLaunchKernelGGL((gemm_nt_f32_kernel<false, 1, 1, false>), dim3((unsigned)small), dim3(256), 0, s, a);
+            break;
+        default:
+            return path;        // a refusal of sbev_linear_f32_path, its message set
     }
     return sbev::check_launch("sbev_linear_f32");
 }
@@ -693,18 +716,40 @@ extern "C" int64_t sbev_linear_splitk_workspace(int64_t M, int N, int splits) {
     return (int64_t)sizeof(float) * M * N * (splits > 0 ? splits : 0);
 }
 
+namespace {
+// K range of one slab of the 128 x 128 split-K tiles: ceil(K / splits) rounded up to whole K steps
+inline int split128_k_per_split(int K, int splits) { return ((K + splits - 1) / splits + BK - 1) / BK * BK; }
+}  // namespace
+
+// Which kernel the GEMM half of sbev_linear_splitk_f32 launches and how many slabs it writes: the one place that decides
+// it (launch_splitk_slabs below switches on the result).
+extern "C" int sbev_linear_splitk_path(int64_t M, int N, int K, int splits, int32_t* used) {
+    SBEV_REQUIRE(M >= 1 && N >= 1 && K >= 1 && splits >= 1, "sbev_linear_splitk_path: bad sizes M=%lld N=%d K=%d splits=%d", (long long)M,
+                 N, K, splits);
+    if (regtile_ok(M, N, K) && splits <= K / 32) {
+        const int fold = sbev::regtile_fold(splits);      // gemm_regtile.hip (reads the SBEV_NO_SPLIT_FOLD switch)
+        if (used) *used = splits / fold;
+        return fold == 2 ? SBEV_SPLITK_REGTILE_FOLD2 : SBEV_SPLITK_REGTILE_FOLD1;
+    }
+    const int kps = split128_k_per_split(K, splits);
+    if (used) *used = (K + kps - 1) / kps;
+    return K % BK != 0 ? SBEV_SPLITK_SPLIT128_RAGGED : SBEV_SPLITK_SPLIT128;
+}
+
 namespace sbev {
 // the GEMM half of sbev_linear_splitk_f32: *used partial slabs [used, M, N] in `workspace`, no reduction (the row-chain
 // tail kernel of the decoder sums them in its prologue)
 int launch_splitk_slabs(const float* X, const float* W, int64_t M, int N, int K, int64_t ldx, int64_t ldw, int splits,
                         float* workspace, int* used, hipStream_t s) {
-    if (regtile_ok(M, N, K) && splits <= K / 32) return launch_splitk_regtile(X, W, workspace, M, N, K, ldx, ldw, splits, used, s);
-    int kps = (K + splits - 1) / splits;
-    kps = (kps + BK - 1) / BK * BK;
-    *used = (K + kps - 1) / kps;
-    GemmArgs a{X, W, nullptr, nullptr, workspace, M, N, K, ldx, ldw, (long long)N, kps, 0};
+    int32_t slabs = 0;
+    const int path = sbev_linear_splitk_path(M, N, K, splits, &slabs);
+    if (path < 0) return path;      // a refusal, its message set
+    if (path == SBEV_SPLITK_REGTILE_FOLD2 || path == SBEV_SPLITK_REGTILE_FOLD1)
+        return launch_splitk_regtile(X, W, workspace, M, N, K, ldx, ldw, splits, path == SBEV_SPLITK_REGTILE_FOLD2 ? 2 : 1, used, s);
+    *used = slabs;
+    GemmArgs a{X, W, nullptr, nullptr, workspace, M, N, K, ldx, ldw, (long long)N, split128_k_per_split(K, splits), 0};
     const long long tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    if (K % BK != 0)
+    if (path == SBEV_SPLITK_SPLIT128_RAGGED)
         hipLaunchKernelGGL((gemm_nt_f32_kernel<true, 2, 2, true>), dim3((unsigned)tiles, 1, (unsigned)*used), dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL((gemm_nt_f32_kernel<true, 2, 2, false>), dim3((unsigned)tiles, 1, (unsigned)*used), dim3(256), 0, s, a);
@@ -757,7 +802,7 @@ extern "C" int sbev_layer_norm_f32(const float* X, const float* ln_w, const floa
     SBEV_REQUIRE(M >= 0 && N >= 4 && N % 4 == 0 && N <= 1024, "sbev_layer_norm_f32: need N %% 4 == 0, N <= 1024 (N=%d)", N);
     if (M == 0) return SBEV_OK;
     SBEV_REQUIRE(X && Y && ln_w && ln_b, "sbev_layer_norm_f32: null pointer");
-    ReduceArgs r{X, nullptr, nullptr, ln_w, ln_b, add_after, Y, M, N, 1, relu, eps};
+    ReduceArgs r{X, nullptr, nullptr, ln_w, ln_b, add_after, Y, M, N, 1, 0, eps, relu};
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), r);
     return sbev::check_launch("sbev_layer_norm_f32");
 }

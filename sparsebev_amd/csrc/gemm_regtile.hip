@@ -139,11 +139,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 }  // namespace
 
 namespace sbev {
-int launch_splitk_regtile(const float* X, const float* W, float* slabs, int64_t M, int N, int K, int64_t ldx, int64_t ldw,
-                          int splits, int* slabs_written, hipStream_t stream) {
-    SBEV_REQUIRE((long long)(K / 32) * (splits + 1) < 0x7fffffffLL, "sbev_linear_splitk_f32: K * splits too large");
+// 2: pairs of adjacent K splits are summed inside the kernel (splits / 2 slabs come out), 1: every split writes its own slab
+int regtile_fold(int splits) {
     static const bool no_fold = getenv("SBEV_NO_SPLIT_FOLD") != nullptr;       // A/B switch
-    const int fold = (splits % 2 == 0 && !no_fold) ? 2 : 1;
+    return (splits % 2 == 0 && !no_fold) ? 2 : 1;
+}
+
+int launch_splitk_regtile(const float* X, const float* W, float* slabs, int64_t M, int N, int K, int64_t ldx, int64_t ldw,
+                          int splits, int fold, int* slabs_written, hipStream_t stream) {
+    SBEV_REQUIRE((long long)(K / 32) * (splits + 1) < 0x7fffffffLL, "sbev_linear_splitk_f32: K * splits too large");
+    SBEV_REQUIRE(fold == 1 || (fold == 2 && splits % 2 == 0), "sbev_linear_splitk_f32: fold=%d with splits=%d", fold, splits);
     *slabs_written = splits / fold;
     RegTileArgs t{X, W, slabs, M, N, K, ldx, ldw, (int)((M + TROWS - 1) / TROWS), N / 128, splits, K / 32, 0u, fold};
     const long long tasks = (long long)t.rgs * t.cgs * splits;

@@ -15,12 +15,14 @@ struct ReduceArgs {
     const float* post;   // [M, N] or null: added after LayerNorm / ReLU  (x = query_feat + pos-encoding form)
     float* Y;            // [M, N]
     long long M;
-    int N, splits, relu;
+    int N, splits;
+    int relu;            // max(., 0) after the bias, BEFORE the residual (the Linear's activation)
     float eps;
+    int ln_relu = 0;     // max(., 0) after LayerNorm, before `post` (nn.LayerNorm + nn.ReLU); needs ln_w
 };
 
 // one wave per output row (N <= 1024, N % 4 == 0): sum the split-K slabs, + bias, (+ residual), optional
-// LayerNorm over the row (two-pass in registers), optional ReLU.
+// LayerNorm over the row (two-pass in registers):  Y = relu'?( LN?( relu?(sum + bias) + res ) ) + post  with relu' = ln_relu.
 __device__ __forceinline__ void reduce_rows(const ReduceArgs& a, unsigned block) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)block * 4 + (threadIdx.x >> 6);
@@ -43,7 +45,7 @@ __device__ __forceinline__ void reduce_rows(const ReduceArgs& a, unsigned block)
                 const float4 b = *reinterpret_cast<const float4*>(a.bias + i4 * 4);
                 acc.x += b.x; acc.y += b.y; acc.z += b.z; acc.w += b.w;
             }
-            if (a.relu && !a.ln_w) {
+            if (a.relu) {
                 acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f);
             }
             if (a.res) {
@@ -77,7 +79,7 @@ __device__ __forceinline__ void reduce_rows(const ReduceArgs& a, unsigned block)
                 o.y = (v[c].y - mean) * rstd * g.y + b.y;
                 o.z = (v[c].z - mean) * rstd * g.z + b.z;
                 o.w = (v[c].w - mean) * rstd * g.w + b.w;
-                if (a.relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+                if (a.ln_relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
                 v[c] = o;
             }
         }

@@ -86,13 +86,13 @@ def linear(x, w, b, relu=False, residual=None, ln=None, ln_relu=False):
     lib = _lib.load()
     splits = _splits_for(M, N, K)
     if splits > 1 or (ln is not None and N % 4 == 0 and N <= 1024 and K >= 1024):
+        if ln is not None and ln_relu:      # the fused epilogue's ReLU is the Linear's activation (before the residual), not the LayerNorm's
+            raise RuntimeError('ln_relu with split-K: use layer_norm(relu=True) separately')
         wsb = lib.sbev_linear_splitk_workspace(M, N, splits)
         ws = _ws(wsb, x.device)
         st = lib.sbev_linear_splitk_f32(_p(x2), _p(w), _p(b), _p(res2), _p(ln[0] if ln else None), _p(ln[1] if ln else None),
                                         1e-5, _p(y), M, N, K, K, K, int(relu or (ln_relu and ln is None)), splits, _p(ws), _stream())
         _lib.check(st, 'sbev_linear_splitk_f32')
-        if ln is not None and ln_relu:
-            raise RuntimeError('ln_relu with split-K: use layer_norm(relu=True) separately')
         return y.reshape(*lead, N)
     st = lib.sbev_linear_f32(_p(x2), _p(w), _p(b), _p(res2), _p(y), M, N, K, K, K, N, int(relu), _stream())
     _lib.check(st, 'sbev_linear_f32')
