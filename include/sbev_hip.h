@@ -40,7 +40,7 @@ enum sbev_status {
     SBEV_EFAULT = -4   /* an EARLIER decoder step's result is invalid (a pair-mode hand-off timed out: sbev_decoder_chain_pair_faults) */
 };
 
-enum sbev_dtype { SBEV_F32 = 0, SBEV_BF16 = 1, SBEV_F16 = 2 };   /* feature STORAGE types of the sampler (fp32 math throughout): bf16 and fp16 taps are widened exactly.
+enum sbev_dtype { SBEV_F32 = 0, SBEV_BF16 = 1, SBEV_F16 = 2, SBEV_U8 = 3 };   /* SBEV_U8: the source of sbev_image_front only.  Otherwise: feature STORAGE types of the sampler (fp32 math throughout): bf16 and fp16 taps are widened exactly.
                                                                    * fp16 is what the reference's eval mode produces before its out_fp32 cast (val.py:115, models/sparsebev.py:46) */
 enum sbev_gemm_mode {
     SBEV_GEMM_F32 = 0,      /* exact: f32-input MFMA */
@@ -1223,6 +1223,39 @@ int sbev_pool_insert_frames(const void* const* table, const int32_t* index, cons
 int sbev_pool_insert(const void* const* table, const int32_t* index, const void* const* src, void* const* out, int n_levels,
                      const int32_t* hw_pixels, int B, int n_views, int channels, int dtype, const int32_t* insert, int n_slots,
                      sbev_stream_t stream);
+
+/*
+ * The detector's GPU-side image stage as ONE launch for all n = B * N images of a step: load, photometric distortion, BGR -> RGB,
+ * normalise, zero pad to a multiple of `div`, GridMask, store.
+ * Replaces: the pre-backbone lines of SparseBEV.extract_feat (models/sparsebev.py:61-100: .float(), color_aug, mean / std, pad_multiple)
+ *           and the GridMask in front of the backbone (models/sparsebev.py:48-49), i.e. GpuPhotoMetricDistortion, rgb_to_hsv, hsv_to_rgb,
+ *           pad_multiple and GridMask of models/utils.py -- a few dozen torch passes over the fp32 image tensor.
+ * src [n, 3, H, W] contiguous, SBEV_U8 or SBEV_F32; dst [n, 3, Hp, Wp] contiguous, SBEV_F32 or SBEV_F16, Hp = ceil(H / div) * div and Wp
+ * likewise; every element of dst is stored by this launch, the padding as zeros.  mean, std: HOST arrays of 3, passed on by value;
+ * to_rgb: img_norm_cfg's flag.  Per pixel, in fp32, every operation rounded on its own and in the reference's order: float(src) read as
+ * RGB; + delta; * alpha (mode 0); rgb_to_hsv; s * sat; h + hue; h > 360 -> h - 360, then h < 0 -> h + 360; hsv_to_rgb; * alpha (mode 1);
+ * the channel permutation; RGB -> BGR; the to_rgb flip; - mean[c]; / std[c] (a division); the pad; the mask; the cast.  No clamp.
+ * colour_on == 0 skips everything up to the to_rgb flip (the reference outside training); with colour_on != 0 EVERY image takes the HSV
+ * round trip, whatever its flags (as in the reference).
+ * table: device memory, 16-byte aligned, SBEV_FRONT_ROW_BYTES per image, read when the kernel runs (a captured launch serves every step:
+ * refresh the table in place).  NULL: no distortion, no mask -- the inference call (colour_on must be 0).  One row, 16 little-endian
+ * 32-bit words:
+ *    0 int32  flags: bit 0 brightness, 1 contrast, 2 saturation, 3 hue, 4 channel swap -- "this transform is applied"
+ *    1 int32  contrast mode: 0 = before the HSV round trip, 1 = after it
+ *    2 float  delta   3 float alpha   4 float saturation factor   5 float hue shift (degrees)
+ *    6..8 int32  the permutation p: channel k of the distorted RGB image becomes channel p[k] of the old one (imgs[idx, p])
+ *    9 int32  GridMask applied   10 int32 d   11 int32 l   12 int32 st_h   13 int32 st_w     (built on the padded size; a pixel is KEPT
+ *             iff it lies on a row stripe or a column stripe, models/utils.py:15-46; d < 1 is "not applied")
+ *    14, 15 unused (zero)
+ * sbev_image_front_plan (pure host): out[0] = Hp, out[1] = Wp, out[2] = elements of dst, out[3] = bytes of the table, out[4] = workgroups.
+ * Checked before any GPU call (SBEV_EINVAL): null src / dst / mean / std, n, H, W or div < 1, a dtype not listed above, std[c] == 0, a
+ * table that is not 16-byte aligned, colour_on without a table, src / dst not aligned to their element size, a padded size or grid
+ * beyond 32 bits.
+ */
+#define SBEV_FRONT_ROW_BYTES 64
+int sbev_image_front_plan(int n, int H, int W, int div, int64_t* out);
+int sbev_image_front(const void* src, int src_dtype, void* dst, int dst_dtype, int n, int H, int W, int div, const float* mean,
+                     const float* std, int to_rgb, int colour_on, const void* table, sbev_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ operator modules without the built library raises -- there is no CPU / PyTorch f
 """
 from ._lib import load as load_library, SbevError, LIB_PATH   # noqa: F401
 
-__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW']
+__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW', 'ImageFrontEnd']
 
 
 def __getattr__(name):
@@ -22,4 +22,7 @@ def __getattr__(name):
     if name == 'FusedAdamW':
         from .optim import FusedAdamW
         return FusedAdamW
+    if name == 'ImageFrontEnd':
+        from .image_front import ImageFrontEnd
+        return ImageFrontEnd
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

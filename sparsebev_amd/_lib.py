@@ -179,6 +179,9 @@ SIGNATURES = {
     'sbev_optim_finish': (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp]),
     'sbev_optim_adamw': (ctypes.c_int, [ctypes.POINTER(_vp)] * 4 + [_c_i64p, _c_i32p, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 3
                          + [_vp, _vp, _vp]),
+    'sbev_image_front_plan': (ctypes.c_int, [ctypes.c_int] * 4 + [_c_i64p]),
+    'sbev_image_front': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_float)] * 2
+                         + [ctypes.c_int, ctypes.c_int, _vp, _vp]),
     'sbev_profile_read': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int]),
     'sbev_linear_splitk_plan': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'sbev_linear_f32_path': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),

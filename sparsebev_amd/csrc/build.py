@@ -42,6 +42,8 @@ UNITS = {
     'head_assign.hip': ['-ffp-contract=off'],
     # the AdamW update is DEFINED by its sequence of individually rounded fp32 operations (tests restate it bit for bit)
     'optim.hip': ['-ffp-contract=off'],
+    # the image front end's normalised pixels equal torch's separate ops bit for bit: nothing contracted, a true division
+    'image_front.hip': ['-ffp-contract=off'],
     'decoder.hip': [],
     'row_chain.hip': [],                 # the row-local op chains of a layer (4x4x1 MFMA with A broadcast)
     # bit-exact projection: no FMA contraction anywhere in this file
