@@ -10,159 +10,21 @@
 
 namespace {
 
-// ---- column sums (bias gradients) with an optional ReLU mask -------------------------------------------------------
-// dZ = dY * (Y > 0)  (Y = the forward OUTPUT of a ReLU; null -> dZ = dY);  db[n] = sum_m dZ[m, n].
-// Two deterministic passes: block (column block of 64, row chunk of ROW_CHUNK rows) = 64 columns x 4 row lanes writes one
-// partial row of sums, a second tiny kernel adds the chunks in order.  (One block per 64 columns over ALL rows was 4
-// workgroups for a 256-wide Linear: 73 us for 0.9 MB.)
-constexpr int ROW_CHUNK = 32;     // rows per partial-sum block: 8 dependent iterations per thread (128 measured 13.7 us for a 900 x 256 gradient)
-struct ColArgs {
-    const float* dY;     // [M, ld]
-    const float* Y;      // [M, ld] or null
-    float* dZ;           // [M, ld] or null (may alias dY)
-    float* part;         // [chunks, N] or null (no column sums wanted)
-    long long M, ld;
-    int N;
-    int accumulate;      // column sums are ADDED to db (the shared parameters' gradients of a decoder call: autograd.ParamTap)
-};
-
-__global__ __launch_bounds__(256) void bias_relu_bwd_kernel(const ColArgs a) {
-    __shared__ float red[4][64];
-    const int c = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const long long n = (long long)blockIdx.x * 64 + c;
-    const long long m0 = (long long)blockIdx.y * ROW_CHUNK, m1 = m0 + ROW_CHUNK < a.M ? m0 + ROW_CHUNK : a.M;
-    float s = 0.f;
-    if (n < a.N) {
-        for (long long m = m0 + rg; m < m1; m += 4) {
-            float g = a.dY[m * a.ld + n];
-            if (a.Y && !(a.Y[m * a.ld + n] > 0.f)) g = 0.f;
-            if (a.dZ) a.dZ[m * a.ld + n] = g;
-            s += g;
-        }
-    }
-    if (!a.part) return;
-    red[rg][c] = s;
-    __syncthreads();
-    if (rg == 0 && n < a.N) a.part[(long long)blockIdx.y * a.N + n] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
-}
-
-// Few rows (<= ONE_PASS_ROWS: the decoder's B*Q = 900): the whole column sum in ONE launch -- block = 64 columns x 16 row lanes, every
-// lane walks its rows 4 at a time (independent loads), the 16 partial sums are added in lane order through LDS: deterministic, and
-// one 8 us launch instead of two of 7.9 + 7.6 (round 3: 222 of a training step's ~1100 launches were this pair).
-constexpr int ONE_PASS_ROWS = 2048;
-__global__ __launch_bounds__(1024) void bias_relu_bwd_onepass_kernel(const ColArgs a, float* __restrict__ db) {
-    __shared__ float red[16][64];
-    const int c = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const long long n = (long long)blockIdx.x * 64 + c;
-    float s = 0.f;
-    if (n < a.N) {
-        long long m = rg;
-        for (; m + 48 < a.M; m += 64) {
-            float g[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) g[i] = a.dY[(m + 16 * i) * a.ld + n];
-            if (a.Y) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (!(a.Y[(m + 16 * i) * a.ld + n] > 0.f)) g[i] = 0.f;
-            }
-            if (a.dZ) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a.dZ[(m + 16 * i) * a.ld + n] = g[i];
-            }
-            s += (g[0] + g[1]) + (g[2] + g[3]);
-        }
-        for (; m < a.M; m += 16) {
-            float g = a.dY[m * a.ld + n];
-            if (a.Y && !(a.Y[m * a.ld + n] > 0.f)) g = 0.f;
-            if (a.dZ) a.dZ[m * a.ld + n] = g;
-            s += g;
-        }
-    }
-    red[rg][c] = s;
-    __syncthreads();
-    if (rg == 0 && n < a.N) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += red[k][c];
-        db[n] = a.accumulate ? db[n] + t : t;
-    }
-}
-
-// Grouped column sums: the bias gradients of up to 16 Linears, each the sum over up to 8 [M, N_b] gradient matrices (the layers of a
-// decoder call that share the bias), in ONE launch -- block = 64 columns of one bias x 16 row lanes, walking all segments' rows 8 at a
-// time; lane-ordered LDS sum: deterministic.  (Per layer and bias this was one 10 us launch: 66 of a training step's launches.)
-struct ColGroup {
-    const float* seg[8];
-    float* out;
-    int N, nseg, blk0, accumulate;
-};
-struct ColGroupArgs {
-    ColGroup g[16];
-    int ng;
-    long long M;
-};
-__global__ __launch_bounds__(1024) void colsum_group_kernel(const ColGroupArgs a) {
-    __shared__ float red[16][64];
-    int gi = 0;
-    for (int i = 1; i < a.ng; ++i)
-        if ((int)blockIdx.x >= a.g[i].blk0) gi = i;
-    const ColGroup& g = a.g[gi];
-    const int c = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int n = ((int)blockIdx.x - g.blk0) * 64 + c;
-    float s = 0.f;
-    if (n < g.N) {
-        for (int sgi = 0; sgi < g.nseg; ++sgi) {
-            const float* p = g.seg[sgi] + n;
-            long long m = rg;
-            for (; m + 112 < a.M; m += 128) {
-                float v[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = p[(m + 16 * i) * g.N];
-                s += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-            }
-            for (; m < a.M; m += 16) s += p[m * g.N];
-        }
-    }
-    red[rg][c] = s;
-    __syncthreads();
-    if (rg == 0 && n < g.N) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) t += red[k][c];
-        g.out[n] = g.accumulate ? g.out[n] + t : t;
-    }
-}
-
-// out[k][n] = sum_chunks part[k][chunk][n]  for K stacked partial sets (K = 1: bias; K = 2: dgamma, dbeta)
-__global__ __launch_bounds__(256) void chunk_sum_kernel(const float* __restrict__ part, float* __restrict__ out0, float* __restrict__ out1,
-                                                        int chunks, int N, int accumulate = 0) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    float* out = blockIdx.y == 0 ? out0 : out1;
-    const float* p = part + (long long)blockIdx.y * chunks * N;
-    float s = 0.f;
-    for (int c = 0; c < chunks; ++c) s += p[(long long)c * N + n];
-    out[n] = accumulate ? out[n] + s : s;
-}
-
 // ---- LayerNorm backward ---------------------------------------------------------------------------------------------
 // y = relu?(xhat * gamma + beta), xhat = (x - mean) * rstd.   One wave per row (N <= 1024, N % 4 == 0):
 //   g  = dY * (y_pre_relu > 0)                         dxhat = g * gamma
 //   dx = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat * xhat))
-// and the row's (mean, rstd) are left in `stats` for the column kernel: dgamma[n] = sum_m g * xhat, dbeta[n] = sum_m g.
+// and the row's (mean, rstd) are left in `stats` for the column sums below: dgamma[n] = sum_m g * xhat, dbeta[n] = sum_m g.
 struct LnBwdArgs {
     const float* dY;     // [M, N]
     const float* X;      // [M, N]   (the LayerNorm INPUT)
     const float* gamma;  // [N]
     const float* beta;   // [N]      (only read when relu)
     float* dX;           // [M, N]
-    float* stats;        // workspace: [M, 2] (mean, rstd) followed by [2][chunks][N] partial column sums
-    float* dgamma;       // [N]
-    float* dbeta;        // [N]
+    float* stats;        // [M, 2] (mean, rstd): the start of the workspace
     long long M;
     int N, relu;
     float eps;
-    int accumulate;      // dgamma / dbeta are added to
 };
 
 __global__ __launch_bounds__(256) void ln_bwd_rows_kernel(const LnBwdArgs a) {
@@ -236,138 +98,240 @@ __global__ __launch_bounds__(256) void ln_bwd_rows_kernel(const LnBwdArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void ln_bwd_cols_kernel(const LnBwdArgs a) {
-    __shared__ float red[2][4][64];
-    const int c = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + c;
-    const long long m0 = (long long)blockIdx.y * ROW_CHUNK, m1 = m0 + ROW_CHUNK < a.M ? m0 + ROW_CHUNK : a.M;
-    const int chunks = gridDim.y;
-    float sg = 0.f, sb = 0.f;
-    if (n < a.N) {
-        const float w = a.gamma[n], bt = a.relu ? a.beta[n] : 0.f;
-        for (long long m = m0 + rg; m < m1; m += 4) {
-            const float h = (a.X[m * a.N + n] - a.stats[m * 2]) * a.stats[m * 2 + 1];
-            float g = a.dY[m * a.N + n];
-            if (a.relu && !(h * w + bt > 0.f)) g = 0.f;
-            sg += g * h;
-            sb += g;
-        }
-    }
-    red[0][rg][c] = sg;
-    red[1][rg][c] = sb;
-    __syncthreads();
-    if (rg == 0 && n < a.N) {
-        float* part = a.stats + 2 * a.M;                   // [2][chunks][N] behind the row statistics
-        part[(long long)blockIdx.y * a.N + n] = (red[0][0][c] + red[0][1][c]) + (red[0][2][c] + red[0][3][c]);
-        part[((long long)chunks + blockIdx.y) * a.N + n] = (red[1][0][c] + red[1][1][c]) + (red[1][2][c] + red[1][3][c]);
-    }
-}
+// ---- column sums: bias gradients, LayerNorm dgamma / dbeta ------------------------------------------------------------
+// Every column reduction of the training step is  term x walk x finish, each stated once:
+//   term    what row m of column n adds up.  BiasTerm: dZ = dY * (Y > 0) (Y = the forward OUTPUT of a ReLU; null -> dZ = dY), stored
+//           if dZ is given, one addend.  LnTerm: g * xhat and g, the ReLU mask recomputed from the rows' (mean, rstd).  PlainTerm: a load.
+//   walk    a lane takes rows rg, rg + LANES, ..: R rows per trip with their loads issued together, the trip's addends joined by
+//           a pairwise halving tree or one after another in row order, then added to the running sum; tail rows one at a time.
+//   finish  one launch (lane_sum_kernel): block = 64 columns x 16 row lanes, the 16 sums added in lane order from 0.f through
+//           LDS, result (+)= out.  Or two passes (chunk_partial_kernel, chunk_sum_kernel): block = 64 columns x 4 row lanes
+//           over a chunk of ROW_CHUNK rows writes (r0 + r1) + (r2 + r3) into one partial row, the chunks are added in order.
+// The sequence of fp32 additions behind an output element is part of the contract (a step's gradients are compared bit for bit across
+// changes), so R and the join belong to the entry point: bias 4 rows / tree, sbev_colsum_group 8 / tree, LayerNorm 4 / in row order.
+// All of it is deterministic: no atomics.
+//
+// Two passes are for many rows: one block per 64 columns over ALL rows was 4 workgroups for a 256-wide Linear, 73 us for 0.9 MB.
+// Up to ONE_PASS_ROWS rows (the decoder's B*Q = 900) the one launch takes 8 us instead of two of 7.9 + 7.6 (round 3: 222 of a
+// training step's ~1100 launches were this pair).  The grouped entry points put up to 16 biases / 8 LayerNorms, each summed over up to 8
+// segments (the layers of a decoder call that share the parameter), into one launch: per layer and bias it was one 10 us launch, 66
+// of a training step's launches.  sbev_layer_norm_bwd's one launch is the grouped LayerNorm launch with one group of one segment.
+constexpr int ROW_CHUNK = 32;     // rows per partial-sum block: 8 dependent iterations per thread (128 measured 13.7 us for a 900 x 256 gradient)
+constexpr int ONE_PASS_ROWS = 2048;
 
-// few rows: dgamma / dbeta in one launch (see bias_relu_bwd_onepass_kernel): block = 64 columns x 16 row lanes
-__global__ __launch_bounds__(1024) void ln_bwd_cols_onepass_kernel(const LnBwdArgs a) {
-    __shared__ float red[2][16][64];
-    const int c = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int n = blockIdx.x * 64 + c;
-    float sg = 0.f, sb = 0.f;
-    if (n < a.N) {
-        const float w = a.gamma[n], bt = a.relu ? a.beta[n] : 0.f;
-        long long m = rg;
-        for (; m + 16 < a.M; m += 32) {                       // two independent rows per trip
-            const float h0 = (a.X[m * a.N + n] - a.stats[m * 2]) * a.stats[m * 2 + 1];
-            const float h1 = (a.X[(m + 16) * a.N + n] - a.stats[(m + 16) * 2]) * a.stats[(m + 16) * 2 + 1];
-            float g0 = a.dY[m * a.N + n], g1 = a.dY[(m + 16) * a.N + n];
-            if (a.relu && !(h0 * w + bt > 0.f)) g0 = 0.f;
-            if (a.relu && !(h1 * w + bt > 0.f)) g1 = 0.f;
-            sg += g0 * h0; sb += g0;
-            sg += g1 * h1; sb += g1;
-        }
-        for (; m < a.M; m += 16) {
-            const float h = (a.X[m * a.N + n] - a.stats[m * 2]) * a.stats[m * 2 + 1];
-            float g = a.dY[m * a.N + n];
-            if (a.relu && !(h * w + bt > 0.f)) g = 0.f;
-            sg += g * h; sb += g;
-        }
-    }
-    red[0][rg][c] = sg;
-    red[1][rg][c] = sb;
-    __syncthreads();
-    if (rg < 2 && n < a.N) {
-        float t = 0.f;
+// rows<R>(m, step, v): the addends v[i][..] of rows m + step * i, i < R, of the term's column.  (The element index stays
+// (m + step * i) * ld + n: written as m * ld + n + (step * ld) * i the compiler kept the bias term's twelve pointers in SGPRs and
+// advanced them with 24 scalar adds behind the trip's wait, 0.7 us on a 12 us launch.)
+struct BiasTerm {
+    static constexpr int K = 1;
+    const float* dY;     // [M, ld]
+    const float* Y;      // [M, ld] or null
+    float* dZ;           // [M, ld] or null (may alias dY)
+    long long ld;
+    int n;
+    template <int R>
+    __device__ void rows(long long m, int step, float (&v)[R][K]) const {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) t += red[rg][k][c];
-        float* o = (rg == 0 ? a.dgamma : a.dbeta) + n;
-        *o = a.accumulate ? *o + t : t;
+        for (int i = 0; i < R; ++i) v[i][0] = dY[(m + step * i) * ld + n];
+        if (Y) {
+#pragma unroll
+            for (int i = 0; i < R; ++i) if (!(Y[(m + step * i) * ld + n] > 0.f)) v[i][0] = 0.f;
+        }
+        if (dZ) {
+#pragma unroll
+            for (int i = 0; i < R; ++i) dZ[(m + step * i) * ld + n] = v[i][0];
+        }
+    }
+};
+
+struct LnTerm {
+    static constexpr int K = 2;      // g * xhat (dgamma), g (dbeta)
+    const float* dY;     // [M, N]
+    const float* X;      // [M, N]
+    const float* st;     // [M, 2] (mean, rstd) as ln_bwd_rows_kernel leaves them
+    int N, n, relu;
+    float w, bt;         // gamma[n]; beta[n] if relu
+    template <int R>
+    __device__ void rows(long long m, int step, float (&v)[R][K]) const {
+        float h[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const long long r = m + step * i;
+            h[i] = (X[r * N + n] - st[r * 2]) * st[r * 2 + 1];
+            v[i][1] = dY[r * N + n];
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            if (relu && !(h[i] * w + bt > 0.f)) v[i][1] = 0.f;
+            v[i][0] = v[i][1] * h[i];
+        }
+    }
+};
+
+struct PlainTerm {
+    static constexpr int K = 1;
+    const float* p;      // [M, N]
+    int N, n;
+    template <int R>
+    __device__ void rows(long long m, int step, float (&v)[R][K]) const {
+#pragma unroll
+        for (int i = 0; i < R; ++i) v[i][0] = p[(m + step * i) * N + n];
+    }
+};
+
+// the pairwise halving tree over addend k of rows I0 .. I0 + R - 1.  R = 4: (v0 + v1) + (v2 + v3); R = 8: ((v0 + v1) + (v2 + v3)) + ((v4 + v5) + (v6 + v7)).
+// Depth first, as the written expression evaluates: level by level gives the same sum, but the 8-row loop's loads then lose their
+// pointer chain (40 instead of 32 instructions).
+template <int I0, int R, int RR, int K>
+__device__ __forceinline__ float halves(const float (&v)[RR][K], int k) {
+    static_assert((R & (R - 1)) == 0, "the halving tree wants a power of two");
+    if constexpr (R == 1) return v[I0][k];
+    else return halves<I0, R / 2>(v, k) + halves<I0 + R / 2, R / 2>(v, k);
+}
+
+// s += the addends of rows m, m + LANES, .. (R of them), joined by the tree or one after another
+template <int LANES, int R, bool TREE, class Term>
+__device__ __forceinline__ void trip(const Term& t, long long m, float (&s)[Term::K]) {
+    float v[R][Term::K];
+    t.template rows<R>(m, LANES, v);
+#pragma unroll
+    for (int k = 0; k < Term::K; ++k) {
+        if (TREE) {
+            s[k] += halves<0, R>(v, k);
+        } else {
+#pragma unroll
+            for (int i = 0; i < R; ++i) s[k] += v[i][k];
+        }
     }
 }
 
-// Grouped LayerNorm parameter gradients: dgamma / dbeta of up to 8 LayerNorms, each summed over up to 8 (dY, X, row statistics)
-// triples -- the layers of a decoder call sharing the LayerNorm -- in ONE launch (block = 64 columns of one LayerNorm x 16 row lanes;
-// the statistics are the [M, 2] (mean, rstd) rows sbev_layer_norm_bwd_acc leaves at the start of its workspace).
-struct LnGroup {
-    const float* dY[8];
-    const float* X[8];
-    const float* stats[8];
+// lane rg of LANES over the rows [m0, m1)
+template <int LANES, int R, bool TREE, class Term>
+__device__ __forceinline__ void walk(const Term& t, long long m0, long long m1, int rg, float (&s)[Term::K]) {
+    long long m = m0 + rg;
+    if constexpr (R > 1)
+        for (; m + LANES * (R - 1) < m1; m += LANES * R) trip<LANES, R, TREE>(t, m, s);
+    for (; m < m1; m += LANES) trip<LANES, 1, TREE>(t, m, s);
+}
+
+// A group = one parameter of N columns, summed over nseg segments of M rows each, blocks blk0 .. of its launch.  A group type names
+// its term and the trip of its one-launch walk; term(n) is column n's term (what it loads of the parameter it loads once, not per
+// segment: a dependent load of ~1 us each), seg(t, s) points it at segment s, dst(k) is where addend k's sums go.
+template <int NSRC>
+struct GroupBase {
+    const float* src[NSRC][8];    // per segment: NSRC matrices
+    int N, nseg, blk0, accumulate;
+};
+struct ColGroup : GroupBase<1> {                 // sbev_colsum_group
+    using Term = PlainTerm;
+    static constexpr int ROWS = 8;
+    static constexpr bool TREE = true;
+    float* out;
+    __device__ Term term(int n) const { return {nullptr, N, n}; }
+    __device__ void seg(Term& t, int s) const { t.p = src[0][s]; }
+    __device__ float* dst(int) const { return out; }
+};
+struct LnGroup : GroupBase<3> {                  // src: dY, X, the [M, 2] row statistics
+    using Term = LnTerm;
+    static constexpr int ROWS = 4;
+    static constexpr bool TREE = false;
     const float* gamma;
     const float* beta;
     float* dgamma;
     float* dbeta;
-    int N, nseg, blk0, relu, accumulate;
+    int relu;
+    __device__ Term term(int n) const { return {nullptr, nullptr, nullptr, N, n, relu, gamma[n], relu ? beta[n] : 0.f}; }
+    __device__ void seg(Term& t, int s) const { t.dY = src[0][s]; t.X = src[1][s]; t.st = src[2][s]; }
+    __device__ float* dst(int k) const { return k == 0 ? dgamma : dbeta; }
 };
-struct LnGroupArgs {
-    LnGroup g[8];
+struct BiasGroup {                               // sbev_bias_relu_bwd: the only group of its launch, one segment
+    using Term = BiasTerm;
+    static constexpr int ROWS = 4;
+    static constexpr bool TREE = true;
+    const float* dY;
+    const float* Y;
+    float* dZ;
+    float* out;          // db; two passes: the partial rows, null = no column sums wanted
+    long long ld;
+    int N, accumulate;
+    static constexpr int nseg = 1, blk0 = 0;
+    __device__ Term term(int n) const { return {dY, Y, dZ, ld, n}; }
+    __device__ void seg(Term&, int) const {}
+    __device__ float* dst(int) const { return out; }
+};
+template <class G, int MAXG>
+struct Groups {
+    G g[MAXG];
     int ng;
     long long M;
 };
-__global__ __launch_bounds__(1024) void ln_param_group_kernel(const LnGroupArgs a) {
-    __shared__ float red[2][16][64];
+
+template <class G, int MAXG>
+__global__ __launch_bounds__(1024) void lane_sum_kernel(const Groups<G, MAXG> a) {
+    constexpr int K = G::Term::K;
+    __shared__ float red[K][16][64];
     int gi = 0;
-    for (int i = 1; i < a.ng; ++i)
-        if ((int)blockIdx.x >= a.g[i].blk0) gi = i;
-    const LnGroup& g = a.g[gi];
+    if constexpr (MAXG > 1)
+        for (int i = 1; i < a.ng; ++i)
+            if ((int)blockIdx.x >= a.g[i].blk0) gi = i;
+    const G& g = a.g[gi];
     const int c = threadIdx.x & 63, rg = threadIdx.x >> 6;
     const int n = ((int)blockIdx.x - g.blk0) * 64 + c;
-    float sg = 0.f, sb = 0.f;
+    float s[K] = {};
     if (n < g.N) {
-        const float w = g.gamma[n], bt = g.relu ? g.beta[n] : 0.f;
+        auto t = g.term(n);
         for (int sgi = 0; sgi < g.nseg; ++sgi) {
-            const float* dY = g.dY[sgi] + n;
-            const float* X = g.X[sgi] + n;
-            const float* st = g.stats[sgi];
-            long long m = rg;
-            for (; m + 48 < a.M; m += 64) {
-                float h[4], gr[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const long long r = m + 16 * i;
-                    h[i] = (X[r * g.N] - st[r * 2]) * st[r * 2 + 1];
-                    gr[i] = dY[r * g.N];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (g.relu && !(h[i] * w + bt > 0.f)) gr[i] = 0.f;
-                    sg += gr[i] * h[i];
-                    sb += gr[i];
-                }
-            }
-            for (; m < a.M; m += 16) {
-                const float hh = (X[m * g.N] - st[m * 2]) * st[m * 2 + 1];
-                float gg = dY[m * g.N];
-                if (g.relu && !(hh * w + bt > 0.f)) gg = 0.f;
-                sg += gg * hh;
-                sb += gg;
-            }
+            g.seg(t, sgi);
+            walk<16, G::ROWS, G::TREE>(t, 0, a.M, rg, s);
         }
     }
-    red[0][rg][c] = sg;
-    red[1][rg][c] = sb;
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[k][rg][c] = s[k];
     __syncthreads();
-    if (rg < 2 && n < g.N) {
+    if (rg < K && n < g.N) {                     // wave k adds addend k's 16 lanes
         float t = 0.f;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) t += red[rg][k][c];
-        float* o = (rg == 0 ? g.dgamma : g.dbeta) + n;
+        for (int l = 0; l < 16; ++l) t += red[rg][l][c];
+        float* o = g.dst(rg) + n;
         *o = g.accumulate ? *o + t : t;
     }
+}
+
+// first of two passes: partial row blockIdx.y of dst(k) [chunks, N]
+template <class G>
+__global__ __launch_bounds__(256) void chunk_partial_kernel(const G g, const long long M) {
+    constexpr int K = G::Term::K;
+    __shared__ float red[K][4][64];
+    const int c = threadIdx.x & 63, rg = threadIdx.x >> 6;
+    const int n = blockIdx.x * 64 + c;
+    const long long m0 = (long long)blockIdx.y * ROW_CHUNK, m1 = m0 + ROW_CHUNK < M ? m0 + ROW_CHUNK : M;
+    float s[K] = {};
+    if (n < g.N) {
+        auto t = g.term(n);
+        g.seg(t, 0);
+        walk<4, 1, false>(t, m0, m1, rg, s);
+    }
+    if (!g.dst(0)) return;                       // dZ only
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[k][rg][c] = s[k];
+    __syncthreads();
+    if (rg == 0 && n < g.N) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            g.dst(k)[(long long)blockIdx.y * g.N + n] = (red[k][0][c] + red[k][1][c]) + (red[k][2][c] + red[k][3][c]);
+    }
+}
+
+// out[k][n] (+)= sum_chunks part[k][chunk][n]  for K stacked partial sets (K = 1: bias; K = 2: dgamma, dbeta)
+__global__ __launch_bounds__(256) void chunk_sum_kernel(const float* __restrict__ part, float* __restrict__ out0, float* __restrict__ out1,
+                                                        int chunks, int N, int accumulate) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    float* out = blockIdx.y == 0 ? out0 : out1;
+    const float* p = part + (long long)blockIdx.y * chunks * N;
+    float s = 0.f;
+    for (int c = 0; c < chunks; ++c) s += p[(long long)c * N + n];
+    out[n] = accumulate ? out[n] + s : s;
 }
 
 // ---- refine_bbox backward (models/sparsebev_transformer.py:155-160,179-183; models/utils.py:87-102) ----------------
@@ -606,15 +570,16 @@ static int bias_relu_bwd_impl(const float* dY, const float* Y, float* dZ, float*
     SBEV_REQUIRE(dY != nullptr && (!db || workspace), "sbev_bias_relu_bwd: null grad / workspace");
     const int chunks = (int)((M + ROW_CHUNK - 1) / ROW_CHUNK);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 cols((unsigned)((N + 63) / 64));
     if (db && M > 0 && M <= ONE_PASS_ROWS) {
-        ColArgs a{dY, Y, dZ, nullptr, M, ld, N, accumulate};
-        hipLaunchKernelGGL(bias_relu_bwd_onepass_kernel, dim3((unsigned)((N + 63) / 64)), dim3(1024), 0, s, a, db);
+        const Groups<BiasGroup, 1> a{{{dY, Y, dZ, db, ld, N, accumulate}}, 1, M};
+        hipLaunchKernelGGL((lane_sum_kernel<BiasGroup, 1>), cols, dim3(1024), 0, s, a);
         return sbev::check_launch("sbev_bias_relu_bwd");
     }
     if (chunks > 0) {
         SBEV_REQUIRE(chunks <= 65535, "sbev_bias_relu_bwd: too many rows");
-        ColArgs a{dY, Y, dZ, db ? workspace : nullptr, M, ld, N, 0};
-        hipLaunchKernelGGL(bias_relu_bwd_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)chunks), dim3(256), 0, s, a);
+        const BiasGroup g{dY, Y, dZ, db ? workspace : nullptr, ld, N, 0};
+        hipLaunchKernelGGL(chunk_partial_kernel<BiasGroup>, dim3(cols.x, (unsigned)chunks), dim3(256), 0, s, g, (long long)M);
         int st = sbev::check_launch("sbev_bias_relu_bwd");
         if (st != SBEV_OK) return st;
     }
@@ -629,10 +594,26 @@ extern "C" int sbev_bias_relu_bwd(const float* dY, const float* Y, float* dZ, fl
                                   float* workspace, sbev_stream_t stream) {
     return bias_relu_bwd_impl(dY, Y, dZ, db, M, N, ld, workspace, 0, stream);
 }
-// the same with the column sums ADDED to db (accumulate != 0): one parameter used by several layers of a call
+// the same with the column sums ADDED to db (accumulate != 0): one parameter used by several layers of a call (autograd.ParamTap)
 extern "C" int sbev_bias_relu_bwd_acc(const float* dY, const float* Y, float* dZ, float* db, int64_t M, int N, int64_t ld,
                                       float* workspace, int accumulate, sbev_stream_t stream) {
     return bias_relu_bwd_impl(dY, Y, dZ, db, M, N, ld, workspace, accumulate, stream);
+}
+
+// What every group of a grouped launch has: sizes, flags, its first block (blk: the launch's block count so far) and its segments'
+// pointers, from the host arrays srcs[i] [ng][8] (row b: group b's nseg_b pointers first).  own = group b's own pointers are there.
+template <int NSRC>
+static int fill_group(GroupBase<NSRC>& g, int& blk, const char* who, int b, bool own, const float* const* const (&srcs)[NSRC],
+                      const int32_t* Ns, const int32_t* nsegs, const int32_t* accumulate) {
+    SBEV_REQUIRE(Ns[b] >= 1 && nsegs[b] >= 1 && nsegs[b] <= 8 && own, "%s: group %d", who, b);
+    g.N = Ns[b]; g.nseg = nsegs[b]; g.blk0 = blk; g.accumulate = accumulate[b];
+    for (int s = 0; s < g.nseg; ++s)
+        for (int i = 0; i < NSRC; ++i) {
+            SBEV_REQUIRE(srcs[i][b * 8 + s], "%s: null segment", who);
+            g.src[i][s] = srcs[i][b * 8 + s];
+        }
+    blk += (g.N + 63) / 64;
+    return SBEV_OK;
 }
 
 // dX and the row statistics only (no dgamma / dbeta): the first half of sbev_layer_norm_bwd, for callers that sum the parameter
@@ -642,7 +623,7 @@ extern "C" int sbev_layer_norm_bwd_rows(const float* dY, const float* X, const f
     SBEV_REQUIRE(M >= 0 && N >= 4 && N % 4 == 0 && N <= 1024, "sbev_layer_norm_bwd_rows: N=%d must be a multiple of 4 in 4..1024", N);
     if (M == 0) return SBEV_OK;
     SBEV_REQUIRE(dY && X && gamma && dX && workspace && (!relu || beta), "sbev_layer_norm_bwd_rows: null pointer");
-    LnBwdArgs a{dY, X, gamma, beta, dX, workspace, nullptr, nullptr, M, N, relu, eps, 0};
+    LnBwdArgs a{dY, X, gamma, beta, dX, workspace, M, N, relu, eps};
     hipLaunchKernelGGL(ln_bwd_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return sbev::check_launch("sbev_layer_norm_bwd_rows");
 }
@@ -656,22 +637,18 @@ extern "C" int sbev_layer_norm_param_group(const float* const* dYs, const float*
     SBEV_REQUIRE(ng >= 0 && ng <= 8 && M >= 0, "sbev_layer_norm_param_group: at most 8 groups");
     if (ng == 0) return SBEV_OK;
     SBEV_REQUIRE(dYs && Xs && stats && gammas && betas && dgammas && dbetas && Ns && nsegs && relus && accumulate, "sbev_layer_norm_param_group: null pointer");
-    LnGroupArgs a{};
+    Groups<LnGroup, 8> a{};
     a.ng = ng; a.M = M;
+    const float* const* const srcs[3] = {dYs, Xs, stats};
     int blk = 0;
     for (int b = 0; b < ng; ++b) {
-        SBEV_REQUIRE(Ns[b] >= 1 && nsegs[b] >= 1 && nsegs[b] <= 8 && gammas[b] && dgammas[b] && dbetas[b] && (!relus[b] || betas[b]),
-                     "sbev_layer_norm_param_group: group %d", b);
         LnGroup& g = a.g[b];
-        g.N = Ns[b]; g.nseg = nsegs[b]; g.blk0 = blk; g.relu = relus[b]; g.accumulate = accumulate[b];
-        g.gamma = gammas[b]; g.beta = betas[b]; g.dgamma = dgammas[b]; g.dbeta = dbetas[b];
-        for (int s = 0; s < nsegs[b]; ++s) {
-            SBEV_REQUIRE(dYs[b * 8 + s] && Xs[b * 8 + s] && stats[b * 8 + s], "sbev_layer_norm_param_group: null segment");
-            g.dY[s] = dYs[b * 8 + s]; g.X[s] = Xs[b * 8 + s]; g.stats[s] = stats[b * 8 + s];
-        }
-        blk += (Ns[b] + 63) / 64;
+        int st = fill_group(g, blk, "sbev_layer_norm_param_group", b, gammas[b] && dgammas[b] && dbetas[b] && (!relus[b] || betas[b]),
+                            srcs, Ns, nsegs, accumulate);
+        if (st != SBEV_OK) return st;
+        g.gamma = gammas[b]; g.beta = betas[b]; g.dgamma = dgammas[b]; g.dbeta = dbetas[b]; g.relu = relus[b];
     }
-    hipLaunchKernelGGL(ln_param_group_kernel, dim3((unsigned)blk), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL((lane_sum_kernel<LnGroup, 8>), dim3((unsigned)blk), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), a);
     return sbev::check_launch("sbev_layer_norm_param_group");
 }
 
@@ -682,19 +659,16 @@ extern "C" int sbev_colsum_group(const float* const* segs, float* const* outs, c
     SBEV_REQUIRE(ng >= 0 && ng <= 16 && M >= 0, "sbev_colsum_group: at most 16 groups");
     if (ng == 0) return SBEV_OK;
     SBEV_REQUIRE(segs && outs && Ns && nsegs && accumulate, "sbev_colsum_group: null pointer");
-    ColGroupArgs a{};
+    Groups<ColGroup, 16> a{};
     a.ng = ng; a.M = M;
+    const float* const* const srcs[1] = {segs};
     int blk = 0;
     for (int b = 0; b < ng; ++b) {
-        SBEV_REQUIRE(Ns[b] >= 1 && nsegs[b] >= 1 && nsegs[b] <= 8 && outs[b], "sbev_colsum_group: group %d", b);
-        a.g[b].N = Ns[b]; a.g[b].nseg = nsegs[b]; a.g[b].out = outs[b]; a.g[b].blk0 = blk; a.g[b].accumulate = accumulate[b];
-        for (int s = 0; s < nsegs[b]; ++s) {
-            SBEV_REQUIRE(segs[b * 8 + s], "sbev_colsum_group: null segment");
-            a.g[b].seg[s] = segs[b * 8 + s];
-        }
-        blk += (Ns[b] + 63) / 64;
+        int st = fill_group(a.g[b], blk, "sbev_colsum_group", b, outs[b] != nullptr, srcs, Ns, nsegs, accumulate);
+        if (st != SBEV_OK) return st;
+        a.g[b].out = outs[b];
     }
-    hipLaunchKernelGGL(colsum_group_kernel, dim3((unsigned)blk), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL((lane_sum_kernel<ColGroup, 16>), dim3((unsigned)blk), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), a);
     return sbev::check_launch("sbev_colsum_group");
 }
 
@@ -703,27 +677,38 @@ extern "C" int64_t sbev_layer_norm_bwd_workspace(int64_t M, int N) {
     return (2 * M + 2 * ((M + ROW_CHUNK - 1) / ROW_CHUNK) * (int64_t)N) * (int64_t)sizeof(float);
 }
 
+// workspace: [M, 2] (mean, rstd), then (two passes) [2][chunks][N] partial column sums
 static int layer_norm_bwd_impl(const float* dY, const float* X, const float* gamma, const float* beta, float eps, int relu,
                                float* dX, float* dgamma, float* dbeta, float* workspace, int64_t M, int N, int accumulate, sbev_stream_t stream) {
     SBEV_REQUIRE(M >= 0 && N >= 4 && N % 4 == 0 && N <= 1024, "sbev_layer_norm_bwd: N=%d must be a multiple of 4 in 4..1024", N);
     SBEV_REQUIRE(dY && X && gamma && dX && dgamma && dbeta && workspace && (!relu || beta), "sbev_layer_norm_bwd: null pointer");
-    LnBwdArgs a{dY, X, gamma, beta, dX, workspace, dgamma, dbeta, M, N, relu, eps, accumulate};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int chunks = (int)((M + ROW_CHUNK - 1) / ROW_CHUNK);
     SBEV_REQUIRE(chunks <= 65535, "sbev_layer_norm_bwd: too many rows");
+    float* part = workspace + 2 * M;
     if (M > 0) {
+        LnBwdArgs a{dY, X, gamma, beta, dX, workspace, M, N, relu, eps};
         hipLaunchKernelGGL(ln_bwd_rows_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, a);
         int st = sbev::check_launch("sbev_layer_norm_bwd (rows)");
         if (st != SBEV_OK) return st;
-        if (M <= ONE_PASS_ROWS) {
-            hipLaunchKernelGGL(ln_bwd_cols_onepass_kernel, dim3((unsigned)((N + 63) / 64)), dim3(1024), 0, s, a);
+        const bool one = M <= ONE_PASS_ROWS;      // the grouped launch over this one (dY, X, statistics) triple, or partial rows
+        Groups<LnGroup, 8> ga{};
+        ga.ng = 1; ga.M = M;
+        LnGroup& g = ga.g[0];
+        g.src[0][0] = dY; g.src[1][0] = X; g.src[2][0] = workspace;
+        g.N = N; g.nseg = 1; g.blk0 = 0; g.accumulate = one ? accumulate : 0;
+        g.gamma = gamma; g.beta = beta; g.relu = relu;
+        g.dgamma = one ? dgamma : part; g.dbeta = one ? dbeta : part + (int64_t)chunks * N;
+        const dim3 cols((unsigned)((N + 63) / 64));
+        if (one) {
+            hipLaunchKernelGGL((lane_sum_kernel<LnGroup, 8>), cols, dim3(1024), 0, s, ga);
             return sbev::check_launch("sbev_layer_norm_bwd (columns)");
         }
-        hipLaunchKernelGGL(ln_bwd_cols_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)chunks), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(chunk_partial_kernel<LnGroup>, dim3(cols.x, (unsigned)chunks), dim3(256), 0, s, g, (long long)M);
         st = sbev::check_launch("sbev_layer_norm_bwd (columns)");
         if (st != SBEV_OK) return st;
     }
-    hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)((N + 255) / 256), 2), dim3(256), 0, s, workspace + 2 * M, dgamma, dbeta, chunks, N, accumulate);
+    hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)((N + 255) / 256), 2), dim3(256), 0, s, part, dgamma, dbeta, chunks, N, accumulate);
     return sbev::check_launch("sbev_layer_norm_bwd (sum)");
 }
 

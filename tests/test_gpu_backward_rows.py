@@ -280,6 +280,57 @@ def test_layer_norm_param_group_vs_fp64_and_vs_per_segment_calls(M):
     report(worst)
 
 
+# ---- one entry point stated through another ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('N', [4, 260, 1024])
+@pytest.mark.parametrize('M', [1, 17, 33, 900, 2048])
+def test_layer_norm_bwd_one_pass_is_the_grouped_launch_of_one_segment(M, N):
+    """up to ONE_PASS_ROWS rows sbev_layer_norm_bwd_acc's dgamma / dbeta are, bit for bit, what sbev_layer_norm_bwd_rows followed by
+    sbev_layer_norm_param_group with one group of one segment gives on the same buffers: relu on / off, written / added to"""
+    lib = _lib.load()
+    for relu in (0, 1):
+        c = C.ln_case(M, N, relu)
+        dYb, Xb, gb, bb = Buf(M, N, init=c['dY']), Buf(M, N, init=c['X']), Buf(1, N, init=c['gamma']), Buf(1, N, init=c['beta'])
+        for acc in (0, 1):
+            got = {}
+            for how in ('acc', 'group'):
+                dXb = Buf(M, N)
+                dgb, dbb = (Buf(1, N, init=c[k] if acc else None) for k in ('dgamma_before', 'dbeta_before'))
+                ws = workspace(lib.sbev_layer_norm_bwd_workspace(M, N))
+                if how == 'acc':
+                    ok(lib.sbev_layer_norm_bwd_acc(dYb.ptr, Xb.ptr, gb.ptr, bb.ptr, C.EPS, relu, dXb.ptr, dgb.ptr, dbb.ptr, ws.ptr, M, N, acc, None))
+                else:
+                    ok(lib.sbev_layer_norm_bwd_rows(dYb.ptr, Xb.ptr, gb.ptr, bb.ptr, C.EPS, relu, dXb.ptr, ws.ptr, M, N, None))
+                    one = lambda b: (VP * 8)(b.ptr.value)
+                    i32 = lambda v: (ctypes.c_int32 * 1)(v)
+                    ok(lib.sbev_layer_norm_param_group(one(dYb), one(Xb), one(ws), _ptrs([gb]), _ptrs([bb]), _ptrs([dgb]), _ptrs([dbb]),
+                                                       i32(N), i32(1), i32(relu), i32(acc), 1, M, None))
+                torch.cuda.synchronize()
+                assert all(b.intact() for b in (dXb, dgb, dbb, ws)), (relu, acc, how)
+                got[how] = (dXb.bits(), dgb.bits(), dbb.bits())
+            assert all(torch.equal(a, b) for a, b in zip(got['acc'], got['group'])), (relu, acc)
+
+
+@pytest.mark.parametrize('N', [1, 65, 776])
+@pytest.mark.parametrize('M', [1, 17, 65, 2048])
+def test_bias_column_sum_against_colsum_group_of_one_segment(M, N):
+    """sbev_bias_relu_bwd without Y and dZ is a plain column sum, as is sbev_colsum_group with one group of one segment: 4 rows per trip
+    against 8, so two different trees -- bit-equal on the integer leg, to the bound on the real leg.
+    measured worst (real leg, max |difference| / max |colsum_group|): 2.3e-7."""
+    lib = _lib.load()
+    worst = {}
+    for leg in ('int', 'real'):
+        dY, _, _ = C.bias_case(M, N, leg, False)
+        dYb, dbb, out = Buf(M, N, init=dY), Buf(1, N), Buf(1, N)
+        ws = workspace(lib.sbev_colsum_workspace(M, N))
+        ok(lib.sbev_bias_relu_bwd(dYb.ptr, None, None, dbb.ptr, M, N, N, ws.ptr, None))
+        i32 = lambda v: (ctypes.c_int32 * 1)(v)
+        ok(lib.sbev_colsum_group((VP * 8)(dYb.ptr.value), _ptrs([out]), i32(N), i32(1), i32(0), 1, M, None))
+        torch.cuda.synchronize()
+        check(dbb.vector(), out.vector().double(), leg, worst, 'bias_relu_bwd db vs colsum_group')
+        assert all(b.intact() for b in (dYb, dbb, out, ws)) and torch.equal(dYb.values(), dY)
+    report(worst)
+
+
 # ---- sbev_gemm_f32_multi -------------------------------------------------------------------------------------------------------------------
 def _ptrs(bufs):
     return (VP * len(bufs))(*[b.ptr.value for b in bufs])
