@@ -1257,6 +1257,39 @@ int sbev_image_front_plan(int n, int H, int W, int div, int64_t* out);
 int sbev_image_front(const void* src, int src_dtype, void* dst, int dst_dtype, int n, int H, int W, int div, const float* mean,
                      const float* std, int to_rgb, int colour_on, const void* table, sbev_stream_t stream);
 
+/*
+ * The loader's image geometry as ONE launch for all n images of a step: decoded camera frames in, the front end's input out.
+ * Replaces: RandomTransformImage of loaders/pipelines/transforms.py (PIL resize -- bicubic, antialiased --, crop with black fill,
+ *           FLIP_LEFT_RIGHT) and the format bundle's HWC -> CHW, which run on the host at 19-28 ms per 900 x 1600 frame.
+ * src [n, H, W, 3] uint8 contiguous (4-byte aligned); dst [n, 3, fH, fW] uint8 contiguous; every byte of dst is stored.  The result
+ * equals Pillow's at every byte: Pillow's 8-bit resampler is integer arithmetic (coefficients rounded to 22 fractional bits, an int
+ * accumulator from 1 << 21, >> 22, clamp, uint8 between the horizontal and the vertical pass) and the kernel does the same.
+ * Output pixel (y, x) of image i reads resized pixel (crop_y + y, crop_x + x'), x' = fW - 1 - x if mirrored, else x; a coordinate
+ * outside the resized image gives 0.
+ * table: device memory, 16-byte aligned: n_transforms blocks written by sbev_image_geom_plan, one per sample; image_rows: int32 [n] on
+ * the device, the block of each image (clamped to [0, n_transforms)).  Both are read when the kernel runs: a captured launch serves
+ * every step, refresh them in place.  A block, in little-endian int32 words (block bytes = out[0] of the plan, a multiple of 16):
+ *    0 newW   1 newH   2 crop_x   3 crop_y   4 flip   5 ksize_x   6 ksize_y   7 unused (zero)
+ *    8 ..                 (first, count) of the fW kept columns: source columns first .. first + count - 1; count 0 = outside
+ *    8 + 2 fW ..          (first, count) of the fH kept rows
+ *    xk = round up to 4 words of (8 + 2 fW + 2 fH) ..   int32 coefficients [fW, SBEV_GEOM_KMAX], zero beyond count
+ *    xk + 16 fW ..        int32 coefficients [fH, SBEV_GEOM_KMAX]
+ * sbev_image_geom_plan (pure host) writes one block into table_out (host memory; NULL: sizes only) for the source H x W resized to
+ * resize_w x resize_h and cropped at (crop_x, crop_y) to fW x fH.  Coefficients in double, in Pillow's order: scale = in / out,
+ * filterscale = max(scale, 1), support = 2 * filterscale, center = (xx + 0.5) * scale, xmin = (int)(center - support + 0.5) clamped to
+ * 0, xmax likewise clamped to the input size, weights bicubic((x + xmin - center + 0.5) * (1 / filterscale)) with a = -0.5, summed in
+ * order, divided by the sum, (int)(+-0.5 + w * 2^22) by sign.  ksize = 2 * ceil(support) + 1.
+ *    out[0] block bytes   out[1] workgroups per image   out[2] ksize_x   out[3] ksize_y   out[4] source bytes the taps read per image
+ *    (0 without table_out)   out[5], out[6] the kernel's output tile (width, height)   out[7] source rows read (0 without table_out)
+ * Checked before any GPU call (SBEV_EINVAL): null pointers, sizes < 1 or above 2^22 - 1, a ksize above SBEV_GEOM_KMAX (an axis shrunk
+ * by more than 3.5: refused, never truncated), a misaligned table / image_rows / src, a grid beyond 31 bits.
+ */
+#define SBEV_GEOM_KMAX 16
+int sbev_image_geom_plan(int H, int W, int fH, int fW, int resize_w, int resize_h, int crop_x, int crop_y, int flip, int32_t* table_out,
+                         int64_t* out);
+int sbev_image_geom(const void* src, void* dst, int n, int H, int W, int fH, int fW, const void* table, const void* image_rows,
+                    int n_transforms, sbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ operator modules without the built library raises -- there is no CPU / PyTorch f
 """
 from ._lib import load as load_library, SbevError, LIB_PATH   # noqa: F401
 
-__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW', 'ImageFrontEnd']
+__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW', 'ImageFrontEnd', 'ImageGeometry']
 
 
 def __getattr__(name):
@@ -25,4 +25,7 @@ def __getattr__(name):
     if name == 'ImageFrontEnd':
         from .image_front import ImageFrontEnd
         return ImageFrontEnd
+    if name == 'ImageGeometry':
+        from .image_geom import ImageGeometry
+        return ImageGeometry
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

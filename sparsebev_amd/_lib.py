@@ -182,6 +182,8 @@ SIGNATURES = {
     'sbev_image_front_plan': (ctypes.c_int, [ctypes.c_int] * 4 + [_c_i64p]),
     'sbev_image_front': (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_float)] * 2
                          + [ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    'sbev_image_geom_plan': (ctypes.c_int, [ctypes.c_int] * 9 + [_c_i32p, _c_i64p]),
+    'sbev_image_geom': (ctypes.c_int, [_vp, _vp] + [ctypes.c_int] * 5 + [_vp, _vp, ctypes.c_int, _vp]),
     'sbev_profile_read': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int]),
     'sbev_linear_splitk_plan': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'sbev_linear_f32_path': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),

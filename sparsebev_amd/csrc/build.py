@@ -44,6 +44,7 @@ UNITS = {
     'optim.hip': ['-ffp-contract=off'],
     # the image front end's normalised pixels equal torch's separate ops bit for bit: nothing contracted, a true division
     'image_front.hip': ['-ffp-contract=off'],
+    'image_geom.hip': [],                # integer arithmetic only: no float flags
     'decoder.hip': [],
     'row_chain.hip': [],                 # the row-local op chains of a layer (4x4x1 MFMA with A broadcast)
     # bit-exact projection: no FMA contraction anywhere in this file
