@@ -1001,6 +1001,21 @@ typedef struct sbev_decoder_weights {
 int64_t sbev_decoder_chain_pack_floats(const sbev_decoder_config* cfg);
 int sbev_decoder_chain_pack(const sbev_decoder_config* cfg, const sbev_decoder_weights* weights, float* out, sbev_stream_t stream);
 int sbev_decoder_row_chain(int enable);
+/* What one row-chain launch of `cfg` (B * Q = 1 .. 4096 rows) does, decided on the host from plain values: no device is touched, no
+ * pointer is needed.  kind: 0 = tail, 1 = front, 2 = attention chain; with_front: the tail goes on with the next layer's front;
+ * pair_ok: pair mode is allowed (switch on, fault word installed, workspace given); cus: the device's compute units (0: none -- no
+ * pairs).  Writes int32 words to out[0 .. capacity) and returns their number, -1 (SBEV_EINVAL) on an uncovered config or a short buffer:
+ *    0 pre (= kind)   1 rg: row groups of 4 rows per row block (1, 2, 4)   2 pair (0 / 1)   3 grid (workgroups)   4 dynamic LDS bytes
+ *    5 n_units        6 n_pairs (0 without pair mode)
+ *    7 warm: float offset into the sbev_decoder_chain_pack image of the weight span the launch streams   8 its 128-byte lines
+ *    9 float offset in the image of the launch's small vectors, copied to   10 vec_off,  11 vec_n: floats [vec_off, vec_off + vec_n)
+ *      of the kernels' LDS parameter block
+ * then the unit table of member 0 and, with pair = 1, of member 1 (the same number of units), 18 words per unit:
+ *    epilogue (0 ffn.0, 1 ffn.1, 2 / 3 branch layers, 4 output + refine_bbox, 5 position encoder, 6 in-projection, 7 attention
+ *    out-projection, 8 sampling Linear), first output column (in-projection), then the unit's two Linears a | b, 8 words each:
+ *    weights (float offset into the image, -1: none), LDS float offset and row stride of the input rows, KH (k-pieces per 64-column
+ *    group), items (= column groups x KH), chunks (16-k chunks per item), kh0, KHT (the Linear covers pieces [kh0, kh0 + KH) of KHT). */
+int sbev_decoder_chain_plan(const sbev_decoder_config* cfg, int kind, int with_front, int pair_ok, int cus, int32_t* out, int capacity);
 
 /* Pair mode of the tail chain (round 4).  A chain workgroup streams every weight of its chain through its CU's ~60 GB/s L2 path, so
  * where two workgroups per row block fit the device in ONE round (<= ~1000 rows at 8 rows per pair, <= ~2000 at 16, on 256 CUs) the

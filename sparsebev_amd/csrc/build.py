@@ -47,6 +47,7 @@ UNITS = {
     'image_geom.hip': [],                # integer arithmetic only: no float flags
     'decoder.hip': [],
     'row_chain.hip': [],                 # the row-local op chains of a layer (4x4x1 MFMA with A broadcast)
+    'fault_word.hip': [],                # host only: the sticky host-mapped fault word row_chain.hip and gemm_bf16s.hip report into
     # bit-exact projection: no FMA contraction anywhere in this file
     'project.hip': ['-ffp-contract=off'],
 }

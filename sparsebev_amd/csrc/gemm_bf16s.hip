@@ -1336,7 +1336,7 @@ __device__ __forceinline__ void dispatch_nfa(int nfa, Run&& run) {          // r
 }
 
 // a chunk-workgroup whose row tile never became complete within the poll bound (the device was shared: not every workgroup of the launch
-// was resident): counted here and in the host-mapped word the decoder's fault gate reads (csrc/row_chain.hip installs both pointers)
+// was resident): counted here and in the host-mapped word the decoder's fault gate reads (csrc/fault_word.hip installs the pointer: out_fold_install)
 __device__ unsigned g_fold_timeouts;
 __device__ unsigned* g_fold_fault_host;
 constexpr unsigned FOLD_POLL_LIMIT = 1u << 20;

@@ -19,9 +19,15 @@
 // item i goes to wave i % 8 in round i / 8 and leaves its partial sums in LDS slot i; the unit's epilogue (wave = row)
 // adds the k-halves in a fixed order, + bias, ReLU / residual / LayerNorm, and writes the next unit's input rows.
 // Results equal the op-by-op launches to fp32 round-off (other summation order), not bit for bit; DESIGN_HISTORY.md section 4.
+//
+// In this file: the kernels (row_chain_kernel<PRE, RG, PAIR> in 11 instantiations, pack_kernel, copy_pad_kernel), then the host side,
+// each thing described once: the table of the image's 12 matrices (kMats -> pack_map, the pack jobs, the warm spans), the table of the
+// instantiations (kInst -> launch, the LDS attribute, chain_lds_ready), and the plan of a launch (chain_plan: instantiation, grid, both
+// pair members' unit tables from ONE function of the share, warm span, small-vector range; pure host, exported as
+// sbev_decoder_chain_plan).  launch_chain_front / _attn / _tail make the plan, bind the image and the activations, launch.  The sticky
+// fault word the pair hand-off reports into lives in fault_word.hip; this file keeps its __device__ end (chain_pair_install).
 #include "sbev_common.hpp"
 #include "sample_point.hpp"
-#include <mutex>
 #include <atomic>
 #include <cstdlib>
 
@@ -420,7 +426,7 @@ __device__ __forceinline__ void gather4_raw(float (&v)[4], const float* P, int K
 // block -> pair map puts both members on one XCD under round-robin dispatch (speed only).  The counters are zeroed by the attention
 // chain of the same layer, which always runs between two tails on the stream (no memset node).
 __device__ unsigned g_chain_pair_timeouts;
-// ... and a STICKY fault word in pinned, device-mapped HOST memory (pair_fault_host() below installs the pointer once per process): a
+// ... and a STICKY fault word in pinned, device-mapped HOST memory (fault_word.hip installs the pointer through chain_pair_install, once per device): a
 // timed-out hand-off also bumps it with a system-scope atomic, so the host sees the fault WITHOUT synchronising the device -- at the next
 // sbev_decoder_forward / graph replay it is an error (SBEV_EFAULT), not eight silently wrong rows.  Read only on the timeout
 // path: no kernel argument, no register in the hot loop.
@@ -889,40 +895,97 @@ __global__ void copy_pad_kernel(const float* src, int n, float* dst, int slot) {
     if (i < slot) dst[i] = i < n ? src[i] : 0.f;
 }
 
+// ======================================================= host side =======================================================================
+using Cfg = sbev_decoder_config;
+
+// ---- the packed weight image, described once ------------------------------------------------------------------------------------------
+// The 12 matrices in image order: the member of sbev_decoder_weights, its rows N and its columns K.  pack_map, the pack jobs,
+// sbev_decoder_chain_pack_floats and the launches' warm spans ("matrices i .. j") all walk this one table.  Behind the matrices lie the
+// small vectors [tail | front | attention] at their PV_* offsets (the vecs[] table of sbev_decoder_chain_pack).
+enum Mat { M_FFN0, M_FFN1, M_CLS0, M_REG0, M_CLS3, M_REG2, M_CLS6, M_REG4, M_PE3, M_ATTN_IN, M_ATTN_OUT, M_SAMP, N_MAT };
+int so_cols(const Cfg& c) { return c.G * c.P * (3 + c.L); }      // the sampling Linear's rows: 3 offsets + L level logits per point
+int n_embed(const Cfg& c) { return c.D; }
+int n_ffn(const Cfg& c) { return c.ffn; }
+int n_cls(const Cfg& c) { return c.num_classes; }
+int n_code(const Cfg& c) { return c.code_size; }
+int n_qkv(const Cfg& c) { return c.attn_in_rows; }
+struct MatDesc {
+    const float* sbev_decoder_weights::*w;
+    int (*N)(const Cfg&);
+    int (*K)(const Cfg&);
+};
+const MatDesc kMats[N_MAT] = {
+    {&sbev_decoder_weights::ffn0_w, n_ffn, n_embed},      {&sbev_decoder_weights::ffn1_w, n_embed, n_ffn},
+    {&sbev_decoder_weights::cls0_w, n_embed, n_embed},    {&sbev_decoder_weights::reg0_w, n_embed, n_embed},
+    {&sbev_decoder_weights::cls3_w, n_embed, n_embed},    {&sbev_decoder_weights::reg2_w, n_embed, n_embed},
+    {&sbev_decoder_weights::cls6_w, n_cls, n_embed},      {&sbev_decoder_weights::reg4_w, n_code, n_embed},
+    {&sbev_decoder_weights::pe3_w, n_embed, n_embed},     {&sbev_decoder_weights::attn_in_w, n_qkv, n_embed},
+    {&sbev_decoder_weights::attn_out_w, n_embed, n_embed}, {&sbev_decoder_weights::samp_w, so_cols, n_embed}};
+
 long long packed_floats(int N, int K) { return (long long)((N + 63) / 64) * 64 * K; }
 
-struct PackMap {     // float offsets into the chain_pack blob
-    long long ffn0, ffn1, cls0, reg0, cls3, reg2, cls6, reg4, pe3, attn_in, attn_out, samp, vec, total;
+struct PackMap {     // float offsets into the chain_pack image: matrix i lies at [at[i], at[i + 1])
+    long long at[N_MAT + 1];
+    long long vec() const { return at[N_MAT]; }                      // the small vectors: [tail | front | attention], PV_* offsets
+    long long total() const { return at[N_MAT] + PV_IMAGE_FLOATS; }
+    int lines(int first, int last) const { return (int)((at[last + 1] - at[first]) / 32); }      // 128-byte lines of matrices first .. last
 };
-PackMap pack_map(const sbev_decoder_config& c) {
+PackMap pack_map(const Cfg& c) {
     PackMap m{};
-    long long o = 0;
-    auto put = [&](long long& slot, int N, int K) { slot = o; o += packed_floats(N, K); };
-    put(m.ffn0, c.ffn, c.D); put(m.ffn1, c.D, c.ffn);
-    put(m.cls0, c.D, c.D); put(m.reg0, c.D, c.D); put(m.cls3, c.D, c.D); put(m.reg2, c.D, c.D);
-    put(m.cls6, c.num_classes, c.D); put(m.reg4, c.code_size, c.D);
-    put(m.pe3, c.D, c.D); put(m.attn_in, c.attn_in_rows, c.D);
-    put(m.attn_out, c.D, c.D); put(m.samp, c.G * c.P * (3 + c.L), c.D);
-    m.vec = o;                     // the small vectors: [tail | front | attention], PV_* offsets
-    m.total = o + PV_IMAGE_FLOATS;
+    for (int i = 0; i < N_MAT; ++i) m.at[i + 1] = m.at[i] + packed_floats(kMats[i].N(c), kMats[i].K(c));
     return m;
 }
 
-// column groups [cg0, cg0 + ncg) of a packed [N, K] weight as items of K / KH k each.  kh = 0: K / 128 (the RG = 1 items)
-Lin lin(const float* wp, int in_off, int ld, int N, int K, int kh = 0, int cg0 = 0, int ncg = -1) {
-    const int KH = kh > 0 ? kh : K / 128;
-    const int all = (N + 63) / 64;
-    if (ncg < 0) ncg = all - cg0;
-    return Lin{wp + (long long)cg0 * K * 64, in_off, ld, KH, ncg * KH, K / (16 * KH), 0, KH};
+// ---- the instantiations, listed once ------------------------------------------------------------------------------------------------------
+// launch, the LDS-attribute raise and chain_lds_ready walk this table.  The kernels use 159 KB of dynamic LDS: the attribute is raised once
+// per device and instantiation (also from sbev_decoder_chain_pack, so that the first launch may already be inside a stream capture).
+struct Inst {
+    int pre, rg;
+    bool pair;
+    void (*kern)(ChainArgs);
+    int rows, lds;                                   // rows per row block (one workgroup, or one pair of them); dynamic LDS bytes
+    std::atomic<unsigned long long> raised;          // bit d: the attribute is raised on device d (a process may drive several devices)
+};
+template <int PRE, int RG, bool PAIR = false>
+Inst inst() { return Inst{PRE, RG, PAIR, row_chain_kernel<PRE, RG, PAIR>, Lay<RG>::R, Lay<RG>::LDS_TOTAL_FLOATS * 4, {0}}; }
+Inst kInst[] = {inst<PRE_SLABS, 1>(), inst<PRE_FRONT, 1>(), inst<PRE_ATT, 1>(), inst<PRE_SLABS, 2>(), inst<PRE_FRONT, 2>(), inst<PRE_ATT, 2>(),
+                inst<PRE_SLABS, 4>(), inst<PRE_FRONT, 4>(), inst<PRE_ATT, 4>(), inst<PRE_SLABS, 2, true>(), inst<PRE_SLABS, 4, true>()};
+Inst* find_inst(int pre, int rg, bool pair) {
+    for (Inst& i : kInst)
+        if (i.pre == pre && i.rg == rg && i.pair == pair) return &i;
+    return nullptr;
 }
-// k-half `half` of a packed [N, K] weight (pair mode): kh pieces of the half, i.e. pieces [half kh, half kh + kh) of 2 kh per row
-Lin lin_khalf(const float* wp, int in_off, int ld, int N, int K, int kh, int half) {
-    return Lin{wp, in_off, ld, kh, ((N + 63) / 64) * kh, K / (32 * kh), half * kh, 2 * kh};
+hipError_t raise_lds(Inst& i) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (i.raised.load(std::memory_order_acquire) & bit) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(i.kern), hipFuncAttributeMaxDynamicSharedMemorySize, i.lds);
+    if (e == hipSuccess) i.raised.fetch_or(bit, std::memory_order_release);
+    return e;
 }
-const Lin kNone{nullptr, 0, LDX, 1, 0, 8, 0, 1};
 
-// k-pieces per column group of a unit with `cgs` column groups in all: RG = 1 keeps 128-k items; RG > 1 aims at 8 items per
-// unit (one per wave; each piece at least 64 k = RDEPTH chunks)
+// ---- a launch, planned once (pure host: no HIP call below this line until "binding and launching") ----------------------------------
+// Lin / Unit with the weights as a float offset into the image (-1: none) instead of a pointer
+struct PLin { long long w; int in_off, ld, KH, items, chunks, kh0, KHT; };
+struct PUnit { PLin a, b; int epi, col0; };
+const PLin kNone{-1, 0, LDX, 1, 0, 8, 0, 1};
+
+struct ChainPlan {
+    int pre, rg, pair;           // the instantiation: the chain (Pre), row groups per row block, pair mode
+    unsigned grid;
+    int lds;                     // dynamic LDS bytes
+    int n_units;
+    PUnit units[2][8];           // [member]; units[1] in pair mode only (same count, same epilogues)
+    int n_pairs;
+    long long warm;              // the launch's packed weights: float offset of the span, ...
+    int warm_lines;              // ... its 128-byte lines
+    long long vec;               // the launch's small vectors: float offset in the image -> LDS parameter block [vec_off, vec_off + vec_n)
+    int vec_off, vec_n;
+};
+
+// k-pieces per column group of a unit in which THIS SHARE of the row block (see Share) computes `cgs` column groups in all: RG = 1 keeps
+// 128-k items; RG > 1 aims at 8 items per unit (one per wave; each piece at least 64 k = RDEPTH chunks)
 // -- <= 12 slots; cost of a choice = sum over its rounds of (chunks per item) x (1 for a round of 5 .. 8 items: two waves per SIMD
 // share the MFMA pipe; 1/2 for a last round of <= 4 items: waves 0 .. 3 sit on four different SIMDs)
 int pieces(int rg, int cgs, int K) {
@@ -950,58 +1013,131 @@ Offs offs(int rg) { return rg == 1 ? offs_of<1>() : rg == 2 ? offs_of<2>() : off
 // pair must be resident at once -- one workgroup per CU (88 KB of LDS and more) -- so the launch, 16 blocks per 8 pairs, has to
 // fit the device's CUs in one round: 8 rows per pair, <= 1024 rows on 256 CUs.  (16 rows per pair would reach 2048 rows, but
 // four row groups per weight chunk are MFMA-bound, not stream-bound: 88 vs 66 us for the single-workgroup tail at 1600 rows;
-// SBEV_CHAIN_PAIR16=1 enables it for A/B runs.)
-std::atomic<int> g_chain_pair{getenv("SBEV_NO_CHAIN_PAIR") ? 0 : 1};
-std::atomic<int> g_chain_pair_drop{0};
-// the sticky fault word (see g_chain_pair_fault_host): 64 bytes of pinned host memory mapped into the device, one per process (a process
-// drives one GPU: one process per GPU is the deployment model; with several devices the word is shared -- a fault on any of them stops
-// pair mode everywhere).  Installed before the first pair-mode launch on a device; nullptr when the allocation fails (the device-side
-// counter still works).
-std::atomic<unsigned> g_pair_fault_acked{0};
-std::atomic<int> g_pair_fault_warned{0};
-volatile unsigned* pair_fault_host() {
-    // NOT a function-local static initialised by the first call: that call may run where hipHostMalloc is illegal (a caller's stream
-    // capture around its first decoder call) and the failure would be cached for the life of the process -- a failed
-    // attempt is retried by the next call; sbev_init() (called when the Python binding loads the library) makes the first attempt early
-    static std::atomic<volatile unsigned*> word{nullptr};
-    static std::mutex mu;
-    volatile unsigned* w = word.load(std::memory_order_acquire);
-    if (w) return w;
-    std::lock_guard<std::mutex> lk(mu);
-    w = word.load(std::memory_order_acquire);
-    if (w) return w;
-    void* h = nullptr;
-    if (hipHostMalloc(&h, 64, hipHostMallocMapped) != hipSuccess || !h) {
-        const hipError_t e = hipGetLastError();
-        if (g_pair_fault_warned.exchange(1) == 0) {
-            sbev::set_error("pair-mode fault word: hipHostMalloc failed (%s) -- pair mode stays off until a later call succeeds (stream capture active? call sbev_init() first)",
-                            hipGetErrorString(e));
-            fprintf(stderr, "sparsebev_amd: %s\n", sbev_last_error());
-        }
-        return nullptr;
-    }
-    *static_cast<volatile unsigned*>(h) = 0u;
-    word.store(static_cast<volatile unsigned*>(h), std::memory_order_release);
-    return static_cast<volatile unsigned*>(h);
-}
-bool pair_fault_install() {            // this device's g_chain_pair_fault_host -> the word; once per device
-    static std::atomic<int> done[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    if (done[dev & 63].load(std::memory_order_acquire)) return true;
-    volatile unsigned* h = pair_fault_host();
-    if (!h) return false;
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, const_cast<unsigned*>(h), 0) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_chain_pair_fault_host), &d, sizeof(d)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (!sbev::out_fold_install(d)) { (void)hipGetLastError(); return false; }      // (the out-projection's in-launch fold reports into the same word)
-    done[dev & 63].store(1, std::memory_order_release);
-    return true;
-}
+// SBEV_CHAIN_PAIR16=1 enables it for A/B runs.)  pair_ok: the switch is on, the fault word is installed (no other way to report a
+// lost partner) and the caller gave the exchange workspace.
 int pair_blocks(long long rows, int rg) {
     const long long pairs = (rows + 4 * rg - 1) / (4 * rg);
     return (int)(16 * ((pairs + 7) / 8));
 }
+int pair_row_groups(long long rows, bool pair_ok, int cus) {
+    if (!pair_ok || rows > 256 * 16) return 0;
+    static const int max_rg = getenv("SBEV_CHAIN_PAIR16") ? 4 : 2;
+    for (int rg = 2; rg <= max_rg; rg *= 2)
+        if (pair_blocks(rows, rg) <= cus) return rg;
+    return 0;
+}
+
+// Who computes a unit table: the one workgroup of a row block, or one member of the pair that shares it.
+enum Share { WHOLE = -1, MEMBER0 = 0, MEMBER1 = 1 };
+
+struct UnitTables {
+    const Cfg& c;
+    const PackMap& m;
+    int rg;
+    Offs o;
+
+    // column groups [cg0, cg0 + ncg) of packed matrix `mat` as items of K / KH k each.  kh = 0: K / 128 (the RG = 1 items)
+    PLin lin(int mat, int in_off, int ld, int kh = 0, int cg0 = 0, int ncg = -1) const {
+        const int N = kMats[mat].N(c), K = kMats[mat].K(c);
+        const int KH = kh > 0 ? kh : K / 128;
+        if (ncg < 0) ncg = (N + 63) / 64 - cg0;
+        return PLin{m.at[mat] + (long long)cg0 * K * 64, in_off, ld, KH, ncg * KH, K / (16 * KH), 0, KH};
+    }
+    // k-half `half` of packed matrix `mat` (pair mode): kh pieces of the half, i.e. pieces [half kh, half kh + kh) of 2 kh per row
+    PLin lin_khalf(int mat, int in_off, int ld, int kh, int half) const {
+        const int N = kMats[mat].N(c), K = kMats[mat].K(c);
+        return PLin{m.at[mat], in_off, ld, kh, ((N + 63) / 64) * kh, K / (32 * kh), half * kh, 2 * kh};
+    }
+
+    // position encoder + attention in-projection (the front chain; the end of a tail with_front).  The position encoder runs where the
+    // regression branch ran (WHOLE, MEMBER1).  In-projection column groups: WHOLE all of them, in units of at most 8; MEMBER1 those from
+    // q0 onward -- it has the x rows in its LDS, member 0 gets them a hand-off (~1.5 us) later, so member 1 takes up to 8 column groups
+    // (one round of 16-chunk items) and member 0 the rest (5 of config 2's 13: 10 items of 8 chunks) -- and MEMBER0 those below q0; a
+    // member has exactly ONE in-projection unit, kNone where its share is empty.
+    int front_units(PUnit* u, int n, Share sh) const {
+        const int dcg = c.D / 64, qcg = (c.attn_in_rows + 63) / 64;
+        u[n++] = PUnit{sh != MEMBER0 ? lin(M_PE3, o.c, LDX, pieces(rg, dcg, c.D)) : kNone, kNone, EPI_PE3, 0};
+        static const int q0_forced = getenv("SBEV_CHAIN_PAIR_Q0") ? atoi(getenv("SBEV_CHAIN_PAIR_Q0")) : -1;      // A/B
+        const int q0 = q0_forced >= 0 && q0_forced <= qcg ? q0_forced : (qcg > 8 ? qcg - 8 : qcg / 2);
+        const int lo = sh == MEMBER1 ? q0 : 0, hi = sh == MEMBER0 ? q0 : qcg;
+        const int cut = sh == WHOLE ? 8 : qcg + 1;
+        if (sh != WHOLE && lo == hi) u[n++] = PUnit{kNone, kNone, EPI_QKV, lo * 64};
+        for (int cg0 = lo; cg0 < hi; cg0 += cut) {
+            const int n_here = hi - cg0 < cut ? hi - cg0 : cut;
+            u[n++] = PUnit{lin(M_ATTN_IN, o.x2, LDX, pieces(rg, n_here, c.D), cg0, n_here), kNone, EPI_QKV, cg0 * 64};
+        }
+        return n;
+    }
+
+    // The tail's unit table, written once as a function of the share (see "pair mode" above the kernel):
+    //   ffn.layers.0   WHOLE: all column groups; member s: half of them, from s x half on
+    //   ffn.layers.1   WHOLE: all of k (lin); member s: k-half s (lin_khalf) for all columns
+    //   branches       the classification side sits in Unit::a, the regression side in Unit::b; WHOLE carries both, MEMBER0 the
+    //                  classification side, MEMBER1 the regression side (the other Lin is kNone)
+    //   front          front_units
+    // Every pieces() call gets the column groups THIS SHARE computes in that unit: both branch sides count for WHOLE (2 dcg; 2 for the
+    // output unit), one side for a member (dcg; 1).  Both members get the same number of units and the same epilogue sequence.
+    int tail_units(PUnit* u, Share sh, bool with_front) const {
+        const int dcg = c.D / 64, fcg = c.ffn / 64;
+        const bool cls = sh != MEMBER1, reg = sh != MEMBER0;
+        const int sides = (cls ? 1 : 0) + (reg ? 1 : 0);
+        const int f_ncg = sh == WHOLE ? fcg : fcg / 2, f_cg0 = sh == WHOLE ? 0 : sh * f_ncg;
+        int n = 0;
+        u[n++] = PUnit{lin(M_FFN0, o.x2, LDX, pieces(rg, f_ncg, c.D), f_cg0, f_ncg), kNone, EPI_FFN0, 0};
+        u[n++] = PUnit{sh == WHOLE ? lin(M_FFN1, o.h, LDH, pieces(rg, dcg, c.ffn)) : lin_khalf(M_FFN1, o.h, LDH, pieces(rg, dcg, c.ffn / 2), sh),
+                       kNone, EPI_FFN1, 0};
+        const auto branch = [&](int mat_c, int in_c, int mat_r, int in_r, int cgs_side, int epi) {
+            const int kh = pieces(rg, sides * cgs_side, c.D);
+            return PUnit{cls ? lin(mat_c, in_c, LDX, kh) : kNone, reg ? lin(mat_r, in_r, LDX, kh) : kNone, epi, 0};
+        };
+        u[n++] = branch(M_CLS0, o.x3, M_REG0, o.x3, dcg, EPI_BR1);
+        u[n++] = branch(M_CLS3, o.c, M_REG2, o.r, dcg, EPI_BR2);
+        u[n++] = branch(M_CLS6, o.c, M_REG4, o.r, 1, EPI_OUT);
+        return with_front ? front_units(u, n, sh) : n;
+    }
+};
+
+// Everything a row-chain launch needs but its pointers, from plain values (sbev_decoder_chain_plan reports it; tests/test_chain_plan_host.py).
+// pre: the chain; with_front: the tail goes on with the next layer's front; pair_ok: see pair_row_groups; cus: the device's CU count
+ChainPlan chain_plan(const Cfg& c, int pre, bool with_front, bool pair_ok, int cus) {
+    const long long rows = (long long)c.B * c.Q;
+    const PackMap m = pack_map(c);
+    ChainPlan p{};
+    p.pre = pre;
+    const int prg = pre == PRE_SLABS ? pair_row_groups(rows, pair_ok, cus) : 0;
+    p.pair = prg != 0;
+    p.rg = p.pair ? prg : row_groups(rows);
+    const Inst& in = *find_inst(p.pre, p.rg, p.pair);
+    const long long blocks = (rows + in.rows - 1) / in.rows;
+    p.grid = p.pair ? (unsigned)pair_blocks(rows, p.rg) : (unsigned)blocks;
+    p.lds = in.lds;
+    p.n_pairs = p.pair ? (int)blocks : 0;
+    const UnitTables t{c, m, p.rg, offs(p.rg)};
+    int first = 0, last = 0;         // the launch streams matrices first .. last: one contiguous span of the image
+    if (pre == PRE_FRONT) {
+        p.n_units = t.front_units(p.units[0], 0, WHOLE);
+        first = M_PE3; last = M_ATTN_IN;
+        p.vec = m.vec() + PV_TAIL_END; p.vec_off = PV_TAIL_END; p.vec_n = PV_FRONT_END - PV_TAIL_END;
+    } else if (pre == PRE_ATT) {
+        p.units[0][0] = PUnit{t.lin(M_ATTN_OUT, t.o.x2, LDX, pieces(p.rg, c.D / 64, c.D)), kNone, EPI_AOUT, 0};
+        p.units[0][1] = PUnit{t.lin(M_SAMP, t.o.x3, LDX, pieces(p.rg, (so_cols(c) + 63) / 64, c.D)), kNone, EPI_SAMP, 0};
+        p.n_units = 2;
+        first = M_ATTN_OUT; last = M_SAMP;
+        p.vec = m.vec() + PV_FRONT_END; p.vec_off = 0; p.vec_n = PV_ATTN_END;
+    } else {
+        p.n_units = t.tail_units(p.units[0], p.pair ? MEMBER0 : WHOLE, with_front);
+        if (p.pair) (void)t.tail_units(p.units[1], MEMBER1, with_front);
+        first = M_FFN0; last = with_front ? M_ATTN_IN : M_REG4;
+        p.vec = m.vec(); p.vec_off = 0; p.vec_n = with_front ? PV_FRONT_END : PV_TAIL_END;
+    }
+    p.warm = m.at[first];
+    p.warm_lines = m.lines(first, last);
+    return p;
+}
+
+std::atomic<int> g_chain_pair{getenv("SBEV_NO_CHAIN_PAIR") ? 0 : 1};
+std::atomic<int> g_chain_pair_drop{0};
+
 int device_cus() {
     static std::atomic<int> cus[64];
     int dev = 0;
@@ -1013,15 +1149,6 @@ int device_cus() {
     }
     return v;
 }
-int pair_row_groups(long long rows) {
-    if (g_chain_pair.load(std::memory_order_relaxed) == 0 || rows > 256 * 16) return 0;
-    if (!pair_fault_install()) return 0;        // no way to report a lost partner: the single-workgroup tail
-    const int cus = device_cus();
-    static const int max_rg = getenv("SBEV_CHAIN_PAIR16") ? 4 : 2;
-    for (int rg = 2; rg <= max_rg; rg *= 2)
-        if (pair_blocks(rows, rg) <= cus) return rg;
-    return 0;
-}
 
 }  // namespace
 
@@ -1032,25 +1159,22 @@ long long chain_pair_floats(long long rows) { return 3 * (rows + 15) * DM; }
 // (+ 64 words behind the pair counters: the out-projection's fold counters, one per row tile -- zeroed by the same attention-chain loop)
 long long chain_pair_sync_words(long long rows) { return (rows + 7) / 8 + 64; }
 long long chain_fold_sync_offset(long long rows) { return (rows + 7) / 8; }
-bool chain_fault_word_ready() { return pair_fault_install(); }
 bool chain_pair_enabled() { return g_chain_pair.load(std::memory_order_relaxed) != 0; }
 
-// Install the fault word for the current device NOW (hipHostMalloc + hipMemcpyToSymbol: neither is legal under stream capture, and a
-// caller's first pair-mode launch may be a captured one): sbev_decoder_workspace_bytes calls this, which every caller runs before its
-// first forward / capture.  Quiet without a device.
-void chain_pair_prepare() {
-    if (g_chain_pair.load(std::memory_order_relaxed) != 0) (void)pair_fault_install();
+// this file's end of the decoder's sticky fault word (fault_word.hip): the device address of the host-mapped word for the pair hand-off's
+// timeout path, and the device-side count of those timeouts (-1: HIP error; synchronises the device)
+bool chain_pair_install(void* host_word_dev) {
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_chain_pair_fault_host), &host_word_dev, sizeof(host_word_dev)) == hipSuccess;
 }
-
-// hand-offs that timed out and were not acknowledged yet (host memory: no device synchronisation)
-unsigned chain_pair_faults_pending() {
-    volatile unsigned* h = pair_fault_host();
-    return h ? *h - g_pair_fault_acked.load(std::memory_order_relaxed) : 0u;
+long long chain_pair_timeouts() {
+    unsigned v = 0;
+    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_chain_pair_timeouts), sizeof(v)) != hipSuccess) return -1;
+    return (long long)v;
 }
 
 bool row_chain_supported(const sbev_decoder_config& c) {
     return c.D == DM && c.ffn == FF && c.code_size == 10 && c.num_classes >= 1 && c.num_classes <= 64 &&
-           c.attn_in_rows <= PV_QKV_PAD && c.G * c.P * (3 + c.L) <= 256 && (long long)c.B * c.Q < 0x7fffffffLL;
+           c.attn_in_rows <= PV_QKV_PAD && so_cols(c) <= 256 && (long long)c.B * c.Q < 0x7fffffffLL;
 }
 
 // Every workgroup streams every weight: that pays while the launch is a single round of workgroups (<= 256 CUs).
@@ -1062,60 +1186,54 @@ bool row_chain_pays(long long rows) {
     return rows <= limit && rows <= 256 * 16;
 }
 
-static void fill_common(ChainArgs& a, const sbev_decoder_config& c, float eps) {
+bool chain_lds_ready() {
+    for (Inst& i : kInst)
+        if (raise_lds(i) != hipSuccess) return false;
+    return true;
+}
+
+// ---- binding and launching: the plan's offsets onto the image, the activations, the kernel ----------------------------------------
+static ChainArgs chain_args(const Cfg& c, float eps) {
+    ChainArgs a{};
     a.M = (long long)c.B * c.Q;
     a.Q = c.Q;
     a.eps = eps;
     a.num_classes = c.num_classes;
     a.attn_in_rows = c.attn_in_rows;
-    a.soN = c.G * c.P * (3 + c.L);
+    a.soN = so_cols(c);
+    return a;
 }
 
-static int add_front(ChainArgs& a, int n, const sbev_decoder_config& c, const float* pk, const PackMap& m, int rg) {
-    const Offs o = offs(rg);
-    a.units[n++] = Unit{lin(pk + m.pe3, o.c, LDX, c.D, c.D, pieces(rg, c.D / 64, c.D)), kNone, EPI_PE3, 0};
-    const int ncg = (c.attn_in_rows + 63) / 64;
-    for (int cg0 = 0; cg0 < ncg; cg0 += 8) {
-        const int n_here = ncg - cg0 < 8 ? ncg - cg0 : 8;
-        a.units[n++] = Unit{lin(pk + m.attn_in, o.x2, LDX, c.attn_in_rows, c.D, pieces(rg, n_here, c.D), cg0, n_here), kNone, EPI_QKV, cg0 * 64};
-    }
-    return n;
-}
+static Lin bound(const PLin& l, const float* pk) { return Lin{l.w < 0 ? nullptr : pk + l.w, l.in_off, l.ld, l.KH, l.items, l.chunks, l.kh0, l.KHT}; }
 
-// the kernels use 159 KB of dynamic LDS: raised once per instantiation (also from sbev_decoder_chain_pack, so that the first
-// launch may already be inside a stream capture)
-template <int PRE, int RG, bool PAIR = false>
-static hipError_t lds_attr() {
-    static std::atomic<unsigned long long> done{0};      // bit d: raised on device d (a process may drive several devices)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(row_chain_kernel<PRE, RG, PAIR>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, Lay<RG>::LDS_TOTAL_FLOATS * 4);
-    if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
-    return e;
-}
-
-template <int PRE, int RG, bool PAIR = false>
-static int launch_t(const ChainArgs& a, hipStream_t s, const char* what) {
-    constexpr int R = Lay<RG>::R, LDS_TOTAL_FLOATS = Lay<RG>::LDS_TOTAL_FLOATS;
-    const hipError_t attr = lds_attr<PRE, RG, PAIR>();
+static int launch(const ChainPlan& p, ChainArgs& a, const float* pk, hipStream_t s, const char* what) {
+    Inst& in = *find_inst(p.pre, p.rg, p.pair);
+    const hipError_t attr = raise_lds(in);
     if (attr != hipSuccess) {
-        set_error("%s: hipFuncSetAttribute(%d bytes of LDS): %s", what, LDS_TOTAL_FLOATS * 4, hipGetErrorString(attr));
+        set_error("%s: hipFuncSetAttribute(%d bytes of LDS): %s", what, in.lds, hipGetErrorString(attr));
         return SBEV_ELAUNCH;
     }
+    for (int mem = 0; mem <= p.pair; ++mem)
+        for (int u = 0; u < p.n_units; ++u) {
+            const PUnit& pu = p.units[mem][u];
+            (mem ? a.units_b : a.units)[u] = Unit{bound(pu.a, pk), bound(pu.b, pk), pu.epi, pu.col0};
+        }
+    a.n_units = p.n_units;
+    a.pre = p.pre;
+    a.n_pairs = p.n_pairs;
     static const bool no_warm = getenv("SBEV_CHAIN_NO_WARM") != nullptr;       // A/B switch
-    ChainArgs b = a;
-    if (no_warm) b.warm_lines = 0;
+    a.warm = pk + p.warm;
+    a.warm_lines = no_warm ? 0 : p.warm_lines;
+    a.vec = pk + p.vec; a.vec_off = p.vec_off; a.vec_n = p.vec_n;
 #ifdef SBEV_CHAIN_TRACE
     static long long* tr = nullptr;
     static int calls = 0;
+    static const Inst* who[13];
     if (!tr) { (void)hipMalloc(&tr, 2 * 64 * 8 * 8 * 64); (void)hipMemset(tr, 0, 2 * 64 * 8 * 8 * 64); }
-    b.trace = tr + (calls % 64) * 512;
+    a.trace = tr + (calls % 64) * 512;
+    if (calls < 13) who[calls] = &in;
 #endif
-    const unsigned grid = PAIR ? (unsigned)pair_blocks(a.M, RG) : (unsigned)((a.M + R - 1) / R);
-    hipLaunchKernelGGL((row_chain_kernel<PRE, RG, PAIR>), dim3(grid), dim3(64 * NWAVE), LDS_TOTAL_FLOATS * 4, s, b);
+    hipLaunchKernelGGL(in.kern, dim3(p.grid), dim3(64 * NWAVE), in.lds, s, a);
 #ifdef SBEV_CHAIN_TRACE
     if (++calls == 13) {        // the first step's 13 launches
         (void)hipDeviceSynchronize();
@@ -1123,7 +1241,7 @@ static int launch_t(const ChainArgs& a, hipStream_t s, const char* what) {
         (void)hipMemcpy(h, tr, sizeof(h), hipMemcpyDeviceToHost);
         for (int c = 0; c < 13; ++c) {
             const long long* t = h + c * 512;
-            printf("launch %d (PRE %d RG %d PAIR %d; 10 ns ticks):", c, PRE, RG, (int)PAIR);
+            printf("launch %d (PRE %d RG %d PAIR %d; 10 ns ticks):", c, who[c]->pre, who[c]->rg, (int)who[c]->pair);
             for (int blk = 0; blk < 2; ++blk)
                 for (int w = 0; w < 8; w += 7) {
                     const long long* tb = t + blk * 64 * 512;
@@ -1137,48 +1255,19 @@ static int launch_t(const ChainArgs& a, hipStream_t s, const char* what) {
     return check_launch(what);
 }
 
-template <int RG>
-static bool lds_ready_rg() {
-    return lds_attr<PRE_SLABS, RG>() == hipSuccess && lds_attr<PRE_FRONT, RG>() == hipSuccess && lds_attr<PRE_ATT, RG>() == hipSuccess;
-}
-bool chain_lds_ready() {
-    return lds_ready_rg<1>() && lds_ready_rg<2>() && lds_ready_rg<4>() && lds_attr<PRE_SLABS, 2, true>() == hipSuccess &&
-           lds_attr<PRE_SLABS, 4, true>() == hipSuccess;
-}
-
-template <int RG>
-static int launch_rg(const ChainArgs& a, hipStream_t s, const char* what) {
-    return a.pre == PRE_SLABS ? launch_t<PRE_SLABS, RG>(a, s, what) : a.pre == PRE_FRONT ? launch_t<PRE_FRONT, RG>(a, s, what)
-                                                                                          : launch_t<PRE_ATT, RG>(a, s, what);
-}
-static int launch(const ChainArgs& a, int rg, hipStream_t s, const char* what) {
-    return rg == 1 ? launch_rg<1>(a, s, what) : rg == 2 ? launch_rg<2>(a, s, what) : launch_rg<4>(a, s, what);
-}
-
 // position encoder + attention in-projection of the FIRST layer (the later layers' run at the end of the previous tail)
 int launch_chain_front(const sbev_decoder_config& c, const sbev_decoder_weights& w, const float* bbox, const float* feat, float* x,
                        float* qkvt, float eps, hipStream_t s, uint32_t* skip_hdr) {
-    const PackMap m = pack_map(c);
-    ChainArgs a{};
-    fill_common(a, c, eps);
-    a.pre = PRE_FRONT;
+    ChainArgs a = chain_args(c, eps);
     a.bbox = bbox; a.feat = feat; a.x = x; a.qkvt = qkvt; a.skip_hdr = skip_hdr;
-    const int rg = row_groups(a.M);
-    a.n_units = add_front(a, 0, c, w.chain_pack, m, rg);
-    a.warm = w.chain_pack + m.pe3;
-    a.warm_lines = (int)((m.attn_out - m.pe3) / 32);
-    a.vec = w.chain_pack + m.vec + PV_TAIL_END; a.vec_off = PV_TAIL_END; a.vec_n = PV_FRONT_END - PV_TAIL_END;
-    return launch(a, rg, s, "row chain (front)");
+    return launch(chain_plan(c, PRE_FRONT, false, false, 0), a, w.chain_pack, s, "row chain (front)");
 }
 
 // attention out-projection + residual + norm1 -> x1, sampling Linear -> sample points -> projection (loc, level weights)
 int launch_chain_attn(const sbev_decoder_config& c, const sbev_decoder_weights& w, const float* att, const float* x, float* x1,
                       const float* bbox, const float* time_diff, const float* lidar2img, float* loc_bp, float* w_bp, float eps,
                       hipStream_t s, uint16_t* x1_frag, const float* x1_scale, uint32_t* pair_sync, const LazyPlan* touch, uint32_t* touch_need) {
-    const PackMap m = pack_map(c);
-    ChainArgs a{};
-    fill_common(a, c, eps);
-    a.pre = PRE_ATT;
+    ChainArgs a = chain_args(c, eps);
     a.zero_words = pair_sync;            // the arrival counters of this layer's tail (pair mode), zeroed here: chain_pair_sync_words()
     a.n_zero = pair_sync ? (int)chain_pair_sync_words(a.M) : 0;
     a.att = att; a.x = const_cast<float*>(x); a.x1_out = x1; a.so = nullptr;
@@ -1186,83 +1275,25 @@ int launch_chain_attn(const sbev_decoder_config& c, const sbev_decoder_weights& 
     a.proj = sbev_ops::sample_point_args(bbox, time_diff, lidar2img, c.pc_range, c.B, c.Q, c.T, c.N, c.G, c.P, c.L, c.image_h, c.image_w,
                                          c.eps_homo, loc_bp, w_bp);
     if (touch && touch_need) sbev_ops::sample_point_touch(a.proj, *touch, c.hw, touch_need);      // on-demand relayout: mark what the points read
-    const int rg = row_groups(a.M);
-    const Offs o = offs(rg);
-    a.units[0] = Unit{lin(w.chain_pack + m.attn_out, o.x2, LDX, c.D, c.D, pieces(rg, c.D / 64, c.D)), kNone, EPI_AOUT, 0};
-    a.units[1] = Unit{lin(w.chain_pack + m.samp, o.x3, LDX, a.soN, c.D, pieces(rg, (a.soN + 63) / 64, c.D)), kNone, EPI_SAMP, 0};
-    a.n_units = 2;
-    a.warm = w.chain_pack + m.attn_out;
-    a.warm_lines = (int)((m.vec - m.attn_out) / 32);
-    a.vec = w.chain_pack + m.vec + PV_FRONT_END; a.vec_off = 0; a.vec_n = PV_ATTN_END;
-    return launch(a, rg, s, "row chain (attention)");
+    return launch(chain_plan(c, PRE_ATT, false, false, 0), a, w.chain_pack, s, "row chain (attention)");
 }
 
 // out_proj slabs -> norm2 -> ffn -> norm3 -> branches -> refine_bbox [-> the next layer's position encoder + in-projection]
 int launch_chain_tail(const sbev_decoder_config& c, const sbev_decoder_weights& w, const float* slabs, int splits, const float* x1,
                       const float* bbox, const float* vel_div, float* x3, float* cls_out, float* box_out, int with_front, float* x,
                       float* qkvt, float eps, hipStream_t s, float* pair_x, uint32_t* pair_sync) {
-    const PackMap m = pack_map(c);
-    const float* pk = w.chain_pack;
-    ChainArgs a{};
-    fill_common(a, c, eps);
-    a.pre = PRE_SLABS;
+    ChainArgs a = chain_args(c, eps);
     a.slabs = slabs; a.splits = splits; a.x1 = x1; a.bbox = bbox; a.vel_div = vel_div;
     a.x3 = x3; a.cls_out = cls_out; a.box_out = box_out; a.front = with_front; a.x = x; a.qkvt = qkvt;
-    a.warm = pk + m.ffn0;
-    a.warm_lines = (int)(((with_front ? m.attn_out : m.pe3) - m.ffn0) / 32);
-    a.vec = pk + m.vec; a.vec_off = 0; a.vec_n = with_front ? PV_FRONT_END : PV_TAIL_END;
-    const int dcg = c.D / 64;
-    const int prg = pair_x && pair_sync ? pair_row_groups(a.M) : 0;
-    if (prg) {
-        // pair mode: two workgroups per row block, each with its own unit table (see "pair mode" above the kernel)
-        const int rg = prg;
-        const Offs o = offs(rg);
-        const int half_cg = c.ffn / 128;                                   // column groups of half the hidden layer
-        const int kh1 = pieces(rg, dcg, c.ffn / 2);                        // k-pieces of a member's half of ffn.layers.1
-        // in-projection: member 1 has the x rows in its LDS, member 0 gets them a hand-off (~1.5 us) later -- so member 1 takes up to
-        // 8 column groups (one round of 16-chunk items) and member 0 the rest (5 of config 2's 13: 10 items of 8 chunks)
-        static const int q0_forced = getenv("SBEV_CHAIN_PAIR_Q0") ? atoi(getenv("SBEV_CHAIN_PAIR_Q0")) : -1;      // A/B
-        const int qcg = (c.attn_in_rows + 63) / 64;
-        const int q0 = q0_forced >= 0 && q0_forced <= qcg ? q0_forced : (qcg > 8 ? qcg - 8 : qcg / 2);
-        int n = 0;
-        for (int mem = 0; mem < 2; ++mem) {
-            Unit* u = mem ? a.units_b : a.units;
-            n = 0;
-            u[n++] = Unit{lin(pk + m.ffn0, o.x2, LDX, c.ffn, c.D, pieces(rg, half_cg, c.D), mem * half_cg, half_cg), kNone, EPI_FFN0, 0};
-            u[n++] = Unit{lin_khalf(pk + m.ffn1, o.h, LDH, c.D, c.ffn, kh1, mem), kNone, EPI_FFN1, 0};
-            const Lin br1 = lin(pk + (mem ? m.reg0 : m.cls0), o.x3, LDX, c.D, c.D, pieces(rg, dcg, c.D));
-            const Lin br2 = lin(pk + (mem ? m.reg2 : m.cls3), mem ? o.r : o.c, LDX, c.D, c.D, pieces(rg, dcg, c.D));
-            const Lin out = mem ? lin(pk + m.reg4, o.r, LDX, c.code_size, c.D, pieces(rg, 1, c.D)) : lin(pk + m.cls6, o.c, LDX, c.num_classes, c.D, pieces(rg, 1, c.D));
-            u[n++] = mem ? Unit{kNone, br1, EPI_BR1, 0} : Unit{br1, kNone, EPI_BR1, 0};
-            u[n++] = mem ? Unit{kNone, br2, EPI_BR2, 0} : Unit{br2, kNone, EPI_BR2, 0};
-            u[n++] = mem ? Unit{kNone, out, EPI_OUT, 0} : Unit{out, kNone, EPI_OUT, 0};
-            if (with_front) {
-                u[n++] = Unit{mem ? lin(pk + m.pe3, o.c, LDX, c.D, c.D, pieces(rg, dcg, c.D)) : kNone, kNone, EPI_PE3, 0};
-                const int cg0 = mem ? q0 : 0, ncg = mem ? qcg - q0 : q0;
-                u[n++] = Unit{ncg > 0 ? lin(pk + m.attn_in, o.x2, LDX, c.attn_in_rows, c.D, pieces(rg, ncg, c.D), cg0, ncg) : kNone, kNone, EPI_QKV, cg0 * 64};
-            }
-        }
-        a.n_units = n;
-        a.n_pairs = (int)((a.M + 4 * rg - 1) / (4 * rg));
+    // pair mode: allowed while the switch is on, the workspace was given and a lost partner can be reported (the fault word is installed)
+    const bool pair_ok = pair_x && pair_sync && chain_pair_enabled() && a.M <= 256 * 16 && chain_fault_word_ready();
+    const ChainPlan p = chain_plan(c, PRE_SLABS, with_front != 0, pair_ok, pair_ok ? device_cus() : 0);
+    if (p.pair) {
         a.pair_x = pair_x;
         a.pair_sync = pair_sync;
         a.debug_drop = g_chain_pair_drop.load(std::memory_order_relaxed);
-        return rg == 2 ? launch_t<PRE_SLABS, 2, true>(a, s, "row chain (tail, pairs)") : launch_t<PRE_SLABS, 4, true>(a, s, "row chain (tail, pairs)");
     }
-    int n = 0;
-    const int rg = row_groups(a.M);
-    const Offs o = offs(rg);
-    a.units[n++] = Unit{lin(pk + m.ffn0, o.x2, LDX, c.ffn, c.D, pieces(rg, c.ffn / 64, c.D)), kNone, EPI_FFN0, 0};
-    a.units[n++] = Unit{lin(pk + m.ffn1, o.h, LDH, c.D, c.ffn, pieces(rg, dcg, c.ffn)), kNone, EPI_FFN1, 0};
-    a.units[n++] = Unit{lin(pk + m.cls0, o.x3, LDX, c.D, c.D, pieces(rg, 2 * dcg, c.D)), lin(pk + m.reg0, o.x3, LDX, c.D, c.D, pieces(rg, 2 * dcg, c.D)),
-                        EPI_BR1, 0};
-    a.units[n++] = Unit{lin(pk + m.cls3, o.c, LDX, c.D, c.D, pieces(rg, 2 * dcg, c.D)), lin(pk + m.reg2, o.r, LDX, c.D, c.D, pieces(rg, 2 * dcg, c.D)),
-                        EPI_BR2, 0};
-    a.units[n++] = Unit{lin(pk + m.cls6, o.c, LDX, c.num_classes, c.D, pieces(rg, 2, c.D)), lin(pk + m.reg4, o.r, LDX, c.code_size, c.D, pieces(rg, 2, c.D)),
-                        EPI_OUT, 0};
-    if (with_front) n = add_front(a, n, c, pk, m, rg);
-    a.n_units = n;
-    return launch(a, rg, s, "row chain (tail)");
+    return launch(p, a, w.chain_pack, s, p.pair ? "row chain (tail, pairs)" : "row chain (tail)");
 }
 
 }  // namespace sbev
@@ -1274,41 +1305,30 @@ extern "C" int sbev_decoder_chain_pair(int enable) { return g_chain_pair.exchang
 // of that pair are garbage, every other row is unaffected, the launch ends); returns the previous setting
 extern "C" int sbev_debug_chain_pair_drop(int enable) { return g_chain_pair_drop.exchange(enable != 0 ? 1 : 0); }
 
-// partners that did not show up within the poll bound since the library was loaded (0 unless the GPU was shared with something
-// that kept half of a pair from being scheduled for about a second); synchronises the device
-extern "C" int64_t sbev_decoder_chain_pair_timeouts(void) {
-    unsigned v = 0;
-    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_chain_pair_timeouts), sizeof(v)) != hipSuccess) return -1;
-    const long long f = sbev::out_fold_timeouts();          // (+ row tiles of the out-projection's in-launch fold that never completed)
-    if (f < 0) return -1;
-    return (int64_t)v + f;
-}
-
-// the sticky fault word: timed-out hand-offs since the last acknowledgement, read from pinned host memory (NO synchronisation; a fault
-// becomes visible once the faulting launch has run, ~1 s after its partner went missing)
-extern "C" int64_t sbev_decoder_chain_pair_faults(void) { return (int64_t)sbev::chain_pair_faults_pending(); }
-// One-time per-device setup that must not happen inside a caller's stream capture: the pair tail's host-mapped fault word (hipHostMalloc +
-// hipMemcpyToSymbol).  The Python binding calls it when it loads the library on a GPU box; C callers call it once per device before their
-// first capture (sbev_decoder_workspace_bytes still does the same lazily, and a failed attempt is retried by later calls).
-extern "C" int sbev_init(void) {
-    if (g_chain_pair.load(std::memory_order_relaxed) == 0) return SBEV_OK;
-    if (!pair_fault_install()) {
-        sbev::set_error("sbev_init: could not install the pair-mode fault word on the current device (pair mode stays off until a later attempt succeeds)");
-        return SBEV_ELAUNCH;
-    }
-    return SBEV_OK;
-}
-// acknowledge them (the caller has dealt with the invalid step): sbev_decoder_forward accepts calls again.  Returns how many there were.
-extern "C" int64_t sbev_decoder_chain_pair_faults_ack(void) {
-    volatile unsigned* h = pair_fault_host();
-    if (!h) return 0;
-    const unsigned now = *h;
-    return (int64_t)(now - g_pair_fault_acked.exchange(now));
-}
-
 extern "C" int64_t sbev_decoder_chain_pack_floats(const sbev_decoder_config* cfg) {
     if (!cfg || !sbev::row_chain_supported(*cfg)) return 0;
-    return pack_map(*cfg).total;
+    return pack_map(*cfg).total();
+}
+
+// chain_plan's answer as int32 words (layout: include/sbev_hip.h).  Touches no device
+extern "C" int sbev_decoder_chain_plan(const sbev_decoder_config* cfg, int kind, int with_front, int pair_ok, int cus, int32_t* out, int capacity) {
+    SBEV_REQUIRE(cfg && sbev::row_chain_supported(*cfg) && cfg->B >= 1 && cfg->Q >= 1 && (long long)cfg->B * cfg->Q <= 256 * 16 &&
+                     kind >= PRE_SLABS && kind <= PRE_ATT && cus >= 0,
+                 "sbev_decoder_chain_plan: config not covered by the row chains (1 .. 4096 rows), or kind / cus out of range");
+    const ChainPlan p = chain_plan(*cfg, kind, with_front != 0, pair_ok != 0, cus);
+    const int members = p.pair ? 2 : 1;
+    const long long words = 12 + 18LL * members * p.n_units;
+    SBEV_REQUIRE(out && capacity >= words, "sbev_decoder_chain_plan: %lld words needed", words);
+    for (int v : {p.pre, p.rg, p.pair, (int)p.grid, p.lds, p.n_units, p.n_pairs, (int)p.warm, p.warm_lines, (int)p.vec, p.vec_off, p.vec_n}) *out++ = v;
+    for (int mem = 0; mem < members; ++mem)
+        for (int u = 0; u < p.n_units; ++u) {
+            const PUnit& pu = p.units[mem][u];
+            *out++ = pu.epi;
+            *out++ = pu.col0;
+            for (const PLin* l : {&pu.a, &pu.b})
+                for (int v : {(int)l->w, l->in_off, l->ld, l->KH, l->items, l->chunks, l->kh0, l->KHT}) *out++ = v;
+        }
+    return (int)words;
 }
 
 extern "C" int sbev_decoder_chain_pack(const sbev_decoder_config* cfg, const sbev_decoder_weights* w, float* out, sbev_stream_t stream) {
@@ -1319,21 +1339,17 @@ extern "C" int sbev_decoder_chain_pack(const sbev_decoder_config* cfg, const sbe
     const PackMap m = pack_map(c);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     SBEV_REQUIRE(sbev::chain_lds_ready(), "sbev_decoder_chain_pack: the device refuses %d bytes of LDS per workgroup", Lay<1>::LDS_TOTAL_FLOATS * 4);
-    struct Job { const float* W; long long off; int N, K; };
-    const Job jobs[12] = {{w->ffn0_w, m.ffn0, c.ffn, c.D}, {w->ffn1_w, m.ffn1, c.D, c.ffn}, {w->cls0_w, m.cls0, c.D, c.D},
-                          {w->reg0_w, m.reg0, c.D, c.D}, {w->cls3_w, m.cls3, c.D, c.D}, {w->reg2_w, m.reg2, c.D, c.D},
-                          {w->cls6_w, m.cls6, c.num_classes, c.D}, {w->reg4_w, m.reg4, c.code_size, c.D}, {w->pe3_w, m.pe3, c.D, c.D},
-                          {w->attn_in_w, m.attn_in, c.attn_in_rows, c.D}, {w->attn_out_w, m.attn_out, c.D, c.D},
-                          {w->samp_w, m.samp, c.G * c.P * (3 + c.L), c.D}};
-    for (const Job& j : jobs) {
-        SBEV_REQUIRE(j.W && (((uintptr_t)j.W) & 15) == 0, "sbev_decoder_chain_pack: null / unaligned weight");
-        const long long n4 = (long long)((j.N + 63) / 64) * j.K * 16;
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, j.W, (long long)j.K, j.N, j.K, out + j.off);
+    for (int i = 0; i < N_MAT; ++i) {
+        const float* W = w->*kMats[i].w;
+        const int N = kMats[i].N(c), K = kMats[i].K(c);
+        SBEV_REQUIRE(W && (((uintptr_t)W) & 15) == 0, "sbev_decoder_chain_pack: null / unaligned weight");
+        const long long n4 = (long long)((N + 63) / 64) * K * 16;
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, W, (long long)K, N, K, out + m.at[i]);
     }
     // the small vectors, zero-padded to their slots
-    float* pv = out + m.vec;
+    float* pv = out + m.vec();
     struct Vec { const float* p; int off, n, slot; };
-    const int soN = c.G * c.P * (3 + c.L);
+    const int soN = so_cols(c);
     const Vec vecs[] = {
         {w->op_b, PV_OP_B, c.D, 256}, {w->norm2_g, PV_N2G, c.D, 256}, {w->norm2_b, PV_N2B, c.D, 256}, {w->ffn0_b, PV_FFN0_B, c.ffn, 512},
         {w->ffn1_b, PV_FFN1_B, c.D, 256}, {w->norm3_g, PV_N3G, c.D, 256}, {w->norm3_b, PV_N3B, c.D, 256},

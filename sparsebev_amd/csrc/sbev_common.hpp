@@ -223,6 +223,10 @@ long long chain_pair_floats(long long rows);         // pair mode of the tail: e
 long long chain_pair_sync_words(long long rows);
 long long chain_fold_sync_offset(long long rows);    // the out-projection's fold counters inside the same zeroed block (64 words)
 bool chain_pair_enabled();                           // sbev_decoder_chain_pair's current setting (the in-launch hand-offs' master switch)
+bool chain_pair_install(void* host_word_dev);        // the pair hand-off's end of the fault word (as out_fold_install / out_fold_timeouts)
+long long chain_pair_timeouts();
+
+// fault_word.hip: the decoder's sticky host-mapped fault word (the pair hand-off and the out-projection's fold report into it)
 bool chain_fault_word_ready();                       // the host-mapped fault word is installed on the current device (never under capture: sbev_init)
 void chain_pair_prepare();                          // install the pair tail's host-mapped fault word for the current device (outside any capture)
 unsigned chain_pair_faults_pending();               // pair hand-offs that timed out and were not acknowledged (host word, no sync)
