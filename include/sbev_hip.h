@@ -1305,6 +1305,45 @@ int sbev_image_geom_plan(int H, int W, int fH, int fW, int resize_w, int resize_
 int sbev_image_geom(const void* src, void* dst, int n, int H, int W, int fH, int fW, const void* table, const void* image_rows,
                     int n_transforms, sbev_stream_t stream);
 
+/*
+ * The FPN neck between the backbone and the decoder, inference only: L + 1 launches for L input levels on v_mfma_f32_32x32x16_f16.
+ * Replaces: mmdet's FPN forward as the detector configures it (in_channels = the backbone's stages, out_channels = 256, num_outs levels,
+ *           no extra convolutions) under fp16 autocast (models/sparsebev.py:46): 2 L convolutions, L - 1 interpolate + add pairs and
+ *           the casts around them, each a launch of its own, and the NCHW -> channels-last relayout in front of the decoder.
+ * Levels l = 0 .. L - 1, finest first, described by chw = {Cin_0, H_0, W_0, Cin_1, ...}; n images.  Everything is channels-last:
+ *   inputs[l]  [n, H_l, W_l, Cin_l]  SBEV_F16 or SBEV_F32 (one dtype for all levels)
+ *   outs[o]    [n, H_o, W_o, 256]    SBEV_F16 or SBEV_F32, o = 0 .. num_outs - 1; every element is stored by the call
+ *   workspace  the merged laterals M_l as fp16 [n, H_l, W_l, 256], level after level (out[2] bytes of the plan); left valid for the caller
+ * Arithmetic: operands are fp16 -- fp32 inputs and the fp32 weights are rounded once, to nearest even --, products are accumulated in
+ * fp32 on the matrix core, biases are fp32.
+ *   M_{L-1} = fp16(conv1x1(C_{L-1}) + b);   M_l = fp16((conv1x1(C_l) + b_l) + float(M_{l+1}[nearest])), the sum in fp32, one rounding
+ *   nearest: F.interpolate(size = (H_l, W_l), mode = 'nearest') for any pair of sizes: source index min(floor(dst * float32(in / out)),
+ *            in - 1) with the product rounded in float32
+ *   outs[l] = conv3x3(M_l, zero pad 1) + b_l in fp32, stored as it is or rounded once to fp16
+ *   outs[L - 1 + e], e = 1 .. num_outs - L: rows 0, 2^e, .. and columns 0, 2^e, .. of outs[L - 1] (F.max_pool2d(prev, 1, stride = 2)
+ *            applied e times), [n, ceil(H / 2^e), ceil(W / 2^e), 256], written by the same launch
+ * Weights: sbev_fpn_pack_weights rounds lateral_w[l] [256, Cin_l, 1, 1] and fpn_w[l] [256, 256, 3, 3] (contiguous, w_dtype SBEV_F32 or
+ * SBEV_F16, device memory) to fp16 in MFMA fragment order into `pack` (out[1] bytes of the plan, device memory); 2 L small launches,
+ * to be repeated whenever a weight changes.  Biases are read as they are: lateral_bias[l], fpn_bias[l] fp32 [256] on the device.
+ * The pointer lists are host arrays, read during the call.
+ * sbev_fpn_plan (pure host): out[SBEV_FPN_PLAN_WORDS]:
+ *    0 launches of a forward (L + 1; 0 for n == 0)   1 pack bytes   2 workspace bytes   3 pixels of all merged laterals
+ *    4 workgroups of the convolution launch   5 .. 8 workgroups of the lateral launch of level 0 .. 3 (128 pixels each)
+ *    9 extra levels   10 + 2 (e - 1), 11 + 2 (e - 1): height and width of extra level e   the rest zero
+ * Checked before any GPU call (SBEV_EINVAL): L outside 1 .. SBEV_FPN_MAX_IN, num_outs outside L .. SBEV_FPN_MAX_OUT, n < 0, Cin_l not a
+ * multiple of 32 in 32 .. 65536, an empty plane or a side above 32767, more pixels than 32-bit indices hold, a dtype not listed; then
+ * n == 0 answers SBEV_OK; then null pointers; then 16-byte alignment of inputs, outs, pack and workspace (4-byte of the biases).
+ */
+#define SBEV_FPN_MAX_IN 4
+#define SBEV_FPN_MAX_OUT 5
+#define SBEV_FPN_PLAN_WORDS 18
+int sbev_fpn_plan(int n_levels, const int32_t* chw, int64_t n, int num_outs, int64_t* out);
+int sbev_fpn_pack_weights(int n_levels, const int32_t* chw, const void* const* lateral_w, const void* const* fpn_w, int w_dtype, void* pack,
+                          sbev_stream_t stream);
+int sbev_fpn_forward(int n_levels, const int32_t* chw, int64_t n, int num_outs, const void* const* inputs, int in_dtype, const void* pack,
+                     const float* const* lateral_bias, const float* const* fpn_bias, void* workspace, void* const* outs, int out_dtype,
+                     sbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

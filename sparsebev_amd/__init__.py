@@ -8,7 +8,7 @@ operator modules without the built library raises -- there is no CPU / PyTorch f
 """
 from ._lib import load as load_library, SbevError, LIB_PATH   # noqa: F401
 
-__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW', 'ImageFrontEnd', 'ImageGeometry']
+__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW', 'ImageFrontEnd', 'ImageGeometry', 'FPNNeck']
 
 
 def __getattr__(name):
@@ -28,4 +28,7 @@ def __getattr__(name):
     if name == 'ImageGeometry':
         from .image_geom import ImageGeometry
         return ImageGeometry
+    if name == 'FPNNeck':
+        from .fpn import FPNNeck
+        return FPNNeck
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

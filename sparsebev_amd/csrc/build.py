@@ -45,6 +45,7 @@ UNITS = {
     # the image front end's normalised pixels equal torch's separate ops bit for bit: nothing contracted, a true division
     'image_front.hip': ['-ffp-contract=off'],
     'image_geom.hip': [],                # integer arithmetic only: no float flags
+    'fpn.hip': [],                       # the FPN neck: fp16 MFMA, fp32 accumulate; single fp32 multiplies and adds, nothing to contract
     'decoder.hip': [],
     'row_chain.hip': [],                 # the row-local op chains of a layer (4x4x1 MFMA with A broadcast)
     'fault_word.hip': [],                # host only: the sticky host-mapped fault word row_chain.hip and gemm_bf16s.hip report into
