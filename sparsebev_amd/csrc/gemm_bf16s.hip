@@ -708,8 +708,8 @@ struct GenWsArgs {
     const float* xscale;         // fp16 modes: {2^ex, 2^-ex}
     // on-demand relayout (round 6): layers 1..5 find and move the feature units their sample points marked and no earlier launch of the
     // step moved -- a few hundred 16-KB units at config 2.  As a launch of its own that is 7-20 us of launch + dependent round trips between
-    // the attention chain and this GEMM; here every workgroup does its share BEFORE its first request of the GEMM (the only kernel between
-    // the marks and the gather that does not touch the features): one round trip for the flags, a wave per found unit.
+    // the attention chain and this GEMM; here every workgroup does its share in its prologue, UNDER its first task's weight load (the only
+    // kernel between the marks and the gather that does not touch the features): one round trip for the flags, a wave per found unit.
     int lazy_on, lazy_esize;
     LazyArgs lazy;
     const uint32_t* skip_hdr;    // layer 0 of a step with a prefix cache (sbev_common.hpp: prefix_clean; never with lazy_on), else null
@@ -753,17 +753,9 @@ __global__ __launch_bounds__(512) void gemm_f16s_gen_ws_kernel(const GenWsArgs a
     const unsigned ldyb = (unsigned)(a.ldy * 4);
     [[maybe_unused]] const int tid = (int)threadIdx.x;
     SBEV_WGTIME(1, 0)
-    if (a.lazy_on) {
-        // (LDS: 8 wave tiles of 8448 B, then the list of up to 4 x 512 units and its counter -- 76 KB of the 128-KB ring, before any DMA)
-        float* wt = reinterpret_cast<float*>(lds);
-        unsigned* list = reinterpret_cast<unsigned*>(lds + 8 * (LZ_TS * WLD * 4));
-        unsigned* n_list = list + 4 * 512;
-        if (a.lazy_esize == 4) lazy_scan_share<float>(a.lazy, blockIdx.x, gridDim.x, 512, wt, list, n_list);
-        else lazy_scan_share<unsigned short>(a.lazy, blockIdx.x, gridDim.x, 512, wt, list, n_list);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the counted waits below start from "nothing outstanding")
-        __syncthreads();
-    }
 
+    // Two bodies, chosen once per launch: LAZY (a.lazy_on: layers 1..5 of a step with on-demand relayout) runs the workgroup's share of
+    // the scan UNDER its first task's weight load; the other one is the kernel as it was before the scan moved in here.
     // One barrier per fragment, all eight waves in the same phase.  (Tried, measured, not kept: the two waves of a SIMD half a fragment
     // apart -- the second group meeting the barrier in the MIDDLE of its fragment, so that one wave's boundary work lies beside its partner's
     // MFMA stream -- and the LDS-DMA issued by one group only: 49.0 vs 49.3 us at c2, 189 vs 190 at c3.  The kernel is power-capped, not
@@ -772,10 +764,43 @@ __global__ __launch_bounds__(512) void gemm_f16s_gen_ws_kernel(const GenWsArgs a
     // make the wait longer); after it every wave refills slot (i + 3) % 4 = (i - 1) % 4, which everybody has finished reading.  The stores of
     // fragment i - 1 ride in the first half of fragment i: behind the barrier, never in front of the counted wait (hipcc otherwise sinks them
     // there and the wait sits out their write latency).
-    {
-        for (int task = (int)xcd_contiguous(blockIdx.x, gridDim.x); task < a.ntask; task += (int)gridDim.x) {
+    auto run = [&](auto lazy_c) {
+        constexpr bool LAZY = decltype(lazy_c)::value;
+        // ---- a wave's weights: 32 columns x K of column tile ct, both images -> 128 registers
+        bf16x8 wf[WS_KS][2];
+        auto load_w = [&](int ct) {
+            const unsigned short* wb = a.Ws + ((long long)(ct * 8 + wave) * (WS_KS * 2) * 64 + lane) * 8;
+#pragma unroll
+            for (int ks = 0; ks < WS_KS; ++ks)
+#pragma unroll
+                for (int img = 0; img < 2; ++img) wf[ks][img] = *reinterpret_cast<const bf16x8*>(wb + (ks * 2 + img) * 512);
+        };
+        int task = (int)xcd_contiguous(blockIdx.x, gridDim.x);
+        [[maybe_unused]] bool w_under_scan = false;                       // LAZY: the next task's weights are already in their registers
+        if constexpr (LAZY) {
+            // The workgroup's share of the relayout scan, with the first task's weight load in flight over it.  The weight load is the
+            // long pole of the prologue (all workgroups together: 67 MB) and the scan is a chain of two dependent round trips that
+            // touches no weight register and no byte the GEMM reads: the flag requests go first, the 32 weight requests behind them, the
+            // units' loads queue behind the weights -- which the first MFMA needs anyway.
+            // (LDS: 8 wave tiles of 8448 B, then the list of up to 4 x 512 units and its counter -- 76 KB of the 128-KB ring, before any DMA)
+            float* wt = reinterpret_cast<float*>(lds);
+            unsigned* list = reinterpret_cast<unsigned*>(lds + 8 * (LZ_TS * WLD * 4));
+            unsigned* n_list = list + 4 * 512;
+            // (a workgroup without a task requests column tile 0's weights for nothing: an unconditional request keeps the waits of
+            // the scan COUNTED -- where a path without these 32 requests joins, the compiler waits for everything outstanding)
+            w_under_scan = task < a.ntask;
+            auto request = [&] { load_w(w_under_scan ? task / a.nrs : 0); };
+            if (a.lazy_esize == 4) lazy_scan_share_under<float>(a.lazy, blockIdx.x, gridDim.x, 512, wt, list, n_list, 8, request);
+            else lazy_scan_share_under<unsigned short>(a.lazy, blockIdx.x, gridDim.x, 512, wt, list, n_list, 8, request);
+            // the scan's LDS use ends here, before the first DMA into the ring; the weights have landed with it
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+        for (; task < a.ntask; task += (int)gridDim.x) {
             const int ct = task / a.nrs, rs = task - ct * a.nrs;
             const int f0 = a.rows.first(rs), nf = a.rows.count(rs);
+            const bool have_w = LAZY && w_under_scan;                     // (the first task only, also where it has no rows)
+            if constexpr (LAZY) w_under_scan = false;
             if (nf <= 0) continue;
             const int n = ct * G_COLS + wave * 32 + l31;                   // this lane's output column
             const float bv = a.bias ? a.bias[n] : 0.f;
@@ -792,19 +817,13 @@ __global__ __launch_bounds__(512) void gemm_f16s_gen_ws_kernel(const GenWsArgs a
             if (nf > 1) issue(1);
             if (nf > 2) issue(2);
             __builtin_amdgcn_sched_barrier(0);
-            // ---- the wave's weights: 32 columns x K, both images -> 128 registers.  Requested BEHIND the first fragments' DMA: loads
-            // return in order, so "at most these 32 outstanding" = the fragments have landed, and the first MFMAs start as soon as
-            // k-step 0's weights arrive (the compiler's own counted waits)
-            bf16x8 wf[WS_KS][2];
-            {
-                const unsigned short* wb = a.Ws + ((long long)(ct * 8 + wave) * (WS_KS * 2) * 64 + lane) * 8;
-#pragma unroll
-                for (int ks = 0; ks < WS_KS; ++ks)
-#pragma unroll
-                    for (int img = 0; img < 2; ++img) wf[ks][img] = *reinterpret_cast<const bf16x8*>(wb + (ks * 2 + img) * 512);
-            }
+            // ---- the wave's weights.  Requested BEHIND the first fragments' DMA: loads return in order, so "at most these 32
+            // outstanding" = the fragments have landed, and the first MFMAs start as soon as k-step 0's weights arrive (the compiler's
+            // own counted waits).  With the weights requested under the scan the fragments are the youngest requests: everything lands.
+            if (!have_w) load_w(ct);
             __builtin_amdgcn_sched_barrier(0);
-            wait_vmcnt_imm<32>();
+            if (have_w) wait_vmcnt_imm<0>();
+            else wait_vmcnt_imm<32>();
             lds_barrier();
             f32x16 prev;                                                  // the finished fragment, scaled + biased, waiting for its stores
 #pragma unroll
@@ -900,7 +919,9 @@ __global__ __launch_bounds__(512) void gemm_f16s_gen_ws_kernel(const GenWsArgs a
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(prev[e]), yrs, (int)(ylast + (unsigned)((e & 3) + 8 * (e >> 2)) * ldyb), 0, 0);
             }
         }
-    }
+    };
+    if (a.lazy_on) run(std::true_type{});
+    else run(std::false_type{});
     SBEV_WGTIME(1, 1)
 }
 
