@@ -1306,7 +1306,7 @@ int sbev_image_geom(const void* src, void* dst, int n, int H, int W, int fH, int
                     int n_transforms, sbev_stream_t stream);
 
 /*
- * The FPN neck between the backbone and the decoder, inference only: L + 1 launches for L input levels on v_mfma_f32_32x32x16_f16.
+ * The FPN neck between the backbone and the decoder (its backward: sbev_fpn_backward below): L + 1 launches for L input levels on v_mfma_f32_32x32x16_f16.
  * Replaces: mmdet's FPN forward as the detector configures it (in_channels = the backbone's stages, out_channels = 256, num_outs levels,
  *           no extra convolutions) under fp16 autocast (models/sparsebev.py:46): 2 L convolutions, L - 1 interpolate + add pairs and
  *           the casts around them, each a launch of its own, and the NCHW -> channels-last relayout in front of the decoder.
@@ -1343,6 +1343,53 @@ int sbev_fpn_pack_weights(int n_levels, const int32_t* chw, const void* const* l
 int sbev_fpn_forward(int n_levels, const int32_t* chw, int64_t n, int num_outs, const void* const* inputs, int in_dtype, const void* pack,
                      const float* const* lateral_bias, const float* const* fpn_bias, void* workspace, void* const* outs, int out_dtype,
                      sbev_stream_t stream);
+
+/*
+ * The FPN neck's backward: from the output gradients to the gradients of the inputs, weights and biases, 4 L + 1 launches (5 L + 1 with
+ * input gradients) and one 16-byte memset node, all four GEMM families on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
+ * Replaces: autograd through mmdet's FPN under fp16 autocast (the backward of 2 L convolutions, the interpolate / add / cast nodes).
+ * The forward is sbev_fpn_forward's; the rounding to fp16 in M_l is straight-through (derivative 1), as under autocast.
+ *   grad_outs[o]   gP_o [n, H_o, W_o, 256] channels-last, g_dtype SBEV_F32 or SBEV_F16, o = 0 .. num_outs - 1
+ *   inputs[l]      C_l as the forward read them (in_dtype); merged: the forward's workspace (M_l, fp16, level after level)
+ *   grad_inputs    null (no input gradient), or per level a [n, H_l, W_l, Cin_l] destination of in_dtype (a null entry skips the level)
+ *   grad_lateral_w[l] [256, Cin_l], grad_lateral_bias[l] [256], grad_fpn_w[l] [256, 256, 3, 3], grad_fpn_bias[l] [256]: fp32, every
+ *                  element is stored by the call (nothing is accumulated into)
+ * Definition (tests/fpn_bwd_cases.py restates it in fp64):
+ *   scale   amax = max |gP_o| over all outputs, found on the device; (2^e, 2^-e) with 2^e amax in [2^W, 2^(W+1)), W =
+ *           SBEV_FPN_GRAD_WINDOW_LOG2 = 3, e capped at 126, is written to the first 8 bytes of the workspace and read from there by every
+ *           consumer: no host read, no synchronisation, the call can be captured.  amax zero or non-finite: e = 0.  Every gradient
+ *           operand is fp16 in the scaled domain: 2^12 of headroom below 65504, full fp16 precision down to 2^-18 amax.  A non-finite
+ *           gP or an fp16 overflow of an intermediate travels as inf / NaN into the parameter gradients, never as a wrong finite value.
+ *   G_l     = gP_l for l < L - 1; G_{L-1} = gP_{L-1} + gP_L + gP_{L+1} .. at the pixels with y, x multiples of 2, 4, .. (the extra
+ *           levels' sources), added in that order in fp32.  g_l = fp16(2^e G_l), rounded once on the way into LDS.
+ *   D_l     = conv3x3(g_l, W3_l'), W3'[ci, co, ky, kx] = fp16(W3[co, ci, 2 - ky, 2 - kx]), fp32 accumulation
+ *   gM_0    = fp16(D_0);  gM_l = fp16(D_l + S), S = the fp32 sum, row-major from zero, of gM_{l-1} over the pixel's children: the (y, x)
+ *           of level l - 1 whose nearest source under the forward's float32 rule is this pixel (any ratio).  No atomics.
+ *   gC_l    = 2^-e gM_l . fp16(Wlat_l), stored in in_dtype
+ *   gW3_l[co, ci, ky, kx] = 2^-e sum_p g_l[p, co] M_l[p + (ky - 1, kx - 1), ci] (zero outside the plane)
+ *   gWlat_l[co, ci]       = 2^-e sum_p gM_l[p, co] fp16(C_l[p, ci])
+ *   gc_l = 2^-e sum_p g_l[p, :],  gblat_l = 2^-e sum_p gM_l[p, :]
+ *           The reductions over pixels p (all images of the level, row-major) are split into slabs of slab_len pixels: the matrix
+ *           products accumulate a slab in fp32 on the matrix core, the bias sums add a slab pixel after pixel in fp32; the slabs'
+ *           partials are then added in order 0, 1, .. and multiplied by 2^-e.  Bit-reproducible.
+ * sbev_fpn_pack_weights_bwd: the flipped / transposed 3x3 images and the transposed lateral images, fp16 in fragment order, into `pack`
+ * (out[2] bytes of the plan: as many as the forward's image); 2 L small launches, repeated whenever a weight changes.
+ * sbev_fpn_backward_plan (pure host): out[SBEV_FPN_BWD_PLAN_WORDS]:
+ *    0 launches of a backward (0 for n == 0)   1 workspace bytes   2 pack bytes   3 .. 6 slabs of level 0 .. 3   7 .. 10 their slab_len
+ *    (max(512, ceil(pixels / 16) rounded up to 256))   11, 12, 13 byte offsets in the workspace of gM (fp16, all levels, as `merged`),
+ *    of D_1 .. D_{L-1} (fp32) and of the slab partials   the rest zero.  Workspace bytes 0 .. 7 hold (2^e, 2^-e) after a call.
+ * Checked before any GPU call, like sbev_fpn_forward: the plan's refusals, the dtypes; n == 0 answers SBEV_OK; null pointers; 16-byte
+ * alignment of inputs, merged, grad_outs, grad_inputs, pack and workspace (4-byte of the fp32 gradients).
+ */
+#define SBEV_FPN_GRAD_WINDOW_LOG2 3
+#define SBEV_FPN_BWD_PLAN_WORDS 16
+int sbev_fpn_backward_plan(int n_levels, const int32_t* chw, int64_t n, int num_outs, int want_input_grads, int64_t* out);
+int sbev_fpn_pack_weights_bwd(int n_levels, const int32_t* chw, const void* const* lateral_w, const void* const* fpn_w, int w_dtype,
+                              void* pack, sbev_stream_t stream);
+int sbev_fpn_backward(int n_levels, const int32_t* chw, int64_t n, int num_outs, const void* const* inputs, int in_dtype,
+                      const void* merged, const void* const* grad_outs, int g_dtype, const void* pack_bwd, void* workspace,
+                      void* const* grad_inputs, float* const* grad_lateral_w, float* const* grad_lateral_bias, float* const* grad_fpn_w,
+                      float* const* grad_fpn_bias, sbev_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 """FPNNeck: the detector's neck (mmdet's ``FPN`` with ``in_channels`` = the backbone's stages, ``out_channels=256``, ``num_outs`` levels,
 no extra convolutions: configs/r50_nuimg_704x256.py:41-45) on the matrix core, as L + 1 launches of csrc/fpn.hip for all images of a call:
 the backbone's stage outputs in channels-last memory in, the channels-last pyramid out that ``FeaturePyramid`` takes in place and
-``FramePool.stream`` lets travel with its pyramid.  Inference only.
+``FramePool.stream`` lets travel with its pyramid.  ``FPNNeck(..., trainable=True)`` also trains: a forward under grad goes through
+``NeckFunction`` and its backward is csrc/fpn_bwd.hip (sbev_fpn_backward: 4 L + 1 launches, 5 L + 1 with input gradients).
 
 Reference counterpart: ``FPN.forward`` under fp16 autocast (models/sparsebev.py:46) -- 2 L convolutions, L - 1 interpolate + add pairs and
 the casts around them, one launch each -- and the NCHW -> channels-last relayout in front of the decoder.
@@ -24,6 +25,7 @@ import torch.nn as nn
 from . import _lib
 
 MAX_IN, MAX_OUT, PLAN_WORDS = 4, 5, 18          # SBEV_FPN_MAX_IN, SBEV_FPN_MAX_OUT, SBEV_FPN_PLAN_WORDS
+BWD_PLAN_WORDS, GRAD_WINDOW_LOG2 = 16, 3         # SBEV_FPN_BWD_PLAN_WORDS, SBEV_FPN_GRAD_WINDOW_LOG2
 _DTYPES = {torch.float32: 0, torch.float16: 2}   # SBEV_F32, SBEV_F16
 
 
@@ -52,13 +54,111 @@ def _vp_array(ptrs):
     return (ctypes.c_void_p * len(ptrs))(*ptrs)
 
 
-class FPNNeck(nn.Module):
-    """``FPNNeck(in_channels, out_channels=256, num_outs=None)``: parameters under mmdet's names (``lateral_convs.{i}.conv.weight`` /
-    ``.bias``, ``fpn_convs.{i}.conv.weight`` / ``.bias``), Xavier-uniform weights and zero biases as mmdet's ``init_cfg`` gives them.
-    ``num_outs`` None: one output per input."""
+def children(in_size, out_size):
+    """The preimage of ``nearest_index(in_size, out_size)``: (start, stop) int64 arrays [in_size]; destination indices start[s] ..
+    stop[s] - 1 read source index s (the rule is monotone, so a preimage is a range; it is empty where no destination reads s).  The
+    top-down adjoint of the neck's backward sums a parent's children over exactly these ranges."""
+    idx = nearest_index(in_size, out_size)
+    s = np.arange(in_size)
+    return np.searchsorted(idx, s, side='left').astype(np.int64), np.searchsorted(idx, s, side='right').astype(np.int64)
 
-    def __init__(self, in_channels, out_channels=256, num_outs=None):
+
+def backward_plan(chw, n, num_outs, input_grads=False):
+    """sbev_fpn_backward_plan, a pure host function: a dict of launches, workspace_bytes, pack_bytes, slabs [L], slab_len [L] and the
+    byte offsets gm_offset, d_offset, part_offset of the scaled lateral gradients, the 3x3 data gradients of levels 1 .. and the slab
+    partials inside the workspace.  Raises SbevError where the plan refuses."""
+    flat = [int(v) for level in chw for v in level]
+    arr = (ctypes.c_int32 * max(len(flat), 1))(*flat)
+    out = (ctypes.c_int64 * BWD_PLAN_WORDS)()
+    _lib.check(_lib.load().sbev_fpn_backward_plan(len(chw), arr, int(n), int(num_outs), int(bool(input_grads)), out), 'sbev_fpn_backward_plan')
+    v = [int(x) for x in out]
+    L = len(chw)
+    return dict(launches=v[0], workspace_bytes=v[1], pack_bytes=v[2], slabs=v[3:3 + L], slab_len=v[7:7 + L], gm_offset=v[11], d_offset=v[12],
+                part_offset=v[13])
+
+
+def backward_raw(chw, n, num_outs, inputs, merged, grad_outs, pack_bwd, workspace, grad_inputs, grad_lateral_w, grad_lateral_b, grad_fpn_w,
+                 grad_fpn_b, stream=None):
+    """sbev_fpn_backward on tensors, nothing allocated and nothing checked beyond what the C entry checks: ``inputs`` / ``grad_outs`` lists
+    of channels-last tensors (one dtype each), ``merged`` the forward's fp16 workspace, ``grad_inputs`` None or a list with None entries
+    for the levels that need no gradient, the four parameter-gradient lists fp32 destinations."""
+    L = len(chw)
+    flat = (ctypes.c_int32 * (3 * L))(*[int(v) for level in chw for v in level])
+    dev = workspace.device
+    with torch.cuda.device(dev):
+        s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if stream is None else stream
+        ptrs = lambda ts: _vp_array([None if t is None else t.data_ptr() for t in ts])
+        _lib.check(_lib.load().sbev_fpn_backward(
+            L, flat, int(n), int(num_outs), ptrs(inputs), _DTYPES[inputs[0].dtype], ctypes.c_void_p(merged.data_ptr()), ptrs(grad_outs),
+            _DTYPES[grad_outs[0].dtype], ctypes.c_void_p(pack_bwd.data_ptr()), ctypes.c_void_p(workspace.data_ptr()),
+            None if grad_inputs is None else ptrs(grad_inputs), ptrs(grad_lateral_w), ptrs(grad_lateral_b), ptrs(grad_fpn_w), ptrs(grad_fpn_b),
+            s), 'sbev_fpn_backward')
+
+
+class NeckFunction(torch.autograd.Function):
+    """A trainable neck's forward under grad.  The node keeps the inputs and parameters by reference (``save_for_backward``: no copy, and
+    an in-place write between forward and backward is an error) and owns the buffer of its merged laterals, so several forwards may
+    precede their backwards.  backward: the output gradients arrive materialised (zeros for an unused output); one that is not
+    channels-last in memory is converted by ONE torch copy; the parameter gradients are fresh fp32 tensors from ``autograd``'s
+    parameter-gradient sink, the input gradients (only for inputs that require one) channels-last tensors of the inputs' dtype."""
+
+    @staticmethod
+    def forward(ctx, neck, chw, out_dtype, *tensors):
+        L = len(chw)
+        inputs = tensors[:L]
+        n, dev = inputs[0].shape[0], inputs[0].device
+        with torch.cuda.device(dev):
+            merged = torch.empty(max(plan(chw, n, neck.num_outs)['workspace_bytes'] // 2, 8), dtype=torch.float16, device=dev)
+            out = [torch.empty((s[0], s[2], s[3], s[1]), dtype=out_dtype, device=dev).permute(0, 3, 1, 2) for s in neck.out_shapes(inputs)]
+            neck.pack_bwd()
+        neck._launch(inputs, chw, merged, out, out_dtype)
+        ctx.neck, ctx.chw, ctx.merged = neck, chw, merged
+        neck.merged = neck._merged_views(merged, chw, n)         # views of THIS node's buffer, until the next forward
+        ctx.save_for_backward(*tensors)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *grad_outs):
+        from . import autograd as A
+        neck, chw, L = ctx.neck, ctx.chw, len(ctx.chw)
+        tensors = ctx.saved_tensors
+        inputs, lat_w, lat_b, out_w, out_b = (tensors[i * L:(i + 1) * L] for i in range(5))
+        n, dev = inputs[0].shape[0], inputs[0].device
+        gs = [g if g.permute(0, 2, 3, 1).is_contiguous() else g.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2) for g in grad_outs]
+        if any(g.dtype != gs[0].dtype for g in gs) or gs[0].dtype not in _DTYPES:
+            raise TypeError('FPNNeck backward: the output gradients must be all fp16 or all fp32')
+        need = ctx.needs_input_grad[3:3 + L]
+        with torch.cuda.device(dev):
+            sink = lambda p: A._NO_TAP.sink(False, id(p), p, tuple(p.shape))[0]
+            gwl, gbl, gw3, gb3 = ([sink(p) for p in ps] for ps in (lat_w, lat_b, out_w, out_b))
+            gx = [torch.empty_like(x) if want else None for x, want in zip(inputs, need)] if any(need) else None
+            if n == 0:
+                for t in gwl + gbl + gw3 + gb3:
+                    t.zero_()
+            ws = neck._backward_workspace(chw, n, gx is not None, dev)
+            backward_raw(chw, n, neck.num_outs, inputs, ctx.merged, gs, neck.pack_bwd(), ws, gx, gwl, gbl, gw3, gb3)
+        params = [A._NO_TAP.commit(False, id(p), g) if want else None
+                  for p, g, want in zip(lat_w + lat_b + out_w + out_b, gwl + gbl + gw3 + gb3, ctx.needs_input_grad[3 + L:])]
+        return (None, None, None, *(gx if gx is not None else [None] * L), *params)
+
+
+class FPNNeck(nn.Module):
+    """``FPNNeck(in_channels, out_channels=256, num_outs=None, trainable=False)``: parameters under mmdet's names
+    (``lateral_convs.{i}.conv.weight`` / ``.bias``, ``fpn_convs.{i}.conv.weight`` / ``.bias``), Xavier-uniform weights and zero biases as
+    mmdet's ``init_cfg`` gives them.  ``num_outs`` None: one output per input.  ``trainable`` False: a forward that would need a gradient
+    is refused (inference only).  ``trainable`` True: such a forward goes through ``NeckFunction``; under ``torch.no_grad()`` nothing
+    differs.  Not built, and refused where asked for: a trainable forward under a graph capture (so the neck inside
+    ``CapturedHeadTrainStep``: the weight packs would have to move into the graph), ``add_extra_convs``, NCHW inputs, an fp16 hi + lo
+    mode of the gradient operands."""
+
+    def __init__(self, in_channels, out_channels=256, num_outs=None, trainable=False, add_extra_convs=False, grad_mode='f16'):
         super().__init__()
+        if add_extra_convs:
+            raise ValueError('FPNNeck: add_extra_convs=%r is not built (extra levels are stride-2 slices of the last output)' % (add_extra_convs,))
+        if grad_mode != 'f16':
+            raise ValueError("FPNNeck: grad_mode=%r is not built (the gradient operands are single fp16 values in the scaled domain: 'f16'; "
+                             'there is no fp16 hi + lo mode)' % (grad_mode,))
+        self.trainable = bool(trainable)
         in_channels = [int(c) for c in in_channels]
         num_outs = len(in_channels) if num_outs is None else int(num_outs)
         if out_channels != 256:
@@ -84,6 +184,9 @@ class FPNNeck(nn.Module):
         self._pack = None               # fp16 weight image at a fixed address per device
         self._pack_key = None
         self._workspaces = {}           # (device index, n, planes) -> fp16 workspace at a fixed address
+        self._pack_bwd = None           # the backward's fp16 weight image (flipped / transposed), same version key
+        self._pack_bwd_key = None
+        self._bwd_workspaces = {}       # (device index, n, planes, input gradients) -> byte workspace of the backward
 
     # ---- weights
     def _weights(self):
@@ -119,6 +222,62 @@ class FPNNeck(nn.Module):
         self._pack_key = key
         return self._pack
 
+    def pack_bwd(self, stream=None):
+        """The backward's weight image (sbev_fpn_pack_weights_bwd), packed now if the weights changed since its last pack."""
+        lat, out = self._weights()
+        ws = lat + out
+        dev = ws[0].device
+        if dev.type != 'cuda':
+            raise RuntimeError('FPNNeck needs its parameters on the device (no CPU fallback)')
+        if any(w.device != dev or w.dtype != ws[0].dtype for w in ws) or ws[0].dtype not in _DTYPES:
+            raise TypeError('FPNNeck: the convolution weights must be all fp32 or all fp16, on one device')
+        key = tuple((w.data_ptr(), w._version) for w in ws)
+        if key == self._pack_bwd_key:
+            return self._pack_bwd
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FPNNeck backward under a capture with weights that are not packed')
+        if any(not w.is_contiguous() for w in ws):
+            raise ValueError('FPNNeck: the convolution weights must be contiguous')
+        chw = [(c, 1, 1) for c in self.in_channels]
+        with torch.cuda.device(dev):
+            if self._pack_bwd is None or self._pack_bwd.device != dev:
+                self._pack_bwd = torch.empty(backward_plan(chw, 0, len(chw))['pack_bytes'] // 2, dtype=torch.float16, device=dev)
+            flat = (ctypes.c_int32 * (3 * len(chw)))(*[v for level in chw for v in level])
+            s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if stream is None else stream
+            _lib.check(_lib.load().sbev_fpn_pack_weights_bwd(len(chw), flat, _vp_array([w.data_ptr() for w in lat]),
+                                                             _vp_array([w.data_ptr() for w in out]), _DTYPES[ws[0].dtype],
+                                                             ctypes.c_void_p(self._pack_bwd.data_ptr()), s), 'sbev_fpn_pack_weights_bwd')
+        self._pack_bwd_key = key
+        return self._pack_bwd
+
+    def _backward_workspace(self, chw, n, input_grads, dev):
+        key = (dev.index, n, tuple(chw), bool(input_grads))
+        ws = self._bwd_workspaces.get(key)
+        if ws is None:
+            nbytes = backward_plan(chw, n, self.num_outs, input_grads)['workspace_bytes']
+            ws = self._bwd_workspaces[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        return ws
+
+    def _launch(self, inputs, chw, ws, out, out_dtype):
+        """sbev_fpn_forward on checked arguments: the merged laterals into ``ws``, the outputs into ``out``"""
+        L, dev, n = len(chw), inputs[0].device, inputs[0].shape[0]
+        lat_b, out_b = self._biases()
+        flat = (ctypes.c_int32 * (3 * L))(*[int(v) for level in chw for v in level])
+        with torch.cuda.device(dev):
+            wpack = self.pack()
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(_lib.load().sbev_fpn_forward(
+                L, flat, n, self.num_outs, _vp_array([x.data_ptr() for x in inputs]), _DTYPES[inputs[0].dtype], ctypes.c_void_p(wpack.data_ptr()),
+                _vp_array([b.data_ptr() for b in lat_b]), _vp_array([b.data_ptr() for b in out_b]), ctypes.c_void_p(ws.data_ptr()),
+                _vp_array([o.data_ptr() for o in out]), _DTYPES[out_dtype], stream), 'sbev_fpn_forward')
+
+    def _merged_views(self, ws, chw, n):
+        views, at = [], 0
+        for _, h, w in chw:
+            views.append(ws[at:at + n * h * w * 256].view(n, h, w, 256).permute(0, 3, 1, 2))
+            at += n * h * w * 256
+        return views
+
     # ---- the call
     def out_shapes(self, inputs):
         """[n, 256, H, W] of every output for these inputs"""
@@ -149,13 +308,25 @@ class FPNNeck(nn.Module):
                 raise ValueError('FPNNeck: input %d is not channels-last in memory: hand the backbone\'s output over with '
                                  'memory_format=torch.channels_last (no copy is made here)' % l)
         lat_b, out_b = self._biases()
-        if torch.is_grad_enabled() and (any(x.requires_grad for x in inputs) or any(p.requires_grad for p in self.parameters())):
-            raise RuntimeError('FPNNeck is inference only (the backward of the neck is not built): call it under torch.no_grad()')
+        wants_grad = torch.is_grad_enabled() and (any(x.requires_grad for x in inputs) or any(p.requires_grad for p in self.parameters()))
+        if wants_grad and not self.trainable:
+            raise RuntimeError('FPNNeck is inference only unless built with trainable=True: call it under torch.no_grad()')
         if not all(x.is_cuda for x in inputs):
             raise RuntimeError('FPNNeck needs device tensors (no CPU fallback)')
         if any(b.dtype != torch.float32 or b.device != dev or not b.is_contiguous() for b in lat_b + out_b):
             raise TypeError('FPNNeck: the biases must be contiguous fp32 tensors on the inputs\' device')
         shapes = self.out_shapes(inputs)
+        if wants_grad:
+            if out is not None:
+                raise ValueError('FPNNeck: out= is not taken by a forward that needs a gradient (autograd owns its outputs)')
+            if out_dtype not in _DTYPES:
+                raise TypeError('FPNNeck: out_dtype must be torch.float16 or torch.float32')
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('FPNNeck: a trainable forward under a graph capture (the neck inside CapturedHeadTrainStep) is not built: '
+                                   'the weight packs would have to move into the graph')
+            chw = tuple((c, int(x.shape[2]), int(x.shape[3])) for c, x in zip(self.in_channels, inputs))
+            lat_w, out_w = self._weights()
+            return list(NeckFunction.apply(self, chw, out_dtype, *inputs, *lat_w, *lat_b, *out_w, *out_b))
         if out is None:
             if out_dtype not in _DTYPES:
                 raise TypeError('FPNNeck: out_dtype must be torch.float16 or torch.float32')
@@ -171,21 +342,12 @@ class FPNNeck(nn.Module):
                 if tuple(o.shape) != s or o.dtype != out_dtype or o.device != dev or (o.numel() and not o.permute(0, 2, 3, 1).is_contiguous()):
                     raise ValueError('FPNNeck: out must be %s tensors of shape %s in channels-last memory on %s' % (out_dtype, s, dev))
         chw = [(c, x.shape[2], x.shape[3]) for c, x in zip(self.in_channels, inputs)]
-        flat = (ctypes.c_int32 * (3 * L))(*[int(v) for level in chw for v in level])
         with torch.cuda.device(dev):
             key = (dev.index, n, tuple(chw))
             ws = self._workspaces.get(key)
             if ws is None:
                 p = plan(chw, n, self.num_outs)
                 ws = self._workspaces[key] = torch.empty(max(p['workspace_bytes'] // 2, 8), dtype=torch.float16, device=dev)
-            wpack = self.pack()
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(_lib.load().sbev_fpn_forward(
-                L, flat, n, self.num_outs, _vp_array([x.data_ptr() for x in inputs]), _DTYPES[dt], ctypes.c_void_p(wpack.data_ptr()),
-                _vp_array([b.data_ptr() for b in lat_b]), _vp_array([b.data_ptr() for b in out_b]), ctypes.c_void_p(ws.data_ptr()),
-                _vp_array([o.data_ptr() for o in out]), _DTYPES[out_dtype], stream), 'sbev_fpn_forward')
-        self.merged, at = [], 0
-        for _, h, w in chw:
-            self.merged.append(ws[at:at + n * h * w * 256].view(n, h, w, 256).permute(0, 3, 1, 2))
-            at += n * h * w * 256
+        self._launch(inputs, chw, ws, out, out_dtype)
+        self.merged = self._merged_views(ws, chw, n)
         return out
