@@ -1391,6 +1391,67 @@ int sbev_fpn_backward(int n_levels, const int32_t* chw, int64_t n, int num_outs,
                       void* const* grad_inputs, float* const* grad_lateral_w, float* const* grad_lateral_bias, float* const* grad_fpn_w,
                       float* const* grad_fpn_bias, sbev_stream_t stream);
 
+/*
+ * The ResNet backbone between the image front end and the FPN neck, inference only: the Bottleneck nets (depth 50 / 101 / 152, style
+ * 'pytorch': the stage's stride on the 3 x 3), BatchNorm in eval mode folded into the convolutions, on v_mfma_f32_32x32x16_f16.
+ * Replaces: mmdet's ResNet forward with norm_eval=True under fp16 autocast (configs/r50_nuimg_704x256.py:31-40): per convolution a
+ *           convolution, a BatchNorm, a ReLU / add and the casts around them, each a launch of its own.
+ * The net: depth picks the blocks per stage ((3,4,6,3), (3,4,23,3), (3,8,36,3)); stage_blocks, when not null, overrides them
+ * (num_stages entries); stage s has mid = base_channels 2^s channels, 4 mid output channels, stride 1 (s = 0) or 2 on its first block.
+ *   x          [n, 3, H, W] NCHW contiguous, SBEV_F32 or SBEV_F16
+ *   outs[k]    [n, h, w, C] channels-last fp16: the output of stage out_indices[k] (increasing), every element stored by the call
+ *   workspace  out[2] bytes of the plan: the activations between the launches
+ * Plane sizes: stem floor((H + 6 - 7) / 2) + 1; pool and every stride-2 3 x 3 floor((H + 2 - 3) / 2) + 1; stride-2 1 x 1 floor((H - 1) / 2) + 1.
+ * Arithmetic.  The fold, per output channel, in fp32 with every operation rounded on its own (true division, true square root):
+ *   s = gamma / sqrt(var + eps),   w' = fp16(w * s),   b' = beta - mean * s
+ * Every convolution: operands fp16 (w' and the previous activation; the stem rounds an fp32 image once, to nearest even), products
+ * accumulated in fp32 on the matrix core, y = acc + b' [+ float(residual)] [then max(y, 0)] in fp32, rounded once to fp16, stored
+ * channels-last.  Zero padding.  A block: conv1 1 x 1 + ReLU; conv2 3 x 3 (pad 1, the block's stride) + ReLU; conv3 1 x 1 + residual +
+ * ReLU; on a stage's first block the residual is downsample = 1 x 1 (the block's stride), no ReLU, else the block's input.  The stem:
+ * 7 x 7 / 2 / pad 3 + ReLU, K = 147 in the weight's own (c, ky, kx) order padded with zeros to 160.  The max-pool 3 x 3 / 2 / pad 1
+ * ignores its padding: a true maximum, exact.  K split: where the plan says 3, the chunks of 64 reduction indices (tap-major, then channels)
+ * are dealt to three groups of waves in turn (chunk c to group c mod 3), each accumulates its own on the matrix core, and acc = (g0 + g1) + g2
+ * in fp32, in that order.  One lane owns each stored element, no atomics: bit-reproducible.
+ * Launch order (the order of the plan's layers, of sbev_resnet_pack_weights' lists for a whole net, and of keep): stem, pool, then per
+ * block conv1, conv2, [downsample], conv3: 2 + 3 blocks + num_stages launches (54 for ResNet-50), all enqueued by one call on one stream,
+ * nothing allocated, nothing synchronised.
+ *
+ * sbev_resnet_plan (pure host): out[SBEV_RESNET_PLAN_WORDS]:
+ *    0 launches of a forward (0 for n == 0)   1 pack bytes   2 workspace bytes   3 layers   4 multiply-adds of a forward   5 outputs
+ *    6 + 3 k .. 8 + 3 k: C, h, w of outs[k]   then from word SBEV_RESNET_PLAN_HEAD, SBEV_RESNET_LAYER_WORDS per layer:
+ *    kind (0 stem, 1 pool, 2 convolution), Cin, Cout, taps (49: the stem), stride, h, w (the output plane), row tiles (128 output pixels),
+ *    column tiles, K split (1 or 3), where the output lives (a byte offset in the workspace, or -(1 + k): outs[k]), epilogue
+ *    the rest zero.  keep != 0: every layer's output has a workspace region of its own (tests read them back); keep == 0: five regions,
+ *    reused (two for block outputs, conv1's, conv2's and downsample's).  Column tiles: the widest of 256 / 128 / 64 channels that divides
+ *    Cout and still gives at least 256 workgroups, 64 where none does.  K split: 3 where 64-channel tiles give fewer than 256 workgroups
+ *    and K has 6 chunks or more (the split is inside the workgroup: no workspace, no extra launch), else 1.
+ * sbev_resnet_pack_weights: fold and pack n_layers convolutions, desc = {Cin, Cout, taps} each (taps 1, 9, or 49 with Cin = 3 for the
+ *    stem), w[i] [Cout, Cin, kh, kw] contiguous (w_dtype SBEV_F32 or SBEV_F16), gamma / beta / mean / var fp32 [Cout], all device memory;
+ *    layer after layer into `pack`: fragment-order fp16 w' (taps Cin Cout halves; the stem 160 Cout), then fp32 b' [Cout].  One small
+ *    launch per layer on the stream; to be repeated whenever a weight or a statistic changes.
+ * sbev_conv_f16: ONE convolution of the family on raw pointers: x [n, H, W, Cin], y [n, h, w, Cout], residual as y (epilogue 2 only),
+ *    pack = one layer's image; taps 1 or 9, stride 1 or 2, epilogue 0 bias / 1 + ReLU / 2 + residual + ReLU, col_tile 0 (the plan's choice)
+ *    or 64 / 128 / 256; the K split follows the plan's rule for the shape and the column tile.
+ * Checked before any GPU call (SBEV_EINVAL): a depth other than 50 / 101 / 152 (18 / 34 are BasicBlock nets), num_stages outside 1 .. 4,
+ * base_channels / Cin / Cout not a multiple of 64, n < 0, an empty plane or a side above 32767, more output pixels in a layer than 32-bit
+ * row indices hold, out_indices not increasing stage numbers, a dtype / taps / stride / epilogue / col_tile not listed; then n == 0
+ * answers SBEV_OK; then null pointers; then 16-byte alignment of x, pack, workspace, outs, residual, y (element alignment of the
+ * tensors sbev_resnet_pack_weights reads).
+ */
+#define SBEV_RESNET_MAX_LAYERS 160
+#define SBEV_RESNET_PLAN_HEAD 18
+#define SBEV_RESNET_LAYER_WORDS 12
+#define SBEV_RESNET_PLAN_WORDS (SBEV_RESNET_PLAN_HEAD + SBEV_RESNET_LAYER_WORDS * SBEV_RESNET_MAX_LAYERS)
+int sbev_resnet_plan(int depth, const int32_t* stage_blocks, int num_stages, int base_channels, int64_t n, int H, int W, int n_out,
+                     const int32_t* out_indices, int keep, int64_t* out);
+int sbev_resnet_pack_weights(int n_layers, const int32_t* desc, const void* const* w, const float* const* gamma, const float* const* beta,
+                             const float* const* mean, const float* const* var, float eps, int w_dtype, void* pack, sbev_stream_t stream);
+int sbev_conv_f16(const void* x, const void* pack, const void* residual, void* y, int64_t n, int H, int W, int Cin, int Cout, int taps,
+                  int stride, int epilogue, int col_tile, sbev_stream_t stream);
+int sbev_resnet_forward(int depth, const int32_t* stage_blocks, int num_stages, int base_channels, int64_t n, int H, int W, int n_out,
+                        const int32_t* out_indices, int keep, const void* x, int x_dtype, const void* pack, void* workspace,
+                        void* const* outs, sbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

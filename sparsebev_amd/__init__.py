@@ -8,7 +8,8 @@ operator modules without the built library raises -- there is no CPU / PyTorch f
 """
 from ._lib import load as load_library, SbevError, LIB_PATH   # noqa: F401
 
-__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW', 'ImageFrontEnd', 'ImageGeometry', 'FPNNeck']
+__all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW', 'ImageFrontEnd', 'ImageGeometry', 'FPNNeck',
+           'ResNetBackbone']
 
 
 def __getattr__(name):
@@ -31,4 +32,7 @@ def __getattr__(name):
     if name == 'FPNNeck':
         from .fpn import FPNNeck
         return FPNNeck
+    if name == 'ResNetBackbone':
+        from .resnet import ResNetBackbone
+        return ResNetBackbone
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

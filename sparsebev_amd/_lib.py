@@ -192,6 +192,12 @@ SIGNATURES = {
     'sbev_fpn_pack_weights_bwd': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, _vp, _vp]),
     'sbev_fpn_backward': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(_vp), ctypes.c_int, _vp,
                                          ctypes.POINTER(_vp), ctypes.c_int, _vp, _vp] + [ctypes.POINTER(_vp)] * 5 + [_vp]),
+    'sbev_resnet_plan': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, _c_i32p, ctypes.c_int, _c_i64p]),
+    'sbev_resnet_pack_weights': (ctypes.c_int, [ctypes.c_int, _c_i32p] + [ctypes.POINTER(_vp)] * 5 + [ctypes.c_float, ctypes.c_int, _vp, _vp]),
+    'sbev_conv_f16': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64] + [ctypes.c_int] * 8 + [_vp]),
+    'sbev_resnet_forward': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, _c_i32p, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     'sbev_profile_read': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int]),
     'sbev_linear_splitk_plan': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'sbev_linear_f32_path': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
