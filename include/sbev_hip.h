@@ -1452,6 +1452,108 @@ int sbev_resnet_forward(int depth, const int32_t* stage_blocks, int num_stages, 
                         const int32_t* out_indices, int keep, const void* x, int x_dtype, const void* pack, void* workspace,
                         void* const* outs, sbev_stream_t stream);
 
+/*
+ * The ResNet backbone's backward: from the gradients of the stage maps to the gradients of the convolution weights and the BatchNorm
+ * gamma / beta of the trainable stages, on v_mfma_f32_32x32x16_f16 with fp32 accumulation.  BatchNorm stays in eval mode (norm_eval=True:
+ * running statistics), so its backward is the backward of the fold.
+ * Replaces: autograd through mmdet's ResNet under fp16 autocast with frozen_stages = first_trainable_stage - 1 and norm_eval=True.
+ * first_trainable_stage is 1 .. num_stages (mmdet's frozen_stages + 1): the stem, the pool and the stages before it get no gradient of any
+ * kind, and no image gradient is ever produced.  0 (a trainable stem: the 7 x 7 weight gradient and the max-pool backward) is refused.
+ *
+ * sbev_resnet_forward_train: sbev_resnet_forward's launches and arithmetic, bit for bit, but every activation from the output of the last
+ *   frozen launch (`first_kept`: the pool, or the last frozen stage's output) onward lives in the caller's `acts` buffer (plan word 3
+ *   bytes), each launch at its own 256-byte aligned offset in launch order; the stage maps still go to outs[k]; the frozen launches
+ *   ping-pong in `workspace` (sbev_resnet_plan's bytes with keep = 0) as before.
+ *
+ * Definition (tests/resnet_bwd_cases.py restates it in fp64).  A block with input x: a1 = relu(conv1(x)), a2 = relu(conv2(a1)),
+ * r = x or downsample(x), out = relu(conv3(a2) + r), all stored fp16 by the forward; w' = fp16(w s), s = gamma / sqrt(var + eps).  The
+ * roundings of w' and of the stored activations are straight-through (derivative 1).  A ReLU's derivative is read from the stored fp16
+ * activation: 1 where it is > 0, else 0 (a select, not a product: a masked inf is 0).
+ *   scale   amax = max |gP_k| over grad_outs, found on the device; (2^e, 2^-e) with 2^e amax in [2^W, 2^(W+1)), W =
+ *           SBEV_RESNET_GRAD_WINDOW_LOG2 = 3, e capped at 126, e = 0 for a zero or non-finite amax; the pair is written to the first 8
+ *           bytes of the workspace and read from there by every consumer: no host read, no synchronisation.  A non-finite gP or an fp16
+ *           overflow of an intermediate travels as inf / NaN into the parameter gradients, never as a wrong finite value.
+ *   blocks, last to first, in the scaled domain, G_out the fp32 gradient of a block's out:
+ *     g3 = fp16(G_out [out > 0])                        (the gradient at conv3's output and at r)
+ *     g2 = fp16(dgrad_1x1(g3, w3') [a2 > 0])
+ *     g1 = fp16(dgrad_3x3,stride(g2, w2') [a1 > 0])
+ *     G_x = dgrad_1x1(g1, w1') + R, the previous block's G_out.  Identity residual: R = float(g3), added to the finished accumulator.
+ *           First block of a stage: the downsample's products dgrad_1x1,stride(g3, wd') -- they land on the pixels (S y, S x) the strided
+ *           1 x 1 read and are zero elsewhere -- CONTINUE conv1's accumulation in the same fp32 accumulator (K = conv1's output
+ *           channels first, then the downsample's).  Where x is a stage output listed in out_indices, 2^e float(gP_k) (the product
+ *           rounded on its own) is added last.  So the order is ((conv1 products, then downsample products) + float(g3)) + 2^e gP.
+ *     The net's last block starts from G_out = 2^e gP (zero when the last stage is not in out_indices); a stage output that is not in
+ *     out_indices gets no addend.  In the first trainable stage's first block no data gradient leaves conv1 or the downsample.
+ *     A data gradient multiplies the fp16 w' transposed (for a 3 x 3 also flipped: tap (ky, kx) -> (2 - ky, 2 - kx)); at stride 2 an input
+ *     pixel sums only the taps whose source (Y + 1 - ky, X + 1 - kx) is even in both coordinates.  K runs tap-major, then channels, in
+ *     chunks of 64 on the matrix core; every stored element is rounded once.
+ *   per trainable convolution, g_y the stored fp16 gradient at its output, x_in its stored fp16 input:
+ *     gW'[co, ci, ky, kx] = 2^-e sum_p g_y[p, co] x_in[S p + (ky - 1, kx - 1), ci] (zero outside the plane; a 1 x 1 reads S p),
+ *     gb'[co] = 2^-e sum_p g_y[p, co].  The reduction over the output pixels p (all images, row-major) is cut into slabs of slab_len =
+ *     max(512, ceil(pixels / 16) rounded up to 256) pixels: the products accumulate a slab in fp32 on the matrix core in steps of 32
+ *     pixels, the bias sums add a slab pixel after pixel in fp32; the partials are added in slab order 0, 1, .. and then multiplied by 2^-e.
+ *   fold backward, fp32, every operation rounded on its own, root = sqrt(var + eps), s = gamma / root, rinv = 1 / root:
+ *     g_w = s gW'      g_beta = gb'      g_gamma = rinv (D - mean gb'),  D = sum_k w[co, k] gW'[co, k]  (= sum_p g_y z for the raw convolution z)
+ *     D's order: lane t of 256 adds its products from zero, tap after tap (tap 0 first) and within a tap ci = t, t + 256, .. ascending;
+ *     then for h = 128, 64, .. 1: lane t < h adds lane t + h's sum to its own.
+ *   All results are fp32 and every element is stored by the call; nothing is accumulated into.  Bit-reproducible: one owner per stored
+ *   element, no float atomics.
+ *
+ * sbev_resnet_backward: one call enqueues everything on one stream, allocates nothing and synchronises nothing (it can be captured):
+ *   a clear of the 16 head bytes (a launch, not a memset node), the amax, the seed of the last block, then per block (last first) weight gradient + fold of conv3, the data
+ *   gradient to a2, the same for conv2 and a1, weight gradient + fold of conv1 and of the downsample, the data gradient to x.
+ *   acts / outs as sbev_resnet_forward_train left them; grad_outs[k] [n, h, w, C] channels-last of g_dtype (SBEV_F32 or SBEV_F16);
+ *   w / gamma / mean / var / grad_w / grad_gamma / grad_beta: one entry per CONVOLUTION in launch order as sbev_resnet_pack_weights
+ *   lists a whole net (entry 0 the stem, entry j the launch j + 1); entries of frozen convolutions are not read; a null grad_gamma[j] /
+ *   grad_beta[j] skips that result (a frozen norm).
+ * sbev_resnet_pack_weights_bwd: n_layers images, desc = {Cin, Cout, taps} each, layer after layer into `pack`: the fragment image of
+ *   W^T[ci][co][tap'] = fp16(w[co][ci][8 - tap'] s[co]) (a 1 x 1: tap 0), [tap'][Cout / 16][Cin / 32][64 lanes][8 halves] -- the forward's
+ *   lane map with the channel roles swapped and the forward's own fp32 fold, so the w' bits are the forward's; taps Cin Cout halves each.
+ *   A whole net packs the launches that send a data gradient in the order of their plan offsets (per block: conv3, conv2, conv1,
+ *   downsample).
+ * sbev_resnet_backward_plan (pure host): out[SBEV_RESNET_BWD_PLAN_WORDS]:
+ *    0 launches of a backward (0 for n == 0)   1 workspace bytes   2 backward-pack bytes   3 activation-buffer bytes   4 the forward's
+ *    workspace bytes   5 layers   6 first_kept   7, 8 byte offsets in the workspace of the two g3 buffers   9, 10 of g2 and g1
+ *    11 of the slab partials   12 the forward's pack bytes; then from word SBEV_RESNET_BWD_PLAN_HEAD, SBEV_RESNET_BWD_LAYER_WORDS per launch:
+ *    slabs, slab_len, where its output is kept (a byte offset in acts, -(2 + k): outs[k], -1: not kept), byte offset of its image in the
+ *    backward's pack (-1: none), trainable (0 / 1), sends a data gradient (0 / 1).
+ * Single operations on raw pointers (tests, tools):
+ *   sbev_conv_dgrad_f16: gx [n, H, W, Cin] = fp16(select(mask > 0, ((acc + float(res)) + scale[0] gp), 0)), acc = the products of
+ *     gy [n, h, w, Cout] (taps 1 or 9, stride 1 or 2) and then, with Cout2 != 0, of gy2 [n, h2, w2, Cout2] (a 1 x 1 of stride2) over the
+ *     images in `pack` (gy's, then gy2's); mask / res / gp may be null; col_tile 0 (the forward's rule on Cin) or 64 / 128 / 256.
+ *   sbev_conv_wgrad_f16: the slab partials of one convolution into part [slabs][taps Cout Cin + Cout] (tap-major [tap][co][ci], then the
+ *     column sums), unscaled; slab_len 0: the rule above, else a multiple of 32.
+ *   sbev_bn_fold_backward: partials of `slabs` slabs -> grad_w [Cout, Cin, kh, kw], grad_gamma, grad_beta (null: skipped); scale null: 1,
+ *     else scale[1] multiplies the slab sum.
+ * Checked before any GPU call (SBEV_EINVAL), like sbev_resnet_forward: the plan's refusals, first_trainable_stage, dtypes, taps / stride /
+ * channel counts / col_tile / slab_len not listed; then n == 0 answers SBEV_OK; then null pointers; then 16-byte alignment of
+ * activations, gradients, packs and workspace (element alignment of the fp32 tensors and the weights).
+ */
+#define SBEV_RESNET_GRAD_WINDOW_LOG2 3
+#define SBEV_RESNET_BWD_PLAN_HEAD 16
+#define SBEV_RESNET_BWD_LAYER_WORDS 6
+#define SBEV_RESNET_BWD_PLAN_WORDS (SBEV_RESNET_BWD_PLAN_HEAD + SBEV_RESNET_BWD_LAYER_WORDS * SBEV_RESNET_MAX_LAYERS)
+int sbev_resnet_backward_plan(int depth, const int32_t* stage_blocks, int num_stages, int base_channels, int64_t n, int H, int W, int n_out,
+                              const int32_t* out_indices, int first_trainable_stage, int64_t* out);
+int sbev_resnet_forward_train(int depth, const int32_t* stage_blocks, int num_stages, int base_channels, int64_t n, int H, int W, int n_out,
+                              const int32_t* out_indices, int first_trainable_stage, const void* x, int x_dtype, const void* pack,
+                              void* workspace, void* acts, void* const* outs, sbev_stream_t stream);
+int sbev_resnet_pack_weights_bwd(int n_layers, const int32_t* desc, const void* const* w, const float* const* gamma, const float* const* var,
+                                 float eps, int w_dtype, void* pack, sbev_stream_t stream);
+int sbev_resnet_backward(int depth, const int32_t* stage_blocks, int num_stages, int base_channels, int64_t n, int H, int W, int n_out,
+                         const int32_t* out_indices, int first_trainable_stage, const void* acts, const void* const* outs,
+                         const void* const* grad_outs, int g_dtype, const void* pack_bwd, void* workspace, const void* const* w, int w_dtype,
+                         const float* const* gamma, const float* const* mean, const float* const* var, float eps, float* const* grad_w,
+                         float* const* grad_gamma, float* const* grad_beta, sbev_stream_t stream);
+int sbev_conv_dgrad_f16(const void* gy, const void* gy2, const void* pack, const void* mask, const void* res, const void* gp, int gp_dtype,
+                        const float* scale, void* gx, int64_t n, int H, int W, int Cin, int Cout, int taps, int stride, int Cout2, int stride2,
+                        int col_tile, sbev_stream_t stream);
+int sbev_conv_wgrad_f16(const void* gy, const void* x, float* part, int64_t n, int H, int W, int Cin, int Cout, int taps, int stride,
+                        int slab_len, sbev_stream_t stream);
+int sbev_bn_fold_backward(const float* part, int slabs, const float* scale, const void* w, int w_dtype, const float* gamma, const float* mean,
+                          const float* var, float eps, int Cin, int Cout, int taps, float* grad_w, float* grad_gamma, float* grad_beta,
+                          sbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

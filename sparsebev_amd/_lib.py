@@ -198,6 +198,19 @@ SIGNATURES = {
     'sbev_conv_f16': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64] + [ctypes.c_int] * 8 + [_vp]),
     'sbev_resnet_forward': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, _c_i32p, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.POINTER(_vp), _vp]),
+    'sbev_resnet_backward_plan': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, _c_i32p, ctypes.c_int, _c_i64p]),
+    'sbev_resnet_forward_train': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, _c_i32p, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
+    'sbev_resnet_pack_weights_bwd': (ctypes.c_int, [ctypes.c_int, _c_i32p] + [ctypes.POINTER(_vp)] * 3 + [ctypes.c_float, ctypes.c_int, _vp, _vp]),
+    'sbev_resnet_backward': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, _c_i32p, ctypes.c_int, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, _vp, _vp,
+                                            ctypes.POINTER(_vp), ctypes.c_int] + [ctypes.POINTER(_vp)] * 3 + [ctypes.c_float] +
+                                           [ctypes.POINTER(_vp)] * 3 + [_vp]),
+    'sbev_conv_dgrad_f16': (ctypes.c_int, [_vp] * 6 + [ctypes.c_int, _vp, _vp, ctypes.c_int64] + [ctypes.c_int] * 9 + [_vp]),
+    'sbev_conv_wgrad_f16': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64] + [ctypes.c_int] * 7 + [_vp]),
+    'sbev_bn_fold_backward': (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_float] + [ctypes.c_int] * 3 +
+                                            [_vp] * 4),
     'sbev_profile_read': (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int]),
     'sbev_linear_splitk_plan': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int]),
     'sbev_linear_f32_path': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int]),

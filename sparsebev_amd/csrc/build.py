@@ -49,6 +49,8 @@ UNITS = {
     'fpn_bwd.hip': [],                   # the neck's backward: the same; its fixed-order fp32 sums have no multiply beside them
     # the ResNet backbone: the BatchNorm fold is DEFINED by individually rounded fp32 operations (tests restate it bit for bit)
     'resnet.hip': ['-ffp-contract=off'],
+    # its backward: the BatchNorm fold's backward is defined the same way (individually rounded fp32 operations, a fixed sum order)
+    'resnet_bwd.hip': ['-ffp-contract=off'],
     'decoder.hip': [],
     'row_chain.hip': [],                 # the row-local op chains of a layer (4x4x1 MFMA with A broadcast)
     'fault_word.hip': [],                # host only: the sticky host-mapped fault word row_chain.hip and gemm_bf16s.hip report into

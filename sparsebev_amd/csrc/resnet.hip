@@ -26,7 +26,11 @@
 // their partial sums are added through LDS in the fixed order (g0 + g1) + g2 before the epilogue.
 //
 // Who writes what: every stored element has one owning lane; no atomics; the K split folds in a fixed order: bit-reproducible.
+//
+// Training: sbev_resnet_forward_train (at the end of this file) is the same launches with every activation the backward reads kept in a
+// caller-owned buffer; resnet_train.hpp hands the net's table to the backward, resnet_bwd.hip.
 #include "fpn_common.hpp"
+#include "resnet_train.hpp"
 
 namespace {
 
@@ -517,6 +521,42 @@ int check_conv_shape(const char* who, int Cin, int Cout, int taps) {
     return SBEV_OK;
 }
 
+// every launch of a forward in launch order; where(layer) is the address of that layer's output
+template <class Where>
+void enqueue_forward(const NetPlan& p, const void* x, int x_dtype, const void* pack, Where where, hipStream_t s) {
+    for (int i = 0; i < p.n_layers; ++i) {
+        const Layer& L = p.layer[i];
+        const char* wl = static_cast<const char*>(pack) + L.pack_off;
+        if (L.kind == KIND_STEM) {
+            StemArgs a;
+            a.x = x;
+            a.wp = reinterpret_cast<const uint4*>(wl);
+            a.bias = reinterpret_cast<const float*>(wl + frag_bytes(L.Cin, L.Cout, L.taps));
+            a.y = static_cast<_Float16*>(where(i));
+            a.rows = (int)L.rows; a.Cout = L.Cout; a.H = L.H; a.W = L.W; a.h = L.h; a.w = L.w;
+            const dim3 grid((unsigned)L.row_tiles, (unsigned)(L.Cout / 64));
+            if (x_dtype == SBEV_F32) hipLaunchKernelGGL(resnet_stem_kernel<true>, grid, dim3(128), 0, s, a);
+            else hipLaunchKernelGGL(resnet_stem_kernel<false>, grid, dim3(128), 0, s, a);
+        } else if (L.kind == KIND_POOL) {
+            PoolArgs a;
+            a.x = static_cast<const _Float16*>(where(L.in_layer));
+            a.y = static_cast<_Float16*>(where(i));
+            a.C8 = L.Cout / 8; a.H = L.H; a.W = L.W; a.h = L.h; a.w = L.w;
+            a.items = L.rows * a.C8;
+            hipLaunchKernelGGL(resnet_pool_kernel, dim3((unsigned)((a.items + 255) / 256)), dim3(256), 0, s, a);
+        } else {
+            ConvArgs a;
+            a.x = static_cast<const _Float16*>(where(L.in_layer));
+            a.wp = reinterpret_cast<const uint4*>(wl);
+            a.bias = reinterpret_cast<const float*>(wl + frag_bytes(L.Cin, L.Cout, L.taps));
+            a.res = L.res_layer >= 0 ? static_cast<const _Float16*>(where(L.res_layer)) : nullptr;
+            a.y = static_cast<_Float16*>(where(i));
+            a.rows = (int)L.rows; a.Cin = L.Cin; a.Cout = L.Cout; a.H = L.H; a.W = L.W; a.h = L.h; a.w = L.w;
+            launch_conv(L.taps, L.stride, L.epi, L.col_tile, L.k_split, a, s);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int sbev_resnet_plan(int depth, const int32_t* stage_blocks, int num_stages, int base_channels, int64_t n, int H, int W, int n_out,
@@ -632,36 +672,83 @@ extern "C" int sbev_resnet_forward(int depth, const int32_t* stage_blocks, int n
         const Layer& L = p.layer[layer];
         return L.role >= 0 ? static_cast<void*>(static_cast<char*>(workspace) + L.out_off) : outs[-2 - L.role];
     };
+    enqueue_forward(p, x, x_dtype, pack, where, s);
+    return sbev::check_launch(who);
+}
+
+// ---------------------------------------------------------------- the trainable forward (its backward: resnet_bwd.hip)
+int sbev_resnet::train_net(const char* who, int depth, const int32_t* stage_blocks, int num_stages, int base, int64_t n, int H, int W, int n_out,
+                           const int32_t* out_indices, int first_trainable_stage, TrainNet* t) {
+    NetPlan p;
+    if (int st = make_net_plan(who, depth, stage_blocks, num_stages, base, n, H, W, n_out, out_indices, 0, &p)) return st;
+    SBEV_REQUIRE(first_trainable_stage != 0, "%s: first_trainable_stage=0 (frozen_stages=-1, a trainable stem: the 7 x 7 weight gradient and the "
+                 "max-pool backward are not built)", who);
+    SBEV_REQUIRE(first_trainable_stage >= 1 && first_trainable_stage <= num_stages, "%s: first_trainable_stage=%d not in 1 .. num_stages=%d", who,
+                 first_trainable_stage, num_stages);
+    t->n_layers = p.n_layers;
+    t->n_out = p.n_out;
+    t->first_trainable_stage = first_trainable_stage;
+    t->ws_bytes = p.ws_total;
+    t->pack_bytes = p.pack_total;
+    for (int k = 0; k < 4; ++k) t->out_layer[k] = k < p.n_out ? p.out_layer[k] : -1;
+    static const int32_t r50[4] = {3, 4, 6, 3}, r101[4] = {3, 4, 23, 3}, r152[4] = {3, 8, 36, 3};
+    const int32_t* blocks = stage_blocks != nullptr ? stage_blocks : depth == 50 ? r50 : depth == 101 ? r101 : r152;
+    int stage = -1, block = 0, which = 3;
+    t->first_kept = 1;
     for (int i = 0; i < p.n_layers; ++i) {
         const Layer& L = p.layer[i];
-        const char* wl = static_cast<const char*>(pack) + L.pack_off;
-        if (L.kind == KIND_STEM) {
-            StemArgs a;
-            a.x = x;
-            a.wp = reinterpret_cast<const uint4*>(wl);
-            a.bias = reinterpret_cast<const float*>(wl + frag_bytes(L.Cin, L.Cout, L.taps));
-            a.y = static_cast<_Float16*>(where(i));
-            a.rows = (int)L.rows; a.Cout = L.Cout; a.H = L.H; a.W = L.W; a.h = L.h; a.w = L.w;
-            const dim3 grid((unsigned)L.row_tiles, (unsigned)(L.Cout / 64));
-            if (x_dtype == SBEV_F32) hipLaunchKernelGGL(resnet_stem_kernel<true>, grid, dim3(128), 0, s, a);
-            else hipLaunchKernelGGL(resnet_stem_kernel<false>, grid, dim3(128), 0, s, a);
-        } else if (L.kind == KIND_POOL) {
-            PoolArgs a;
-            a.x = static_cast<const _Float16*>(where(L.in_layer));
-            a.y = static_cast<_Float16*>(where(i));
-            a.C8 = L.Cout / 8; a.H = L.H; a.W = L.W; a.h = L.h; a.w = L.w;
-            a.items = L.rows * a.C8;
-            hipLaunchKernelGGL(resnet_pool_kernel, dim3((unsigned)((a.items + 255) / 256)), dim3(256), 0, s, a);
+        TLayer& T = t->layer[i];
+        T.kind = L.kind; T.Cin = L.Cin; T.Cout = L.Cout; T.taps = L.taps; T.stride = L.stride; T.H = L.H; T.W = L.W; T.h = L.h; T.w = L.w;
+        T.in_layer = L.in_layer; T.res_layer = L.res_layer; T.rows = L.rows; T.pack_off = L.pack_off;
+        T.out_k = L.role < 0 ? -2 - L.role : -1;
+        if (L.kind == KIND_CONV) {
+            // launch order inside a block: conv1, conv2, [downsample], conv3
+            if (which == 3) { which = 0; if (stage < 0 || block + 1 == blocks[stage]) { ++stage; block = 0; } else { ++block; } }
+            else if (which == 0) which = 1;
+            else if (which == 1) which = L.epi == EPI_BIAS ? 2 : 3;
+            else which = 3;
+            T.stage = stage; T.block = block; T.which = which;
+            if (which == 0 && block == 0 && stage == first_trainable_stage - 1) t->first_kept = L.in_layer;
         } else {
-            ConvArgs a;
-            a.x = static_cast<const _Float16*>(where(L.in_layer));
-            a.wp = reinterpret_cast<const uint4*>(wl);
-            a.bias = reinterpret_cast<const float*>(wl + frag_bytes(L.Cin, L.Cout, L.taps));
-            a.res = L.res_layer >= 0 ? static_cast<const _Float16*>(where(L.res_layer)) : nullptr;
-            a.y = static_cast<_Float16*>(where(i));
-            a.rows = (int)L.rows; a.Cin = L.Cin; a.Cout = L.Cout; a.H = L.H; a.W = L.W; a.h = L.h; a.w = L.w;
-            launch_conv(L.taps, L.stride, L.epi, L.col_tile, L.k_split, a, s);
+            T.stage = -1; T.block = 0; T.which = 0;
         }
     }
+    long long at = 0;
+    for (int i = 0; i < p.n_layers; ++i) {
+        TLayer& T = t->layer[i];
+        T.act = kNotKept;
+        if (i < t->first_kept) continue;
+        T.act = 0;
+        if (T.out_k >= 0) continue;
+        T.act = at;
+        at += align256(T.rows * T.Cout * 2);
+    }
+    t->acts_bytes = at;
+    return SBEV_OK;
+}
+
+extern "C" int sbev_resnet_forward_train(int depth, const int32_t* stage_blocks, int num_stages, int base_channels, int64_t n, int H, int W,
+                                         int n_out, const int32_t* out_indices, int first_trainable_stage, const void* x, int x_dtype,
+                                         const void* pack, void* workspace, void* acts, void* const* outs, sbev_stream_t stream) {
+    const char* who = "sbev_resnet_forward_train";
+    sbev_resnet::TrainNet t;
+    if (int st = sbev_resnet::train_net(who, depth, stage_blocks, num_stages, base_channels, n, H, W, n_out, out_indices, first_trainable_stage, &t))
+        return st;
+    NetPlan p;
+    if (int st = make_net_plan(who, depth, stage_blocks, num_stages, base_channels, n, H, W, n_out, out_indices, 0, &p)) return st;
+    SBEV_REQUIRE(x_dtype == SBEV_F32 || x_dtype == SBEV_F16, "%s: x_dtype %d (SBEV_F32 or SBEV_F16)", who, x_dtype);
+    if (n == 0) return SBEV_OK;
+    SBEV_REQUIRE(x && pack && workspace && acts && outs, "%s: null pointer", who);
+    for (int k = 0; k < n_out; ++k) SBEV_REQUIRE(outs[k] != nullptr, "%s: output %d: null pointer", who, k);
+    bool al = aligned16(x) && aligned16(pack) && aligned16(workspace) && aligned16(acts);
+    for (int k = 0; k < n_out; ++k) al = al && aligned16(outs[k]);
+    SBEV_REQUIRE(al, "%s: 16-byte alignment", who);
+    auto where = [&](int layer) -> void* {
+        const Layer& L = p.layer[layer];
+        if (L.role < 0) return outs[-2 - L.role];
+        if (layer >= t.first_kept) return static_cast<char*>(acts) + t.layer[layer].act;
+        return static_cast<char*>(workspace) + L.out_off;
+    };
+    enqueue_forward(p, x, x_dtype, pack, where, reinterpret_cast<hipStream_t>(stream));
     return sbev::check_launch(who);
 }

@@ -11,8 +11,10 @@ convolution multiplies fp16 operands, accumulates in fp32 and stores ``fp16(acc 
 reference's chain rounds the convolution, the norm and the sum to fp16 one after the other.
 
 The fold and the fragment-order pack are redone when a parameter or a buffer changed (every tensor's ``_version`` and address: an
-in-place write, ``load_state_dict`` or ``.to()`` repacks at the next call).  Inference only: the parameters are created with
-``requires_grad=False`` and a forward that would need a gradient raises.  There is no CPU path and no silent copy.
+in-place write, ``load_state_dict`` or ``.to()`` repacks at the next call).  By default inference only: the parameters are created with
+``requires_grad=False`` and a forward that would need a gradient raises.  ``ResNetBackbone(..., trainable=True, frozen_stages=f)`` also
+trains stages f + 1 .. (configs/r50_nuimg_704x256.py:31-40 with ``norm_eval=True``): a forward under grad goes through
+``BackboneFunction`` and its backward is csrc/resnet_bwd.hip (sbev_resnet_backward).  There is no CPU path and no silent copy.
 """
 import ctypes
 
@@ -101,6 +103,174 @@ def conv_f16(x, pack, residual, y, taps, stride, epilogue, col_tile=0):
     return y
 
 
+BWD_PLAN_HEAD, BWD_LAYER_WORDS, GRAD_WINDOW_LOG2 = 16, 6, 3      # SBEV_RESNET_BWD_PLAN_HEAD, .._LAYER_WORDS, SBEV_RESNET_GRAD_WINDOW_LOG2
+BWD_PLAN_WORDS = BWD_PLAN_HEAD + BWD_LAYER_WORDS * MAX_LAYERS
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _vp_opt(tensors):
+    return (ctypes.c_void_p * max(len(tensors), 1))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def wgrad_slabs(pixels):
+    """(slabs, slab_len) of a weight gradient's reduction over ``pixels`` output pixels: slab_len = max(512, ceil(pixels / 16) rounded up
+    to a multiple of 256) -- part of the backward's definition (include/sbev_hip.h: sbev_resnet_backward)"""
+    slab_len = max(512, -(-(-(-pixels // 16)) // 256) * 256)
+    return -(-pixels // slab_len), slab_len
+
+
+def backward_plan(depth, n, H, W, out_indices=(0, 1, 2, 3), num_stages=4, base_channels=64, stage_blocks=None, first_trainable_stage=2):
+    """sbev_resnet_backward_plan, a pure host function: a dict of launches, workspace_bytes, pack_bytes (the backward's image),
+    acts_bytes (the activation buffer of a trainable forward), forward_workspace_bytes, forward_pack_bytes, first_kept, the byte offsets
+    g3_offsets / g2_offset / g1_offset / part_offset inside the workspace, and layers: per launch slabs, slab_len, kept (a byte offset
+    in acts, -(2 + k): outs[k], -1: not kept), pack_offset (-1: no image), trainable, dgrad.  Raises SbevError where the plan refuses."""
+    out = (ctypes.c_int64 * BWD_PLAN_WORDS)()
+    blocks = None if stage_blocks is None else _i32(stage_blocks)
+    if stage_blocks is not None and len(stage_blocks) != num_stages:
+        raise ValueError('stage_blocks must list num_stages=%d block counts' % num_stages)
+    _lib.check(_lib.load().sbev_resnet_backward_plan(int(depth), blocks, int(num_stages), int(base_channels), int(n), int(H), int(W),
+                                                     len(out_indices), _i32(out_indices), int(first_trainable_stage), out),
+               'sbev_resnet_backward_plan')
+    v = [int(x) for x in out]
+    names = ('slabs', 'slab_len', 'kept', 'pack_offset', 'trainable', 'dgrad')
+    layers = [dict(zip(names, v[BWD_PLAN_HEAD + BWD_LAYER_WORDS * i:BWD_PLAN_HEAD + BWD_LAYER_WORDS * (i + 1)])) for i in range(v[5])]
+    return dict(launches=v[0], workspace_bytes=v[1], pack_bytes=v[2], acts_bytes=v[3], forward_workspace_bytes=v[4], first_kept=v[6],
+                g3_offsets=(v[7], v[8]), g2_offset=v[9], g1_offset=v[10], part_offset=v[11], forward_pack_bytes=v[12], layers=layers)
+
+
+def pack_layers_bwd(layers, eps=1e-5, pack=None):
+    """sbev_resnet_pack_weights_bwd on a list of ``(weight, gamma, var)`` device tensors: the transposed (3 x 3: and flipped) fragment
+    images of w', layer after layer.  Returns (the uint8 pack tensor, the byte offset of every layer's image)."""
+    ws = [l[0] for l in layers]
+    dev = ws[0].device
+    desc, at, offs = [], 0, []
+    for w in ws:
+        cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+        desc += [cin, cout, k * k]
+        offs.append(at)
+        at += k * k * cin * cout * 2
+    with torch.cuda.device(dev):
+        if pack is None:
+            pack = torch.empty(max(at, 16), dtype=torch.uint8, device=dev)
+        cols = [_vp_array([l[j] for l in layers]) for j in range(3)]
+        _lib.check(_lib.load().sbev_resnet_pack_weights_bwd(len(layers), _i32(desc), *cols, float(eps), _DTYPES[ws[0].dtype], _ptr(pack),
+                                                            _stream(dev)), 'sbev_resnet_pack_weights_bwd')
+    return pack, offs
+
+
+def conv_dgrad_f16(gy, pack, gx, taps, stride, gy2=None, stride2=1, mask=None, res=None, gp=None, scale=None, col_tile=0):
+    """sbev_conv_dgrad_f16 on tensors, nothing allocated: ``gy`` [n, h, w, Cout] and ``gx`` [n, H, W, Cin] contiguous fp16, ``pack`` the
+    image(s) of ``pack_layers_bwd``, ``gy2`` the optional second K segment (a 1 x 1 of ``stride2``), ``mask`` / ``res`` as gx, ``gp`` as gx
+    in fp16 or fp32 with ``scale`` the fp32 pair (2^e, 2^-e)."""
+    n, H, W, cin = (int(v) for v in gx.shape)
+    dev = gx.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sbev_conv_dgrad_f16(
+            _ptr(gy), _ptr(gy2), _ptr(pack), _ptr(mask), _ptr(res), _ptr(gp), _DTYPES[gp.dtype] if gp is not None else 0, _ptr(scale), _ptr(gx),
+            n, H, W, cin, int(gy.shape[3]), int(taps), int(stride), 0 if gy2 is None else int(gy2.shape[3]), int(stride2), int(col_tile),
+            _stream(dev)), 'sbev_conv_dgrad_f16')
+    return gx
+
+
+def conv_wgrad_f16(gy, x, part, taps, stride, slab_len=0):
+    """sbev_conv_wgrad_f16 on tensors: the unscaled slab partials of one convolution's weight gradient and column sums into ``part``
+    [slabs, taps * Cout * Cin + Cout] fp32; ``gy`` [n, h, w, Cout], ``x`` [n, H, W, Cin] contiguous fp16."""
+    n, H, W, cin = (int(v) for v in x.shape)
+    dev = x.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sbev_conv_wgrad_f16(_ptr(gy), _ptr(x), _ptr(part), n, H, W, cin, int(gy.shape[3]), int(taps), int(stride),
+                                                   int(slab_len), _stream(dev)), 'sbev_conv_wgrad_f16')
+    return part
+
+
+def bn_fold_backward(part, w, gamma, mean, var, eps, grad_w, grad_gamma, grad_beta, scale=None):
+    """sbev_bn_fold_backward on tensors: ``part`` [slabs, taps * Cout * Cin + Cout] fp32 -> grad_w (as w, fp32), grad_gamma, grad_beta
+    (None: skipped); ``scale`` the fp32 pair (2^e, 2^-e) or None (1)."""
+    cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+    dev = w.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sbev_bn_fold_backward(_ptr(part), int(part.shape[0]), _ptr(scale), _ptr(w), _DTYPES[w.dtype], _ptr(gamma),
+                                                     _ptr(mean), _ptr(var), float(eps), cin, cout, k * k, _ptr(grad_w), _ptr(grad_gamma),
+                                                     _ptr(grad_beta), _stream(dev)), 'sbev_bn_fold_backward')
+
+
+def backward_raw(net, n, H, W, first_trainable_stage, acts, outs, grad_outs, pack_bwd, workspace, grad_w, grad_gamma, grad_beta):
+    """sbev_resnet_backward on tensors, nothing allocated and nothing checked beyond what the C entry checks: ``net`` a ResNetBackbone
+    (its shape and its parameters), ``acts`` / ``outs`` as the trainable forward left them, ``grad_outs`` channels-last tensors of one
+    dtype, the three gradient lists one entry per convolution in launch order (None: not wanted / frozen)."""
+    pairs = net.conv_bn_pairs()
+    dev = workspace.device
+    to_nhwc = lambda t: t.permute(0, 2, 3, 1)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sbev_resnet_backward(
+            net.depth, _i32(net.stage_blocks), net.num_stages, net.base_channels, int(n), int(H), int(W), len(net.out_indices),
+            _i32(net.out_indices), int(first_trainable_stage), _ptr(acts), _vp_array([to_nhwc(o) for o in outs]),
+            _vp_array([to_nhwc(g) for g in grad_outs]), _DTYPES[grad_outs[0].dtype], _ptr(pack_bwd), _ptr(workspace),
+            _vp_array([c.weight for c, _ in pairs]), _DTYPES[pairs[0][0].weight.dtype], _vp_array([b.weight for _, b in pairs]),
+            _vp_array([b.running_mean for _, b in pairs]), _vp_array([b.running_var for _, b in pairs]), float(net.eps), _vp_opt(grad_w),
+            _vp_opt(grad_gamma), _vp_opt(grad_beta), _stream(dev)), 'sbev_resnet_backward')
+
+
+class BackboneFunction(torch.autograd.Function):
+    """A trainable backbone's forward under grad.  The node owns the buffer of the activations its backward reads (every launch's output
+    from the last frozen stage's onward), so several forwards may precede their backwards; the parameters are kept by reference
+    (``save_for_backward``: an in-place write between forward and backward is an error).  backward: the output gradients arrive
+    materialised (zeros for an unused map), all fp16 or all fp32; one that is not channels-last in memory is converted by ONE torch copy;
+    the parameter gradients are fresh fp32 tensors from ``autograd``'s parameter-gradient sink; the image gets None."""
+
+    @staticmethod
+    def forward(ctx, net, x, *params):
+        dev = x.device
+        n, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+        fts = net.frozen_stages + 1
+        with torch.cuda.device(dev):
+            wpack = net.pack()
+            net.pack_bwd()
+            bp = net.backward_plan(n, H, W)
+            acts = torch.empty(max(bp['acts_bytes'], 256), dtype=torch.uint8, device=dev)
+            p, ws = net._workspace(dev, n, H, W, False)
+            out = [torch.empty((n, h, w, c), dtype=torch.float16, device=dev).permute(0, 3, 1, 2) for c, h, w in p['outs']]
+            _lib.check(_lib.load().sbev_resnet_forward_train(
+                net.depth, _i32(net.stage_blocks), net.num_stages, net.base_channels, n, H, W, len(net.out_indices), _i32(net.out_indices), fts,
+                _ptr(x), _DTYPES[x.dtype], _ptr(wpack), _ptr(ws), _ptr(acts), _vp_array(out), _stream(dev)), 'sbev_resnet_forward_train')
+        ctx.net, ctx.acts, ctx.shape, ctx.fts = net, acts, (n, H, W), fts
+        ctx.save_for_backward(*out, *params)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *grad_outs):
+        from . import autograd as A
+        net, (n, H, W) = ctx.net, ctx.shape
+        saved = ctx.saved_tensors
+        k = len(net.out_indices)
+        outs, params = saved[:k], saved[k:]
+        gs = [g if g.permute(0, 2, 3, 1).is_contiguous() else g.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2) for g in grad_outs]
+        if any(g.dtype != gs[0].dtype for g in gs) or gs[0].dtype not in _DTYPES:
+            raise TypeError('ResNetBackbone backward: the output gradients must be all fp16 or all fp32')
+        dev = outs[0].device
+        need = ctx.needs_input_grad[2:]
+        index = net._trainable_conv_index(ctx.fts)           # convolution number (launch order) of every (w, gamma, beta) triple in params
+        nconv = len(net.conv_bn_pairs())
+        gw, gg, gb = [None] * nconv, [None] * nconv, [None] * nconv
+        with torch.cuda.device(dev):
+            sink = lambda p: A._NO_TAP.sink(False, id(p), p, tuple(p.shape))[0]
+            grads = [sink(p) if want else None for p, want in zip(params, need)]
+            for t, j in enumerate(index):
+                gw[j], gg[j], gb[j] = grads[3 * t], grads[3 * t + 1], grads[3 * t + 2]
+                if gw[j] is None:      # the C entry always stores a weight gradient
+                    gw[j] = torch.empty(params[3 * t].shape, dtype=torch.float32, device=dev)
+            if n == 0:
+                for g in grads:
+                    if g is not None:
+                        g.zero_()
+            ws = net._backward_workspace(dev, n, H, W)
+            backward_raw(net, n, H, W, ctx.fts, ctx.acts, outs, gs, net.pack_bwd(), ws, gw, gg, gb)
+        return (None, None, *[A._NO_TAP.commit(False, id(p), g) if want else None for p, g, want in zip(params, grads, need)])
+
+
 class _Bottleneck(nn.Module):
     """the parameters of one block under torchvision's / mmdet's names (the launches are the backbone's)"""
 
@@ -126,12 +296,20 @@ class ResNetBackbone(nn.Module):
     ``img_backbone.*`` entries load with ``strict=True``), He-normal weights.  ``stage_blocks`` overrides the blocks per stage (tests).
     Accepted without effect (inference only): ``frozen_stages``, ``norm_eval=True``, ``with_cp``, ``zero_init_residual``, ``init_cfg``,
     ``pretrained``, ``requires_grad`` inside ``norm_cfg``.  Not built, and refused by name: ``style='caffe'``, a depth below 50, ``dcn``,
-    ``deep_stem``, ``avg_down``, dilations, ``norm_eval=False``, other strides, an ``out_dtype`` other than fp16."""
+    ``deep_stem``, ``avg_down``, dilations, ``norm_eval=False``, other strides, an ``out_dtype`` other than fp16.
+
+    ``trainable=False`` (the default) behaves exactly so.  ``trainable=True``: ``frozen_stages=f`` (0 .. num_stages) takes effect -- the
+    stem and stages 1 .. f stay frozen, the convolution weights of the later stages get ``requires_grad=True`` and, unless
+    ``norm_cfg['requires_grad']`` is False, so do their BatchNorm gamma / beta; ``norm_eval=True`` stays mandatory (running statistics
+    always).  A forward under grad then goes through ``BackboneFunction``; under ``torch.no_grad()`` nothing differs, bit for bit.
+    ``with_cp`` stays accepted without effect: nothing is recomputed, the activations are kept.  Refused by name: ``frozen_stages=-1``
+    with ``trainable=True`` (a trainable stem: the 7 x 7 weight gradient and the max-pool backward are not built), an image that requires
+    a gradient, a trainable forward under a graph capture."""
 
     def __init__(self, depth=50, num_stages=4, out_indices=(0, 1, 2, 3), style='pytorch', base_channels=64, norm_cfg=None,
                  out_dtype=torch.float16, stage_blocks=None, in_channels=3, strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1), frozen_stages=-1,
                  norm_eval=True, with_cp=False, zero_init_residual=True, dcn=None, stage_with_dcn=(False, False, False, False),
-                 deep_stem=False, avg_down=False, conv_cfg=None, plugins=None, init_cfg=None, pretrained=None):
+                 deep_stem=False, avg_down=False, conv_cfg=None, plugins=None, init_cfg=None, pretrained=None, trainable=False):
         super().__init__()
         if style != 'pytorch':
             raise ValueError("ResNetBackbone: style=%r is not built (the stride sits on the 3 x 3: style='pytorch')" % (style,))
@@ -157,6 +335,11 @@ class ResNetBackbone(nn.Module):
             raise ValueError('ResNetBackbone: conv_cfg / plugins are not built')
         if out_dtype != torch.float16:
             raise ValueError('ResNetBackbone: out_dtype=%r (torch.float16, what FPNNeck reads, is built)' % (out_dtype,))
+        self.trainable = bool(trainable)
+        self.frozen_stages = int(frozen_stages)
+        if self.trainable and self.frozen_stages < 0:
+            raise ValueError('ResNetBackbone: frozen_stages=%r with trainable=True is not built (a trainable stem needs the 7 x 7 weight '
+                             'gradient and the max-pool backward): freeze at least the stem, frozen_stages >= 0' % (frozen_stages,))
         norm_cfg = dict(norm_cfg or {})
         if norm_cfg.get('type', 'BN2d') not in ('BN', 'BN2d'):
             raise ValueError('ResNetBackbone: norm_cfg type=%r is not built (BatchNorm2d is)' % (norm_cfg.get('type'),))
@@ -186,10 +369,21 @@ class ResNetBackbone(nn.Module):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
         for p in self.parameters():
             p.requires_grad_(False)
+        if self.trainable:
+            norms_learn = norm_cfg.get('requires_grad', True) is not False
+            for s in range(self.frozen_stages, num_stages):
+                for block in getattr(self, 'layer%d' % (s + 1)):
+                    for conv, bn in block.pairs():
+                        conv.weight.requires_grad_(True)
+                        bn.weight.requires_grad_(norms_learn)
+                        bn.bias.requires_grad_(norms_learn)
         self.eval()
         self._pack = None               # folded weight image at a fixed address per device
         self._pack_key = None
         self._workspaces = {}           # (device index, n, H, W, keep) -> (plan, uint8 workspace at a fixed address)
+        self._pack_bwd = None           # the backward's weight image (transposed / flipped w'), same version key
+        self._pack_bwd_key = None
+        self._bwd_workspaces = {}       # (device index, n, H, W) -> uint8 workspace of the backward
 
     # ---- weights
     def conv_bn_pairs(self):
@@ -227,6 +421,57 @@ class ResNetBackbone(nn.Module):
         self._pack_key = key
         return self._pack
 
+    def _trainable_conv_index(self, first_trainable_stage):
+        """convolution numbers (launch order, 0 the stem) of the stages from first_trainable_stage on"""
+        at, index = 1, []
+        for s in range(self.num_stages):
+            for block in getattr(self, 'layer%d' % (s + 1)):
+                k = len(block.pairs())
+                if s >= first_trainable_stage - 1:
+                    index += list(range(at, at + k))
+                at += k
+        return index
+
+    def pack_bwd(self):
+        """The backward's weight image (sbev_resnet_pack_weights_bwd), packed now if a parameter or a statistic changed since its last
+        pack.  Returns the image."""
+        pairs = self.conv_bn_pairs()
+        layers = [(c.weight, b.weight, b.bias, b.running_mean, b.running_var) for c, b in pairs]
+        dev = layers[0][0].device
+        key = (self.frozen_stages,) + tuple((t.data_ptr(), t._version) for l in layers for t in l)
+        if key == self._pack_bwd_key:
+            return self._pack_bwd
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ResNetBackbone backward under a capture with weights that are not packed')
+        self.pack()           # its checks of devices, dtypes and contiguity hold for this image too
+        bp = self.backward_plan(1, 32, 32)
+        order = sorted((l['pack_offset'], i) for i, l in enumerate(bp['layers']) if l['pack_offset'] >= 0)
+        todo = [(layers[i - 1][0], layers[i - 1][1], layers[i - 1][4]) for _, i in order]          # launch i is convolution i - 1
+        if self._pack_bwd is not None and (self._pack_bwd.device != dev or self._pack_bwd.numel() < bp['pack_bytes']):
+            self._pack_bwd = None
+        self._pack_bwd, offs = pack_layers_bwd(todo, self.eps, self._pack_bwd)
+        assert offs == [o for o, _ in order]
+        self._pack_bwd_key = key
+        return self._pack_bwd
+
+    def backward_plan(self, n, H, W):
+        return backward_plan(self.depth, n, H, W, self.out_indices, self.num_stages, self.base_channels, self.stage_blocks,
+                             self.frozen_stages + 1)
+
+    def _workspace(self, dev, n, H, W, keep):
+        key = (dev.index, n, H, W, keep)
+        if key not in self._workspaces:
+            p = self.plan(n, H, W, keep)
+            self._workspaces[key] = (p, torch.empty(max(p['workspace_bytes'], 256), dtype=torch.uint8, device=dev))
+        return self._workspaces[key]
+
+    def _backward_workspace(self, dev, n, H, W):
+        key = (dev.index, n, H, W)
+        ws = self._bwd_workspaces.get(key)
+        if ws is None:
+            ws = self._bwd_workspaces[key] = torch.empty(max(self.backward_plan(n, H, W)['workspace_bytes'], 256), dtype=torch.uint8, device=dev)
+        return ws
+
     # ---- the call
     def plan(self, n, H, W, keep=False):
         return plan(self.depth, n, H, W, self.out_indices, self.num_stages, self.base_channels, self.stage_blocks, keep)
@@ -245,9 +490,12 @@ class ResNetBackbone(nn.Module):
             raise TypeError('ResNetBackbone: x must be fp32 or fp16 (got %s)' % x.dtype)
         if not x.is_contiguous():
             raise ValueError('ResNetBackbone: x is not NCHW-contiguous (ImageFrontEnd emits NCHW; no copy is made here)')
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        wants_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if wants_grad and not self.trainable:
             raise RuntimeError('ResNetBackbone is inference only (its backward is not built): call it under torch.no_grad() and keep the '
                                'parameters frozen')
+        if wants_grad:
+            return self._forward_train(x, out, keep)
         dev = x.device
         n, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
         if H < 1 or W < 1:
@@ -256,11 +504,7 @@ class ResNetBackbone(nn.Module):
             raise ValueError('ResNetBackbone: x is on %s, the parameters on %s' % (dev, self.conv1.weight.device))
         with torch.cuda.device(dev):
             wpack = self.pack()
-            key = (dev.index, n, H, W, keep is not None)
-            if key not in self._workspaces:
-                p = self.plan(n, H, W, keep is not None)
-                self._workspaces[key] = (p, torch.empty(max(p['workspace_bytes'], 256), dtype=torch.uint8, device=dev))
-            p, ws = self._workspaces[key]
+            p, ws = self._workspace(dev, n, H, W, keep is not None)
             shapes = [(n, c, h, w) for c, h, w in p['outs']]
             if out is None:
                 out = [torch.empty((n, h, w, c), dtype=torch.float16, device=dev).permute(0, 3, 1, 2) for _, c, h, w in shapes]
@@ -284,3 +528,28 @@ class ResNetBackbone(nn.Module):
                     nbytes = n * l['h'] * l['w'] * l['cout'] * 2
                     keep.append(ws[l['where']:l['where'] + nbytes].view(torch.float16).view(n, l['h'], l['w'], l['cout']).permute(0, 3, 1, 2))
         return out
+
+    def _forward_train(self, x, out, keep):
+        """a forward that needs a gradient, on checked x: through BackboneFunction"""
+        if x.requires_grad:
+            raise ValueError('ResNetBackbone: the image requires a gradient; no image gradient is ever produced (the stem is frozen): detach it')
+        if out is not None or keep is not None:
+            raise ValueError('ResNetBackbone: out= / keep= are not taken by a forward that needs a gradient (autograd owns its outputs)')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ResNetBackbone: a trainable forward under a graph capture (the backbone inside CapturedHeadTrainStep) is not '
+                               'built: the weight packs would have to move into the graph')
+        if x.device != self.conv1.weight.device:
+            raise ValueError('ResNetBackbone: x is on %s, the parameters on %s' % (x.device, self.conv1.weight.device))
+        if x.shape[2] < 1 or x.shape[3] < 1:
+            raise ValueError('ResNetBackbone: an empty image (%d x %d)' % (x.shape[2], x.shape[3]))
+        fts = self.frozen_stages + 1
+        if fts > self.num_stages:
+            raise RuntimeError('ResNetBackbone: frozen_stages=%d freezes every stage but a parameter requires a gradient' % self.frozen_stages)
+        pairs = self.conv_bn_pairs()
+        index = self._trainable_conv_index(fts)
+        allowed = {id(t) for j in index for t in (pairs[j][0].weight, pairs[j][1].weight, pairs[j][1].bias)}
+        for name, p in self.named_parameters():
+            if p.requires_grad and id(p) not in allowed:
+                raise RuntimeError('ResNetBackbone: %s requires a gradient but lies in the frozen part (frozen_stages=%d)' % (name, self.frozen_stages))
+        params = [t for j in index for t in (pairs[j][0].weight, pairs[j][1].weight, pairs[j][1].bias)]
+        return list(BackboneFunction.apply(self, x, *params))
