@@ -1016,6 +1016,21 @@ int sbev_decoder_row_chain(int enable);
  *    weights (float offset into the image, -1: none), LDS float offset and row stride of the input rows, KH (k-pieces per 64-column
  *    group), items (= column groups x KH), chunks (16-k chunks per item), kh0, KHT (the Linear covers pieces [kh0, kh0 + KH) of KHT). */
 int sbev_decoder_chain_plan(const sbev_decoder_config* cfg, int kind, int with_front, int pair_ok, int cus, int32_t* out, int capacity);
+/* Fixed plans.  A launch's unit tables depend on the chain, rg, pair, with_front and the column-group counts of the in-projection and of
+ * the sampling Linear only; for the keys of config 2's launches (tail on pairs with / without front, attention chain, front: rg as
+ * planned, 13 and 2 column groups) the library holds kernels with the table compiled in -- no table in the kernel arguments, no scalar
+ * load of one between two units.  A launch takes such a kernel when its key is covered and its planned table equals the compiled one
+ * (always, unless SBEV_CHAIN_TIE_SMALL / _PAIR_Q0 / _RG / _PAIR16 is set in the environment); results are bit-identical either way.
+ * sbev_decoder_chain_fixed(0 / 1) switches them (returns the previous setting; default 1, SBEV_CHAIN_FIXED=0 in the environment starts
+ * with 0).  The switch is NOT one of sbev_decoder_switches: a captured step keeps the kernels it was recorded with.
+ * sbev_decoder_chain_fixed_plan: sbev_decoder_chain_plan's words (same arguments, same layout) with the unit tables taken from the
+ * compiled-in table of the fixed kernel that covers the launch's key, or 0 = none covers it (also: config not covered by the row
+ * chains at all); -1 on a short buffer.  Touches no device.
+ * sbev_decoder_chain_fixed_launches: row-chain launches since the library was loaded that took a fixed kernel (a captured launch counts
+ * once, at its capture). */
+int sbev_decoder_chain_fixed(int enable);
+int64_t sbev_decoder_chain_fixed_launches(void);
+int sbev_decoder_chain_fixed_plan(const sbev_decoder_config* cfg, int kind, int with_front, int pair_ok, int cus, int32_t* out, int capacity);
 
 /* Pair mode of the tail chain (round 4).  A chain workgroup streams every weight of its chain through its CU's ~60 GB/s L2 path, so
  * where two workgroups per row block fit the device in ONE round (<= ~1000 rows at 8 rows per pair, <= ~2000 at 16, on 256 CUs) the

@@ -244,6 +244,9 @@ SIGNATURES = {
     'sbev_decoder_chain_pack': (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     'sbev_decoder_chain_plan': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p, ctypes.c_int]),
     'sbev_decoder_row_chain': (ctypes.c_int, [ctypes.c_int]),
+    'sbev_decoder_chain_fixed_plan': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i32p, ctypes.c_int]),
+    'sbev_decoder_chain_fixed': (ctypes.c_int, [ctypes.c_int]),
+    'sbev_decoder_chain_fixed_launches': (ctypes.c_int64, []),
     'sbev_decoder_chain_pair': (ctypes.c_int, [ctypes.c_int]),
     'sbev_decoder_chain_pair_timeouts': (ctypes.c_int64, []),
     'sbev_decoder_chain_pair_faults': (ctypes.c_int64, []),

@@ -20,7 +20,8 @@
 // adds the k-halves in a fixed order, + bias, ReLU / residual / LayerNorm, and writes the next unit's input rows.
 // Results equal the op-by-op launches to fp32 round-off (other summation order), not bit for bit; DESIGN_HISTORY.md section 4.
 //
-// In this file: the kernels (row_chain_kernel<PRE, RG, PAIR> in 11 instantiations, pack_kernel, copy_pad_kernel), then the host side,
+// In this file: the kernels (row_chain_kernel<PRE, RG, PAIR> in 11 instantiations and row_chain_fixed_kernel, the same body with a unit
+// table compiled in, in 4; pack_kernel, copy_pad_kernel), the constexpr planner of the unit tables between them, then the host side,
 // each thing described once: the table of the image's 12 matrices (kMats -> pack_map, the pack jobs, the warm spans), the table of the
 // instantiations (kInst -> launch, the LDS attribute, chain_lds_ready), and the plan of a launch (chain_plan: instantiation, grid, both
 // pair members' unit tables from ONE function of the share, warm span, small-vector range; pure host, exported as
@@ -30,6 +31,9 @@
 #include "sample_point.hpp"
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
+#include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -76,13 +80,18 @@ struct Unit {
 #define SBEV_TRACE(i)
 #endif
 
-struct ChainArgs {
+// The kernel arguments: what every row-chain kernel takes (ChainCommon), behind either the unit tables (ChainArgs: row_chain_kernel,
+// which reads them at run time) or the image's base alone (ChainArgsFx: row_chain_fixed_kernel, whose tables are constants of the
+// instantiation, see "fixed plans" below).
+struct UnitTab {
+    Unit units[8];
+    Unit units_b[8];             // pair mode: the second member's units (same count, same epilogues)
+};
+struct ChainCommon {
 #ifdef SBEV_CHAIN_TRACE
     long long* trace;
 #endif
-    Unit units[8];
-    Unit units_b[8];             // pair mode: the second member's units (same count, same epilogues)
-    int n_units, pre, front;     // front: EPI_OUT continues with the next layer's position encoder
+    int n_units, pre, front;     // n_units: of the tables (a fixed kernel knows its own); front: EPI_OUT continues with the next layer's position encoder
     int n_pairs;                 // pair mode: pairs of workgroups (= row blocks)
     float* pair_x;               // pair mode: exchange rows [n_pairs][3][R][256] (ffn.1 partial sums of member 0 / 1, x rows)
     unsigned* pair_sync;         // pair mode: one arrival counter per pair; the ATTENTION chain of the same layer zeroes them:
@@ -113,6 +122,10 @@ struct ChainArgs {
     sbev_ops::SamplePointArgs proj;
     float eps;
     uint32_t* skip_hdr;          // PRE_FRONT of a step with a prefix cache (sbev_common.hpp: prefix_clean), else null; read by that instantiation only
+};
+struct ChainArgs : UnitTab, ChainCommon {};
+struct ChainArgsFx : ChainCommon {
+    const float* image;          // the chain_pack image: the constant tables hold float offsets into it
 };
 
 // ---- the weight stream --------------------------------------------------------------------------------------------------
@@ -163,7 +176,7 @@ template <int RG> constexpr Offs offs_of() { return Offs{Lay<RG>::OFF_X2, Lay<RG
 // weight span between them and touch one dword per 128-byte line of their slice up front, while the prologue runs; the
 // loads go to an LDS sink (no register to keep alive) and are older than every chunk load, so the counted waits stay valid.
 template <int RG>
-__device__ __forceinline__ void warm_l2(const ChainArgs& a, int wave, int lane) {
+__device__ __forceinline__ void warm_l2(const ChainCommon& a, int wave, int lane) {
     const int per_xcd = ((int)gridDim.x + 7) / 8;
     const int parts = per_xcd < 32 ? per_xcd : 32;
     const int part = ((int)blockIdx.x / 8) % parts;
@@ -188,22 +201,13 @@ struct Walk {            // position of a wave in its item stream
     int u, it, step;
 };
 
-__device__ __forceinline__ int unit_items(const Unit* U, int u) { return U[u].a.items + U[u].b.items; }
-
-// first item of this wave at or after (u, it)
-__device__ __forceinline__ void walk_settle(const ChainArgs& a, const Unit* U, Walk& w, int wave) {
-    while (w.u < a.n_units && w.it >= unit_items(U, w.u)) {
-        ++w.u;
-        w.it = wave;
-    }
-}
-
-__device__ __forceinline__ const float* item_weights(const Unit& un, int it) {
-    const bool second = it >= un.a.items;
-    const Lin& l = second ? un.b : un.a;
-    const int j = it - (second ? un.a.items : 0);
+__device__ __forceinline__ const float* lin_item_weights(const Lin& l, int j) {
     const int piece = l.KHT == l.KH ? j : (j / l.KH) * l.KHT + l.kh0 + j % l.KH;
     return l.wp + (long long)piece * (l.chunks * CHUNK_FLOATS);
+}
+__device__ __forceinline__ const float* item_weights(const Unit& un, int it) {
+    const bool second = it >= un.a.items;
+    return lin_item_weights(second ? un.b : un.a, it - (second ? un.a.items : 0));
 }
 
 // (M0 carries the LDS destination of an LDS-DMA load and is written inside the asm block; hipcc does not use M0 anywhere else
@@ -222,7 +226,6 @@ __device__ __forceinline__ void issue_chunk(const float* g, unsigned lds_byte, u
 }
 
 struct Stream {
-    const Unit* U;       // the workgroup's unit table (kernel arguments)
     Walk iw;             // item of the next chunk to issue
     const float* g;      // its weights (next chunk)
     int nchunk;          // chunks of that item
@@ -230,43 +233,63 @@ struct Stream {
     int islot, uslot;    // issued % RING_SLOTS, used % RING_SLOTS
     unsigned ring_byte;  // LDS byte address of this wave's ring
     unsigned voff;       // lane * 16
+    // fixed plans only (FxTab): the item being multiplied and the wave's next one -- their weights; whether there is a next one; whether
+    // the stream has anything left to issue
+    const float *g_cur, *g_next;
+    bool has_next, live;
 };
-
-__device__ __forceinline__ void stream_seek(const ChainArgs& a, Stream& st, int wave) {
-    walk_settle(a, st.U, st.iw, wave);
-    st.iw.step = 0;
-    if (st.iw.u < a.n_units) {
-        const Unit& un = st.U[st.iw.u];
-        st.g = item_weights(un, st.iw.it);
-        st.nchunk = st.iw.it >= un.a.items ? un.b.chunks : un.a.chunks;
-    }
-}
-
-__device__ __forceinline__ void stream_issue(const ChainArgs& a, Stream& st, int wave) {
-    if (st.iw.u >= a.n_units) return;
-    issue_chunk(st.g + st.iw.step * CHUNK_FLOATS, st.ring_byte + (unsigned)st.islot * (CHUNK_FLOATS * 4), st.voff);
-    ++st.issued;
-    st.islot = st.islot == RING_SLOTS - 1 ? 0 : st.islot + 1;
-    if (++st.iw.step == st.nchunk) {
-        st.iw.it += NWAVE;
-        stream_seek(a, st, wave);
-    }
-}
 
 // RG > 1: the next chunk of the stream into 16 registers (four 1 KB wave-loads; the compiler counts the waits)
 struct RChunk { float4 q[4]; };
-// The loads are UNCONDITIONAL (past the end of the stream a wave re-reads the first chunk of its last item, <= 16 KB per wave):
-// a load under a branch would make the number of younger loads unknown to the compiler, which then waits vmcnt(0) before every
-// chunk instead of vmcnt(12).
-__device__ __forceinline__ void stream_load(const ChainArgs& a, Stream& st, int wave, int lane, RChunk& c) {
-    const float* g = st.g + st.iw.step * CHUNK_FLOATS + lane * 4;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) c.q[m] = *reinterpret_cast<const float4*>(g + 256 * m);
-    if (st.iw.u < a.n_units && ++st.iw.step == st.nchunk) {
-        st.iw.it += NWAVE;
-        stream_seek(a, st, wave);
+
+// How the stream finds its way through a unit table (TAB).  RtTab walks the table in the kernel arguments: it carries a position (Walk)
+// and seeks the next item whenever one is issued to its end.  FxTab ("fixed plans" below) knows the table at compile time and is told
+// where the multiply is (begin_item, begin_round): what to issue follows from that with immediates.
+struct RtTab {
+    const ChainArgs& a;
+    const Unit* U;       // the workgroup's unit table (kernel arguments)
+
+    // first item of this wave at or after (u, it)
+    __device__ __forceinline__ void settle(Walk& w, int wave) const {
+        while (w.u < a.n_units && w.it >= U[w.u].a.items + U[w.u].b.items) {
+            ++w.u;
+            w.it = wave;
+        }
     }
-}
+    __device__ __forceinline__ void seek(Stream& st, int wave) const {
+        settle(st.iw, wave);
+        st.iw.step = 0;
+        if (st.iw.u < a.n_units) {
+            const Unit& un = U[st.iw.u];
+            st.g = item_weights(un, st.iw.it);
+            st.nchunk = st.iw.it >= un.a.items ? un.b.chunks : un.a.chunks;
+        }
+    }
+    __device__ __forceinline__ void issue(Stream& st, int wave) const {
+        if (st.iw.u >= a.n_units) return;
+        issue_chunk(st.g + st.iw.step * CHUNK_FLOATS, st.ring_byte + (unsigned)st.islot * (CHUNK_FLOATS * 4), st.voff);
+        ++st.issued;
+        st.islot = st.islot == RING_SLOTS - 1 ? 0 : st.islot + 1;
+        if (++st.iw.step == st.nchunk) {
+            st.iw.it += NWAVE;
+            seek(st, wave);
+        }
+    }
+    // The loads are UNCONDITIONAL (past the end of the stream a wave re-reads the first chunk of its last item, <= 16 KB per wave):
+    // a load under a branch would make the number of younger loads unknown to the compiler, which then waits vmcnt(0) before every
+    // chunk instead of vmcnt(12).
+    __device__ __forceinline__ void load(Stream& st, int wave, int lane, RChunk& c) const {
+        const float* g = st.g + st.iw.step * CHUNK_FLOATS + lane * 4;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) c.q[m] = *reinterpret_cast<const float4*>(g + 256 * m);
+        if (st.iw.u < a.n_units && ++st.iw.step == st.nchunk) {
+            st.iw.it += NWAVE;
+            seek(st, wave);
+        }
+    }
+    template <class UC> __device__ __forceinline__ void begin_item(UC, Stream&, int, int) const {}
+    __device__ __forceinline__ void begin_round(Stream&, int, int) const {}
+};
 constexpr int RDEPTH = 4;        // chunks in registers per wave (one multiplying, three on their way)
 
 #define SBEV_MF(KK, BV) acc[(KK) & 1] = __builtin_amdgcn_mfma_f32_4x4x1f32(av, BV, acc[(KK) & 1], 4, KK, 0);
@@ -275,7 +298,8 @@ constexpr int RDEPTH = 4;        // chunks in registers per wave (one multiplyin
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // one item (64 columns x 128 k) of Linear `l`: 8 chunks from the ring; partial sums -> P[slot]
-__device__ __forceinline__ void mma_item(const ChainArgs& a, Stream& st, const Lin& l, int j, float* smem, int pslot, int lane, int wave) {
+template <class TAB>
+__device__ __forceinline__ void mma_item(const TAB& a, Stream& st, const Lin& l, int j, float* smem, int pslot, int lane, int wave) {
     constexpr int R = 4, OFF_RING = Lay<1>::OFF_RING, OFF_P = Lay<1>::OFF_P;
     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     const int kh = j % l.KH;
@@ -296,7 +320,7 @@ __device__ __forceinline__ void mma_item(const ChainArgs& a, Stream& st, const L
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         ++st.used;
         st.uslot = st.uslot == RING_SLOTS - 1 ? 0 : st.uslot + 1;
-        stream_issue(a, st, wave);
+        a.issue(st, wave);
         __builtin_amdgcn_sched_barrier(0);
         SBEV_MSTEP(0, q0) SBEV_MSTEP(1, q1) SBEV_MSTEP(2, q2) SBEV_MSTEP(3, q3)
     }
@@ -307,8 +331,8 @@ __device__ __forceinline__ void mma_item(const ChainArgs& a, Stream& st, const L
 
 // RG > 1: one item (64 columns x 16 l.chunks k) for the workgroup's RG row groups; the chunk registers rb[d] are consumed and
 // refilled in ring order (l.chunks is a multiple of RDEPTH, so slot d of the ring is a compile-time register set)
-template <int RG>
-__device__ __forceinline__ void mma_item_wide(const ChainArgs& a, Stream& st, RChunk (&rb)[RDEPTH], const Lin& l, int j, float* smem, int pslot,
+template <int RG, class TAB>
+__device__ __forceinline__ void mma_item_wide(const TAB& a, Stream& st, RChunk (&rb)[RDEPTH], const Lin& l, int j, float* smem, int pslot,
                                               int lane, int wave) {
     constexpr int NACC = RG >= 4 ? 1 : 2;          // >= 4 independent accumulator chains back to back
     f32x4 acc[RG][NACC];
@@ -321,7 +345,9 @@ __device__ __forceinline__ void mma_item_wide(const ChainArgs& a, Stream& st, RC
     float avn[RG];                                 // the A registers (16 k x 4 rows per row group) of the NEXT chunk: read one chunk ahead
 #pragma unroll
     for (int rg = 0; rg < RG; ++rg) avn[rg] = arow[rg * 4 * l.ld];
+#pragma nounroll      // (a fixed plan's constant chunk count must not multiply the code: 64 RG MFMAs per round already)
     for (int s0 = 0; s0 < l.chunks; s0 += RDEPTH) {
+        a.begin_round(st, l.chunks, s0);
 #pragma unroll
         for (int d = 0; d < RDEPTH; ++d) {
             float av[RG];
@@ -337,7 +363,7 @@ __device__ __forceinline__ void mma_item_wide(const ChainArgs& a, Stream& st, RC
 #undef SBEV_MWSTEP
 #undef SBEV_MW
             __builtin_amdgcn_sched_barrier(0);
-            stream_load(a, st, wave, lane, rb[d]);       // refill: three chunks stay in flight while the next one multiplies
+            a.load(st, wave, lane, rb[d]);               // refill: three chunks stay in flight while the next one multiplies
         }
     }
     float* p = smem + Lay<RG>::OFF_P + pslot * (Lay<RG>::R * 64) + lane;
@@ -470,7 +496,7 @@ __device__ __forceinline__ void store_rows(float* smem, int off, int ld, int row
 
 // position_encoder[0..2]: Linear(3 -> 256) + LayerNorm + ReLU of one row (sparsebev_transformer.py:116-119), into LDS
 template <int RG>
-__device__ __forceinline__ void pe0_row(const ChainArgs& a, float* smem, int row, int lane, float x0, float x1, float x2) {
+__device__ __forceinline__ void pe0_row(const ChainCommon& a, float* smem, int row, int lane, float x0, float x1, float x2) {
     constexpr int OFF_PARAM = Lay<RG>::OFF_PARAM, OFF_C = Lay<RG>::OFF_C;
     const float* pv = smem + OFF_PARAM;
     const LnW lw(pv + PV_PE1G, pv + PV_PE1B, lane);
@@ -485,9 +511,306 @@ __device__ __forceinline__ void pe0_row(const ChainArgs& a, float* smem, int row
     store_rows(smem, OFF_C, LDX, row, lane, v);
 }
 
+// ---- the plan of a launch, as far as it is a COMPILE-TIME function of the config: the image, the unit tables -----------------------------
+// (constexpr: chain_plan evaluates it on the host at every launch, the fixed-plan kernels at compile time -- one description)
+using Cfg = sbev_decoder_config;
+
+// ---- the packed weight image, described once ------------------------------------------------------------------------------------------
+// The 12 matrices in image order: the member of sbev_decoder_weights, its rows N and its columns K.  pack_map, the pack jobs,
+// sbev_decoder_chain_pack_floats and the launches' warm spans ("matrices i .. j") all walk this one table.  Behind the matrices lie the
+// small vectors [tail | front | attention] at their PV_* offsets (the vecs[] table of sbev_decoder_chain_pack).
+enum Mat { M_FFN0, M_FFN1, M_CLS0, M_REG0, M_CLS3, M_REG2, M_CLS6, M_REG4, M_PE3, M_ATTN_IN, M_ATTN_OUT, M_SAMP, N_MAT };
+constexpr int so_cols(const Cfg& c) { return c.G * c.P * (3 + c.L); }      // the sampling Linear's rows: 3 offsets + L level logits per point
+constexpr int n_embed(const Cfg& c) { return c.D; }
+constexpr int n_ffn(const Cfg& c) { return c.ffn; }
+constexpr int n_cls(const Cfg& c) { return c.num_classes; }
+constexpr int n_code(const Cfg& c) { return c.code_size; }
+constexpr int n_qkv(const Cfg& c) { return c.attn_in_rows; }
+struct MatDesc {
+    const float* sbev_decoder_weights::*w;
+    int (*N)(const Cfg&);
+    int (*K)(const Cfg&);
+};
+constexpr MatDesc kMats[N_MAT] = {
+    {&sbev_decoder_weights::ffn0_w, n_ffn, n_embed},      {&sbev_decoder_weights::ffn1_w, n_embed, n_ffn},
+    {&sbev_decoder_weights::cls0_w, n_embed, n_embed},    {&sbev_decoder_weights::reg0_w, n_embed, n_embed},
+    {&sbev_decoder_weights::cls3_w, n_embed, n_embed},    {&sbev_decoder_weights::reg2_w, n_embed, n_embed},
+    {&sbev_decoder_weights::cls6_w, n_cls, n_embed},      {&sbev_decoder_weights::reg4_w, n_code, n_embed},
+    {&sbev_decoder_weights::pe3_w, n_embed, n_embed},     {&sbev_decoder_weights::attn_in_w, n_qkv, n_embed},
+    {&sbev_decoder_weights::attn_out_w, n_embed, n_embed}, {&sbev_decoder_weights::samp_w, so_cols, n_embed}};
+
+constexpr long long packed_floats(int N, int K) { return (long long)((N + 63) / 64) * 64 * K; }
+
+struct PackMap {     // float offsets into the chain_pack image: matrix i lies at [at[i], at[i + 1])
+    long long at[N_MAT + 1];
+    constexpr long long vec() const { return at[N_MAT]; }                      // the small vectors: [tail | front | attention], PV_* offsets
+    constexpr long long total() const { return at[N_MAT] + PV_IMAGE_FLOATS; }
+    constexpr int lines(int first, int last) const { return (int)((at[last + 1] - at[first]) / 32); }      // 128-byte lines of matrices first .. last
+};
+constexpr PackMap pack_map(const Cfg& c) {
+    PackMap m{};
+    for (int i = 0; i < N_MAT; ++i) m.at[i + 1] = m.at[i] + packed_floats(kMats[i].N(c), kMats[i].K(c));
+    return m;
+}
+
+// Lin / Unit with the weights as a float offset into the image (-1: none) instead of a pointer
+struct PLin { long long w; int in_off, ld, KH, items, chunks, kh0, KHT; };
+struct PUnit { PLin a, b; int epi, col0; };
+constexpr PLin kNone{-1, 0, LDX, 1, 0, 8, 0, 1};
+
+// k-pieces per column group of a unit in which THIS SHARE of the row block (see Share) computes `cgs` column groups in all: RG = 1 keeps
+// 128-k items; RG > 1 aims at 8 items per unit (one per wave; each piece at least 64 k = RDEPTH chunks)
+// -- <= 12 slots; cost of a choice = sum over its rounds of (chunks per item) x (1 for a round of 5 .. 8 items: two waves per SIMD
+// share the MFMA pipe; 1/2 for a last round of <= 4 items: waves 0 .. 3 sit on four different SIMDs)
+// The two A/B switches of the environment that change a unit table.  They exist at run time only (chain_plan: env_tweaks); every fixed
+// plan is built with kNoTweaks, so a launch under either switch finds no equal fixed table and takes the run-time-table kernel.
+struct Tweaks {
+    bool tie_large;      // SBEV_CHAIN_TIE_SMALL unset.  Equal cost: more, shorter items
+    int q0_forced;       // SBEV_CHAIN_PAIR_Q0, -1 = unset: the in-projection's cut between the pair members
+};
+constexpr Tweaks kNoTweaks{true, -1};
+
+constexpr int pieces(int rg, int cgs, int K, bool tie_large) {
+    if (rg == 1) return 0;
+    int best = 1;
+    double best_cost = 1e30;
+    for (int kh = 1; kh <= 4 && cgs * kh <= 12 && K / kh >= 16 * RDEPTH; kh *= 2) {
+        const int items = cgs * kh, full = items / NWAVE, rest = items % NWAVE;
+        const double cost = (K / (16.0 * kh)) * (full + (rest == 0 ? 0.0 : rest <= 4 ? 0.5 : 1.0));
+        if (tie_large ? cost < best_cost + 1e-9 : cost < best_cost - 1e-9) { best_cost = cost; best = kh; }
+    }
+    return best;
+}
+
+constexpr Offs offs(int rg) { return rg == 1 ? offs_of<1>() : rg == 2 ? offs_of<2>() : offs_of<4>(); }
+
+// Who computes a unit table: the one workgroup of a row block, or one member of the pair that shares it.
+enum Share { WHOLE = -1, MEMBER0 = 0, MEMBER1 = 1 };
+
+struct UnitTables {
+    const Cfg& c;
+    const PackMap& m;
+    int rg;
+    Offs o;
+    Tweaks tw;
+
+    constexpr int pieces(int rg_, int cgs, int K) const { return ::pieces(rg_, cgs, K, tw.tie_large); }
+
+    // column groups [cg0, cg0 + ncg) of packed matrix `mat` as items of K / KH k each.  kh = 0: K / 128 (the RG = 1 items)
+    constexpr PLin lin(int mat, int in_off, int ld, int kh = 0, int cg0 = 0, int ncg = -1) const {
+        const int N = kMats[mat].N(c), K = kMats[mat].K(c);
+        const int KH = kh > 0 ? kh : K / 128;
+        if (ncg < 0) ncg = (N + 63) / 64 - cg0;
+        return PLin{m.at[mat] + (long long)cg0 * K * 64, in_off, ld, KH, ncg * KH, K / (16 * KH), 0, KH};
+    }
+    // k-half `half` of packed matrix `mat` (pair mode): kh pieces of the half, i.e. pieces [half kh, half kh + kh) of 2 kh per row
+    constexpr PLin lin_khalf(int mat, int in_off, int ld, int kh, int half) const {
+        const int N = kMats[mat].N(c), K = kMats[mat].K(c);
+        return PLin{m.at[mat], in_off, ld, kh, ((N + 63) / 64) * kh, K / (32 * kh), half * kh, 2 * kh};
+    }
+
+    // position encoder + attention in-projection (the front chain; the end of a tail with_front).  The position encoder runs where the
+    // regression branch ran (WHOLE, MEMBER1).  In-projection column groups: WHOLE all of them, in units of at most 8; MEMBER1 those from
+    // q0 onward -- it has the x rows in its LDS, member 0 gets them a hand-off (~1.5 us) later, so member 1 takes up to 8 column groups
+    // (one round of 16-chunk items) and member 0 the rest (5 of config 2's 13: 10 items of 8 chunks) -- and MEMBER0 those below q0; a
+    // member has exactly ONE in-projection unit, kNone where its share is empty.
+    constexpr int front_units(PUnit* u, int n, Share sh) const {
+        const int dcg = c.D / 64, qcg = (c.attn_in_rows + 63) / 64;
+        u[n++] = PUnit{sh != MEMBER0 ? lin(M_PE3, o.c, LDX, pieces(rg, dcg, c.D)) : kNone, kNone, EPI_PE3, 0};
+        const int q0_forced = tw.q0_forced;
+        const int q0 = q0_forced >= 0 && q0_forced <= qcg ? q0_forced : (qcg > 8 ? qcg - 8 : qcg / 2);
+        const int lo = sh == MEMBER1 ? q0 : 0, hi = sh == MEMBER0 ? q0 : qcg;
+        const int cut = sh == WHOLE ? 8 : qcg + 1;
+        if (sh != WHOLE && lo == hi) u[n++] = PUnit{kNone, kNone, EPI_QKV, lo * 64};
+        for (int cg0 = lo; cg0 < hi; cg0 += cut) {
+            const int n_here = hi - cg0 < cut ? hi - cg0 : cut;
+            u[n++] = PUnit{lin(M_ATTN_IN, o.x2, LDX, pieces(rg, n_here, c.D), cg0, n_here), kNone, EPI_QKV, cg0 * 64};
+        }
+        return n;
+    }
+
+    // The tail's unit table, written once as a function of the share (see "pair mode" above the kernel):
+    //   ffn.layers.0   WHOLE: all column groups; member s: half of them, from s x half on
+    //   ffn.layers.1   WHOLE: all of k (lin); member s: k-half s (lin_khalf) for all columns
+    //   branches       the classification side sits in Unit::a, the regression side in Unit::b; WHOLE carries both, MEMBER0 the
+    //                  classification side, MEMBER1 the regression side (the other Lin is kNone)
+    //   front          front_units
+    // Every pieces() call gets the column groups THIS SHARE computes in that unit: both branch sides count for WHOLE (2 dcg; 2 for the
+    // output unit), one side for a member (dcg; 1).  Both members get the same number of units and the same epilogue sequence.
+    constexpr int tail_units(PUnit* u, Share sh, bool with_front) const {
+        const int dcg = c.D / 64, fcg = c.ffn / 64;
+        const bool cls = sh != MEMBER1, reg = sh != MEMBER0;
+        const int sides = (cls ? 1 : 0) + (reg ? 1 : 0);
+        const int f_ncg = sh == WHOLE ? fcg : fcg / 2, f_cg0 = sh == WHOLE ? 0 : sh * f_ncg;
+        int n = 0;
+        u[n++] = PUnit{lin(M_FFN0, o.x2, LDX, pieces(rg, f_ncg, c.D), f_cg0, f_ncg), kNone, EPI_FFN0, 0};
+        u[n++] = PUnit{sh == WHOLE ? lin(M_FFN1, o.h, LDH, pieces(rg, dcg, c.ffn)) : lin_khalf(M_FFN1, o.h, LDH, pieces(rg, dcg, c.ffn / 2), sh),
+                       kNone, EPI_FFN1, 0};
+        const auto branch = [&](int mat_c, int in_c, int mat_r, int in_r, int cgs_side, int epi) {
+            const int kh = pieces(rg, sides * cgs_side, c.D);
+            return PUnit{cls ? lin(mat_c, in_c, LDX, kh) : kNone, reg ? lin(mat_r, in_r, LDX, kh) : kNone, epi, 0};
+        };
+        u[n++] = branch(M_CLS0, o.x3, M_REG0, o.x3, dcg, EPI_BR1);
+        u[n++] = branch(M_CLS3, o.c, M_REG2, o.r, dcg, EPI_BR2);
+        u[n++] = branch(M_CLS6, o.c, M_REG4, o.r, 1, EPI_OUT);
+        return with_front ? front_units(u, n, sh) : n;
+    }
+};
+
+// The unit tables of one launch: chain `pre` on row blocks of 4 rg rows, on pairs or not, the tail with or without the next front
+struct PlanUnits {
+    int n_units;
+    PUnit units[2][8];           // [member]; units[1] in pair mode only (same count, same epilogues)
+};
+constexpr PlanUnits plan_units(const Cfg& c, int pre, int rg, bool pair, bool with_front, Tweaks tw) {
+    const PackMap m = pack_map(c);
+    const UnitTables t{c, m, rg, offs(rg), tw};
+    PlanUnits p{};
+    if (pre == PRE_FRONT) {
+        p.n_units = t.front_units(p.units[0], 0, WHOLE);
+    } else if (pre == PRE_ATT) {
+        p.units[0][0] = PUnit{t.lin(M_ATTN_OUT, t.o.x2, LDX, t.pieces(rg, c.D / 64, c.D)), kNone, EPI_AOUT, 0};
+        p.units[0][1] = PUnit{t.lin(M_SAMP, t.o.x3, LDX, t.pieces(rg, (so_cols(c) + 63) / 64, c.D)), kNone, EPI_SAMP, 0};
+        p.n_units = 2;
+    } else {
+        p.n_units = t.tail_units(p.units[0], pair ? MEMBER0 : WHOLE, with_front);
+        if (pair) (void)t.tail_units(p.units[1], MEMBER1, with_front);
+    }
+    return p;
+}
+
+// ---- fixed plans: unit tables as compile-time constants of a kernel instantiation ---------------------------------------------------------
+// row_chain_supported fixes D, ffn and code_size, and num_classes <= 64 is one column group, so a launch's tables depend on nothing but
+// this key.  The keys listed here get a kernel (row_chain_fixed_kernel) whose table is plan_units of the key, evaluated by the compiler:
+// epilogue, item counts, LDS offsets and weight offsets are immediates, and the kernel arguments carry the image's base instead of 1.4 KB
+// of tables.  A launch takes it when its own plan_units -- the same function, at run time -- gives the same words (fixed_match).
+struct FixKey {
+    int pre, rg, pair, with_front;
+    int qcg, scg;                // 64-column groups of the attention in-projection and of the sampling Linear
+};
+constexpr int N_FIX = 4;         // config 2's launches: the tail on pairs with and without the next front, the attention chain, the front
+constexpr FixKey fix_key(int i) {
+    switch (i) {
+    case 0: return FixKey{PRE_SLABS, 2, 1, 1, 13, 2};
+    case 1: return FixKey{PRE_SLABS, 2, 1, 0, 13, 2};
+    case 2: return FixKey{PRE_ATT, 1, 0, 0, 13, 2};
+    default: return FixKey{PRE_FRONT, 1, 0, 0, 13, 2};
+    }
+}
+constexpr bool same_key(const FixKey& a, const FixKey& b) {
+    return a.pre == b.pre && a.rg == b.rg && a.pair == b.pair && a.with_front == b.with_front && a.qcg == b.qcg && a.scg == b.scg;
+}
+// a config with the key's column-group counts (any would do: the tables see a config through its column groups only)
+constexpr Cfg key_cfg(const FixKey& k) {
+    Cfg c{};
+    c.D = DM; c.ffn = FF; c.code_size = 10; c.num_classes = 1;
+    c.attn_in_rows = 64 * k.qcg;
+    c.G = 1; c.P = 16 * k.scg; c.L = 1;       // G P (3 + L) = 64 scg sampling columns
+    return c;
+}
+constexpr PlanUnits fixed_units(int i) {
+    const FixKey k = fix_key(i);
+    return plan_units(key_cfg(k), k.pre, k.rg, k.pair != 0, k.with_front != 0, kNoTweaks);
+}
+
+__host__ __device__ __forceinline__ Lin bound(const PLin& l, const float* pk) {
+    return Lin{l.w < 0 ? nullptr : pk + l.w, l.in_off, l.ld, l.KH, l.items, l.chunks, l.kh0, l.KHT};
+}
+
+// The stream (see RtTab) over member MEM's table of fixed plan FIX.  A wave multiplies its items in a fixed order -- unit by unit, item
+// wave, then wave + 8 -- and the stream runs a constant distance ahead of the multiply (RG = 1: 3 chunks through the LDS ring; RG > 1: the
+// RDEPTH chunks in registers), less than the shortest item.  So what is issued belongs to the item being multiplied or to the wave's
+// NEXT item, and begin_item -- called where the multiply enters item `it` of unit U, U a constant -- finds both with compares of
+// `wave` and `it` against immediates; no table, no position to keep.
+template <int FIX, int MEM>
+struct FxTab {
+    const float* image;
+    static constexpr int N = fixed_units(FIX).n_units;
+    template <int U> static constexpr PUnit pu() { return fixed_units(FIX).units[MEM][U]; }
+    template <int U> static constexpr int items() { return pu<U>().a.items + pu<U>().b.items; }
+    template <int U> __device__ __forceinline__ Unit unit() const {
+        constexpr PUnit p = pu<U>();
+        return Unit{bound(p.a, image), bound(p.b, image), p.epi, p.col0};
+    }
+    // weights of item `it` of unit U
+    template <int U> __device__ __forceinline__ const float* weights(int it) const {
+        constexpr PUnit p = pu<U>();
+        if constexpr (p.b.items == 0) return lin_item_weights(bound(p.a, image), it);
+        else if constexpr (p.a.items == 0) return lin_item_weights(bound(p.b, image), it);
+        else return it >= p.a.items ? lin_item_weights(bound(p.b, image), it - p.a.items) : lin_item_weights(bound(p.a, image), it);
+    }
+    // the wave's first item in units U .. N - 1: its weights -> g; false: none
+    template <int U> __device__ __forceinline__ bool first_from(int wave, const float*& g) const {
+        if constexpr (U >= N) {
+            return false;
+        } else {
+            if (wave < items<U>()) {
+                g = weights<U>(wave);
+                return true;
+            }
+            return first_from<U + 1>(wave, g);
+        }
+    }
+    // the wave's item after item `it` of unit U
+    template <int U> __device__ __forceinline__ bool next(int it, int wave, const float*& g) const {
+        if constexpr (items<U>() > NWAVE) {
+            if (it + NWAVE < items<U>()) {
+                g = weights<U>(it + NWAVE);
+                return true;
+            }
+        }
+        return first_from<U + 1>(wave, g);
+    }
+
+    // kernel start: the wave's first item (none: the image's first chunks stand in for stream_load's unconditional loads)
+    __device__ __forceinline__ void seek(Stream& st, int wave) const {
+        st.iw.step = 0;
+        st.g = image;
+        st.live = first_from<0>(wave, st.g);
+        st.g_next = st.g;
+        st.has_next = false;
+    }
+    template <int U> __device__ __forceinline__ void begin_item(std::integral_constant<int, U>, Stream& st, int it, int wave) const {
+        st.g_cur = weights<U>(it);
+        st.g_next = st.g_cur;         // (no next item: RG > 1 re-reads this item's first chunks, as the run-time stream does)
+        st.has_next = next<U>(it, wave, st.g_next);
+    }
+    // RG = 1.  Every item has 8 chunks; the last of them is issued while the multiply is in the same item, so g_next is its successor's
+    __device__ __forceinline__ void issue(Stream& st, int) const {
+        if (!st.live) return;
+        issue_chunk(st.g + st.iw.step * CHUNK_FLOATS, st.ring_byte + (unsigned)st.islot * (CHUNK_FLOATS * 4), st.voff);
+        ++st.issued;
+        st.islot = st.islot == RING_SLOTS - 1 ? 0 : st.islot + 1;
+        if (++st.iw.step == 8) {
+            st.iw.step = 0;
+            st.g = st.g_next;
+            st.live = st.has_next;
+        }
+    }
+    // RG > 1.  The round that multiplies chunks s0 .. s0 + 3 of the item refills the registers with the chunks RDEPTH further on: the
+    // item's own, or -- in its last round -- the first RDEPTH of the next item
+    __device__ __forceinline__ void begin_round(Stream& st, int chunks, int s0) const {
+        st.g = s0 + RDEPTH < chunks ? st.g_cur + (s0 + RDEPTH) * CHUNK_FLOATS : st.g_next;
+        st.iw.step = 0;
+    }
+    __device__ __forceinline__ void load(Stream& st, int, int lane, RChunk& c) const {
+        const float* g = st.g + st.iw.step * CHUNK_FLOATS + lane * 4;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) c.q[m] = *reinterpret_cast<const float4*>(g + 256 * m);
+        ++st.iw.step;
+    }
+};
+
+template <class F, int... I>
+__device__ __forceinline__ void for_each_unit(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+
 // PRE: how the input rows are produced (compile-time: the three chains are three instantiations)
-template <int PRE, int RG, bool PAIR = false>
-__global__ __launch_bounds__(64 * NWAVE) void row_chain_kernel(const ChainArgs a) {
+// FIX: -1 = the unit table is read from the kernel arguments (A = ChainArgs), else the fixed plan whose member MEM's table is compiled in
+// (A = ChainArgsFx; `member` is then the constant MEM).  One body: the run-time and the fixed kernels differ in where a unit comes from.
+template <int PRE, int RG, bool PAIR, int FIX, int MEM, class A>
+__device__ __forceinline__ void chain_body(const A& a, const int pair, const int member) {
     using L = Lay<RG>;
     static_assert(!PAIR || (PRE == PRE_SLABS && RG > 1), "pair mode: the tail, wide row blocks");
     constexpr int R = L::R, RPW = L::RPW, OFF_X2 = L::OFF_X2, OFF_X3 = L::OFF_X3, OFF_H = L::OFF_H, OFF_C = L::OFF_C, OFF_R = L::OFF_R,
@@ -495,16 +818,11 @@ __global__ __launch_bounds__(64 * NWAVE) void row_chain_kernel(const ChainArgs a
     extern __shared__ __attribute__((aligned(16))) float smem[];      // L::LDS_TOTAL_FLOATS (dynamic: > 64 KB)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // pair mode: block b -> XCD b % 8 under round-robin dispatch, so the members of pair p are blocks b and b + 8
-    int pair = (int)blockIdx.x, member = 0;
-    if constexpr (PAIR) {
-        const int li = (int)blockIdx.x >> 3;
-        pair = (li >> 1) * 8 + ((int)blockIdx.x & 7);
-        member = li & 1;
-        if (pair >= a.n_pairs) return;
-        if (a.debug_drop && pair == 0 && member == 1) return;
-    }
-    const Unit* const U = (PAIR && member) ? a.units_b : a.units;
+    const auto tab = [&] {
+        if constexpr (FIX >= 0) return FxTab<FIX, MEM>{a.image};
+        else return RtTab{a, (PAIR && member) ? a.units_b : a.units};
+    }();
+    constexpr int front_fx = fix_key(FIX < 0 ? 0 : FIX).with_front;
     unsigned* const pword = PAIR ? a.pair_sync + pair : nullptr;
     float* const px = PAIR ? a.pair_x + (long long)pair * (3 * R * DM) : nullptr;       // [3][R][256]
     const long long row0 = (long long)pair * R;
@@ -528,26 +846,25 @@ __global__ __launch_bounds__(64 * NWAVE) void row_chain_kernel(const ChainArgs a
     SBEV_TRACE(0)
     warm_l2<RG>(a, wave, lane);
     Stream st;
-    st.U = U;
     st.iw = Walk{0, wave, 0};
     st.issued = st.used = st.islot = st.uslot = 0;
     st.ring_byte = (unsigned)(L::OFF_RING + wave * (RING_SLOTS * CHUNK_FLOATS)) * 4u;
     st.voff = (unsigned)lane * 16u;
     st.g = a.warm;           // (valid for stream_load's unconditional loads even if this wave has no item)
     st.nchunk = 8;
-    stream_seek(a, st, wave);
+    tab.seek(st, wave);
     RChunk rb[RDEPTH];
     if constexpr (L::WIDE) {
 #pragma unroll
         for (int d = 0; d < RDEPTH; ++d) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) rb[d].q[m] = make_float4(0.f, 0.f, 0.f, 0.f);
-            stream_load(a, st, wave, lane, rb[d]);
+            tab.load(st, wave, lane, rb[d]);
         }
     } else {
-        stream_issue(a, st, wave);
-        stream_issue(a, st, wave);
-        stream_issue(a, st, wave);
+        tab.issue(st, wave);
+        tab.issue(st, wave);
+        tab.issue(st, wave);
     }
 
     // ---- prologue: every global load of it is issued before the first wait (one memory latency, not one per phase) -----
@@ -646,13 +963,19 @@ __global__ __launch_bounds__(64 * NWAVE) void row_chain_kernel(const ChainArgs a
     __syncthreads();
 
     SBEV_TRACE(1)
-    for (int u = 0; u < a.n_units; ++u) {
-        const Unit& un = U[u];
+    // one unit: its items, then its epilogue.  `only`: 1 / 2 = the unit is known at compile time to have items of Lin a / b alone
+    // (every unit of today's fixed plans), 0 = choose per item
+    const auto run_unit = [&](const Unit& un, const auto uc, const auto only) __attribute__((always_inline)) {
+        constexpr int ONLY = decltype(only)::value;
+        [[maybe_unused]] const int u = uc;      // (the trace stamps number by it)
         const int items = un.a.items + un.b.items;
+#pragma nounroll
         for (int it = wave; it < items; it += NWAVE) {
-            const bool second = it >= un.a.items;
-            if constexpr (L::WIDE) mma_item_wide<RG>(a, st, rb, second ? un.b : un.a, it - (second ? un.a.items : 0), smem, it, lane, wave);
-            else mma_item(a, st, second ? un.b : un.a, it - (second ? un.a.items : 0), smem, it, lane, wave);
+            const bool second = ONLY == 0 ? it >= un.a.items : ONLY == 2;
+            const Lin& l = ONLY == 1 ? un.a : ONLY == 2 ? un.b : second ? un.b : un.a;
+            tab.begin_item(uc, st, it, wave);
+            if constexpr (L::WIDE) mma_item_wide<RG>(tab, st, rb, l, it - (second ? un.a.items : 0), smem, it, lane, wave);
+            else mma_item(tab, st, l, it - (second ? un.a.items : 0), smem, it, lane, wave);
         }
         SBEV_TRACE(2 + 4 * u)
         __syncthreads();
@@ -748,7 +1071,7 @@ __global__ __launch_bounds__(64 * NWAVE) void row_chain_kernel(const ChainArgs a
                         }
                         if (live) a.box_out[g * 10 + lane] = o;
                     }
-                    if (a.front) {
+                    if (FIX >= 0 ? front_fx : a.front) {
                         const int ob = (int)__float_as_uint(o);
                         const float x0 = __uint_as_float((unsigned)__builtin_amdgcn_readlane(ob, 0));
                         const float x1 = __uint_as_float((unsigned)__builtin_amdgcn_readlane(ob, 1));
@@ -851,6 +1174,16 @@ __global__ __launch_bounds__(64 * NWAVE) void row_chain_kernel(const ChainArgs a
         if (PAIR && un.epi == EPI_PE3 && member == 1) pair_arrive(pword);
         __syncthreads();
         SBEV_TRACE(5 + 4 * u)
+    };
+    if constexpr (FIX >= 0) {
+        for_each_unit([&](const auto uc) __attribute__((always_inline)) {
+            constexpr int UI = decltype(uc)::value;
+            constexpr PUnit p = FxTab<FIX, MEM>::template pu<UI>();
+            const Unit un = tab.template unit<UI>();
+            run_unit(un, uc, std::integral_constant<int, p.b.items == 0 ? 1 : p.a.items == 0 ? 2 : 0>{});
+        }, std::make_integer_sequence<int, FxTab<FIX, MEM>::N>{});
+    } else {
+        for (int u = 0; u < a.n_units; ++u) run_unit(tab.U[u], u, std::integral_constant<int, 0>{});
     }
     if (PRE == PRE_ATT && a.proj.loc_bp) {
         // adaptive spatio-temporal sampling, projection and camera selection of the rows' sample points (sample_point.hpp: the
@@ -868,6 +1201,42 @@ __global__ __launch_bounds__(64 * NWAVE) void row_chain_kernel(const ChainArgs a
             const float* so = smem + OFF_H + row * 256;
             sbev_ops::sample_point(a.proj, b, t, q, gp, a.proj.bbox + g * 10, so + gp * 3, so + GP * 3 + gp * a.proj.L);
         }
+    }
+}
+
+// pair mode: block b -> XCD b % 8 under round-robin dispatch, so the members of pair p are blocks b and b + 8.  False: this
+// workgroup has no pair (or is the member the test hook drops)
+template <bool PAIR>
+__device__ __forceinline__ bool pair_of_block(const ChainCommon& a, int& pair, int& member) {
+    pair = (int)blockIdx.x;
+    member = 0;
+    if constexpr (PAIR) {
+        const int li = (int)blockIdx.x >> 3;
+        pair = (li >> 1) * 8 + ((int)blockIdx.x & 7);
+        member = li & 1;
+        if (pair >= a.n_pairs) return false;
+        if (a.debug_drop && pair == 0 && member == 1) return false;
+    }
+    return true;
+}
+
+template <int PRE, int RG, bool PAIR = false>
+__global__ __launch_bounds__(64 * NWAVE) void row_chain_kernel(const ChainArgs a) {
+    int pair, member;
+    if (!pair_of_block<PAIR>(a, pair, member)) return;
+    chain_body<PRE, RG, PAIR, -1, -1>(a, pair, member);
+}
+
+// the same chain with fixed plan FIX compiled in; a pair's two members run two instantiations of the body, one per table
+template <int PRE, int RG, bool PAIR, int FIX>
+__global__ __launch_bounds__(64 * NWAVE) void row_chain_fixed_kernel(const ChainArgsFx a) {
+    int pair, member;
+    if (!pair_of_block<PAIR>(a, pair, member)) return;
+    if constexpr (PAIR) {
+        if (member == 0) chain_body<PRE, RG, PAIR, FIX, 0>(a, pair, 0);
+        else chain_body<PRE, RG, PAIR, FIX, 1>(a, pair, 1);
+    } else {
+        chain_body<PRE, RG, PAIR, FIX, 0>(a, pair, 0);
     }
 }
 
@@ -896,63 +1265,33 @@ __global__ void copy_pad_kernel(const float* src, int n, float* dst, int slot) {
 }
 
 // ======================================================= host side =======================================================================
-using Cfg = sbev_decoder_config;
-
-// ---- the packed weight image, described once ------------------------------------------------------------------------------------------
-// The 12 matrices in image order: the member of sbev_decoder_weights, its rows N and its columns K.  pack_map, the pack jobs,
-// sbev_decoder_chain_pack_floats and the launches' warm spans ("matrices i .. j") all walk this one table.  Behind the matrices lie the
-// small vectors [tail | front | attention] at their PV_* offsets (the vecs[] table of sbev_decoder_chain_pack).
-enum Mat { M_FFN0, M_FFN1, M_CLS0, M_REG0, M_CLS3, M_REG2, M_CLS6, M_REG4, M_PE3, M_ATTN_IN, M_ATTN_OUT, M_SAMP, N_MAT };
-int so_cols(const Cfg& c) { return c.G * c.P * (3 + c.L); }      // the sampling Linear's rows: 3 offsets + L level logits per point
-int n_embed(const Cfg& c) { return c.D; }
-int n_ffn(const Cfg& c) { return c.ffn; }
-int n_cls(const Cfg& c) { return c.num_classes; }
-int n_code(const Cfg& c) { return c.code_size; }
-int n_qkv(const Cfg& c) { return c.attn_in_rows; }
-struct MatDesc {
-    const float* sbev_decoder_weights::*w;
-    int (*N)(const Cfg&);
-    int (*K)(const Cfg&);
-};
-const MatDesc kMats[N_MAT] = {
-    {&sbev_decoder_weights::ffn0_w, n_ffn, n_embed},      {&sbev_decoder_weights::ffn1_w, n_embed, n_ffn},
-    {&sbev_decoder_weights::cls0_w, n_embed, n_embed},    {&sbev_decoder_weights::reg0_w, n_embed, n_embed},
-    {&sbev_decoder_weights::cls3_w, n_embed, n_embed},    {&sbev_decoder_weights::reg2_w, n_embed, n_embed},
-    {&sbev_decoder_weights::cls6_w, n_cls, n_embed},      {&sbev_decoder_weights::reg4_w, n_code, n_embed},
-    {&sbev_decoder_weights::pe3_w, n_embed, n_embed},     {&sbev_decoder_weights::attn_in_w, n_qkv, n_embed},
-    {&sbev_decoder_weights::attn_out_w, n_embed, n_embed}, {&sbev_decoder_weights::samp_w, so_cols, n_embed}};
-
-long long packed_floats(int N, int K) { return (long long)((N + 63) / 64) * 64 * K; }
-
-struct PackMap {     // float offsets into the chain_pack image: matrix i lies at [at[i], at[i + 1])
-    long long at[N_MAT + 1];
-    long long vec() const { return at[N_MAT]; }                      // the small vectors: [tail | front | attention], PV_* offsets
-    long long total() const { return at[N_MAT] + PV_IMAGE_FLOATS; }
-    int lines(int first, int last) const { return (int)((at[last + 1] - at[first]) / 32); }      // 128-byte lines of matrices first .. last
-};
-PackMap pack_map(const Cfg& c) {
-    PackMap m{};
-    for (int i = 0; i < N_MAT; ++i) m.at[i + 1] = m.at[i] + packed_floats(kMats[i].N(c), kMats[i].K(c));
-    return m;
-}
-
 // ---- the instantiations, listed once ------------------------------------------------------------------------------------------------------
 // launch, the LDS-attribute raise and chain_lds_ready walk this table.  The kernels use 159 KB of dynamic LDS: the attribute is raised once
 // per device and instantiation (also from sbev_decoder_chain_pack, so that the first launch may already be inside a stream capture).
 struct Inst {
     int pre, rg;
     bool pair;
+    int fix;                                         // -1: the run-time-table kernel (kern); else the fixed plan compiled into kern_fx
     void (*kern)(ChainArgs);
+    void (*kern_fx)(ChainArgsFx);
     int rows, lds;                                   // rows per row block (one workgroup, or one pair of them); dynamic LDS bytes
     std::atomic<unsigned long long> raised;          // bit d: the attribute is raised on device d (a process may drive several devices)
 };
 template <int PRE, int RG, bool PAIR = false>
-Inst inst() { return Inst{PRE, RG, PAIR, row_chain_kernel<PRE, RG, PAIR>, Lay<RG>::R, Lay<RG>::LDS_TOTAL_FLOATS * 4, {0}}; }
+Inst inst() { return Inst{PRE, RG, PAIR, -1, row_chain_kernel<PRE, RG, PAIR>, nullptr, Lay<RG>::R, Lay<RG>::LDS_TOTAL_FLOATS * 4, {0}}; }
+template <int FIX>
+Inst inst_fixed() {
+    constexpr FixKey k = fix_key(FIX);
+    return Inst{k.pre, k.rg, k.pair != 0, FIX, nullptr, row_chain_fixed_kernel<k.pre, k.rg, k.pair != 0, FIX>, Lay<k.rg>::R,
+                Lay<k.rg>::LDS_TOTAL_FLOATS * 4, {0}};
+}
 Inst kInst[] = {inst<PRE_SLABS, 1>(), inst<PRE_FRONT, 1>(), inst<PRE_ATT, 1>(), inst<PRE_SLABS, 2>(), inst<PRE_FRONT, 2>(), inst<PRE_ATT, 2>(),
-                inst<PRE_SLABS, 4>(), inst<PRE_FRONT, 4>(), inst<PRE_ATT, 4>(), inst<PRE_SLABS, 2, true>(), inst<PRE_SLABS, 4, true>()};
-Inst* find_inst(int pre, int rg, bool pair) {
+                inst<PRE_SLABS, 4>(), inst<PRE_FRONT, 4>(), inst<PRE_ATT, 4>(), inst<PRE_SLABS, 2, true>(), inst<PRE_SLABS, 4, true>(),
+                inst_fixed<0>(), inst_fixed<1>(), inst_fixed<2>(), inst_fixed<3>()};
+static_assert(N_FIX == 4, "one inst_fixed row per fixed plan");
+Inst* find_inst(int pre, int rg, bool pair, int fix = -1) {
     for (Inst& i : kInst)
-        if (i.pre == pre && i.rg == rg && i.pair == pair) return &i;
+        if (i.pre == pre && i.rg == rg && i.pair == pair && i.fix == fix) return &i;
     return nullptr;
 }
 hipError_t raise_lds(Inst& i) {
@@ -960,23 +1299,16 @@ hipError_t raise_lds(Inst& i) {
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
     const unsigned long long bit = 1ull << (dev & 63);
     if (i.raised.load(std::memory_order_acquire) & bit) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(i.kern), hipFuncAttributeMaxDynamicSharedMemorySize, i.lds);
+    const hipError_t e = hipFuncSetAttribute(i.fix < 0 ? reinterpret_cast<const void*>(i.kern) : reinterpret_cast<const void*>(i.kern_fx), hipFuncAttributeMaxDynamicSharedMemorySize, i.lds);
     if (e == hipSuccess) i.raised.fetch_or(bit, std::memory_order_release);
     return e;
 }
 
 // ---- a launch, planned once (pure host: no HIP call below this line until "binding and launching") ----------------------------------
-// Lin / Unit with the weights as a float offset into the image (-1: none) instead of a pointer
-struct PLin { long long w; int in_off, ld, KH, items, chunks, kh0, KHT; };
-struct PUnit { PLin a, b; int epi, col0; };
-const PLin kNone{-1, 0, LDX, 1, 0, 8, 0, 1};
-
-struct ChainPlan {
+struct ChainPlan : PlanUnits {   // (the unit tables: n_units, units[member][u])
     int pre, rg, pair;           // the instantiation: the chain (Pre), row groups per row block, pair mode
     unsigned grid;
     int lds;                     // dynamic LDS bytes
-    int n_units;
-    PUnit units[2][8];           // [member]; units[1] in pair mode only (same count, same epilogues)
     int n_pairs;
     long long warm;              // the launch's packed weights: float offset of the span, ...
     int warm_lines;              // ... its 128-byte lines
@@ -984,31 +1316,12 @@ struct ChainPlan {
     int vec_off, vec_n;
 };
 
-// k-pieces per column group of a unit in which THIS SHARE of the row block (see Share) computes `cgs` column groups in all: RG = 1 keeps
-// 128-k items; RG > 1 aims at 8 items per unit (one per wave; each piece at least 64 k = RDEPTH chunks)
-// -- <= 12 slots; cost of a choice = sum over its rounds of (chunks per item) x (1 for a round of 5 .. 8 items: two waves per SIMD
-// share the MFMA pipe; 1/2 for a last round of <= 4 items: waves 0 .. 3 sit on four different SIMDs)
-int pieces(int rg, int cgs, int K) {
-    if (rg == 1) return 0;
-    static const bool tie_large = getenv("SBEV_CHAIN_TIE_SMALL") == nullptr;      // equal cost: more, shorter items (A/B switch)
-    int best = 1;
-    double best_cost = 1e30;
-    for (int kh = 1; kh <= 4 && cgs * kh <= 12 && K / kh >= 16 * RDEPTH; kh *= 2) {
-        const int items = cgs * kh, full = items / NWAVE, rest = items % NWAVE;
-        const double cost = (K / (16.0 * kh)) * (full + (rest == 0 ? 0.0 : rest <= 4 ? 0.5 : 1.0));
-        if (tie_large ? cost < best_cost + 1e-9 : cost < best_cost - 1e-9) { best_cost = cost; best = kh; }
-    }
-    return best;
-}
-
 // rows per workgroup = 4 rg: the smallest of 4, 8, 16 that covers the rows with one round of workgroups (256 CUs)
 int row_groups(long long rows) {
     static const int forced = getenv("SBEV_CHAIN_RG") ? atoi(getenv("SBEV_CHAIN_RG")) : 0;      // A/B: 1, 2 or 4 row groups whatever the row count
     if ((forced == 1 && rows <= 256 * 4) || (forced == 2 && rows <= 256 * 8) || forced == 4) return forced;
     return rows <= 256 * 4 ? 1 : rows <= 256 * 8 ? 2 : 4;
 }
-Offs offs(int rg) { return rg == 1 ? offs_of<1>() : rg == 2 ? offs_of<2>() : offs_of<4>(); }
-
 // Pair mode of the tail (see "pair mode" above): row groups per PAIR of workgroups, 0 = not applicable.  Both members of every
 // pair must be resident at once -- one workgroup per CU (88 KB of LDS and more) -- so the launch, 16 blocks per 8 pairs, has to
 // fit the device's CUs in one round: 8 rows per pair, <= 1024 rows on 256 CUs.  (16 rows per pair would reach 2048 rows, but
@@ -1027,76 +1340,6 @@ int pair_row_groups(long long rows, bool pair_ok, int cus) {
     return 0;
 }
 
-// Who computes a unit table: the one workgroup of a row block, or one member of the pair that shares it.
-enum Share { WHOLE = -1, MEMBER0 = 0, MEMBER1 = 1 };
-
-struct UnitTables {
-    const Cfg& c;
-    const PackMap& m;
-    int rg;
-    Offs o;
-
-    // column groups [cg0, cg0 + ncg) of packed matrix `mat` as items of K / KH k each.  kh = 0: K / 128 (the RG = 1 items)
-    PLin lin(int mat, int in_off, int ld, int kh = 0, int cg0 = 0, int ncg = -1) const {
-        const int N = kMats[mat].N(c), K = kMats[mat].K(c);
-        const int KH = kh > 0 ? kh : K / 128;
-        if (ncg < 0) ncg = (N + 63) / 64 - cg0;
-        return PLin{m.at[mat] + (long long)cg0 * K * 64, in_off, ld, KH, ncg * KH, K / (16 * KH), 0, KH};
-    }
-    // k-half `half` of packed matrix `mat` (pair mode): kh pieces of the half, i.e. pieces [half kh, half kh + kh) of 2 kh per row
-    PLin lin_khalf(int mat, int in_off, int ld, int kh, int half) const {
-        const int N = kMats[mat].N(c), K = kMats[mat].K(c);
-        return PLin{m.at[mat], in_off, ld, kh, ((N + 63) / 64) * kh, K / (32 * kh), half * kh, 2 * kh};
-    }
-
-    // position encoder + attention in-projection (the front chain; the end of a tail with_front).  The position encoder runs where the
-    // regression branch ran (WHOLE, MEMBER1).  In-projection column groups: WHOLE all of them, in units of at most 8; MEMBER1 those from
-    // q0 onward -- it has the x rows in its LDS, member 0 gets them a hand-off (~1.5 us) later, so member 1 takes up to 8 column groups
-    // (one round of 16-chunk items) and member 0 the rest (5 of config 2's 13: 10 items of 8 chunks) -- and MEMBER0 those below q0; a
-    // member has exactly ONE in-projection unit, kNone where its share is empty.
-    int front_units(PUnit* u, int n, Share sh) const {
-        const int dcg = c.D / 64, qcg = (c.attn_in_rows + 63) / 64;
-        u[n++] = PUnit{sh != MEMBER0 ? lin(M_PE3, o.c, LDX, pieces(rg, dcg, c.D)) : kNone, kNone, EPI_PE3, 0};
-        static const int q0_forced = getenv("SBEV_CHAIN_PAIR_Q0") ? atoi(getenv("SBEV_CHAIN_PAIR_Q0")) : -1;      // A/B
-        const int q0 = q0_forced >= 0 && q0_forced <= qcg ? q0_forced : (qcg > 8 ? qcg - 8 : qcg / 2);
-        const int lo = sh == MEMBER1 ? q0 : 0, hi = sh == MEMBER0 ? q0 : qcg;
-        const int cut = sh == WHOLE ? 8 : qcg + 1;
-        if (sh != WHOLE && lo == hi) u[n++] = PUnit{kNone, kNone, EPI_QKV, lo * 64};
-        for (int cg0 = lo; cg0 < hi; cg0 += cut) {
-            const int n_here = hi - cg0 < cut ? hi - cg0 : cut;
-            u[n++] = PUnit{lin(M_ATTN_IN, o.x2, LDX, pieces(rg, n_here, c.D), cg0, n_here), kNone, EPI_QKV, cg0 * 64};
-        }
-        return n;
-    }
-
-    // The tail's unit table, written once as a function of the share (see "pair mode" above the kernel):
-    //   ffn.layers.0   WHOLE: all column groups; member s: half of them, from s x half on
-    //   ffn.layers.1   WHOLE: all of k (lin); member s: k-half s (lin_khalf) for all columns
-    //   branches       the classification side sits in Unit::a, the regression side in Unit::b; WHOLE carries both, MEMBER0 the
-    //                  classification side, MEMBER1 the regression side (the other Lin is kNone)
-    //   front          front_units
-    // Every pieces() call gets the column groups THIS SHARE computes in that unit: both branch sides count for WHOLE (2 dcg; 2 for the
-    // output unit), one side for a member (dcg; 1).  Both members get the same number of units and the same epilogue sequence.
-    int tail_units(PUnit* u, Share sh, bool with_front) const {
-        const int dcg = c.D / 64, fcg = c.ffn / 64;
-        const bool cls = sh != MEMBER1, reg = sh != MEMBER0;
-        const int sides = (cls ? 1 : 0) + (reg ? 1 : 0);
-        const int f_ncg = sh == WHOLE ? fcg : fcg / 2, f_cg0 = sh == WHOLE ? 0 : sh * f_ncg;
-        int n = 0;
-        u[n++] = PUnit{lin(M_FFN0, o.x2, LDX, pieces(rg, f_ncg, c.D), f_cg0, f_ncg), kNone, EPI_FFN0, 0};
-        u[n++] = PUnit{sh == WHOLE ? lin(M_FFN1, o.h, LDH, pieces(rg, dcg, c.ffn)) : lin_khalf(M_FFN1, o.h, LDH, pieces(rg, dcg, c.ffn / 2), sh),
-                       kNone, EPI_FFN1, 0};
-        const auto branch = [&](int mat_c, int in_c, int mat_r, int in_r, int cgs_side, int epi) {
-            const int kh = pieces(rg, sides * cgs_side, c.D);
-            return PUnit{cls ? lin(mat_c, in_c, LDX, kh) : kNone, reg ? lin(mat_r, in_r, LDX, kh) : kNone, epi, 0};
-        };
-        u[n++] = branch(M_CLS0, o.x3, M_REG0, o.x3, dcg, EPI_BR1);
-        u[n++] = branch(M_CLS3, o.c, M_REG2, o.r, dcg, EPI_BR2);
-        u[n++] = branch(M_CLS6, o.c, M_REG4, o.r, 1, EPI_OUT);
-        return with_front ? front_units(u, n, sh) : n;
-    }
-};
-
 // Everything a row-chain launch needs but its pointers, from plain values (sbev_decoder_chain_plan reports it; tests/test_chain_plan_host.py).
 // pre: the chain; with_front: the tail goes on with the next layer's front; pair_ok: see pair_row_groups; cus: the device's CU count
 ChainPlan chain_plan(const Cfg& c, int pre, bool with_front, bool pair_ok, int cus) {
@@ -1112,21 +1355,16 @@ ChainPlan chain_plan(const Cfg& c, int pre, bool with_front, bool pair_ok, int c
     p.grid = p.pair ? (unsigned)pair_blocks(rows, p.rg) : (unsigned)blocks;
     p.lds = in.lds;
     p.n_pairs = p.pair ? (int)blocks : 0;
-    const UnitTables t{c, m, p.rg, offs(p.rg)};
+    static const Tweaks tw{getenv("SBEV_CHAIN_TIE_SMALL") == nullptr, getenv("SBEV_CHAIN_PAIR_Q0") ? atoi(getenv("SBEV_CHAIN_PAIR_Q0")) : -1};      // A/B
+    static_cast<PlanUnits&>(p) = plan_units(c, pre, p.rg, p.pair != 0, with_front, tw);
     int first = 0, last = 0;         // the launch streams matrices first .. last: one contiguous span of the image
     if (pre == PRE_FRONT) {
-        p.n_units = t.front_units(p.units[0], 0, WHOLE);
         first = M_PE3; last = M_ATTN_IN;
         p.vec = m.vec() + PV_TAIL_END; p.vec_off = PV_TAIL_END; p.vec_n = PV_FRONT_END - PV_TAIL_END;
     } else if (pre == PRE_ATT) {
-        p.units[0][0] = PUnit{t.lin(M_ATTN_OUT, t.o.x2, LDX, pieces(p.rg, c.D / 64, c.D)), kNone, EPI_AOUT, 0};
-        p.units[0][1] = PUnit{t.lin(M_SAMP, t.o.x3, LDX, pieces(p.rg, (so_cols(c) + 63) / 64, c.D)), kNone, EPI_SAMP, 0};
-        p.n_units = 2;
         first = M_ATTN_OUT; last = M_SAMP;
         p.vec = m.vec() + PV_FRONT_END; p.vec_off = 0; p.vec_n = PV_ATTN_END;
     } else {
-        p.n_units = t.tail_units(p.units[0], p.pair ? MEMBER0 : WHOLE, with_front);
-        if (p.pair) (void)t.tail_units(p.units[1], MEMBER1, with_front);
         first = M_FFN0; last = with_front ? M_ATTN_IN : M_REG4;
         p.vec = m.vec(); p.vec_off = 0; p.vec_n = with_front ? PV_FRONT_END : PV_TAIL_END;
     }
@@ -1137,6 +1375,45 @@ ChainPlan chain_plan(const Cfg& c, int pre, bool with_front, bool pair_ok, int c
 
 std::atomic<int> g_chain_pair{getenv("SBEV_NO_CHAIN_PAIR") ? 0 : 1};
 std::atomic<int> g_chain_pair_drop{0};
+
+// ---- choosing a fixed plan ---------------------------------------------------------------------------------------------------------------------
+constexpr PlanUnits kFixedUnits[N_FIX] = {fixed_units(0), fixed_units(1), fixed_units(2), fixed_units(3)};
+// the fixed kernels are taken (default) / only the run-time-table kernels are (sbev_decoder_chain_fixed, SBEV_CHAIN_FIXED=0)
+std::atomic<int> g_chain_fixed{getenv("SBEV_CHAIN_FIXED") ? (atoi(getenv("SBEV_CHAIN_FIXED")) != 0 ? 1 : 0) : 1};
+std::atomic<long long> g_chain_fixed_launches{0};      // launches (enqueued or captured) that took a fixed kernel, for tests
+
+// a unit as the 18 int32 words sbev_decoder_chain_plan reports (and fixed_match compares)
+void unit_words(const PUnit& pu, int32_t* out) {
+    *out++ = pu.epi;
+    *out++ = pu.col0;
+    for (const PLin* l : {&pu.a, &pu.b})
+        for (int v : {(int)l->w, l->in_off, l->ld, l->KH, l->items, l->chunks, l->kh0, l->KHT}) *out++ = v;
+}
+// the key of a planned launch
+FixKey key_of(const Cfg& c, const ChainPlan& p, bool with_front) {
+    return FixKey{p.pre, p.rg, p.pair, p.pre == PRE_SLABS && with_front ? 1 : 0, (c.attn_in_rows + 63) / 64, (so_cols(c) + 63) / 64};
+}
+// the fixed plan with this key, -1: none is compiled in
+int find_fixed(const FixKey& k) {
+    for (int i = 0; i < N_FIX; ++i)
+        if (same_key(fix_key(i), k)) return i;
+    return -1;
+}
+// ... and whose constant table equals the plan's run-time table word for word (it does, unless an A/B switch of the environment changed
+// the plan: the key does not know those), -1: the launch takes the run-time-table kernel
+int fixed_match(const ChainPlan& p, const FixKey& k) {
+    static const bool ab_env = getenv("SBEV_CHAIN_TIE_SMALL") || getenv("SBEV_CHAIN_PAIR_Q0") || getenv("SBEV_CHAIN_RG") || getenv("SBEV_CHAIN_PAIR16");
+    const int fix = ab_env ? -1 : find_fixed(k);
+    if (fix < 0 || kFixedUnits[fix].n_units != p.n_units) return -1;
+    for (int mem = 0; mem <= p.pair; ++mem)
+        for (int u = 0; u < p.n_units; ++u) {
+            int32_t a[18], b[18];
+            unit_words(p.units[mem][u], a);
+            unit_words(kFixedUnits[fix].units[mem][u], b);
+            if (memcmp(a, b, sizeof(a)) != 0) return -1;
+        }
+    return fix;
+}
 
 int device_cus() {
     static std::atomic<int> cus[64];
@@ -1204,10 +1481,9 @@ static ChainArgs chain_args(const Cfg& c, float eps) {
     return a;
 }
 
-static Lin bound(const PLin& l, const float* pk) { return Lin{l.w < 0 ? nullptr : pk + l.w, l.in_off, l.ld, l.KH, l.items, l.chunks, l.kh0, l.KHT}; }
-
-static int launch(const ChainPlan& p, ChainArgs& a, const float* pk, hipStream_t s, const char* what) {
-    Inst& in = *find_inst(p.pre, p.rg, p.pair);
+static int launch(const Cfg& c, const ChainPlan& p, ChainArgs& a, const float* pk, hipStream_t s, const char* what) {
+    const int fix = g_chain_fixed.load(std::memory_order_relaxed) ? fixed_match(p, key_of(c, p, a.front != 0)) : -1;
+    Inst& in = *find_inst(p.pre, p.rg, p.pair, fix);
     const hipError_t attr = raise_lds(in);
     if (attr != hipSuccess) {
         set_error("%s: hipFuncSetAttribute(%d bytes of LDS): %s", what, in.lds, hipGetErrorString(attr));
@@ -1233,7 +1509,15 @@ static int launch(const ChainPlan& p, ChainArgs& a, const float* pk, hipStream_t
     a.trace = tr + (calls % 64) * 512;
     if (calls < 13) who[calls] = &in;
 #endif
-    hipLaunchKernelGGL(in.kern, dim3(p.grid), dim3(64 * NWAVE), in.lds, s, a);
+    if (fix >= 0) {
+        ChainArgsFx f{};
+        static_cast<ChainCommon&>(f) = a;
+        f.image = pk;
+        g_chain_fixed_launches.fetch_add(1, std::memory_order_relaxed);
+        hipLaunchKernelGGL(in.kern_fx, dim3(p.grid), dim3(64 * NWAVE), in.lds, s, f);
+    } else {
+        hipLaunchKernelGGL(in.kern, dim3(p.grid), dim3(64 * NWAVE), in.lds, s, a);
+    }
 #ifdef SBEV_CHAIN_TRACE
     if (++calls == 13) {        // the first step's 13 launches
         (void)hipDeviceSynchronize();
@@ -1260,7 +1544,7 @@ int launch_chain_front(const sbev_decoder_config& c, const sbev_decoder_weights&
                        float* qkvt, float eps, hipStream_t s, uint32_t* skip_hdr) {
     ChainArgs a = chain_args(c, eps);
     a.bbox = bbox; a.feat = feat; a.x = x; a.qkvt = qkvt; a.skip_hdr = skip_hdr;
-    return launch(chain_plan(c, PRE_FRONT, false, false, 0), a, w.chain_pack, s, "row chain (front)");
+    return launch(c, chain_plan(c, PRE_FRONT, false, false, 0), a, w.chain_pack, s, "row chain (front)");
 }
 
 // attention out-projection + residual + norm1 -> x1, sampling Linear -> sample points -> projection (loc, level weights)
@@ -1275,7 +1559,7 @@ int launch_chain_attn(const sbev_decoder_config& c, const sbev_decoder_weights& 
     a.proj = sbev_ops::sample_point_args(bbox, time_diff, lidar2img, c.pc_range, c.B, c.Q, c.T, c.N, c.G, c.P, c.L, c.image_h, c.image_w,
                                          c.eps_homo, loc_bp, w_bp);
     if (touch && touch_need) sbev_ops::sample_point_touch(a.proj, *touch, c.hw, touch_need);      // on-demand relayout: mark what the points read
-    return launch(chain_plan(c, PRE_ATT, false, false, 0), a, w.chain_pack, s, "row chain (attention)");
+    return launch(c, chain_plan(c, PRE_ATT, false, false, 0), a, w.chain_pack, s, "row chain (attention)");
 }
 
 // out_proj slabs -> norm2 -> ffn -> norm3 -> branches -> refine_bbox [-> the next layer's position encoder + in-projection]
@@ -1293,7 +1577,7 @@ int launch_chain_tail(const sbev_decoder_config& c, const sbev_decoder_weights& 
         a.pair_sync = pair_sync;
         a.debug_drop = g_chain_pair_drop.load(std::memory_order_relaxed);
     }
-    return launch(p, a, w.chain_pack, s, p.pair ? "row chain (tail, pairs)" : "row chain (tail)");
+    return launch(c, p, a, w.chain_pack, s, p.pair ? "row chain (tail, pairs)" : "row chain (tail)");
 }
 
 }  // namespace sbev
@@ -1310,25 +1594,42 @@ extern "C" int64_t sbev_decoder_chain_pack_floats(const sbev_decoder_config* cfg
     return pack_map(*cfg).total();
 }
 
+// the fixed-plan kernels: on / off; returns the previous setting (A/B measurements, tests).  Results are bit-identical either way
+extern "C" int sbev_decoder_chain_fixed(int enable) { return g_chain_fixed.exchange(enable != 0 ? 1 : 0); }
+extern "C" int64_t sbev_decoder_chain_fixed_launches(void) { return g_chain_fixed_launches.load(std::memory_order_relaxed); }
+
+// a plan's int32 words (layout: include/sbev_hip.h): its header, then `t`'s unit tables
+static int plan_words(const ChainPlan& p, const PlanUnits& t, int32_t* out, int capacity, const char* who) {
+    const int members = p.pair ? 2 : 1;
+    const long long words = 12 + 18LL * members * t.n_units;
+    SBEV_REQUIRE(out && capacity >= words, "%s: %lld words needed", who, words);
+    for (int v : {p.pre, p.rg, p.pair, (int)p.grid, p.lds, t.n_units, p.n_pairs, (int)p.warm, p.warm_lines, (int)p.vec, p.vec_off, p.vec_n}) *out++ = v;
+    for (int mem = 0; mem < members; ++mem)
+        for (int u = 0; u < t.n_units; ++u, out += 18) unit_words(t.units[mem][u], out);
+    return (int)words;
+}
+
+static bool plan_args_ok(const sbev_decoder_config* cfg, int kind, int cus) {
+    return cfg && sbev::row_chain_supported(*cfg) && cfg->B >= 1 && cfg->Q >= 1 && (long long)cfg->B * cfg->Q <= 256 * 16 && kind >= PRE_SLABS &&
+           kind <= PRE_ATT && cus >= 0;
+}
+
+// The same launch as a fixed plan would run it: the header of chain_plan, the unit tables from the constant table of the fixed kernel
+// with the launch's key.  0 = none: no fixed kernel has that key (or the config is not covered by the row chains at all).  Touches no device
+extern "C" int sbev_decoder_chain_fixed_plan(const sbev_decoder_config* cfg, int kind, int with_front, int pair_ok, int cus, int32_t* out, int capacity) {
+    if (!plan_args_ok(cfg, kind, cus)) return 0;
+    const ChainPlan p = chain_plan(*cfg, kind, with_front != 0, pair_ok != 0, cus);
+    const int fix = find_fixed(key_of(*cfg, p, with_front != 0));
+    if (fix < 0) return 0;
+    return plan_words(p, kFixedUnits[fix], out, capacity, "sbev_decoder_chain_fixed_plan");
+}
+
 // chain_plan's answer as int32 words (layout: include/sbev_hip.h).  Touches no device
 extern "C" int sbev_decoder_chain_plan(const sbev_decoder_config* cfg, int kind, int with_front, int pair_ok, int cus, int32_t* out, int capacity) {
-    SBEV_REQUIRE(cfg && sbev::row_chain_supported(*cfg) && cfg->B >= 1 && cfg->Q >= 1 && (long long)cfg->B * cfg->Q <= 256 * 16 &&
-                     kind >= PRE_SLABS && kind <= PRE_ATT && cus >= 0,
+    SBEV_REQUIRE(plan_args_ok(cfg, kind, cus),
                  "sbev_decoder_chain_plan: config not covered by the row chains (1 .. 4096 rows), or kind / cus out of range");
     const ChainPlan p = chain_plan(*cfg, kind, with_front != 0, pair_ok != 0, cus);
-    const int members = p.pair ? 2 : 1;
-    const long long words = 12 + 18LL * members * p.n_units;
-    SBEV_REQUIRE(out && capacity >= words, "sbev_decoder_chain_plan: %lld words needed", words);
-    for (int v : {p.pre, p.rg, p.pair, (int)p.grid, p.lds, p.n_units, p.n_pairs, (int)p.warm, p.warm_lines, (int)p.vec, p.vec_off, p.vec_n}) *out++ = v;
-    for (int mem = 0; mem < members; ++mem)
-        for (int u = 0; u < p.n_units; ++u) {
-            const PUnit& pu = p.units[mem][u];
-            *out++ = pu.epi;
-            *out++ = pu.col0;
-            for (const PLin* l : {&pu.a, &pu.b})
-                for (int v : {(int)l->w, l->in_off, l->ld, l->KH, l->items, l->chunks, l->kh0, l->KHT}) *out++ = v;
-        }
-    return (int)words;
+    return plan_words(p, p, out, capacity, "sbev_decoder_chain_plan");
 }
 
 extern "C" int sbev_decoder_chain_pack(const sbev_decoder_config* cfg, const sbev_decoder_weights* w, float* out, sbev_stream_t stream) {

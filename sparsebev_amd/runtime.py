@@ -899,6 +899,18 @@ def chain_pair(enable):
     return bool(_lib.load().sbev_decoder_chain_pair(int(bool(enable))))
 
 
+def chain_fixed(enable):
+    """The row-chain kernels with config 2's unit tables compiled in (csrc/row_chain.hip, "fixed plans"; default on, ``SBEV_CHAIN_FIXED=0``
+    starts with them off).  Bit-identical results either way.  Not part of the step-graph key: a captured step keeps the kernels it was
+    recorded with.  Returns the previous setting."""
+    return bool(_lib.load().sbev_decoder_chain_fixed(int(bool(enable))))
+
+
+def chain_fixed_launches():
+    """Row-chain launches since the library was loaded that took a fixed-plan kernel (a captured launch counts once, at its capture)."""
+    return int(_lib.load().sbev_decoder_chain_fixed_launches())
+
+
 def _on_pair_fault():
     """SBEV_EFAULT came back (``_lib.check``): pair mode off (the library did that already; captured pair-mode steps are keyed on
     the switch and are not hit again) and acknowledge, so that the caller's repeated step runs on the single-workgroup tail."""
