@@ -1361,7 +1361,7 @@ int sbev_fpn_forward(int n_levels, const int32_t* chw, int64_t n, int num_outs, 
 
 /*
  * The FPN neck's backward: from the output gradients to the gradients of the inputs, weights and biases, 4 L + 1 launches (5 L + 1 with
- * input gradients) and one 16-byte memset node, all four GEMM families on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
+ * input gradients) and one tiny launch that clears the 16 head bytes (a kernel, not a memset node), all four GEMM families on v_mfma_f32_32x32x16_f16 with fp32 accumulation.
  * Replaces: autograd through mmdet's FPN under fp16 autocast (the backward of 2 L convolutions, the interpolate / add / cast nodes).
  * The forward is sbev_fpn_forward's; the rounding to fp16 in M_l is straight-through (derivative 1), as under autocast.
  *   grad_outs[o]   gP_o [n, H_o, W_o, 256] channels-last, g_dtype SBEV_F32 or SBEV_F16, o = 0 .. num_outs - 1
@@ -1568,6 +1568,40 @@ int sbev_conv_wgrad_f16(const void* gy, const void* x, float* part, int64_t n, i
 int sbev_bn_fold_backward(const float* part, int slabs, const float* scale, const void* w, int w_dtype, const float* gamma, const float* mean,
                           const float* var, float eps, int Cin, int Cout, int taps, float* grad_w, float* grad_gamma, float* grad_beta,
                           sbev_stream_t stream);
+
+/*
+ * Both weight images of the ResNet backbone by ONE launch that takes no host array, so that it records into a graph and a replay folds
+ * the weights as they are then (a captured training step after an optimizer update).
+ * Replaces, inside a captured step: one sbev_resnet_pack_weights launch per convolution plus one sbev_resnet_pack_weights_bwd launch per
+ * convolution that sends a data gradient (about 100 launches for ResNet-50); those entries stay the eager path and this one's reference.
+ *
+ * sbev_resnet_repack_plan (pure host): the net as the other resnet plans describe it; first_trainable_stage 1 .. num_stages as
+ *   sbev_resnet_backward_plan takes it, or num_stages + 1: nothing trains, the backward image is empty.  w / gamma / beta / mean / var:
+ *   one DEVICE pointer per convolution in launch order (entry 0 the stem), only looked at, never read through.  Fills `table`
+ *   (SBEV_RESNET_REPACK_WORDS words of host memory; the caller uploads the first out[0] of them to the device):
+ *     0 convolutions   1 work items   2 forward-image bytes   3 backward-image bytes   4 w_dtype   the rest of the head zero; then from
+ *     word SBEV_RESNET_REPACK_HEAD, SBEV_RESNET_REPACK_LAYER_WORDS per convolution: the addresses of w, gamma, beta, mean, var; Cin, Cout,
+ *     taps (49: the stem); the byte offset of its forward fragments and of its fp32 bias (exactly where sbev_resnet_pack_weights puts
+ *     them for the whole net); the byte offset of its backward image (sbev_resnet_backward_plan's, -1: none); its first work item.
+ *   A work item is 32 output channels x 64 reduction indices x all taps; a workgroup finds an item's convolution by a binary search over
+ *   the first-item column.  out[4]: table words, work items (the grid of a launch with one workgroup per item), forward-image bytes
+ *   (sbev_resnet_plan's pack bytes), backward-image bytes (sbev_resnet_backward_plan's).
+ *   Checked (SBEV_EINVAL): null table / out, w_dtype, the plans' refusals, first_trainable_stage, a null or misaligned tensor (element
+ *   alignment, as the pack entries ask).
+ * sbev_resnet_repack: one kernel launch on the stream -- a fixed number of workgroups striding over the table's work items, so the call
+ *   needs no host copy of the table.  fwd_image / bwd_image: the plan's bytes, 16-byte aligned; bwd_image may be null when the backward
+ *   image is empty; where it is null although the table gives convolutions a backward offset, those images are silently NOT written
+ *   (the table lives on the device: the host entry cannot see it; the caller sizes bwd_image from the plan's word 3).  Bit for bit what sbev_resnet_pack_weights and sbev_resnet_pack_weights_bwd write (s = gamma / sqrt(var + eps),
+ *   b' = beta - mean s, w' = fp16(w s), each operation rounded on its own; w' is computed once and feeds both images).  Every weight
+ *   element is read once; every 16-byte piece of both images is stored exactly once, whole; no atomics; nothing else is written.
+ */
+#define SBEV_RESNET_REPACK_HEAD 8
+#define SBEV_RESNET_REPACK_LAYER_WORDS 12
+#define SBEV_RESNET_REPACK_WORDS (SBEV_RESNET_REPACK_HEAD + SBEV_RESNET_REPACK_LAYER_WORDS * SBEV_RESNET_MAX_LAYERS)
+int sbev_resnet_repack_plan(int depth, const int32_t* stage_blocks, int num_stages, int base_channels, int first_trainable_stage,
+                            const void* const* w, const float* const* gamma, const float* const* beta, const float* const* mean,
+                            const float* const* var, int w_dtype, int64_t* table, int64_t* out);
+int sbev_resnet_repack(const int64_t* table_dev, void* fwd_image, void* bwd_image, float eps, sbev_stream_t stream);
 
 #ifdef __cplusplus
 }

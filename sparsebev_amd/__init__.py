@@ -9,7 +9,7 @@ operator modules without the built library raises -- there is no CPU / PyTorch f
 from ._lib import load as load_library, SbevError, LIB_PATH   # noqa: F401
 
 __all__ = ['load_library', 'SbevError', 'LIB_PATH', 'SparseBEVHead', 'SparseBEVTrainHead', 'FusedAdamW', 'ImageFrontEnd', 'ImageGeometry', 'FPNNeck',
-           'ResNetBackbone']
+           'ResNetBackbone', 'SparseBEV']
 
 
 def __getattr__(name):
@@ -35,4 +35,7 @@ def __getattr__(name):
     if name == 'ResNetBackbone':
         from .resnet import ResNetBackbone
         return ResNetBackbone
+    if name == 'SparseBEV':
+        from .detector import SparseBEV
+        return SparseBEV
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

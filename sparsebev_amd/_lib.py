@@ -203,6 +203,9 @@ SIGNATURES = {
     'sbev_resnet_forward_train': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, _c_i32p, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp]),
     'sbev_resnet_pack_weights_bwd': (ctypes.c_int, [ctypes.c_int, _c_i32p] + [ctypes.POINTER(_vp)] * 3 + [ctypes.c_float, ctypes.c_int, _vp, _vp]),
+    'sbev_resnet_repack_plan': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.POINTER(_vp)] * 5 +
+                                [ctypes.c_int, _c_i64p, _c_i64p]),
+    'sbev_resnet_repack': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp]),
     'sbev_resnet_backward': (ctypes.c_int, [ctypes.c_int, _c_i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, _c_i32p, ctypes.c_int, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.c_int, _vp, _vp,
                                             ctypes.POINTER(_vp), ctypes.c_int] + [ctypes.POINTER(_vp)] * 3 + [ctypes.c_float] +

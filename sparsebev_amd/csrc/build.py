@@ -51,6 +51,8 @@ UNITS = {
     'resnet.hip': ['-ffp-contract=off'],
     # its backward: the BatchNorm fold's backward is defined the same way (individually rounded fp32 operations, a fixed sum order)
     'resnet_bwd.hip': ['-ffp-contract=off'],
+    # both of the backbone's weight images by one launch: the same fold, so the same flag (bit-identical to the two units above)
+    'resnet_repack.hip': ['-ffp-contract=off'],
     'decoder.hip': [],
     'row_chain.hip': [],                 # the row-local op chains of a layer (4x4x1 MFMA with A broadcast)
     'fault_word.hip': [],                # host only: the sticky host-mapped fault word row_chain.hip and gemm_bf16s.hip report into

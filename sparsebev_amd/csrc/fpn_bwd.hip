@@ -3,7 +3,8 @@
 // domain: one launch finds amax = max |gP_o| and writes (2^e, 2^-e) with 2^e amax in [2^3, 2^4) to device memory; every consumer reads
 // the pair from there (no host read: the call can be captured), fp32 results are multiplied by 2^-e on the way out.
 //
-// Launches for L levels (plus one 16-byte memset node that clears the amax word and the ticket): 4 L + 1, or 5 L + 1 with input gradients.
+// Launches for L levels (plus one tiny launch that clears the amax word and the ticket -- a kernel, not a memset node: a captured 16-byte
+// memset wrote stale bytes from the second replay of a graph on, resnet_bwd.hip met the same): 4 L + 1, or 5 L + 1 with input gradients.
 //   1            fpn_amax_kernel: amax over every output gradient (integer max of the absolute bit patterns: order-free), the last
 //                workgroup (a ticket) writes the pair.  A zero or non-finite amax gives e = 0: an inf or NaN then travels as it is.
 //   1            fpn_dgrad3_kernel: D_l = conv3x3(fp16(2^e G_l), W3_l'), the forward's convolution kernel shape (same tile table, same
@@ -46,6 +47,11 @@ struct AmaxArgs {
     unsigned* ws;                        // [0] 2^e  [1] 2^-e  (floats)  [2] amax bits  [3] ticket
     int n, f32;
 };
+
+// the four head words (pair, amax bits, ticket) back to zero before every amax
+__global__ __launch_bounds__(64) void fpn_clear_kernel(unsigned* ws) {
+    if (threadIdx.x < 4) ws[threadIdx.x] = 0u;
+}
 
 __global__ __launch_bounds__(256) void fpn_amax_kernel(const AmaxArgs a) {
     __shared__ unsigned smax;
@@ -626,11 +632,8 @@ extern "C" int sbev_fpn_backward(int n_levels, const int32_t* chw, int64_t n, in
     const bool gf32 = g_dtype == SBEV_F32, xf32 = in_dtype == SBEV_F32;
     auto d_of = [&](int l) { return dbuf + (p.base[l] - p.base[1 < p.L ? 1 : 0]) * kOut; };
 
-    if (hipMemsetAsync(ws, 0, 16, s) != hipSuccess) {
-        (void)hipGetLastError();
-        sbev::set_error("%s: cannot clear the scale words", who);
-        return SBEV_ELAUNCH;
-    }
+    hipLaunchKernelGGL(fpn_clear_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned*>(ws));
+    if (int st = sbev::check_launch(who)) return st;          // the scale words are cleared or nothing else is enqueued
     {
         AmaxArgs a;
         long long most = 0;

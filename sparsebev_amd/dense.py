@@ -350,6 +350,11 @@ def step_images():
         _STEP_IMAGES = outer
 
 
+def in_step_images():
+    """True inside a step_images() scope (the backbone's and the neck's weight packs then belong to the step: resnet.py, fpn.py)"""
+    return _STEP_IMAGES is not None
+
+
 def derived_image(cache_ok, kind, tensors, make, lookup, store):
     """One derived image of ``tensors`` by ``make()``: from the step's scope inside step_images(); from the process-wide cache
     (``lookup()`` -> image or None, ``store(image)``) in eager code; and while the current stream is capturing outside a scope the caches

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, dense
 
 MAX_IN, MAX_OUT, PLAN_WORDS = 4, 5, 18          # SBEV_FPN_MAX_IN, SBEV_FPN_MAX_OUT, SBEV_FPN_PLAN_WORDS
 BWD_PLAN_WORDS, GRAD_WINDOW_LOG2 = 16, 3         # SBEV_FPN_BWD_PLAN_WORDS, SBEV_FPN_GRAD_WINDOW_LOG2
@@ -147,8 +147,9 @@ class FPNNeck(nn.Module):
     (``lateral_convs.{i}.conv.weight`` / ``.bias``, ``fpn_convs.{i}.conv.weight`` / ``.bias``), Xavier-uniform weights and zero biases as
     mmdet's ``init_cfg`` gives them.  ``num_outs`` None: one output per input.  ``trainable`` False: a forward that would need a gradient
     is refused (inference only).  ``trainable`` True: such a forward goes through ``NeckFunction``; under ``torch.no_grad()`` nothing
-    differs.  Not built, and refused where asked for: a trainable forward under a graph capture (so the neck inside
-    ``CapturedHeadTrainStep``: the weight packs would have to move into the graph), ``add_extra_convs``, NCHW inputs, an fp16 hi + lo
+    differs.  Inside a ``dense.step_images()`` scope (a captured training step) both weight packs are derived once per scope by the step's
+    own pack calls into fresh tensors and the ``_version``-keyed caches are left alone; a trainable forward may then be captured.  Not
+    built, and refused where asked for: a trainable forward under a graph capture outside such a scope, ``add_extra_convs``, NCHW inputs, an fp16 hi + lo
     mode of the gradient operands."""
 
     def __init__(self, in_channels, out_channels=256, num_outs=None, trainable=False, add_extra_convs=False, grad_mode='f16'):
@@ -204,23 +205,36 @@ class FPNNeck(nn.Module):
             raise RuntimeError('FPNNeck needs its parameters on the device (no CPU fallback)')
         if any(w.device != dev or w.dtype != ws[0].dtype for w in ws) or ws[0].dtype not in _DTYPES:
             raise TypeError('FPNNeck: the convolution weights must be all fp32 or all fp16, on one device')
+        if dense.in_step_images():      # a training step's scope: derived by the step's own launches, the cache neither read nor filled
+            return dense.derived_image(True, 'fpn_pack', tuple(ws), lambda: self._pack_launch(False, lat, out, None, stream), None, None)
         key = tuple((w.data_ptr(), w._version) for w in ws)
         if key == self._pack_key:
             return self._pack
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError('FPNNeck.forward under a capture with weights that are not packed: run one forward (or pack()) before the capture')
+        if self._pack is not None and self._pack.device != dev:
+            self._pack = None
+        self._pack = self._pack_launch(False, lat, out, self._pack, stream)
+        self._pack_key = key
+        return self._pack
+
+    def _pack_launch(self, bwd, lat, out, dest, stream):
+        """sbev_fpn_pack_weights (``bwd``: sbev_fpn_pack_weights_bwd) on checked weights into ``dest`` (None: a fresh tensor)"""
+        ws = lat + out
+        dev = ws[0].device
         if any(not w.is_contiguous() for w in ws):
             raise ValueError('FPNNeck: the convolution weights must be contiguous')
         chw = [(c, 1, 1) for c in self.in_channels]
+        name = 'sbev_fpn_pack_weights_bwd' if bwd else 'sbev_fpn_pack_weights'
         with torch.cuda.device(dev):
-            if self._pack is None or self._pack.device != dev:
-                self._pack = torch.empty(plan(chw, 0, len(chw))['pack_bytes'] // 2, dtype=torch.float16, device=dev)
+            if dest is None:
+                nbytes = (backward_plan if bwd else plan)(chw, 0, len(chw))['pack_bytes']
+                dest = torch.empty(nbytes // 2, dtype=torch.float16, device=dev)
             flat = (ctypes.c_int32 * (3 * len(chw)))(*[v for level in chw for v in level])
             s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if stream is None else stream
-            _lib.check(_lib.load().sbev_fpn_pack_weights(len(chw), flat, _vp_array([w.data_ptr() for w in lat]), _vp_array([w.data_ptr() for w in out]),
-                                                         _DTYPES[ws[0].dtype], ctypes.c_void_p(self._pack.data_ptr()), s), 'sbev_fpn_pack_weights')
-        self._pack_key = key
-        return self._pack
+            _lib.check(getattr(_lib.load(), name)(len(chw), flat, _vp_array([w.data_ptr() for w in lat]), _vp_array([w.data_ptr() for w in out]),
+                                                  _DTYPES[ws[0].dtype], ctypes.c_void_p(dest.data_ptr()), s), name)
+        return dest
 
     def pack_bwd(self, stream=None):
         """The backward's weight image (sbev_fpn_pack_weights_bwd), packed now if the weights changed since its last pack."""
@@ -231,22 +245,16 @@ class FPNNeck(nn.Module):
             raise RuntimeError('FPNNeck needs its parameters on the device (no CPU fallback)')
         if any(w.device != dev or w.dtype != ws[0].dtype for w in ws) or ws[0].dtype not in _DTYPES:
             raise TypeError('FPNNeck: the convolution weights must be all fp32 or all fp16, on one device')
+        if dense.in_step_images():
+            return dense.derived_image(True, 'fpn_pack_bwd', tuple(ws), lambda: self._pack_launch(True, lat, out, None, stream), None, None)
         key = tuple((w.data_ptr(), w._version) for w in ws)
         if key == self._pack_bwd_key:
             return self._pack_bwd
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError('FPNNeck backward under a capture with weights that are not packed')
-        if any(not w.is_contiguous() for w in ws):
-            raise ValueError('FPNNeck: the convolution weights must be contiguous')
-        chw = [(c, 1, 1) for c in self.in_channels]
-        with torch.cuda.device(dev):
-            if self._pack_bwd is None or self._pack_bwd.device != dev:
-                self._pack_bwd = torch.empty(backward_plan(chw, 0, len(chw))['pack_bytes'] // 2, dtype=torch.float16, device=dev)
-            flat = (ctypes.c_int32 * (3 * len(chw)))(*[v for level in chw for v in level])
-            s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if stream is None else stream
-            _lib.check(_lib.load().sbev_fpn_pack_weights_bwd(len(chw), flat, _vp_array([w.data_ptr() for w in lat]),
-                                                             _vp_array([w.data_ptr() for w in out]), _DTYPES[ws[0].dtype],
-                                                             ctypes.c_void_p(self._pack_bwd.data_ptr()), s), 'sbev_fpn_pack_weights_bwd')
+        if self._pack_bwd is not None and self._pack_bwd.device != dev:
+            self._pack_bwd = None
+        self._pack_bwd = self._pack_launch(True, lat, out, self._pack_bwd, stream)
         self._pack_bwd_key = key
         return self._pack_bwd
 
@@ -321,7 +329,7 @@ class FPNNeck(nn.Module):
                 raise ValueError('FPNNeck: out= is not taken by a forward that needs a gradient (autograd owns its outputs)')
             if out_dtype not in _DTYPES:
                 raise TypeError('FPNNeck: out_dtype must be torch.float16 or torch.float32')
-            if torch.cuda.is_current_stream_capturing():
+            if torch.cuda.is_current_stream_capturing() and not dense.in_step_images():
                 raise RuntimeError('FPNNeck: a trainable forward under a graph capture (the neck inside CapturedHeadTrainStep) is not built: '
                                    'the weight packs would have to move into the graph')
             chw = tuple((c, int(x.shape[2]), int(x.shape[3])) for c, x in zip(self.in_channels, inputs))

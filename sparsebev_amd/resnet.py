@@ -21,7 +21,7 @@ import ctypes
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, dense
 
 MAX_LAYERS, PLAN_HEAD, LAYER_WORDS = 160, 18, 12        # SBEV_RESNET_MAX_LAYERS, SBEV_RESNET_PLAN_HEAD, SBEV_RESNET_LAYER_WORDS
 PLAN_WORDS = PLAN_HEAD + LAYER_WORDS * MAX_LAYERS
@@ -105,6 +105,8 @@ def conv_f16(x, pack, residual, y, taps, stride, epilogue, col_tile=0):
 
 BWD_PLAN_HEAD, BWD_LAYER_WORDS, GRAD_WINDOW_LOG2 = 16, 6, 3      # SBEV_RESNET_BWD_PLAN_HEAD, .._LAYER_WORDS, SBEV_RESNET_GRAD_WINDOW_LOG2
 BWD_PLAN_WORDS = BWD_PLAN_HEAD + BWD_LAYER_WORDS * MAX_LAYERS
+REPACK_HEAD, REPACK_LAYER_WORDS = 8, 12                          # SBEV_RESNET_REPACK_HEAD, SBEV_RESNET_REPACK_LAYER_WORDS
+REPACK_WORDS = REPACK_HEAD + REPACK_LAYER_WORDS * MAX_LAYERS
 
 
 def _ptr(t):
@@ -159,6 +161,34 @@ def pack_layers_bwd(layers, eps=1e-5, pack=None):
         _lib.check(_lib.load().sbev_resnet_pack_weights_bwd(len(layers), _i32(desc), *cols, float(eps), _DTYPES[ws[0].dtype], _ptr(pack),
                                                             _stream(dev)), 'sbev_resnet_pack_weights_bwd')
     return pack, offs
+
+
+def repack_plan(depth, pointers, w_dtype=torch.float32, num_stages=4, base_channels=64, stage_blocks=None, first_trainable_stage=2):
+    """sbev_resnet_repack_plan, a pure host function.  ``pointers``: one (w, gamma, beta, mean, var) tuple of device ADDRESSES per
+    convolution in launch order (0 the stem).  Returns a dict of table (the int64 words to upload), items (the work items: the grid of a
+    launch with one workgroup each), pack_bytes / pack_bwd_bytes (the two images), and layers: per convolution w, gamma, beta, mean, var,
+    cin, cout, taps, offset, bias_offset, bwd_offset (-1: no backward image), first_item.  ``first_trainable_stage`` = num_stages + 1:
+    nothing trains, the backward image is empty.  Raises SbevError where the plan refuses."""
+    if stage_blocks is not None and len(stage_blocks) != num_stages:
+        raise ValueError('stage_blocks must list num_stages=%d block counts' % num_stages)
+    blocks = None if stage_blocks is None else _i32(stage_blocks)
+    cols = [(ctypes.c_void_p * max(len(pointers), 1))(*[p[j] for p in pointers]) for j in range(5)]
+    table, out = (ctypes.c_int64 * REPACK_WORDS)(), (ctypes.c_int64 * 4)()
+    _lib.check(_lib.load().sbev_resnet_repack_plan(int(depth), blocks, int(num_stages), int(base_channels), int(first_trainable_stage), *cols,
+                                                   _DTYPES[w_dtype], table, out), 'sbev_resnet_repack_plan')
+    words = [int(v) for v in table[:int(out[0])]]
+    names = ('w', 'gamma', 'beta', 'mean', 'var', 'cin', 'cout', 'taps', 'offset', 'bias_offset', 'bwd_offset', 'first_item')
+    layers = [dict(zip(names, words[REPACK_HEAD + REPACK_LAYER_WORDS * i:REPACK_HEAD + REPACK_LAYER_WORDS * (i + 1)])) for i in range(words[0])]
+    return dict(table=words, items=int(out[1]), pack_bytes=int(out[2]), pack_bwd_bytes=int(out[3]), layers=layers)
+
+
+def repack(table_dev, pack, pack_bwd, eps=1e-5):
+    """sbev_resnet_repack: ONE launch on the current stream that writes both images of the net ``table_dev`` (the uploaded table of
+    ``repack_plan``) describes into the uint8 tensors ``pack`` and ``pack_bwd`` (None where the backward image is empty)."""
+    dev = pack.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sbev_resnet_repack(_ptr(table_dev), _ptr(pack), _ptr(pack_bwd), float(eps), _stream(dev)), 'sbev_resnet_repack')
+    return pack, pack_bwd
 
 
 def conv_dgrad_f16(gy, pack, gx, taps, stride, gy2=None, stride2=1, mask=None, res=None, gp=None, scale=None, col_tile=0):
@@ -304,7 +334,10 @@ class ResNetBackbone(nn.Module):
     always).  A forward under grad then goes through ``BackboneFunction``; under ``torch.no_grad()`` nothing differs, bit for bit.
     ``with_cp`` stays accepted without effect: nothing is recomputed, the activations are kept.  Refused by name: ``frozen_stages=-1``
     with ``trainable=True`` (a trainable stem: the 7 x 7 weight gradient and the max-pool backward are not built), an image that requires
-    a gradient, a trainable forward under a graph capture."""
+    a gradient, a trainable forward under a graph capture outside a ``dense.step_images()`` scope.  Inside such a scope (a captured
+    training step: ``train_graph.CapturedDetectorTrainStep``) ``pack()`` / ``pack_bwd()`` derive both images once per scope by ONE launch
+    of the step itself (``sbev_resnet_repack``, through a device table of the parameters' addresses that a warm-up step uploads) and leave
+    the ``_version``-keyed caches alone, so a replay folds the weights as they are then."""
 
     def __init__(self, depth=50, num_stages=4, out_indices=(0, 1, 2, 3), style='pytorch', base_channels=64, norm_cfg=None,
                  out_dtype=torch.float16, stage_blocks=None, in_channels=3, strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1), frozen_stages=-1,
@@ -384,6 +417,7 @@ class ResNetBackbone(nn.Module):
         self._pack_bwd = None           # the backward's weight image (transposed / flipped w'), same version key
         self._pack_bwd_key = None
         self._bwd_workspaces = {}       # (device index, n, H, W) -> uint8 workspace of the backward
+        self._repack_tables = {}        # repack_key() -> (device table of sbev_resnet_repack, its plan), the latest key only: step_images() scopes
 
     # ---- weights
     def conv_bn_pairs(self):
@@ -407,6 +441,8 @@ class ResNetBackbone(nn.Module):
             raise TypeError('ResNetBackbone: the convolution weights must be all fp32 or all fp16, on one device')
         if any(t.device != dev or t.dtype != torch.float32 for t in stats):
             raise TypeError('ResNetBackbone: the BatchNorm weights and statistics must be fp32, on the weights\' device')
+        if dense.in_step_images():      # a training step's scope: both images by the step's own single launch, the caches untouched
+            return self._step_images(layers)[0]
         key = tuple((t.data_ptr(), t._version) for l in layers for t in l)
         if key == self._pack_key:
             return self._pack
@@ -438,6 +474,9 @@ class ResNetBackbone(nn.Module):
         pairs = self.conv_bn_pairs()
         layers = [(c.weight, b.weight, b.bias, b.running_mean, b.running_var) for c, b in pairs]
         dev = layers[0][0].device
+        if dense.in_step_images():
+            self.pack()           # its checks; the same scope entry
+            return self._step_images(layers)[1]
         key = (self.frozen_stages,) + tuple((t.data_ptr(), t._version) for l in layers for t in l)
         if key == self._pack_bwd_key:
             return self._pack_bwd
@@ -453,6 +492,59 @@ class ResNetBackbone(nn.Module):
         assert offs == [o for o, _ in order]
         self._pack_bwd_key = key
         return self._pack_bwd
+
+    # ---- the two images inside a training step's scope (dense.step_images): one sbev_resnet_repack launch per step
+    def repack_key(self):
+        """what the device table of sbev_resnet_repack bakes in: device, dtype, first trainable stage, every tensor's address"""
+        pairs = self.conv_bn_pairs()
+        w = pairs[0][0].weight
+        fts = self.frozen_stages + 1 if self.trainable else self.num_stages + 1
+        return (w.device.index, w.dtype, min(fts, self.num_stages + 1)) + tuple(
+            t.data_ptr() for c, b in pairs for t in (c.weight, b.weight, b.bias, b.running_mean, b.running_var))
+
+    def repack_table(self, key):
+        """the (device table, plan) built for ``key``, or None: a captured step keeps it alive beside its graph"""
+        return self._repack_tables.get(key)
+
+    def check_repack_table(self, key):
+        """A captured step's replay-time check: the graph's repack launch reads the table built for ``key`` (``repack_key()`` at
+        capture); a parameter or buffer that has moved since (``.to()``, ``p.data = ...``, ``load_state_dict(assign=True)``) would be
+        folded from its OLD address."""
+        now = self.repack_key()
+        if now != key:
+            moved = sum(a != b for a, b in zip(now[3:], key[3:]))
+            raise RuntimeError('ResNetBackbone: %d parameter / buffer tensor(s) have another address, dtype or device than the captured '
+                               "step's weight-repack table holds: capture a new step" % max(moved, 1))
+
+    def _repack_table(self, layers):
+        key = self.repack_key()
+        hit = self._repack_tables.get(key)
+        if hit is not None:
+            return hit
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ResNetBackbone under a capture inside step_images(): no weight-repack table for the current parameter '
+                               'addresses (the table is uploaded outside a capture): run a warm-up step first')
+        if any(not t.is_contiguous() for l in layers for t in l):
+            raise ValueError('ResNetBackbone: parameters and buffers must be contiguous')
+        dev = layers[0][0].device
+        p = repack_plan(self.depth, [tuple(t.data_ptr() for t in l) for l in layers], layers[0][0].dtype, self.num_stages, self.base_channels,
+                        self.stage_blocks, key[2])
+        table = torch.tensor(p['table'], dtype=torch.int64).to(dev)
+        self._repack_tables = {key: (table, p)}         # the latest only: a captured step holds the table its graph reads (repack_table)
+        return self._repack_tables[key]
+
+    def _step_images(self, layers):
+        """(forward image, backward image) of the current step_images() scope: derived at the first call by ONE launch on the current
+        stream into fresh tensors (under a capture: from the capture's pool), returned by the later ones"""
+        def make():
+            table, p = self._repack_table(layers)
+            dev = table.device
+            with torch.cuda.device(dev):
+                fwd = torch.empty(max(p['pack_bytes'], 16), dtype=torch.uint8, device=dev)
+                bwd = torch.empty(p['pack_bwd_bytes'], dtype=torch.uint8, device=dev) if p['pack_bwd_bytes'] else None
+            return repack(table, fwd, bwd, self.eps)
+
+        return dense.derived_image(True, 'resnet_repack', tuple(t for l in layers for t in l), make, None, None)
 
     def backward_plan(self, n, H, W):
         return backward_plan(self.depth, n, H, W, self.out_indices, self.num_stages, self.base_channels, self.stage_blocks,
@@ -535,7 +627,7 @@ class ResNetBackbone(nn.Module):
             raise ValueError('ResNetBackbone: the image requires a gradient; no image gradient is ever produced (the stem is frozen): detach it')
         if out is not None or keep is not None:
             raise ValueError('ResNetBackbone: out= / keep= are not taken by a forward that needs a gradient (autograd owns its outputs)')
-        if torch.cuda.is_current_stream_capturing():
+        if torch.cuda.is_current_stream_capturing() and not dense.in_step_images():
             raise RuntimeError('ResNetBackbone: a trainable forward under a graph capture (the backbone inside CapturedHeadTrainStep) is not '
                                'built: the weight packs would have to move into the graph')
         if x.device != self.conv1.weight.device:

@@ -41,6 +41,10 @@ consumed.  With ``optimizer=`` a process group of more than one rank is refused:
 cost, assignment, plan, both set-loss calls, the embeddings' backward) on a ``SparseBEVTrainHead(gt_capacity=...)``: there the ground
 truth is one more per-call constant, a ``head_train.GroundTruthSlab`` refreshed in place outside the graph, with the dn noise beside it.
 
+``CapturedDetectorTrainStep`` is the whole detector's step (``detector.SparseBEV``): image front end, backbone, neck, the head's step,
+their backward and the update.  The backbone's and the neck's weight packs are derived images like the ones above: inside ``step_images()``
+they are made by the step's own launches (resnet.py, fpn.py).
+
 Reference counterpart: the training loop around SparseBEVTransformer.forward (models/sparsebev_transformer.py:86-101) and its
 backward through msmv_sampling (models/csrc/wrapper.py:51-61); the reference has no graph capture.
 """
@@ -241,19 +245,23 @@ class CapturedHeadTrainStep(_CapturedStep):
         self.mlvl_feats = list(mlvl_feats)
         if not all(torch.is_tensor(f) and f.is_cuda and f.dtype == torch.float32 for f in self.mlvl_feats):
             raise ValueError('CapturedHeadTrainStep: mlvl_feats must be a list of fp32 CUDA tensors (they are read in place)')
-        self.B, self.device = self.mlvl_feats[0].shape[0], self.mlvl_feats[0].device
-        layer = head.transformer.decoder.decoder_layer
-        self.dropout = bool(layer.self_attn.attn_drop > 0 or layer.ffn_drop > 0)
-        self.slab = head.gt_slab(self.B, self.device)
-        self._set_ground_truth([m['gt_bboxes_3d'] for m in img_metas], [m['gt_labels_3d'] for m in img_metas])
-        self.ctx = DecoderContext(img_metas, self.B, self.device)          # host -> device: outside the graph
-        self.noise = head.draw_noise(self.slab.G, self.device)            # static: replay() writes the next draw into these
+        self._bind_head(head, self.mlvl_feats[0].shape[0], self.mlvl_feats[0].device, img_metas)
         params = [p for p in head.parameters() if p.requires_grad]
         self._bind_optimizer(optimizer, params)
         self._leaves = params + [f for f in self.mlvl_feats if f.requires_grad]
         self.losses = self._capture(warmup)
         self.grads = {n: p.grad for n, p in head.named_parameters() if p.grad is not None}
         self.input_grads = {'mlvl_feats': [f.grad for f in self.mlvl_feats]}
+
+    def _bind_head(self, head, B, device, img_metas):
+        """what a step through the training head keeps in static device memory: the ground-truth slab, the camera block, the dn noise"""
+        self.B, self.device = B, device
+        layer = head.transformer.decoder.decoder_layer
+        self.dropout = bool(layer.self_attn.attn_drop > 0 or layer.ffn_drop > 0)
+        self.slab = head.gt_slab(self.B, self.device)
+        self._set_ground_truth([m['gt_bboxes_3d'] for m in img_metas], [m['gt_labels_3d'] for m in img_metas])
+        self.ctx = DecoderContext(img_metas, self.B, self.device)          # host -> device: outside the graph
+        self.noise = head.draw_noise(self.slab.G, self.device)            # static: replay() writes the next draw into these
 
     def _set_ground_truth(self, boxes, labels):
         if len(boxes) != self.B or len(labels) != self.B:
@@ -281,6 +289,12 @@ class CapturedHeadTrainStep(_CapturedStep):
         dict -- clone what has to survive the next replay.  ``ValueError`` before anything is enqueued when a sample is above the
         capacity."""
         self._check_feature_grad_mode()
+        self._refresh_head(gt_bboxes_list, gt_labels_list, img_metas, new_masks, noise)
+        self._replay_graph()
+        return self.losses
+
+    def _refresh_head(self, gt_bboxes_list, gt_labels_list, img_metas, new_masks, noise):
+        """the slab, the camera block, the dn noise and the dropout word of the next step: in place, outside the graph"""
         self._set_ground_truth(gt_bboxes_list, gt_labels_list)
         if img_metas is not None:
             self._refresh_cameras(img_metas)
@@ -291,5 +305,102 @@ class CapturedHeadTrainStep(_CapturedStep):
                 dst.copy_(src.to(self.device))
         if self.seed_dev is not None and new_masks:
             self.seed_dev.random_()
+
+
+class CapturedDetectorTrainStep(CapturedHeadTrainStep):
+    """``step = CapturedDetectorTrainStep(detector, img, img_metas)`` captures the WHOLE detector's training step --
+    ``losses = detector.forward_train(img, img_metas, gt_bboxes, gt_labels)``, ``sum(losses.values()).backward()`` and, with ``optimizer=``,
+    the AdamW update -- as one graph: image front end, backbone forward, neck forward, the head's step (``CapturedHeadTrainStep``), neck
+    backward, backbone backward.  ``detector``: a ``detector.SparseBEV`` whose head is a ``SparseBEVTrainHead(gt_capacity=...)`` in
+    ``train()`` with denoising on; ``img``: the STATIC uint8 or fp32 [B, N, 3, H, W] device tensor; the ground truth is
+    ``img_metas[i]['gt_bboxes_3d'] / ['gt_labels_3d']``.
+
+    The backbone's and the neck's weight images are derived INSIDE the graph (``dense.step_images``: one ``sbev_resnet_repack`` launch
+    and the neck's two pack calls), so a replay after an optimizer update folds the weights as they are then.  The repack launch reads
+    the parameters through a device table of their addresses, uploaded during the warm-up; ``replay`` checks that no tensor has moved
+    since and raises otherwise -- and, since every other launch holds its parameters' addresses as kernel arguments, the same for every
+    parameter and buffer of the detector.
+
+    ``replay(gt_bboxes, gt_labels, img=None, img_metas=None, front_params=None, noise=None, new_masks=True)`` refreshes, outside the
+    graph: the static image tensor (``img``: the next images, copied in), the front end's table (``front_params``, or a fresh
+    ``front.draw``), the slab, the cameras, the dn noise and the dropout word -- then replays.  ``step.grads`` maps the detector's prefixed
+    parameter names to the static gradient tensors.  ``optimizer``: a FusedAdamW over exactly the detector's trainable parameters (the
+    reference's recipe: ``FusedAdamW(detector.param_groups(...))``); its three launches end the graph.  More than one rank is refused."""
+
+    def __init__(self, detector, img, img_metas, warmup=3, optimizer=None):
+        from .detector import SparseBEV
+        from .head_train import SparseBEVTrainHead
+        from .image_front import update_metas
+        who = 'CapturedDetectorTrainStep'
+        self._refuse_ranks(optimizer, always='the all-reduce of the averaging factors cannot be captured (run the eager step)')
+        if not torch.is_grad_enabled():
+            raise RuntimeError('%s: grad is disabled' % who)
+        VERSION.require_supported()
+        if not isinstance(detector, SparseBEV):
+            raise TypeError('%s: the detector must be a sparsebev_amd.detector.SparseBEV' % who)
+        head = detector.pts_bbox_head
+        if not isinstance(head, SparseBEVTrainHead) or head.gt_capacity is None:
+            raise ValueError('%s: the head must be a SparseBEVTrainHead(gt_capacity=...): at a dynamic shape nothing can be replayed' % who)
+        if not (detector.training and head.training and head.dn_enabled):
+            raise ValueError('%s: the detector must be in train() mode with query denoising on' % who)
+        if not (torch.is_tensor(img) and img.is_cuda and img.dim() == 5 and img.shape[0] == len(img_metas) and img.shape[2] == 3
+                and img.dtype in (torch.uint8, torch.float32) and img.is_contiguous()):
+            raise ValueError('%s: img must be a contiguous uint8 or fp32 [B, N, 3, H, W] CUDA tensor with one img_metas entry per sample '
+                             '(it is read in place)' % who)
+        self.detector, self.head, self.img = detector, head, img
+        self.front = detector.front
+        self._update_metas = lambda metas: update_metas(metas, img.shape[0], img.shape[1], img.shape[3], img.shape[4], self.front.size_divisor)
+        metas = [dict(m) for m in img_metas]
+        Hp, _ = self._update_metas(metas)                              # the padded image size: the camera block's
+        self._Hp = Hp
+        self._bind_head(head, img.shape[0], img.device, metas)
+        self.front.upload(self.front.draw(img.shape[0] * img.shape[1], Hp), self.device)
+        named = [(n, p) for n, p in detector.named_parameters() if p.requires_grad]
+        self._bind_optimizer(optimizer, [p for _, p in named])
+        self._leaves = [p for _, p in named]
+        self.losses = self._capture(warmup)
+        self._repack_key = detector.img_backbone.repack_key()         # the addresses the graph's repack launch reads through
+        self._repack_table = detector.img_backbone.repack_table(self._repack_key)      # alive as long as the graph that reads it
+        # every launch of the graph holds its parameters' and buffers' addresses as kernel arguments: none may move before a replay
+        self._addresses = [(n, t.data_ptr()) for n, t in list(detector.named_parameters()) + list(detector.named_buffers())]
+        self.grads = {n: p.grad for n, p in named if p.grad is not None}
+        self.input_grads = {}
+
+    def _run(self):
+        head = self.head
+        saved = (head.dn_noise, head.decoder_ctx)
+        head.dn_noise, head.decoder_ctx = self.noise, self.ctx
+        try:
+            losses = self.detector.forward_train(self.img, [dict(m) for m in self._metas], self._boxes, self._labels)
+            sum(losses.values()).backward()
+        finally:
+            head.dn_noise, head.decoder_ctx = saved
+        return {k: v.detach() for k, v in losses.items()}
+
+    def replay(self, gt_bboxes_list, gt_labels_list, img=None, img_metas=None, front_params=None, noise=None, new_masks=True):
+        """Run the captured step on the next batch (class text).  Returns the graph's own loss dict -- clone what has to survive the next
+        replay.  Raises before anything is enqueued: ``ValueError`` for a sample above the capacity or an ``img`` of another shape or
+        dtype, ``RuntimeError`` when a backbone tensor has moved since the capture."""
+        who = type(self).__name__
+        self._check_feature_grad_mode()
+        self.detector.img_backbone.check_repack_table(self._repack_key)
+        now = dict(list(self.detector.named_parameters()) + list(self.detector.named_buffers()))
+        moved = [n for n, ptr in self._addresses if n not in now or now[n].data_ptr() != ptr]
+        if moved:
+            raise RuntimeError('%s.replay: %d parameter / buffer tensor(s) have another address than at capture (%s%s); the graph would read '
+                               'the old one: capture a new step' % (who, len(moved), ', '.join(moved[:3]), ', ...' if len(moved) > 3 else ''))
+        if img is not None:
+            if not torch.is_tensor(img) or tuple(img.shape) != tuple(self.img.shape) or img.dtype != self.img.dtype:
+                raise ValueError('%s.replay: img must be a %s tensor of shape %s, the captured step\'s' % (who, self.img.dtype, tuple(self.img.shape)))
+        n = self.img.shape[0] * self.img.shape[1]
+        if front_params is not None and len(front_params) != n:
+            raise ValueError('%s.replay: front_params for %d images, %d given' % (who, n, len(front_params)))
+        if img_metas is not None:
+            img_metas = [dict(m) for m in img_metas]
+            self._update_metas(img_metas)
+        self._refresh_head(gt_bboxes_list, gt_labels_list, img_metas, new_masks, noise)
+        if img is not None:
+            self.img.copy_(img, non_blocking=True)
+        self.front.upload(self.front.draw(n, self._Hp) if front_params is None else front_params, self.device)
         self._replay_graph()
         return self.losses
