@@ -1372,7 +1372,9 @@ int sbev_fpn_forward(int n_levels, const int32_t* chw, int64_t n, int num_outs, 
  * Definition (tests/fpn_bwd_cases.py restates it in fp64):
  *   scale   amax = max |gP_o| over all outputs, found on the device; (2^e, 2^-e) with 2^e amax in [2^W, 2^(W+1)), W =
  *           SBEV_FPN_GRAD_WINDOW_LOG2 = 3, e capped at 126, is written to the first 8 bytes of the workspace and read from there by every
- *           consumer: no host read, no synchronisation, the call can be captured.  amax zero or non-finite: e = 0.  Every gradient
+ *           consumer: no host read, no synchronisation, the call can be captured.  amax zero or non-finite: e = 0.  This is ONE rule
+ *           with sbev_resnet_backward's scale (one implementation; SBEV_RESNET_GRAD_WINDOW_LOG2 is the same constant).  Workspace head,
+ *           32-bit words: [0] 2^e  [1] 2^-e  (floats)  [2] amax bits  [3] ticket.  Every gradient
  *           operand is fp16 in the scaled domain: 2^12 of headroom below 65504, full fp16 precision down to 2^-18 amax.  A non-finite
  *           gP or an fp16 overflow of an intermediate travels as inf / NaN into the parameter gradients, never as a wrong finite value.
  *   G_l     = gP_l for l < L - 1; G_{L-1} = gP_{L-1} + gP_L + gP_{L+1} .. at the pixels with y, x multiples of 2, 4, .. (the extra
@@ -1486,7 +1488,9 @@ int sbev_resnet_forward(int depth, const int32_t* stage_blocks, int num_stages, 
  * activation: 1 where it is > 0, else 0 (a select, not a product: a masked inf is 0).
  *   scale   amax = max |gP_k| over grad_outs, found on the device; (2^e, 2^-e) with 2^e amax in [2^W, 2^(W+1)), W =
  *           SBEV_RESNET_GRAD_WINDOW_LOG2 = 3, e capped at 126, e = 0 for a zero or non-finite amax; the pair is written to the first 8
- *           bytes of the workspace and read from there by every consumer: no host read, no synchronisation.  A non-finite gP or an fp16
+ *           bytes of the workspace and read from there by every consumer: no host read, no synchronisation.  ONE rule with
+ *           sbev_fpn_backward's scale (one implementation, the same workspace head; SBEV_FPN_GRAD_WINDOW_LOG2 is the same constant).
+ *           A non-finite gP or an fp16
  *           overflow of an intermediate travels as inf / NaN into the parameter gradients, never as a wrong finite value.
  *   blocks, last to first, in the scaled domain, G_out the fp32 gradient of a block's out:
  *     g3 = fp16(G_out [out > 0])                        (the gradient at conv3's output and at r)

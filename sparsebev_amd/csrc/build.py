@@ -47,6 +47,7 @@ UNITS = {
     'image_geom.hip': [],                # integer arithmetic only: no float flags
     'fpn.hip': [],                       # the FPN neck: fp16 MFMA, fp32 accumulate; single fp32 multiplies and adds, nothing to contract
     'fpn_bwd.hip': [],                   # the neck's backward: the same; its fixed-order fp32 sums have no multiply beside them
+    'grad_scale.hip': [],                # the scaled domain of both dense backwards: integer max and exponent arithmetic, no fp multiply
     # the ResNet backbone: the BatchNorm fold is DEFINED by individually rounded fp32 operations (tests restate it bit for bit)
     'resnet.hip': ['-ffp-contract=off'],
     # its backward: the BatchNorm fold's backward is defined the same way (individually rounded fp32 operations, a fixed sum order)

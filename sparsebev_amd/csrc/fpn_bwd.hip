@@ -1,12 +1,13 @@
 // The FPN neck's backward (include/sbev_hip.h: sbev_fpn_backward) on v_mfma_f32_32x32x16_f16: from the output gradients gP_o to the
 // gradients of the inputs, the 1x1 and 3x3 weights and the biases.  Every gradient operand goes to the matrix core as fp16 in a SCALED
-// domain: one launch finds amax = max |gP_o| and writes (2^e, 2^-e) with 2^e amax in [2^3, 2^4) to device memory; every consumer reads
-// the pair from there (no host read: the call can be captured), fp32 results are multiplied by 2^-e on the way out.
+// domain (grad_scale.hip, shared with the backbone's backward): amax = max |gP_o| is found on the device and (2^e, 2^-e) with 2^e amax in
+// [2^3, 2^4) written to the head of the workspace; every consumer reads the pair from there (no host read: the call can be captured),
+// fp32 results are multiplied by 2^-e on the way out.
 //
-// Launches for L levels (plus one tiny launch that clears the amax word and the ticket -- a kernel, not a memset node: a captured 16-byte
-// memset wrote stale bytes from the second replay of a graph on, resnet_bwd.hip met the same): 4 L + 1, or 5 L + 1 with input gradients.
-//   1            fpn_amax_kernel: amax over every output gradient (integer max of the absolute bit patterns: order-free), the last
-//                workgroup (a ticket) writes the pair.  A zero or non-finite amax gives e = 0: an inf or NaN then travels as it is.
+// Launches for L levels (plus grad_scale.hip's tiny launch that clears the amax word and the ticket): 4 L + 1, or 5 L + 1 with input
+// gradients.
+//   1            grad_scale_amax_kernel: amax over every output gradient, the last workgroup writes the pair.  A zero or non-finite
+//                amax gives e = 0: an inf or NaN then travels as it is.
 //   1            fpn_dgrad3_kernel: D_l = conv3x3(fp16(2^e G_l), W3_l'), the forward's convolution kernel shape (same tile table, same
 //                fragment-ordered weight image, of the flipped and transposed weights).  G_l is staged from gP_l on the way into LDS:
 //                fp32 (or fp16) -> + the extra levels' gradients at the pixels they were taken from (last level) -> x 2^e -> fp16.
@@ -30,68 +31,6 @@
 namespace {
 
 using namespace sbev_fpn;
-
-typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
-
-constexpr int kWindowLog2 = SBEV_FPN_GRAD_WINDOW_LOG2;      // 2^e amax in [2^3, 2^4)
-constexpr int kMaxSlabs = 16;            // slabs per level at most
-constexpr int kMinSlab = 512;            // pixels per slab at least
-constexpr int kSlabRound = 256;          // a slab length is a multiple of this
-constexpr int kWK = 32;                  // pixels per K step of the weight gradients
-constexpr int kWPitch = 160;             // halves per LDS row of a weight-gradient operand tile: 128 + 32
-
-// ---------------------------------------------------------------- the scale
-struct AmaxArgs {
-    const void* g[kMaxOut];
-    long long count[kMaxOut];            // elements (a multiple of 8)
-    unsigned* ws;                        // [0] 2^e  [1] 2^-e  (floats)  [2] amax bits  [3] ticket
-    int n, f32;
-};
-
-// the four head words (pair, amax bits, ticket) back to zero before every amax
-__global__ __launch_bounds__(64) void fpn_clear_kernel(unsigned* ws) {
-    if (threadIdx.x < 4) ws[threadIdx.x] = 0u;
-}
-
-__global__ __launch_bounds__(256) void fpn_amax_kernel(const AmaxArgs a) {
-    __shared__ unsigned smax;
-    if (threadIdx.x == 0) smax = 0u;
-    __syncthreads();
-    unsigned m = 0u;
-    const long long stride = (long long)gridDim.x * 256, t0 = (long long)blockIdx.x * 256 + threadIdx.x;
-    for (int o = 0; o < a.n; ++o) {
-        const uint4* p = static_cast<const uint4*>(a.g[o]);
-        const long long nv = a.f32 ? a.count[o] / 4 : a.count[o] / 8;
-        for (long long i = t0; i < nv; i += stride) {
-            const uint4 v = p[i];
-            if (a.f32) {
-                m = max(m, max(max(v.x & 0x7fffffffu, v.y & 0x7fffffffu), max(v.z & 0x7fffffffu, v.w & 0x7fffffffu)));
-            } else {
-                const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned h = max(w[j] & 0x7fffu, (w[j] >> 16) & 0x7fffu);
-                    m = max(m, __float_as_uint((float)__builtin_bit_cast(_Float16, (unsigned short)h)));
-                }
-            }
-        }
-    }
-    atomicMax(&smax, m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicMax(a.ws + 2, smax);
-        __threadfence();
-        const unsigned ticket = atomicAdd(a.ws + 3, 1u);
-        if (ticket == gridDim.x - 1) {
-            __threadfence();
-            const unsigned bits = atomicMax(a.ws + 2, 0u);
-            int e = 0;
-            if (bits != 0u && bits < 0x7f800000u) e = min(kWindowLog2 - ilogbf(__uint_as_float(bits)), 126);
-            a.ws[0] = (unsigned)(127 + e) << 23;
-            a.ws[1] = (unsigned)(127 - e) << 23;
-        }
-    }
-}
 
 // ---------------------------------------------------------------- staging of the gradient operand G_l
 template <bool F32>
@@ -338,19 +277,6 @@ struct WgradArgs {
     int pixels, H, W, N, slab_len, n_extra;
 };
 
-// operand of v_mfma_f32_32x32x16_f16 from a [pixel][channel] LDS tile: lane (fr, fh) gets channel col0 + fr, pixels k0 + 8 fh .. + 8.
-// Two transposed reads of 4 pixels x 16 channels per 16-lane group; lane 4 q + pp of a group addresses pixel q, channels 4 pp .. + 4.
-__device__ __forceinline__ f16x8 tr_frag(const _Float16* tile, int k0, int col0, int lane) {
-    const int grp = lane >> 4, idx = lane & 15;
-    const _Float16* p = tile + (k0 + 8 * (grp >> 1) + (idx >> 2)) * kWPitch + col0 + 16 * (grp & 1) + 4 * (idx & 3);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * kWPitch));
-    typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(f16x8, v);
-}
-
 template <int MODE, bool F32>
 __global__ __launch_bounds__(256) void fpn_wgrad_kernel(const WgradArgs a) {
     constexpr bool AF32 = MODE == 0 && F32, BF32 = MODE == 1 && F32;
@@ -526,8 +452,6 @@ struct BwdPlan {
     int launches;
 };
 
-long long round_up(long long v, long long m) { return (v + m - 1) / m * m; }
-
 int make_bwd_plan(const char* who, int n_levels, const int32_t* chw, int64_t n, int num_outs, int want_input_grads, BwdPlan* b) {
     if (int st = make_plan(who, n_levels, chw, n, num_outs, &b->f)) return st;
     SBEV_REQUIRE(want_input_grads == 0 || want_input_grads == 1, "%s: want_input_grads=%d (0 or 1)", who, want_input_grads);
@@ -535,9 +459,7 @@ int make_bwd_plan(const char* who, int n_levels, const int32_t* chw, int64_t n, 
     long long part = 0;
     for (int l = 0; l < kMaxIn; ++l) b->slabs[l] = b->slab_len[l] = 0, b->part_stride[l] = 0;
     for (int l = 0; l < p.L; ++l) {
-        const long long len = std::max<long long>(kMinSlab, round_up((p.pixels[l] + kMaxSlabs - 1) / kMaxSlabs, kSlabRound));
-        b->slab_len[l] = (int)len;
-        b->slabs[l] = (int)((p.pixels[l] + len - 1) / len);
+        slab_rule(p.pixels[l], &b->slabs[l], &b->slab_len[l]);
         b->part_stride[l] = 9LL * kOut * kOut + (long long)kOut * p.Cin[l] + 2 * kOut;
         part = std::max(part, b->slabs[l] * b->part_stride[l]);
     }
@@ -632,23 +554,11 @@ extern "C" int sbev_fpn_backward(int n_levels, const int32_t* chw, int64_t n, in
     const bool gf32 = g_dtype == SBEV_F32, xf32 = in_dtype == SBEV_F32;
     auto d_of = [&](int l) { return dbuf + (p.base[l] - p.base[1 < p.L ? 1 : 0]) * kOut; };
 
-    hipLaunchKernelGGL(fpn_clear_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned*>(ws));
-    if (int st = sbev::check_launch(who)) return st;          // the scale words are cleared or nothing else is enqueued
     {
-        AmaxArgs a;
-        long long most = 0;
-        for (int o = 0; o < kMaxOut; ++o) {
-            a.g[o] = o < num_outs ? grad_outs[o] : nullptr;
-            a.count[o] = 0;
-            if (o < p.L) a.count[o] = p.pixels[o] * kOut;
-            else if (o < num_outs) a.count[o] = (long long)n * p.eH[o - p.L + 1] * p.eW[o - p.L + 1] * kOut;
-            most = std::max(most, a.count[o]);
-        }
-        a.ws = reinterpret_cast<unsigned*>(ws);
-        a.n = num_outs;
-        a.f32 = gf32;
-        const long long blocks = std::min<long long>(1024, std::max<long long>(1, most / (256 * 8 * 4)));
-        hipLaunchKernelGGL(fpn_amax_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
+        long long count[kMaxOut];
+        for (int o = 0; o < num_outs; ++o)
+            count[o] = o < p.L ? p.pixels[o] * kOut : (long long)n * p.eH[o - p.L + 1] * p.eW[o - p.L + 1] * kOut;
+        if (int st = sbev::launch_grad_scale(who, grad_outs, count, num_outs, gf32, ws, s)) return st;
     }
     {
         DgradArgs c;

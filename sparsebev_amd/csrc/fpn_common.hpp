@@ -1,7 +1,10 @@
 // What the FPN neck's forward (fpn.hip) and backward (fpn_bwd.hip) share: the staging of a pixel-major A operand through LDS, the
 // 2 x 2 MFMA step of an 8-wave workgroup over a fragment-ordered weight image, the accumulator's row map, the nearest rule, and the
-// host plan of the levels.  Everything is internal to a translation unit (static / inline): the kernels of each file stay its own.
+// host plan of the levels -- and what the neck's and the backbone's backward (resnet_bwd.hip) share beyond that: the slab rule of the
+// weight gradients and their transposed LDS operand read.  Everything is internal to a translation unit (static / inline): the kernels
+// of each file stay its own.
 #pragma once
+#include <algorithm>
 #include <cmath>
 
 #include "sbev_common.hpp"
@@ -149,5 +152,38 @@ inline int make_plan(const char* who, int n_levels, const int32_t* chw, int64_t 
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline long long round_up(long long v, long long m) { return (v + m - 1) / m * m; }
+
+// ---------------------------------------------------------------- weight gradients (fpn_bwd.hip, resnet_bwd.hip): slabs and operand tiles
+// The reduction over a convolution's output pixels is split into slabs (grid.y), one fp32 partial per slab, folded in slab order:
+// slab_len = max(kMinSlab, ceil(pixels / kMaxSlabs) rounded up to kSlabRound) -- part of both backward passes' definition
+// (include/sbev_hip.h: sbev_fpn_backward_plan, sbev_resnet_backward).
+constexpr int kMaxSlabs = 16;            // slabs per level / layer at most
+constexpr int kMinSlab = 512;            // pixels per slab at least
+constexpr int kSlabRound = 256;          // a slab length is a multiple of this
+
+inline void slab_rule(long long pixels, int* slabs, int* slab_len) {
+    const long long len = std::max<long long>(kMinSlab, round_up((pixels + kMaxSlabs - 1) / kMaxSlabs, kSlabRound));
+    *slab_len = (int)len;
+    *slabs = (int)((pixels + len - 1) / len);
+}
+
+constexpr int kWK = 32;                  // pixels per K step of the weight gradients
+constexpr int kWPitch = 160;             // halves per LDS row of a weight-gradient operand tile: 128 + 32
+
+typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
+
+// operand of v_mfma_f32_32x32x16_f16 from a [pixel][channel] LDS tile: lane (fr, fh) gets channel col0 + fr, pixels k0 + 8 fh .. + 8.
+// Two transposed reads of 4 pixels x 16 channels per 16-lane group; lane 4 q + pp of a group addresses pixel q, channels 4 pp .. + 4.
+__device__ __forceinline__ f16x8 tr_frag(const _Float16* tile, int k0, int col0, int lane) {
+    const int grp = lane >> 4, idx = lane & 15;
+    const _Float16* p = tile + (k0 + 8 * (grp >> 1) + (idx >> 2)) * kWPitch + col0 + 16 * (grp & 1) + 4 * (idx & 3);
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * kWPitch));
+    typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
+    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(f16x8, v);
+}
 
 }  // namespace sbev_fpn

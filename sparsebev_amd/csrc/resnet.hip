@@ -350,7 +350,7 @@ __global__ __launch_bounds__(256) void resnet_fold_pack_kernel(const FoldArgs a)
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.frags) return;
     if (i < a.Cout) {
-        const float s = a.gamma[i] / sqrtf(a.var[i] + a.eps);
+        const float s = sbev_resnet::bn_fold_scale(a.gamma[i], a.var[i], a.eps);
         a.bias[i] = a.beta[i] - a.mean[i] * s;
     }
     const int NF = a.Cout / 32, KS = a.Kpad / 16;
@@ -361,22 +361,25 @@ __global__ __launch_bounds__(256) void resnet_fold_pack_kernel(const FoldArgs a)
     const int ks = (int)(rest % KS), tap = (int)(rest / KS);
     const int co = 64 * (nt >> 1) + 2 * (lane & 31) + (nt & 1);
     const int k0 = 16 * ks + 8 * (lane >> 5);
-    const float s = a.gamma[co] / sqrtf(a.var[co] + a.eps);
+    const float s = sbev_resnet::bn_fold_scale(a.gamma[co], a.var[co], a.eps);
+    float p[8];      // the eight products first, their second rounding afterwards: all loads in flight (resnet_train.hpp: bn_fold_round)
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int k = k0 + t;
+        p[t] = 0.f;
+        if (k < a.Cin) {
+            const size_t e = ((size_t)co * a.Cin + k) * a.taps + tap;
+            const float w = a.f32 ? static_cast<const float*>(a.w)[e] : (float)static_cast<const _Float16*>(a.w)[e];
+            p[t] = w * s;
+        }
+    }
     unsigned h[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        float v[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int k = k0 + 2 * j + t;
-            v[t] = 0.f;
-            if (k < a.Cin) {
-                const size_t e = ((size_t)co * a.Cin + k) * a.taps + tap;
-                const float w = a.f32 ? static_cast<const float*>(a.w)[e] : (float)static_cast<const _Float16*>(a.w)[e];
-                v[t] = w * s;
-            }
-        }
-        h[j] = pack_h2(v[0], v[1]);
+        f16x2 v;
+        v.x = sbev_resnet::bn_fold_round(p[2 * j]);
+        v.y = sbev_resnet::bn_fold_round(p[2 * j + 1]);
+        h[j] = __builtin_bit_cast(unsigned, v);
     }
     a.dst[i] = make_uint4(h[0], h[1], h[2], h[3]);
 }

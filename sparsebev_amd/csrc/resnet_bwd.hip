@@ -1,10 +1,10 @@
 // The ResNet backbone's backward (include/sbev_hip.h: sbev_resnet_backward) on v_mfma_f32_32x32x16_f16: from the gradients of the stage
 // maps to the gradients of the convolution weights and of the BatchNorm gamma / beta of the trainable stages.  The forward is
 // resnet.hip's with every activation from the last frozen stage's output onward kept (sbev_resnet_forward_train).  Every gradient
-// operand goes to the matrix core as fp16 in a SCALED domain, fpn_bwd.hip's rule: one launch finds amax = max |gP_k| and writes
-// (2^e, 2^-e) with 2^e amax in [2^3, 2^4) to the head of the workspace; every consumer reads the pair from there.
+// operand goes to the matrix core as fp16 in a SCALED domain (grad_scale.hip, shared with the neck's backward): amax = max |gP_k| is found
+// on the device and (2^e, 2^-e) with 2^e amax in [2^3, 2^4) written to the head of the workspace; every consumer reads the pair from there.
 //
-// Launches: clear (the amax word and its ticket), amax, seed, then per block, last block first,
+// Launches: grad_scale.hip's clear (the amax word and its ticket) and amax, seed, then per block, last block first,
 //   rb_wgrad + rb_fold_bwd   conv3: A = g3, B = a2
 //   rb_dgrad                 g2 = fp16(dgrad(g3, w3') [a2 > 0])
 //   rb_wgrad + rb_fold_bwd   conv2: A = g2, B = a1 read at the block's stride, nine taps
@@ -14,8 +14,9 @@
 //   rb_dgrad                 the previous block's g3 = fp16((acc + float(g3)) [+ 2^e gP] masked by x > 0); on a first block the
 //                            downsample's products continue conv1's accumulation (one K loop over [g1 | g3 at the even pixels])
 // rb_dgrad is resnet.hip's implicit GEMM (128 output pixels x 64 WN channels per workgroup, K in chunks of 64 channels of one tap) over
-// the transposed / flipped fragment image of w'; rb_wgrad is fpn_bwd.hip's pixel-major product (32 pixels per K step staged row-major,
-// read back transposed by ds_read_b64_tr_b16) with both channel counts and the input stride as arguments.
+// the transposed / flipped fragment image of w'; rb_wgrad is the pixel-major product of the neck's weight gradients (32 pixels per K step
+// staged row-major, read back transposed by fpn_common.hpp's tr_frag; the same slab rule) with both channel counts and the input stride
+// as arguments.
 //
 // Who writes what: every stored element has one owning lane; nothing is read-modify-written except the amax word (integer max) and its
 // ticket; slab partials fold in slab order.  Bit-reproducible.  Built with -ffp-contract=off: the fold backward is defined by
@@ -28,70 +29,8 @@ namespace {
 using namespace sbev_fpn;
 using namespace sbev_resnet;
 
-typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
-
-constexpr int kWindowLog2 = SBEV_RESNET_GRAD_WINDOW_LOG2;
 constexpr int kKC = 64, kPitch = kKC + 8;
-constexpr int kMaxSlabs = 16;            // slabs per layer at most
-constexpr int kMinSlab = 512;            // pixels per slab at least
-constexpr int kSlabRound = 256;          // a slab length is a multiple of this
-constexpr int kWK = 32;                  // pixels per K step of the weight gradients
-constexpr int kWPitch = 160;             // halves per LDS row of a weight-gradient operand tile: 128 + 32
 constexpr int kMaxLayers = SBEV_RESNET_MAX_LAYERS;
-
-// ---------------------------------------------------------------- the scale (fpn_bwd.hip's rule)
-struct AmaxArgs {
-    const void* g[4];
-    long long count[4];                  // elements (a multiple of 8)
-    unsigned* ws;                        // [0] 2^e  [1] 2^-e  (floats)  [2] amax bits  [3] ticket
-    int n, f32;
-};
-
-// the four head words back to zero before every amax.  A launch of its own, not a memset node: a captured 16-byte memset wrote stale
-// bytes from the second replay of a graph on, a kernel's stores replay like any other
-__global__ __launch_bounds__(64) void rb_clear_kernel(unsigned* ws) {
-    if (threadIdx.x < 4) ws[threadIdx.x] = 0u;
-}
-
-__global__ __launch_bounds__(256) void rb_amax_kernel(const AmaxArgs a) {
-    __shared__ unsigned smax;
-    if (threadIdx.x == 0) smax = 0u;
-    __syncthreads();
-    unsigned m = 0u;
-    const long long stride = (long long)gridDim.x * 256, t0 = (long long)blockIdx.x * 256 + threadIdx.x;
-    for (int o = 0; o < a.n; ++o) {
-        const uint4* p = static_cast<const uint4*>(a.g[o]);
-        const long long nv = a.f32 ? a.count[o] / 4 : a.count[o] / 8;
-        for (long long i = t0; i < nv; i += stride) {
-            const uint4 v = p[i];
-            if (a.f32) {
-                m = max(m, max(max(v.x & 0x7fffffffu, v.y & 0x7fffffffu), max(v.z & 0x7fffffffu, v.w & 0x7fffffffu)));
-            } else {
-                const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned h = max(w[j] & 0x7fffu, (w[j] >> 16) & 0x7fffu);
-                    m = max(m, __float_as_uint((float)__builtin_bit_cast(_Float16, (unsigned short)h)));
-                }
-            }
-        }
-    }
-    atomicMax(&smax, m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicMax(a.ws + 2, smax);
-        __threadfence();
-        const unsigned ticket = atomicAdd(a.ws + 3, 1u);
-        if (ticket == gridDim.x - 1) {
-            __threadfence();
-            const unsigned bits = atomicMax(a.ws + 2, 0u);
-            int e = 0;
-            if (bits != 0u && bits < 0x7f800000u) e = min(kWindowLog2 - ilogbf(__uint_as_float(bits)), 126);
-            a.ws[0] = (unsigned)(127 + e) << 23;
-            a.ws[1] = (unsigned)(127 - e) << 23;
-        }
-    }
-}
 
 // ---------------------------------------------------------------- the last block's g3 = fp16(2^e gP [out > 0]), or zeros without a gP
 struct SeedArgs {
@@ -269,18 +208,6 @@ struct WgradArgs {
     int pixels, Cout, Cin, taps, stride, H, W, h, w, slab_len, TI, TJ;
 };
 
-// operand of v_mfma_f32_32x32x16_f16 from a [pixel][channel] LDS tile (fpn_bwd.hip: tr_frag)
-__device__ __forceinline__ f16x8 tr_frag(const _Float16* tile, int k0, int col0, int lane) {
-    const int grp = lane >> 4, idx = lane & 15;
-    const _Float16* p = tile + (k0 + 8 * (grp >> 1) + (idx >> 2)) * kWPitch + col0 + 16 * (grp & 1) + 4 * (idx & 3);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * kWPitch));
-    typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
-    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(f16x8, v);
-}
-
 __global__ __launch_bounds__(256) void rb_wgrad_kernel(const WgradArgs a) {
     __shared__ __attribute__((aligned(16))) _Float16 sA[kWK * kWPitch];
     __shared__ __attribute__((aligned(16))) _Float16 sB[kWK * kWPitch];
@@ -370,8 +297,8 @@ struct FoldBwdArgs {
 __global__ __launch_bounds__(256) void rb_fold_bwd_kernel(const FoldBwdArgs a) {
     __shared__ float red[256];
     const int co = (int)blockIdx.x, tid = (int)threadIdx.x;
-    const float root = sqrtf(a.var[co] + a.eps);
-    const float s = a.gamma[co] / root;
+    const float root = sqrtf(a.var[co] + a.eps);          // bn_fold_scale's denominator
+    const float s = bn_fold_scale(a.gamma[co], a.var[co], a.eps);
     const float down = a.scale != nullptr ? a.scale[1] : 1.f;
     const int K = a.Cin * a.taps;
     float dot = 0.f;
@@ -426,32 +353,28 @@ __global__ __launch_bounds__(256) void rb_pack_bwd_kernel(const PackBwdArgs a) {
     const int ci = 64 * (nt >> 1) + 2 * (lane & 31) + (nt & 1);
     const int k0 = 16 * ks + 8 * (lane >> 5);
     const int tap = a.taps == 9 ? 8 - tapp : 0;
+    float p[8];      // the eight products first, their second rounding afterwards: all gathers in flight (resnet_train.hpp: bn_fold_round)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int co = k0 + k;
+        const float s = bn_fold_scale(a.gamma[co], a.var[co], a.eps);
+        const size_t e = ((size_t)co * a.Cin + ci) * a.taps + tap;
+        const float w = a.f32 ? static_cast<const float*>(a.w)[e] : (float)static_cast<const _Float16*>(a.w)[e];
+        p[k] = w * s;
+    }
     unsigned h[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        float v[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int co = k0 + 2 * j + t;
-            const float s = a.gamma[co] / sqrtf(a.var[co] + a.eps);       // the forward's fold: the same w' bits
-            const size_t e = ((size_t)co * a.Cin + ci) * a.taps + tap;
-            const float w = a.f32 ? static_cast<const float*>(a.w)[e] : (float)static_cast<const _Float16*>(a.w)[e];
-            v[t] = w * s;
-        }
-        h[j] = pack_h2(v[0], v[1]);
+        f16x2 v;
+        v.x = bn_fold_round(p[2 * j]);      // the forward's fold: the same w' bits
+        v.y = bn_fold_round(p[2 * j + 1]);
+        h[j] = __builtin_bit_cast(unsigned, v);
     }
     a.dst[i] = make_uint4(h[0], h[1], h[2], h[3]);
 }
 
 // ---------------------------------------------------------------- the plan (pure host)
-long long round_up(long long v, long long m) { return (v + m - 1) / m * m; }
 int out_side(int in, int stride) { return (in - 1) / stride + 1; }
-
-void slab_rule(long long pixels, int* slabs, int* slab_len) {
-    const long long len = std::max<long long>(kMinSlab, round_up((pixels + kMaxSlabs - 1) / kMaxSlabs, kSlabRound));
-    *slab_len = (int)len;
-    *slabs = (int)((pixels + len - 1) / len);
-}
 
 struct BwdPlan {
     TrainNet t;
@@ -731,20 +654,10 @@ extern "C" int sbev_resnet_backward(int depth, const int32_t* stage_blocks, int 
         launch_dgrad(pick_col_tile((a.rows + kTileM - 1) / kTileM, a.N), a, s);
     };
 
-    hipLaunchKernelGGL(rb_clear_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned*>(ws));
     {
-        AmaxArgs a;
-        long long most = 0;
-        for (int k = 0; k < 4; ++k) {
-            a.g[k] = k < n_out ? grad_outs[k] : nullptr;
-            a.count[k] = k < n_out ? t.layer[t.out_layer[k]].rows * t.layer[t.out_layer[k]].Cout : 0;
-            most = std::max(most, a.count[k]);
-        }
-        a.ws = reinterpret_cast<unsigned*>(ws);
-        a.n = n_out;
-        a.f32 = gf32;
-        const long long blocks = std::min<long long>(1024, std::max<long long>(1, most / (256 * 8 * 4)));
-        hipLaunchKernelGGL(rb_amax_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
+        long long count[4];
+        for (int k = 0; k < n_out; ++k) count[k] = t.layer[t.out_layer[k]].rows * t.layer[t.out_layer[k]].Cout;
+        if (int st = sbev::launch_grad_scale(who, grad_outs, count, n_out, gf32, ws, s)) return st;
     }
     int cur = 0;      // gbuf[cur] holds the g3 of the block being walked
     {

@@ -3,9 +3,9 @@
 // WHOLE net by ONE launch that takes no host array: a device table holds every convolution's source pointers, shape and offsets, so the
 // launch records into a graph and a replay folds the weights as they are then (a training step after an optimizer update).
 //
-// Arithmetic: the existing entries', bit for bit (this unit is built with -ffp-contract=off like theirs): s = gamma / sqrtf(var + eps),
-// b' = beta - mean * s, w' = fp16(fp32(w * s)), every operation rounded on its own (the product to fp32 first, then to fp16: two roundings, as
-// the pack kernels' v_mul_f32 + v_cvt_pk_f16_f32 do).  w' is computed ONCE per element and feeds both images.
+// Arithmetic: the per-layer entries', bit for bit (this unit is built with -ffp-contract=off like theirs): s = gamma / sqrtf(var + eps),
+// b' = beta - mean * s, w' = fp16(fp32(w * s)), every operation rounded on its own -- resnet_train.hpp's bn_fold_scale and bn_fold_weight,
+// which the pack kernels of resnet.hip and resnet_bwd.hip use too.  w' is computed ONCE per element and feeds both images.
 //
 // Work item = a tile of 32 output channels x 64 reduction indices (input channels; the stem: 64 of its 147 flat (c, ky, kx) indices, padded
 // with zeros to 160) x all taps of one convolution.  The workgroup (256 threads)
@@ -51,15 +51,12 @@ __device__ __forceinline__ void load_tile(const void* w, const float* sc, _Float
 #pragma unroll
         for (int i = 0; i < TAPS; ++i) {
             const int e = lane + 64 * i;
-            float v = 0.f;
+            _Float16 v = (_Float16)0.f;
             if (e < row_len) {
                 const float x = F32 ? static_cast<const float*>(w)[base + e] : (float)static_cast<const _Float16*>(w)[base + e];
-                v = x * s;
-                // the product exists as an fp32 value, rounded, before it is rounded to fp16 -- as in the two pack kernels.  Without the
-                // barrier the backend folds multiply and conversion into v_fma_mixlo_f16, ONE rounding: other bits in 1 of ~10^4 elements
-                asm volatile("" : "+v"(v));
+                v = sbev_resnet::bn_fold_weight(x, s);
             }
-            tile[r * pitch + (e % TAPS) * kK + e / TAPS] = (_Float16)v;
+            tile[r * pitch + (e % TAPS) * kK + e / TAPS] = v;
         }
     }
 }
@@ -127,7 +124,7 @@ __global__ __launch_bounds__(kThreads256) void resnet_repack_kernel(const long l
         const int nks = min(4, Kpad / 16 - kb * 4);            // 16-wide K steps of this tile (the stem's last: 2)
         const float* gamma = reinterpret_cast<const float*>(L[W_GAMMA]);
         const float* var = reinterpret_cast<const float*>(L[W_VAR]);
-        if (tid < kCo) sc[tid] = gamma[co0 + tid] / sqrtf(var[co0 + tid] + eps);
+        if (tid < kCo) sc[tid] = sbev_resnet::bn_fold_scale(gamma[co0 + tid], var[co0 + tid], eps);
         __syncthreads();
         if (kb == 0 && tid < kCo / 4) {
             const float* beta = reinterpret_cast<const float*>(L[W_BETA]);

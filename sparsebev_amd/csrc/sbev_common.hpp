@@ -48,6 +48,12 @@ int launch_splitk_slabs(const float* X, const float* W, int64_t M, int N, int K,
 int launch_splitk_slabs_bf16x3(const float* X, const uint16_t* W2, int64_t M, int N, int K, int64_t ldx, int splits,
                                float* workspace, int* used, hipStream_t s);
 
+// grad_scale.hip: the scaled domain of the neck's and the backbone's backward.  Two launches on `s`: the four 32-bit words at `ws_head`
+// ([0] 2^e  [1] 2^-e  [2] amax bits  [3] ticket) are cleared -- that launch is checked before anything else is enqueued -- then amax over
+// the n tensors grads[i] of counts[i] elements (a multiple of 8; all fp32 or all fp16, 16-byte aligned) writes the pair.  Returns the status.
+constexpr int kGradScaleMaxTensors = SBEV_FPN_MAX_OUT > 4 ? SBEV_FPN_MAX_OUT : 4;      // the neck's outputs, the backbone's four stage maps
+int launch_grad_scale(const char* who, const void* const* grads, const long long* counts, int n, bool f32, void* ws_head, hipStream_t s);
+
 // Every process-wide switch that influences what a decoder step enqueues, read ONCE per step (decoder.hip: read_switches) and handed
 // down from there.  sbev_decoder_switches() copies this struct out field by field IN THIS ORDER (include/sbev_hip.h lists it), so a
 // switch added here is part of every caller's graph key: int32_t fields only.

@@ -355,19 +355,24 @@ def in_step_images():
     return _STEP_IMAGES is not None
 
 
+def step_image(kind, tensors, make):
+    """Inside a step_images() scope: the scope's one derived image ``kind`` of ``tensors``, by ``make()`` at the first call"""
+    scope = _STEP_IMAGES
+    key = (kind,) + tuple(id(t) for t in tensors)
+    hit = scope.get(key)
+    if hit is not None and all(a is b for a, b in zip(hit[0], tensors)):
+        return hit[1]
+    out = make()
+    scope[key] = (tensors, out)       # keeps the sources alive for the step: a recycled id cannot match
+    return out
+
+
 def derived_image(cache_ok, kind, tensors, make, lookup, store):
     """One derived image of ``tensors`` by ``make()``: from the step's scope inside step_images(); from the process-wide cache
     (``lookup()`` -> image or None, ``store(image)``) in eager code; and while the current stream is capturing outside a scope the caches
     are neither read nor filled -- an image cached at capture would be read by every replay, whatever the weights have become."""
-    scope = _STEP_IMAGES
-    if scope is not None:
-        key = (kind,) + tuple(id(t) for t in tensors)
-        hit = scope.get(key)
-        if hit is not None and all(a is b for a, b in zip(hit[0], tensors)):
-            return hit[1]
-        out = make()
-        scope[key] = (tensors, out)       # keeps the sources alive for the step: a recycled id cannot match
-        return out
+    if _STEP_IMAGES is not None:
+        return step_image(kind, tensors, make)
     if not cache_ok or (tensors[0].is_cuda and torch.cuda.is_current_stream_capturing()):
         return make()
     out = lookup()
@@ -375,6 +380,55 @@ def derived_image(cache_ok, kind, tensors, make, lookup, store):
         out = make()
         store(out)
     return out
+
+
+class WeightImage:
+    """A module's packed weight image at a fixed address (FPNNeck's and ResNetBackbone's forward and backward packs).  ``key`` is
+    ``(data_ptr, _version)`` of every source tensor at the last pack (after ``extra``), None before the first; ``image`` the tensor.
+    ``kind`` names the image in a step_images() scope, ``refusal`` is the message of a stale key under a capture."""
+
+    def __init__(self, kind, refusal):
+        self.kind, self.refusal = kind, refusal
+        self.key = self.image = None
+
+    def get(self, tensors, make, extra=(), in_step=None):
+        """The image of ``tensors``.  Inside step_images(): the scope's own (``in_step()``, else ``make(None)`` once per scope), the
+        cache neither read nor filled.  Otherwise the SAME tensor object while the key stands; under a capture a stale key is refused;
+        else ``make(dest)`` repacks -- into the old image (``make`` may decline a ``dest`` it cannot use), so the image keeps its
+        address and an already captured forward reads the new weights; ``dest`` is None at first and after a change of device."""
+        if _STEP_IMAGES is not None:
+            return in_step() if in_step is not None else step_image(self.kind, tuple(tensors), lambda: make(None))
+        key = tuple(extra) + tuple((t.data_ptr(), t._version) for t in tensors)
+        if key == self.key:
+            return self.image
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(self.refusal)
+        if self.image is not None and self.image.device != tensors[0].device:
+            self.image = None
+        self.image = make(self.image)
+        self.key = key
+        return self.image
+
+
+def ptr_array(tensors):
+    """void* [max(len, 1)] of the tensors' addresses for a C entry's pointer list; None: a null entry"""
+    return (ctypes.c_void_p * max(len(tensors), 1))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def channels_last_out(who, out, shapes, dev, dtype=None):
+    """``out=`` of a dense module's forward, checked: a list of len(shapes) tensors [n, C, h, w] of ``shapes`` in channels-last memory
+    on ``dev``, all of ``dtype`` (None: of the first one's, fp16 or fp32).  Returns (the list, the dtype)."""
+    out = list(out)
+    if len(out) != len(shapes):
+        raise ValueError('%s: out must list %d tensors' % (who, len(shapes)))
+    if dtype is None:
+        dtype = out[0].dtype
+        if dtype not in (torch.float16, torch.float32):
+            raise TypeError('%s: out must be fp16 or fp32' % who)
+    for o, s in zip(out, shapes):
+        if tuple(o.shape) != s or o.dtype != dtype or o.device != dev or (o.numel() and not o.permute(0, 2, 3, 1).is_contiguous()):
+            raise ValueError('%s: out must be %s tensors of shape %s in channels-last memory on %s' % (who, dtype, s, dev))
+    return out, dtype
 
 
 def _cat_rows(*tensors):

@@ -50,10 +50,6 @@ def plan(chw, n, num_outs):
                 extra=[(v[10 + 2 * e], v[11 + 2 * e]) for e in range(v[9])])
 
 
-def _vp_array(ptrs):
-    return (ctypes.c_void_p * len(ptrs))(*ptrs)
-
-
 def children(in_size, out_size):
     """The preimage of ``nearest_index(in_size, out_size)``: (start, stop) int64 arrays [in_size]; destination indices start[s] ..
     stop[s] - 1 read source index s (the rule is monotone, so a preimage is a range; it is empty where no destination reads s).  The
@@ -87,7 +83,7 @@ def backward_raw(chw, n, num_outs, inputs, merged, grad_outs, pack_bwd, workspac
     dev = workspace.device
     with torch.cuda.device(dev):
         s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if stream is None else stream
-        ptrs = lambda ts: _vp_array([None if t is None else t.data_ptr() for t in ts])
+        ptrs = dense.ptr_array
         _lib.check(_lib.load().sbev_fpn_backward(
             L, flat, int(n), int(num_outs), ptrs(inputs), _DTYPES[inputs[0].dtype], ctypes.c_void_p(merged.data_ptr()), ptrs(grad_outs),
             _DTYPES[grad_outs[0].dtype], ctypes.c_void_p(pack_bwd.data_ptr()), ctypes.c_void_p(workspace.data_ptr()),
@@ -182,11 +178,11 @@ class FPNNeck(nn.Module):
         self.lateral_convs = nn.ModuleList([conv(c, 1) for c in in_channels])
         self.fpn_convs = nn.ModuleList([conv(256, 3) for _ in in_channels])
         self.merged = None              # the last forward's merged laterals M_l: [n, 256, H_l, W_l] fp16 views of the workspace
-        self._pack = None               # fp16 weight image at a fixed address per device
-        self._pack_key = None
+        # the fp16 weight image and the backward's (flipped / transposed), each at a fixed address per device, keyed on the weights' versions
+        self._image = dense.WeightImage('fpn_pack', 'FPNNeck.forward under a capture with weights that are not packed: run one forward '
+                                        '(or pack()) before the capture')
+        self._image_bwd = dense.WeightImage('fpn_pack_bwd', 'FPNNeck backward under a capture with weights that are not packed')
         self._workspaces = {}           # (device index, n, planes) -> fp16 workspace at a fixed address
-        self._pack_bwd = None           # the backward's fp16 weight image (flipped / transposed), same version key
-        self._pack_bwd_key = None
         self._bwd_workspaces = {}       # (device index, n, planes, input gradients) -> byte workspace of the backward
 
     # ---- weights
@@ -196,8 +192,8 @@ class FPNNeck(nn.Module):
     def _biases(self):
         return [m.conv.bias for m in self.lateral_convs], [m.conv.bias for m in self.fpn_convs]
 
-    def pack(self, stream=None):
-        """Pack the weights now if they changed since the last pack (forward does this itself).  Returns the fp16 image."""
+    def _checked_weights(self):
+        """(lateral weights, output weights), all fp32 or all fp16 on one device"""
         lat, out = self._weights()
         ws = lat + out
         dev = ws[0].device
@@ -205,18 +201,12 @@ class FPNNeck(nn.Module):
             raise RuntimeError('FPNNeck needs its parameters on the device (no CPU fallback)')
         if any(w.device != dev or w.dtype != ws[0].dtype for w in ws) or ws[0].dtype not in _DTYPES:
             raise TypeError('FPNNeck: the convolution weights must be all fp32 or all fp16, on one device')
-        if dense.in_step_images():      # a training step's scope: derived by the step's own launches, the cache neither read nor filled
-            return dense.derived_image(True, 'fpn_pack', tuple(ws), lambda: self._pack_launch(False, lat, out, None, stream), None, None)
-        key = tuple((w.data_ptr(), w._version) for w in ws)
-        if key == self._pack_key:
-            return self._pack
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('FPNNeck.forward under a capture with weights that are not packed: run one forward (or pack()) before the capture')
-        if self._pack is not None and self._pack.device != dev:
-            self._pack = None
-        self._pack = self._pack_launch(False, lat, out, self._pack, stream)
-        self._pack_key = key
-        return self._pack
+        return lat, out
+
+    def pack(self, stream=None):
+        """Pack the weights now if they changed since the last pack (forward does this itself).  Returns the fp16 image."""
+        lat, out = self._checked_weights()
+        return self._image.get(lat + out, lambda dest: self._pack_launch(False, lat, out, dest, stream))
 
     def _pack_launch(self, bwd, lat, out, dest, stream):
         """sbev_fpn_pack_weights (``bwd``: sbev_fpn_pack_weights_bwd) on checked weights into ``dest`` (None: a fresh tensor)"""
@@ -232,31 +222,14 @@ class FPNNeck(nn.Module):
                 dest = torch.empty(nbytes // 2, dtype=torch.float16, device=dev)
             flat = (ctypes.c_int32 * (3 * len(chw)))(*[v for level in chw for v in level])
             s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if stream is None else stream
-            _lib.check(getattr(_lib.load(), name)(len(chw), flat, _vp_array([w.data_ptr() for w in lat]), _vp_array([w.data_ptr() for w in out]),
+            _lib.check(getattr(_lib.load(), name)(len(chw), flat, dense.ptr_array(lat), dense.ptr_array(out),
                                                   _DTYPES[ws[0].dtype], ctypes.c_void_p(dest.data_ptr()), s), name)
         return dest
 
     def pack_bwd(self, stream=None):
         """The backward's weight image (sbev_fpn_pack_weights_bwd), packed now if the weights changed since its last pack."""
-        lat, out = self._weights()
-        ws = lat + out
-        dev = ws[0].device
-        if dev.type != 'cuda':
-            raise RuntimeError('FPNNeck needs its parameters on the device (no CPU fallback)')
-        if any(w.device != dev or w.dtype != ws[0].dtype for w in ws) or ws[0].dtype not in _DTYPES:
-            raise TypeError('FPNNeck: the convolution weights must be all fp32 or all fp16, on one device')
-        if dense.in_step_images():
-            return dense.derived_image(True, 'fpn_pack_bwd', tuple(ws), lambda: self._pack_launch(True, lat, out, None, stream), None, None)
-        key = tuple((w.data_ptr(), w._version) for w in ws)
-        if key == self._pack_bwd_key:
-            return self._pack_bwd
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('FPNNeck backward under a capture with weights that are not packed')
-        if self._pack_bwd is not None and self._pack_bwd.device != dev:
-            self._pack_bwd = None
-        self._pack_bwd = self._pack_launch(True, lat, out, self._pack_bwd, stream)
-        self._pack_bwd_key = key
-        return self._pack_bwd
+        lat, out = self._checked_weights()
+        return self._image_bwd.get(lat + out, lambda dest: self._pack_launch(True, lat, out, dest, stream))
 
     def _backward_workspace(self, chw, n, input_grads, dev):
         key = (dev.index, n, tuple(chw), bool(input_grads))
@@ -275,9 +248,9 @@ class FPNNeck(nn.Module):
             wpack = self.pack()
             stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             _lib.check(_lib.load().sbev_fpn_forward(
-                L, flat, n, self.num_outs, _vp_array([x.data_ptr() for x in inputs]), _DTYPES[inputs[0].dtype], ctypes.c_void_p(wpack.data_ptr()),
-                _vp_array([b.data_ptr() for b in lat_b]), _vp_array([b.data_ptr() for b in out_b]), ctypes.c_void_p(ws.data_ptr()),
-                _vp_array([o.data_ptr() for o in out]), _DTYPES[out_dtype], stream), 'sbev_fpn_forward')
+                L, flat, n, self.num_outs, dense.ptr_array(inputs), _DTYPES[inputs[0].dtype], ctypes.c_void_p(wpack.data_ptr()),
+                dense.ptr_array(lat_b), dense.ptr_array(out_b), ctypes.c_void_p(ws.data_ptr()),
+                dense.ptr_array(out), _DTYPES[out_dtype], stream), 'sbev_fpn_forward')
 
     def _merged_views(self, ws, chw, n):
         views, at = [], 0
@@ -340,15 +313,7 @@ class FPNNeck(nn.Module):
                 raise TypeError('FPNNeck: out_dtype must be torch.float16 or torch.float32')
             out = [torch.empty((s[0], s[2], s[3], s[1]), dtype=out_dtype, device=dev).permute(0, 3, 1, 2) for s in shapes]
         else:
-            out = list(out)
-            if len(out) != len(shapes):
-                raise ValueError('FPNNeck: out must list %d tensors' % len(shapes))
-            out_dtype = out[0].dtype
-            if out_dtype not in _DTYPES:
-                raise TypeError('FPNNeck: out must be fp16 or fp32')
-            for o, s in zip(out, shapes):
-                if tuple(o.shape) != s or o.dtype != out_dtype or o.device != dev or (o.numel() and not o.permute(0, 2, 3, 1).is_contiguous()):
-                    raise ValueError('FPNNeck: out must be %s tensors of shape %s in channels-last memory on %s' % (out_dtype, s, dev))
+            out, out_dtype = dense.channels_last_out('FPNNeck', out, shapes, dev)
         chw = [(c, x.shape[2], x.shape[3]) for c, x in zip(self.in_channels, inputs)]
         with torch.cuda.device(dev):
             key = (dev.index, n, tuple(chw))

@@ -36,10 +36,6 @@ def _i32(values):
     return (ctypes.c_int32 * max(len(values), 1))(*values)
 
 
-def _vp_array(tensors):
-    return (ctypes.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
-
-
 def _stream(dev):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
@@ -83,7 +79,7 @@ def pack_layers(layers, eps=1e-5, pack=None):
     with torch.cuda.device(dev):
         if pack is None:
             pack = torch.empty(max(at, 16), dtype=torch.uint8, device=dev)
-        cols = [_vp_array([l[j] for l in layers]) for j in range(5)]
+        cols = [dense.ptr_array([l[j] for l in layers]) for j in range(5)]
         _lib.check(_lib.load().sbev_resnet_pack_weights(len(layers), _i32(desc), *cols, float(eps), _DTYPES[ws[0].dtype],
                                                         ctypes.c_void_p(pack.data_ptr()), _stream(dev)), 'sbev_resnet_pack_weights')
     return pack, offs, bias_offs
@@ -111,10 +107,6 @@ REPACK_WORDS = REPACK_HEAD + REPACK_LAYER_WORDS * MAX_LAYERS
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _vp_opt(tensors):
-    return (ctypes.c_void_p * max(len(tensors), 1))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
 def wgrad_slabs(pixels):
@@ -157,7 +149,7 @@ def pack_layers_bwd(layers, eps=1e-5, pack=None):
     with torch.cuda.device(dev):
         if pack is None:
             pack = torch.empty(max(at, 16), dtype=torch.uint8, device=dev)
-        cols = [_vp_array([l[j] for l in layers]) for j in range(3)]
+        cols = [dense.ptr_array([l[j] for l in layers]) for j in range(3)]
         _lib.check(_lib.load().sbev_resnet_pack_weights_bwd(len(layers), _i32(desc), *cols, float(eps), _DTYPES[ws[0].dtype], _ptr(pack),
                                                             _stream(dev)), 'sbev_resnet_pack_weights_bwd')
     return pack, offs
@@ -237,11 +229,11 @@ def backward_raw(net, n, H, W, first_trainable_stage, acts, outs, grad_outs, pac
     with torch.cuda.device(dev):
         _lib.check(_lib.load().sbev_resnet_backward(
             net.depth, _i32(net.stage_blocks), net.num_stages, net.base_channels, int(n), int(H), int(W), len(net.out_indices),
-            _i32(net.out_indices), int(first_trainable_stage), _ptr(acts), _vp_array([to_nhwc(o) for o in outs]),
-            _vp_array([to_nhwc(g) for g in grad_outs]), _DTYPES[grad_outs[0].dtype], _ptr(pack_bwd), _ptr(workspace),
-            _vp_array([c.weight for c, _ in pairs]), _DTYPES[pairs[0][0].weight.dtype], _vp_array([b.weight for _, b in pairs]),
-            _vp_array([b.running_mean for _, b in pairs]), _vp_array([b.running_var for _, b in pairs]), float(net.eps), _vp_opt(grad_w),
-            _vp_opt(grad_gamma), _vp_opt(grad_beta), _stream(dev)), 'sbev_resnet_backward')
+            _i32(net.out_indices), int(first_trainable_stage), _ptr(acts), dense.ptr_array([to_nhwc(o) for o in outs]),
+            dense.ptr_array([to_nhwc(g) for g in grad_outs]), _DTYPES[grad_outs[0].dtype], _ptr(pack_bwd), _ptr(workspace),
+            dense.ptr_array([c.weight for c, _ in pairs]), _DTYPES[pairs[0][0].weight.dtype], dense.ptr_array([b.weight for _, b in pairs]),
+            dense.ptr_array([b.running_mean for _, b in pairs]), dense.ptr_array([b.running_var for _, b in pairs]), float(net.eps), dense.ptr_array(grad_w),
+            dense.ptr_array(grad_gamma), dense.ptr_array(grad_beta), _stream(dev)), 'sbev_resnet_backward')
 
 
 class BackboneFunction(torch.autograd.Function):
@@ -265,7 +257,7 @@ class BackboneFunction(torch.autograd.Function):
             out = [torch.empty((n, h, w, c), dtype=torch.float16, device=dev).permute(0, 3, 1, 2) for c, h, w in p['outs']]
             _lib.check(_lib.load().sbev_resnet_forward_train(
                 net.depth, _i32(net.stage_blocks), net.num_stages, net.base_channels, n, H, W, len(net.out_indices), _i32(net.out_indices), fts,
-                _ptr(x), _DTYPES[x.dtype], _ptr(wpack), _ptr(ws), _ptr(acts), _vp_array(out), _stream(dev)), 'sbev_resnet_forward_train')
+                _ptr(x), _DTYPES[x.dtype], _ptr(wpack), _ptr(ws), _ptr(acts), dense.ptr_array(out), _stream(dev)), 'sbev_resnet_forward_train')
         ctx.net, ctx.acts, ctx.shape, ctx.fts = net, acts, (n, H, W), fts
         ctx.save_for_backward(*out, *params)
         return tuple(out)
@@ -411,11 +403,12 @@ class ResNetBackbone(nn.Module):
                         bn.weight.requires_grad_(norms_learn)
                         bn.bias.requires_grad_(norms_learn)
         self.eval()
-        self._pack = None               # folded weight image at a fixed address per device
-        self._pack_key = None
+        # the folded weight image and the backward's (transposed / flipped w'), each at a fixed address per device, keyed on the versions
+        # of every parameter and buffer (the backward's also on frozen_stages); inside step_images() both come from _step_images()
+        self._image = dense.WeightImage('resnet_pack', 'ResNetBackbone.forward under a capture with weights that are not packed: run one '
+                                        'forward (or pack()) before the capture')
+        self._image_bwd = dense.WeightImage('resnet_pack_bwd', 'ResNetBackbone backward under a capture with weights that are not packed')
         self._workspaces = {}           # (device index, n, H, W, keep) -> (plan, uint8 workspace at a fixed address)
-        self._pack_bwd = None           # the backward's weight image (transposed / flipped w'), same version key
-        self._pack_bwd_key = None
         self._bwd_workspaces = {}       # (device index, n, H, W) -> uint8 workspace of the backward
         self._repack_tables = {}        # repack_key() -> (device table of sbev_resnet_repack, its plan), the latest key only: step_images() scopes
 
@@ -428,10 +421,10 @@ class ResNetBackbone(nn.Module):
                 pairs += block.pairs()
         return pairs
 
-    def pack(self):
-        """Fold and pack now if any parameter or buffer changed since the last pack (forward does this itself).  Returns the image."""
-        pairs = self.conv_bn_pairs()
-        layers = [(c.weight, b.weight, b.bias, b.running_mean, b.running_var) for c, b in pairs]
+    def _checked_layers(self):
+        """(weight, gamma, beta, mean, var) of every convolution in launch order: the weights all fp32 or all fp16, the rest fp32, on
+        one device"""
+        layers = [(c.weight, b.weight, b.bias, b.running_mean, b.running_var) for c, b in self.conv_bn_pairs()]
         ws = [l[0] for l in layers]
         stats = [t for l in layers for t in l[1:]]
         dev = ws[0].device
@@ -441,21 +434,19 @@ class ResNetBackbone(nn.Module):
             raise TypeError('ResNetBackbone: the convolution weights must be all fp32 or all fp16, on one device')
         if any(t.device != dev or t.dtype != torch.float32 for t in stats):
             raise TypeError('ResNetBackbone: the BatchNorm weights and statistics must be fp32, on the weights\' device')
-        if dense.in_step_images():      # a training step's scope: both images by the step's own single launch, the caches untouched
-            return self._step_images(layers)[0]
-        key = tuple((t.data_ptr(), t._version) for l in layers for t in l)
-        if key == self._pack_key:
-            return self._pack
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('ResNetBackbone.forward under a capture with weights that are not packed: run one forward (or pack()) before '
-                               'the capture')
-        if any(not t.is_contiguous() for l in layers for t in l):
-            raise ValueError('ResNetBackbone: parameters and buffers must be contiguous')
-        if self._pack is not None and self._pack.device != dev:
-            self._pack = None
-        self._pack = pack_layers(layers, self.eps, self._pack)[0]
-        self._pack_key = key
-        return self._pack
+        return layers
+
+    def pack(self):
+        """Fold and pack now if any parameter or buffer changed since the last pack (forward does this itself).  Returns the image.
+        Inside step_images(): the scope's, both images by the step's own single launch."""
+        layers = self._checked_layers()
+
+        def make(dest):
+            if any(not t.is_contiguous() for l in layers for t in l):
+                raise ValueError('ResNetBackbone: parameters and buffers must be contiguous')
+            return pack_layers(layers, self.eps, dest)[0]
+
+        return self._image.get([t for l in layers for t in l], make, in_step=lambda: self._step_images(layers)[0])
 
     def _trainable_conv_index(self, first_trainable_stage):
         """convolution numbers (launch order, 0 the stem) of the stages from first_trainable_stage on"""
@@ -471,27 +462,24 @@ class ResNetBackbone(nn.Module):
     def pack_bwd(self):
         """The backward's weight image (sbev_resnet_pack_weights_bwd), packed now if a parameter or a statistic changed since its last
         pack.  Returns the image."""
-        pairs = self.conv_bn_pairs()
-        layers = [(c.weight, b.weight, b.bias, b.running_mean, b.running_var) for c, b in pairs]
-        dev = layers[0][0].device
-        if dense.in_step_images():
+        layers = [(c.weight, b.weight, b.bias, b.running_mean, b.running_var) for c, b in self.conv_bn_pairs()]
+
+        def make(dest):
+            self.pack()           # its checks of devices, dtypes and contiguity hold for this image too
+            bp = self.backward_plan(1, 32, 32)
+            order = sorted((l['pack_offset'], i) for i, l in enumerate(bp['layers']) if l['pack_offset'] >= 0)
+            todo = [(layers[i - 1][0], layers[i - 1][1], layers[i - 1][4]) for _, i in order]          # launch i is convolution i - 1
+            if dest is not None and dest.numel() < bp['pack_bytes']:
+                dest = None
+            image, offs = pack_layers_bwd(todo, self.eps, dest)
+            assert offs == [o for o, _ in order]
+            return image
+
+        def in_step():
             self.pack()           # its checks; the same scope entry
             return self._step_images(layers)[1]
-        key = (self.frozen_stages,) + tuple((t.data_ptr(), t._version) for l in layers for t in l)
-        if key == self._pack_bwd_key:
-            return self._pack_bwd
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('ResNetBackbone backward under a capture with weights that are not packed')
-        self.pack()           # its checks of devices, dtypes and contiguity hold for this image too
-        bp = self.backward_plan(1, 32, 32)
-        order = sorted((l['pack_offset'], i) for i, l in enumerate(bp['layers']) if l['pack_offset'] >= 0)
-        todo = [(layers[i - 1][0], layers[i - 1][1], layers[i - 1][4]) for _, i in order]          # launch i is convolution i - 1
-        if self._pack_bwd is not None and (self._pack_bwd.device != dev or self._pack_bwd.numel() < bp['pack_bytes']):
-            self._pack_bwd = None
-        self._pack_bwd, offs = pack_layers_bwd(todo, self.eps, self._pack_bwd)
-        assert offs == [o for o, _ in order]
-        self._pack_bwd_key = key
-        return self._pack_bwd
+
+        return self._image_bwd.get([t for l in layers for t in l], make, extra=(self.frozen_stages,), in_step=in_step)
 
     # ---- the two images inside a training step's scope (dense.step_images): one sbev_resnet_repack launch per step
     def repack_key(self):
@@ -544,7 +532,7 @@ class ResNetBackbone(nn.Module):
                 bwd = torch.empty(p['pack_bwd_bytes'], dtype=torch.uint8, device=dev) if p['pack_bwd_bytes'] else None
             return repack(table, fwd, bwd, self.eps)
 
-        return dense.derived_image(True, 'resnet_repack', tuple(t for l in layers for t in l), make, None, None)
+        return dense.step_image('resnet_repack', tuple(t for l in layers for t in l), make)
 
     def backward_plan(self, n, H, W):
         return backward_plan(self.depth, n, H, W, self.out_indices, self.num_stages, self.base_channels, self.stage_blocks,
@@ -601,17 +589,12 @@ class ResNetBackbone(nn.Module):
             if out is None:
                 out = [torch.empty((n, h, w, c), dtype=torch.float16, device=dev).permute(0, 3, 1, 2) for _, c, h, w in shapes]
             else:
-                out = list(out)
-                if len(out) != len(shapes):
-                    raise ValueError('ResNetBackbone: out must list %d tensors' % len(shapes))
-                for o, s in zip(out, shapes):
-                    if tuple(o.shape) != s or o.dtype != torch.float16 or o.device != dev or (o.numel() and not o.permute(0, 2, 3, 1).is_contiguous()):
-                        raise ValueError('ResNetBackbone: out must be fp16 tensors of shape %s in channels-last memory on %s' % (s, dev))
+                out = dense.channels_last_out('ResNetBackbone', out, shapes, dev, torch.float16)[0]
             blocks = _i32(self.stage_blocks)
             _lib.check(_lib.load().sbev_resnet_forward(
                 self.depth, blocks, self.num_stages, self.base_channels, n, H, W, len(self.out_indices), _i32(self.out_indices),
                 int(keep is not None), ctypes.c_void_p(x.data_ptr()), _DTYPES[x.dtype], ctypes.c_void_p(wpack.data_ptr()),
-                ctypes.c_void_p(ws.data_ptr()), _vp_array(out), _stream(dev)), 'sbev_resnet_forward')
+                ctypes.c_void_p(ws.data_ptr()), dense.ptr_array(out), _stream(dev)), 'sbev_resnet_forward')
         if keep is not None:
             for l in p['layers']:
                 if l['where'] < 0:

@@ -144,7 +144,7 @@ def test_backbone_and_neck_capture_inside_step_images():
             with dense.step_images():
                 outs = run(net, neck)
     torch.cuda.current_stream().wait_stream(side)
-    assert net._pack_key is None and net._pack_bwd_key is None and neck._pack_key is None and neck._pack_bwd_key is None      # caches untouched
+    assert all(holder.key is None for holder in (net._image, net._image_bwd, neck._image, neck._image_bwd))      # caches untouched
     grads = {id(p): p.grad for p in leaves(net, neck)}
     assert all(g is not None for g in grads.values())
 

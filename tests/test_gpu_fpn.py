@@ -135,6 +135,7 @@ def test_weights_move():
     assert max(float(m.abs().max()) for m in M2) < 2 ** 11 and max(float(p.abs().max()) for p in P2) < 2 ** 24
     got = neck(inputs, out_dtype=F32)
     assert not torch.equal(neck.pack(), before)
+    assert neck.pack().data_ptr() == image.data_ptr()             # repacked in place: an already captured forward reads the new image
     assert all(torch.equal(m.cpu().double(), w) for m, w in zip(neck.merged, M2))
     assert all(torch.equal(g.cpu(), p.float()) for g, p in zip(got, P2))
     assert not torch.equal(P2[0], P[0]) and not torch.equal(M2[0], M[0])

@@ -257,11 +257,13 @@ def test_optimizer_step_repacks_both_images():
     _, outs, loss = autograd_run(neck, xs, R, F32, F32, False)
     before = [o.detach().clone() for o in outs]
     images = neck.pack().clone(), neck.pack_bwd().clone()
+    at = neck.pack().data_ptr(), neck.pack_bwd().data_ptr()
     loss.backward()
     opt.step()
     neck.zero_grad(set_to_none=True)
     _, outs, loss = autograd_run(neck, xs, R, F32, F32, False)
     assert not torch.equal(neck.pack(), images[0]) and not torch.equal(neck.pack_bwd(), images[1])
+    assert (neck.pack().data_ptr(), neck.pack_bwd().data_ptr()) == at          # both repacked in place
     assert not any(torch.equal(o, b) for o, b in zip(outs, before))
     loss.backward()
     moved = {k: v.detach().cpu() for k, v in neck.state_dict().items()}

@@ -168,6 +168,7 @@ def test_weights_move():
     moved['layer1.0.bn2.running_var'][3:40] *= 4
     got = run_and_check(moved)
     assert not torch.equal(net.pack(), before) and not torch.equal(got[0], base[0])
+    assert net.pack().data_ptr() == image.data_ptr()          # repacked in place: an already captured forward reads the new image
     # ... a convolution weight written in place ...
     net.layer2[0].conv3.weight.mul_(0.5)
     moved['layer2.0.conv3.weight'] *= 0.5

@@ -522,12 +522,14 @@ def test_no_grad_equals_the_inference_module_and_an_optimizer_step_repacks():
     opt = FusedAdamW([p for p in mod.parameters() if p.requires_grad], lr=1e-2)
     with torch.enable_grad():
         loss_of(mod(x), gouts).backward()
-    keys = (mod._pack_key, mod._pack_bwd_key)
+    keys = (mod._image.key, mod._image_bwd.key)
     before = mod.pack_bwd().clone()
+    at = mod.pack().data_ptr(), mod.pack_bwd().data_ptr()
     opt.step()
     with torch.enable_grad():
         o = mod(x)
-    assert mod._pack_key != keys[0] and mod._pack_bwd_key != keys[1] and not torch.equal(mod.pack_bwd(), before)
+    assert mod._image.key != keys[0] and mod._image_bwd.key != keys[1] and not torch.equal(mod.pack_bwd(), before)
+    assert (mod.pack().data_ptr(), mod.pack_bwd().data_ptr()) == at          # both repacked in place
     assert torch.equal(o[0], outs[0]) and not torch.equal(o[1], outs[1])          # stage 1 is frozen, stage 2 moved
     # the next forward and backward see the new weights: a fresh module on the stepped parameters agrees bit for bit
     fresh, _ = make_net(1)

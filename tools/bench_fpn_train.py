@@ -174,8 +174,8 @@ def kernel_trace(n):
             for r in csv.DictReader(f):
                 rows.append(dict(name=re.sub(r'\(anonymous namespace\)::', '', r.get('Name', ''))[:120], calls=int(r.get('Calls', 0)),
                                  average_us=round(float(r.get('AverageNs', 0)) / 1e3, 2), total_us=round(float(r.get('TotalDurationNs', 0)) / 1e3, 1)))
-    ours = [r for r in rows if 'fpn_' in r['name']]
-    rest = [r for r in rows if 'fpn_' not in r['name']]
+    ours = [r for r in rows if 'fpn_' in r['name'] or 'grad_scale_' in r['name']]      # grad_scale.hip: the scale's two kernels, shared with the backbone
+    rest = [r for r in rows if r not in ours]
     k = STEPS_UNDER_PROFILER
     return dict(steps=k, input_grads=True, fpn_neck_kernels=sorted(ours, key=lambda r: -r['total_us']),
                 torch_kernels=sorted(rest, key=lambda r: -r['total_us'])[:14],
